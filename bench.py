@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- eMagLS filter-design throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one complete filter-set design (both ears, all channels) of BASELINE.json config 3:
 getEMagLsFilters, em32 (32 mics, r = 4.2 cm), N = 4, complex SH, 2702 HRIR directions, 512 taps,
@@ -22,6 +22,10 @@ smaller batch object), with a barrier + device synchronisation on both sides of 
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the sequential sweep);
 `cpu_baseline` times the NumPy oracle on this host on the same workload (full 512 bins).
+
+`--dump-outputs DIR` writes the filters of the timed region's K designs (every rank's, after the gather) to DIR/wL.npy and
+DIR/wR.npy, [design][tap][channel][re, im] float64; beyond 64 MB a fixed seeded sample of the designs that holds the last one.
+The inputs depend only on the arguments (seeded HRIRs), so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -36,13 +40,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# Hardware queues: the runtime multiplexes the streams of the process onto GPU_MAX_HW_QUEUES queues (default 4) and work of two
-# streams that share a queue executes in order.  Four batches in flight with two lane groups each: 8 streams (+ the partial
-# batches' 4) -> 16 queues, set before the runtime initialises and inherited by the ranks `--gpus N` spawns.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-# (measured, profiles/r03_*: more hardware queues than the runtime's default 4 -- GPU_MAX_HW_QUEUES=8 / 16 / 24 -- change nothing
-# up to 16 and cost 12-25 % at 24; forking a batch's stages before the sweep onto side streams (--fork 4) costs 13-20 % with
-# four batches in flight: the forks compete with the other batches' kernels and with the resident sweep for the same CUs)
+# Hardware queues: the bench leaves the runtime's number of hardware queues as the environment sets it; the streams of the
+# process share those queues.  (Measured, profiles/r03_*: raising the queue count above the runtime's default changes nothing;
+# forking a batch's stages before the sweep onto side streams (--fork 4) costs 13-20 % with four batches in flight: the forks
+# compete with the other batches' kernels and with the resident sweep for the same CUs.)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 SLOTS, BSZ = 4, 32     # resident batches per GPU x designs per batch (a launch of the register-resident sweep covers 32 designs, four per XCD: sweep_reg.hip)
@@ -100,6 +101,32 @@ def schedule(n_designs, bsz=BSZ):
     chunks of bsz, the rest last -- exactly n_designs, never a design more."""
     full, tail = divmod(int(n_designs), bsz)
     return [bsz] * full + ([tail] if tail else [])
+
+
+DUMP_BUDGET = 64 * 10 ** 6   # bytes --dump-outputs writes at most
+
+
+def dump_sample(n_designs, bytes_per_design, budget=DUMP_BUDGET, seed=0):
+    """Designs of the timed region whose filters --dump-outputs writes (sorted): all of them when they fit into `budget`, otherwise
+    a fixed seeded sample that always holds the last one."""
+    m = max(1, int(budget) // int(bytes_per_design))
+    if n_designs <= m:
+        return np.arange(n_designs)
+    pick = np.random.default_rng(seed).choice(n_designs - 1, m - 1, replace=False)
+    return np.sort(np.append(pick, n_designs - 1))
+
+
+def dump_outputs(dst, filters):
+    """--dump-outputs: the filters the timed region computed, as the caller of emagls_jobs_run receives them, per ear
+    [design][tap][channel][re, im] in float64 (dst/wL.npy, dst/wR.npy; a seeded sample of the designs beyond DUMP_BUDGET).
+    `filters` is the region's output [design][ear][channel][tap][re, im].  Returns the indices of the designs written."""
+    import torch
+    idx = dump_sample(filters.shape[0], filters[0].numel() * 8)
+    sel = filters[torch.as_tensor(idx, device=filters.device)].cpu().numpy()
+    os.makedirs(dst, exist_ok=True)
+    for e, name in enumerate(("wL", "wR")):
+        np.save(os.path.join(dst, name + ".npy"), np.ascontiguousarray(sel[:, e].transpose(0, 2, 1, 3), dtype=np.float64))
+    return idx
 
 
 # --------------------------------------------------------------------------------------------
@@ -265,6 +292,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sh-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the config 4 / config 5 / one-shot secondary figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write the filters it computed to DIR/wL.npy and DIR/wR.npy (float64, at most 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or not 1 <= args.batch <= 32 or args.slots < 1:
         raise SystemExit("bench.py: invalid arguments")
@@ -429,6 +458,9 @@ def main():
     chunk_times = [(nd_arr[i], ms_arr[i]) for i in range(min(cnt.value, cap)) if nd_arr[i] in sizes_timed]
     big = max((n for n, _ in chunk_times), default=0)
     batch_sweep_ms = [t for n, t in chunk_times if n == big]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # (rank 0 holds every rank's filters after the gather, ranks in order)
+        dumped = dump_outputs(args.dump_outputs, torch.cat(gathered) if gathered is not None else out)
 
     if rank == 0:
         D, Cc = inputs[4].shape[1], info.num_channels
@@ -576,6 +608,9 @@ def main():
             "single_design_latency_ms": round(single_ms, 4),
             "stages_ms": {k: round(v, 4) for k, v in stages},
         }
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "files": ["wL.npy", "wR.npy"], "designs_written": len(dumped),
+                                   "designs_timed": world * K, "layout": "[design][tap][channel][re, im] float64"}
         if gather_ms is not None:
             res["gather_ms"] = round(gather_ms, 4)
             res["gather_note"] = ("rank 0's wall time of the one collective on the data path (the filters of all ranks, %d bytes per rank, "

@@ -286,7 +286,7 @@ struct emagls_plan {
     bool alone = false;           // the plan of a one-shot call (the device to itself, like a plan with forked stages)
     hipStream_t hh_stream = nullptr;   // the stream of the stages that run next to the sweep
     hipStream_t sync_stream = nullptr;  // stream whose completion means this plan's results are ready
-    // fork/join inside one design: independent branches run on side streams (captured into the same graph)
+    // fork/join inside one design: independent branches run on side streams (such a plan runs eagerly: forks_streams)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};   // taken from the pool when a multi-stream execute first needs them (need_sides)
     bool owns_stream = true;      // false: `stream` belongs to the job slot that created the plan (one stream for all plans of a chunk)
     void need_sides(int n) { for (int i = 0; i < n - 1 && i < 3; ++i) if (!side[i]) side[i] = StreamPool::get().take(); }
@@ -2060,6 +2060,11 @@ void run_pipeline(emagls_plan& p) {
 }
 
 void plan_pre_stage(emagls_plan& p);
+// Graphs are captured from ONE stream only.  A capture whose stages fork onto side streams yields a graph with parallel branches,
+// and hipGraphLaunch of such graphs faults inside the HIP 7.0 runtime bundled with torch (hip::Graph::UpdateStreams): in long
+// sessions (StreamPool above), and on the first replay of a lone job chunk's forked lane batch when the process has two hardware
+// queues.  Forked stages therefore run eagerly on their streams; everything on one stream keeps its graphs.
+static bool forks_streams(const emagls_plan& p) { return p.nstreams >= 2; }
 template <typename F> void capture_into(hipStream_t st, hipGraph_t* g, hipGraphExec_t* ge, F&& body) {
     HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     try {
@@ -2094,7 +2099,7 @@ void plan_execute(emagls_plan& p) {
         if (!p.pre_exec) p.defer_hh = (p.nstreams >= 2 || p.alone) && array_kind(d.kind) && plan_defers_hh_route(p);
         p.pre_phase = p.defer_hh ? 1 : 0;
         try {
-            if (!p.pre_exec && p.eager_runs >= 1) capture_into(p.stream, &p.pre_graph, &p.pre_exec, [&] { plan_pre_stage(p); });
+            if (!p.pre_exec && p.eager_runs >= 1 && !forks_streams(p)) capture_into(p.stream, &p.pre_graph, &p.pre_exec, [&] { plan_pre_stage(p); });
             if (p.pre_exec) HIP_CHECK(hipGraphLaunch(p.pre_exec, p.stream)); else plan_pre_stage(p);
         } catch (...) { p.pre_phase = 0; throw; }
         p.pre_phase = 0;
@@ -2129,7 +2134,7 @@ void plan_execute(emagls_plan& p) {
         return;
     }
     p.geo_run_version = p.atf_side_version;
-    if (p.prof_level == 0 && p.use_graph) {
+    if (p.prof_level == 0 && p.use_graph && !forks_streams(p)) {
         // first execute runs eagerly (one-time function attributes, lazy module load), the second is captured
         if (!p.graph_exec && p.eager_runs >= 1) {
             HIP_CHECK(hipStreamBeginCapture(p.stream, hipStreamCaptureModeThreadLocal));
@@ -2266,7 +2271,8 @@ void batch_lanes_part(emagls_batch& b, int part, int first, int count, hipStream
 // next to each other overlap their latency-bound kernels (measured at --steps 20: the 16-lane sequence 8.6 ms).
 int batch_group_first(const emagls_batch& b, int g) { const int n = (int)b.plans.size(), h = (n + b.groups - 1) / b.groups; return std::min(n, g * h); }
 void batch_execute_lanes(emagls_batch& b) {
-    const bool replay = b.use_graph && b.eager_runs >= 1;
+    // (one lane group with more than one stream forks its stages: never captured, see forks_streams)
+    const bool replay = b.use_graph && b.eager_runs >= 1 && !(b.groups == 1 && b.nstreams > 1);
     const int n = (int)b.plans.size();
     const int ng = b.groups;
     for (int g = 1; g < ng; ++g) if (!b.side[g - 1]) b.side[g - 1] = emagls::pool_stream_take();
@@ -2768,7 +2774,7 @@ void batch_execute(emagls_batch& b) {
         batch_execute_lanes(b);
         return;
     }
-    const bool replay = b.use_graph && b.eager_runs >= 1;
+    const bool replay = b.use_graph && b.eager_runs >= 1 && std::none_of(b.plans.begin(), b.plans.end(), [](const emagls_plan* p) { return forks_streams(*p); });
     if (replay && !b.plans[0]->pre_exec) {
         for (auto* p : b.plans) capture_into(p->stream, &p->pre_graph, &p->pre_exec, [&] { plan_pre_stage(*p); });
         if (!b.plans[0]->sweep_persist) capture_into(b.stream, &b.graph, &b.graph_exec, [&] { batch_sweep_stage(b); });
@@ -3839,7 +3845,7 @@ int emagls_batch_set_streams(emagls_batch* b, int nstreams) {
         if (nstreams < 1 || nstreams > 4) throw Error(EMAGLS_ERR_ARG, "nstreams must be 1..4");
         HIP_CHECK(hipStreamSynchronize(b->stream));
         for (int i = 0; i < nstreams - 1; ++i) if (!b->side[i]) b->side[i] = emagls::pool_stream_take();
-        if (nstreams != b->nstreams) drop_batch_graphs(*b);   // (the next execute runs eagerly, the one after it captures the forks)
+        if (nstreams != b->nstreams) drop_batch_graphs(*b);   // (forked stages run eagerly; back on one stream, the execute after the next captures)
         b->nstreams = nstreams;
     });
 }

@@ -309,7 +309,8 @@ int emagls_plan_get_info(emagls_plan* plan, emagls_plan_info* info);
  * dominant kernel by (the form is decided per launch, by the number of designs in it) */
 int emagls_plan_sweep_form_in_batch(emagls_plan* plan, int designs, int* form);
 /* 1..4: number of HIP streams one design may use (independent branches fork onto side streams; default 3,
- * best for the latency of ONE design; use 1 when several plans are in flight). Drops the captured graph. */
+ * best for the latency of ONE design; use 1 when several plans are in flight). Drops the captured graph; with more than one
+ * stream the plan runs eagerly (a graph is only captured from one stream). */
 int emagls_plan_set_streams(emagls_plan* plan, int nstreams);
 /* profiling: level 0 none, 1 = HIP events between stages, 2 = additionally around every sweep launch */
 int emagls_plan_set_profiling(emagls_plan* plan, int level);
@@ -458,8 +459,8 @@ int emagls_batch_set_stream(emagls_batch* batch, void* hip_stream);
 int emagls_batch_set_side_stream(emagls_batch* batch, void* hip_stream);
 int emagls_batch_sweep_time(emagls_batch* batch, double* ms);
 /* Lane mode: 1..4 HIP streams for the stages before the sweep (default 1).  With more than one the independent branches of the
- * design fork onto side streams and the captured graph carries the forks: [HRIR-grid SH matrix, Gram matrix, Cholesky factor,
- * Householder-route factors] | [array model, order terms, G_k of every bin] | [HRIR prologue, least-squares right-hand sides]
+ * design fork onto side streams and the batch runs eagerly (a graph is only captured from one stream): [HRIR-grid SH matrix,
+ * Gram matrix, Cholesky factor, Householder-route factors] | [array model, order terms, G_k of every bin] | [HRIR prologue, least-squares right-hand sides]
  * | [Gram-route factors].  Shortens the path to the batch's sweep from the sum of the kernels to its longest branch (what a
  * short run, a pipeline filling from empty, is bound by); with many batches in flight it only adds queue contention.  A batch with
  * forked stages is taken to have the device to itself: what its sweep does not need -- the Cholesky factor and the orthonormal

@@ -3,7 +3,7 @@
 THIS IS TEST INFRASTRUCTURE.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg
 may import it; the product (emagls_amd/) never does and fails loudly without its HIP library.
 
-Every function cites the reference file:line it restates (paths relative to /root/reference).
+Every function cites the reference file:line it restates (paths relative to the reference repository's root).
 The reference is MATLAB and cannot run in this container or on the GPU box (no matlab/octave), so
 the oracle is pinned against the reference's own shipped golden filter sets
 (resources/HRIR_L2702_512samples_32channels_sh4_*.mat -> tests/golden/ref_fixtures.npz) through
@@ -13,7 +13,7 @@ UNPINNED: the KATs pin the SH convention, ACN order, Condon-Shortley phase, the 
 relation, getShFreqDomainConjugate's semantics, window end points, delay bookkeeping and (to
 discrimination level, ~5 %) the rigid-sphere modal coefficients -- not the tap values.
 
-Third-party arithmetic that is NOT under /root/reference (empty git submodules, .gitmodules:1-9,
+Third-party arithmetic that is NOT in the reference repository (empty git submodules, .gitmodules:1-9,
 pinned SHAs unrecoverable) is restated from the published algorithms:
   * getSH                     polarch/Spherical-Harmonic-Transform  (orthonormal SH, ACN, [azi zen])
   * sphModalCoeffs            polarch/Array-Response-Simulator      (b_n(kr), rigid sphere)

@@ -2,6 +2,7 @@
 import importlib.util
 import os
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +25,34 @@ def test_schedule_processes_exactly_the_requested_designs():
         s = sch(k)
         assert sum(s) == k and all(x == 32 for x in s[:-1]) and 1 <= s[-1] <= 32
     assert sch(20) == [20] and sch(128) == [32] * 4 and sch(5, 8) == [5] and sch(20, 8) == [8, 8, 4] and sch(20, 16) == [16, 4]
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: every design of the timed region while they fit into 64 MB, beyond that the same seeded sample on every run,
+    always with the last design."""
+    b = _bench()
+    per = 2 * 25 * 512 * 2 * 8          # config 3: both ears, 25 channels, 512 taps, complex float64
+    assert list(b.dump_sample(20, per)) == list(range(20)) and list(b.dump_sample(128, per)) == list(range(128))
+    for k in (157, 1000, 100000):
+        s = b.dump_sample(k, per)
+        assert len(s) * per <= b.DUMP_BUDGET and len(s) == b.DUMP_BUDGET // per
+        assert s[-1] == k - 1 and len(set(s.tolist())) == len(s) and (s[1:] > s[:-1]).all() and s[0] >= 0
+        assert list(s) == list(b.dump_sample(k, per))
+    assert list(b.dump_sample(3, 10 ** 9)) == [2]      # a design larger than the budget: the last one still goes out
+
+
+def test_dump_outputs_writes_the_callers_layout(tmp_path):
+    """The files hold the filters as getEMagLsFilters returns them: [tap][channel] complex per design and ear, as (re, im) float64."""
+    import torch
+    b = _bench()
+    g = torch.arange(3 * 2 * 4 * 5 * 2, dtype=torch.float64).reshape(3, 2, 4, 5, 2)   # [design][ear][channel][tap][re, im]
+    assert list(b.dump_outputs(str(tmp_path / "d"), g)) == [0, 1, 2]
+    for e, name in enumerate(("wL", "wR")):
+        w = np.load(tmp_path / "d" / (name + ".npy"))
+        assert w.dtype == np.float64 and w.shape == (3, 5, 4, 2)
+        for k in range(3):
+            c = w[k, ..., 0] + 1j * w[k, ..., 1]
+            assert np.array_equal(c, (g[k, e, ..., 0].numpy() + 1j * g[k, e, ..., 1].numpy()).T)
 
 
 def test_gpus_flag_spawns_fresh_ranks(tmp_path):

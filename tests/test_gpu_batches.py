@@ -109,8 +109,8 @@ def test_lane_batch_matches_single_designs(grids, thin):
         else:
             for (wL, wR), (fL, fR) in zip(res, first):
                 assert np.array_equal(wL, fL) and np.array_equal(wR, fR), it
-    # the stages before the sweep forked onto four streams (emagls_batch_set_streams; what a job list of one chunk runs): eager,
-    # captured with the forks, replayed -- the same filters as on one stream to rounding (since round 5 the forked form takes its
+    # the stages before the sweep forked onto four streams (emagls_batch_set_streams; what a job list of one chunk runs): three
+    # eager executes (forked stages are never captured) -- the same filters as on one stream to rounding (since round 5 the forked form takes its
     # Gram-route Jacobi bins one by one and the lane groups in warm-started runs of two: not bitwise the same), and bitwise the same
     # from execute to execute
     b.set_streams(4)
