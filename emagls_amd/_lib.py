@@ -12,6 +12,7 @@ OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NUMERIC = 0, 1, 2, 3, 4
 BASIS = {"real": 0, "complex": 1}
 KIND_LS, KIND_MAGLS, KIND_EMAGLS, KIND_EMAGLS2, KIND_FROM_ATF, KIND_EMA_CH, KIND_MAGLS_2D, KIND_EMA_SH = range(8)
 RADIAL = {"tikhonov": 0, "softlimit": 1, "full": 2, "none": 3}
+LAYOUT = {"sh": 0, "ch": 1}
 
 c_dp = C.POINTER(C.c_double)
 c_i64 = C.c_int64
@@ -88,6 +89,12 @@ SYMBOLS = {
                                                  C.c_void_p, C.c_void_p]),
     "emagls_binaural_decode_device": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    "emagls_rotate_yaw": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p]),
+    "emagls_binaural_decode_render": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64, C.c_int,
+                                                C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "emagls_binaural_decode_render_device": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64,
+                                                       C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
     "emagls_get_magls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_double, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_get_emagls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_double,

@@ -363,13 +363,46 @@ def getEMagLsFiltersFromAtf(hL, hR, hrirGridAziZenRad, atfIrs, atfGridAziZenRad,
     return wL, wR
 
 
+def _layout(domain):
+    key = str(domain).lower()
+    if key not in L.LAYOUT:
+        raise ValueError("rotation domain must be 'sh' or 'ch'")
+    return L.LAYOUT[key]
+
+
+def rotateYaw(sig, angleRad, shDefinition="real", domain="sh"):
+    """Yaw rotation of an SH (ACN, (N+1)^2 channels) or CH ([C_0, C_-1, C_1, ..., C_-N, C_N], 2N+1 channels) signal
+    [numSamples x numChannels]: the yaw part of the rotateHOA_N3D call in dependencies/binauralDecode.m:27-31, own
+    specification.  The signal of a plane wave from azimuth a, conj(getSH(N, [a zen], shDefinition))
+    or conj(getCH(N, a, shDefinition)), becomes the one of the plane wave from a + angleRad.  angleRad: a scalar, or one angle
+    per sample.  The result is complex when the signal is or the basis is 'complex', real otherwise."""
+    b, cb = _basis(shDefinition)
+    lay = _layout(domain)
+    in_c = np.iscomplexobj(sig)
+    x = np.asfortranarray(np.asarray(sig, dtype=np.complex128 if in_c else np.float64))
+    if x.ndim != 2:
+        raise ValueError("sig must be [numSamples x numChannels]")
+    n, Cc = x.shape
+    yaw = np.ascontiguousarray(np.asarray(angleRad, dtype=np.float64).reshape(-1))
+    if yaw.size not in (1, n):
+        raise ValueError("angleRad must be a scalar or have one angle per sample (%d), not %d" % (n, yaw.size))
+    out, po = _out(n, Cc, in_c or cb)
+    L.check(L.load().emagls_rotate_yaw(x.ctypes.data_as(C.c_void_p), 1 if in_c else 0, n, Cc, lay, b,
+                                       yaw.ctypes.data_as(C.c_void_p), yaw.size, po))
+    return out
+
+
 def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingFilterFs, compensateDelay=False,
-                   signal=None, signalFs=None, horRotAngleRad=None):
-    """dependencies/binauralDecode.m:1-2.  Real or complex (complex-SH) signals and filters; the output is real: the reference
-    forces it and warns with the absolute sum of the discarded imaginary part (:59-64), and so does this function."""
+                   signal=None, signalFs=None, horRotAngleRad=None, *, shDefinition="real", rotationDomain="sh"):
+    """dependencies/binauralDecode.m:1-64 without the resampling.  Real or complex (complex-SH) signals and filters; the output
+    is real: the reference forces it and warns with the absolute sum of the discarded imaginary part (:59-64), and so does this
+    function.  horRotAngleRad: a scalar (the reference's fixed yaw) or one angle per input sample (a head-tracker trajectory),
+    applied as rotateYaw(sig, horRotAngleRad, shDefinition, rotationDomain); shDefinition is the basis of `sig` ('real' is the
+    one rotateHOA_N3D assumes).  signal: the dry source the rendered impulse response is convolved with (:44-48); only its
+    first column is used, and the output then has as many samples as it."""
     import warnings
-    if decodingFilterFs != inFs or signal is not None or (horRotAngleRad not in (None, 0)):
-        raise NotImplementedError("resampling, rotation and the extra convolution are outside the accelerated path")
+    if decodingFilterFs != inFs or (signalFs is not None and signalFs != inFs):
+        raise NotImplementedError("resampling (decodingFilterFs or signalFs != inFs) is outside the accelerated path")
     in_c = np.iscomplexobj(sig)
     w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
 
@@ -384,14 +417,39 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
     ln = wL.shape[0]
     if wL.shape != wR.shape or wL.shape[1] != Cc:
         raise ValueError("filters must be [len x numChannels] matching the signal's channel count")
+    yaw = None
+    if horRotAngleRad is not None:
+        yaw = np.ascontiguousarray(np.asarray(horRotAngleRad, dtype=np.float64).reshape(-1))
+        if yaw.size == 1 and yaw[0] == 0:      # :28: `horRotAngleRad ~= 0`
+            yaw = None
+        elif yaw.size not in (1, n):
+            raise ValueError("horRotAngleRad must be a scalar or have one angle per input sample (%d), not %d" % (n, yaw.size))
+    src = None
+    if signal is not None:
+        s = np.asarray(signal)
+        if s.size:
+            if np.iscomplexobj(s):
+                raise ValueError("signal must be real")
+            src = np.ascontiguousarray((s.reshape(s.shape[0], -1)[:, 0] if s.ndim > 1 else s.reshape(-1)).astype(np.float64))
     skip = (ln // 2 - 1) if (compensateDelay and ln // 2 > 0) else 0
-    out, po = _out(max(n - skip, 0), 2, False)
-    if not (in_c or w_c):
-        L.check(L.load().emagls_binaural_decode(ps, n, Cc, pwL, pwR, ln, 1 if compensateDelay else 0, po))
-        return out
-    im = (C.c_double * 2)(0.0, 0.0)
-    L.check(L.load().emagls_binaural_decode_complex(ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln,
-                                                    1 if compensateDelay else 0, po, im))
+    if yaw is None and src is None:       # today's entry points, bit for bit
+        out, po = _out(max(n - skip, 0), 2, False)
+        if not (in_c or w_c):
+            L.check(L.load().emagls_binaural_decode(ps, n, Cc, pwL, pwR, ln, 1 if compensateDelay else 0, po))
+            return out
+        im = (C.c_double * 2)(0.0, 0.0)
+        L.check(L.load().emagls_binaural_decode_complex(ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln,
+                                                        1 if compensateDelay else 0, po, im))
+    else:
+        b, cb = _basis(shDefinition)
+        lay = _layout(rotationDomain)
+        nout = src.size if src is not None else n
+        out, po = _out(max(nout - skip, 0), 2, False)
+        im = (C.c_double * 2)(0.0, 0.0)
+        L.check(L.load().emagls_binaural_decode_render(
+            ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln, 1 if compensateDelay else 0, lay, b,
+            yaw.ctypes.data_as(C.c_void_p) if yaw is not None else None, yaw.size if yaw is not None else 0,
+            src.ctypes.data_as(C.c_void_p) if src is not None else None, src.size if src is not None else 0, po, im))
     # binauralDecode.m:59-63: `if ~isreal(binauralOut)` -- whenever the accumulated result is a complex array, which it is as
     # soon as a signal or a filter is complex (MATLAB only drops an all-zero imaginary part at the end of an arithmetic
     # operation; a sum that happens to be exactly real is the one case in which the reference stays silent, and so do we)

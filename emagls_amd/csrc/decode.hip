@@ -576,7 +576,12 @@ __global__ void __launch_bounds__(1024) abs_sum_kernel(const double* __restrict_
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
-// hipFFT plans and work buffers of the last decode shape, kept across calls (creating three plans and six buffers costs
+void launch_abs_sum_cols(const double* x, int64_t n, int64_t skip, int ncols, double* out, hipStream_t st) {
+    abs_sum_kernel<<<ncols, 1024, 0, st>>>(x, n, skip, out);
+    KERNEL_CHECK();
+}
+
+// hipFFT plans and work buffers of the last two decode shapes, kept across calls (creating three plans and six buffers costs
 // more than rendering a short signal); released by emagls_cache_clear().  One render at a time per process.
 namespace {
 struct DecodeWork {
@@ -625,12 +630,27 @@ struct DecodeWork {
     }
 };
 std::mutex g_decode_mu;
-DecodeWork g_decode;
+// two shapes are kept: a render with a source signal alternates between the decode of the SH signal and the one-channel
+// convolution of its response (emagls_binaural_decode_render), and re-planning hipFFT at every call would cost more than both
+DecodeWork g_decode[2];
+int g_decode_last = 0;
+DecodeWork& decode_work(int C, int64_t nblocks, int Nf) {   // (g_decode_mu held)
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    for (int i = 0; i < 2; ++i) {
+        DecodeWork& w = g_decode[i];
+        if (w.C == C && w.nblocks == nblocks && w.Nf == Nf && w.device == dev) { g_decode_last = i; return w; }
+    }
+    g_decode_last ^= 1;   // the least recently used slot
+    g_decode[g_decode_last].ensure(C, nblocks, Nf);
+    return g_decode[g_decode_last];
+}
 }  // namespace
 
 void decode_cache_clear() {
     std::lock_guard<std::mutex> lk(g_decode_mu);
-    g_decode.release();
+    g_decode[0].release();
+    g_decode[1].release();
 }
 
 // EMAGLS_DECODE_FUSED=0: always the hipFFT passes
@@ -655,8 +675,7 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
         const int64_t B = Nf - (len - 1);
         const int64_t nblocks = ceil_div(n, B);
         std::lock_guard<std::mutex> lk(g_decode_mu);
-        DecodeWork& w = g_decode;
-        w.ensure(C, 0, Nf);
+        DecodeWork& w = decode_work(C, 0, Nf);
         const char* e_rr = getenv("EMAGLS_DECODE_REGFFT");   // (read at every call: a test switches forms inside one process)
         const bool use_rr = !(e_rr && e_rr[0] == '0');
         const char* e_wave = getenv("EMAGLS_DECODE_WAVE");
@@ -747,8 +766,7 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
     const int64_t nblocks = ceil_div(n, B);
     const int Pf = Nf / 2 + 1;
     std::lock_guard<std::mutex> lk(g_decode_mu);
-    DecodeWork& w = g_decode;
-    w.ensure(C, nblocks, Nf);
+    DecodeWork& w = decode_work(C, nblocks, Nf);
     fft_check(hipfftSetStream(w.pf, st), "set stream");
     fft_check(hipfftSetStream(w.pw, st), "set stream");
     fft_check(hipfftSetStream(w.pi, st), "set stream");

@@ -196,7 +196,18 @@ bool decode_wave_form(int64_t len);
 void binaural_decode_complex(const void* sig, bool sig_cplx, int64_t n, int C, const void* wL, const void* wR, bool w_cplx, int64_t len,
                              double* sig2, double* w2L, double* w2R, double* out, double* imag_abs, double* d_tmp, hipStream_t st,
                              int64_t imag_skip = 0 /* samples left out of the imaginary-part sums (the compensateDelay cut) */);
+// (with imag_abs: d_tmp [2n + 2] holds the discarded imaginary part [2][n] on return, then its two sums)
 void decode_cache_clear();
+// out[e] = sum(|x[e*n + i]|, i = skip .. n-1) for the ncols columns of x [ncols][n]
+void launch_abs_sum_cols(const double* x, int64_t n, int64_t skip, int ncols, double* out, hipStream_t st);
+
+// ---- rotate.hip
+// N of a layout (0: SH, (N+1)^2 channels in ACN order; 1: CH, 2N+1 channels [C_0, C_-1, C_1, ..., C_-N, C_N]); -1 if C fits not
+int rotate_order(int layout, int64_t C);
+// yaw rotation of in [C][n] (real, or interleaved complex): out [C][n], complex when in_cplx || cplx_basis.  yaw: device, one
+// angle (per_sample false) or n angles.  transpose: the filter-side form of a fixed angle (w Rot instead of x Rot^T)
+void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
+                       bool transpose, void* out, hipStream_t st);
 void filter_channels_by_order(const double* sig, int64_t n_in, int64_t n, int C, const double* ir /* [nOrd][len] */, int nOrd, int64_t len,
                               int64_t skip, double* out /* [C][n-skip] */, hipStream_t st);
 

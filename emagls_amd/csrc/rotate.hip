@@ -1,0 +1,92 @@
+// Yaw rotation of SH / CH signals (the yaw part of rotateHOA_N3D, called by dependencies/binauralDecode.m:27-31).  OWN
+// SPECIFICATION: rotating by theta turns the sound field counter-clockwise about z, so the signal of a
+// plane wave from azimuth a, conj(getSH(N, [a zen])) / conj(getCH(N, a)), becomes the one of the plane wave from a + theta.
+// Only the channels (n, m) and (n, -m) mix:
+//   real basis      out(n, m) = cos(m t) x(n, m) - sin(m t) x(n, -m),  out(n, -m) = cos(m t) x(n, -m) + sin(m t) x(n, m)   (m > 0)
+//   complex basis   out(n, m) = exp(-i m t) x(n, m)                                                                    (any m)
+// whatever the normalisation.  theta is reduced modulo 2 pi in FP64 before m theta is formed.
+#include "kernels.hpp"
+
+namespace emagls {
+
+int rotate_order(int layout, int64_t C) {
+    if (C < 1) return -1;
+    if (layout == 0) {   // SH, ACN: (N + 1)^2 channels
+        int64_t N = (int64_t)std::llround(std::sqrt((double)C)) - 1;
+        return (N >= 0 && (N + 1) * (N + 1) == C) ? (int)N : -1;
+    }
+    if (layout == 1) return (C % 2) ? (int)((C - 1) / 2) : -1;   // CH: [C_0, C_-1, C_1, ..., C_-N, C_N], 2N + 1 channels
+    return -1;
+}
+
+namespace {
+
+template <bool C_> struct Val;
+template <> struct Val<false> { using T = double; };
+template <> struct Val<true> { using T = cplx; };
+
+__device__ __forceinline__ cplx widen(double v) { return mk(v, 0.0); }
+__device__ __forceinline__ cplx widen(cplx v) { return v; }
+
+// one thread = one sample (row) of every channel; columns are channel planes of n values, so a wave's loads are contiguous
+// IC / OC: input / output complex (OC = IC || complex basis).  sgn = -1 applies the transpose of the real-basis rotation
+// (the decoding filters of a fixed angle: sum_i w_i * (x Rot^T)_i = sum_j (w Rot)_j * x_j); the complex basis is diagonal.
+template <bool IC, bool OC>
+__global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict__ in_, int64_t n, int N, int layout, int cb,
+                                                         const double* __restrict__ yaw, int per_sample, double sgn, void* __restrict__ out_) {
+    using TI = typename Val<IC>::T;
+    using TO = typename Val<OC>::T;
+    const TI* __restrict__ in = reinterpret_cast<const TI*>(in_);
+    TO* __restrict__ out = reinterpret_cast<TO*>(out_);
+    const int nl = layout == 0 ? N + 1 : 1;   // channels of one |m|: SH orders n = m..N, CH one pair
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double th = fmod(yaw[per_sample ? t : 0], 2.0 * kPi);
+        for (int j = 0; j < nl; ++j) {          // m = 0: unchanged
+            const int64_t k = layout == 0 ? (int64_t)j * j + j : 0;
+            if constexpr (OC) out[k * n + t] = widen(in[k * n + t]);
+            else out[k * n + t] = in[k * n + t];
+        }
+        for (int m = 1; m <= N; ++m) {
+            double s, c;
+            sincos((double)m * th, &s, &c);
+            for (int nn = layout == 0 ? m : 0; nn < (layout == 0 ? N + 1 : 1); ++nn) {
+                const int64_t p = layout == 0 ? (int64_t)nn * nn + nn + m : 2 * m;        // (n, m)
+                const int64_t q = layout == 0 ? (int64_t)nn * nn + nn - m : 2 * m - 1;    // (n, -m)
+                const TI a = in[p * n + t], b = in[q * n + t];
+                if constexpr (OC) {
+                    const cplx ac = widen(a), bc = widen(b);
+                    if (cb) {   // exp(-i m t) and exp(+i m t)
+                        out[p * n + t] = mk(c * ac.x + s * ac.y, c * ac.y - s * ac.x);
+                        out[q * n + t] = mk(c * bc.x - s * bc.y, c * bc.y + s * bc.x);
+                    } else {
+                        const double ss = sgn * s;
+                        out[p * n + t] = mk(c * ac.x - ss * bc.x, c * ac.y - ss * bc.y);
+                        out[q * n + t] = mk(c * bc.x + ss * ac.x, c * bc.y + ss * ac.y);
+                    }
+                } else {
+                    const double ss = sgn * s;
+                    out[p * n + t] = c * a - ss * b;
+                    out[q * n + t] = c * b + ss * a;
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
+                       bool transpose, void* out, hipStream_t st) {
+    if (n <= 0) return;
+    const int N = rotate_order(layout, C);
+    if (N < 0) throw Error(1, "rotate_yaw: the channel count fits neither (N+1)^2 (SH) nor 2N+1 (CH)");
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 256), 65536);
+    const double sgn = (transpose && !cplx_basis) ? -1.0 : 1.0;
+    const int cb = cplx_basis ? 1 : 0, ps = per_sample ? 1 : 0;
+    if (in_cplx) rotate_yaw_kernel<true, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out);
+    else if (cplx_basis) rotate_yaw_kernel<false, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out);
+    else rotate_yaw_kernel<false, false><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out);
+    KERNEL_CHECK();
+}
+
+}  // namespace emagls

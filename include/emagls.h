@@ -173,6 +173,41 @@ int emagls_binaural_decode_complex(const void* in, int in_is_complex, int64_t ns
 int emagls_binaural_decode_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL, const void* d_wR,
                                   int filters_are_complex, int64_t len, double* d_out, double* imag_abs_sum, void* stream);
 
+/* Channel layouts of the yaw rotation: SH in ACN order, (N+1)^2 channels; CH in getCH's order [C_0, C_-1, C_1, ..., C_-N, C_N],
+ * 2N+1 channels (dependencies/getCH.m:17-28). */
+#define EMAGLS_LAYOUT_SH 0
+#define EMAGLS_LAYOUT_CH 1
+
+/* Yaw rotation of an SH or CH signal (the yaw part of the rotateHOA_N3D call in dependencies/binauralDecode.m:27-31).  OWN
+ * SPECIFICATION: rotating by yaw turns the sound field counter-clockwise about z, seen from above, so the
+ * signal of a plane wave from azimuth a -- conj(getSH(N, [a zen], basis)) or conj(getCH(N, a, basis)) -- becomes the one of the
+ * plane wave from a + yaw.  Only (n, m) and (n, -m) mix, through cos(m yaw) and sin(m yaw); the normalisation does not matter.
+ * yaw is reduced modulo 2 pi in FP64 before m yaw is formed.
+ * in [nsamp x nch] real or interleaved complex as flagged; yaw [n_yaw], n_yaw = 1 (one angle) or nsamp (one angle per sample);
+ * out [nsamp x nch], interleaved complex when in_is_complex or basis == EMAGLS_BASIS_COMPLEX, real otherwise.  A channel count
+ * that does not fit the layout is EMAGLS_ERR_ARG. */
+int emagls_rotate_yaw(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int layout, int basis, const double* yaw,
+                      int64_t n_yaw, void* out);
+
+/* dependencies/binauralDecode.m:1-64 without the resampling: emagls_binaural_decode_complex's arguments, plus
+ *  - the yaw rotation of the input (layout, basis, yaw [n_yaw]; n_yaw = 0: none, 1: one fixed angle, applied to the decoding
+ *    filters, nsamp: one angle per input sample, applied to the signal), and
+ *  - the source-signal convolution of :44-48 (signal [n_signal], the first column of the reference's `signal`; NULL or
+ *    n_signal = 0: none): out(:, e) = fftfilt(ear_e, signal), ear_e being the rendered impulse response of ear e.
+ * out [nout x 2] real, nout = (n_signal > 0 ? n_signal : nsamp) - (compensate_delay ? len/2 - 1 : 0): the cut uses the decoding
+ * filters' length (:53-57).  imag_abs_sum (optional, [2]) as for emagls_binaural_decode_complex, over the returned samples.
+ * Without rotation and signal this is emagls_binaural_decode_complex (emagls_binaural_decode when nothing is complex). */
+int emagls_binaural_decode_render(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                  int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
+                                  int64_t n_yaw, const double* signal, int64_t n_signal, double* out, double* imag_abs_sum);
+
+/* emagls_binaural_decode_render on buffers that are already in HBM, on the model of emagls_binaural_decode_device: d_yaw and
+ * d_signal are device arrays too; d_out [nout x 2], nout = n_signal > 0 ? n_signal : nsamp, without the delay cut. */
+int emagls_binaural_decode_render_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                         const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis,
+                                         const double* d_yaw, int64_t n_yaw, const double* d_signal, int64_t n_signal, double* d_out,
+                                         double* imag_abs_sum, void* stream);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

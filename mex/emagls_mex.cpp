@@ -69,7 +69,8 @@ void at_exit() { emagls_cache_clear(); }
 // emagls_mex('fromatf', hL, hR, hrirGridAziZen, atfIrs, atfGridAziZen, fs, filterLen, fTrans)
 // emagls_mex('emainch' | 'emainsh', hL, hR, azi, zen, micRadius, micAzi, order, fs, len, shDefinition)
 // emagls_mex('magls_dc' | 'emagls_dc' | 'emagls2_dc', <the arguments of 'magls' / 'emagls' / 'emagls2'>, applyDiffusenessConst)
-// emagls_mex('decode',  in, wL, wR, compensateDelay)            real or complex in / filters; [out, imagAbsSum] = ...
+// emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain])   real or complex in / filters; [out, imagAbsSum] = ...
+// emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
 // emagls_mex('sets', kind, hL, hR, azi, zen, micRadius, micAzi, micZen, order, fs, len, shDefinition)   3-D hL / hR: a loop over HRIR sets in one call
 // emagls_mex('fromatfsets', hL, hR, hrirGridAziZen, atfIrs, atfGridAziZen, fs, filterLen, fTrans)      3-D hL / hR: the subjects of one ATF set
 // emagls_mex('jobs', jobs[, batchSize, inFlight, shareGeometry, devices])   struct array of independent designs (any kinds, radii, HRIR sets): W = {wL, wR} per job
@@ -91,6 +92,56 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     char cmd[16] = {0};
     mxGetString(prhs[0], cmd, sizeof cmd);
     const std::string c(cmd);
+    if (c == "decode" && nrhs > 5) {
+        // dependencies/binauralDecode.m:27-31,44-48 on the GPU: yaw ([] / 0: none, a scalar, or one angle per input sample), the
+        // dry source signal ([]: none; its first column), the basis of `in` and the rotation domain ('sh' / 'ch')
+        const mwSize n = mxGetM(prhs[1]), ch = mxGetN(prhs[1]), len = mxGetM(prhs[2]);
+        const int comp = mxIsLogicalScalarTrue(prhs[4]) || (mxIsDouble(prhs[4]) && !mxIsEmpty(prhs[4]) && mxGetScalar(prhs[4]) != 0);
+        const bool ic = mxIsComplex(prhs[1]), wc = mxIsComplex(prhs[2]);
+        if (wc != (bool)mxIsComplex(prhs[3])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
+        const mxArray* ayaw = prhs[5];
+        const mwSize nyaw_in = mxIsEmpty(ayaw) ? 0 : mxGetNumberOfElements(ayaw);
+        const double* yaw = nyaw_in ? dbl(ayaw, "horRotAngleRad") : nullptr;
+        const mwSize nyaw = (nyaw_in == 1 && yaw[0] == 0.0) ? 0 : nyaw_in;        // :28: horRotAngleRad ~= 0
+        const mxArray* asig = nrhs > 6 ? prhs[6] : nullptr;
+        const mwSize nsig = (asig && !mxIsEmpty(asig)) ? mxGetM(asig) : 0;
+        const double* sig = nsig ? dbl(asig, "signal") : nullptr;                // (column-major: the first column leads)
+        const int basis = basis_of(nrhs > 7 ? prhs[7] : nullptr);
+        int layout = EMAGLS_LAYOUT_SH;
+        if (nrhs > 8 && !mxIsEmpty(prhs[8])) {
+            char buf[8] = {0};
+            mxGetString(prhs[8], buf, sizeof buf);
+            if (!std::strcmp(buf, "ch")) layout = EMAGLS_LAYOUT_CH;
+            else if (std::strcmp(buf, "sh")) mexErrMsgIdAndTxt("eMagLS:arg", "rotation domain must be 'sh' or 'ch'");
+        }
+        const mwSize rows = nsig ? nsig : n, skip = comp ? (len / 2 > 0 ? len / 2 - 1 : 0) : 0;
+        plhs[0] = mxCreateDoubleMatrix(rows > skip ? rows - skip : 0, 2, mxREAL);
+        double imag_sum[2] = {0, 0};
+        const int rc = emagls_binaural_decode_render(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout,
+                                                     basis, yaw, nyaw, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
+        if (rc) fail(rc);
+        if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
+        return;
+    }
+    if (c == "rotate") {
+        // out = emagls_mex('rotate', in, yawRad[, shDefinition, domain]): the yaw rotation alone (emagls_rotate_yaw)
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "rotate needs (in, yawRad[, shDefinition, domain])");
+        const mwSize n = mxGetM(prhs[1]), ch = mxGetN(prhs[1]);
+        const bool ic = mxIsComplex(prhs[1]);
+        const int basis = basis_of(nrhs > 3 ? prhs[3] : nullptr);
+        int layout = EMAGLS_LAYOUT_SH;
+        if (nrhs > 4 && !mxIsEmpty(prhs[4])) {
+            char buf[8] = {0};
+            mxGetString(prhs[4], buf, sizeof buf);
+            if (!std::strcmp(buf, "ch")) layout = EMAGLS_LAYOUT_CH;
+            else if (std::strcmp(buf, "sh")) mexErrMsgIdAndTxt("eMagLS:arg", "rotation domain must be 'sh' or 'ch'");
+        }
+        plhs[0] = mxCreateDoubleMatrix(n, ch, (ic || basis == EMAGLS_BASIS_COMPLEX) ? mxCOMPLEX : mxREAL);
+        const int rc = emagls_rotate_yaw(in_ptr(prhs[1]), ic, n, ch, layout, basis, dbl(prhs[2], "yawRad"), mxGetNumberOfElements(prhs[2]),
+                                         out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
     if (c == "decode") {
         if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "decode needs (in, wL, wR[, compensateDelay])");
         const mwSize n = mxGetM(prhs[1]), ch = mxGetN(prhs[1]), len = mxGetM(prhs[2]);
