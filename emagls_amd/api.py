@@ -26,6 +26,7 @@ emagls_*_with_basis entry points -- exactly what the MEX wrappers do with a MATL
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -392,14 +393,70 @@ def rotateYaw(sig, angleRad, shDefinition="real", domain="sh"):
     return out
 
 
+def _angles(a, n, name):
+    """None, or a contiguous float64 vector of one angle or one angle per sample (n)."""
+    if a is None:
+        return None
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+    if v.size not in (1, n):
+        raise ValueError("%s must be a scalar or have one angle per sample (%d), not %d" % (name, n, v.size))
+    return v
+
+
+def _sh_order(Cc):
+    N = int(round(math.sqrt(Cc))) - 1
+    if N < 0 or (N + 1) ** 2 != Cc:
+        raise ValueError("the three-axis rotation needs (N+1)^2 SH channels in ACN order, not %d" % Cc)
+    return N
+
+
+def _vp(v):
+    return (v.ctypes.data_as(C.c_void_p), v.size) if v is not None else (None, 0)
+
+
+def rotateSH(sig, yawRad=0.0, pitchRad=0.0, rollRad=0.0, shDefinition="real"):
+    """Three-axis rotation of an SH signal [numSamples x (N+1)^2] (ACN), N <= 15: rotateHOA_N3D(in, yaw, pitch, roll) of
+    dependencies/binauralDecode.m:27-31, own specification.  R = Rz(yaw) Ry(pitch) Rx(roll) with getSH's
+    axes (x front, y left, z up); the signal of a plane wave from u, conj(getSH(N, u, shDefinition)), becomes the one from R u.
+    Each angle: a scalar or one angle per sample.  With pitch and roll all zero this is rotateYaw, bit for bit.  The result is
+    complex when the signal is or the basis is 'complex'."""
+    b, cb = _basis(shDefinition)
+    in_c = np.iscomplexobj(sig)
+    x = np.asfortranarray(np.asarray(sig, dtype=np.complex128 if in_c else np.float64))
+    if x.ndim != 2:
+        raise ValueError("sig must be [numSamples x numChannels]")
+    n, Cc = x.shape
+    _sh_order(Cc)
+    yaw, pitch, roll = _angles(yawRad, n, "yawRad"), _angles(pitchRad, n, "pitchRad"), _angles(rollRad, n, "rollRad")
+    out, po = _out(n, Cc, in_c or cb)
+    L.check(L.load().emagls_rotate_sh(x.ctypes.data_as(C.c_void_p), 1 if in_c else 0, n, Cc, b, *_vp(yaw), *_vp(pitch), *_vp(roll), po))
+    return out
+
+
+def shRotationMatrix(order, yawRad, pitchRad, rollRad, shDefinition="real"):
+    """The matrix M [(N+1)^2 x (N+1)^2] of rotateSH: rotateSH(x, yaw, pitch, roll) == x @ M.T.  Block-diagonal by order, orthogonal
+    (real basis) or unitary (complex basis); the closed form of an SH rotation matrix from angles (getSHrotMtx takes the 3 x 3
+    matrix instead).  N <= 15."""
+    b, cb = _basis(shDefinition)
+    if int(order) != order or order < 0:
+        raise ValueError("order must be a non-negative integer")
+    Cc = (int(order) + 1) ** 2
+    out, po = _out(Cc, Cc, cb)
+    L.check(L.load().emagls_sh_rotation_matrix(int(order), b, float(yawRad), float(pitchRad), float(rollRad), po))
+    return out
+
+
 def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingFilterFs, compensateDelay=False,
-                   signal=None, signalFs=None, horRotAngleRad=None, *, shDefinition="real", rotationDomain="sh"):
+                   signal=None, signalFs=None, horRotAngleRad=None, *, shDefinition="real", rotationDomain="sh", pitchRad=None,
+                   rollRad=None):
     """dependencies/binauralDecode.m:1-64 without the resampling.  Real or complex (complex-SH) signals and filters; the output
     is real: the reference forces it and warns with the absolute sum of the discarded imaginary part (:59-64), and so does this
     function.  horRotAngleRad: a scalar (the reference's fixed yaw) or one angle per input sample (a head-tracker trajectory),
     applied as rotateYaw(sig, horRotAngleRad, shDefinition, rotationDomain); shDefinition is the basis of `sig` ('real' is the
     one rotateHOA_N3D assumes).  signal: the dry source the rendered impulse response is convolved with (:44-48); only its
-    first column is used, and the output then has as many samples as it."""
+    first column is used, and the output then has as many samples as it.  pitchRad, rollRad: the other two angles of
+    rotateHOA_N3D (rotateSH's rotation with yaw = horRotAngleRad), each a scalar or one angle per input sample; SH signals only.
+    With both None, or all zero, the call is the yaw-only one, bit for bit."""
     import warnings
     if decodingFilterFs != inFs or (signalFs is not None and signalFs != inFs):
         raise NotImplementedError("resampling (decodingFilterFs or signalFs != inFs) is outside the accelerated path")
@@ -431,8 +488,24 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
             if np.iscomplexobj(s):
                 raise ValueError("signal must be real")
             src = np.ascontiguousarray((s.reshape(s.shape[0], -1)[:, 0] if s.ndim > 1 else s.reshape(-1)).astype(np.float64))
+    ypr = None
+    if pitchRad is not None or rollRad is not None:
+        pitch, roll = _angles(pitchRad, n, "pitchRad"), _angles(rollRad, n, "rollRad")
+        if any(a is not None and np.any(a != 0) for a in (pitch, roll)):
+            if _layout(rotationDomain) != L.LAYOUT["sh"]:
+                raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
+            _sh_order(Cc)
+            ypr = (pitch, roll)
     skip = (ln // 2 - 1) if (compensateDelay and ln // 2 > 0) else 0
-    if yaw is None and src is None:       # today's entry points, bit for bit
+    if ypr is not None:
+        b, cb = _basis(shDefinition)
+        nout = src.size if src is not None else n
+        out, po = _out(max(nout - skip, 0), 2, False)
+        im = (C.c_double * 2)(0.0, 0.0)
+        L.check(L.load().emagls_binaural_decode_render_ypr(
+            ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln, 1 if compensateDelay else 0, L.LAYOUT["sh"], b, *_vp(yaw),
+            *_vp(ypr[0]), *_vp(ypr[1]), *_vp(src), po, im))
+    elif yaw is None and src is None:       # today's entry points, bit for bit
         out, po = _out(max(n - skip, 0), 2, False)
         if not (in_c or w_c):
             L.check(L.load().emagls_binaural_decode(ps, n, Cc, pwL, pwR, ln, 1 if compensateDelay else 0, po))

@@ -3336,6 +3336,7 @@ int emagls_cache_clear(void) {
                 if (!g_cache[i].busy) g_cache.erase(g_cache.begin() + i);
         }
         decode_cache_clear();
+        rotate3_cache_clear();
         {
             std::lock_guard<std::mutex> lk(g_decode_scratch.mu);
             g_decode_scratch.release();
@@ -4073,9 +4074,12 @@ static void check_render_args(int64_t nsamp, int64_t nch, int layout, int basis,
 
 // Device-resident body of the two render entry points; the caller holds g_render_scratch.mu.  d_out [nout][2], nout = nsig ? nsig :
 // nsamp, no delay cut; `cut` only moves the start of the imaginary-part sums.
-static void render_core(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len,
-                        int layout, bool cb, const double* d_yaw, int64_t n_yaw, const double* d_sig, int64_t nsig, int64_t cut,
-                        double* d_out, double* imag_abs, hipStream_t st) {
+}  // extern "C"
+std::mutex& emagls::render_scratch_mutex() { return g_render_scratch.mu; }
+void* emagls::render_scratch(RenderBuf which, size_t bytes) { return g_render_scratch.get((int)which, bytes); }
+void emagls::render_core(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len,
+                         int layout, bool cb, const double* d_yaw, int64_t n_yaw, const double* d_sig, int64_t nsig, int64_t cut,
+                         double* d_out, double* imag_abs, hipStream_t st) {
     RenderScratch& r = g_render_scratch;
     if (n_yaw == 1) {           // fixed angle: rotate the filters, sum_i w_i * (x Rot^T)_i = sum_j (w Rot)_j * x_j
         const bool wc2 = w_c || cb;
@@ -4115,6 +4119,7 @@ static void render_core(const void* d_in, bool in_c, int64_t nsamp, int nch, con
     HIP_CHECK(hipStreamSynchronize(st));
 }
 
+extern "C" {
 int emagls_rotate_yaw(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int layout, int basis, const double* yaw,
                       int64_t n_yaw, void* out) {
     return guarded([&] {

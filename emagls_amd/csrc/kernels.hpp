@@ -208,6 +208,25 @@ int rotate_order(int layout, int64_t C);
 // angle (per_sample false) or n angles.  transpose: the filter-side form of a fixed angle (w Rot instead of x Rot^T)
 void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
                        bool transpose, void* out, hipStream_t st);
+// ---- rotate3.hip
+int rotate3_max_order();   // 15: the largest SH order of the three-axis rotation
+// rotation R = Rz(yaw) Ry(pitch) Rx(roll) of the SH (ACN) signal in [C][n] (real, or interleaved complex): out [C][n], complex
+// when in_cplx || cplx_basis.  Each angle: device pointer, null (0), one value (*_ps false) or n values.  transpose: the
+// filter-side form of a fixed rotation (w M instead of x M^T).  C = (N+1)^2 with N <= 15, else Error
+void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch,
+                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st);
+// M [(N+1)^2 x (N+1)^2] column-major, out_row = in_row M^T; the same device code as launch_rotate3
+void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st);
+void rotate3_cache_clear();
+
+// ---- capi.hip: the body of emagls_binaural_decode_render(_device), for the entry points that rotate first (rotate3_api.hip)
+enum RenderBuf { RENDER_ROT_SIG, RENDER_ROT_WL, RENDER_ROT_WR };
+std::mutex& render_scratch_mutex();
+void* render_scratch(RenderBuf which, size_t bytes);   // (render_scratch_mutex() held)
+void render_core(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len,
+                 int layout, bool cb, const double* d_yaw, int64_t n_yaw, const double* d_sig, int64_t nsig, int64_t cut,
+                 double* d_out, double* imag_abs, hipStream_t st);   // (render_scratch_mutex() held)
+
 void filter_channels_by_order(const double* sig, int64_t n_in, int64_t n, int C, const double* ir /* [nOrd][len] */, int nOrd, int64_t len,
                               int64_t skip, double* out /* [C][n-skip] */, hipStream_t st);
 

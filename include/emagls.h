@@ -208,6 +208,38 @@ int emagls_binaural_decode_render_device(const void* d_in, int in_is_complex, in
                                          const double* d_yaw, int64_t n_yaw, const double* d_signal, int64_t n_signal, double* d_out,
                                          double* imag_abs_sum, void* stream);
 
+/* Three-axis rotation of an SH signal (rotateHOA_N3D(in, yaw, pitch, roll), called by dependencies/binauralDecode.m:27-31).  OWN
+ * SPECIFICATION: axes of getSH (x front, y left, z up); R = Rz(yaw) Ry(pitch) Rx(roll), each factor a
+ * right-handed active rotation about a fixed axis; the signal of a plane wave from u, conj(getSH(N, u, basis)), becomes the one
+ * of the plane wave from R u.  yaw = pi/2 moves the front to the left, pitch = pi/2 the front to the floor, roll = pi/2 the left
+ * to the top; with pitch = roll = 0 this is emagls_rotate_yaw.  SH orders 0 to 15 ((N+1)^2 channels, ACN); a higher order is
+ * EMAGLS_ERR_UNSUPPORTED.
+ * M [(N+1)^2 x (N+1)^2] column-major (interleaved complex for the complex basis): the rotation is out_row = in_row M^T; M is
+ * block-diagonal by order, orthogonal (real basis) or unitary (complex basis). */
+int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, double roll, void* out);
+
+/* in [nsamp x nch] real or interleaved complex as flagged; each of yaw [n_yaw], pitch [n_pitch], roll [n_roll] has 0 (absent: 0),
+ * 1 (one angle) or nsamp values (one per sample); out [nsamp x nch], interleaved complex when in_is_complex or basis ==
+ * EMAGLS_BASIS_COMPLEX.  When every pitch and roll value is 0 this is emagls_rotate_yaw, bit for bit. */
+int emagls_rotate_sh(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int basis, const double* yaw, int64_t n_yaw,
+                     const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll, void* out);
+
+/* emagls_binaural_decode_render with the three-axis rotation: pitch [n_pitch] and roll [n_roll] as yaw (0, 1 or nsamp values
+ * each).  Every count <= 1: a fixed rotation, applied to the decoding filters; otherwise a per-sample pass over the signal.  A CH
+ * layout with a nonzero pitch or roll is EMAGLS_ERR_ARG.  When every pitch and roll value is 0 this is
+ * emagls_binaural_decode_render, bit for bit. */
+int emagls_binaural_decode_render_ypr(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                      int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
+                                      int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll,
+                                      const double* signal, int64_t n_signal, double* out, double* imag_abs_sum);
+
+/* emagls_binaural_decode_render_ypr on device buffers (angles and signal included), as emagls_binaural_decode_render_device;
+ * n_pitch == n_roll == 0 is emagls_binaural_decode_render_device. */
+int emagls_binaural_decode_render_ypr_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                             const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
+                                             int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
+                                             const double* d_signal, int64_t n_signal, double* d_out, double* imag_abs_sum, void* stream);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

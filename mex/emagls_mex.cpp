@@ -69,8 +69,10 @@ void at_exit() { emagls_cache_clear(); }
 // emagls_mex('fromatf', hL, hR, hrirGridAziZen, atfIrs, atfGridAziZen, fs, filterLen, fTrans)
 // emagls_mex('emainch' | 'emainsh', hL, hR, azi, zen, micRadius, micAzi, order, fs, len, shDefinition)
 // emagls_mex('magls_dc' | 'emagls_dc' | 'emagls2_dc', <the arguments of 'magls' / 'emagls' / 'emagls2'>, applyDiffusenessConst)
-// emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain])   real or complex in / filters; [out, imagAbsSum] = ...
+// emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain, pitchRad, rollRad])   real or complex in / filters; [out, imagAbsSum] = ...
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
+// emagls_mex('rotate3', in, yawRad, pitchRad, rollRad[, shDefinition])   three-axis rotation of an SH signal (orders 0-15)
+// emagls_mex('shrotmtx', order, yawRad, pitchRad, rollRad[, shDefinition])   its matrix M: out = in * M.'
 // emagls_mex('sets', kind, hL, hR, azi, zen, micRadius, micAzi, micZen, order, fs, len, shDefinition)   3-D hL / hR: a loop over HRIR sets in one call
 // emagls_mex('fromatfsets', hL, hR, hrirGridAziZen, atfIrs, atfGridAziZen, fs, filterLen, fTrans)      3-D hL / hR: the subjects of one ATF set
 // emagls_mex('jobs', jobs[, batchSize, inFlight, shareGeometry, devices])   struct array of independent designs (any kinds, radii, HRIR sets): W = {wL, wR} per job
@@ -117,8 +119,16 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize rows = nsig ? nsig : n, skip = comp ? (len / 2 > 0 ? len / 2 - 1 : 0) : 0;
         plhs[0] = mxCreateDoubleMatrix(rows > skip ? rows - skip : 0, 2, mxREAL);
         double imag_sum[2] = {0, 0};
-        const int rc = emagls_binaural_decode_render(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout,
-                                                     basis, yaw, nyaw, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
+        // pitch (prhs[9]) and roll (prhs[10]): [] or absent: none, a scalar, or one angle per input sample
+        const mwSize npitch = (nrhs > 9 && !mxIsEmpty(prhs[9])) ? mxGetNumberOfElements(prhs[9]) : 0;
+        const mwSize nroll = (nrhs > 10 && !mxIsEmpty(prhs[10])) ? mxGetNumberOfElements(prhs[10]) : 0;
+        const double* pitch = npitch ? dbl(prhs[9], "pitchRad") : nullptr;
+        const double* roll = nroll ? dbl(prhs[10], "rollRad") : nullptr;
+        const int rc = (npitch || nroll)
+            ? emagls_binaural_decode_render_ypr(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout, basis,
+                                                yaw, nyaw, pitch, npitch, roll, nroll, sig, nsig, mxGetDoubles(plhs[0]), imag_sum)
+            : emagls_binaural_decode_render(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout,
+                                            basis, yaw, nyaw, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
         if (rc) fail(rc);
         if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
         return;
@@ -139,6 +149,32 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[0] = mxCreateDoubleMatrix(n, ch, (ic || basis == EMAGLS_BASIS_COMPLEX) ? mxCOMPLEX : mxREAL);
         const int rc = emagls_rotate_yaw(in_ptr(prhs[1]), ic, n, ch, layout, basis, dbl(prhs[2], "yawRad"), mxGetNumberOfElements(prhs[2]),
                                          out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "rotate3") {
+        // out = emagls_mex('rotate3', in, yaw, pitch, roll[, shDefinition]): three-axis rotation of an SH signal (emagls_rotate_sh);
+        // each angle a scalar or one per sample
+        if (nrhs < 5) mexErrMsgIdAndTxt("eMagLS:arg", "rotate3 needs (in, yawRad, pitchRad, rollRad[, shDefinition])");
+        const mwSize n = mxGetM(prhs[1]), ch = mxGetN(prhs[1]);
+        const bool ic = mxIsComplex(prhs[1]);
+        const int basis = basis_of(nrhs > 5 ? prhs[5] : nullptr);
+        plhs[0] = mxCreateDoubleMatrix(n, ch, (ic || basis == EMAGLS_BASIS_COMPLEX) ? mxCOMPLEX : mxREAL);
+        const int rc = emagls_rotate_sh(in_ptr(prhs[1]), ic, n, ch, basis, dbl(prhs[2], "yawRad"), mxGetNumberOfElements(prhs[2]),
+                                        dbl(prhs[3], "pitchRad"), mxGetNumberOfElements(prhs[3]), dbl(prhs[4], "rollRad"),
+                                        mxGetNumberOfElements(prhs[4]), out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "shrotmtx") {
+        // M = emagls_mex('shrotmtx', order, yaw, pitch, roll[, shDefinition]): rotate3's matrix, out_row = in_row * M.'
+        if (nrhs < 5) mexErrMsgIdAndTxt("eMagLS:arg", "shrotmtx needs (order, yawRad, pitchRad, rollRad[, shDefinition])");
+        const int order = (int)mxGetScalar(prhs[1]);
+        const int basis = basis_of(nrhs > 5 ? prhs[5] : nullptr);
+        const mwSize C = order >= 0 ? (mwSize)(order + 1) * (order + 1) : 0;
+        plhs[0] = mxCreateDoubleMatrix(C, C, basis == EMAGLS_BASIS_COMPLEX ? mxCOMPLEX : mxREAL);
+        const int rc = emagls_sh_rotation_matrix(order, basis, mxGetScalar(prhs[2]), mxGetScalar(prhs[3]), mxGetScalar(prhs[4]),
+                                                 out_ptr(plhs[0]));
         if (rc) fail(rc);
         return;
     }
