@@ -497,32 +497,17 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
             _sh_order(Cc)
             ypr = (pitch, roll)
     skip = (ln // 2 - 1) if (compensateDelay and ln // 2 > 0) else 0
-    if ypr is not None:
-        b, cb = _basis(shDefinition)
-        nout = src.size if src is not None else n
-        out, po = _out(max(nout - skip, 0), 2, False)
-        im = (C.c_double * 2)(0.0, 0.0)
-        L.check(L.load().emagls_binaural_decode_render_ypr(
-            ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln, 1 if compensateDelay else 0, L.LAYOUT["sh"], b, *_vp(yaw),
-            *_vp(ypr[0]), *_vp(ypr[1]), *_vp(src), po, im))
-    elif yaw is None and src is None:       # today's entry points, bit for bit
-        out, po = _out(max(n - skip, 0), 2, False)
-        if not (in_c or w_c):
-            L.check(L.load().emagls_binaural_decode(ps, n, Cc, pwL, pwR, ln, 1 if compensateDelay else 0, po))
-            return out
-        im = (C.c_double * 2)(0.0, 0.0)
-        L.check(L.load().emagls_binaural_decode_complex(ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln,
-                                                        1 if compensateDelay else 0, po, im))
-    else:
-        b, cb = _basis(shDefinition)
+    b, lay = L.BASIS["real"], L.LAYOUT["sh"]     # (not looked at without rotation and signal)
+    if ypr is not None or yaw is not None or src is not None:
+        b = _basis(shDefinition)[0]
         lay = _layout(rotationDomain)
-        nout = src.size if src is not None else n
-        out, po = _out(max(nout - skip, 0), 2, False)
-        im = (C.c_double * 2)(0.0, 0.0)
-        L.check(L.load().emagls_binaural_decode_render(
-            ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln, 1 if compensateDelay else 0, lay, b,
-            yaw.ctypes.data_as(C.c_void_p) if yaw is not None else None, yaw.size if yaw is not None else 0,
-            src.ctypes.data_as(C.c_void_p) if src is not None else None, src.size if src is not None else 0, po, im))
+    pitch, roll = ypr or (None, None)
+    nout = src.size if src is not None else n
+    out, po = _out(max(nout - skip, 0), 2, False)
+    im = (C.c_double * 2)(0.0, 0.0)
+    L.check(L.load().emagls_binaural_decode_render_ypr(
+        ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln, 1 if compensateDelay else 0, lay, b, *_vp(yaw), *_vp(pitch),
+        *_vp(roll), *_vp(src), po, im))
     # binauralDecode.m:59-63: `if ~isreal(binauralOut)` -- whenever the accumulated result is a complex array, which it is as
     # soon as a signal or a filter is complex (MATLAB only drops an all-zero imaginary part at the end of an arithmetic
     # operation; a sum that happens to be exactly real is the one case in which the reference stays silent, and so do we)

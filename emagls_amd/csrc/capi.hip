@@ -3248,54 +3248,6 @@ namespace {
 std::atomic<int> g_batch_max{[] { const char* e = getenv("EMAGLS_BATCH_MAX"); return e ? std::max(1, std::min(REG_SWEEP_MAX, atoi(e))) : 8; }()};
 thread_local int g_batch_max_override = 0;   // emagls_design_hrir_sets builds batches of 16 of its own whatever the caller's limit is
 }
-// work planes of the complex device-resident decode, grown on demand and kept (released by emagls_cache_clear)
-namespace {
-struct DecodeScratch {
-    std::mutex mu;
-    int device = -1;
-    size_t cap_sig = 0, cap_w = 0, cap_tmp = 0;
-    double *sig2 = nullptr, *w2L = nullptr, *w2R = nullptr, *tmp = nullptr;
-    void release() {
-        hipFree(sig2); hipFree(w2L); hipFree(w2R); hipFree(tmp);
-        sig2 = w2L = w2R = tmp = nullptr; cap_sig = cap_w = cap_tmp = 0; device = -1;
-    }
-    void ensure(size_t nsig, size_t nw, size_t ntmp) {
-        int dev = 0;
-        HIP_CHECK(hipGetDevice(&dev));
-        if (dev != device) { release(); device = dev; }
-        if (nsig > cap_sig) { hipFree(sig2); sig2 = nullptr; cap_sig = 0; HIP_CHECK(hipMalloc(&sig2, sizeof(double) * nsig)); cap_sig = nsig; }
-        if (nw > cap_w) {
-            hipFree(w2L); hipFree(w2R); w2L = w2R = nullptr; cap_w = 0;
-            HIP_CHECK(hipMalloc(&w2L, sizeof(double) * nw)); HIP_CHECK(hipMalloc(&w2R, sizeof(double) * nw)); cap_w = nw;
-        }
-        if (ntmp > cap_tmp) { hipFree(tmp); tmp = nullptr; cap_tmp = 0; HIP_CHECK(hipMalloc(&tmp, sizeof(double) * ntmp)); cap_tmp = ntmp; }
-    }
-};
-DecodeScratch g_decode_scratch;
-
-// work buffers of the render calls with rotation / source signal (emagls_binaural_decode_render*), grown on demand and kept
-// (released by emagls_cache_clear); one render at a time per process, like the decode plans
-struct RenderScratch {
-    enum { ROT_SIG, ROT_WL, ROT_WR, SIG2, W2L, W2R, TMP, IR, YIM, YAW, NBUF };
-    std::mutex mu;
-    int device = -1;
-    void* p[NBUF] = {};
-    size_t cap[NBUF] = {};
-    void release() {
-        for (int i = 0; i < NBUF; ++i) { hipFree(p[i]); p[i] = nullptr; cap[i] = 0; }
-        device = -1;
-    }
-    template <typename T = void> T* get(int i, size_t bytes) {
-        int dev = 0;
-        HIP_CHECK(hipGetDevice(&dev));
-        if (dev != device) { release(); device = dev; }
-        bytes = std::max<size_t>(bytes, 16);
-        if (bytes > cap[i]) { hipFree(p[i]); p[i] = nullptr; cap[i] = 0; HIP_CHECK(hipMalloc(&p[i], bytes)); cap[i] = bytes; }
-        return reinterpret_cast<T*>(p[i]);
-    }
-};
-RenderScratch g_render_scratch;
-}  // namespace
 
 // =============================================================================================
 extern "C" {
@@ -3335,16 +3287,7 @@ int emagls_cache_clear(void) {
             for (size_t i = g_cache.size(); i-- > 0;)
                 if (!g_cache[i].busy) g_cache.erase(g_cache.begin() + i);
         }
-        decode_cache_clear();
-        rotate3_cache_clear();
-        {
-            std::lock_guard<std::mutex> lk(g_decode_scratch.mu);
-            g_decode_scratch.release();
-        }
-        {
-            std::lock_guard<std::mutex> lk(g_render_scratch.mu);
-            g_render_scratch.release();
-        }
+        decode_family_cache_clear();
         emagls_sets_cache_clear_internal();
         emagls_atfsets_cache_clear_internal();
         emagls_jobs_cache_clear_internal();
@@ -3985,251 +3928,6 @@ int emagls_get_emagls_filters_from_atf(const double* hL, const double* hR, int64
     d.nmics = nmics; d.f_trans = f_trans; d.atf_taps = atf_taps; d.natf = natf;
     if (!atf_irs || !atf_azi || !atf_zen) { g_last_error = "null ATF set"; return EMAGLS_ERR_ARG; }
     return one_shot(d, hL, hR, azi, zen, nullptr, nullptr, atf_irs, atf_azi, atf_zen, wL, wR, mean_dev);
-}
-
-// common body of the two decode entry points
-static int decode_entry(const void* in, bool in_cplx, int64_t nsamp, int64_t nch, const void* wL, const void* wR, bool w_cplx, int64_t len,
-                        int compensate_delay, double* out, double* imag_abs_sum) {
-    return guarded([&] {
-        if (!in || !wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        if (nsamp < 0 || nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
-        if (nsamp == 0) return;
-        const bool any_cplx = in_cplx || w_cplx;
-        const size_t es_in = in_cplx ? sizeof(cplx) : sizeof(double), es_w = w_cplx ? sizeof(cplx) : sizeof(double);
-        void *d_in = nullptr, *d_wL = nullptr, *d_wR = nullptr;
-        double *d_out = nullptr, *d_sig2 = nullptr, *d_w2L = nullptr, *d_w2R = nullptr, *d_tmp = nullptr;
-        hipStream_t st = nullptr;
-        auto cleanup = [&] {
-            hipFree(d_in); hipFree(d_wL); hipFree(d_wR); hipFree(d_out); hipFree(d_sig2); hipFree(d_w2L); hipFree(d_w2R); hipFree(d_tmp);
-            emagls::pool_stream_give(st);
-        };
-        try {
-            st = emagls::pool_stream_take();
-            HIP_CHECK(hipMalloc(&d_in, es_in * nsamp * nch));
-            HIP_CHECK(hipMalloc(&d_wL, es_w * len * nch));
-            HIP_CHECK(hipMalloc(&d_wR, es_w * len * nch));
-            HIP_CHECK(hipMalloc(&d_out, sizeof(double) * nsamp * 2));
-            HIP_CHECK(hipMemcpy(d_in, in, es_in * nsamp * nch, hipMemcpyDefault));
-            HIP_CHECK(hipMemcpy(d_wL, wL, es_w * len * nch, hipMemcpyDefault));
-            HIP_CHECK(hipMemcpy(d_wR, wR, es_w * len * nch, hipMemcpyDefault));
-            if (!any_cplx) {
-                binaural_decode_real((const double*)d_in, nsamp, (int)nch, (const double*)d_wL, (const double*)d_wR, len, d_out, st);
-            } else {
-                HIP_CHECK(hipMalloc(&d_sig2, sizeof(double) * 2 * nsamp * nch));
-                HIP_CHECK(hipMalloc(&d_w2L, sizeof(double) * 2 * len * nch));
-                HIP_CHECK(hipMalloc(&d_w2R, sizeof(double) * 2 * len * nch));
-                if (imag_abs_sum) HIP_CHECK(hipMalloc(&d_tmp, sizeof(double) * (2 * nsamp + 2)));
-                // (the reference sums the discarded imaginary part AFTER binauralOut(del:end,:), binauralDecode.m:53-62)
-                const int64_t cut = (compensate_delay && len / 2 > 0) ? len / 2 - 1 : 0;
-                binaural_decode_complex(d_in, in_cplx, nsamp, (int)nch, d_wL, d_wR, w_cplx, len, d_sig2, d_w2L, d_w2R, d_out,
-                                        imag_abs_sum, d_tmp, st, std::min(cut, nsamp));
-            }
-            if (!compensate_delay) {
-                HIP_CHECK(hipMemcpy(out, d_out, sizeof(double) * nsamp * 2, hipMemcpyDefault));
-            } else {
-                // binauralOut(del:end,:), del = len/2 (1-based)   (binauralDecode.m:53-57)
-                const int64_t del = len / 2;
-                const int64_t skip = del > 0 ? del - 1 : 0;
-                const int64_t nout = nsamp - skip;
-                if (nout > 0) {
-                    HIP_CHECK(hipMemcpy(out, d_out + skip, sizeof(double) * nout, hipMemcpyDefault));
-                    HIP_CHECK(hipMemcpy(out + nout, d_out + nsamp + skip, sizeof(double) * nout, hipMemcpyDefault));
-                }
-            }
-        } catch (...) { cleanup(); throw; }
-        cleanup();
-    });
-}
-
-int emagls_binaural_decode_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL, const void* d_wR,
-                                  int filters_are_complex, int64_t len, double* d_out, double* imag_abs_sum, void* stream) {
-    return guarded([&] {
-        if (!d_in || !d_wL || !d_wR || !d_out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        if (nsamp < 0 || nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
-        if (nsamp == 0) return;
-        hipStream_t st = (hipStream_t)stream;
-        if (!in_is_complex && !filters_are_complex) {
-            binaural_decode_real((const double*)d_in, nsamp, (int)nch, (const double*)d_wL, (const double*)d_wR, len, d_out, st);
-            return;
-        }
-        std::lock_guard<std::mutex> lk(g_decode_scratch.mu);
-        g_decode_scratch.ensure((size_t)2 * nsamp * nch, (size_t)2 * len * nch, imag_abs_sum ? (size_t)(2 * nsamp + 2) : 0);
-        binaural_decode_complex(d_in, in_is_complex != 0, nsamp, (int)nch, d_wL, d_wR, filters_are_complex != 0, len, g_decode_scratch.sig2,
-                                g_decode_scratch.w2L, g_decode_scratch.w2R, d_out, imag_abs_sum, g_decode_scratch.tmp, st, 0);
-    });
-}
-
-// ---- binauralDecode with rotation and source signal (dependencies/binauralDecode.m:27-31,44-48)
-static void check_render_args(int64_t nsamp, int64_t nch, int layout, int basis, int64_t n_yaw, bool yaw_ptr) {
-    if (n_yaw == 0) return;
-    if (!yaw_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer");
-    if (basis != EMAGLS_BASIS_REAL && basis != EMAGLS_BASIS_COMPLEX) throw Error(EMAGLS_ERR_ARG, "shDefinition must be 'real' or 'complex'");
-    if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
-    if (n_yaw != 1 && n_yaw != nsamp) throw Error(EMAGLS_ERR_ARG, "the rotation needs one angle or one angle per input sample");
-    if (rotate_order(layout, nch) < 0)
-        throw Error(EMAGLS_ERR_ARG, layout == EMAGLS_LAYOUT_SH ? "the rotation needs (N+1)^2 SH channels" : "the rotation needs 2N+1 CH channels");
-}
-
-// Device-resident body of the two render entry points; the caller holds g_render_scratch.mu.  d_out [nout][2], nout = nsig ? nsig :
-// nsamp, no delay cut; `cut` only moves the start of the imaginary-part sums.
-}  // extern "C"
-std::mutex& emagls::render_scratch_mutex() { return g_render_scratch.mu; }
-void* emagls::render_scratch(RenderBuf which, size_t bytes) { return g_render_scratch.get((int)which, bytes); }
-void emagls::render_core(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len,
-                         int layout, bool cb, const double* d_yaw, int64_t n_yaw, const double* d_sig, int64_t nsig, int64_t cut,
-                         double* d_out, double* imag_abs, hipStream_t st) {
-    RenderScratch& r = g_render_scratch;
-    if (n_yaw == 1) {           // fixed angle: rotate the filters, sum_i w_i * (x Rot^T)_i = sum_j (w Rot)_j * x_j
-        const bool wc2 = w_c || cb;
-        void* rL = r.get(RenderScratch::ROT_WL, esz(wc2) * (size_t)len * nch);
-        void* rR = r.get(RenderScratch::ROT_WR, esz(wc2) * (size_t)len * nch);
-        launch_rotate_yaw(d_wL, w_c, len, nch, layout, cb, d_yaw, false, true, rL, st);
-        launch_rotate_yaw(d_wR, w_c, len, nch, layout, cb, d_yaw, false, true, rR, st);
-        d_wL = rL; d_wR = rR; w_c = wc2;
-    } else if (n_yaw > 1) {     // trajectory: a separate pass over the signal
-        const bool ic2 = in_c || cb;
-        void* x = r.get(RenderScratch::ROT_SIG, esz(ic2) * (size_t)nsamp * nch);
-        launch_rotate_yaw(d_in, in_c, nsamp, nch, layout, cb, d_yaw, true, false, x, st);
-        d_in = x; in_c = ic2;
-    }
-    const bool any_c = in_c || w_c, want_imag = imag_abs && any_c;
-    double* stage1 = nsig > 0 ? r.get<double>(RenderScratch::IR, sizeof(double) * 2 * (size_t)nsamp) : d_out;
-    double* tmp = want_imag ? r.get<double>(RenderScratch::TMP, sizeof(double) * (2 * (size_t)nsamp + 2)) : nullptr;
-    double im1[2] = {0.0, 0.0};
-    if (!any_c) {
-        binaural_decode_real((const double*)d_in, nsamp, nch, (const double*)d_wL, (const double*)d_wR, len, stage1, st);
-    } else {
-        double* sig2 = r.get<double>(RenderScratch::SIG2, sizeof(double) * 2 * (size_t)nsamp * nch);
-        double* w2L = r.get<double>(RenderScratch::W2L, sizeof(double) * 2 * (size_t)len * nch);
-        double* w2R = r.get<double>(RenderScratch::W2R, sizeof(double) * 2 * (size_t)len * nch);
-        binaural_decode_complex(d_in, in_c, nsamp, nch, d_wL, d_wR, w_c, len, sig2, w2L, w2R, stage1,
-                                want_imag ? (nsig > 0 ? im1 : imag_abs) : nullptr, tmp, st, nsig > 0 ? 0 : std::min(cut, nsamp));
-    }
-    if (nsig > 0) {   // :44-48: the two ears of the first stage are the filters of a one-channel overlap-save over the signal
-        binaural_decode_real(d_sig, nsig, 1, stage1, stage1 + nsamp, nsamp, d_out, st);
-        if (want_imag) {   // real(conv(e, s)) = conv(real(e), s); the imaginary part only feeds the two warning sums
-            double* yim = r.get<double>(RenderScratch::YIM, sizeof(double) * (2 * (size_t)nsig + 2));
-            binaural_decode_real(d_sig, nsig, 1, tmp, tmp + nsamp, nsamp, yim, st);
-            launch_abs_sum_cols(yim, nsig, std::min(cut, nsig), 2, yim + 2 * nsig, st);
-            HIP_CHECK(hipMemcpyAsync(imag_abs, yim + 2 * nsig, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-    }
-    HIP_CHECK(hipStreamSynchronize(st));
-}
-
-extern "C" {
-int emagls_rotate_yaw(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int layout, int basis, const double* yaw,
-                      int64_t n_yaw, void* out) {
-    return guarded([&] {
-        if (!in || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        if (nsamp < 0 || nch < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-        if (n_yaw < 1) throw Error(EMAGLS_ERR_ARG, "the rotation needs one angle or one angle per input sample");
-        check_render_args(nsamp, nch, layout, basis, n_yaw, yaw != nullptr);
-        if (nsamp == 0) return;
-        const bool ic = in_is_complex != 0, cb = basis == EMAGLS_BASIS_COMPLEX, oc = ic || cb;
-        const size_t bin = esz(ic) * (size_t)nsamp * nch, bout = esz(oc) * (size_t)nsamp * nch;
-        void *d_in = nullptr, *d_out = nullptr;
-        double* d_yaw = nullptr;
-        hipStream_t st = nullptr;
-        auto cleanup = [&] { hipFree(d_in); hipFree(d_out); hipFree(d_yaw); emagls::pool_stream_give(st); };
-        try {
-            st = emagls::pool_stream_take();
-            HIP_CHECK(hipMalloc(&d_in, bin));
-            HIP_CHECK(hipMalloc(&d_out, bout));
-            HIP_CHECK(hipMalloc(&d_yaw, sizeof(double) * n_yaw));
-            HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(d_yaw, yaw, sizeof(double) * n_yaw, hipMemcpyHostToDevice, st));
-            launch_rotate_yaw(d_in, ic, nsamp, (int)nch, layout, cb, d_yaw, n_yaw > 1, false, d_out, st);
-            HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-        } catch (...) { cleanup(); throw; }
-        cleanup();
-    });
-}
-
-int emagls_binaural_decode_render(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
-                                  int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
-                                  int64_t n_yaw, const double* signal, int64_t n_signal, double* out, double* imag_abs_sum) {
-    const int64_t nsig = signal ? n_signal : 0;
-    if (n_yaw == 0 && nsig == 0) {   // nothing to add: today's entry points, bit for bit
-        if (!in_is_complex && !filters_are_complex)
-            return decode_entry(in, false, nsamp, nch, wL, wR, false, len, compensate_delay, out, nullptr);
-        return decode_entry(in, in_is_complex != 0, nsamp, nch, wL, wR, filters_are_complex != 0, len, compensate_delay, out, imag_abs_sum);
-    }
-    return guarded([&] {
-        if (!in || !wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        if (nsamp < 0 || nch < 1 || len < 1 || n_yaw < 0 || n_signal < 0) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-        check_render_args(nsamp, nch, layout, basis, n_yaw, yaw != nullptr);
-        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
-        const int64_t nout = nsig > 0 ? nsig : nsamp;
-        const int64_t skip = (compensate_delay && len / 2 > 0) ? len / 2 - 1 : 0;    // binauralOut(del:end,:), del = len/2 (:53-57)
-        if (nsamp == 0) {   // the rendered impulse response is empty: so is its convolution with the signal
-            if (nout - skip > 0) std::fill(out, out + 2 * (nout - skip), 0.0);
-            return;
-        }
-        const bool ic = in_is_complex != 0, wc = filters_are_complex != 0;
-        const size_t bin = esz(ic) * (size_t)nsamp * nch, bw = esz(wc) * (size_t)len * nch;
-        void *d_in = nullptr, *d_wL = nullptr, *d_wR = nullptr;
-        double *d_yaw = nullptr, *d_sig = nullptr, *d_out = nullptr;
-        hipStream_t st = nullptr;
-        auto cleanup = [&] {
-            hipFree(d_in); hipFree(d_wL); hipFree(d_wR); hipFree(d_yaw); hipFree(d_sig); hipFree(d_out);
-            emagls::pool_stream_give(st);
-        };
-        try {
-            st = emagls::pool_stream_take();
-            HIP_CHECK(hipMalloc(&d_in, bin));
-            HIP_CHECK(hipMalloc(&d_wL, bw));
-            HIP_CHECK(hipMalloc(&d_wR, bw));
-            HIP_CHECK(hipMalloc(&d_out, sizeof(double) * 2 * nout));
-            HIP_CHECK(hipMemcpy(d_in, in, bin, hipMemcpyDefault));
-            HIP_CHECK(hipMemcpy(d_wL, wL, bw, hipMemcpyDefault));
-            HIP_CHECK(hipMemcpy(d_wR, wR, bw, hipMemcpyDefault));
-            if (n_yaw > 0) {
-                HIP_CHECK(hipMalloc(&d_yaw, sizeof(double) * n_yaw));
-                HIP_CHECK(hipMemcpy(d_yaw, yaw, sizeof(double) * n_yaw, hipMemcpyDefault));
-            }
-            if (nsig > 0) {
-                HIP_CHECK(hipMalloc(&d_sig, sizeof(double) * nsig));
-                HIP_CHECK(hipMemcpy(d_sig, signal, sizeof(double) * nsig, hipMemcpyDefault));
-            }
-            {
-                std::lock_guard<std::mutex> lk(g_render_scratch.mu);
-                render_core(d_in, ic, nsamp, (int)nch, d_wL, d_wR, wc, len, layout, basis == EMAGLS_BASIS_COMPLEX, d_yaw, n_yaw, d_sig, nsig,
-                            skip, d_out, imag_abs_sum, st);
-            }
-            const int64_t rows = nout - skip;
-            if (rows > 0) {
-                HIP_CHECK(hipMemcpy(out, d_out + skip, sizeof(double) * rows, hipMemcpyDefault));
-                HIP_CHECK(hipMemcpy(out + rows, d_out + nout + skip, sizeof(double) * rows, hipMemcpyDefault));
-            }
-        } catch (...) { cleanup(); throw; }
-        cleanup();
-    });
-}
-
-int emagls_binaural_decode_render_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
-                                         const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis,
-                                         const double* d_yaw, int64_t n_yaw, const double* d_signal, int64_t n_signal, double* d_out,
-                                         double* imag_abs_sum, void* stream) {
-    return guarded([&] {
-        if (!d_in || !d_wL || !d_wR || !d_out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        if (nsamp < 0 || nch < 1 || len < 1 || n_yaw < 0 || n_signal < 0) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-        check_render_args(nsamp, nch, layout, basis, n_yaw, d_yaw != nullptr);
-        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
-        const int64_t nsig = d_signal ? n_signal : 0;
-        hipStream_t st = (hipStream_t)stream;
-        if (nsamp == 0) {
-            if (nsig > 0) HIP_CHECK(hipMemsetAsync(d_out, 0, sizeof(double) * 2 * nsig, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            return;
-        }
-        std::lock_guard<std::mutex> lk(g_render_scratch.mu);
-        render_core(d_in, in_is_complex != 0, nsamp, (int)nch, d_wL, d_wR, filters_are_complex != 0, len, layout, basis == EMAGLS_BASIS_COMPLEX,
-                    d_yaw, n_yaw, d_signal, nsig, 0, d_out, imag_abs_sum, st);
-    });
 }
 
 int emagls_get_magls_filters_dc(const double* hL, const double* hR, int64_t nsamp, int64_t ndirs, const double* azi, const double* zen,
@@ -5026,15 +4724,6 @@ int emagls_from_atf_hrir_sets(const double* hL, const double* hR, int64_t nsamp,
             first += n;
         }
     });
-}
-
-int emagls_binaural_decode(const double* in, int64_t nsamp, int64_t nch, const double* wL, const double* wR, int64_t len,
-                           int compensate_delay, double* out) {
-    return decode_entry(in, false, nsamp, nch, wL, wR, false, len, compensate_delay, out, nullptr);
-}
-int emagls_binaural_decode_complex(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
-                                   int filters_are_complex, int64_t len, int compensate_delay, double* out, double* imag_abs_sum) {
-    return decode_entry(in, in_is_complex != 0, nsamp, nch, wL, wR, filters_are_complex != 0, len, compensate_delay, out, imag_abs_sum);
 }
 
 }  // extern "C"

@@ -1,0 +1,354 @@
+// C ABI of binauralDecode and the SH rotations (include/emagls.h: emagls_binaural_decode*, emagls_rotate_yaw, emagls_rotate_sh,
+// emagls_sh_rotation_matrix): the argument check, host staging, the work buffers and the choice of kernels, once for all ten
+// entry points.  The kernels are decode.hip's, rotate.hip's and rotate3.hip's.  No CPU fallback.
+#include <algorithm>
+#include <initializer_list>
+#include <vector>
+
+#include "../../include/emagls.h"
+#include "kernels.hpp"
+
+using namespace emagls;
+
+namespace {
+
+// The head rotation of a call: each angle absent (0 values), one value or one value per input sample.  Yaw-only means
+// n_pitch == n_roll == 0: such a call takes rotate.hip's kernel (SH or CH), any other rotate3.hip's (SH, orders 0 to 15).
+struct Angles {
+    const double* yaw = nullptr;
+    int64_t n_yaw = 0;
+    const double* pitch = nullptr;
+    int64_t n_pitch = 0;
+    const double* roll = nullptr;
+    int64_t n_roll = 0;
+    bool yaw_only() const { return n_pitch == 0 && n_roll == 0; }
+    bool any() const { return n_yaw != 0 || !yaw_only(); }
+    bool fixed() const { return n_yaw <= 1 && n_pitch <= 1 && n_roll <= 1; }
+};
+
+struct Scratch {   // device buffers and a pool stream of one host call, freed on every exit path
+    std::vector<void*> ptrs;
+    hipStream_t st = nullptr;
+    Scratch() { st = pool_stream_take(); }
+    ~Scratch() {
+        for (void* p : ptrs) hipFree(p);
+        pool_stream_give(st);
+    }
+    template <typename T = void> T* get(size_t bytes) {
+        void* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16));
+        ptrs.push_back(p);
+        return reinterpret_cast<T*>(p);
+    }
+    template <typename T> const T* put(const T* host, size_t count) {   // a device copy of host[count]; null for none
+        if (!host || !count) return nullptr;
+        T* p = get<T>(sizeof(T) * count);
+        HIP_CHECK(hipMemcpyAsync(p, host, sizeof(T) * count, hipMemcpyDefault, st));
+        return p;
+    }
+    Angles put(const Angles& a) {
+        return {put(a.yaw, (size_t)a.n_yaw), a.n_yaw, put(a.pitch, (size_t)a.n_pitch), a.n_pitch, put(a.roll, (size_t)a.n_roll), a.n_roll};
+    }
+};
+
+// work buffers of the device-resident body, grown on demand and kept (released by decode_family_cache_clear); one decode at a
+// time per process, like decode.hip's plans
+struct Work {
+    enum { ROT_SIG, ROT_WL, ROT_WR, SIG2, W2L, W2R, TMP, IR, YIM, NBUF };
+    std::mutex mu;
+    int device = -1;
+    void* p[NBUF] = {};
+    size_t cap[NBUF] = {};
+    void release() {
+        for (int i = 0; i < NBUF; ++i) { hipFree(p[i]); p[i] = nullptr; cap[i] = 0; }
+        device = -1;
+    }
+    template <typename T = void> T* get(int i, size_t bytes) {
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        if (dev != device) { release(); device = dev; }
+        bytes = std::max<size_t>(bytes, 16);
+        if (bytes > cap[i]) { hipFree(p[i]); p[i] = nullptr; cap[i] = 0; HIP_CHECK(hipMalloc(&p[i], bytes)); cap[i] = bytes; }
+        return reinterpret_cast<T*>(p[i]);
+    }
+};
+Work g_work;
+
+bool all_zero(const double* a, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (a[i] != 0.0) return false;
+    return true;
+}
+
+// Host entry points drop pitch and roll arrays that hold only zeros, so such a call is yaw-only: bit for bit the yaw path.
+// (Device arrays are not read: there only absent pitch and roll make a call yaw-only.)
+Angles host_angles(Angles a) {
+    auto zero = [](const double* p, int64_t n) { return n == 0 || (p && n > 0 && all_zero(p, n)); };
+    if (zero(a.pitch, a.n_pitch) && zero(a.roll, a.n_roll)) { a.pitch = a.roll = nullptr; a.n_pitch = a.n_roll = 0; }
+    return a;
+}
+
+void check_basis(int basis) {
+    if (basis != EMAGLS_BASIS_REAL && basis != EMAGLS_BASIS_COMPLEX) throw Error(EMAGLS_ERR_ARG, "shDefinition must be 'real' or 'complex'");
+}
+
+void check_order3(int N) {
+    if (N > rotate3_max_order()) throw Error(EMAGLS_ERR_UNSUPPORTED, "the three-axis rotation supports SH orders 0 to 15");
+}
+
+void check_angles(int64_t nsamp, const double* p, int64_t n, const char* name) {
+    if (n < 0 || (n > 1 && n != nsamp)) throw Error(EMAGLS_ERR_ARG, std::string(name) + " needs no value, one value or one value per input sample");
+    if (n > 0 && !p) throw Error(EMAGLS_ERR_ARG, "null pointer");
+}
+
+// The argument check of every entry point, in the order in which they have always reported (the messages and the statuses are
+// part of the ABI).  decode: a decode with filters of length len and a signal of n_signal samples, rather than a rotation alone,
+// which needs an angle.
+void check_args(bool decode, std::initializer_list<const void*> ptrs, int64_t nsamp, int64_t nch, int64_t len, int64_t n_signal,
+                int layout, int basis, const Angles& a) {
+    static const char* const count = "the rotation needs one angle or one angle per input sample";
+    for (const void* p : ptrs)
+        if (!p) throw Error(EMAGLS_ERR_ARG, "null pointer");
+    if (nsamp < 0 || nch < 1 || (decode && (len < 1 || n_signal < 0 || (a.yaw_only() && a.n_yaw < 0))))
+        throw Error(EMAGLS_ERR_ARG, "invalid shape");
+    if (a.yaw_only()) {
+        if (!decode && a.n_yaw < 1) throw Error(EMAGLS_ERR_ARG, count);
+        if (a.n_yaw == 0) return;
+        if (!a.yaw) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        check_basis(basis);
+        if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
+        if (a.n_yaw != 1 && a.n_yaw != nsamp) throw Error(EMAGLS_ERR_ARG, count);
+        if (rotate_order(layout, nch) < 0)
+            throw Error(EMAGLS_ERR_ARG, layout == EMAGLS_LAYOUT_SH ? "the rotation needs (N+1)^2 SH channels" : "the rotation needs 2N+1 CH channels");
+        return;
+    }
+    check_angles(nsamp, a.yaw, a.n_yaw, "yaw");
+    check_angles(nsamp, a.pitch, a.n_pitch, "pitch");
+    check_angles(nsamp, a.roll, a.n_roll, "roll");
+    if (layout == EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "a CH signal can only be turned about z: pitch and roll must be 0");
+    if (layout != EMAGLS_LAYOUT_SH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
+    check_basis(basis);
+    const int N = rotate_order(EMAGLS_LAYOUT_SH, nch);
+    if (N < 0) throw Error(EMAGLS_ERR_ARG, "the three-axis rotation needs (N+1)^2 SH channels in ACN order");
+    check_order3(N);
+}
+
+// in [C][n] -> out [C][n] (complex when in_c or cb) by rotate.hip's kernel for a yaw-only rotation, rotate3.hip's otherwise;
+// transpose: the filter-side form of a fixed rotation (w Rot instead of x Rot^T)
+void launch_rotation(const Angles& a, const void* in, bool in_c, int64_t n, int nch, int layout, bool cb, bool transpose, void* out,
+                     hipStream_t st) {
+    if (a.yaw_only())
+        launch_rotate_yaw(in, in_c, n, nch, layout, cb, a.yaw, a.n_yaw > 1, transpose, out, st);
+    else
+        launch_rotate3(in, in_c, n, nch, cb, a.n_yaw ? a.yaw : nullptr, a.n_yaw > 1, a.n_pitch ? a.pitch : nullptr, a.n_pitch > 1,
+                       a.n_roll ? a.roll : nullptr, a.n_roll > 1, transpose, out, st);
+}
+
+// The rotation before the decode.  A fixed one (every count <= 1) turns the decoding filters, sum_i w_i * (x Rot^T)_i =
+// sum_j (w Rot)_j * x_j; a trajectory is a pass over the signal into ROT_SIG.  The operands it replaces
+// are complex from here on in the complex basis.  (g_work.mu held)
+void rotate_step(const Angles& a, int layout, bool cb, int64_t nsamp, int nch, int64_t len, const void*& d_in, bool& in_c,
+                 const void*& d_wL, const void*& d_wR, bool& w_c, hipStream_t st) {
+    if (a.fixed()) {
+        const bool wc2 = w_c || cb;
+        void* rL = g_work.get(Work::ROT_WL, esz(wc2) * (size_t)len * nch);
+        void* rR = g_work.get(Work::ROT_WR, esz(wc2) * (size_t)len * nch);
+        launch_rotation(a, d_wL, w_c, len, nch, layout, cb, true, rL, st);
+        launch_rotation(a, d_wR, w_c, len, nch, layout, cb, true, rR, st);
+        d_wL = rL; d_wR = rR; w_c = wc2;
+    } else {
+        const bool ic2 = in_c || cb;
+        void* x = g_work.get(Work::ROT_SIG, esz(ic2) * (size_t)nsamp * nch);
+        launch_rotation(a, d_in, in_c, nsamp, nch, layout, cb, false, x, st);
+        d_in = x; in_c = ic2;
+    }
+}
+
+// The device-resident body of every decode entry (nsamp > 0): the rotation, the real or complex decode, and the source-signal
+// convolution of dependencies/binauralDecode.m:44-48 with its imaginary-part sums.  d_out [nout][2], nout = nsig ? nsig : nsamp,
+// without the delay cut; `cut` only moves the start of the imaginary-part sums.  Returns with st synchronised (every
+// binaural_decode_real call synchronises it).
+void decode_body(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len, int layout,
+                 bool cb, const Angles& a, const double* d_sig, int64_t nsig, int64_t cut, double* d_out, double* imag_abs, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(g_work.mu);
+    if (a.any()) rotate_step(a, layout, cb, nsamp, nch, len, d_in, in_c, d_wL, d_wR, w_c, st);
+    const bool any_c = in_c || w_c, want_imag = imag_abs && any_c;
+    double* stage1 = nsig > 0 ? g_work.get<double>(Work::IR, sizeof(double) * 2 * (size_t)nsamp) : d_out;
+    double* tmp = want_imag ? g_work.get<double>(Work::TMP, sizeof(double) * (2 * (size_t)nsamp + 2)) : nullptr;
+    double im1[2] = {0.0, 0.0};
+    if (!any_c) {
+        binaural_decode_real((const double*)d_in, nsamp, nch, (const double*)d_wL, (const double*)d_wR, len, stage1, st);
+    } else {
+        double* sig2 = g_work.get<double>(Work::SIG2, sizeof(double) * 2 * (size_t)nsamp * nch);
+        double* w2L = g_work.get<double>(Work::W2L, sizeof(double) * 2 * (size_t)len * nch);
+        double* w2R = g_work.get<double>(Work::W2R, sizeof(double) * 2 * (size_t)len * nch);
+        // (the reference sums the discarded imaginary part after binauralOut(del:end,:), binauralDecode.m:53-62)
+        binaural_decode_complex(d_in, in_c, nsamp, nch, d_wL, d_wR, w_c, len, sig2, w2L, w2R, stage1,
+                                want_imag ? (nsig > 0 ? im1 : imag_abs) : nullptr, tmp, st, nsig > 0 ? 0 : std::min(cut, nsamp));
+    }
+    if (nsig > 0) {   // the two ears of the first stage are the filters of a one-channel overlap-save over the signal
+        binaural_decode_real(d_sig, nsig, 1, stage1, stage1 + nsamp, nsamp, d_out, st);
+        if (want_imag) {   // real(conv(e, s)) = conv(real(e), s); the imaginary part only feeds the two warning sums
+            double* yim = g_work.get<double>(Work::YIM, sizeof(double) * (2 * (size_t)nsig + 2));
+            binaural_decode_real(d_sig, nsig, 1, tmp, tmp + nsamp, nsamp, yim, st);
+            launch_abs_sum_cols(yim, nsig, std::min(cut, nsig), 2, yim + 2 * nsig, st);
+            HIP_CHECK(hipMemcpyAsync(imag_abs, yim + 2 * nsig, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+    }
+}
+
+// The host decode entries: staging, the body, and the compensate_delay cut on the way back (binauralOut(del:end,:), del = len/2,
+// dependencies/binauralDecode.m:53-57): out [nout - (len/2 - 1)][2].
+int host_decode(const void* in, bool ic, int64_t nsamp, int64_t nch, const void* wL, const void* wR, bool wc, int64_t len, int compensate_delay,
+                int layout, int basis, const Angles& a, const double* signal, int64_t n_signal, double* out, double* imag_abs_sum) {
+    return guarded_call([&] {
+        const int64_t nsig = signal ? n_signal : 0;
+        // (without rotation and signal, the checks of emagls_binaural_decode_complex: they never looked at n_signal)
+        check_args(true, {in, wL, wR, out}, nsamp, nch, len, a.any() || nsig ? n_signal : 0, layout, basis, a);
+        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
+        const int64_t nout = nsig > 0 ? nsig : nsamp;
+        const int64_t cut = (compensate_delay && len / 2 > 0) ? len / 2 - 1 : 0;
+        const int64_t rows = nout - cut;
+        if (nsamp == 0) {   // the rendered impulse response is empty: so is its convolution with the signal
+            if (rows > 0) std::fill(out, out + 2 * rows, 0.0);
+            return;
+        }
+        Scratch s;
+        const void* d_in = s.put((const char*)in, esz(ic) * (size_t)nsamp * nch);
+        const void* d_wL = s.put((const char*)wL, esz(wc) * (size_t)len * nch);
+        const void* d_wR = s.put((const char*)wR, esz(wc) * (size_t)len * nch);
+        double* d_out = s.get<double>(sizeof(double) * 2 * nout);
+        decode_body(d_in, ic, nsamp, (int)nch, d_wL, d_wR, wc, len, layout, basis == EMAGLS_BASIS_COMPLEX, s.put(a), s.put(signal, (size_t)nsig),
+                    nsig, cut, d_out, imag_abs_sum, s.st);
+        if (rows > 0) {
+            HIP_CHECK(hipMemcpyAsync(out, d_out + cut, sizeof(double) * rows, hipMemcpyDefault, s.st));
+            HIP_CHECK(hipMemcpyAsync(out + rows, d_out + nout + cut, sizeof(double) * rows, hipMemcpyDefault, s.st));
+            HIP_CHECK(hipStreamSynchronize(s.st));
+        }
+    });
+}
+
+// The two host rotation entries: staging, the rotation, the result back
+int host_rotate(const void* in, bool ic, int64_t nsamp, int64_t nch, int layout, int basis, const Angles& a, void* out) {
+    return guarded_call([&] {
+        check_args(false, {in, out}, nsamp, nch, 0, 0, layout, basis, a);
+        if (nsamp == 0) return;
+        const bool cb = basis == EMAGLS_BASIS_COMPLEX;
+        const size_t bout = esz(ic || cb) * (size_t)nsamp * nch;
+        Scratch s;
+        const void* d_in = s.put((const char*)in, esz(ic) * (size_t)nsamp * nch);
+        void* d_out = s.get(bout);
+        launch_rotation(s.put(a), d_in, ic, nsamp, (int)nch, layout, cb, false, d_out, s.st);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDefault, s.st));
+        HIP_CHECK(hipStreamSynchronize(s.st));
+    });
+}
+
+}  // namespace
+
+void emagls::decode_family_cache_clear() {
+    decode_cache_clear();
+    rotate3_cache_clear();
+    std::lock_guard<std::mutex> lk(g_work.mu);
+    g_work.release();
+}
+
+extern "C" {
+
+int emagls_binaural_decode(const double* in, int64_t nsamp, int64_t nch, const double* wL, const double* wR, int64_t len,
+                           int compensate_delay, double* out) {
+    return host_decode(in, false, nsamp, nch, wL, wR, false, len, compensate_delay, EMAGLS_LAYOUT_SH, EMAGLS_BASIS_REAL, {}, nullptr, 0,
+                       out, nullptr);
+}
+
+int emagls_binaural_decode_complex(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                   int filters_are_complex, int64_t len, int compensate_delay, double* out, double* imag_abs_sum) {
+    return host_decode(in, in_is_complex != 0, nsamp, nch, wL, wR, filters_are_complex != 0, len, compensate_delay, EMAGLS_LAYOUT_SH,
+                       EMAGLS_BASIS_REAL, {}, nullptr, 0, out, imag_abs_sum);
+}
+
+int emagls_binaural_decode_render_ypr(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                      int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
+                                      int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll,
+                                      const double* signal, int64_t n_signal, double* out, double* imag_abs_sum) {
+    const Angles a = host_angles({yaw, n_yaw, pitch, n_pitch, roll, n_roll});
+    // (without rotation and signal, with nothing complex, this is emagls_binaural_decode: imag_abs_sum is left alone)
+    const bool plain_real = !a.any() && !(signal && n_signal) && !in_is_complex && !filters_are_complex;
+    return host_decode(in, in_is_complex != 0, nsamp, nch, wL, wR, filters_are_complex != 0, len, compensate_delay, layout, basis, a, signal,
+                       n_signal, out, plain_real ? nullptr : imag_abs_sum);
+}
+
+int emagls_binaural_decode_render(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                  int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
+                                  int64_t n_yaw, const double* signal, int64_t n_signal, double* out, double* imag_abs_sum) {
+    return emagls_binaural_decode_render_ypr(in, in_is_complex, nsamp, nch, wL, wR, filters_are_complex, len, compensate_delay, layout, basis,
+                                             yaw, n_yaw, nullptr, 0, nullptr, 0, signal, n_signal, out, imag_abs_sum);
+}
+
+int emagls_binaural_decode_render_ypr_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                             const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
+                                             int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
+                                             const double* d_signal, int64_t n_signal, double* d_out, double* imag_abs_sum, void* stream) {
+    return guarded_call([&] {
+        const Angles a{d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll};
+        check_args(true, {d_in, d_wL, d_wR, d_out}, nsamp, nch, len, n_signal, layout, basis, a);
+        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
+        const int64_t nsig = d_signal ? n_signal : 0;
+        hipStream_t st = (hipStream_t)stream;
+        if (nsamp == 0) {
+            if (nsig > 0) HIP_CHECK(hipMemsetAsync(d_out, 0, sizeof(double) * 2 * nsig, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            return;
+        }
+        decode_body(d_in, in_is_complex != 0, nsamp, (int)nch, d_wL, d_wR, filters_are_complex != 0, len, layout, basis == EMAGLS_BASIS_COMPLEX,
+                    a, d_signal, nsig, 0, d_out, imag_abs_sum, st);
+    });
+}
+
+int emagls_binaural_decode_render_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                         const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis,
+                                         const double* d_yaw, int64_t n_yaw, const double* d_signal, int64_t n_signal, double* d_out,
+                                         double* imag_abs_sum, void* stream) {
+    return emagls_binaural_decode_render_ypr_device(d_in, in_is_complex, nsamp, nch, d_wL, d_wR, filters_are_complex, len, layout, basis,
+                                                    d_yaw, n_yaw, nullptr, 0, nullptr, 0, d_signal, n_signal, d_out, imag_abs_sum, stream);
+}
+
+int emagls_binaural_decode_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL, const void* d_wR,
+                                  int filters_are_complex, int64_t len, double* d_out, double* imag_abs_sum, void* stream) {
+    return emagls_binaural_decode_render_ypr_device(d_in, in_is_complex, nsamp, nch, d_wL, d_wR, filters_are_complex, len, EMAGLS_LAYOUT_SH,
+                                                    EMAGLS_BASIS_REAL, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, d_out, imag_abs_sum,
+                                                    stream);
+}
+
+int emagls_rotate_yaw(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int layout, int basis, const double* yaw,
+                      int64_t n_yaw, void* out) {
+    return host_rotate(in, in_is_complex != 0, nsamp, nch, layout, basis, {yaw, n_yaw}, out);
+}
+
+int emagls_rotate_sh(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int basis, const double* yaw, int64_t n_yaw,
+                     const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll, void* out) {
+    Angles a{yaw, n_yaw, pitch, n_pitch, roll, n_roll};
+    auto counted = [&](int64_t n) { return n >= 0 && (n <= 1 || n == nsamp); };
+    if (counted(n_pitch) && counted(n_roll)) a = host_angles(a);   // (zeros in a count that does not fit are reported, not dropped)
+    const double zero = 0.0;
+    if (a.yaw_only() && a.n_yaw == 0) { a.yaw = &zero; a.n_yaw = 1; }   // (an absent yaw is 0)
+    return host_rotate(in, in_is_complex != 0, nsamp, nch, EMAGLS_LAYOUT_SH, basis, a, out);
+}
+
+int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, double roll, void* out) {
+    return guarded_call([&] {
+        if (!out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
+        check_order3(order);
+        check_basis(basis);
+        const size_t C = (size_t)(order + 1) * (order + 1), bytes = esz(basis == EMAGLS_BASIS_COMPLEX) * C * C;
+        Scratch s;
+        void* d = s.get(bytes);
+        launch_rotate3_matrix(order, basis == EMAGLS_BASIS_COMPLEX, yaw, pitch, roll, d, s.st);
+        HIP_CHECK(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, s.st));
+        HIP_CHECK(hipStreamSynchronize(s.st));
+    });
+}
+
+}  // extern "C"

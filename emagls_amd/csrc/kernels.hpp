@@ -1,4 +1,4 @@
-// Launcher declarations shared by the kernel translation units and the C ABI (capi.hip).
+// Launcher declarations shared by the kernel translation units and the C ABI (capi.hip, decode_api.hip, render_api.hip).
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -219,13 +219,8 @@ void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_ba
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st);
 void rotate3_cache_clear();
 
-// ---- capi.hip: the body of emagls_binaural_decode_render(_device), for the entry points that rotate first (rotate3_api.hip)
-enum RenderBuf { RENDER_ROT_SIG, RENDER_ROT_WL, RENDER_ROT_WR };
-std::mutex& render_scratch_mutex();
-void* render_scratch(RenderBuf which, size_t bytes);   // (render_scratch_mutex() held)
-void render_core(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len,
-                 int layout, bool cb, const double* d_yaw, int64_t n_yaw, const double* d_sig, int64_t nsig, int64_t cut,
-                 double* d_out, double* imag_abs, hipStream_t st);   // (render_scratch_mutex() held)
+// ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables and the decode family's work buffers
+void decode_family_cache_clear();
 
 void filter_channels_by_order(const double* sig, int64_t n_in, int64_t n, int C, const double* ir /* [nOrd][len] */, int nOrd, int64_t len,
                               int64_t skip, double* out /* [C][n-skip] */, hipStream_t st);

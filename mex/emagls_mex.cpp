@@ -124,11 +124,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize nroll = (nrhs > 10 && !mxIsEmpty(prhs[10])) ? mxGetNumberOfElements(prhs[10]) : 0;
         const double* pitch = npitch ? dbl(prhs[9], "pitchRad") : nullptr;
         const double* roll = nroll ? dbl(prhs[10], "rollRad") : nullptr;
-        const int rc = (npitch || nroll)
-            ? emagls_binaural_decode_render_ypr(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout, basis,
-                                                yaw, nyaw, pitch, npitch, roll, nroll, sig, nsig, mxGetDoubles(plhs[0]), imag_sum)
-            : emagls_binaural_decode_render(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout,
-                                            basis, yaw, nyaw, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
+        const int rc = emagls_binaural_decode_render_ypr(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp, layout,
+                                                         basis, yaw, nyaw, pitch, npitch, roll, nroll, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
         if (rc) fail(rc);
         if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
         return;
@@ -186,15 +183,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[0] = mxCreateDoubleMatrix(nout, 2, mxREAL);
         const bool ic = mxIsComplex(prhs[1]), wc = mxIsComplex(prhs[2]);
         if (wc != (bool)mxIsComplex(prhs[3])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
-        int rc;
-        if (!ic && !wc) {
-            rc = emagls_binaural_decode(dbl(prhs[1], "in"), n, ch, dbl(prhs[2], "wL"), dbl(prhs[3], "wR"), len, comp, mxGetDoubles(plhs[0]));
-        } else {   // dependencies/binauralDecode.m:39-42,59-64: complex products accumulated, the real part kept
-            double imag_sum[2] = {0, 0};
-            rc = emagls_binaural_decode_complex(in_ptr(prhs[1]), ic, n, ch, in_ptr(prhs[2]), in_ptr(prhs[3]), wc, len, comp,
-                                                mxGetDoubles(plhs[0]), imag_sum);
-            if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
-        }
+        // (complex: dependencies/binauralDecode.m:39-42,59-64, complex products accumulated, the real part kept)
+        const bool cplx = ic || wc;
+        const void* in = cplx ? in_ptr(prhs[1]) : dbl(prhs[1], "in");
+        const void* wL = cplx ? in_ptr(prhs[2]) : dbl(prhs[2], "wL");
+        const void* wR = cplx ? in_ptr(prhs[3]) : dbl(prhs[3], "wR");
+        double imag_sum[2] = {0, 0};
+        const int rc = emagls_binaural_decode_complex(in, ic, n, ch, wL, wR, wc, len, comp, mxGetDoubles(plhs[0]), imag_sum);
+        if (cplx && nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
         if (rc) fail(rc);
         return;
     }
