@@ -55,6 +55,18 @@ def test_dump_outputs_writes_the_callers_layout(tmp_path):
             assert np.array_equal(c, (g[k, e, ..., 0].numpy() + 1j * g[k, e, ..., 1].numpy()).T)
 
 
+def test_plain_run_is_the_default():
+    """A plain `bench.py` run measures the headline figure only; --full adds the other figures, and the --no-* options only trim a
+    --full run."""
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and (a.gpus, a.steps, a.warmup) == (1, 20, 5)
+    a = b.parse_args(["--full", "--no-secondary"])
+    assert a.full and a.no_secondary and not a.no_cpu_baseline and not a.no_sh_roofline
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])
+
+
 def test_gpus_flag_spawns_fresh_ranks(tmp_path):
     """`bench.py --gpus N` without WORLD_SIZE starts N children with the torch.distributed environment (gloo here: the
     children rendezvous on 127.0.0.1 and all-reduce their ranks), before the parent imports torch or touches HIP."""
@@ -182,3 +194,34 @@ def test_bench_with_two_ranks_on_the_gpus_that_exist():
     assert d["n_gpus"] == 2 and d["steps"] == 8 and d["warmup"] == 4 and d["value"] > 0 and d["scaling"] == "weak"
     import torch
     assert ("INVALID_as_a_measurement" in d) == (torch.cuda.device_count() < 2)
+
+
+@pytest.mark.gpu
+def test_plain_and_full_runs_compute_the_same_filters(tmp_path):
+    """`bench.py` without --full prints the headline figure and no figure that takes runs of its own; with --full the line also
+    carries the lone-design, roofline and FP64-peak figures.  Both runs time the same designs and dump the same filters bit for
+    bit."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-sh-roofline", "--no-secondary"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / mode)] + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, (mode, r.stdout[-2000:], r.stderr[-4000:])
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(out) == 1
+        lines[mode] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    extras = ("roofline", "flops", "single_design_latency_ms", "stages_ms")
+    assert not any(k in plain for k in extras) and all(full[k] for k in extras)
+    assert not any(k in plain for k in ("parity", "cpu_baseline", "sh_basis_roofline", "one_shot_ms", "secondary"))
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    for name in ("wL.npy", "wR.npy"):
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.shape == (8, 512, 25, 2) and np.array_equal(a, b)

@@ -5,7 +5,7 @@
 # Prints value (filter sets/s) and the sweep launch's average duration per run; the JSON lines land in gpurun_out/<tag>_*.json.
 tag=$1; shift
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out
-B="--no-cpu-baseline --no-sh-roofline --no-secondary $BENCH_ARGS"
+B="--full --no-cpu-baseline --no-sh-roofline --no-secondary $BENCH_ARGS"
 i=0
 for cfg in "$@"; do
   i=$((i+1))

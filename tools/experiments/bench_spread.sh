@@ -3,7 +3,7 @@
 # interleaved.      bash tools/experiments/bench_spread.sh [N]      (through gpurun; prints one line per run and the means)
 N=${1:-8}
 cd $GRAFT_REPO_ROOT
-B="--no-cpu-baseline --no-sh-roofline --no-secondary"
+B="--full --no-cpu-baseline --no-sh-roofline --no-secondary"
 for rep in $(seq 1 $N); do
   for sw in "20 5" "128 32"; do
     set -- $sw

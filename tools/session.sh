@@ -5,8 +5,8 @@
 # ',' the items of a list; ENV=VALUE items are exported for that step only):
 #   tests:<file-or--k-expr>[,...]      pytest -m gpu -x -q -s on the given test files (a name without '/' is a -k expression)
 #   suite                              the whole gpu suite the way the round-end driver runs it, then smoke()
-#   bench:<steps>:<warmup>[:ENV=V,...] bench.py without the secondary figures; one summary line (value, ms/step, sweep launch, frac)
-#   full                               bench.py as the driver runs it (--steps 20 --warmup 5, everything)
+#   bench:<steps>:<warmup>[:ENV=V,...] bench.py --full without the secondary figures; one summary line (value, ms/step, sweep launch, frac)
+#   full                               bench.py --full --steps 20 --warmup 5 (every figure)
 #   timing:<n>[,<n>...]                in-kernel stamps of the resident sweep for launches of n designs (tools/sweep_timing.py)
 #   prof20                             rocprofv3 kernel trace of the driver's command: fill timeline, kernel averages, sweep launches
 #   pmc                                the PMC passes of tools/gpu_round.sh (32-design chunks) -> pmc.md, pmc_traffic.json
@@ -17,7 +17,7 @@
 tag=${1:-s}; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; O=gpurun_out/$tag; mkdir -p $O
 export EMAGLS_BUILD_TAG=$tag
-B="--no-cpu-baseline --no-sh-roofline --no-secondary"
+B="--full --no-cpu-baseline --no-sh-roofline --no-secondary"
 summ() { python - "$1" <<'PY'
 import json, sys
 f = sys.argv[1]
@@ -47,7 +47,7 @@ for step in "$@"; do
       n=1; while [ -e $O/${nm}_$n.json ]; do n=$((n+1)); done
       env "${envs[@]}" timeout 900 python bench.py --steps $a1 --warmup ${a2:-5} $B > $O/${nm}_$n.json 2> $O/${nm}_$n.err; summ $O/${nm}_$n.json ;;
     full)
-      timeout 1200 python bench.py --steps 20 --warmup 5 > $O/full.json 2> $O/full.err; echo "bench rc=$?"; summ $O/full.json; tail -2 $O/full.err ;;
+      timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/full.json 2> $O/full.err; echo "bench rc=$?"; summ $O/full.json; tail -2 $O/full.err ;;
     timing)
       IFS=',' read -ra items <<< "$a1"
       for n in "${items[@]}"; do timeout 300 python tools/sweep_timing.py $n > $O/sweep_timing_$n.log 2>&1; cut -c1-200 $O/sweep_timing_$n.log | tail -25; done ;;

@@ -27,7 +27,7 @@ def main():
     kname = js.get("roofline", {}).get("kernel", "sweep_persist_kernel")
     allrows = [(n, s, e, gx) for n, s, e, gx in cur.execute(f"select s.kernel_name, d.start, d.end, d.grid_size_x / d.workgroup_size_x from {kd} d "
                                                             f"join {ks} s on d.kernel_id=s.id order by d.start") if ("sweep_persist" in n or "sweep_synth" in n or "sweep_reg" in n)]
-    print(f"command: python3 bench.py --steps {js['steps']} --warmup {js['warmup']} --no-secondary   ->  {js['value']:.1f} {js['unit']}")
+    print(f"command: python3 bench.py --full --steps {js['steps']} --warmup {js['warmup']} --no-secondary   ->  {js['value']:.1f} {js['unit']}")
     if "sweep_reg" in kname:
         # round 5: the timed region is ONE job list (chunks of `bsz` designs, the partial chunk last); its chunks' sweeps are the last
         # launches of the register-resident kernel in the trace (set-up runs and warm-up come before; launches of up to 8 designs take
