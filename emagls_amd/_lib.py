@@ -104,6 +104,16 @@ SYMBOLS = {
     "emagls_binaural_decode_render_ypr_device": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64,
                                                            C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
                                                            C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "emagls_resample_length": (c_i64, [c_i64, c_i64, c_i64]),
+    "emagls_resample": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, c_i64, c_i64, C.c_void_p]),
+    "emagls_resample_device": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "emagls_binaural_decode_render_fs": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64, C.c_int,
+                                                   C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
+                                                   C.c_void_p, c_i64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "emagls_binaural_decode_render_fs_device": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64,
+                                                          C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
+                                                          C.c_void_p, c_i64, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]),
     "emagls_get_magls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_double, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_get_emagls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_double,

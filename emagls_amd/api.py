@@ -446,10 +446,54 @@ def shRotationMatrix(order, yawRad, pitchRad, rollRad, shDefinition="real"):
     return out
 
 
+def _rate(v, name):
+    """A sample rate or resampling factor as MATLAB's resample takes it: a positive integer value (int or integer-valued float)."""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a positive integer, not %r" % (name, v)) from None
+    if not math.isfinite(f) or f < 1 or f != math.floor(f) or f > 9e15:
+        raise ValueError("%s must be a positive integer, not %r" % (name, v))
+    return int(f)
+
+
+def _resampled_length(n, p, q):
+    return -(-n * p // q)
+
+
+def resample(x, p, q):
+    """MATLAB's resample(x, p, q) with its defaults N = 10, bta = 5 (Signal Processing Toolbox; called by
+    dependencies/binauralDecode.m:15,21-22), on the GPU.  Own restatement of resample.m: a Kaiser-windowed
+    sinc of 20 max(p, q) + 1 taps, polyphase, with resample.m's alignment; MATLAB's exact tap values are not pinned.  p and q:
+    positive integers (reduced by their gcd; max(p, q) <= 65536 after that).  x: a vector (1-D, or a 1 x n row) is resampled along
+    its length, a matrix [numSamples x numChannels] per column; real or complex.  The result has ceil(numSamples * p / q) samples
+    and x's shape otherwise."""
+    p, q = _rate(p, "p"), _rate(q, "q")
+    a = np.asarray(x)
+    cplx = np.iscomplexobj(a)
+    a = a.astype(np.complex128 if cplx else np.float64, copy=False)
+    if a.ndim > 2:
+        raise ValueError("x must be a vector or a [numSamples x numChannels] matrix")
+    row = a.ndim == 2 and a.shape[0] == 1
+    m = a.reshape(-1, 1) if a.ndim < 2 else (a.reshape(-1, 1) if row else a)
+    m = np.asfortranarray(m)
+    n, Cc = m.shape
+    ny = _resampled_length(n, p, q)
+    out, po = _out(ny, Cc, cplx)
+    if n and Cc:
+        L.check(L.load().emagls_resample(m.ctypes.data_as(C.c_void_p), 1 if cplx else 0, n, Cc, p, q, po))
+    if a.ndim < 2:
+        return out.reshape(-1)
+    return out.reshape(1, -1) if row else out
+
+
 def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingFilterFs, compensateDelay=False,
                    signal=None, signalFs=None, horRotAngleRad=None, *, shDefinition="real", rotationDomain="sh", pitchRad=None,
-                   rollRad=None):
-    """dependencies/binauralDecode.m:1-64 without the resampling.  Real or complex (complex-SH) signals and filters; the output
+                   rollRad=None, allowResampling=False):
+    """dependencies/binauralDecode.m:1-64.  The resampling of :12-23 (decodingFilterFs or signalFs != inFs; the rates then
+    positive integers) runs only with allowResampling=True, because its taps are our restatement of MATLAB's resample (see
+    `resample`), not checked against MATLAB; without it such a call raises NotImplementedError.  It runs on the device before
+    everything else, and compensateDelay then cuts half the resampled filters' length.  Real or complex (complex-SH) signals and filters; the output
     is real: the reference forces it and warns with the absolute sum of the discarded imaginary part (:59-64), and so does this
     function.  horRotAngleRad: a scalar (the reference's fixed yaw) or one angle per input sample (a head-tracker trajectory),
     applied as rotateYaw(sig, horRotAngleRad, shDefinition, rotationDomain); shDefinition is the basis of `sig` ('real' is the
@@ -458,8 +502,14 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
     rotateHOA_N3D (rotateSH's rotation with yaw = horRotAngleRad), each a scalar or one angle per input sample; SH signals only.
     With both None, or all zero, the call is the yaw-only one, bit for bit."""
     import warnings
-    if decodingFilterFs != inFs or (signalFs is not None and signalFs != inFs):
-        raise NotImplementedError("resampling (decodingFilterFs or signalFs != inFs) is outside the accelerated path")
+    rs_filter = decodingFilterFs != inFs
+    rs_signal = signal is not None and signalFs is not None and signalFs != inFs
+    if (rs_filter or (signalFs is not None and signalFs != inFs)) and not allowResampling:
+        raise NotImplementedError("resampling (decodingFilterFs or signalFs != inFs) is outside the accelerated path unless "
+                                  "allowResampling=True")
+    fs = None
+    if rs_filter or rs_signal:
+        fs = (_rate(inFs, "inFs"), _rate(decodingFilterFs, "decodingFilterFs"), _rate(signalFs, "signalFs") if rs_signal else _rate(inFs, "inFs"))
     in_c = np.iscomplexobj(sig)
     w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
 
@@ -488,6 +538,11 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
             if np.iscomplexobj(s):
                 raise ValueError("signal must be real")
             src = np.ascontiguousarray((s.reshape(s.shape[0], -1)[:, 0] if s.ndim > 1 else s.reshape(-1)).astype(np.float64))
+    if fs is not None and fs[2] != fs[0] and src is not None:
+        print("binauralDecode: resampling signal")                 # :14 (the resampled signal, then its first column)
+    if fs is not None and fs[1] != fs[0]:
+        print("binauralDecode: resampling decoding filter")        # :20
+        ln = _resampled_length(ln, fs[0] // math.gcd(fs[0], fs[1]), fs[1] // math.gcd(fs[0], fs[1]))
     ypr = None
     if pitchRad is not None or rollRad is not None:
         pitch, roll = _angles(pitchRad, n, "pitchRad"), _angles(rollRad, n, "rollRad")
@@ -503,11 +558,19 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
         lay = _layout(rotationDomain)
     pitch, roll = ypr or (None, None)
     nout = src.size if src is not None else n
+    if fs is not None and src is not None:
+        nout = _resampled_length(nout, fs[0] // math.gcd(fs[0], fs[2]), fs[2] // math.gcd(fs[0], fs[2]))
     out, po = _out(max(nout - skip, 0), 2, False)
     im = (C.c_double * 2)(0.0, 0.0)
-    L.check(L.load().emagls_binaural_decode_render_ypr(
-        ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, ln, 1 if compensateDelay else 0, lay, b, *_vp(yaw), *_vp(pitch),
-        *_vp(roll), *_vp(src), po, im))
+    lnf = wL.shape[0]     # (the filters' length before the resampling; ln is the one after it)
+    if fs is None:
+        L.check(L.load().emagls_binaural_decode_render_ypr(
+            ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, lnf, 1 if compensateDelay else 0, lay, b, *_vp(yaw), *_vp(pitch),
+            *_vp(roll), *_vp(src), po, im))
+    else:
+        L.check(L.load().emagls_binaural_decode_render_fs(
+            ps, 1 if in_c else 0, n, Cc, pwL, pwR, 1 if w_c else 0, lnf, 1 if compensateDelay else 0, lay, b, *_vp(yaw), *_vp(pitch),
+            *_vp(roll), *_vp(src), float(fs[0]), float(fs[1]), float(fs[2]), po, im))
     # binauralDecode.m:59-63: `if ~isreal(binauralOut)` -- whenever the accumulated result is a complex array, which it is as
     # soon as a signal or a filter is complex (MATLAB only drops an all-zero imaginary part at the end of an arithmetic
     # operation; a sum that happens to be exactly real is the one case in which the reference stays silent, and so do we)

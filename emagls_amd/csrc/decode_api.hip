@@ -1,8 +1,10 @@
-// C ABI of binauralDecode and the SH rotations (include/emagls.h: emagls_binaural_decode*, emagls_rotate_yaw, emagls_rotate_sh,
-// emagls_sh_rotation_matrix): the argument check, host staging, the work buffers and the choice of kernels, once for all ten
-// entry points.  The kernels are decode.hip's, rotate.hip's and rotate3.hip's.  No CPU fallback.
+// C ABI of binauralDecode, the SH rotations and the resampler (include/emagls.h: emagls_binaural_decode*, emagls_rotate_yaw,
+// emagls_rotate_sh, emagls_sh_rotation_matrix, emagls_resample*): the argument check, host staging, the work buffers and the
+// choice of kernels, once for the whole family.  The kernels are decode.hip's, rotate.hip's, rotate3.hip's and resample.hip's.
+// No CPU fallback.
 #include <algorithm>
 #include <initializer_list>
+#include <numeric>
 #include <vector>
 
 #include "../../include/emagls.h"
@@ -54,7 +56,7 @@ struct Scratch {   // device buffers and a pool stream of one host call, freed o
 // work buffers of the device-resident body, grown on demand and kept (released by decode_family_cache_clear); one decode at a
 // time per process, like decode.hip's plans
 struct Work {
-    enum { ROT_SIG, ROT_WL, ROT_WR, SIG2, W2L, W2R, TMP, IR, YIM, NBUF };
+    enum { RS_SIG, RS_WL, RS_WR, ROT_SIG, ROT_WL, ROT_WR, SIG2, W2L, W2R, TMP, IR, YIM, NBUF };
     std::mutex mu;
     int device = -1;
     void* p[NBUF] = {};
@@ -73,6 +75,30 @@ struct Work {
     }
 };
 Work g_work;
+
+// A sample-rate conversion of dependencies/binauralDecode.m:12-23, MATLAB's resample(x, p, q) with p / q reduced by their gcd
+struct Ratio {
+    int64_t p = 1, q = 1;
+    bool identity() const { return p == q; }
+    int64_t length(int64_t n) const { return resample_length(n, p, q); }
+};
+
+Ratio reduce_ratio(int64_t p, int64_t q) {
+    if (p < 1 || q < 1) throw Error(EMAGLS_ERR_ARG, "resample needs positive integer rates p and q");
+    const int64_t g = std::gcd(p, q);
+    const Ratio r{p / g, q / g};
+    if (std::max(r.p, r.q) > kResampleMaxRatio)
+        throw Error(EMAGLS_ERR_UNSUPPORTED, "resample supports max(p, q) <= 65536 after reduction by their gcd");
+    return r;
+}
+
+// to_fs / from_fs: sample rates given as doubles, which must be positive and integer-valued (MATLAB's resample requires it)
+Ratio rate_ratio(double to_fs, double from_fs, const char* what) {
+    auto integral = [](double f) { return std::isfinite(f) && f >= 1.0 && f <= 9.0e15 && std::floor(f) == f; };
+    if (!integral(to_fs) || !integral(from_fs))
+        throw Error(EMAGLS_ERR_ARG, std::string("resampling the ") + what + " needs positive integer-valued sample rates");
+    return reduce_ratio((int64_t)to_fs, (int64_t)from_fs);
+}
 
 bool all_zero(const double* a, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
@@ -164,13 +190,35 @@ void rotate_step(const Angles& a, int layout, bool cb, int64_t nsamp, int nch, i
     }
 }
 
-// The device-resident body of every decode entry (nsamp > 0): the rotation, the real or complex decode, and the source-signal
-// convolution of dependencies/binauralDecode.m:44-48 with its imaginary-part sums.  d_out [nout][2], nout = nsig ? nsig : nsamp,
-// without the delay cut; `cut` only moves the start of the imaginary-part sums.  Returns with st synchronised (every
-// binaural_decode_real call synchronises it).
+// The resampling of dependencies/binauralDecode.m:12-23 before everything else: the decoding filters by rf into RS_WL / RS_WR,
+// the source signal by rs into RS_SIG; len and nsig become the resampled lengths.  (g_work.mu held)
+void resample_step(const Ratio& rf, const Ratio& rs, int nch, const void*& d_wL, const void*& d_wR, bool w_c, int64_t& len,
+                   const double*& d_sig, int64_t& nsig, hipStream_t st) {
+    if (!rf.identity()) {
+        const int64_t len2 = rf.length(len);
+        void* rL = g_work.get(Work::RS_WL, esz(w_c) * (size_t)len2 * nch);
+        void* rR = g_work.get(Work::RS_WR, esz(w_c) * (size_t)len2 * nch);
+        launch_resample(d_wL, w_c, len, nch, rf.p, rf.q, rL, st);
+        launch_resample(d_wR, w_c, len, nch, rf.p, rf.q, rR, st);
+        d_wL = rL; d_wR = rR; len = len2;
+    }
+    if (nsig > 0 && !rs.identity()) {
+        const int64_t n2 = rs.length(nsig);
+        double* s2 = g_work.get<double>(Work::RS_SIG, sizeof(double) * (size_t)n2);
+        launch_resample(d_sig, false, nsig, 1, rs.p, rs.q, s2, st);
+        d_sig = s2; nsig = n2;
+    }
+}
+
+// The device-resident body of every decode entry (nsamp > 0): the resampling, the rotation, the real or complex decode, and the
+// source-signal convolution of dependencies/binauralDecode.m:44-48 with its imaginary-part sums.  d_out [nout][2], nout = the
+// resampled nsig if there is a signal, else nsamp, without the delay cut; `cut` only moves the start of the imaginary-part sums.
+// Returns with st synchronised (every binaural_decode_real call synchronises it).
 void decode_body(const void* d_in, bool in_c, int64_t nsamp, int nch, const void* d_wL, const void* d_wR, bool w_c, int64_t len, int layout,
-                 bool cb, const Angles& a, const double* d_sig, int64_t nsig, int64_t cut, double* d_out, double* imag_abs, hipStream_t st) {
+                 bool cb, const Angles& a, const double* d_sig, int64_t nsig, int64_t cut, double* d_out, double* imag_abs, hipStream_t st,
+                 const Ratio& rf = {}, const Ratio& rs = {}) {
     std::lock_guard<std::mutex> lk(g_work.mu);
+    resample_step(rf, rs, nch, d_wL, d_wR, w_c, len, d_sig, nsig, st);
     if (a.any()) rotate_step(a, layout, cb, nsamp, nch, len, d_in, in_c, d_wL, d_wR, w_c, st);
     const bool any_c = in_c || w_c, want_imag = imag_abs && any_c;
     double* stage1 = nsig > 0 ? g_work.get<double>(Work::IR, sizeof(double) * 2 * (size_t)nsamp) : d_out;
@@ -198,17 +246,29 @@ void decode_body(const void* d_in, bool in_c, int64_t nsamp, int nch, const void
     }
 }
 
-// The host decode entries: staging, the body, and the compensate_delay cut on the way back (binauralOut(del:end,:), del = len/2,
-// dependencies/binauralDecode.m:53-57): out [nout - (len/2 - 1)][2].
+// The two rate conversions of a decode: fs = {in_fs, filter_fs, signal_fs}, or null for none.  signal_fs is looked at only when
+// there is a signal (binauralDecode.m:12-17).
+void decode_ratios(const double* fs, int64_t nsig, Ratio& rf, Ratio& rs) {
+    if (!fs) return;
+    rf = rate_ratio(fs[0], fs[1], "decoding filters");
+    if (nsig > 0) rs = rate_ratio(fs[0], fs[2], "signal");
+}
+
+// The host decode entries: staging, the body, and the compensate_delay cut on the way back (binauralOut(del:end,:), del = len/2 of
+// the resampled filters, dependencies/binauralDecode.m:53-57): out [nout - (len/2 - 1)][2].
 int host_decode(const void* in, bool ic, int64_t nsamp, int64_t nch, const void* wL, const void* wR, bool wc, int64_t len, int compensate_delay,
-                int layout, int basis, const Angles& a, const double* signal, int64_t n_signal, double* out, double* imag_abs_sum) {
+                int layout, int basis, const Angles& a, const double* signal, int64_t n_signal, double* out, double* imag_abs_sum,
+                const double* fs = nullptr) {
     return guarded_call([&] {
         const int64_t nsig = signal ? n_signal : 0;
         // (without rotation and signal, the checks of emagls_binaural_decode_complex: they never looked at n_signal)
         check_args(true, {in, wL, wR, out}, nsamp, nch, len, a.any() || nsig ? n_signal : 0, layout, basis, a);
+        Ratio rf, rs;
+        decode_ratios(fs, nsig, rf, rs);
         if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
-        const int64_t nout = nsig > 0 ? nsig : nsamp;
-        const int64_t cut = (compensate_delay && len / 2 > 0) ? len / 2 - 1 : 0;
+        const int64_t len2 = rf.length(len);
+        const int64_t nout = nsig > 0 ? rs.length(nsig) : nsamp;
+        const int64_t cut = (compensate_delay && len2 / 2 > 0) ? len2 / 2 - 1 : 0;
         const int64_t rows = nout - cut;
         if (nsamp == 0) {   // the rendered impulse response is empty: so is its convolution with the signal
             if (rows > 0) std::fill(out, out + 2 * rows, 0.0);
@@ -220,7 +280,7 @@ int host_decode(const void* in, bool ic, int64_t nsamp, int64_t nch, const void*
         const void* d_wR = s.put((const char*)wR, esz(wc) * (size_t)len * nch);
         double* d_out = s.get<double>(sizeof(double) * 2 * nout);
         decode_body(d_in, ic, nsamp, (int)nch, d_wL, d_wR, wc, len, layout, basis == EMAGLS_BASIS_COMPLEX, s.put(a), s.put(signal, (size_t)nsig),
-                    nsig, cut, d_out, imag_abs_sum, s.st);
+                    nsig, cut, d_out, imag_abs_sum, s.st, rf, rs);
         if (rows > 0) {
             HIP_CHECK(hipMemcpyAsync(out, d_out + cut, sizeof(double) * rows, hipMemcpyDefault, s.st));
             HIP_CHECK(hipMemcpyAsync(out + rows, d_out + nout + cut, sizeof(double) * rows, hipMemcpyDefault, s.st));
@@ -250,6 +310,7 @@ int host_rotate(const void* in, bool ic, int64_t nsamp, int64_t nch, int layout,
 void emagls::decode_family_cache_clear() {
     decode_cache_clear();
     rotate3_cache_clear();
+    resample_cache_clear();
     std::lock_guard<std::mutex> lk(g_work.mu);
     g_work.release();
 }
@@ -286,23 +347,85 @@ int emagls_binaural_decode_render(const void* in, int in_is_complex, int64_t nsa
                                              yaw, n_yaw, nullptr, 0, nullptr, 0, signal, n_signal, out, imag_abs_sum);
 }
 
-int emagls_binaural_decode_render_ypr_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
-                                             const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
-                                             int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
-                                             const double* d_signal, int64_t n_signal, double* d_out, double* imag_abs_sum, void* stream) {
+int emagls_binaural_decode_render_fs(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                     int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
+                                     int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll,
+                                     const double* signal, int64_t n_signal, double in_fs, double filter_fs, double signal_fs, double* out,
+                                     double* imag_abs_sum) {
+    const Angles a = host_angles({yaw, n_yaw, pitch, n_pitch, roll, n_roll});
+    const bool plain_real = !a.any() && !(signal && n_signal) && !in_is_complex && !filters_are_complex;
+    const double fs[3] = {in_fs, filter_fs, signal_fs};
+    return host_decode(in, in_is_complex != 0, nsamp, nch, wL, wR, filters_are_complex != 0, len, compensate_delay, layout, basis, a, signal,
+                       n_signal, out, plain_real ? nullptr : imag_abs_sum, fs);
+}
+
+static int device_decode(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL, const void* d_wR,
+                         int filters_are_complex, int64_t len, int layout, int basis, const Angles& a, const double* d_signal, int64_t n_signal,
+                         const double* fs, double* d_out, double* imag_abs_sum, void* stream) {
     return guarded_call([&] {
-        const Angles a{d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll};
         check_args(true, {d_in, d_wL, d_wR, d_out}, nsamp, nch, len, n_signal, layout, basis, a);
-        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
         const int64_t nsig = d_signal ? n_signal : 0;
+        Ratio rf, rs;
+        decode_ratios(fs, nsig, rf, rs);
+        if (imag_abs_sum) imag_abs_sum[0] = imag_abs_sum[1] = 0.0;
         hipStream_t st = (hipStream_t)stream;
         if (nsamp == 0) {
-            if (nsig > 0) HIP_CHECK(hipMemsetAsync(d_out, 0, sizeof(double) * 2 * nsig, st));
+            if (nsig > 0) HIP_CHECK(hipMemsetAsync(d_out, 0, sizeof(double) * 2 * rs.length(nsig), st));
             HIP_CHECK(hipStreamSynchronize(st));
             return;
         }
         decode_body(d_in, in_is_complex != 0, nsamp, (int)nch, d_wL, d_wR, filters_are_complex != 0, len, layout, basis == EMAGLS_BASIS_COMPLEX,
-                    a, d_signal, nsig, 0, d_out, imag_abs_sum, st);
+                    a, d_signal, nsig, 0, d_out, imag_abs_sum, st, rf, rs);
+    });
+}
+
+int emagls_binaural_decode_render_ypr_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                             const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
+                                             int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
+                                             const double* d_signal, int64_t n_signal, double* d_out, double* imag_abs_sum, void* stream) {
+    return device_decode(d_in, in_is_complex, nsamp, nch, d_wL, d_wR, filters_are_complex, len, layout, basis,
+                         {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, d_signal, n_signal, nullptr, d_out, imag_abs_sum, stream);
+}
+
+int emagls_binaural_decode_render_fs_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                            const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
+                                            int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
+                                            const double* d_signal, int64_t n_signal, double in_fs, double filter_fs, double signal_fs,
+                                            double* d_out, double* imag_abs_sum, void* stream) {
+    const double fs[3] = {in_fs, filter_fs, signal_fs};
+    return device_decode(d_in, in_is_complex, nsamp, nch, d_wL, d_wR, filters_are_complex, len, layout, basis,
+                         {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, d_signal, n_signal, fs, d_out, imag_abs_sum, stream);
+}
+
+int64_t emagls_resample_length(int64_t nsamp, int64_t p, int64_t q) {
+    if (nsamp < 0 || p < 1 || q < 1) return -1;
+    const int64_t g = std::gcd(p, q);
+    return resample_length(nsamp, p / g, q / g);
+}
+
+int emagls_resample(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int64_t p, int64_t q, void* out) {
+    return guarded_call([&] {
+        if (!in || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        if (nsamp < 0 || nch < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        const Ratio r = reduce_ratio(p, q);
+        if (nsamp == 0) return;
+        const bool c = in_is_complex != 0;
+        const size_t bout = esz(c) * (size_t)r.length(nsamp) * nch;
+        Scratch s;
+        const void* d_in = s.put((const char*)in, esz(c) * (size_t)nsamp * nch);
+        void* d_out = s.get(bout);
+        launch_resample(d_in, c, nsamp, nch, r.p, r.q, d_out, s.st);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDefault, s.st));
+        HIP_CHECK(hipStreamSynchronize(s.st));
+    });
+}
+
+int emagls_resample_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, int64_t p, int64_t q, void* d_out, void* stream) {
+    return guarded_call([&] {
+        if (!d_in || !d_out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        if (nsamp < 0 || nch < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        const Ratio r = reduce_ratio(p, q);
+        launch_resample(d_in, in_is_complex != 0, nsamp, nch, r.p, r.q, d_out, (hipStream_t)stream);
     });
 }
 

@@ -218,8 +218,15 @@ void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_ba
 // M [(N+1)^2 x (N+1)^2] column-major, out_row = in_row M^T; the same device code as launch_rotate3
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st);
 void rotate3_cache_clear();
+// ---- resample.hip
+constexpr int64_t kResampleMaxRatio = 65536;   // the largest max(p, q) after reduction
+int64_t resample_length(int64_t n, int64_t p, int64_t q);   // ceil(n p / q)
+// MATLAB's resample(x, p, q) of each column of in [nch][n] (real, or interleaved complex): out [nch][ceil(n p / q)], same type.
+// p, q reduced, both >= 1; max(p, q) > kResampleMaxRatio: Error(EMAGLS_ERR_UNSUPPORTED)
+void launch_resample(const void* in, bool cplx_in, int64_t n, int64_t nch, int64_t p, int64_t q, void* out, hipStream_t st);
+void resample_cache_clear();
 
-// ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables and the decode family's work buffers
+// ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables, resample.hip's taps and the decode family's work buffers
 void decode_family_cache_clear();
 
 void filter_channels_by_order(const double* sig, int64_t n_in, int64_t n, int C, const double* ir /* [nOrd][len] */, int nOrd, int64_t len,

@@ -9,6 +9,7 @@
  *   emagls_get_emagls_filters_from_atf <-  lib/getEMagLsFiltersFromAtf.m:1
  *   emagls_get_emagls_filters_ema_in_ch <- lib/getEMagLsFiltersEMAinCH.m:1-2  (default chFunction @getCH, dependencies/getCH.m)
  *   emagls_binaural_decode[_complex]   <-  dependencies/binauralDecode.m:1-2 (core loop :33-42,53-64)
+ *   emagls_resample                    <-  resample(x, p, q) (Signal Processing Toolbox, call sites dependencies/binauralDecode.m:15,21-22)
  *   emagls_sh_basis                    <-  getSH (polarch/Spherical-Harmonic-Transform, call site lib/getLsFilters.m:30)
  *   emagls_modal_bn                    <-  sphModalCoeffs (polarch/Array-Response-Simulator, call site dependencies/getSMAIRMatrix.m:107)
  *
@@ -189,7 +190,8 @@ int emagls_binaural_decode_device(const void* d_in, int in_is_complex, int64_t n
 int emagls_rotate_yaw(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int layout, int basis, const double* yaw,
                       int64_t n_yaw, void* out);
 
-/* dependencies/binauralDecode.m:1-64 without the resampling: emagls_binaural_decode_complex's arguments, plus
+/* dependencies/binauralDecode.m:1-64 without the resampling (emagls_binaural_decode_render_fs adds it): emagls_binaural_decode_complex's
+ * arguments, plus
  *  - the yaw rotation of the input (layout, basis, yaw [n_yaw]; n_yaw = 0: none, 1: one fixed angle, applied to the decoding
  *    filters, nsamp: one angle per input sample, applied to the signal), and
  *  - the source-signal convolution of :44-48 (signal [n_signal], the first column of the reference's `signal`; NULL or
@@ -239,6 +241,43 @@ int emagls_binaural_decode_render_ypr_device(const void* d_in, int in_is_complex
                                              const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
                                              int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
                                              const double* d_signal, int64_t n_signal, double* d_out, double* imag_abs_sum, void* stream);
+
+/* Resampling with the semantics of MATLAB's resample(x, p, q) at its defaults N = 10, bta = 5 (the calls of
+ * dependencies/binauralDecode.m:12-23).  OWN RESTATEMENT of resample.m: p / q is reduced by their gcd;
+ * m = max(p, q), a Kaiser-windowed (bta 5) sinc of 20 m + 1 taps with cut-off 1/(2m), scaled to p / sum; the polyphase filter
+ * applied to each column with the alignment of resample.m.  MATLAB's own tap values are not pinned.
+ * emagls_resample_length: ceil(nsamp p / q); -1 when nsamp < 0 or p or q < 1. */
+int64_t emagls_resample_length(int64_t nsamp, int64_t p, int64_t q);
+
+/* in [nsamp x nch] real or interleaved complex as flagged (complex: the real taps applied to both parts); out
+ * [ceil(nsamp p / q) x nch] of the same type.  p, q >= 1 (else EMAGLS_ERR_ARG); max(p, q) > 65536 after reduction is
+ * EMAGLS_ERR_UNSUPPORTED; p == q copies.  The taps of a ratio are designed once and kept per device (emagls_cache_clear frees
+ * them). */
+int emagls_resample(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, int64_t p, int64_t q, void* out);
+
+/* emagls_resample on device buffers, enqueued on `stream` (hipStream_t, NULL = default) and not synchronised. */
+int emagls_resample_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, int64_t p, int64_t q, void* d_out,
+                           void* stream);
+
+/* emagls_binaural_decode_render_ypr plus the three rates of dependencies/binauralDecode.m:1-2 (positive, integer-valued doubles,
+ * else EMAGLS_ERR_ARG): the decoding filters are resampled from filter_fs to in_fs (len' = ceil(len in_fs / filter_fs) taps) and
+ * the signal from signal_fs to in_fs (n_signal' = ceil(n_signal in_fs / signal_fs) samples; signal_fs is looked at only when there
+ * is a signal), on the device, before the rotation (:12-23).  out [nout x 2], nout = (n_signal > 0 ? n_signal' : nsamp) -
+ * (compensate_delay ? len'/2 - 1 : 0).  With filter_fs == in_fs and signal_fs == in_fs this is emagls_binaural_decode_render_ypr,
+ * bit for bit. */
+int emagls_binaural_decode_render_fs(const void* in, int in_is_complex, int64_t nsamp, int64_t nch, const void* wL, const void* wR,
+                                     int filters_are_complex, int64_t len, int compensate_delay, int layout, int basis, const double* yaw,
+                                     int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll,
+                                     const double* signal, int64_t n_signal, double in_fs, double filter_fs, double signal_fs, double* out,
+                                     double* imag_abs_sum);
+
+/* emagls_binaural_decode_render_fs on device buffers, as emagls_binaural_decode_render_ypr_device: d_out [nout x 2], nout =
+ * n_signal > 0 ? n_signal' : nsamp, without the delay cut. */
+int emagls_binaural_decode_render_fs_device(const void* d_in, int in_is_complex, int64_t nsamp, int64_t nch, const void* d_wL,
+                                            const void* d_wR, int filters_are_complex, int64_t len, int layout, int basis, const double* d_yaw,
+                                            int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll,
+                                            const double* d_signal, int64_t n_signal, double in_fs, double filter_fs, double signal_fs,
+                                            double* d_out, double* imag_abs_sum, void* stream);
 
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's

@@ -11,6 +11,7 @@
 // by tests/test_mex_gateway.py (tests/mexstub/).  It is a thin adapter: argument checks, pointer hand-over, mxArray
 // allocation, error forwarding.
 #include <cctype>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -70,6 +71,7 @@ void at_exit() { emagls_cache_clear(); }
 // emagls_mex('emainch' | 'emainsh', hL, hR, azi, zen, micRadius, micAzi, order, fs, len, shDefinition)
 // emagls_mex('magls_dc' | 'emagls_dc' | 'emagls2_dc', <the arguments of 'magls' / 'emagls' / 'emagls2'>, applyDiffusenessConst)
 // emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain, pitchRad, rollRad])   real or complex in / filters; [out, imagAbsSum] = ...
+// emagls_mex('resample', x, p, q)   MATLAB's resample(x, p, q) (N = 10, bta = 5): a row vector along its length, else per column
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
 // emagls_mex('rotate3', in, yawRad, pitchRad, rollRad[, shDefinition])   three-axis rotation of an SH signal (orders 0-15)
 // emagls_mex('shrotmtx', order, yawRad, pitchRad, rollRad[, shDefinition])   its matrix M: out = in * M.'
@@ -128,6 +130,27 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                                          basis, yaw, nyaw, pitch, npitch, roll, nroll, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
         if (rc) fail(rc);
         if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
+        return;
+    }
+    if (c == "resample") {
+        // y = emagls_mex('resample', x, p, q): emagls_resample; p and q positive integers
+        if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "resample needs (x, p, q)");
+        const mwSize M = mxGetM(prhs[1]), N = mxGetN(prhs[1]);
+        const bool row = M == 1, ic = mxIsComplex(prhs[1]);
+        const mwSize n = row ? N : M, ch = row ? 1 : N;
+        if (!mxIsDouble(prhs[1])) mexErrMsgIdAndTxt("eMagLS:arg", "x must be a double array");
+        auto rate = [](const mxArray* a, const char* what) -> int64_t {
+            const double v = (mxIsDouble(a) && !mxIsComplex(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
+            if (!(v >= 1.0 && v <= 9.0e15 && v == std::floor(v))) mexErrMsgIdAndTxt("eMagLS:arg", "%s must be a positive integer", what);
+            return (int64_t)v;
+        };
+        const int64_t p = rate(prhs[2], "p"), q = rate(prhs[3], "q");
+        const mwSize ny = (mwSize)emagls_resample_length((int64_t)n, p, q);
+        plhs[0] = row ? mxCreateDoubleMatrix(1, ny, ic ? mxCOMPLEX : mxREAL) : mxCreateDoubleMatrix(ny, ch, ic ? mxCOMPLEX : mxREAL);
+        if (n && ch) {
+            const int rc = emagls_resample(in_ptr(prhs[1]), ic, n, ch, p, q, out_ptr(plhs[0]));
+            if (rc) fail(rc);
+        }
         return;
     }
     if (c == "rotate") {
