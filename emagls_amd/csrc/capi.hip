@@ -3305,7 +3305,7 @@ int emagls_fp64_peak_tflops(int which, double* tflops) {
 int emagls_self_test(int which, double* max_err) {
     return guarded([&] {
         if (!max_err || which < 0 || which > 2) throw Error(EMAGLS_ERR_ARG, "invalid argument");
-        *max_err = which == 0 ? reg_reduce_selftest() : gram_tile_selftest(which == 2);
+        *max_err = which == 0 ? reg_contract_selftest() : gram_tile_selftest(which == 2);
     });
 }
 

@@ -9,16 +9,14 @@
 // per workgroup, two workgroups per CU, 29 CUs per design, four barriers and a two-hop exchange per bin; its vector ALUs
 // were busy 24 % of the time while the launch held 232 CUs (profiles/r04_pmc.md).
 //
-// Here a LANE owns ONE direction and all NU units of it: x_du (17 values for the em32) and the bin's E_u, O_u (68 values) live in
-// registers.  Per bin a wave
-//   * p phase:   p_e[d] = sum_u (wE_e[u] E_u + wO_e[u] O_u)  with  wE = w'[row A] + w'[row B], wO = w'[row A] - w'[row B]  read as
-//                LDS broadcasts -- no cross-lane step at all;
-//   * t = |H| p/|p| in the lane;
-//   * partial:   t_e conj(E_u), t_e conj(O_u) (136 values per lane) summed over the wave's 64 directions by a halving
-//                reduction: v_permlane32_swap / v_permlane16_swap exchange half of the values with the lane 32 / 16 away (one
-//                instruction per word, no select), two DPP steps inside the rows, an all-reduce inside the quads -- 9 values
-//                per lane are left, each total owned by one quad;
-//   * the four waves' partials are summed through 4.6 KB of LDS, turned into microphone rows (u = uE +- uO) and published as tagged
+// Here a QUAD of lanes owns two directions ("sets") and all NU units of them, each lane the units u = x (mod 4) of both: x_du (nine
+// slots per lane for the em32's 17 units) and the bin's E_u, O_u (36 values) live in registers.  Per bin a wave
+//   * p phase:   p_e[d] = sum_u (wE_e[u] E_u + wO_e[u] O_u)  with  wE = w'[row A] + w'[row B], wO = w'[row A] - w'[row B]  read from
+//                LDS, each lane over its own units, then summed over the quad by two DPP steps;
+//   * t = |H| p/|p| in every lane of the quad, for the lane's ear;
+//   * partial:   t_e conj(E_u), t_e conj(O_u) summed over the wave's 32 directions on the matrix pipe (rg_contract: 40
+//                v_mfma_f64_4x4x4_4b, the contraction over the quads built into the instruction, two DPP rotations for its four blocks);
+//   * the waves' partials are summed through LDS, turned into microphone rows (u = uE +- uO) and published as tagged
 //     granules; every workgroup of the design reads ALL partials of the bin (one hop: 11 workgroups x 2 KB at 2702 directions) and
 //     sums them in workgroup order;
 //   * the SAME waves then evaluate E, O of the next bin (1020 fused operations per lane at 20 orders) while the partials of the
@@ -42,29 +40,68 @@ namespace {
 
 constexpr int RG_MLD = 36;      // row stride of M~ in LDS (16 dwords mod 64)
 
-// ---- halving steps of the wave reduction.  Each takes two values per lane and returns ONE: half of the lanes get the sum of `a`
-// over the lane pair, the other half the sum of `b`.
-// lanes 0-31: a[l] + a[l + 32]; lanes 32-63: b[l - 32] + b[l]
-__device__ __forceinline__ double halve32(double a, double b) {
-    const unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
-    const unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
-    const auto lo = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);   // lanes 32-63 of the first <-> lanes 0-31 of the second
-    const auto hi = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-}
-// even rows (of 16 lanes): a[l] + a[l + 16]; odd rows: b[l - 16] + b[l]
-__device__ __forceinline__ double halve16(double a, double b) {
-    const unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
-    const unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
-    const auto lo = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);   // odd rows of the first <-> even rows of the second
-    const auto hi = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-}
-// inside a row: lanes with keep_a get a[l] + a[perm(l)], the others b[l] + b[perm(l)]; perm (a DPP control, its own inverse) maps the
-// keep_a lanes onto the others
-template <int CTRL> __device__ __forceinline__ double halve_row(double a, double b, bool keep_a) {
-    const double x = keep_a ? a : b, y = keep_a ? b : a;
-    return x + dpp_d<CTRL>(y);
+// ---- the quad layout: lane x = lane & 3 of a quad holds two directions of the quad ("sets") and, of each, the units u = x (mod 4).
+// Unit slot i of a lane: slots 0-3 set 0, units 4 i + x; slots 4-7 set 1, the same units; slot 8 the units 16, 17 of both sets
+// (set x >> 1, unit 16 + (x & 1)).
+constexpr int DPP_ROR4 = 0x124, DPP_ROR8 = 0x128;   // row_ror:4 / row_ror:8 (rotation inside each 16 lanes)
+__device__ __forceinline__ int rg_slot_set(int i, int x) { return i < 4 ? 0 : i < 8 ? 1 : x >> 1; }
+__device__ __forceinline__ int rg_slot_unit(int i, int x) { return i < 8 ? 4 * (i & 3) + x : 16 + (x & 1); }
+
+// The wave's partial  sum_d t_e(d) conj(g_u(d))  (g = E_u, O_u; the wave's 32 directions) on v_mfma_f64_4x4x4_4b.  Lane l = x + 4 b + 16 y
+// supplies A_b[i = x][k = y], B_b[k = y][j = x] and receives D_b[i = y][j = x] (gram_chol.hip): the quad (b, y) is direction k of block b,
+// the row i the component (ear, re / im) of the partial, the column j the lane's unit.  With t = t_e of the lane's ear e = x >> 1
+//     Re(t conj g) = t.re Re g + t.im Im g,    Im(t conj g) = t.im Re g - t.re Im g,
+// so lane x supplies (x & 1 ? t.im : t.re) against Re g and (x & 1 ? -t.re : t.im) against Im g.  Slots i and i + 4 (the two sets, same
+// units) accumulate in one register; slot 8 (both sets in one register) takes one pass per set with the other set's columns masked, and
+// its two sets are added at the end.  Two row rotations sum the four blocks; the lanes with b = 0 write the wave's partial to
+// wp[unit][E / O][ear][re / im].  ts: t of the lane's ear for the two sets; slot8: slot 8 holds units (wave-uniform).
+template <int NUL>
+__device__ __forceinline__ void rg_contract(const cplx (&E)[NUL], const cplx (&O)[NUL], const cplx (&ts)[2], int lane, bool slot8, double* wp) {
+    static_assert(NUL == 9, "quad layout of 18 units");
+    const int x = lane & 3;
+    double ar[2], ai[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) { ar[s] = (x & 1) ? ts[s].y : ts[s].x; ai[s] = (x & 1) ? -ts[s].x : ts[s].y; }
+    double aE[5], aO[5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) { aE[r] = 0.0; aO[r] = 0.0; }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {   // (eight independent accumulators between two instructions on one)
+            const double a = c ? ai[s] : ar[s];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                aE[r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, c ? E[4 * s + r].y : E[4 * s + r].x, aE[r], 0, 0, 0);
+                aO[r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, c ? O[4 * s + r].y : O[4 * s + r].x, aO[r], 0, 0, 0);
+            }
+        }
+    if (slot8) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const bool mine = (x >> 1) == s;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const double a = c ? ai[s] : ar[s];
+                aE[4] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, mine ? (c ? E[8].y : E[8].x) : 0.0, aE[4], 0, 0, 0);
+                aO[4] = __builtin_amdgcn_mfma_f64_4x4x4f64(a, mine ? (c ? O[8].y : O[8].x) : 0.0, aO[4], 0, 0, 0);
+            }
+        }
+    }
+    const int nacc = slot8 ? 5 : 4;
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        if (r >= nacc) break;
+        aE[r] += dpp_d<DPP_ROR4>(aE[r]); aE[r] += dpp_d<DPP_ROR8>(aE[r]);
+        aO[r] += dpp_d<DPP_ROR4>(aO[r]); aO[r] += dpp_d<DPP_ROR8>(aO[r]);
+    }
+    if (slot8) { aE[4] += dpp_d<DPP_XOR2>(aE[4]); aO[4] += dpp_d<DPP_XOR2>(aO[4]); }   // (set 1's columns onto set 0's)
+    if ((lane & 12) == 0) {
+        const int y = lane >> 4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { wp[8 * (4 * r + x) + y] = aE[r]; wp[8 * (4 * r + x) + 4 + y] = aO[r]; }
+        if (slot8 && x < 2) { wp[8 * (16 + x) + y] = aE[4]; wp[8 * (16 + x) + 4 + y] = aO[4]; }
+    }
 }
 
 // E_u, O_u of GS unit slots accumulated in place (synth_group's schedule: two terms per pass, the coefficients of the next pass
@@ -133,16 +170,17 @@ __device__ __forceinline__ void rg_wait_loads(u32x4_t (&g)[RG_POLL]) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(g[4]), "+v"(g[5]), "+v"(g[6]), "+v"(g[7]), "+v"(g[8]), "+v"(g[9]),
                  "+v"(g[10]), "+v"(g[11]) :: "memory");
 }
+constexpr int RG_NUL = 9;   // unit slots per lane: designs of up to 18 units (the em32: 15 antipodal pairs + 2 single capsules)
 constexpr int RG_NEX = 4 * PS_CMAX;   // doubles a workgroup publishes per bin: [ear][row (32, zero beyond the microphones)][re / im]
 constexpr int RG_SVC = 256;           // threads that serve the workgroup: exchange, M phase, M~ staging (waves 0-3)
 
-// NUL: unit slots per lane (a direction's units are split between the two waves of a pair: 2 NUL >= units); NW: waves per workgroup
+// NUL: unit slots per lane (the quad layout above: 2 NUL >= units); NW: waves per workgroup
+// (three waves per SIMD, i.e. at most 168 registers: three 4-wave workgroups share a CU)
 template <int NUL, int NW>
-__global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs* __restrict__ args, int n, int nWG, int spread, int prio) {
-    constexpr int NT = 64 * NW, DPW = 32 * NW, NB = NW / 2;   // threads, directions and 64-direction blocks of a workgroup
-    constexpr int NU2 = 2 * NUL;            // unit slots of a direction
-    constexpr int NCH = (NUL + 1) / 2;      // chunks of two slots in the wave reduction
-    constexpr int NVW = 16 * NCH;           // values of a wave's partial: [slot][E / O][ear][re / im], padded to whole chunks
+__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) sweep_reg_kernel(const HalfSweepArgs* __restrict__ args, int n, int nWG, int spread, int prio) {
+    constexpr int NT = 64 * NW, DPW = 32 * NW;   // threads and directions of a workgroup
+    constexpr int NU2 = 2 * NUL;            // units of a design at most
+    constexpr int NVW = 8 * NU2;            // values of a wave's partial: [unit][E / O][ear][re / im]
     constexpr int GA = (NUL + 1) / 2, GB = NUL - GA;   // slot groups of the synthesis (9: 5, 4)
     static_assert(GB >= 1 && NW % 2 == 0 && NT >= RG_SVC, "layout");
     extern __shared__ __attribute__((aligned(16))) char dyn[];
@@ -152,8 +190,7 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
     cplx* WO = WE + 2 * NU2;                                         // [2][NU2]      w'[row A] - w'[row B]
     double* vt = reinterpret_cast<double*>(WO + 2 * NU2);            // [2][2][32][2] totals of the previous bin in microphone rows: the sums over the even and over the odd workgroups
     double* wpart = vt + 2 * RG_NEX;                                 // [NW][NVW]     the waves' partials
-    double* pp = wpart + NW * NVW;                                   // [NW][4][64]   a wave's share of p (its half of the units): [ear][re / im][lane]
-    double* xs = pp + NW * 256;                                      // [NUL][NT]     2 cos(direction, unit): a lane reads its own column
+    double* xs = wpart + NW * NVW;                                   // [NUL][NT]     2 cos(direction, unit): a lane reads its own column
     __shared__ int s_abort, s_local;
 
     // block -> (XCD, slot) -> (design, member): design j lives on XCD j % 8, the (j / 8)-th design there.  (One design's workgroups
@@ -195,29 +232,32 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
     const gu64_t xcc_ll = part_ll + (size_t)2 * nWG * RG_NEX * 2;    // [nWG]
     if (tid == 0) { s_abort = 0; s_local = 0; }
     const int d0 = member * DPW;
-    // thread -> direction of the workgroup: wave pair q = wave / 2 takes the directions 64 q .. 64 q + 63 (lane = direction), wave
-    // parity h the unit slots h NUL .. h NUL + NUL - 1
-    auto dir_of = [&](int t) __attribute__((always_inline)) { return d0 + 64 * (t >> 7) + (t & 63); };
+    // thread -> directions of the workgroup: wave w takes the directions 32 w .. 32 w + 31, the quad q = lane / 4 of it the directions
+    // 32 w + q (set 0) and 32 w + 16 + q (set 1); lane x = lane & 3 of the quad the units x, x + 4, ... of both (rg_slot_set / _unit)
+    auto dir_of = [&](int t, int s) __attribute__((always_inline)) { return d0 + 32 * (t >> 6) + 16 * s + ((t & 63) >> 2); };
 
-    // ---- twice the cosine of the angle between the lane's direction and the (first) microphone of each of its units, kept in LDS (a
-    // lane reads back only its own column, a few values at a time)
+    // ---- twice the cosine of the angle between the direction and the (first) microphone of each of the lane's (set, unit) slots, kept
+    // in LDS (a lane reads back only its own column, a few values at a time)
     {
         const size_t ncplx = (size_t)2 * SY_NORD + PS_CMAX * RG_MLD + 4 * NU2;
         for (size_t i = tid; i < ncplx; i += NT) ring[i] = mk(0, 0);
-        for (int i = tid; i < 2 * RG_NEX + NW * NVW + NW * 256; i += NT) vt[i] = 0.0;
-        const int dgi = dir_of(tid) < D ? dir_of(tid) : D - 1;
-        double sd, cd;
-        sincos(a.dir_zen[dgi], &sd, &cd);
-        const double daz = a.dir_azi[dgi];
+        for (int i = tid; i < 2 * RG_NEX + NW * NVW; i += NT) vt[i] = 0.0;
+        double sd[2], cd[2], daz[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int dgi = dir_of(tid, s) < D ? dir_of(tid, s) : D - 1;
+            sincos(a.dir_zen[dgi], &sd[s], &cd[s]);
+            daz[s] = a.dir_azi[dgi];
+        }
 #pragma unroll 1
         for (int i = 0; i < NUL; ++i) {
-            const int u = ((tid >> 6) & 1) * NUL + i;
+            const int u = rg_slot_unit(i, tid & 3), s = rg_slot_set(i, tid & 3);
             double v = 0.0;
             if (u < nun) {
                 const int jm = smap[u < npr ? 2 * u : 2 * npr + (u - npr)];
                 double sm, cm;
                 sincos(a.mic_zen ? a.mic_zen[jm] : 1.5707963267948966, &sm, &cm);
-                v = fma(sd * sm, cos(daz - a.mic_azi[jm]), cd * cm);
+                v = fma((s ? sd[1] : sd[0]) * sm, cos((s ? daz[1] : daz[0]) - a.mic_azi[jm]), (s ? cd[1] : cd[0]) * cm);
                 v = 2.0 * fmin(1.0, fmax(-1.0, v));   // (2x: the factor of the Chebyshev recurrence)
             }
             xs[i * NT + tid] = v;
@@ -247,12 +287,13 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
 #pragma unroll
         for (int i = 0; i < NLM; ++i) ms[r * RG_MLD + c0 + i] = (r < C && c0 + i < C) ? mReg[i] : mk(0, 0);
     };
+    // |H| of the lane's ear (x >> 1) for its two sets
     double hCur[2], hNext[2] = {0.0, 0.0};
     auto fetch_h = [&](int kb, double (&h)[2], int t) __attribute__((always_inline)) {
         const int kbg = (kb < P ? kb : P - 1) - kabs0;
-        const int dgi = dir_of(t) < D ? dir_of(t) : D - 1;
-        h[0] = (Habs + (int64_t)kbg * ldH)[dgi];
-        h[1] = (Habs + ((int64_t)(P - kabs0) + kbg) * ldH)[dgi];
+        const gcd_t He = Habs + ((int64_t)((t >> 1) & 1) * (P - kabs0) + kbg) * ldH;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) h[s] = He[dir_of(t, s) < D ? dir_of(t, s) : D - 1];
     };
     fetch_h(kfirst, hCur, tid);
     if (tid < RG_SVC) { fetch_m(kfirst, tid); stage_m(tid); }
@@ -283,8 +324,8 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
     const bool local = s_local != 0;
     if (s_abort) return;
 
-    // ---- operand of one bin: E_u, O_u of the lane's direction, the wave's half of the units
-    const bool last_slot_used = ((tid >> 6) & 1) * NUL + NUL - 1 < nun || GB < 2;   // (wave-uniform)
+    // ---- operand of one bin: E_u, O_u of the lane's slots
+    const bool slot8 = nun > 16 || GB < 2;   // (uniform: slot 8 holds units 16, 17)
     cplx E[NUL], O[NUL];
 #pragma unroll
     for (int u = 0; u < NUL; ++u) { E[u] = mk(0, 0); O[u] = mk(0, 0); }
@@ -302,9 +343,8 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
             const double* xcol = xs + launder(tid);
             synth_units<0, GA, NUL, NT>(xcol, E, O, bs, nord_pad);
             __builtin_amdgcn_sched_barrier(0);
-            // (the em32's 17 units: the second wave of a pair holds 8 -- its last slot stays zero and is skipped here, in the p phase's
-            // weights (zero) and in the wave reduction)
-            if (last_slot_used) synth_units<GA, GB, NUL, NT>(xcol, E, O, bs, nord_pad);
+            // (up to 16 units: slot 8 stays zero and is skipped here, in the p phase and in the contraction)
+            if (slot8) synth_units<GA, GB, NUL, NT>(xcol, E, O, bs, nord_pad);
             else synth_units<GA, GB - 1, NUL, NT>(xcol, E, O, bs, nord_pad);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -382,75 +422,48 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
         RSTAMP(3);
         const bool svc = launder(tid) < RG_SVC;
         if (svc) fetch_m(kb, launder(tid));      // M~ of the next iteration: requested here, staged behind the p phase (which covers the round trip)
-        // ---- p = w'(kb-1,:) g^T: this wave's units, then the sum with the partner wave's;  t = |H| p/|p|
-        cplx t0, t1;
+        // ---- p = w'(kb-1,:) g^T: the lane's units of both sets, summed over the quad;  t = |H| p/|p| of the lane's ear
+        cplx ts[2];
         {
             const int t = launder(tid);
-            const int wave = t >> 6, lane = t & 63;
-            const cplx* we = WE + (wave & 1) * NUL, *wo = WO + (wave & 1) * NUL;
-            cplx p0 = mk(0, 0), p1 = mk(0, 0);
+            const int x = t & 3;
+            cplx p[2][2];   // [set][ear]
 #pragma unroll
-            for (int u = 0; u < NUL; ++u) {
-                if (u == NUL - 1 && !last_slot_used) continue;
-                const cplx we0 = we[u], wo0 = wo[u], we1 = we[NU2 + u], wo1 = wo[NU2 + u];
-                cfma(p0, we0, E[u]); cfma(p0, wo0, O[u]);
-                cfma(p1, we1, E[u]); cfma(p1, wo1, O[u]);
-            }
-            double* mine = pp + wave * 256 + lane;
-            mine[0] = p0.x; mine[64] = p0.y; mine[128] = p1.x; mine[192] = p1.y;
-            if (svc) stage_m(t);
-            __syncthreads();  // Bp: the partner wave's share of p
-            RSTAMP(8);
-            const double* theirs = pp + (wave ^ 1) * 256 + lane;
-            p0.x += theirs[0]; p0.y += theirs[64]; p1.x += theirs[128]; p1.y += theirs[192];
-            const bool dvalid = dir_of(t) < D;
-            t0 = dvalid ? unit_phase(hCur[0], p0, nyq) : mk(0, 0);
-            t1 = dvalid ? unit_phase(hCur[1], p1, nyq) : mk(0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- this wave's partial  t conj(E_u), t conj(O_u)  summed over its 64 directions
-        {
-            const int t = launder(tid);
-            const int lane = t & 63;
-            const bool keep8 = (lane & 8) == 0, keep4 = (lane & 4) == 0;
-            // two unit slots (sixteen values: slot, E / O, ear, re / im) at a time: four halving steps leave ONE register whose lane l
-            // holds the sum over sixteen lanes of value 16 c + (l >> 2), the all-reduce inside the quad completes it
-            double r[NCH];
+            for (int s = 0; s < 2; ++s) { p[s][0] = mk(0, 0); p[s][1] = mk(0, 0); }
 #pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-                if (NUL % 2 == 1 && c == NCH - 1 && !last_slot_used) { r[c] = 0.0; continue; }   // (a chunk of the unused slot alone)
-                double v[16];   // value j = 8 (slot & 1) + 4 eo + 2 e + ri
+            for (int r = 0; r < 4; ++r) {
+                const int u = 4 * r + x;
+                const cplx we0 = WE[u], wo0 = WO[u], we1 = WE[NU2 + u], wo1 = WO[NU2 + u];
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    if (2 * c + s < NUL) {
-                        const cplx gE = E[2 * c + s < NUL ? 2 * c + s : 0], gO = O[2 * c + s < NUL ? 2 * c + s : 0];
-                        v[8 * s + 0] = fma(t0.x, gE.x, t0.y * gE.y); v[8 * s + 1] = fma(t0.y, gE.x, -(t0.x * gE.y));
-                        v[8 * s + 2] = fma(t1.x, gE.x, t1.y * gE.y); v[8 * s + 3] = fma(t1.y, gE.x, -(t1.x * gE.y));
-                        v[8 * s + 4] = fma(t0.x, gO.x, t0.y * gO.y); v[8 * s + 5] = fma(t0.y, gO.x, -(t0.x * gO.y));
-                        v[8 * s + 6] = fma(t1.x, gO.x, t1.y * gO.y); v[8 * s + 7] = fma(t1.y, gO.x, -(t1.x * gO.y));
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[8 * s + j] = 0.0;
-                    }
+                    cfma(p[s][0], we0, E[4 * s + r]); cfma(p[s][0], wo0, O[4 * s + r]);
+                    cfma(p[s][1], we1, E[4 * s + r]); cfma(p[s][1], wo1, O[4 * s + r]);
                 }
-                double h1[8], h2[4], h3[2];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) h1[j] = halve32(v[j], v[j + 8]);                         // lanes >= 32: the odd slot
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h2[j] = halve16(h1[j], h1[j + 4]);                       // odd rows: O
-#pragma unroll
-                for (int j = 0; j < 2; ++j) h3[j] = halve_row<DPP_ROW_MIRROR>(h2[j], h2[j + 2], keep8);   // bit 3: ear 1
-                double x = halve_row<DPP_HALF_MIRROR>(h3[0], h3[1], keep4);                          // bit 2: imaginary part
-                x += dpp_d<DPP_XOR1>(x);
-                x += dpp_d<DPP_XOR2>(x);
-                r[c] = x;
-                __builtin_amdgcn_sched_barrier(0);   // (one chunk at a time: the scheduler otherwise starts them all)
             }
-            if ((lane & 3) == 0) {
-                double* wp = wpart + (t >> 6) * NVW + (lane >> 2);
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) wp[16 * c] = r[c];
+            if (slot8) {
+                const int u = 16 + (x & 1);
+                cplx q0 = mk(0, 0), q1 = mk(0, 0);
+                cfma(q0, WE[u], E[8]); cfma(q0, WO[u], O[8]);
+                cfma(q1, WE[NU2 + u], E[8]); cfma(q1, WO[NU2 + u], O[8]);
+                const bool s1 = (x & 2) != 0;
+                const cplx z = mk(0, 0);
+                p[0][0] = p[0][0] + (s1 ? z : q0); p[0][1] = p[0][1] + (s1 ? z : q1);
+                p[1][0] = p[1][0] + (s1 ? q0 : z); p[1][1] = p[1][1] + (s1 ? q1 : z);
             }
+            if (svc) stage_m(t);
+            RSTAMP(8);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const cplx pe0 = group_sum<4>(p[s][0]), pe1 = group_sum<4>(p[s][1]);   // (both ears: the quad's other pair needs the other one)
+                const cplx pe = (x & 2) ? pe1 : pe0;
+                ts[s] = dir_of(t, s) < D ? unit_phase(hCur[s], pe, nyq) : mk(0, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- this wave's partial  t conj(E_u), t conj(O_u)  summed over its 32 directions, on the matrix pipe
+        {
+            const int t = launder(tid);
+            rg_contract<NUL>(E, O, ts, t & 63, slot8, wpart + (t >> 6) * NVW);
         }
         // (the operand registers are free now: what the next iterations need from memory is requested here)
         {
@@ -468,11 +481,10 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
             if (xr < C) {
                 const int xu = xr < 2 * npr ? (xr >> 1) : npr + (xr - 2 * npr);
                 const bool xneg = xr < 2 * npr && (xr & 1);
-                const int h = xu >= NUL ? 1 : 0;
-                const double* wE = wpart + h * NVW + 8 * (xu - h * NUL) + 2 * xe + xri;   // wave h of block 0; + 4: the O value
+                const double* wE = wpart + 8 * xu + 2 * xe + xri;   // wave 0; + 4: the O value
                 double sE = 0.0, sO = 0.0;
 #pragma unroll
-                for (int q = 0; q < NB; ++q) { sE += wE[2 * q * NVW]; sO += wE[2 * q * NVW + 4]; }
+                for (int w = 0; w < NW; ++w) { sE += wE[w * NVW]; sO += wE[w * NVW + 4]; }
                 v = xneg ? sE - sO : sE + sO;
             }
             const gu64_t dst = part_ll + (((size_t)(kb & 1) * nWG + member) * RG_NEX + t) * 2;
@@ -486,23 +498,20 @@ __global__ void __launch_bounds__(64 * NW) sweep_reg_kernel(const HalfSweepArgs*
 #undef RSTAMP
 }
 
-// the wave reduction of the kernel above on its own: in [64 lanes][16 values] -> out [16] (lane l ends up with the sum over all lanes of
-// value l >> 2)
-__global__ void __launch_bounds__(64) reg_reduce_selftest_kernel(const double* __restrict__ in, double* __restrict__ out) {
-    const int lane = threadIdx.x;
-    const double* v = in + lane * 16;
-    const bool keep8 = (lane & 8) == 0, keep4 = (lane & 4) == 0;
-    double h1[8], h2[4], h3[2];
+// the contraction of the kernel above on its own, in the kernel's quad layout: t [32 directions][ear], g [32 directions][18 units][E / O]
+// (complex) -> out [18 units][E / O][ear][re / im]
+__global__ void __launch_bounds__(64) reg_contract_selftest_kernel(const cplx* __restrict__ t, const cplx* __restrict__ g, double* __restrict__ out) {
+    const int lane = threadIdx.x, x = lane & 3;
+    cplx E[RG_NUL], O[RG_NUL], ts[2];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) h1[j] = halve32(v[j], v[j + 8]);
+    for (int i = 0; i < RG_NUL; ++i) {
+        const int d = 16 * rg_slot_set(i, x) + (lane >> 2), u = rg_slot_unit(i, x);
+        E[i] = ldc(g + (d * 18 + u) * 2);
+        O[i] = ldc(g + (d * 18 + u) * 2 + 1);
+    }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) h2[j] = halve16(h1[j], h1[j + 4]);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) h3[j] = halve_row<DPP_ROW_MIRROR>(h2[j], h2[j + 2], keep8);
-    double x = halve_row<DPP_HALF_MIRROR>(h3[0], h3[1], keep4);
-    x += dpp_d<DPP_XOR1>(x);
-    x += dpp_d<DPP_XOR2>(x);
-    if ((lane & 3) == 0) out[lane >> 2] = x;
+    for (int s = 0; s < 2; ++s) ts[s] = ldc(t + (16 * s + (lane >> 2)) * 2 + (x >> 1));
+    rg_contract<RG_NUL>(E, O, ts, lane, true, out);
 }
 
 // argument blocks into device memory, stream-ordered (no host buffer has to outlive the call)
@@ -516,11 +525,10 @@ __global__ void __launch_bounds__(64) store_args_kernel(HalfSweepMulti m, HalfSw
 }
 static_assert(sizeof(HalfSweepArgs) % 8 == 0, "argument block in whole words");
 
-constexpr int RG_NUL = 9;   // unit slots per wave: designs of up to 18 units (the em32: 15 antipodal pairs + 2 single capsules)
 size_t reg_dyn_bytes(int nul, int nw) {
-    const size_t nu2 = 2 * (size_t)nul, nvw = 16 * (((size_t)nul + 1) / 2);
+    const size_t nu2 = 2 * (size_t)nul, nvw = 8 * nu2;
     return sizeof(cplx) * ((size_t)2 * SY_NORD + PS_CMAX * RG_MLD + 4 * nu2) +
-           sizeof(double) * (2 * RG_NEX + (size_t)nw * nvw + (size_t)nw * 256 + (size_t)nul * 64 * nw);
+           sizeof(double) * (2 * RG_NEX + (size_t)nw * nvw + (size_t)nul * 64 * nw);
 }
 constexpr int RG_WAVES[] = {4, 6, 8, 10, 12};   // waves per workgroup of the instantiations
 const void* reg_kernel_ptr(int nw) {
@@ -628,24 +636,39 @@ void launch_sweep_reg(const HalfSweepArgs* args_dev, const HalfSweepArgs& a0, in
     KERNEL_CHECK();
 }
 
-// max |device - host| of the wave reduction on pseudo-random values (debug entry emagls_self_test)
-double reg_reduce_selftest() {
-    double h_in[64 * 16], h_out[16], want[16] = {0};
+// max |device - host| of the contraction on pseudo-random values (debug entry emagls_self_test)
+double reg_contract_selftest() {
+    constexpr int ND = 32, NU = 2 * RG_NUL, NO = 8 * NU;
+    cplx h_t[ND * 2], h_g[ND * NU * 2];
+    double h_out[NO], want[NO] = {0};
     unsigned long long x = 88172645463325252ull;
-    for (int i = 0; i < 64 * 16; ++i) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; h_in[i] = (double)(x % 2000001ull) / 1000000.0 - 1.0; }
-    for (int l = 0; l < 64; ++l) for (int j = 0; j < 16; ++j) want[j] += h_in[l * 16 + j];
-    double *d_in = nullptr, *d_out = nullptr;
-    HIP_CHECK(hipMalloc(&d_in, sizeof h_in));
+    auto rnd = [&] { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return (double)(x % 2000001ull) / 1000000.0 - 1.0; };
+    for (cplx& v : h_t) { v.x = rnd(); v.y = rnd(); }
+    for (cplx& v : h_g) { v.x = rnd(); v.y = rnd(); }
+    for (int d = 0; d < ND; ++d)
+        for (int u = 0; u < NU; ++u)
+            for (int eo = 0; eo < 2; ++eo)
+                for (int e = 0; e < 2; ++e) {
+                    const cplx tv = h_t[d * 2 + e], gv = h_g[(d * NU + u) * 2 + eo];
+                    want[8 * u + 4 * eo + 2 * e] += tv.x * gv.x + tv.y * gv.y;       // t conj(g)
+                    want[8 * u + 4 * eo + 2 * e + 1] += tv.y * gv.x - tv.x * gv.y;
+                }
+    cplx *d_t = nullptr, *d_g = nullptr;
+    double* d_out = nullptr;
+    HIP_CHECK(hipMalloc(&d_t, sizeof h_t));
+    HIP_CHECK(hipMalloc(&d_g, sizeof h_g));
     HIP_CHECK(hipMalloc(&d_out, sizeof h_out));
-    HIP_CHECK(hipMemcpy(d_in, h_in, sizeof h_in, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_t, h_t, sizeof h_t, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_g, h_g, sizeof h_g, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemset(d_out, 0, sizeof h_out));
-    reg_reduce_selftest_kernel<<<1, 64>>>(d_in, d_out);
+    reg_contract_selftest_kernel<<<1, 64>>>(d_t, d_g, d_out);
     KERNEL_CHECK();
     HIP_CHECK(hipMemcpy(h_out, d_out, sizeof h_out, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(d_in));
+    HIP_CHECK(hipFree(d_t));
+    HIP_CHECK(hipFree(d_g));
     HIP_CHECK(hipFree(d_out));
     double err = 0.0;
-    for (int i = 0; i < 16; ++i) err = std::max(err, std::fabs(h_out[i] - want[i]));
+    for (int i = 0; i < NO; ++i) err = std::max(err, std::fabs(h_out[i] - want[i]));
     return err;
 }
 
