@@ -114,6 +114,16 @@ SYMBOLS = {
                                                           C.c_int, C.c_int, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
                                                           C.c_void_p, c_i64, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                                           C.c_void_p, C.c_void_p]),
+    "emagls_decode_stream_create": (C.c_int, [c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, c_i64,
+                                              C.POINTER(C.c_void_p)]),
+    "emagls_decode_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
+                                            C.c_void_p]),
+    "emagls_decode_stream_push_device": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64,
+                                                   C.c_void_p, C.c_void_p]),
+    "emagls_decode_stream_reset": (C.c_int, [C.c_void_p]),
+    "emagls_decode_stream_info": (C.c_int, [C.c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64),
+                                            C.POINTER(C.c_int)]),
+    "emagls_decode_stream_destroy": (C.c_int, [C.c_void_p]),
     "emagls_get_magls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_double, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_get_emagls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_double,

@@ -579,6 +579,135 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
     return out
 
 
+class BinauralDecodeStream:
+    """binauralDecode a block at a time, for a listener whose head moves while the sound plays.  Created
+    once from the decoding filters [len x numChannels] (real or complex); then `push` takes consecutive blocks of the SH (or CH)
+    signal, each with the head orientation for that block, and returns the two ear signals of that block, [n x 2].  With x the
+    concatenation of the pushed blocks and the angles concatenated per sample, the concatenated outputs equal
+    binauralDecode(x, fs, wL, wR, fs, False, horRotAngleRad=yaw, pitchRad=pitch, rollRad=roll, shDefinition=..., rotationDomain=...)
+    to rounding: no delay cut (offset your read by len/2 - 1 yourself), no resampling, no source signal; for complex signals or
+    filters the output is the real part and the discarded imaginary sum is not reported.
+    blockSize: a power of two from 64 to 2048.  complexInput: the pushed blocks are complex.  Uniformly partitioned overlap-save
+    with its state on the GPU; `info` gives block, partitions, state_bytes, filter_bytes and launches_per_block."""
+
+    def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition="real", rotationDomain="sh", complexInput=False):
+        self._h = None
+        self._basis, self._cb = _basis(shDefinition)
+        self._layout = _layout(rotationDomain)
+        w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
+        wL = np.asfortranarray(np.asarray(decodingFilterLeft, dtype=np.complex128 if w_c else np.float64))
+        wR = np.asfortranarray(np.asarray(decodingFilterRight, dtype=np.complex128 if w_c else np.float64))
+        if wL.ndim != 2 or wL.shape != wR.shape:
+            raise ValueError("filters must be [len x numChannels] arrays of equal shape")
+        if int(blockSize) != blockSize:
+            raise ValueError("blockSize must be an integer")
+        self.blockSize, self.numChannels, self.complexInput = int(blockSize), wL.shape[1], bool(complexInput)
+        h = C.c_void_p()
+        L.check(L.load().emagls_decode_stream_create(self.numChannels, wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p),
+                                                     1 if w_c else 0, wL.shape[0], 1 if complexInput else 0, self._layout, self._basis,
+                                                     self.blockSize, C.byref(h)))
+        self._h = h
+
+    @property
+    def info(self):
+        b, p, sb, fb, nl = L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), C.c_int(0)
+        L.check(L.load().emagls_decode_stream_info(self._handle(), C.byref(b), C.byref(p), C.byref(sb), C.byref(fb), C.byref(nl)))
+        return {"block": b.value, "partitions": p.value, "state_bytes": sb.value, "filter_bytes": fb.value, "launches_per_block": nl.value}
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the decode stream is closed")
+        return self._h
+
+    def _check_angles(self, n, hor, pitch, roll, size):
+        """The argument errors of binauralDecode, in its wording; `size` gives the number of values of an angle argument."""
+        for a, name in ((hor, "horRotAngleRad"), (pitch, "pitchRad"), (roll, "rollRad")):
+            if a is not None and size(a) not in (1, n):
+                raise ValueError("%s must be a scalar or have one angle per input sample (%d), not %d" % (name, n, size(a)))
+
+    def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None):
+        """block [n x numChannels], n a multiple of blockSize: a NumPy array (host entry; returns a NumPy array), or a torch tensor
+        on the stream's device (device entry on torch's current stream, not synchronised; returns a torch tensor).  Each angle:
+        None (0), a scalar (constant over this push) or one value per sample; with torch blocks also device tensors."""
+        h = self._handle()
+        if type(block).__module__.split(".")[0] == "torch":
+            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad)
+        if np.iscomplexobj(block) and not self.complexInput:
+            raise ValueError("the stream was created for real blocks (complexInput=False)")
+        x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
+        n = self._check_block(x.shape, x.ndim)
+        self._check_angles(n, horRotAngleRad, pitchRad, rollRad, lambda a: np.asarray(a).size)
+        yaw, pitch, roll = (_angles(a, n, "angle") for a in (horRotAngleRad, pitchRad, rollRad))
+        if any(a is not None and np.any(a != 0) for a in (pitch, roll)):
+            if self._layout != L.LAYOUT["sh"]:
+                raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
+            _sh_order(self.numChannels)
+        out, po = _out(n, 2, False)
+        L.check(L.load().emagls_decode_stream_push(h, x.ctypes.data_as(C.c_void_p), n, *_vp(yaw), *_vp(pitch), *_vp(roll), po))
+        return out
+
+    def _check_block(self, shape, ndim):
+        if ndim != 2 or shape[1] != self.numChannels:
+            raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
+        if shape[0] % self.blockSize:
+            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
+        return shape[0]
+
+    def _push_torch(self, h, block, hor, pitch, roll):
+        import torch
+        n = self._check_block(tuple(block.shape), block.dim())
+        if not block.is_cuda:
+            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        if block.is_complex() and not self.complexInput:
+            raise ValueError("the stream was created for real blocks (complexInput=False)")
+        size = lambda a: a.numel() if torch.is_tensor(a) else np.asarray(a).size   # noqa: E731
+        self._check_angles(n, hor, pitch, roll, size)
+        dt = torch.complex128 if self.complexInput else torch.float64
+        xt = block.to(dt).t().contiguous()                  # [numChannels][n]: the library's column-major [n x numChannels]
+
+        def dev(a):
+            if a is None:
+                return None, 0
+            t = a.to(device=block.device, dtype=torch.float64).reshape(-1).contiguous() if torch.is_tensor(a) else \
+                torch.as_tensor(np.asarray(a, dtype=np.float64).reshape(-1), device=block.device)
+            return t, t.numel()
+        (ty, ny), (tp, npi), (tr, nr) = dev(hor), dev(pitch), dev(roll)
+        if (npi or nr) and self._layout != L.LAYOUT["sh"]:
+            raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
+        if npi or nr:
+            _sh_order(self.numChannels)
+        out = torch.empty((2, n), dtype=torch.float64, device=block.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(block.device):
+            st = torch.cuda.current_stream().cuda_stream
+            L.check(L.load().emagls_decode_stream_push_device(h, p(xt), n, p(ty), ny, p(tp), npi, p(tr), nr, p(out), C.c_void_p(st)))
+        for t in (xt, ty, tp, tr):      # (their memory may be reused only after the stream has passed the enqueued kernels)
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(block.device))
+        return out.t()
+
+    def reset(self):
+        """Zero history: what follows equals a fresh stream bit for bit."""
+        L.check(L.load().emagls_decode_stream_reset(self._handle()))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L.check(L.load().emagls_decode_stream_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # --------------------------------------------------------------------------------------------
 # render-side neighbours
 # --------------------------------------------------------------------------------------------

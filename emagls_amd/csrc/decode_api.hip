@@ -1,9 +1,11 @@
 // C ABI of binauralDecode, the SH rotations and the resampler (include/emagls.h: emagls_binaural_decode*, emagls_rotate_yaw,
-// emagls_rotate_sh, emagls_sh_rotation_matrix, emagls_resample*): the argument check, host staging, the work buffers and the
-// choice of kernels, once for the whole family.  The kernels are decode.hip's, rotate.hip's, rotate3.hip's and resample.hip's.
+// emagls_rotate_sh, emagls_sh_rotation_matrix, emagls_resample*, emagls_decode_stream_*): the argument check, host staging, the work buffers and the
+// choice of kernels, once for the whole family.  The kernels are decode.hip's, decode_stream.hip's, rotate.hip's, rotate3.hip's and
+// resample.hip's.
 // No CPU fallback.
 #include <algorithm>
 #include <initializer_list>
+#include <memory>
 #include <numeric>
 #include <vector>
 
@@ -161,13 +163,14 @@ void check_args(bool decode, std::initializer_list<const void*> ptrs, int64_t ns
 
 // in [C][n] -> out [C][n] (complex when in_c or cb) by rotate.hip's kernel for a yaw-only rotation, rotate3.hip's otherwise;
 // transpose: the filter-side form of a fixed rotation (w Rot instead of x Rot^T)
+// ld_in / ld_out: elements between the channels of in / out (0: n)
 void launch_rotation(const Angles& a, const void* in, bool in_c, int64_t n, int nch, int layout, bool cb, bool transpose, void* out,
-                     hipStream_t st) {
+                     hipStream_t st, int64_t ld_in = 0, int64_t ld_out = 0) {
     if (a.yaw_only())
-        launch_rotate_yaw(in, in_c, n, nch, layout, cb, a.yaw, a.n_yaw > 1, transpose, out, st);
+        launch_rotate_yaw(in, in_c, n, nch, layout, cb, a.yaw, a.n_yaw > 1, transpose, out, st, ld_in, ld_out);
     else
         launch_rotate3(in, in_c, n, nch, cb, a.n_yaw ? a.yaw : nullptr, a.n_yaw > 1, a.n_pitch ? a.pitch : nullptr, a.n_pitch > 1,
-                       a.n_roll ? a.roll : nullptr, a.n_roll > 1, transpose, out, st);
+                       a.n_roll ? a.roll : nullptr, a.n_roll > 1, transpose, out, st, ld_in, ld_out);
 }
 
 // The rotation before the decode.  A fixed one (every count <= 1) turns the decoding filters, sum_i w_i * (x Rot^T)_i =
@@ -471,6 +474,218 @@ int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, do
         launch_rotate3_matrix(order, basis == EMAGLS_BASIS_COMPLEX, yaw, pitch, roll, d, s.st);
         HIP_CHECK(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, s.st));
         HIP_CHECK(hipStreamSynchronize(s.st));
+    });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// The decode stream (decode_stream.hip).  The object owns its device buffers: emagls_cache_clear() does
+// not reach them.
+// ---------------------------------------------------------------------------------------------
+struct emagls_decode_stream {
+    std::mutex mu;
+    int64_t nch = 0, len = 0;
+    int layout = 0, basis = 0;
+    bool in_c = false;
+    int device = -1;              // bound at the first use of the device (creation, when there is one)
+    bool ready = false;
+    std::vector<double> wpl;      // [2][Cp][len] the real filter planes [re w; -im w], until the device has their spectra
+    DecodeStreamState d;
+    void* xrot = nullptr;         // [nch][B] the rotated block (cplx when the signal or the basis is complex)
+    void* stage[3] = {};          // host entry: the push's input, angles and output on the device, grown on demand and kept
+    size_t stage_cap[3] = {};
+    int cp() const { return d.planes2 ? 2 * d.C : d.C; }
+    size_t ring_bytes() const { return sizeof(cplx) * 2 * (size_t)d.P * (d.B + 1); }
+    size_t hist_bytes() const { return esz(d.planes2) * (size_t)d.C * d.B; }
+    size_t filter_bytes() const { return sizeof(cplx) * 2 * (size_t)d.P * cp() * (d.B + 1); }
+    void release() {
+        hipFree(d.Wf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos); hipFree(xrot);
+        for (void*& p : stage) { hipFree(p); p = nullptr; }
+        d.Wf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr; xrot = nullptr;
+        ready = false;
+    }
+    void zero_state(hipStream_t st) {
+        HIP_CHECK(hipMemsetAsync(d.ring, 0, ring_bytes(), st));
+        HIP_CHECK(hipMemsetAsync(d.hist, 0, hist_bytes(), st));
+        HIP_CHECK(hipMemsetAsync(d.pos, 0, sizeof(int), st));
+    }
+    // the device side, once: buffers, the partition spectra, zero history (mu held)
+    void ensure_device() {
+        if (ready) return;
+        HIP_CHECK(hipGetDevice(&device));
+        try {
+            HIP_CHECK(hipMalloc(&d.Wf, filter_bytes()));
+            HIP_CHECK(hipMalloc(&d.ring, ring_bytes()));
+            HIP_CHECK(hipMalloc(&d.hist, hist_bytes()));
+            HIP_CHECK(hipMalloc(&d.pos, sizeof(int)));
+            HIP_CHECK(hipMalloc(&xrot, sizeof(cplx) * (size_t)d.C * d.B));
+            Scratch s;
+            launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.Wf, s.st);
+            zero_state(s.st);
+            HIP_CHECK(hipStreamSynchronize(s.st));
+        } catch (...) { release(); device = -1; throw; }
+        wpl = std::vector<double>();
+        ready = true;
+    }
+    template <typename T> T* staged(int i, size_t bytes) {
+        bytes = std::max<size_t>(bytes, 16);
+        if (bytes > stage_cap[i]) { hipFree(stage[i]); stage[i] = nullptr; stage_cap[i] = 0; HIP_CHECK(hipMalloc(&stage[i], bytes)); stage_cap[i] = bytes; }
+        return reinterpret_cast<T*>(stage[i]);
+    }
+};
+
+namespace {
+
+void stream_check_push(const emagls_decode_stream* s, const void* in, const void* out, int64_t nsamp, const Angles& a) {
+    if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+    if (nsamp < 0 || nsamp % s->d.B) throw Error(EMAGLS_ERR_ARG, "a push needs a multiple of the block size of samples");
+    check_args(true, {in, out}, nsamp, s->nch, s->len, 0, s->layout, s->basis, a);
+}
+
+// k blocks in order on st; device pointers; not synchronised (s->mu held, device current)
+void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const Angles& a, double* d_out, hipStream_t st) {
+    s->ensure_device();
+    const int64_t B = s->d.B;
+    const bool cb = s->basis == EMAGLS_BASIS_COMPLEX;
+    auto at = [&](const double* p, int64_t n, int64_t b) { return n > 1 ? p + b * B : p; };
+    for (int64_t b = 0; b < nsamp / B; ++b) {
+        const void* x = (const char*)d_in + esz(s->in_c) * (size_t)(b * B);
+        bool x_c = s->in_c;
+        int64_t ldx = nsamp;
+        if (a.any()) {
+            const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
+                             at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
+            launch_rotation(blk, x, x_c, B, (int)s->nch, s->layout, cb, false, s->xrot, st, nsamp, B);
+            x = s->xrot; x_c = x_c || cb; ldx = B;
+        }
+        launch_decode_stream_block(s->d, x, x_c, ldx, d_out + b * B, nsamp, st);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
+                                int layout, int basis, int64_t block, emagls_decode_stream** out) {
+    return guarded_call([&] {
+        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *out = nullptr;
+        if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
+        check_basis(basis);
+        if (!decode_stream_block_ok(block))
+            throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports block sizes 64, 128, 256, 512, 1024 and 2048");
+        if (len > 16384) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports filters of up to 16384 taps");
+        std::unique_ptr<emagls_decode_stream> s(new emagls_decode_stream);
+        s->nch = nch; s->len = len; s->layout = layout; s->basis = basis; s->in_c = in_is_complex != 0;
+        s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block);
+        // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
+        s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
+        const int Cp = s->cp();
+        const bool wc = filters_are_complex != 0;
+        s->wpl.assign((size_t)2 * Cp * len, 0.0);
+        for (int e = 0; e < 2; ++e) {
+            const double* w = reinterpret_cast<const double*>(e ? wR : wL);
+            for (int64_t c = 0; c < nch; ++c)
+                for (int64_t t = 0; t < len; ++t) {
+                    const size_t i = (size_t)(c * len + t);
+                    s->wpl[((size_t)e * Cp + c) * len + t] = wc ? w[2 * i] : w[i];
+                    if (wc && s->d.planes2) s->wpl[((size_t)e * Cp + nch + c) * len + t] = -w[2 * i + 1];
+                }
+        }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
+            std::lock_guard<std::mutex> lk(s->mu);
+            s->ensure_device();
+        } else {
+            (void)hipGetLastError();
+        }
+        *out = s.release();
+    });
+}
+
+int emagls_decode_stream_push_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const double* d_yaw, int64_t n_yaw,
+                                     const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll, double* d_out,
+                                     void* stream) {
+    return guarded_call([&] {
+        const Angles a{d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll};
+        stream_check_push(s, d_in, d_out, nsamp, a);
+        if (nsamp == 0) return;
+        std::lock_guard<std::mutex> lk(s->mu);
+        DeviceGuard dg(s->device);
+        stream_push_blocks(s, d_in, nsamp, a, d_out, (hipStream_t)stream);
+    });
+}
+
+int emagls_decode_stream_push(emagls_decode_stream* s, const void* in, int64_t nsamp, const double* yaw, int64_t n_yaw, const double* pitch,
+                              int64_t n_pitch, const double* roll, int64_t n_roll, double* out) {
+    return guarded_call([&] {
+        Angles a{yaw, n_yaw, pitch, n_pitch, roll, n_roll};
+        auto counted = [&](int64_t n) { return n >= 0 && (n <= 1 || n == nsamp); };
+        if (counted(n_pitch) && counted(n_roll)) a = host_angles(a);   // (zeros in a count that does not fit are reported, not dropped)
+        stream_check_push(s, in, out, nsamp, a);
+        if (nsamp == 0) return;
+        std::lock_guard<std::mutex> lk(s->mu);
+        DeviceGuard dg(s->device);
+        s->ensure_device();
+        hipStream_t st = pool_stream_take();
+        struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
+        const size_t bin = esz(s->in_c) * (size_t)nsamp * s->nch;
+        char* d_in = s->staged<char>(0, bin);
+        double* d_ang = s->staged<double>(1, sizeof(double) * 3 * (size_t)nsamp);
+        double* d_out = s->staged<double>(2, sizeof(double) * 2 * (size_t)nsamp);
+        HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
+        auto up = [&](const double* p, int64_t n, int slot) -> const double* {
+            if (!n) return nullptr;
+            double* dst = d_ang + (size_t)slot * nsamp;
+            HIP_CHECK(hipMemcpyAsync(dst, p, sizeof(double) * n, hipMemcpyHostToDevice, st));
+            return dst;
+        };
+        const Angles da{up(a.yaw, a.n_yaw, 0), a.n_yaw, up(a.pitch, a.n_pitch, 1), a.n_pitch, up(a.roll, a.n_roll, 2), a.n_roll};
+        stream_push_blocks(s, d_in, nsamp, da, d_out, st);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * nsamp, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
+int emagls_decode_stream_reset(emagls_decode_stream* s) {
+    return guarded_call([&] {
+        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+        std::lock_guard<std::mutex> lk(s->mu);
+        DeviceGuard dg(s->device);
+        s->ensure_device();
+        HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
+        s->zero_state(nullptr);
+        HIP_CHECK(hipStreamSynchronize(nullptr));
+    });
+}
+
+int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int64_t* partitions, int64_t* state_bytes, int64_t* filter_bytes,
+                              int* launches_per_block) {
+    return guarded_call([&] {
+        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+        if (block) *block = s->d.B;
+        if (partitions) *partitions = s->d.P;
+        if (state_bytes) *state_bytes = (int64_t)(s->ring_bytes() + s->hist_bytes() + sizeof(int));
+        if (filter_bytes) *filter_bytes = (int64_t)s->filter_bytes();
+        if (launches_per_block) *launches_per_block = 3;   // rotation, forward transform with the products, inverse transform
+    });
+}
+
+int emagls_decode_stream_destroy(emagls_decode_stream* s) {
+    return guarded_call([&] {
+        if (!s) return;
+        {
+            std::lock_guard<std::mutex> lk(s->mu);
+            if (s->ready) {
+                DeviceGuard dg(s->device);
+                (void)hipDeviceSynchronize();
+                s->release();
+            }
+        }
+        delete s;
     });
 }
 

@@ -1,0 +1,260 @@
+// Block-streaming binauralDecode (include/emagls.h: emagls_decode_stream_*): out(:, ear) = sum_c fftfilt(w_ear(:, c), x(:, c)) fed a
+// block of B samples at a time, with the state of the convolution kept in HBM between the calls.
+//
+// Uniformly partitioned overlap-save.  The filters are cut into P = ceil(len / B) partitions of B taps, w_p, and transformed once at
+// length Nf = 2B: W_p = FFT([w_p, 0]).  Block j of the signal, behind its predecessor, has the spectrum X_j = FFT([x_(j-1), x_j]), and
+//     y_j = last B samples of IFFT( sum_p sum_c X_(j-p),c W_p,c ).
+// The state is the SCATTERED form: a ring of P pending output spectra per ear.  Block j adds X_j W_p into the slot of output block
+// j + p, for every p, and then takes its own slot out.  Nothing of the input's past is read again but the previous block (the
+// overlap), and the ring is C times smaller than a ring of input spectra.
+//
+// Per block (after the rotation kernel of rotate.hip / rotate3.hip, when the push has angles):
+//   ds_forward_kernel   grid (P, 2 ears): every workgroup transforms the block's channels itself (two real channels, or one complex
+//                       one, per packed transform, in LDS) and accumulates its partition over the channels, thread = frequency bin,
+//                       into ITS ring slot.  A slot has one writer per launch and the channel order is fixed: no atomics, equal
+//                       pushes give equal bits.  Partition P - 1 lands in the slot the previous block just gave up and stores
+//                       instead of adding, so a slot needs no clearing.
+//   ds_inverse_kernel   workgroup 0: the block's slot, both ears in one packed inverse transform, the last B samples out, and the
+//                       ring position (device memory) one step on; the other workgroups keep the block as the next overlap.
+// A complex signal (or a real one turned in the complex basis) is decoded as 2C real planes [re x; im x] against the filters
+// [re w; -im w] (decode.hip, binaural_decode_complex): a complex sample IS the packed pair of its two planes, so it is read as it lies.
+#include "kernels.hpp"
+#include "lds_fft.hpp"
+
+namespace emagls {
+
+namespace {
+
+constexpr int DS_NT = 512;     // threads of every kernel here
+constexpr int DS_ELEMS = 4096; // elements of the transform buffer: DS_ELEMS / Nf transforms per round, 8 loads per thread
+
+__device__ __forceinline__ void ds_twiddles(cplx* tws, int Nf) {
+    for (int j = threadIdx.x; j < Nf / 2; j += DS_NT) {
+        double sn, cs;
+        sincospi(-2.0 * (double)j / (double)Nf, &sn, &cs);   // (exact at the multiples of 1/4: Nf is a power of two)
+        tws[j] = mk(cs, sn);
+    }
+}
+
+// Z = FFT(a + i b) with real a, b:  A[k] = (Z[k] + conj(Z[N-k])) / 2,  B[k] = (Z[k] - conj(Z[N-k])) / (2i)
+__device__ __forceinline__ void ds_unpack(cplx z, cplx zr /* conj(Z[N-k]) */, cplx& pa, cplx& pb) {
+    pa = mk(0.5 * (z.x + zr.x), 0.5 * (z.y + zr.y));
+    pb = mk(0.5 * (z.y - zr.y), -0.5 * (z.x - zr.x));
+}
+
+// Wf[e][p][c][k] (k <= B) = FFT([w_e,c(pB .. pB + B - 1), 0])[k]; wpl [2][Cp][len] real planes.  grid (pairs of planes, P, 2)
+__global__ void __launch_bounds__(DS_NT) ds_filter_kernel(const double* __restrict__ wpl, int Cp, int64_t len, int B, int log2n, int P,
+                                                          cplx* __restrict__ Wf) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    const int Nf = 2 * B, Pf = B + 1, mask = Nf - 1;
+    cplx* buf = reinterpret_cast<cplx*>(dyn);      // [Nf], padded
+    cplx* tws = buf + (Nf + Nf / 16);               // [Nf / 2]
+    const int tid = threadIdx.x, p = blockIdx.y, e = blockIdx.z;
+    const int ca = 2 * blockIdx.x, cb = ca + 1;
+    ds_twiddles(tws, Nf);
+    const double* wa = wpl + ((int64_t)e * Cp + ca) * len;
+    const double* wb = wpl + ((int64_t)e * Cp + min(cb, Cp - 1)) * len;
+    for (int i = tid; i < Nf; i += DS_NT) {
+        const int64_t t = (int64_t)p * B + i;
+        const bool in = i < B && t < len;
+        buf[lds_fft_ix<true>((int)bitrev((unsigned)i, log2n))] = in ? mk(wa[t], cb < Cp ? wb[t] : 0.0) : mk(0.0, 0.0);
+    }
+    __syncthreads();
+    lds_fft_stages<false, true>(buf, tws, Nf, log2n, 1);
+    cplx* oa = Wf + (((int64_t)e * P + p) * Cp + ca) * Pf;
+    for (int k = tid; k < Pf; k += DS_NT) {
+        cplx pa, pb;
+        ds_unpack(buf[lds_fft_ix<true>(k)], conj(buf[lds_fft_ix<true>((Nf - k) & mask)]), pa, pb);
+        oa[k] = pa;
+        if (cb < Cp) oa[Pf + k] = pb;
+    }
+}
+
+// One block into the ring.  xnew: the block, channel c at xnew + c ldx (double, or cplx when x_cplx); hist [C][B]: the previous
+// block (cplx when planes2, else double).  planes2: 2C planes, pair p = complex channel p = planes (p, p + C); else pair p = the
+// real channels (2p, 2p + 1).  KU: frequency bins per thread (B + 1 <= KU * DS_NT).  grid (P, 2)
+template <int KU>
+__global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restrict__ xnew, int x_cplx, int64_t ldx, const void* __restrict__ hist,
+                                                           int C, int planes2, const cplx* __restrict__ Wf, int B, int log2n, int P,
+                                                           const int* __restrict__ pos_p, cplx* __restrict__ ring) {
+    constexpr int NLD = DS_ELEMS / DS_NT;
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    const int Nf = 2 * B, Pf = B + 1, mask = Nf - 1;
+    const int NTP = DS_ELEMS >> log2n;              // transforms per round
+    cplx* buf = reinterpret_cast<cplx*>(dyn);      // [NTP][Nf], padded
+    cplx* tws = buf + (DS_ELEMS + DS_ELEMS / 16);   // [Nf / 2]
+    const int tid = threadIdx.x, part = blockIdx.x, e = blockIdx.y;
+    const int Cp = planes2 ? 2 * C : C, npairs = planes2 ? C : (C + 1) / 2;
+    ds_twiddles(tws, Nf);
+    const int G = Pf <= DS_NT ? DS_NT / Pf : 1;     // groups of threads that share the pairs of a round (short transforms)
+    cplx acc[KU];
+#pragma unroll
+    for (int u = 0; u < KU; ++u) acc[u] = mk(0, 0);
+    const double* xr = reinterpret_cast<const double*>(xnew);
+    const cplx* xc = reinterpret_cast<const cplx*>(xnew);
+    const double* hr = reinterpret_cast<const double*>(hist);
+    const cplx* hc = reinterpret_cast<const cplx*>(hist);
+    // a round's samples travel global -> registers -> LDS; the loads of round r + 1 are issued before the transforms of round r
+    cplx xv[NLD];
+    auto fetch = [&](int p0) __attribute__((always_inline)) {
+        const int np = min(NTP, npairs - p0);
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int idx = tid + DS_NT * j;
+            const int t = idx >> log2n, i = idx & mask;
+            cplx v = mk(0.0, 0.0);
+            if (t < np) {
+                const int pr = p0 + t;
+                if (planes2) {
+                    if (i < B) v = hc[(int64_t)pr * B + i];
+                    else v = x_cplx ? xc[(int64_t)pr * ldx + (i - B)] : mk(xr[(int64_t)pr * ldx + (i - B)], 0.0);
+                } else {
+                    const int ca = 2 * pr, cb = min(ca + 1, C - 1);
+                    if (i < B) v = mk(hr[(int64_t)ca * B + i], hr[(int64_t)cb * B + i]);
+                    else v = mk(xr[(int64_t)ca * ldx + (i - B)], xr[(int64_t)cb * ldx + (i - B)]);
+                    if (ca + 1 >= C) v.y = 0.0;
+                }
+            }
+            xv[j] = v;
+        }
+    };
+    const cplx* Wp = Wf + ((int64_t)e * P + part) * Cp * Pf;
+    fetch(0);
+    for (int p0 = 0; p0 < npairs; p0 += NTP) {
+        const int np = min(NTP, npairs - p0);
+        __syncthreads();   // the previous round's spectra have been read (first round: the twiddles are written)
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+            const int idx = tid + DS_NT * j;
+            const int t = idx >> log2n, i = idx & mask;
+            if (t < np) buf[lds_fft_ix<true>((t << log2n) + (int)bitrev((unsigned)i, log2n))] = xv[j];
+        }
+        if (p0 + NTP < npairs) fetch(p0 + NTP);
+        __syncthreads();
+        lds_fft_stages<false, true>(buf, tws, Nf, log2n, np);
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+            const int idx = tid + DS_NT * u;
+            const int g = idx / Pf, k = idx - g * Pf;
+            if (g < G) {
+                const cplx* wk = Wp + k;
+#pragma unroll 1
+                for (int t = g; t < np; t += G) {   // (ascending pairs per group, the groups summed in order below: a fixed order)
+                    const int pr = p0 + t;
+                    const int ca = planes2 ? pr : 2 * pr, cb = planes2 ? pr + C : 2 * pr + 1;
+                    cplx pa, pb;
+                    ds_unpack(buf[lds_fft_ix<true>((t << log2n) + k)], conj(buf[lds_fft_ix<true>((t << log2n) + ((Nf - k) & mask))]), pa, pb);
+                    cfma(acc[u], pa, wk[(int64_t)ca * Pf]);
+                    if (cb < Cp) cfma(acc[u], pb, wk[(int64_t)cb * Pf]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (G > 1) {   // the groups' partial sums meet in LDS; group 0 adds them in the order of the groups
+        const int g = tid / Pf, k = tid - g * Pf;
+        if (g > 0 && g < G) buf[g * Pf + k] = acc[0];
+        __syncthreads();
+        if (g == 0) {
+            for (int o = 1; o < G; ++o) { const cplx x = buf[o * Pf + k]; acc[0].x += x.x; acc[0].y += x.y; }
+        }
+    }
+    const int pos = *pos_p;
+    int slot = pos + part;
+    if (slot >= P) slot -= P;
+    cplx* dst = ring + ((int64_t)e * P + slot) * Pf;
+#pragma unroll
+    for (int u = 0; u < KU; ++u) {
+        const int k = tid + DS_NT * u;
+        if (k < Pf) {
+            if (part == P - 1) dst[k] = acc[u];   // the slot the previous block gave up
+            else { const cplx old = dst[k]; dst[k] = mk(old.x + acc[u].x, old.y + acc[u].y); }
+        }
+    }
+}
+
+// workgroup 0: out[i] (left), out[ldo + i] (right) = the last B samples of IFFT(ring slot `pos`) -- both ears in one packed
+// transform, Y_L + i Y_R with Y_e[N - k] = conj(Y_e[k]) -- and pos <- (pos + 1) mod P.  The other workgroups: hist <- the block
+__global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restrict__ ring, int B, int log2n, int P, int* __restrict__ pos_p,
+                                                           double* __restrict__ out, int64_t ldo, const void* __restrict__ xnew, int x_cplx,
+                                                           int64_t ldx, void* __restrict__ hist, int planes2, int C) {
+    const int tid = threadIdx.x;
+    if (blockIdx.x > 0) {
+        const int64_t total = (int64_t)C * B;
+        const double* xr = reinterpret_cast<const double*>(xnew);
+        const cplx* xc = reinterpret_cast<const cplx*>(xnew);
+        for (int64_t idx = (int64_t)(blockIdx.x - 1) * DS_NT + tid; idx < total; idx += (int64_t)(gridDim.x - 1) * DS_NT) {
+            const int64_t c = idx >> (log2n - 1), i = idx & (B - 1);
+            if (planes2) reinterpret_cast<cplx*>(hist)[idx] = x_cplx ? xc[c * ldx + i] : mk(xr[c * ldx + i], 0.0);
+            else reinterpret_cast<double*>(hist)[idx] = xr[c * ldx + i];
+        }
+        return;
+    }
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    const int Nf = 2 * B, Pf = B + 1;
+    cplx* buf = reinterpret_cast<cplx*>(dyn);      // [Nf], padded
+    cplx* tws = buf + (Nf + Nf / 16);               // [Nf / 2]
+    ds_twiddles(tws, Nf);
+    const int pos = *pos_p;
+    const cplx* yl = ring + (int64_t)pos * Pf;
+    const cplx* yr = ring + ((int64_t)P + pos) * Pf;
+    for (int k = tid; k < Pf; k += DS_NT) {
+        const cplx l = yl[k], r = yr[k];
+        buf[lds_fft_ix<true>((int)bitrev((unsigned)k, log2n))] = mk(l.x - r.y, l.y + r.x);
+        if (k > 0 && k < B) buf[lds_fft_ix<true>((int)bitrev((unsigned)(Nf - k), log2n))] = mk(l.x + r.y, r.x - l.y);
+    }
+    __syncthreads();
+    lds_fft_stages<true, true>(buf, tws, Nf, log2n, 1);
+    const double scale = 1.0 / (double)Nf;
+    for (int i = tid; i < B; i += DS_NT) {
+        const cplx y = buf[lds_fft_ix<true>(B + i)];
+        out[i] = y.x * scale;
+        out[ldo + i] = y.y * scale;
+    }
+    if (tid == 0) *pos_p = pos + 1 == P ? 0 : pos + 1;
+}
+
+size_t ds_forward_lds(int B) { return sizeof(cplx) * ((size_t)DS_ELEMS + DS_ELEMS / 16 + (size_t)B); }
+size_t ds_single_lds(int B) { const size_t Nf = 2 * (size_t)B; return sizeof(cplx) * (Nf + Nf / 16 + Nf / 2); }
+int ds_log2(int Nf) { int l = 0; while ((1 << l) < Nf) ++l; return l; }
+
+void ds_attributes() {
+    static PerDeviceOnce once;
+    if (!once.first()) return;
+#define EMAGLS_DS_ATTR(K) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024))
+    EMAGLS_DS_ATTR(ds_filter_kernel);
+    EMAGLS_DS_ATTR(ds_inverse_kernel);
+    EMAGLS_DS_ATTR(ds_forward_kernel<1>);
+    EMAGLS_DS_ATTR(ds_forward_kernel<2>);
+    EMAGLS_DS_ATTR(ds_forward_kernel<3>);
+    EMAGLS_DS_ATTR(ds_forward_kernel<5>);
+#undef EMAGLS_DS_ATTR
+}
+
+}  // namespace
+
+bool decode_stream_block_ok(int64_t B) { return B >= 64 && B <= 2048 && (B & (B - 1)) == 0; }
+
+void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, cplx* Wf, hipStream_t st) {
+    ds_attributes();
+    const dim3 grid((unsigned)((Cp + 1) / 2), (unsigned)P, 2);
+    ds_filter_kernel<<<grid, DS_NT, ds_single_lds(B), st>>>(wpl, Cp, len, B, ds_log2(2 * B), P, Wf);
+    KERNEL_CHECK();
+}
+
+void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, double* out, int64_t ldo, hipStream_t st) {
+    ds_attributes();
+    const int log2n = ds_log2(2 * s.B), Pf = s.B + 1, ku = (Pf + DS_NT - 1) / DS_NT;
+    const dim3 grid((unsigned)s.P, 2);
+    const size_t dyn = ds_forward_lds(s.B);
+#define EMAGLS_DS_GO(KU) ds_forward_kernel<KU><<<grid, DS_NT, dyn, st>>>(x, x_cplx ? 1 : 0, ldx, s.hist, s.C, s.planes2 ? 1 : 0, s.Wf, s.B, log2n, s.P, s.pos, s.ring)
+    if (ku == 1) EMAGLS_DS_GO(1); else if (ku == 2) EMAGLS_DS_GO(2); else if (ku == 3) EMAGLS_DS_GO(3); else EMAGLS_DS_GO(5);
+#undef EMAGLS_DS_GO
+    KERNEL_CHECK();
+    const unsigned ncopy = (unsigned)std::min<int64_t>(32, ceil_div((int64_t)s.C * s.B, 4 * DS_NT));
+    ds_inverse_kernel<<<1 + ncopy, DS_NT, ds_single_lds(s.B), st>>>(s.ring, s.B, log2n, s.P, s.pos, out, ldo, x, x_cplx ? 1 : 0, ldx, s.hist,
+                                                                  s.planes2 ? 1 : 0, s.C);
+    KERNEL_CHECK();
+}
+
+}  // namespace emagls

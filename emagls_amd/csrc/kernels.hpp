@@ -205,16 +205,18 @@ void launch_abs_sum_cols(const double* x, int64_t n, int64_t skip, int ncols, do
 // N of a layout (0: SH, (N+1)^2 channels in ACN order; 1: CH, 2N+1 channels [C_0, C_-1, C_1, ..., C_-N, C_N]); -1 if C fits not
 int rotate_order(int layout, int64_t C);
 // yaw rotation of in [C][n] (real, or interleaved complex): out [C][n], complex when in_cplx || cplx_basis.  yaw: device, one
-// angle (per_sample false) or n angles.  transpose: the filter-side form of a fixed angle (w Rot instead of x Rot^T)
+// angle (per_sample false) or n angles.  transpose: the filter-side form of a fixed angle (w Rot instead of x Rot^T).
+// ld_in / ld_out: elements between the channels of in / out (0: n) -- a block of a longer signal, decode_stream.hip
 void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
-                       bool transpose, void* out, hipStream_t st);
+                       bool transpose, void* out, hipStream_t st, int64_t ld_in = 0, int64_t ld_out = 0);
 // ---- rotate3.hip
 int rotate3_max_order();   // 15: the largest SH order of the three-axis rotation
 // rotation R = Rz(yaw) Ry(pitch) Rx(roll) of the SH (ACN) signal in [C][n] (real, or interleaved complex): out [C][n], complex
 // when in_cplx || cplx_basis.  Each angle: device pointer, null (0), one value (*_ps false) or n values.  transpose: the
-// filter-side form of a fixed rotation (w M instead of x M^T).  C = (N+1)^2 with N <= 15, else Error
+// filter-side form of a fixed rotation (w M instead of x M^T).  C = (N+1)^2 with N <= 15, else Error.  ld_in / ld_out as above
 void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch,
-                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st);
+                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st, int64_t ld_in = 0,
+                    int64_t ld_out = 0);
 // M [(N+1)^2 x (N+1)^2] column-major, out_row = in_row M^T; the same device code as launch_rotate3
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st);
 void rotate3_cache_clear();
@@ -225,6 +227,22 @@ int64_t resample_length(int64_t n, int64_t p, int64_t q);   // ceil(n p / q)
 // p, q reduced, both >= 1; max(p, q) > kResampleMaxRatio: Error(EMAGLS_ERR_UNSUPPORTED)
 void launch_resample(const void* in, bool cplx_in, int64_t n, int64_t nch, int64_t p, int64_t q, void* out, hipStream_t st);
 void resample_cache_clear();
+
+// ---- decode_stream.hip: the block-streaming decode (uniformly partitioned overlap-save, state in HBM)
+struct DecodeStreamState {
+    int C = 0;              // channels of the signal
+    bool planes2 = false;   // the signal is decoded as 2C real planes [re x; im x] (complex signal, or complex basis with a rotation)
+    int B = 0, P = 0;       // block size, partitions
+    cplx* Wf = nullptr;     // [2][P][Cp][B + 1] partition spectra, Cp = planes2 ? 2C : C
+    cplx* ring = nullptr;   // [2][P][B + 1] pending output spectra
+    void* hist = nullptr;   // [C][B] the previous block (cplx when planes2)
+    int* pos = nullptr;     // the ring slot of the next output block
+};
+bool decode_stream_block_ok(int64_t B);   // a power of two from 64 to 2048
+// Wf from the real filter planes wpl [2][Cp][len] (device)
+void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, cplx* Wf, hipStream_t st);
+// one block: x + c ldx = channel c of the (rotated) block, B samples (cplx only when planes2); out[i], out[ldo + i] = the two ears
+void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, double* out, int64_t ldo, hipStream_t st);
 
 // ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables, resample.hip's taps and the decode family's work buffers
 void decode_family_cache_clear();

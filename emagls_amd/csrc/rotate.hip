@@ -33,7 +33,7 @@ __device__ __forceinline__ cplx widen(cplx v) { return v; }
 // (the decoding filters of a fixed angle: sum_i w_i * (x Rot^T)_i = sum_j (w Rot)_j * x_j); the complex basis is diagonal.
 template <bool IC, bool OC>
 __global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict__ in_, int64_t n, int N, int layout, int cb,
-                                                         const double* __restrict__ yaw, int per_sample, double sgn, void* __restrict__ out_) {
+                                                         const double* __restrict__ yaw, int per_sample, double sgn, void* __restrict__ out_, int64_t ldi, int64_t ldo) {
     using TI = typename Val<IC>::T;
     using TO = typename Val<OC>::T;
     const TI* __restrict__ in = reinterpret_cast<const TI*>(in_);
@@ -43,8 +43,8 @@ __global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict_
         const double th = fmod(yaw[per_sample ? t : 0], 2.0 * kPi);
         for (int j = 0; j < nl; ++j) {          // m = 0: unchanged
             const int64_t k = layout == 0 ? (int64_t)j * j + j : 0;
-            if constexpr (OC) out[k * n + t] = widen(in[k * n + t]);
-            else out[k * n + t] = in[k * n + t];
+            if constexpr (OC) out[k * ldo + t] = widen(in[k * ldi + t]);
+            else out[k * ldo + t] = in[k * ldi + t];
         }
         for (int m = 1; m <= N; ++m) {
             double s, c;
@@ -52,21 +52,21 @@ __global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict_
             for (int nn = layout == 0 ? m : 0; nn < (layout == 0 ? N + 1 : 1); ++nn) {
                 const int64_t p = layout == 0 ? (int64_t)nn * nn + nn + m : 2 * m;        // (n, m)
                 const int64_t q = layout == 0 ? (int64_t)nn * nn + nn - m : 2 * m - 1;    // (n, -m)
-                const TI a = in[p * n + t], b = in[q * n + t];
+                const TI a = in[p * ldi + t], b = in[q * ldi + t];
                 if constexpr (OC) {
                     const cplx ac = widen(a), bc = widen(b);
                     if (cb) {   // exp(-i m t) and exp(+i m t)
-                        out[p * n + t] = mk(c * ac.x + s * ac.y, c * ac.y - s * ac.x);
-                        out[q * n + t] = mk(c * bc.x - s * bc.y, c * bc.y + s * bc.x);
+                        out[p * ldo + t] = mk(c * ac.x + s * ac.y, c * ac.y - s * ac.x);
+                        out[q * ldo + t] = mk(c * bc.x - s * bc.y, c * bc.y + s * bc.x);
                     } else {
                         const double ss = sgn * s;
-                        out[p * n + t] = mk(c * ac.x - ss * bc.x, c * ac.y - ss * bc.y);
-                        out[q * n + t] = mk(c * bc.x + ss * ac.x, c * bc.y + ss * ac.y);
+                        out[p * ldo + t] = mk(c * ac.x - ss * bc.x, c * ac.y - ss * bc.y);
+                        out[q * ldo + t] = mk(c * bc.x + ss * ac.x, c * bc.y + ss * ac.y);
                     }
                 } else {
                     const double ss = sgn * s;
-                    out[p * n + t] = c * a - ss * b;
-                    out[q * n + t] = c * b + ss * a;
+                    out[p * ldo + t] = c * a - ss * b;
+                    out[q * ldo + t] = c * b + ss * a;
                 }
             }
         }
@@ -76,16 +76,17 @@ __global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict_
 }  // namespace
 
 void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
-                       bool transpose, void* out, hipStream_t st) {
+                       bool transpose, void* out, hipStream_t st, int64_t ld_in, int64_t ld_out) {
     if (n <= 0) return;
+    const int64_t ldi = ld_in ? ld_in : n, ldo = ld_out ? ld_out : n;
     const int N = rotate_order(layout, C);
     if (N < 0) throw Error(1, "rotate_yaw: the channel count fits neither (N+1)^2 (SH) nor 2N+1 (CH)");
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 256), 65536);
     const double sgn = (transpose && !cplx_basis) ? -1.0 : 1.0;
     const int cb = cplx_basis ? 1 : 0, ps = per_sample ? 1 : 0;
-    if (in_cplx) rotate_yaw_kernel<true, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out);
-    else if (cplx_basis) rotate_yaw_kernel<false, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out);
-    else rotate_yaw_kernel<false, false><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out);
+    if (in_cplx) rotate_yaw_kernel<true, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo);
+    else if (cplx_basis) rotate_yaw_kernel<false, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo);
+    else rotate_yaw_kernel<false, false><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo);
     KERNEL_CHECK();
 }
 

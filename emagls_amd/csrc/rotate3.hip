@@ -256,7 +256,7 @@ __host__ __device__ constexpr int r3_waves(int NB, bool cplx_v) { return NB <= 2
 template <int NB, bool IC, bool CB>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(r3_waves(NB, IC || CB)))) rotate3_kernel(int N, const void* __restrict__ in_, int64_t n, const double* __restrict__ yaw, int yps,
                                                       const double* __restrict__ pitch, int pps, const double* __restrict__ roll, int rps,
-                                                      int transpose, const double* __restrict__ jpk, void* __restrict__ out_) {
+                                                      int transpose, const double* __restrict__ jpk, void* __restrict__ out_, int64_t ldi, int64_t ldo) {
     using TI = std::conditional_t<IC, cplx, double>;
     using V = std::conditional_t<IC || CB, cplx, double>;
     __shared__ double J[jpk_off(NB + 1)];
@@ -265,8 +265,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(r3_wav
     V* __restrict__ out = reinterpret_cast<V*>(out_);
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
         const Ang a = zyz(yaw ? yaw[yps ? t : 0] : 0.0, pitch ? pitch[pps ? t : 0] : 0.0, roll ? roll[rps ? t : 0] : 0.0, transpose != 0);
-        rot_orders<0, NB, CB, V>(N, J, a, [&](int k) { return to_v(in[(int64_t)k * n + t], (V*)nullptr); },
-                                [&](int k, V v) { out[(int64_t)k * n + t] = v; });
+        rot_orders<0, NB, CB, V>(N, J, a, [&](int k) { return to_v(in[(int64_t)k * ldi + t], (V*)nullptr); },
+                                [&](int k, V v) { out[(int64_t)k * ldo + t] = v; });
     }
 }
 
@@ -307,11 +307,11 @@ const double* j_pack(hipStream_t st) {
 }
 
 template <int NB> void launch_nb(int N, const void* in, bool ic, int64_t n, bool cb, const double* yaw, bool yps, const double* pitch,
-                                bool pps, const double* roll, bool rps, bool transpose, const double* jpk, void* out, hipStream_t st) {
+                                bool pps, const double* roll, bool rps, bool transpose, const double* jpk, void* out, hipStream_t st, int64_t ldi, int64_t ldo) {
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 256), 1 << 20);   // one sample per lane up to 268 M samples
     auto k = ic ? (cb ? rotate3_kernel<NB, true, true> : rotate3_kernel<NB, true, false>)
                 : (cb ? rotate3_kernel<NB, false, true> : rotate3_kernel<NB, false, false>);
-    k<<<grid, 256, 0, st>>>(N, in, n, yaw, yps, pitch, pps, roll, rps, transpose ? 1 : 0, jpk, out);
+    k<<<grid, 256, 0, st>>>(N, in, n, yaw, yps, pitch, pps, roll, rps, transpose ? 1 : 0, jpk, out, ldi, ldo);
     KERNEL_CHECK();
 }
 
@@ -332,15 +332,16 @@ void check_order(int N) {
 int rotate3_max_order() { return R3_NMAX; }
 
 void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch,
-                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st) {
+                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st, int64_t ld_in, int64_t ld_out) {
     if (n <= 0) return;
+    const int64_t ldi = ld_in ? ld_in : n, ldo = ld_out ? ld_out : n;
     const int N = rotate_order(0, C);
     check_order(N);
     const double* jpk = j_pack(st);
-    if (N <= 2) launch_nb<2>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st);
-    else if (N <= 4) launch_nb<4>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st);
-    else if (N <= 8) launch_nb<8>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st);
-    else launch_nb<R3_NMAX>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st);
+    if (N <= 2) launch_nb<2>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
+    else if (N <= 4) launch_nb<4>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
+    else if (N <= 8) launch_nb<8>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
+    else launch_nb<R3_NMAX>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
 }
 
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st) {

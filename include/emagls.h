@@ -279,6 +279,55 @@ int emagls_binaural_decode_render_fs_device(const void* d_in, int in_is_complex,
                                             const double* d_signal, int64_t n_signal, double in_fs, double filter_fs, double signal_fs,
                                             double* d_out, double* imag_abs_sum, void* stream);
 
+/* ---- block-streaming decode: a head-tracked renderer gets audio and the head orientation a block at a time ----
+ * A decode stream is created once from the decoding filters and then fed consecutive blocks of the input signal, each with the
+ * orientation for that block; every push returns the two ear signals of the samples it was given (nothing is held back, and the
+ * output depends only on samples already pushed).  With x the concatenation of all pushed blocks and yaw / pitch / roll the
+ * concatenation of their per-sample angles, the concatenated outputs equal, to rounding,
+ * emagls_binaural_decode_render_ypr(x, ..., compensate_delay = 0, yaw, pitch, roll, no signal): the per-sample rotation of the
+ * signal, then sum_c fftfilt(w_c, x_c).  No delay cut (the caller offsets its read), no resampling, no source signal.
+ * For complex signals or filters the output is the real part (dependencies/binauralDecode.m:59-64); the stream does NOT report
+ * the discarded imaginary sum.
+ * Uniformly partitioned overlap-save: block = B samples, a power of two from 64 to 2048 (anything else
+ * is EMAGLS_ERR_UNSUPPORTED); 1 <= len <= 16384 (longer: EMAGLS_ERR_UNSUPPORTED); tested up to 256 channels.  The state (a ring of ceil(len / B) pending output spectra
+ * per ear, the previous block, the ring position) lives in device memory; pushes of equal size differ only in the caller's
+ * pointers; equal pushes on fresh streams give equal bits.
+ * wL / wR [len x nch] host arrays, interleaved complex when filters_are_complex.  in_is_complex: the pushed blocks are
+ * interleaved complex.  layout / basis: of the rotation (EMAGLS_LAYOUT_*, EMAGLS_BASIS_*).  Every argument is checked before the
+ * device is touched.  The stream is bound to the device that is current at creation (without a device the object still exists,
+ * so that argument errors can be reported, and its first push fails with EMAGLS_ERR_HIP).  emagls_cache_clear() does not
+ * touch a live stream.  One push at a time per stream. */
+typedef struct emagls_decode_stream emagls_decode_stream;
+int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
+                                int layout, int basis, int64_t block, emagls_decode_stream** s);
+
+/* in [nsamp x nch] host array, nsamp = k * block (k blocks are run in order inside the call; else EMAGLS_ERR_ARG); each of yaw
+ * [n_yaw], pitch [n_pitch], roll [n_roll] has 0 values (absent: 0), 1 (constant over this push) or nsamp (one per sample),
+ * anything else is EMAGLS_ERR_ARG; out [nsamp x 2].  Angles need a channel count that fits the layout (EMAGLS_ERR_ARG); a CH
+ * layout takes yaw only; pitch or roll above SH order 15 is EMAGLS_ERR_UNSUPPORTED.  When every pitch and roll value of the
+ * push is 0 the push takes the yaw rule, as the offline call does. */
+int emagls_decode_stream_push(emagls_decode_stream* s, const void* in, int64_t nsamp, const double* yaw, int64_t n_yaw,
+                              const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll, double* out);
+
+/* emagls_decode_stream_push on device arrays (the angles included), on the model of emagls_binaural_decode_render_ypr_device:
+ * enqueued on `stream` (hipStream_t, NULL = default) and NOT synchronised; no allocation, no copy of state.  At most three
+ * kernel launches per block (rotation, forward transform with the products, inverse transform).  Device angle arrays are not
+ * read by the host: only absent pitch and roll (counts 0) make a push yaw-only. */
+int emagls_decode_stream_push_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const double* d_yaw, int64_t n_yaw,
+                                     const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll, double* d_out,
+                                     void* stream);
+
+/* Zero history: what follows equals a fresh stream bit for bit.  Waits for the pushes in flight. */
+int emagls_decode_stream_reset(emagls_decode_stream* s);
+
+/* block, partitions = ceil(len / block), state_bytes (ring, previous block and position: what a push reads and writes besides
+ * the filter spectra), filter_bytes (the partition spectra, written once) and the kernel launches per block (each output
+ * optional). */
+int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int64_t* partitions, int64_t* state_bytes,
+                              int64_t* filter_bytes, int* launches_per_block);
+
+int emagls_decode_stream_destroy(emagls_decode_stream* s);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

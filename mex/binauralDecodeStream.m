@@ -1,0 +1,42 @@
+classdef binauralDecodeStream < handle
+% binauralDecode a block at a time on the GPU, for a listener whose head moves while the sound plays (DESIGN.md section 9.3).
+%   s = binauralDecodeStream(decodingFilterLeft, decodingFilterRight, blockSize, shDefinition, rotationDomain, complexInput)
+%   out = s.push(block, horRotAngleRad, pitchRad, rollRad)    block [k*blockSize x numChannels] -> out [k*blockSize x 2]
+%   s.reset()    zero history        delete(s)    releases the device memory
+% Concatenating the pushed blocks into x and the angles per sample, the concatenated outputs equal
+% binauralDecode(x, fs, wL, wR, fs, false, [], [], yaw, shDefinition, rotationDomain, pitch, roll) to rounding: no delay cut, no
+% resampling, no source signal.  blockSize: a power of two from 64 to 2048.  Each angle: [] (0), a scalar (constant over the push)
+% or one value per sample.  For complex signals or filters the output is the real part; the discarded sum is not reported.
+    properties (SetAccess = private)
+        handle = 0
+        blockSize
+    end
+    methods
+        function s = binauralDecodeStream(decodingFilterLeft, decodingFilterRight, blockSize, shDefinition, rotationDomain, complexInput)
+            if nargin < 4; shDefinition = 'real'; end
+            if nargin < 5; rotationDomain = 'sh'; end
+            if nargin < 6; complexInput = false; end
+            if isreal(decodingFilterLeft) ~= isreal(decodingFilterRight)
+                decodingFilterLeft = complex(decodingFilterLeft); decodingFilterRight = complex(decodingFilterRight);
+            end
+            s.blockSize = blockSize;
+            s.handle = emagls_mex('stream_create', double(decodingFilterLeft), double(decodingFilterRight), double(blockSize), ...
+                                  shDefinition, rotationDomain, logical(complexInput));
+        end
+        function out = push(s, block, horRotAngleRad, pitchRad, rollRad)
+            if nargin < 3; horRotAngleRad = []; end
+            if nargin < 4; pitchRad = []; end
+            if nargin < 5; rollRad = []; end
+            out = emagls_mex('stream_push', s.handle, double(block), double(horRotAngleRad), double(pitchRad), double(rollRad));
+        end
+        function reset(s)
+            emagls_mex('stream_reset', s.handle);
+        end
+        function delete(s)
+            if s.handle > 0
+                emagls_mex('stream_destroy', s.handle);
+                s.handle = 0;
+            end
+        end
+    end
+end

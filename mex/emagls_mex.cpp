@@ -58,8 +58,30 @@ int radial_type(const mxArray* a) {
     mexErrMsgIdAndTxt("eMagLS:arg", "Unkown radialFilter parameter \"%s\".", buf);
     return 0;
 }
+// decode streams live in a table; MATLAB holds the 1-based index (mex/binauralDecodeStream.m)
+std::vector<emagls_decode_stream*> g_streams;
+struct StreamShape { mwSize nch; bool in_complex; };
+std::vector<StreamShape> g_stream_shapes;   // what 'stream_push' checks its block against
+emagls_decode_stream* stream_of(const mxArray* a, size_t* index = nullptr) {
+    const double v = (a && mxIsDouble(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
+    const size_t i = (v >= 1 && v <= (double)g_streams.size() && v == std::floor(v)) ? (size_t)v : 0;
+    if (!i || !g_streams[i - 1]) mexErrMsgIdAndTxt("eMagLS:arg", "invalid decode stream handle");
+    if (index) *index = i - 1;
+    return g_streams[i - 1];
+}
+int layout_of(const mxArray* a) {
+    if (!a || mxIsEmpty(a)) return EMAGLS_LAYOUT_SH;
+    char buf[8] = {0};
+    mxGetString(a, buf, sizeof buf);
+    if (!std::strcmp(buf, "ch")) return EMAGLS_LAYOUT_CH;
+    if (std::strcmp(buf, "sh")) mexErrMsgIdAndTxt("eMagLS:arg", "rotation domain must be 'sh' or 'ch'");
+    return EMAGLS_LAYOUT_SH;
+}
 // the plans the one-shot entry points cache (device buffers, captured graphs) are released when the MEX file is cleared
-void at_exit() { emagls_cache_clear(); }
+void at_exit() {
+    for (emagls_decode_stream*& s : g_streams) { if (s) emagls_decode_stream_destroy(s); s = nullptr; }
+    emagls_cache_clear();
+}
 
 }  // namespace
 
@@ -71,6 +93,9 @@ void at_exit() { emagls_cache_clear(); }
 // emagls_mex('emainch' | 'emainsh', hL, hR, azi, zen, micRadius, micAzi, order, fs, len, shDefinition)
 // emagls_mex('magls_dc' | 'emagls_dc' | 'emagls2_dc', <the arguments of 'magls' / 'emagls' / 'emagls2'>, applyDiffusenessConst)
 // emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain, pitchRad, rollRad])   real or complex in / filters; [out, imagAbsSum] = ...
+// h = emagls_mex('stream_create', wL, wR, blockSize[, shDefinition, domain, complexInput])   a decode stream (mex/binauralDecodeStream.m)
+// out = emagls_mex('stream_push', h, in[, yawRad, pitchRad, rollRad])   in [k*blockSize x nch]; each angle [], a scalar or one per sample
+// emagls_mex('stream_reset', h)      emagls_mex('stream_destroy', h)
 // emagls_mex('resample', x, p, q)   MATLAB's resample(x, p, q) (N = 10, bta = 5): a row vector along its length, else per column
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
 // emagls_mex('rotate3', in, yawRad, pitchRad, rollRad[, shDefinition])   three-axis rotation of an SH signal (orders 0-15)
@@ -130,6 +155,56 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                                          basis, yaw, nyaw, pitch, npitch, roll, nroll, sig, nsig, mxGetDoubles(plhs[0]), imag_sum);
         if (rc) fail(rc);
         if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 2, mxREAL); mxGetDoubles(plhs[1])[0] = imag_sum[0]; mxGetDoubles(plhs[1])[1] = imag_sum[1]; }
+        return;
+    }
+    if (c == "stream_create") {
+        if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "stream_create needs (wL, wR, blockSize[, shDefinition, domain, complexInput])");
+        const mwSize len = mxGetM(prhs[1]), ch = mxGetN(prhs[1]);
+        const bool wc = mxIsComplex(prhs[1]);
+        if (!mxIsDouble(prhs[1]) || !mxIsDouble(prhs[2]) || mxGetM(prhs[2]) != len || mxGetN(prhs[2]) != ch)
+            mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must be double arrays of equal size");
+        if (wc != (bool)mxIsComplex(prhs[2])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
+        const int basis = basis_of(nrhs > 4 ? prhs[4] : nullptr), layout = layout_of(nrhs > 5 ? prhs[5] : nullptr);
+        const int ic = nrhs > 6 && (mxIsLogicalScalarTrue(prhs[6]) || (mxIsDouble(prhs[6]) && !mxIsEmpty(prhs[6]) && mxGetScalar(prhs[6]) != 0));
+        emagls_decode_stream* st = nullptr;
+        const int rc = emagls_decode_stream_create((int64_t)ch, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic, layout, basis,
+                                                   (int64_t)mxGetScalar(prhs[3]), &st);
+        if (rc) fail(rc);
+        size_t slot = 0;
+        while (slot < g_streams.size() && g_streams[slot]) ++slot;
+        if (slot == g_streams.size()) { g_streams.push_back(nullptr); g_stream_shapes.push_back({0, false}); }
+        g_streams[slot] = st;
+        g_stream_shapes[slot] = {ch, ic != 0};
+        plhs[0] = mxCreateDoubleScalar((double)(slot + 1));
+        return;
+    }
+    if (c == "stream_push") {
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "stream_push needs (handle, in[, yawRad, pitchRad, rollRad])");
+        size_t slot = 0;
+        emagls_decode_stream* st = stream_of(prhs[1], &slot);
+        if (!mxIsDouble(prhs[2]) || mxGetN(prhs[2]) != g_stream_shapes[slot].nch)
+            mexErrMsgIdAndTxt("eMagLS:arg", "in must be a double array with the filters' channel count (%d)", (int)g_stream_shapes[slot].nch);
+        if ((bool)mxIsComplex(prhs[2]) != g_stream_shapes[slot].in_complex)
+            mexErrMsgIdAndTxt("eMagLS:arg", "in must be %s, as the stream was created", g_stream_shapes[slot].in_complex ? "complex" : "real");
+        const mwSize n = mxGetM(prhs[2]);
+        const double* ang[3] = {nullptr, nullptr, nullptr};
+        mwSize cnt[3] = {0, 0, 0};
+        static const char* const names[3] = {"horRotAngleRad", "pitchRad", "rollRad"};
+        for (int i = 0; i < 3; ++i)
+            if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) { ang[i] = dbl(prhs[3 + i], names[i]); cnt[i] = mxGetNumberOfElements(prhs[3 + i]); }
+        plhs[0] = mxCreateDoubleMatrix(n, 2, mxREAL);
+        const int rc = emagls_decode_stream_push(st, in_ptr(prhs[2]), (int64_t)n, ang[0], (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2],
+                                                 (int64_t)cnt[2], mxGetDoubles(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "stream_reset" || c == "stream_destroy") {
+        if (nrhs < 2) mexErrMsgIdAndTxt("eMagLS:arg", "%s needs (handle)", cmd);
+        size_t slot = 0;
+        emagls_decode_stream* st = stream_of(prhs[1], &slot);
+        const int rc = c == "stream_reset" ? emagls_decode_stream_reset(st) : emagls_decode_stream_destroy(st);
+        if (c == "stream_destroy") g_streams[slot] = nullptr;
+        if (rc) fail(rc);
         return;
     }
     if (c == "resample") {

@@ -1,0 +1,167 @@
+"""Timing of the decode stream (emagls_decode_stream_push_device) against what the library offered before it for the same job:
+emagls_binaural_decode_render_ypr_device on the window of the last len - 1 + B samples with their angles, once per block.  Both in
+one process, alternating, buffers resident in HBM; device events around runs of `run` pushes, `blocks` blocks per shape and side
+after `warm` warm ones.  Per shape (C, len, B), without rotation and with a three-axis trajectory:
+
+  (a) stream   median / p99 time per block of push_device (enqueued back to back, no synchronise inside a run)
+  (b) window   the same of the offline device entry (which synchronises its stream at every call)
+
+Gates (exit status 1 when one fails): median (a) < median (b), and median (a) < B / 48000 s, the block's own duration.
+
+    python tools/decode_stream_timing.py [--blocks 2000] [--warm 50] [--run 100] [--shapes 25,512,64 ...] [--stream-only]
+                                         [--dry-run] [--out profiles/r10_decode_stream.md]
+--dry-run prints the shapes and the bytes a push moves, computed from the shapes, without a device.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E, nominal
+FS = 48000.0
+SHAPES = [(25, 512, 64), (25, 512, 256), (25, 2048, 64), (25, 2048, 1024), (64, 2048, 128), (256, 512, 128)]
+
+
+def push_bytes(Cc, ln, B, rotated):
+    """Bytes one block moves, from the shapes (real signal): the partition spectra once, the ring read and written, the block and
+    the previous block read, the block kept, the output; with a rotation its pass over the block and the three angles."""
+    P, Pf = -(-ln // B), B + 1
+    filt = 16 * 2 * P * Cc * Pf
+    ring = 2 * 16 * 2 * P * Pf
+    sig = 8 * Cc * B * 3 + 8 * 2 * B
+    rot = (2 * 8 * Cc * B + 3 * 8 * B) if rotated else 0
+    return {"filters": filt, "ring": ring, "signal": sig, "rotation": rot, "total": filt + ring + sig + rot}
+
+
+def parse_shapes(items):
+    if not items:
+        return SHAPES
+    out = []
+    for it in items:
+        c, ln, b = (int(v) for v in it.split(","))
+        if b < 64 or b > 2048 or b & (b - 1):
+            raise SystemExit("block size %d is not a power of two from 64 to 2048" % b)
+        if c < 1 or ln < 1:
+            raise SystemExit("bad shape %s" % it)
+        out.append((c, ln, b))
+    return out
+
+
+def run_shape(lib, L, torch, Cc, ln, B, rotated, blocks, warm, run, stream_only):
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(Cc + ln + B)
+    rnd = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)   # noqa: E731
+    wL, wR = rnd(Cc, ln), rnd(Cc, ln)                       # [C][len] row-major == [len x C] column-major
+    nwin = ln - 1 + B
+    d_win, d_wL, d_wR = rnd(Cc, nwin).to(dev), wL.to(dev), wR.to(dev)
+    d_blk = d_win[:, -B:].contiguous()
+    ang = [(0.3 + 0.01 * torch.cumsum(rnd(nwin), 0)).to(dev) for _ in range(3)]
+    ang_blk = [a[-B:].contiguous() for a in ang]
+    d_out_a = torch.zeros((2, B), dtype=torch.float64, device=dev)
+    d_out_b = torch.zeros((2, nwin), dtype=torch.float64, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    h = C.c_void_p()
+    L.check(lib.emagls_decode_stream_create(Cc, C.c_void_p(wL.data_ptr()), C.c_void_p(wR.data_ptr()), 0, ln, 0, L.LAYOUT["sh"], L.BASIS["real"],
+                                            B, C.byref(h)))
+    st = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(st.cuda_stream)
+    na, nb = (B, nwin) if rotated else (0, 0)
+    aa = [p(a) if rotated else None for a in ang_blk]
+    ab = [p(a) if rotated else None for a in ang]
+
+    def side_a():
+        L.check(lib.emagls_decode_stream_push_device(h, p(d_blk), B, aa[0], na, aa[1], na, aa[2], na, p(d_out_a), sp))
+
+    def side_b():
+        L.check(lib.emagls_binaural_decode_render_ypr_device(p(d_win), 0, nwin, Cc, p(d_wL), p(d_wR), 0, ln, L.LAYOUT["sh"], L.BASIS["real"],
+                                                             ab[0], nb, ab[1], nb, ab[2], nb, None, 0, p(d_out_b), None, sp))
+
+    sides = [("stream", side_a)] + ([] if stream_only else [("window", side_b)])
+    times = {k: [] for k, _ in sides}
+    with torch.cuda.stream(st):
+        for _, f in sides:
+            for _ in range(warm):
+                f()
+        st.synchronize()
+        for _ in range(max(1, blocks // run)):
+            for k, f in sides:                       # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(run):
+                    f()
+                e1.record(st)
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / run)   # us per block
+    L.check(lib.emagls_decode_stream_destroy(h))
+    res = {"shape": [Cc, ln, B], "rotation": "ypr" if rotated else "none", "block_us": round(B / FS * 1e6, 1),
+           "bytes": push_bytes(Cc, ln, B, rotated)}
+    for k, v in times.items():
+        res[k] = {"median_us": round(float(np.median(v)), 2), "p99_us": round(float(np.percentile(v, 99)), 2), "min_us": round(float(np.min(v)), 2)}
+    if "window" in res:
+        res["window_over_stream"] = round(res["window"]["median_us"] / res["stream"]["median_us"], 2)
+    return res
+
+
+def markdown(rows, device):
+    lines = ["`python tools/decode_stream_timing.py` on %s: time per block in us (median and p99 of the run averages).  stream:" % device,
+             "`emagls_decode_stream_push_device`; window: `emagls_binaural_decode_render_ypr_device` on the last len - 1 + B samples.", "",
+             "| (C, len, B) | rotation | block us | stream median | stream p99 | window median | window p99 | window / stream | bytes per push |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        w = r.get("window", {"median_us": float("nan"), "p99_us": float("nan")})
+        lines.append("| %s | %s | %.0f | %.1f | %.1f | %.1f | %.1f | %s | %d |" % (
+            tuple(r["shape"]), r["rotation"], r["block_us"], r["stream"]["median_us"], r["stream"]["p99_us"], w["median_us"], w["p99_us"],
+            r.get("window_over_stream", "-"), r["bytes"]["total"]))
+    return "\n".join(lines) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=2000)
+    ap.add_argument("--warm", type=int, default=50)
+    ap.add_argument("--run", type=int, default=100)
+    ap.add_argument("--shapes", nargs="*", default=None, help="C,len,B ...")
+    ap.add_argument("--stream-only", action="store_true", help="only side (a): for a kernel trace of the stream alone")
+    ap.add_argument("--rotation", choices=["both", "none", "ypr"], default="both")
+    ap.add_argument("--dry-run", action="store_true")
+    ap.add_argument("--out", default=None, help="markdown table")
+    a = ap.parse_args()
+    if a.blocks < a.run or a.run < 1 or a.warm < 0:
+        raise SystemExit("--blocks must be at least --run, --run at least 1")
+    shapes = parse_shapes(a.shapes)
+    rots = {"both": (False, True), "none": (False,), "ypr": (True,)}[a.rotation]
+    if a.dry_run:
+        for s in shapes:
+            for r in rots:
+                print(json.dumps({"shape": s, "rotation": "ypr" if r else "none", "partitions": -(-s[1] // s[2]), "window": s[1] - 1 + s[2],
+                                  "block_us": round(s[2] / FS * 1e6, 1), "bytes": push_bytes(*s, r)}))
+        return 0
+    import torch
+    from emagls_amd import _lib as L
+    lib = L.load()
+    rows, ok = [], True
+    for s in shapes:
+        for r in rots:
+            res = run_shape(lib, L, torch, *s, r, a.blocks, a.warm, a.run, a.stream_only)
+            res["gate_realtime"] = res["stream"]["median_us"] < res["block_us"]
+            res["gate_faster"] = a.stream_only or res["stream"]["median_us"] < res["window"]["median_us"]
+            ok = ok and res["gate_realtime"] and res["gate_faster"]
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(markdown(rows, torch.cuda.get_device_name(0)))
+    print("gates:", "pass" if ok else "FAIL")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
