@@ -588,7 +588,13 @@ class BinauralDecodeStream:
     to rounding: no delay cut (offset your read by len/2 - 1 yourself), no resampling, no source signal; for complex signals or
     filters the output is the real part and the discarded imaginary sum is not reported.
     blockSize: a power of two from 64 to 2048.  complexInput: the pushed blocks are complex.  Uniformly partitioned overlap-save
-    with its state on the GPU; `info` gives block, partitions, state_bytes, filter_bytes and launches_per_block."""
+    with its state on the GPU; `info` gives block, partitions, state_bytes, filter_bytes and launches_per_block.
+    A bank: filters [numSets x len x numChannels] make a stream of `numSets` filter sets, and `push`
+    takes a set index per block.  A change of set is cross-faded over the block that changes: its sample i goes to the new set
+    with the gain (i + 1) / blockSize and to the old one with the rest; the first block after creation or reset does not fade.
+    The outputs equal sum_s binauralDecode(g_s * x, wL[s], wR[s]) with g_s the gain of set s per sample; a constant index gives
+    the bits of the plain stream on that set.  For designs on raw microphone signals, which no rotation can turn, a bank of
+    one set per head orientation (`designYawBank`, `yawBankIndex`) is what follows the head."""
 
     def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition="real", rotationDomain="sh", complexInput=False):
         self._h = None
@@ -597,15 +603,23 @@ class BinauralDecodeStream:
         w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
         wL = np.asfortranarray(np.asarray(decodingFilterLeft, dtype=np.complex128 if w_c else np.float64))
         wR = np.asfortranarray(np.asarray(decodingFilterRight, dtype=np.complex128 if w_c else np.float64))
-        if wL.ndim != 2 or wL.shape != wR.shape:
-            raise ValueError("filters must be [len x numChannels] arrays of equal shape")
+        if wL.ndim not in (2, 3) or wL.shape != wR.shape:
+            raise ValueError("filters must be [len x numChannels] or [numSets x len x numChannels] arrays of equal shape")
         if int(blockSize) != blockSize:
             raise ValueError("blockSize must be an integer")
-        self.blockSize, self.numChannels, self.complexInput = int(blockSize), wL.shape[1], bool(complexInput)
+        self.numSets = wL.shape[0] if wL.ndim == 3 else 1
+        if self.numSets < 1:
+            raise ValueError("a bank needs at least one filter set")
+        if wL.ndim == 3:    # the library takes the sets one after the other, each column-major [len x numChannels]
+            wL, wR = (np.ascontiguousarray(w.transpose(0, 2, 1)) for w in (wL, wR))
+            ln, self.numChannels = wL.shape[2], wL.shape[1]
+        else:
+            ln, self.numChannels = wL.shape
+        self.blockSize, self.complexInput = int(blockSize), bool(complexInput)
         h = C.c_void_p()
-        L.check(L.load().emagls_decode_stream_create(self.numChannels, wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p),
-                                                     1 if w_c else 0, wL.shape[0], 1 if complexInput else 0, self._layout, self._basis,
-                                                     self.blockSize, C.byref(h)))
+        L.check(L.load().emagls_decode_stream_create_bank(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
+                                                          wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
+                                                          self._layout, self._basis, self.blockSize, C.byref(h)))
         self._h = h
 
     @property
@@ -625,13 +639,30 @@ class BinauralDecodeStream:
             if a is not None and size(a) not in (1, n):
                 raise ValueError("%s must be a scalar or have one angle per input sample (%d), not %d" % (name, n, size(a)))
 
-    def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None):
+    def _set_index(self, setIndex, n):
+        """setIndex as an int32 array of 1 or n / blockSize values, checked against the bank (None: None)."""
+        if setIndex is None:
+            return None
+        a = np.asarray(setIndex)
+        if a.dtype.kind not in "iu":
+            raise ValueError("setIndex must be an integer or integers")
+        a = a.reshape(-1)
+        if a.size not in (1, n // self.blockSize):
+            raise ValueError("setIndex must be an integer or have one index per block (%d), not %d" % (n // self.blockSize, a.size))
+        if a.size and (a.min() < 0 or a.max() >= self.numSets):
+            raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None, setIndex=None):
         """block [n x numChannels], n a multiple of blockSize: a NumPy array (host entry; returns a NumPy array), or a torch tensor
         on the stream's device (device entry on torch's current stream, not synchronised; returns a torch tensor).  Each angle:
-        None (0), a scalar (constant over this push) or one value per sample; with torch blocks also device tensors."""
+        None (0), a scalar (constant over this push) or one value per sample; with torch blocks also device tensors.
+        setIndex: None (every block keeps the set of the block before it; set 0 on a fresh stream), an int (every block of this
+        push) or one int per block; with torch blocks also a device int32 tensor, which is not read on the host: the kernels then
+        clamp its values into [0, numSets - 1]."""
         h = self._handle()
         if type(block).__module__.split(".")[0] == "torch":
-            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad)
+            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
         if np.iscomplexobj(block) and not self.complexInput:
             raise ValueError("the stream was created for real blocks (complexInput=False)")
         x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
@@ -642,8 +673,10 @@ class BinauralDecodeStream:
             if self._layout != L.LAYOUT["sh"]:
                 raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
             _sh_order(self.numChannels)
+        sets = self._set_index(setIndex, n)
         out, po = _out(n, 2, False)
-        L.check(L.load().emagls_decode_stream_push(h, x.ctypes.data_as(C.c_void_p), n, *_vp(yaw), *_vp(pitch), *_vp(roll), po))
+        ps, ns = (None, 0) if sets is None else (sets.ctypes.data_as(C.c_void_p), sets.size)
+        L.check(L.load().emagls_decode_stream_push_sets(h, x.ctypes.data_as(C.c_void_p), n, ps, ns, *_vp(yaw), *_vp(pitch), *_vp(roll), po))
         return out
 
     def _check_block(self, shape, ndim):
@@ -653,7 +686,7 @@ class BinauralDecodeStream:
             raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
         return shape[0]
 
-    def _push_torch(self, h, block, hor, pitch, roll):
+    def _push_torch(self, h, block, hor, pitch, roll, setIndex=None):
         import torch
         n = self._check_block(tuple(block.shape), block.dim())
         if not block.is_cuda:
@@ -676,12 +709,24 @@ class BinauralDecodeStream:
             raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
         if npi or nr:
             _sh_order(self.numChannels)
+        ts, ns = None, 0
+        if torch.is_tensor(setIndex):
+            if setIndex.dtype != torch.int32:
+                raise ValueError("a setIndex tensor must be int32")
+            ts = setIndex.to(device=block.device).reshape(-1).contiguous()
+            ns = ts.numel()
+            if ns not in (1, n // self.blockSize):
+                raise ValueError("setIndex must be an integer or have one index per block (%d), not %d" % (n // self.blockSize, ns))
+        elif setIndex is not None:
+            ts = torch.as_tensor(self._set_index(setIndex, n), device=block.device)
+            ns = ts.numel()
         out = torch.empty((2, n), dtype=torch.float64, device=block.device)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
         with torch.cuda.device(block.device):
             st = torch.cuda.current_stream().cuda_stream
-            L.check(L.load().emagls_decode_stream_push_device(h, p(xt), n, p(ty), ny, p(tp), npi, p(tr), nr, p(out), C.c_void_p(st)))
-        for t in (xt, ty, tp, tr):      # (their memory may be reused only after the stream has passed the enqueued kernels)
+            L.check(L.load().emagls_decode_stream_push_sets_device(h, p(xt), n, p(ts), ns, p(ty), ny, p(tp), npi, p(tr), nr, p(out),
+                                                                   C.c_void_p(st)))
+        for t in (xt, ty, tp, tr, ts):      # (their memory may be reused only after the stream has passed the enqueued kernels)
             if t is not None:
                 t.record_stream(torch.cuda.current_stream(block.device))
         return out.t()
@@ -706,6 +751,63 @@ class BinauralDecodeStream:
             self.close()
         except Exception:
             pass
+
+
+def designYawBank(kind, hL, hR, hrirGridAziRad, hrirGridZenRad, yawRad, *, order=4, fs=48000.0, len=512, shDefinition="real",
+                  micRadius=0.0, micGridAziRad=None, micGridZenRad=None, atfIrs=None, atfGridAziZenRad=None, fTrans=0.0):
+    """A bank of filter sets for BinauralDecodeStream, one per head yaw: set j is the design `kind` on the HRIR grid turned against
+    the head, hrirGridAziRad - yawRad[j], one job per angle on the library's job list (jobs.JobList).  kind: 'ls', 'magls'
+    (order, fs, len, shDefinition), 'emagls', 'emagls2' (also micRadius, micGridAziRad, micGridZenRad) or 'fromatf' (atfIrs
+    [taps x numMics x numAtfDirections], atfGridAziZenRad, fs, len, fTrans).  Returns (wL, wR) of shape
+    [len(yawRad) x len x numChannels] ('ls': the HRIRs' length).  The sign is the stream's yaw rule: set j
+    renders what turning the sound field by +yawRad[j] and decoding with the set for 0 renders -- for LS filters an identity
+    to rounding."""
+    from .batch import _out_shape
+    from .jobs import JobList
+    kinds = {"ls": L.KIND_LS, "magls": L.KIND_MAGLS, "emagls": L.KIND_EMAGLS, "emagls2": L.KIND_EMAGLS2, "fromatf": L.KIND_FROM_ATF}
+    if kind not in kinds:
+        raise ValueError("kind must be one of %s" % sorted(kinds))
+    hL = np.asfortranarray(hL, dtype=np.float64)
+    hR = np.asfortranarray(hR, dtype=np.float64)
+    if hL.ndim != 2 or hL.shape != hR.shape:
+        raise ValueError("hL / hR must be equal-shaped [numSamples x numDirections] arrays")
+    azi, _ = _vec(hrirGridAziRad, hL.shape[1], "hrirGridAziRad")
+    zen, _ = _vec(hrirGridZenRad, hL.shape[1], "hrirGridZenRad")
+    yaw = np.asarray(yawRad, dtype=np.float64).reshape(-1)
+    if yaw.size < 1:
+        raise ValueError("yawRad must hold at least one angle")
+    kw = dict(kind=kinds[kind], basis=shDefinition, order=int(order), fs=float(fs), length=int(len), hL=hL, hR=hR, hrir_zen=zen)
+    if kind in ("emagls", "emagls2"):
+        if micGridAziRad is None or micGridZenRad is None:
+            raise ValueError("kind '%s' needs micRadius, micGridAziRad and micGridZenRad" % kind)
+        maz, _ = _vec(micGridAziRad)
+        mzn, _ = _vec(micGridZenRad, maz.size, "micGridZenRad")
+        kw.update(mic_radius=float(micRadius), mic_azi=maz, mic_zen=mzn)
+    if kind == "fromatf":
+        if atfIrs is None or atfGridAziZenRad is None:
+            raise ValueError("kind 'fromatf' needs atfIrs and atfGridAziZenRad")
+        ag = np.asarray(atfGridAziZenRad, dtype=np.float64)
+        kw.update(basis="real", order=0, atf=np.asfortranarray(atfIrs, dtype=np.float64), atf_azi=np.ascontiguousarray(ag[:, 0]),
+                  atf_zen=np.ascontiguousarray(ag[:, 1]), f_trans=float(fTrans))
+    shape = _out_shape(dict(kw, hrir_azi=azi))
+    jl = JobList()
+    for t in yaw:
+        jl.add(hrir_azi=azi - t, out_shape=shape, **kw)
+    jl.run()
+    res = jl.results()
+    return np.stack([r[0] for r in res]), np.stack([r[1] for r in res])
+
+
+def yawBankIndex(yawRad, numSets):
+    """The set of a uniform yaw bank (set j designed for the yaw 2 pi j / numSets, as designYawBank(..., yawRad =
+    2 pi arange(numSets) / numSets)) that is nearest to yawRad, for a scalar (an int) or an array (an int32 array of its shape);
+    any angle, negative and multi-turn ones included."""
+    S = int(numSets)
+    if S < 1:
+        raise ValueError("numSets must be at least 1")
+    a = np.asarray(yawRad, dtype=np.float64)
+    j = np.mod(np.rint(a * (S / (2.0 * np.pi))), S).astype(np.int32)   # (mod of an integer-valued double by S: exact, in [0, S - 1])
+    return int(j) if j.ndim == 0 else j
 
 
 # --------------------------------------------------------------------------------------------

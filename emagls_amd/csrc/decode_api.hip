@@ -480,8 +480,8 @@ int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, do
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// The decode stream (decode_stream.hip).  The object owns its device buffers: emagls_cache_clear() does
-// not reach them.
+// The decode stream (decode_stream.hip; DESIGN.md sections 9.3 and 9.4).  The object owns its device buffers:
+// emagls_cache_clear() does not reach them.
 // ---------------------------------------------------------------------------------------------
 struct emagls_decode_stream {
     std::mutex mu;
@@ -490,15 +490,18 @@ struct emagls_decode_stream {
     bool in_c = false;
     int device = -1;              // bound at the first use of the device (creation, when there is one)
     bool ready = false;
-    std::vector<double> wpl;      // [2][Cp][len] the real filter planes [re w; -im w], until the device has their spectra
+    std::vector<double> wpl;      // [S][2][Cp][len] the real filter planes [re w; -im w], until the device has their spectra
     DecodeStreamState d;
     void* xrot = nullptr;         // [nch][B] the rotated block (cplx when the signal or the basis is complex)
-    void* stage[3] = {};          // host entry: the push's input, angles and output on the device, grown on demand and kept
-    size_t stage_cap[3] = {};
+    void* stage[4] = {};          // host entry: the push's input, angles, output and set indices on the device, grown on demand and kept
+    size_t stage_cap[4] = {};
+    int known[2] = {-1, -1};      // what the host knows of the selection state on the device: the set indices of the two previous
+                                  // blocks, -1: none yet, -2: not known (a push took its indices from device memory)
     int cp() const { return d.planes2 ? 2 * d.C : d.C; }
     size_t ring_bytes() const { return sizeof(cplx) * 2 * (size_t)d.P * (d.B + 1); }
     size_t hist_bytes() const { return esz(d.planes2) * (size_t)d.C * d.B; }
-    size_t filter_bytes() const { return sizeof(cplx) * 2 * (size_t)d.P * cp() * (d.B + 1); }
+    size_t filter_bytes() const { return sizeof(cplx) * (size_t)d.S * 2 * (size_t)d.P * cp() * (d.B + 1); }
+    size_t pos_bytes() const { return sizeof(int) * (d.S > 1 ? 3 : 1); }   // the ring position; with a bank, the two previous set indices
     void release() {
         hipFree(d.Wf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos); hipFree(xrot);
         for (void*& p : stage) { hipFree(p); p = nullptr; }
@@ -509,6 +512,8 @@ struct emagls_decode_stream {
         HIP_CHECK(hipMemsetAsync(d.ring, 0, ring_bytes(), st));
         HIP_CHECK(hipMemsetAsync(d.hist, 0, hist_bytes(), st));
         HIP_CHECK(hipMemsetAsync(d.pos, 0, sizeof(int), st));
+        if (d.S > 1) HIP_CHECK(hipMemsetAsync(d.pos + 1, 0xff, 2 * sizeof(int), st));   // -1: no block yet
+        known[0] = known[1] = -1;
     }
     // the device side, once: buffers, the partition spectra, zero history (mu held)
     void ensure_device() {
@@ -518,10 +523,10 @@ struct emagls_decode_stream {
             HIP_CHECK(hipMalloc(&d.Wf, filter_bytes()));
             HIP_CHECK(hipMalloc(&d.ring, ring_bytes()));
             HIP_CHECK(hipMalloc(&d.hist, hist_bytes()));
-            HIP_CHECK(hipMalloc(&d.pos, sizeof(int)));
+            HIP_CHECK(hipMalloc(&d.pos, pos_bytes()));
             HIP_CHECK(hipMalloc(&xrot, sizeof(cplx) * (size_t)d.C * d.B));
             Scratch s;
-            launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.Wf, s.st);
+            launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.S, d.Wf, s.st);
             zero_state(s.st);
             HIP_CHECK(hipStreamSynchronize(s.st));
         } catch (...) { release(); device = -1; throw; }
@@ -537,14 +542,23 @@ struct emagls_decode_stream {
 
 namespace {
 
-void stream_check_push(const emagls_decode_stream* s, const void* in, const void* out, int64_t nsamp, const Angles& a) {
+constexpr int64_t kDecodeStreamMaxSets = 65536;
+
+// the set indices of a push: 0 values (the set of the previous block), 1 (every block of the push) or one per block
+struct Sets { const int32_t* p = nullptr; int64_t n = 0; const int32_t* host = nullptr; /* the same values, where the host has them */ };
+
+void stream_check_push(const emagls_decode_stream* s, const void* in, const void* out, int64_t nsamp, const Angles& a, const Sets& sets = {}) {
     if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
     if (nsamp < 0 || nsamp % s->d.B) throw Error(EMAGLS_ERR_ARG, "a push needs a multiple of the block size of samples");
+    if (sets.n != 0 && sets.n != 1 && sets.n != nsamp / s->d.B)
+        throw Error(EMAGLS_ERR_ARG, "a push takes 0 set indices, 1, or one per block");
+    if (sets.n && !sets.p) throw Error(EMAGLS_ERR_ARG, "null pointer");
     check_args(true, {in, out}, nsamp, s->nch, s->len, 0, s->layout, s->basis, a);
 }
 
 // k blocks in order on st; device pointers; not synchronised (s->mu held, device current)
-void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const Angles& a, double* d_out, hipStream_t st) {
+void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const Angles& a, const Sets& sets, double* d_out,
+                        hipStream_t st) {
     s->ensure_device();
     const int64_t B = s->d.B;
     const bool cb = s->basis == EMAGLS_BASIS_COMPLEX;
@@ -559,7 +573,17 @@ void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp
             launch_rotation(blk, x, x_c, B, (int)s->nch, s->layout, cb, false, s->xrot, st, nsamp, B);
             x = s->xrot; x_c = x_c || cb; ldx = B;
         }
-        launch_decode_stream_block(s->d, x, x_c, ldx, d_out + b * B, nsamp, st);
+        // the host's copy of the selection, moved on as the kernels move theirs: three equal known indices are a standing set
+        int cur = -2, standing = -1;
+        if (sets.n == 0) cur = s->known[0] == -2 ? -2 : std::max(s->known[0], 0);
+        else if (sets.host) cur = sets.host[sets.n > 1 ? b : 0];
+        if (cur >= 0) {
+            const int s1 = s->known[0] == -1 ? cur : s->known[0], s2 = s->known[1] == -1 ? s1 : s->known[1];
+            if (s1 == cur && s2 == cur) standing = cur;
+        }
+        s->known[1] = s->known[0] == -1 ? cur : s->known[0];
+        s->known[0] = cur;
+        launch_decode_stream_block(s->d, x, x_c, ldx, sets.n > 1 ? sets.p + b : sets.p, standing, d_out + b * B, nsamp, st);
     }
 }
 
@@ -569,10 +593,17 @@ extern "C" {
 
 int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
                                 int layout, int basis, int64_t block, emagls_decode_stream** out) {
+    return emagls_decode_stream_create_bank(nch, 1, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, out);
+}
+
+int emagls_decode_stream_create_bank(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
+                                     int in_is_complex, int layout, int basis, int64_t block, emagls_decode_stream** out) {
     return guarded_call([&] {
         if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
         *out = nullptr;
         if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        if (n_sets < 1) throw Error(EMAGLS_ERR_ARG, "a decode stream needs at least one filter set");
+        if (n_sets > kDecodeStreamMaxSets) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports banks of up to 65536 filter sets");
         if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
         check_basis(basis);
         if (!decode_stream_block_ok(block))
@@ -580,21 +611,23 @@ int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int
         if (len > 16384) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports filters of up to 16384 taps");
         std::unique_ptr<emagls_decode_stream> s(new emagls_decode_stream);
         s->nch = nch; s->len = len; s->layout = layout; s->basis = basis; s->in_c = in_is_complex != 0;
-        s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block);
+        s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block); s->d.S = (int)n_sets;
         // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
         s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
         const int Cp = s->cp();
         const bool wc = filters_are_complex != 0;
-        s->wpl.assign((size_t)2 * Cp * len, 0.0);
-        for (int e = 0; e < 2; ++e) {
-            const double* w = reinterpret_cast<const double*>(e ? wR : wL);
-            for (int64_t c = 0; c < nch; ++c)
-                for (int64_t t = 0; t < len; ++t) {
-                    const size_t i = (size_t)(c * len + t);
-                    s->wpl[((size_t)e * Cp + c) * len + t] = wc ? w[2 * i] : w[i];
-                    if (wc && s->d.planes2) s->wpl[((size_t)e * Cp + nch + c) * len + t] = -w[2 * i + 1];
-                }
-        }
+        s->wpl.assign((size_t)n_sets * 2 * Cp * len, 0.0);
+        for (int64_t set = 0; set < n_sets; ++set)
+            for (int e = 0; e < 2; ++e) {
+                const double* w = reinterpret_cast<const double*>(e ? wR : wL) + (size_t)set * nch * len * (wc ? 2 : 1);
+                double* pl = s->wpl.data() + ((size_t)set * 2 + e) * Cp * len;
+                for (int64_t c = 0; c < nch; ++c)
+                    for (int64_t t = 0; t < len; ++t) {
+                        const size_t i = (size_t)(c * len + t);
+                        pl[(size_t)c * len + t] = wc ? w[2 * i] : w[i];
+                        if (wc && s->d.planes2) pl[(size_t)(nch + c) * len + t] = -w[2 * i + 1];
+                    }
+            }
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
             std::lock_guard<std::mutex> lk(s->mu);
@@ -609,23 +642,38 @@ int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int
 int emagls_decode_stream_push_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const double* d_yaw, int64_t n_yaw,
                                      const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll, double* d_out,
                                      void* stream) {
+    return emagls_decode_stream_push_sets_device(s, d_in, nsamp, nullptr, 0, d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll, d_out, stream);
+}
+
+int emagls_decode_stream_push_sets_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
+                                          const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll,
+                                          int64_t n_roll, double* d_out, void* stream) {
     return guarded_call([&] {
         const Angles a{d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll};
-        stream_check_push(s, d_in, d_out, nsamp, a);
+        const Sets sets{d_set, n_set};
+        stream_check_push(s, d_in, d_out, nsamp, a, sets);
         if (nsamp == 0) return;
         std::lock_guard<std::mutex> lk(s->mu);
         DeviceGuard dg(s->device);
-        stream_push_blocks(s, d_in, nsamp, a, d_out, (hipStream_t)stream);
+        stream_push_blocks(s, d_in, nsamp, a, sets, d_out, (hipStream_t)stream);   // (the kernels clamp the indices: the host never sees them)
     });
 }
 
 int emagls_decode_stream_push(emagls_decode_stream* s, const void* in, int64_t nsamp, const double* yaw, int64_t n_yaw, const double* pitch,
                               int64_t n_pitch, const double* roll, int64_t n_roll, double* out) {
+    return emagls_decode_stream_push_sets(s, in, nsamp, nullptr, 0, yaw, n_yaw, pitch, n_pitch, roll, n_roll, out);
+}
+
+int emagls_decode_stream_push_sets(emagls_decode_stream* s, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set,
+                                   const double* yaw, int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll,
+                                   int64_t n_roll, double* out) {
     return guarded_call([&] {
         Angles a{yaw, n_yaw, pitch, n_pitch, roll, n_roll};
         auto counted = [&](int64_t n) { return n >= 0 && (n <= 1 || n == nsamp); };
         if (counted(n_pitch) && counted(n_roll)) a = host_angles(a);   // (zeros in a count that does not fit are reported, not dropped)
-        stream_check_push(s, in, out, nsamp, a);
+        stream_check_push(s, in, out, nsamp, a, {set, n_set});
+        for (int64_t i = 0; i < n_set; ++i)
+            if (set[i] < 0 || set[i] >= s->d.S) throw Error(EMAGLS_ERR_ARG, "set index outside the stream's bank");
         if (nsamp == 0) return;
         std::lock_guard<std::mutex> lk(s->mu);
         DeviceGuard dg(s->device);
@@ -644,7 +692,13 @@ int emagls_decode_stream_push(emagls_decode_stream* s, const void* in, int64_t n
             return dst;
         };
         const Angles da{up(a.yaw, a.n_yaw, 0), a.n_yaw, up(a.pitch, a.n_pitch, 1), a.n_pitch, up(a.roll, a.n_roll, 2), a.n_roll};
-        stream_push_blocks(s, d_in, nsamp, da, d_out, st);
+        Sets dsets{nullptr, n_set, set};
+        if (n_set) {
+            int32_t* d_set = s->staged<int32_t>(3, sizeof(int32_t) * (size_t)n_set);
+            HIP_CHECK(hipMemcpyAsync(d_set, set, sizeof(int32_t) * (size_t)n_set, hipMemcpyHostToDevice, st));
+            dsets.p = d_set;
+        }
+        stream_push_blocks(s, d_in, nsamp, da, dsets, d_out, st);
         HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * nsamp, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
     });
@@ -668,9 +722,17 @@ int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int
         if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
         if (block) *block = s->d.B;
         if (partitions) *partitions = s->d.P;
-        if (state_bytes) *state_bytes = (int64_t)(s->ring_bytes() + s->hist_bytes() + sizeof(int));
+        if (state_bytes) *state_bytes = (int64_t)(s->ring_bytes() + s->hist_bytes() + s->pos_bytes());
         if (filter_bytes) *filter_bytes = (int64_t)s->filter_bytes();
         if (launches_per_block) *launches_per_block = 3;   // rotation, forward transform with the products, inverse transform
+    });
+}
+
+int emagls_decode_stream_sets(const emagls_decode_stream* s, int64_t* n_sets) {
+    return guarded_call([&] {
+        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+        if (!n_sets) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *n_sets = s->d.S;
     });
 }
 

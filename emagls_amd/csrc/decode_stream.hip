@@ -18,6 +18,14 @@
 //                       ring position (device memory) one step on; the other workgroups keep the block as the next overlap.
 // A complex signal (or a real one turned in the complex basis) is decoded as 2C real planes [re x; im x] against the filters
 // [re w; -im w] (decode.hip, binaural_decode_complex): a complex sample IS the packed pair of its two planes, so it is read as it lies.
+//
+// A bank of S filter sets: every block t has a set index s_t, and a change of set is cross-faded on the INPUT
+// side over the block that changes: its sample i goes to the new set with the gain r[i] = (i + 1) / B and to the old one with
+// 1 - r[i].  The window [x_(t-1), x_t] therefore meets up to three sets, s_(t-2), s_(t-1), s_t; for every distinct one, oldest role
+// first, the forward kernel transforms the window under that set's gains (each half one of 0, 1, r, 1 - r, applied to the registers
+// the samples wait in between global memory and LDS) and accumulates with that set's spectra into the same sums.  Three equal
+// indices are one pass without a gain: the plain stream's arithmetic.  The indices of the two previous blocks live beside the ring
+// position and move on with it.
 #include "kernels.hpp"
 #include "lds_fft.hpp"
 
@@ -27,6 +35,7 @@ namespace {
 
 constexpr int DS_NT = 512;     // threads of every kernel here
 constexpr int DS_ELEMS = 4096; // elements of the transform buffer: DS_ELEMS / Nf transforms per round, 8 loads per thread
+enum { DS_G_ZERO = 0, DS_G_ONE = 1, DS_G_R = 2, DS_G_1MR = 3 };   // gain of a set over a block: 0, 1, r[i] = (i + 1) / B, 1 - r[i]
 
 __device__ __forceinline__ void ds_twiddles(cplx* tws, int Nf) {
     for (int j = threadIdx.x; j < Nf / 2; j += DS_NT) {
@@ -42,7 +51,8 @@ __device__ __forceinline__ void ds_unpack(cplx z, cplx zr /* conj(Z[N-k]) */, cp
     pb = mk(0.5 * (z.y - zr.y), -0.5 * (z.x - zr.x));
 }
 
-// Wf[e][p][c][k] (k <= B) = FFT([w_e,c(pB .. pB + B - 1), 0])[k]; wpl [2][Cp][len] real planes.  grid (pairs of planes, P, 2)
+// Wf[z][p][c][k] (k <= B) = FFT([w_z,c(pB .. pB + B - 1), 0])[k], z = 2 set + ear; wpl [Z][Cp][len] real planes.
+// grid (pairs of planes, P, Z): Z = the (set, ear) pairs of this launch (the launcher cuts a large bank into several)
 __global__ void __launch_bounds__(DS_NT) ds_filter_kernel(const double* __restrict__ wpl, int Cp, int64_t len, int B, int log2n, int P,
                                                           cplx* __restrict__ Wf) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
@@ -73,10 +83,13 @@ __global__ void __launch_bounds__(DS_NT) ds_filter_kernel(const double* __restri
 // One block into the ring.  xnew: the block, channel c at xnew + c ldx (double, or cplx when x_cplx); hist [C][B]: the previous
 // block (cplx when planes2, else double).  planes2: 2C planes, pair p = complex channel p = planes (p, p + C); else pair p = the
 // real channels (2p, 2p + 1).  KU: frequency bins per thread (B + 1 <= KU * DS_NT).  grid (P, 2)
-template <int KU>
+// BANK: Wf holds S sets; set_p: this block's index (null: the previous block's, 0 on a fresh stream), clamped into [0, S - 1] before
+// it forms an address; sel: the indices of the blocks t - 1 and t - 2 (-1: none yet, the block then does not fade).
+template <int KU, bool BANK>
 __global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restrict__ xnew, int x_cplx, int64_t ldx, const void* __restrict__ hist,
                                                            int C, int planes2, const cplx* __restrict__ Wf, int B, int log2n, int P,
-                                                           const int* __restrict__ pos_p, cplx* __restrict__ ring) {
+                                                           const int* __restrict__ pos_p, cplx* __restrict__ ring,
+                                                           const int* __restrict__ set_p, const int* __restrict__ sel, int S) {
     constexpr int NLD = DS_ELEMS / DS_NT;
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     const int Nf = 2 * B, Pf = B + 1, mask = Nf - 1;
@@ -118,18 +131,47 @@ __global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restric
             xv[j] = v;
         }
     };
-    const cplx* Wp = Wf + ((int64_t)e * P + part) * Cp * Pf;
-    fetch(0);
-    for (int p0 = 0; p0 < npairs; p0 += NTP) {
+    fetch(0);   // (issued ahead of the selection's dependent loads: the samples do not depend on the sets)
+    int s0 = 0, s1 = 0, s2 = 0;   // sigma_t, sigma_(t-1), sigma_(t-2)
+    int nu = 1, u1 = 0, u2 = 0;   // the distinct sets of the window, oldest role first: s2, then u1, then u2
+    if (BANK) {
+        const int p1 = min(sel[0], S - 1), p2 = min(sel[1], S - 1);
+        s0 = set_p ? min(max(*set_p, 0), S - 1) : max(p1, 0);
+        s1 = p1 < 0 ? s0 : p1;
+        s2 = p2 < 0 ? s1 : p2;
+        if (s1 != s2) { u1 = s1; nu = 2; if (s0 != s1 && s0 != s2) { u2 = s0; nu = 3; } }
+        else if (s0 != s1) { u1 = s0; nu = 2; }
+    }
+    const double invB = 1.0 / (double)B;
+    const int nr = (npairs + NTP - 1) / NTP;   // rounds per set
+    // one loop over (set, round): per set the plain stream's rounds, the sums carried from set to set
+    int p0 = 0, q = 0;
+#pragma unroll 1
+    for (int it = 0; it < nu * nr; ++it) {
         const int np = min(NTP, npairs - p0);
+        const int set = q == 0 ? s2 : q == 1 ? u1 : u2;
+        // the gain shapes of the window's two halves under this set: its gains in block t - 1 and in block t
+        const int ga = set == s1 ? (s1 == s2 ? DS_G_ONE : DS_G_R) : set == s2 ? DS_G_1MR : DS_G_ZERO;
+        const int gb = set == s0 ? (s0 == s1 ? DS_G_ONE : DS_G_R) : set == s1 ? DS_G_1MR : DS_G_ZERO;
+        const cplx* Wp = Wf + (((int64_t)set * 2 + e) * P + part) * Cp * Pf;
         __syncthreads();   // the previous round's spectra have been read (first round: the twiddles are written)
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
             const int idx = tid + DS_NT * j;
             const int t = idx >> log2n, i = idx & mask;
+            if (BANK) {   // the gains, on the way from the registers to LDS
+                const int shape = i < B ? ga : gb;
+                if (shape != DS_G_ONE) {   // (a gain of 1 is not multiplied: a constant index gives the plain stream's bits)
+                    const double r = (double)((i & (B - 1)) + 1) * invB;   // exact: B is a power of two
+                    const double g = shape == DS_G_R ? r : shape == DS_G_1MR ? 1.0 - r : 0.0;
+                    xv[j].x *= g; xv[j].y *= g;
+                }
+            }
             if (t < np) buf[lds_fft_ix<true>((t << log2n) + (int)bitrev((unsigned)i, log2n))] = xv[j];
         }
-        if (p0 + NTP < npairs) fetch(p0 + NTP);
+        int p0n = p0 + NTP, qn = q;
+        if (p0n >= npairs) { p0n = 0; ++qn; }
+        if (qn < nu) fetch(p0n);
         __syncthreads();
         lds_fft_stages<false, true>(buf, tws, Nf, log2n, np);
 #pragma unroll
@@ -149,6 +191,7 @@ __global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restric
                 }
             }
         }
+        p0 = p0n; q = qn;
     }
     __syncthreads();
     if (G > 1) {   // the groups' partial sums meet in LDS; group 0 adds them in the order of the groups
@@ -174,10 +217,13 @@ __global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restric
 }
 
 // workgroup 0: out[i] (left), out[ldo + i] (right) = the last B samples of IFFT(ring slot `pos`) -- both ears in one packed
-// transform, Y_L + i Y_R with Y_e[N - k] = conj(Y_e[k]) -- and pos <- (pos + 1) mod P.  The other workgroups: hist <- the block
+// transform, Y_L + i Y_R with Y_e[N - k] = conj(Y_e[k]) -- and pos <- (pos + 1) mod P; with a bank (sel not null) the same thread
+// moves the selection on: sel <- (this block's index as the forward kernel took it, the previous block's).  The other workgroups:
+// hist <- the block
 __global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restrict__ ring, int B, int log2n, int P, int* __restrict__ pos_p,
                                                            double* __restrict__ out, int64_t ldo, const void* __restrict__ xnew, int x_cplx,
-                                                           int64_t ldx, void* __restrict__ hist, int planes2, int C) {
+                                                           int64_t ldx, void* __restrict__ hist, int planes2, int C,
+                                                           const int* __restrict__ set_p, int* __restrict__ sel, int S) {
     const int tid = threadIdx.x;
     if (blockIdx.x > 0) {
         const int64_t total = (int64_t)C * B;
@@ -194,8 +240,14 @@ __global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restric
     const int Nf = 2 * B, Pf = B + 1;
     cplx* buf = reinterpret_cast<cplx*>(dyn);      // [Nf], padded
     cplx* tws = buf + (Nf + Nf / 16);               // [Nf / 2]
-    ds_twiddles(tws, Nf);
     const int pos = *pos_p;
+    int sel_new0 = 0, sel_new1 = 0;   // the selection after this block, read ahead of the transform
+    if (sel) {
+        const int p1 = min(sel[0], S - 1);
+        sel_new0 = set_p ? min(max(*set_p, 0), S - 1) : max(p1, 0);
+        sel_new1 = p1 < 0 ? sel_new0 : p1;
+    }
+    ds_twiddles(tws, Nf);
     const cplx* yl = ring + (int64_t)pos * Pf;
     const cplx* yr = ring + ((int64_t)P + pos) * Pf;
     for (int k = tid; k < Pf; k += DS_NT) {
@@ -211,7 +263,10 @@ __global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restric
         out[i] = y.x * scale;
         out[ldo + i] = y.y * scale;
     }
-    if (tid == 0) *pos_p = pos + 1 == P ? 0 : pos + 1;
+    if (tid == 0) {
+        *pos_p = pos + 1 == P ? 0 : pos + 1;
+        if (sel) { sel[1] = sel_new1; sel[0] = sel_new0; }
+    }
 }
 
 size_t ds_forward_lds(int B) { return sizeof(cplx) * ((size_t)DS_ELEMS + DS_ELEMS / 16 + (size_t)B); }
@@ -224,10 +279,14 @@ void ds_attributes() {
 #define EMAGLS_DS_ATTR(K) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024))
     EMAGLS_DS_ATTR(ds_filter_kernel);
     EMAGLS_DS_ATTR(ds_inverse_kernel);
-    EMAGLS_DS_ATTR(ds_forward_kernel<1>);
-    EMAGLS_DS_ATTR(ds_forward_kernel<2>);
-    EMAGLS_DS_ATTR(ds_forward_kernel<3>);
-    EMAGLS_DS_ATTR(ds_forward_kernel<5>);
+    EMAGLS_DS_ATTR((ds_forward_kernel<1, false>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<2, false>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<3, false>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<5, false>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<1, true>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<2, true>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<3, true>));
+    EMAGLS_DS_ATTR((ds_forward_kernel<5, true>));
 #undef EMAGLS_DS_ATTR
 }
 
@@ -235,25 +294,37 @@ void ds_attributes() {
 
 bool decode_stream_block_ok(int64_t B) { return B >= 64 && B <= 2048 && (B & (B - 1)) == 0; }
 
-void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, cplx* Wf, hipStream_t st) {
+void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, int64_t S, cplx* Wf, hipStream_t st) {
     ds_attributes();
-    const dim3 grid((unsigned)((Cp + 1) / 2), (unsigned)P, 2);
-    ds_filter_kernel<<<grid, DS_NT, ds_single_lds(B), st>>>(wpl, Cp, len, B, ds_log2(2 * B), P, Wf);
-    KERNEL_CHECK();
+    // the kernel's "ear" index runs over the 2 S (set, ear) pairs: wpl [S][2] and Wf [S][2] are both laid out that way
+    constexpr int64_t kPairs = 32768;   // (set, ear) pairs per launch: grid.z stays below 65536
+    for (int64_t z0 = 0; z0 < 2 * S; z0 += kPairs) {
+        const dim3 grid((unsigned)((Cp + 1) / 2), (unsigned)P, (unsigned)std::min<int64_t>(kPairs, 2 * S - z0));
+        ds_filter_kernel<<<grid, DS_NT, ds_single_lds(B), st>>>(wpl + z0 * Cp * len, Cp, len, B, ds_log2(2 * B), P,
+                                                               Wf + z0 * P * Cp * (int64_t)(B + 1));
+        KERNEL_CHECK();
+    }
 }
 
-void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, double* out, int64_t ldo, hipStream_t st) {
+void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, const int* set, int standing, double* out,
+                                int64_t ldo, hipStream_t st) {
     ds_attributes();
     const int log2n = ds_log2(2 * s.B), Pf = s.B + 1, ku = (Pf + DS_NT - 1) / DS_NT;
     const dim3 grid((unsigned)s.P, 2);
     const size_t dyn = ds_forward_lds(s.B);
-#define EMAGLS_DS_GO(KU) ds_forward_kernel<KU><<<grid, DS_NT, dyn, st>>>(x, x_cplx ? 1 : 0, ldx, s.hist, s.C, s.planes2 ? 1 : 0, s.Wf, s.B, log2n, s.P, s.pos, s.ring)
-    if (ku == 1) EMAGLS_DS_GO(1); else if (ku == 2) EMAGLS_DS_GO(2); else if (ku == 3) EMAGLS_DS_GO(3); else EMAGLS_DS_GO(5);
+    int* sel = s.S > 1 ? s.pos + 1 : nullptr;   // (a bank of one set has no selection to keep)
+    // a window the host knows to meet one set alone runs the plain instance on that set's spectra: the same arithmetic, without
+    // the selection's loads (the inverse kernel still moves the selection on)
+    const cplx* Wf = s.Wf + (standing > 0 ? (int64_t)standing * 2 * s.P * (s.planes2 ? 2 * s.C : s.C) * Pf : 0);
+#define EMAGLS_DS_GO(KU, BANK) ds_forward_kernel<KU, BANK><<<grid, DS_NT, dyn, st>>>(x, x_cplx ? 1 : 0, ldx, s.hist, s.C, s.planes2 ? 1 : 0, Wf, s.B, log2n, s.P, s.pos, s.ring, set, sel, s.S)
+#define EMAGLS_DS_KU(BANK) if (ku == 1) EMAGLS_DS_GO(1, BANK); else if (ku == 2) EMAGLS_DS_GO(2, BANK); else if (ku == 3) EMAGLS_DS_GO(3, BANK); else EMAGLS_DS_GO(5, BANK)
+    if (sel && standing < 0) { EMAGLS_DS_KU(true); } else { EMAGLS_DS_KU(false); }
+#undef EMAGLS_DS_KU
 #undef EMAGLS_DS_GO
     KERNEL_CHECK();
     const unsigned ncopy = (unsigned)std::min<int64_t>(32, ceil_div((int64_t)s.C * s.B, 4 * DS_NT));
     ds_inverse_kernel<<<1 + ncopy, DS_NT, ds_single_lds(s.B), st>>>(s.ring, s.B, log2n, s.P, s.pos, out, ldo, x, x_cplx ? 1 : 0, ldx, s.hist,
-                                                                  s.planes2 ? 1 : 0, s.C);
+                                                                  s.planes2 ? 1 : 0, s.C, set, sel, s.S);
     KERNEL_CHECK();
 }
 

@@ -233,16 +233,21 @@ struct DecodeStreamState {
     int C = 0;              // channels of the signal
     bool planes2 = false;   // the signal is decoded as 2C real planes [re x; im x] (complex signal, or complex basis with a rotation)
     int B = 0, P = 0;       // block size, partitions
-    cplx* Wf = nullptr;     // [2][P][Cp][B + 1] partition spectra, Cp = planes2 ? 2C : C
+    int S = 1;              // filter sets of the bank
+    cplx* Wf = nullptr;     // [S][2][P][Cp][B + 1] partition spectra, Cp = planes2 ? 2C : C
     cplx* ring = nullptr;   // [2][P][B + 1] pending output spectra
     void* hist = nullptr;   // [C][B] the previous block (cplx when planes2)
-    int* pos = nullptr;     // the ring slot of the next output block
+    int* pos = nullptr;     // the ring slot of the next output block; with S > 1 followed by the set indices of the two previous
+                            // blocks (-1: none yet)
 };
 bool decode_stream_block_ok(int64_t B);   // a power of two from 64 to 2048
-// Wf from the real filter planes wpl [2][Cp][len] (device)
-void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, cplx* Wf, hipStream_t st);
-// one block: x + c ldx = channel c of the (rotated) block, B samples (cplx only when planes2); out[i], out[ldo + i] = the two ears
-void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, double* out, int64_t ldo, hipStream_t st);
+// Wf from the real filter planes wpl [S][2][Cp][len] (device)
+void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, int64_t S, cplx* Wf, hipStream_t st);
+// one block: x + c ldx = channel c of the (rotated) block, B samples (cplx only when planes2); set: device, this block's set index
+// (null: the previous block's; not looked at when S == 1); standing: the set the host KNOWS this block and the two before it to be
+// on (their window then runs the plain kernel on that set), -1 when it does not know; out[i], out[ldo + i] = the two ears
+void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, const int* set, int standing, double* out,
+                                int64_t ldo, hipStream_t st);
 
 // ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables, resample.hip's taps and the decode family's work buffers
 void decode_family_cache_clear();

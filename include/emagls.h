@@ -328,6 +328,42 @@ int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int
 
 int emagls_decode_stream_destroy(emagls_decode_stream* s);
 
+/* ---- a bank of filter sets on a decode stream, cross-faded per block ----
+ * Filters that act on raw microphone signals (eMagLS2, FromAtf, EMAinCH) cannot follow the head by rotating the signal: the
+ * orientation goes into the FILTERS, one set per orientation, and the renderer changes set as the head moves.  The same serves
+ * to switch between designs or HRTF subjects while the sound plays.  A bank stream holds n_sets >= 1 filter sets of one shape;
+ * every block t of B samples has a set index s_t.  Sample i of block t (i = 0 .. B - 1) goes to set s_t with the gain 1 when
+ * s_t == s_(t-1); otherwise to s_t with r[i] = (i + 1) / B and to s_(t-1) with 1 - r[i]; s_(-1) := s_0 (the first block after
+ * creation or reset does not fade).  With x the concatenated (and, where the push has angles, rotated) input and g_s the gain
+ * of set s per sample, the concatenated outputs equal, to rounding, sum_s decode(g_s x, wL_s, wR_s): the filter a sample meets
+ * is the one of the moment it was pushed, linearly interpolated across the block that changes.  A constant index gives the
+ * plain stream's bits.  A block is still at most three kernel launches; a block whose window [x_(t-1), x_t] meets k = 1, 2 or 3
+ * distinct sets costs k forward transforms.  Where the host knows that the set stands (the indices of this block and the two
+ * before it came from host arrays or were kept, n_set = 0) the block runs the plain stream's kernel on that set; indices given in
+ * device memory are decided upon in the kernel.
+ * wL / wR: n_sets consecutive [len x nch] arrays.  n_sets < 1: EMAGLS_ERR_ARG; above 65536: EMAGLS_ERR_UNSUPPORTED.  Everything
+ * else as emagls_decode_stream_create, which is the bank of one set; push, reset (which also forgets the selection), info
+ * (filter_bytes grows with n_sets; state_bytes counts the two previous set indices when n_sets > 1) and destroy are shared. */
+int emagls_decode_stream_create_bank(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
+                                     int in_is_complex, int layout, int basis, int64_t block, emagls_decode_stream** s);
+
+/* emagls_decode_stream_push with set indices: set [n_set], n_set = 0 (every block keeps the set of the block before it; set 0
+ * on a fresh stream), 1 (every block of this push) or nsamp / block (one per block); anything else, a null array with
+ * n_set > 0, or an index outside [0, n_sets - 1] is EMAGLS_ERR_ARG, reported before the device is touched.
+ * emagls_decode_stream_push is this call with n_set = 0. */
+int emagls_decode_stream_push_sets(emagls_decode_stream* s, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set,
+                                   const double* yaw, int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll,
+                                   int64_t n_roll, double* out);
+
+/* emagls_decode_stream_push_device with set indices in device memory: d_set is not read by the host (the call still only
+ * enqueues), so the kernels clamp every index into [0, n_sets - 1] before they form an address from it. */
+int emagls_decode_stream_push_sets_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
+                                          const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch,
+                                          const double* d_roll, int64_t n_roll, double* d_out, void* stream);
+
+/* The number of filter sets of the stream's bank. */
+int emagls_decode_stream_sets(const emagls_decode_stream* s, int64_t* n_sets);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

@@ -93,8 +93,10 @@ void at_exit() {
 // emagls_mex('emainch' | 'emainsh', hL, hR, azi, zen, micRadius, micAzi, order, fs, len, shDefinition)
 // emagls_mex('magls_dc' | 'emagls_dc' | 'emagls2_dc', <the arguments of 'magls' / 'emagls' / 'emagls2'>, applyDiffusenessConst)
 // emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain, pitchRad, rollRad])   real or complex in / filters; [out, imagAbsSum] = ...
-// h = emagls_mex('stream_create', wL, wR, blockSize[, shDefinition, domain, complexInput])   a decode stream (mex/binauralDecodeStream.m)
-// out = emagls_mex('stream_push', h, in[, yawRad, pitchRad, rollRad])   in [k*blockSize x nch]; each angle [], a scalar or one per sample
+// h = emagls_mex('stream_create', wL, wR, blockSize[, shDefinition, domain, complexInput])   a decode stream (mex/binauralDecodeStream.m);
+//                                     wL / wR [len x nch], or [len x nch x numSets]: a bank of filter sets
+// out = emagls_mex('stream_push', h, in[, yawRad, pitchRad, rollRad, setIndex])   in [k*blockSize x nch]; each angle [], a scalar or one per
+//                                     sample; setIndex ONE-based: [] (keep the set), a scalar or one per block
 // emagls_mex('stream_reset', h)      emagls_mex('stream_destroy', h)
 // emagls_mex('resample', x, p, q)   MATLAB's resample(x, p, q) (N = 10, bta = 5): a row vector along its length, else per column
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
@@ -159,16 +161,21 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     }
     if (c == "stream_create") {
         if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "stream_create needs (wL, wR, blockSize[, shDefinition, domain, complexInput])");
-        const mwSize len = mxGetM(prhs[1]), ch = mxGetN(prhs[1]);
+        // [len x nch], or [len x nch x numSets]: column-major, the sets of a bank lie one after the other as the library takes them
+        const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* dims = mxGetDimensions(prhs[1]);
+        if (nd > 3) mexErrMsgIdAndTxt("eMagLS:arg", "the decoding filters must be [len x numChannels] or [len x numChannels x numSets]");
+        const mwSize len = mxGetM(prhs[1]), ch = nd >= 2 ? dims[1] : 1, nsets = nd == 3 ? dims[2] : 1;
         const bool wc = mxIsComplex(prhs[1]);
-        if (!mxIsDouble(prhs[1]) || !mxIsDouble(prhs[2]) || mxGetM(prhs[2]) != len || mxGetN(prhs[2]) != ch)
-            mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must be double arrays of equal size");
+        bool same = mxIsDouble(prhs[1]) && mxIsDouble(prhs[2]) && mxGetNumberOfDimensions(prhs[2]) == nd;
+        for (mwSize i = 0; same && i < nd; ++i) same = mxGetDimensions(prhs[2])[i] == dims[i];
+        if (!same) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must be double arrays of equal size");
         if (wc != (bool)mxIsComplex(prhs[2])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
         const int basis = basis_of(nrhs > 4 ? prhs[4] : nullptr), layout = layout_of(nrhs > 5 ? prhs[5] : nullptr);
         const int ic = nrhs > 6 && (mxIsLogicalScalarTrue(prhs[6]) || (mxIsDouble(prhs[6]) && !mxIsEmpty(prhs[6]) && mxGetScalar(prhs[6]) != 0));
         emagls_decode_stream* st = nullptr;
-        const int rc = emagls_decode_stream_create((int64_t)ch, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic, layout, basis,
-                                                   (int64_t)mxGetScalar(prhs[3]), &st);
+        const int rc = emagls_decode_stream_create_bank((int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic,
+                                                        layout, basis, (int64_t)mxGetScalar(prhs[3]), &st);
         if (rc) fail(rc);
         size_t slot = 0;
         while (slot < g_streams.size() && g_streams[slot]) ++slot;
@@ -179,7 +186,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         return;
     }
     if (c == "stream_push") {
-        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "stream_push needs (handle, in[, yawRad, pitchRad, rollRad])");
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "stream_push needs (handle, in[, yawRad, pitchRad, rollRad, setIndex])");
         size_t slot = 0;
         emagls_decode_stream* st = stream_of(prhs[1], &slot);
         if (!mxIsDouble(prhs[2]) || mxGetN(prhs[2]) != g_stream_shapes[slot].nch)
@@ -192,9 +199,21 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         static const char* const names[3] = {"horRotAngleRad", "pitchRad", "rollRad"};
         for (int i = 0; i < 3; ++i)
             if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) { ang[i] = dbl(prhs[3 + i], names[i]); cnt[i] = mxGetNumberOfElements(prhs[3 + i]); }
+        // setIndex (prhs[6]): MATLAB counts the sets from 1, the library from 0
+        std::vector<int32_t> sets;
+        if (nrhs > 6 && !mxIsEmpty(prhs[6])) {
+            const double* v = dbl(prhs[6], "setIndex");
+            sets.resize(mxGetNumberOfElements(prhs[6]));
+            for (size_t i = 0; i < sets.size(); ++i) {
+                if (!(v[i] >= 1.0 && v[i] <= 2147483647.0) || v[i] != std::floor(v[i]))
+                    mexErrMsgIdAndTxt("eMagLS:arg", "setIndex must hold positive integers (the sets count from 1)");
+                sets[i] = (int32_t)v[i] - 1;
+            }
+        }
         plhs[0] = mxCreateDoubleMatrix(n, 2, mxREAL);
-        const int rc = emagls_decode_stream_push(st, in_ptr(prhs[2]), (int64_t)n, ang[0], (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2],
-                                                 (int64_t)cnt[2], mxGetDoubles(plhs[0]));
+        const int rc = emagls_decode_stream_push_sets(st, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(),
+                                                      ang[0], (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2], (int64_t)cnt[2],
+                                                      mxGetDoubles(plhs[0]));
         if (rc) fail(rc);
         return;
     }

@@ -11,6 +11,21 @@ Gates (exit status 1 when one fails): median (a) < median (b), and median (a) < 
     python tools/decode_stream_timing.py [--blocks 2000] [--warm 50] [--run 100] [--shapes 25,512,64 ...] [--stream-only]
                                          [--dry-run] [--out profiles/r10_decode_stream.md]
 --dry-run prints the shapes and the bytes a push moves, computed from the shapes, without a device.
+
+--bank times the bank of filter sets (emagls_decode_stream_create_bank / _push_sets_device) instead, without
+rotation, per shape and alternating in one process, every side on streams of its own:
+
+  plain    the plain stream (emagls_decode_stream_create): the kernel instance without the bank
+  const    a bank stream of --sets sets with a constant index read from device memory (the kernels decide that it stands)
+  keep     a bank stream pushed without an index (the host knows that the set stands and runs the plain instance)
+  switch   a bank stream with a new set in EVERY block
+  three    what a caller has to do without the bank for the output of `switch`: three plain streams, the block weighted by r and
+           by 1 - r on the device (two torch.mul) for the new and the old set, a zero block for the third (its pending tails
+           still have to come out), and the three outputs added on the device (two torch.add)
+
+spread = p90 - p10 of a side's run averages.  Gates: (a) median(const) <= median(plain) + its spread: a constant index is meant to
+be the plain stream's arithmetic; (b) median(switch) <= median(three) + the spread of `three`.  A shape that misses a gate is
+reported as such and the exit status is 1.
 """
 import argparse
 import ctypes as C
@@ -109,6 +124,116 @@ def run_shape(lib, L, torch, Cc, ln, B, rotated, blocks, warm, run, stream_only)
     return res
 
 
+def _spread(v):
+    return float(np.percentile(v, 90) - np.percentile(v, 10))
+
+
+def run_bank_shape(lib, L, torch, Cc, ln, B, S, blocks, warm, run):
+    """The sides of --bank for one shape."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(Cc + ln + B)
+    rnd = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)   # noqa: E731
+    wL, wR = rnd(S, Cc, ln), rnd(S, Cc, ln)                 # [S][C][len] row-major == S column-major [len x C] arrays
+    d_blk = rnd(Cc, B).to(dev)
+    r = ((torch.arange(B, dtype=torch.float64) + 1) / B).to(dev)
+    omr = 1.0 - r
+    xa, xb, zero = torch.empty_like(d_blk), torch.empty_like(d_blk), torch.zeros_like(d_blk)
+    outs = [torch.zeros((2, B), dtype=torch.float64, device=dev) for _ in range(4)]
+    d_idx = torch.arange(S, dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    st = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(st.cuda_stream)
+    sh, re = L.LAYOUT["sh"], L.BASIS["real"]
+
+    def plain_stream(s):
+        h = C.c_void_p()
+        L.check(lib.emagls_decode_stream_create(Cc, p(wL[s]), p(wR[s]), 0, ln, 0, sh, re, B, C.byref(h)))
+        return h
+
+    def push(h, x, out):
+        L.check(lib.emagls_decode_stream_push_device(h, p(x), B, None, 0, None, 0, None, 0, p(out), sp))
+
+    def bank_stream():
+        h = C.c_void_p()
+        L.check(lib.emagls_decode_stream_create_bank(Cc, S, p(wL), p(wR), 0, ln, 0, sh, re, B, C.byref(h)))
+        return h
+
+    h_plain = plain_stream(0)
+    h_three = [plain_stream(s) for s in range(3)]
+    h_const, h_keep, h_switch = bank_stream(), bank_stream(), bank_stream()   # (a stream each: a side's index history is its own)
+    count = [0]
+
+    def side_const():
+        L.check(lib.emagls_decode_stream_push_sets_device(h_const, p(d_blk), B, C.c_void_p(d_idx.data_ptr() + 4), 1, None, 0, None, 0, None, 0,
+                                                          p(outs[0]), sp))
+
+    def side_keep():
+        L.check(lib.emagls_decode_stream_push_sets_device(h_keep, p(d_blk), B, None, 0, None, 0, None, 0, None, 0, p(outs[0]), sp))
+
+    def side_switch():
+        count[0] += 1
+        L.check(lib.emagls_decode_stream_push_sets_device(h_switch, p(d_blk), B, C.c_void_p(d_idx.data_ptr() + 4 * (count[0] % S)), 1, None, 0, None,
+                                                          0, None, 0, p(outs[0]), sp))
+
+    def side_three():
+        count[0] += 1
+        new, prev, third = count[0] % 3, (count[0] - 1) % 3, (count[0] + 1) % 3
+        torch.mul(d_blk, r, out=xa)
+        torch.mul(d_blk, omr, out=xb)
+        push(h_three[new], xa, outs[1])
+        push(h_three[prev], xb, outs[2])
+        push(h_three[third], zero, outs[3])
+        torch.add(outs[1], outs[2], out=outs[0])
+        outs[0].add_(outs[3])
+
+    sides = [("plain", lambda: push(h_plain, d_blk, outs[0])), ("const", side_const), ("keep", side_keep), ("switch", side_switch),
+             ("three", side_three)]
+    times = {k: [] for k, _ in sides}
+    with torch.cuda.stream(st):
+        for _, f in sides:
+            for _ in range(warm):
+                f()
+        st.synchronize()
+        for _ in range(max(1, blocks // run)):
+            for k, f in sides:                       # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(run):
+                    f()
+                e1.record(st)
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / run)   # us per block
+    for h in [h_plain, h_const, h_keep, h_switch] + h_three:
+        lib.emagls_decode_stream_destroy(h)
+    res = {"shape": [Cc, ln, B], "sets": S, "block_us": round(B / FS * 1e6, 1)}
+    for k, v in times.items():
+        res[k] = {"median_us": round(float(np.median(v)), 2), "min_us": round(float(np.min(v)), 2), "max_us": round(float(np.max(v)), 2),
+                  "spread_us": round(_spread(v), 2)}
+    base = res["plain"]
+    res["const_over_plain"] = round(res["const"]["median_us"] / base["median_us"], 3)
+    res["keep_over_plain"] = round(res["keep"]["median_us"] / base["median_us"], 3)
+    res["three_over_switch"] = round(res["three"]["median_us"] / res["switch"]["median_us"], 2)
+    res["switch_over_const"] = round(res["switch"]["median_us"] / res["const"]["median_us"], 2)
+    res["gate_a"] = res["const"]["median_us"] <= base["median_us"] + base["spread_us"]
+    res["gate_b"] = res["switch"]["median_us"] <= res["three"]["median_us"] + res["three"]["spread_us"]
+    return res
+
+
+def bank_markdown(rows, device):
+    lines = ["`python tools/decode_stream_timing.py --bank` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
+             "plain: the plain stream; const: a bank stream with a constant index from device memory; keep: a bank stream pushed without",
+             "an index; switch: a new set in every block; three: three plain streams fed the gain-weighted blocks, outputs added on the",
+             "device.", "",
+             "| (C, len, B) | plain | spread | const | spread | const / plain | (a) | keep | keep / plain | switch | three | spread | three / switch | (b) | switch / const |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append("| %s | %.1f | %.2f | %.1f | %.2f | %.3f | %s | %.1f | %.3f | %.1f | %.1f | %.2f | %.2f | %s | %.2f |" % (
+            tuple(r["shape"]), r["plain"]["median_us"], r["plain"]["spread_us"], r["const"]["median_us"], r["const"]["spread_us"],
+            r["const_over_plain"], "ok" if r["gate_a"] else "MISS", r["keep"]["median_us"], r["keep_over_plain"], r["switch"]["median_us"],
+            r["three"]["median_us"], r["three"]["spread_us"], r["three_over_switch"], "ok" if r["gate_b"] else "MISS", r["switch_over_const"]))
+    return "\n".join(lines) + "\n"
+
+
 def markdown(rows, device):
     lines = ["`python tools/decode_stream_timing.py` on %s: time per block in us (median and p99 of the run averages).  stream:" % device,
              "`emagls_decode_stream_push_device`; window: `emagls_binaural_decode_render_ypr_device` on the last len - 1 + B samples.", "",
@@ -132,6 +257,8 @@ def main():
     ap.add_argument("--rotation", choices=["both", "none", "ypr"], default="both")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default=None, help="markdown table")
+    ap.add_argument("--bank", action="store_true", help="time the bank of filter sets (see above)")
+    ap.add_argument("--sets", type=int, default=3, help="--bank: filter sets of the bank stream (at least 3)")
     a = ap.parse_args()
     if a.blocks < a.run or a.run < 1 or a.warm < 0:
         raise SystemExit("--blocks must be at least --run, --run at least 1")
@@ -147,6 +274,20 @@ def main():
     from emagls_amd import _lib as L
     lib = L.load()
     rows, ok = [], True
+    if a.bank:
+        if a.sets < 3:
+            raise SystemExit("--sets must be at least 3")
+        for s in shapes:
+            res = run_bank_shape(lib, L, torch, *s, a.sets, a.blocks, a.warm, a.run)
+            ok = ok and res["gate_a"] and res["gate_b"]
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(bank_markdown(rows, torch.cuda.get_device_name(0)))
+        print("gates:", "pass" if ok else "MISS")
+        return 0 if ok else 1
     for s in shapes:
         for r in rots:
             res = run_shape(lib, L, torch, *s, r, a.blocks, a.warm, a.run, a.stream_only)
