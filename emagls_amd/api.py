@@ -753,6 +753,181 @@ class BinauralDecodeStream:
             pass
 
 
+class BinauralDecodeGroup:
+    """Many listeners of one sound field in one push: one bank of filter sets, stored once, and
+    `numListeners` listeners, each with the state a BinauralDecodeStream has.  `push` takes one block of the common signal and, per
+    listener, their head orientation and their set index, and returns [numListeners x n x 2].  Listener l's output is, bit for bit,
+    what a BinauralDecodeStream of the same filters returns when it is fed the same blocks with listener l's angles and indices;
+    a block costs at most three kernel launches for the whole group.  One choice is made per push rather than per listener: the
+    push takes the yaw rule when no listener has a pitch or a roll, otherwise every listener goes through the three-axis rotation.
+    Filters [len x numChannels] or [numSets x len x numChannels]; everything else as BinauralDecodeStream.  1 <= numListeners <= 4096."""
+
+    def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition="real", rotationDomain="sh",
+                 complexInput=False):
+        self._h = None
+        self._basis, self._cb = _basis(shDefinition)
+        self._layout = _layout(rotationDomain)
+        w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
+        wL = np.asfortranarray(np.asarray(decodingFilterLeft, dtype=np.complex128 if w_c else np.float64))
+        wR = np.asfortranarray(np.asarray(decodingFilterRight, dtype=np.complex128 if w_c else np.float64))
+        if wL.ndim not in (2, 3) or wL.shape != wR.shape:
+            raise ValueError("filters must be [len x numChannels] or [numSets x len x numChannels] arrays of equal shape")
+        if int(blockSize) != blockSize or int(numListeners) != numListeners:
+            raise ValueError("blockSize and numListeners must be integers")
+        self.numSets = wL.shape[0] if wL.ndim == 3 else 1
+        if self.numSets < 1:
+            raise ValueError("a bank needs at least one filter set")
+        if wL.ndim == 3:    # the library takes the sets one after the other, each column-major [len x numChannels]
+            wL, wR = (np.ascontiguousarray(w.transpose(0, 2, 1)) for w in (wL, wR))
+            ln, self.numChannels = wL.shape[2], wL.shape[1]
+        else:
+            ln, self.numChannels = wL.shape
+        self.blockSize, self.numListeners, self.complexInput = int(blockSize), int(numListeners), bool(complexInput)
+        h = C.c_void_p()
+        L.check(L.load().emagls_decode_group_create(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
+                                                    wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
+                                                    self._layout, self._basis, self.blockSize, self.numListeners, C.byref(h)))
+        self._h = h
+
+    def info(self):
+        b, p, nl, sb, fb, k = L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), C.c_int(0)
+        L.check(L.load().emagls_decode_group_info(self._handle(), C.byref(b), C.byref(p), C.byref(nl), C.byref(sb), C.byref(fb), C.byref(k)))
+        return {"block": b.value, "partitions": p.value, "listeners": nl.value, "state_bytes": sb.value, "filter_bytes": fb.value,
+                "launches_per_block": k.value}
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the decode group is closed")
+        return self._h
+
+    def _check_block(self, shape, ndim):
+        if ndim != 2 or shape[1] != self.numChannels:
+            raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
+        if shape[0] % self.blockSize:
+            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
+        return shape[0]
+
+    def _per_listener(self, a, per, name, what, xp):
+        """An argument of push as [L] or [L x per] (None: None): a scalar is the same for every listener."""
+        if a is None:
+            return None
+        nl = self.numListeners
+        shape = tuple(a.shape)
+        if len(shape) == 0 or (len(shape) == 1 and shape[0] == 1):
+            return xp.broadcast_to(a.reshape(1), (nl,))
+        if shape == (nl,) or shape == (nl, 1):
+            return a.reshape(nl)
+        if shape == (nl, per):
+            return a
+        if nl == 1 and shape == (per,):
+            return a.reshape(1, per)
+        raise ValueError("%s must be a scalar, [numListeners] or [numListeners x %s] = [%d x %d], not %s" % (name, what, nl, per, list(shape)))
+
+    def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None, setIndex=None):
+        """block [n x numChannels], the common signal, n a multiple of blockSize: a NumPy array (host entry) or a torch tensor on
+        the group's device (device entry on torch's current stream, not synchronised).  Each angle: None (0), a scalar (every
+        listener), [numListeners] (constant over this push) or [numListeners x n].  setIndex: None (every listener keeps their
+        set; set 0 on a fresh listener), an int (every listener), [numListeners] or [numListeners x n / blockSize]; a device int32
+        tensor is not read on the host: the kernels then clamp its values into [0, numSets - 1].
+        Returns [numListeners x n x 2]."""
+        h = self._handle()
+        if type(block).__module__.split(".")[0] == "torch":
+            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
+        if np.iscomplexobj(block) and not self.complexInput:
+            raise ValueError("the group was created for real blocks (complexInput=False)")
+        x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
+        n = self._check_block(x.shape, x.ndim)
+        names = ("horRotAngleRad", "pitchRad", "rollRad")
+        yaw, pitch, roll = (None if a is None else np.ascontiguousarray(self._per_listener(np.asarray(a, dtype=np.float64), n, nm, "n", np))
+                            for a, nm in zip((horRotAngleRad, pitchRad, rollRad), names))
+        if any(a is not None and np.any(a != 0) for a in (pitch, roll)):
+            if self._layout != L.LAYOUT["sh"]:
+                raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
+            _sh_order(self.numChannels)
+        sets = None
+        if setIndex is not None:
+            a = np.asarray(setIndex)
+            if a.dtype.kind not in "iu":
+                raise ValueError("setIndex must be an integer or integers")
+            a = self._per_listener(a, n // self.blockSize, "setIndex", "n / blockSize", np)
+            if a.size and (a.min() < 0 or a.max() >= self.numSets):
+                raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
+            sets = np.ascontiguousarray(a, dtype=np.int32)
+        out = np.zeros((self.numListeners, 2, n))
+        ps, ns = (None, 0) if sets is None else (sets.ctypes.data_as(C.c_void_p), sets.size)
+        L.check(L.load().emagls_decode_group_push(h, x.ctypes.data_as(C.c_void_p), n, ps, ns, *_vp(yaw), *_vp(pitch), *_vp(roll),
+                                                  out.ctypes.data_as(C.c_void_p)))
+        return out.transpose(0, 2, 1)
+
+    def _push_torch(self, h, block, hor, pitch, roll, setIndex):
+        import torch
+        n = self._check_block(tuple(block.shape), block.dim())
+        if not block.is_cuda:
+            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        if block.is_complex() and not self.complexInput:
+            raise ValueError("the group was created for real blocks (complexInput=False)")
+        xt = block.to(torch.complex128 if self.complexInput else torch.float64).t().contiguous()   # [numChannels][n]
+
+        def dev(a, name):
+            if a is None:
+                return None, 0
+            t = a.to(device=block.device, dtype=torch.float64) if torch.is_tensor(a) else \
+                torch.as_tensor(np.asarray(a, dtype=np.float64), device=block.device)
+            t = self._per_listener(t, n, name, "n", torch).contiguous()
+            return t, t.numel()
+        (ty, ny), (tp, npi), (tr, nr) = dev(hor, "horRotAngleRad"), dev(pitch, "pitchRad"), dev(roll, "rollRad")
+        if (npi or nr) and self._layout != L.LAYOUT["sh"]:
+            raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
+        if npi or nr:
+            _sh_order(self.numChannels)
+        ts, ns = None, 0
+        if torch.is_tensor(setIndex):
+            if setIndex.dtype != torch.int32:
+                raise ValueError("a setIndex tensor must be int32")
+            ts = self._per_listener(setIndex.to(device=block.device), n // self.blockSize, "setIndex", "n / blockSize", torch).contiguous()
+        elif setIndex is not None:
+            a = np.asarray(setIndex)
+            if a.dtype.kind not in "iu":
+                raise ValueError("setIndex must be an integer or integers")
+            a = self._per_listener(a, n // self.blockSize, "setIndex", "n / blockSize", np)
+            if a.size and (a.min() < 0 or a.max() >= self.numSets):
+                raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
+            ts = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=block.device)
+        if ts is not None:
+            ns = ts.numel()
+        out = torch.empty((self.numListeners, 2, n), dtype=torch.float64, device=block.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(block.device):
+            st = torch.cuda.current_stream().cuda_stream
+            L.check(L.load().emagls_decode_group_push_device(h, p(xt), n, p(ts), ns, p(ty), ny, p(tp), npi, p(tr), nr, p(out), C.c_void_p(st)))
+        for t in (xt, ty, tp, tr, ts):      # (their memory may be reused only after the stream has passed the enqueued kernels)
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(block.device))
+        return out.transpose(1, 2)
+
+    def reset(self, listener=None):
+        """Zero history for one listener (what a listener who joins gets; the others are untouched) or, with None, for all: what
+        follows equals a fresh stream bit for bit."""
+        L.check(L.load().emagls_decode_group_reset(self._handle(), -1 if listener is None else int(listener)))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L.check(L.load().emagls_decode_group_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def designYawBank(kind, hL, hR, hrirGridAziRad, hrirGridZenRad, yawRad, *, order=4, fs=48000.0, len=512, shDefinition="real",
                   micRadius=0.0, micGridAziRad=None, micGridZenRad=None, atfIrs=None, atfGridAziZenRad=None, fTrans=0.0):
     """A bank of filter sets for BinauralDecodeStream, one per head yaw: set j is the design `kind` on the HRIR grid turned against

@@ -1,5 +1,5 @@
 // C ABI of binauralDecode, the SH rotations and the resampler (include/emagls.h: emagls_binaural_decode*, emagls_rotate_yaw,
-// emagls_rotate_sh, emagls_sh_rotation_matrix, emagls_resample*, emagls_decode_stream_*): the argument check, host staging, the work buffers and the
+// emagls_rotate_sh, emagls_sh_rotation_matrix, emagls_resample*, emagls_decode_stream_*, emagls_decode_group_*): the argument check, host staging, the work buffers and the
 // choice of kernels, once for the whole family.  The kernels are decode.hip's, decode_stream.hip's, rotate.hip's, rotate3.hip's and
 // resample.hip's.
 // No CPU fallback.
@@ -164,13 +164,14 @@ void check_args(bool decode, std::initializer_list<const void*> ptrs, int64_t ns
 // in [C][n] -> out [C][n] (complex when in_c or cb) by rotate.hip's kernel for a yaw-only rotation, rotate3.hip's otherwise;
 // transpose: the filter-side form of a fixed rotation (w Rot instead of x Rot^T)
 // ld_in / ld_out: elements between the channels of in / out (0: n)
+// L listeners of the one signal (a listener group): la[3] the listener strides of the three angle arrays, lo of out
 void launch_rotation(const Angles& a, const void* in, bool in_c, int64_t n, int nch, int layout, bool cb, bool transpose, void* out,
-                     hipStream_t st, int64_t ld_in = 0, int64_t ld_out = 0) {
+                     hipStream_t st, int64_t ld_in = 0, int64_t ld_out = 0, int L = 1, const int64_t* la = nullptr, int64_t lo = 0) {
     if (a.yaw_only())
-        launch_rotate_yaw(in, in_c, n, nch, layout, cb, a.yaw, a.n_yaw > 1, transpose, out, st, ld_in, ld_out);
+        launch_rotate_yaw(in, in_c, n, nch, layout, cb, a.yaw, a.n_yaw > 1, transpose, out, st, ld_in, ld_out, L, la ? la[0] : 0, lo);
     else
         launch_rotate3(in, in_c, n, nch, cb, a.n_yaw ? a.yaw : nullptr, a.n_yaw > 1, a.n_pitch ? a.pitch : nullptr, a.n_pitch > 1,
-                       a.n_roll ? a.roll : nullptr, a.n_roll > 1, transpose, out, st, ld_in, ld_out);
+                       a.n_roll ? a.roll : nullptr, a.n_roll > 1, transpose, out, st, ld_in, ld_out, L, la, lo);
 }
 
 // The rotation before the decode.  A fixed one (every count <= 1) turns the decoding filters, sum_i w_i * (x Rot^T)_i =
@@ -480,7 +481,8 @@ int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, do
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// The decode stream (decode_stream.hip; DESIGN.md sections 9.3 and 9.4).  The object owns its device buffers:
+// The decode stream (decode_stream.hip; DESIGN.md sections 9.3 and 9.4) and the listener group (section 9.5), which is the same
+// object with d.L listeners: the per-listener state L times over, the bank once.  The object owns its device buffers:
 // emagls_cache_clear() does not reach them.
 // ---------------------------------------------------------------------------------------------
 struct emagls_decode_stream {
@@ -492,27 +494,33 @@ struct emagls_decode_stream {
     bool ready = false;
     std::vector<double> wpl;      // [S][2][Cp][len] the real filter planes [re w; -im w], until the device has their spectra
     DecodeStreamState d;
-    void* xrot = nullptr;         // [nch][B] the rotated block (cplx when the signal or the basis is complex)
+    void* xrot = nullptr;         // [L][nch][B] the rotated block of every listener (cplx when the signal or the basis is complex)
     void* stage[4] = {};          // host entry: the push's input, angles, output and set indices on the device, grown on demand and kept
     size_t stage_cap[4] = {};
     int known[2] = {-1, -1};      // what the host knows of the selection state on the device: the set indices of the two previous
                                   // blocks, -1: none yet, -2: not known (a push took its indices from device memory)
     int cp() const { return d.planes2 ? 2 * d.C : d.C; }
+    // per listener:
     size_t ring_bytes() const { return sizeof(cplx) * 2 * (size_t)d.P * (d.B + 1); }
     size_t hist_bytes() const { return esz(d.planes2) * (size_t)d.C * d.B; }
-    size_t filter_bytes() const { return sizeof(cplx) * (size_t)d.S * 2 * (size_t)d.P * cp() * (d.B + 1); }
     size_t pos_bytes() const { return sizeof(int) * (d.S > 1 ? 3 : 1); }   // the ring position; with a bank, the two previous set indices
+    size_t state_bytes() const { return (size_t)d.L * (ring_bytes() + hist_bytes() + pos_bytes()); }
+    // once, whatever the number of listeners:
+    size_t filter_bytes() const { return sizeof(cplx) * (size_t)d.S * 2 * (size_t)d.P * cp() * (d.B + 1); }
     void release() {
         hipFree(d.Wf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos); hipFree(xrot);
         for (void*& p : stage) { hipFree(p); p = nullptr; }
         d.Wf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr; xrot = nullptr;
         ready = false;
     }
-    void zero_state(hipStream_t st) {
-        HIP_CHECK(hipMemsetAsync(d.ring, 0, ring_bytes(), st));
-        HIP_CHECK(hipMemsetAsync(d.hist, 0, hist_bytes(), st));
-        HIP_CHECK(hipMemsetAsync(d.pos, 0, sizeof(int), st));
-        if (d.S > 1) HIP_CHECK(hipMemsetAsync(d.pos + 1, 0xff, 2 * sizeof(int), st));   // -1: no block yet
+    // the listeners first .. first + count - 1 back to a fresh stream's state
+    void zero_state(hipStream_t st, int64_t first = 0, int64_t count = 1) {
+        const size_t n = (size_t)count, pb = pos_bytes();
+        HIP_CHECK(hipMemsetAsync((char*)d.ring + (size_t)first * ring_bytes(), 0, n * ring_bytes(), st));
+        HIP_CHECK(hipMemsetAsync((char*)d.hist + (size_t)first * hist_bytes(), 0, n * hist_bytes(), st));
+        char* pos = (char*)d.pos + (size_t)first * pb;
+        HIP_CHECK(hipMemset2DAsync(pos, pb, 0, sizeof(int), n, st));
+        if (d.S > 1) HIP_CHECK(hipMemset2DAsync(pos + sizeof(int), pb, 0xff, 2 * sizeof(int), n, st));   // -1: no block yet
         known[0] = known[1] = -1;
     }
     // the device side, once: buffers, the partition spectra, zero history (mu held)
@@ -521,13 +529,13 @@ struct emagls_decode_stream {
         HIP_CHECK(hipGetDevice(&device));
         try {
             HIP_CHECK(hipMalloc(&d.Wf, filter_bytes()));
-            HIP_CHECK(hipMalloc(&d.ring, ring_bytes()));
-            HIP_CHECK(hipMalloc(&d.hist, hist_bytes()));
-            HIP_CHECK(hipMalloc(&d.pos, pos_bytes()));
-            HIP_CHECK(hipMalloc(&xrot, sizeof(cplx) * (size_t)d.C * d.B));
+            HIP_CHECK(hipMalloc(&d.ring, d.L * ring_bytes()));
+            HIP_CHECK(hipMalloc(&d.hist, d.L * hist_bytes()));
+            HIP_CHECK(hipMalloc(&d.pos, d.L * pos_bytes()));
+            HIP_CHECK(hipMalloc(&xrot, esz(d.planes2) * (size_t)d.L * d.C * d.B));   // (a rotated block is complex exactly when planes2)
             Scratch s;
             launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.S, d.Wf, s.st);
-            zero_state(s.st);
+            zero_state(s.st, 0, d.L);
             HIP_CHECK(hipStreamSynchronize(s.st));
         } catch (...) { release(); device = -1; throw; }
         wpl = std::vector<double>();
@@ -540,9 +548,12 @@ struct emagls_decode_stream {
     }
 };
 
+struct emagls_decode_group : emagls_decode_stream {};   // (d.L listeners; the host's copy of the selection, `known`, is not used)
+
 namespace {
 
 constexpr int64_t kDecodeStreamMaxSets = 65536;
+constexpr int64_t kDecodeGroupMaxListeners = 4096;   // well under the grid's limit; keeps xrot and the rings of large shapes bounded
 
 // the set indices of a push: 0 values (the set of the previous block), 1 (every block of the push) or one per block
 struct Sets { const int32_t* p = nullptr; int64_t n = 0; const int32_t* host = nullptr; /* the same values, where the host has them */ };
@@ -587,6 +598,100 @@ void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp
     }
 }
 
+
+// The creation of a stream or of a listener group (T), every argument checked before the device is touched
+template <typename T>
+T* stream_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
+                 int layout, int basis, int64_t block, int64_t listeners) {
+    if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+    if (n_sets < 1) throw Error(EMAGLS_ERR_ARG, "a decode stream needs at least one filter set");
+    if (n_sets > kDecodeStreamMaxSets) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports banks of up to 65536 filter sets");
+    if (listeners < 1) throw Error(EMAGLS_ERR_ARG, "a listener group needs at least one listener");
+    if (listeners > kDecodeGroupMaxListeners) throw Error(EMAGLS_ERR_UNSUPPORTED, "a listener group supports up to 4096 listeners");
+    if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
+    check_basis(basis);
+    if (!decode_stream_block_ok(block))
+        throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports block sizes 64, 128, 256, 512, 1024 and 2048");
+    if (len > 16384) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports filters of up to 16384 taps");
+    std::unique_ptr<T> s(new T);
+    s->nch = nch; s->len = len; s->layout = layout; s->basis = basis; s->in_c = in_is_complex != 0;
+    s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block); s->d.S = (int)n_sets; s->d.L = (int)listeners;
+    // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
+    s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
+    const int Cp = s->cp();
+    const bool wc = filters_are_complex != 0;
+    s->wpl.assign((size_t)n_sets * 2 * Cp * len, 0.0);
+    for (int64_t set = 0; set < n_sets; ++set)
+        for (int e = 0; e < 2; ++e) {
+            const double* w = reinterpret_cast<const double*>(e ? wR : wL) + (size_t)set * nch * len * (wc ? 2 : 1);
+            double* pl = s->wpl.data() + ((size_t)set * 2 + e) * Cp * len;
+            for (int64_t c = 0; c < nch; ++c)
+                for (int64_t t = 0; t < len; ++t) {
+                    const size_t i = (size_t)(c * len + t);
+                    pl[(size_t)c * len + t] = wc ? w[2 * i] : w[i];
+                    if (wc && s->d.planes2) pl[(size_t)(nch + c) * len + t] = -w[2 * i + 1];
+                }
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->ensure_device();
+    } else {
+        (void)hipGetLastError();
+    }
+    return s.release();
+}
+
+// ---- the listener group: one push of the common block for all listeners (device pointers; arrays listener-major)
+// A count of a push: 0, L (one value per listener) or L * per (per = nsamp for an angle, nsamp / block for a set index)
+int64_t group_count(int64_t n, int64_t L, int64_t per, const void* p, const char* what) {
+    if (n != 0 && n != L && n != L * per) throw Error(EMAGLS_ERR_ARG, std::string("a group push takes ") + what);
+    if (n > 0 && !p) throw Error(EMAGLS_ERR_ARG, "null pointer");
+    return n == 0 ? 0 : (per != 1 && n == L * per) ? per : 1;   // what one listener has
+}
+
+// what one listener has of each array, and the checks of a stream's push on that
+struct GroupPush { Angles one; int64_t set_per = 0; };
+
+GroupPush group_check_push(const emagls_decode_group* g, const void* in, const void* out, int64_t nsamp, const Angles& a, const Sets& sets) {
+    if (!g) throw Error(EMAGLS_ERR_ARG, "null decode group");
+    const int64_t B = g->d.B, L = g->d.L;
+    if (nsamp < 0 || nsamp % B) throw Error(EMAGLS_ERR_ARG, "a push needs a multiple of the block size of samples");
+    static const char* const kAngleCount = "no value of an angle, one per listener, or one per listener and sample";
+    GroupPush r;
+    r.set_per = group_count(sets.n, L, nsamp / B, sets.p, "0 set indices, one per listener, or one per listener and block");
+    r.one = {a.yaw, group_count(a.n_yaw, L, nsamp, a.yaw, kAngleCount), a.pitch, group_count(a.n_pitch, L, nsamp, a.pitch, kAngleCount), a.roll,
+             group_count(a.n_roll, L, nsamp, a.roll, kAngleCount)};
+    check_args(true, {in, out}, nsamp, g->nch, g->len, 0, g->layout, g->basis, r.one);
+    return r;
+}
+
+// k blocks in order on st, at most three launches each whatever L is; not synchronised (g->mu held, device current)
+void group_push_blocks(emagls_decode_group* g, const void* d_in, int64_t nsamp, const GroupPush& p, const Sets& sets, double* d_out,
+                       hipStream_t st) {
+    g->ensure_device();
+    const int64_t B = g->d.B, C = g->d.C, nb = nsamp / B;
+    const bool cb = g->basis == EMAGLS_BASIS_COMPLEX;
+    const Angles& a = p.one;
+    // per-sample angles are [L][nsamp]: block b of listener l at + l nsamp + b B; one value per listener: [L]
+    const int64_t la[3] = {a.n_yaw > 1 ? nsamp : 1, a.n_pitch > 1 ? nsamp : 1, a.n_roll > 1 ? nsamp : 1};
+    auto at = [&](const double* q, int64_t n, int64_t b) { return n > 1 ? q + b * B : q; };
+    for (int64_t b = 0; b < nb; ++b) {
+        const void* x = (const char*)d_in + esz(g->in_c) * (size_t)(b * B);
+        bool x_c = g->in_c;
+        int64_t ldx = nsamp, lsx = 0;   // without angles every listener reads the common block
+        if (a.any()) {
+            const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
+                             at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
+            launch_rotation(blk, x, x_c, B, (int)g->nch, g->layout, cb, false, g->xrot, st, nsamp, B, g->d.L, la, C * B);
+            x = g->xrot; x_c = x_c || cb; ldx = B; lsx = C * B;
+        }
+        // with a bank the kernels decide for every listener whether their set stands (section 9.4: the same bits either way)
+        const int* set = p.set_per > 1 ? sets.p + b : sets.p;
+        launch_decode_stream_block(g->d, x, x_c, ldx, p.set_per ? set : nullptr, -1, d_out + b * B, nsamp, st, lsx,
+                                   (int)(p.set_per > 1 ? nb : 1), 2 * nsamp);
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -601,41 +706,7 @@ int emagls_decode_stream_create_bank(int64_t nch, int64_t n_sets, const void* wL
     return guarded_call([&] {
         if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
         *out = nullptr;
-        if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-        if (n_sets < 1) throw Error(EMAGLS_ERR_ARG, "a decode stream needs at least one filter set");
-        if (n_sets > kDecodeStreamMaxSets) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports banks of up to 65536 filter sets");
-        if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
-        check_basis(basis);
-        if (!decode_stream_block_ok(block))
-            throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports block sizes 64, 128, 256, 512, 1024 and 2048");
-        if (len > 16384) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports filters of up to 16384 taps");
-        std::unique_ptr<emagls_decode_stream> s(new emagls_decode_stream);
-        s->nch = nch; s->len = len; s->layout = layout; s->basis = basis; s->in_c = in_is_complex != 0;
-        s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block); s->d.S = (int)n_sets;
-        // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
-        s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
-        const int Cp = s->cp();
-        const bool wc = filters_are_complex != 0;
-        s->wpl.assign((size_t)n_sets * 2 * Cp * len, 0.0);
-        for (int64_t set = 0; set < n_sets; ++set)
-            for (int e = 0; e < 2; ++e) {
-                const double* w = reinterpret_cast<const double*>(e ? wR : wL) + (size_t)set * nch * len * (wc ? 2 : 1);
-                double* pl = s->wpl.data() + ((size_t)set * 2 + e) * Cp * len;
-                for (int64_t c = 0; c < nch; ++c)
-                    for (int64_t t = 0; t < len; ++t) {
-                        const size_t i = (size_t)(c * len + t);
-                        pl[(size_t)c * len + t] = wc ? w[2 * i] : w[i];
-                        if (wc && s->d.planes2) pl[(size_t)(nch + c) * len + t] = -w[2 * i + 1];
-                    }
-            }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
-            std::lock_guard<std::mutex> lk(s->mu);
-            s->ensure_device();
-        } else {
-            (void)hipGetLastError();
-        }
-        *out = s.release();
+        *out = stream_create<emagls_decode_stream>(nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, 1);
     });
 }
 
@@ -722,7 +793,7 @@ int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int
         if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
         if (block) *block = s->d.B;
         if (partitions) *partitions = s->d.P;
-        if (state_bytes) *state_bytes = (int64_t)(s->ring_bytes() + s->hist_bytes() + s->pos_bytes());
+        if (state_bytes) *state_bytes = (int64_t)s->state_bytes();
         if (filter_bytes) *filter_bytes = (int64_t)s->filter_bytes();
         if (launches_per_block) *launches_per_block = 3;   // rotation, forward transform with the products, inverse transform
     });
@@ -748,6 +819,114 @@ int emagls_decode_stream_destroy(emagls_decode_stream* s) {
             }
         }
         delete s;
+    });
+}
+
+// ---- the listener group
+int emagls_decode_group_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
+                               int in_is_complex, int layout, int basis, int64_t block, int64_t n_listeners, emagls_decode_group** out) {
+    return guarded_call([&] {
+        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *out = nullptr;
+        *out = stream_create<emagls_decode_group>(nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block,
+                                                  n_listeners);
+    });
+}
+
+int emagls_decode_group_push_device(emagls_decode_group* g, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
+                                    const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll,
+                                    int64_t n_roll, double* d_out, void* stream) {
+    return guarded_call([&] {
+        const Sets sets{d_set, n_set};
+        const GroupPush p = group_check_push(g, d_in, d_out, nsamp, {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, sets);
+        if (nsamp == 0) return;
+        std::lock_guard<std::mutex> lk(g->mu);
+        DeviceGuard dg(g->device);
+        group_push_blocks(g, d_in, nsamp, p, sets, d_out, (hipStream_t)stream);   // (the kernels clamp the indices: the host never sees them)
+    });
+}
+
+int emagls_decode_group_push(emagls_decode_group* g, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set, const double* yaw,
+                             int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll, double* out) {
+    return guarded_call([&] {
+        Angles a{yaw, n_yaw, pitch, n_pitch, roll, n_roll};
+        if (g) {   // (zeros in a count that does not fit are reported, not dropped)
+            auto counted = [&](int64_t n) { return n == 0 || n == g->d.L || n == g->d.L * nsamp; };
+            if (counted(n_pitch) && counted(n_roll)) a = host_angles(a);
+        }
+        const GroupPush p = group_check_push(g, in, out, nsamp, a, {set, n_set});
+        for (int64_t i = 0; i < n_set; ++i)
+            if (set[i] < 0 || set[i] >= g->d.S) throw Error(EMAGLS_ERR_ARG, "set index outside the group's bank");
+        if (nsamp == 0) return;
+        std::lock_guard<std::mutex> lk(g->mu);
+        DeviceGuard dg(g->device);
+        g->ensure_device();
+        hipStream_t st = pool_stream_take();
+        struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
+        const size_t L = (size_t)g->d.L, bin = esz(g->in_c) * (size_t)nsamp * g->nch;
+        char* d_in = g->staged<char>(0, bin);
+        double* d_ang = g->staged<double>(1, sizeof(double) * 3 * L * (size_t)nsamp);
+        double* d_out = g->staged<double>(2, sizeof(double) * 2 * L * (size_t)nsamp);
+        HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
+        auto up = [&](const double* q, int64_t n, int slot) -> const double* {
+            if (!n) return nullptr;
+            double* dst = d_ang + (size_t)slot * L * nsamp;
+            HIP_CHECK(hipMemcpyAsync(dst, q, sizeof(double) * n, hipMemcpyHostToDevice, st));
+            return dst;
+        };
+        GroupPush dp = p;
+        dp.one.yaw = up(a.yaw, a.n_yaw, 0); dp.one.pitch = up(a.pitch, a.n_pitch, 1); dp.one.roll = up(a.roll, a.n_roll, 2);
+        Sets dsets{nullptr, n_set};
+        if (n_set) {
+            int32_t* d_set = g->staged<int32_t>(3, sizeof(int32_t) * (size_t)n_set);
+            HIP_CHECK(hipMemcpyAsync(d_set, set, sizeof(int32_t) * (size_t)n_set, hipMemcpyHostToDevice, st));
+            dsets.p = d_set;
+        }
+        group_push_blocks(g, d_in, nsamp, dp, dsets, d_out, st);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * L * nsamp, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
+int emagls_decode_group_reset(emagls_decode_group* g, int64_t listener) {
+    return guarded_call([&] {
+        if (!g) throw Error(EMAGLS_ERR_ARG, "null decode group");
+        if (listener < -1 || listener >= g->d.L) throw Error(EMAGLS_ERR_ARG, "listener outside the group (-1: all of them)");
+        std::lock_guard<std::mutex> lk(g->mu);
+        DeviceGuard dg(g->device);
+        g->ensure_device();
+        HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
+        if (listener < 0) g->zero_state(nullptr, 0, g->d.L);
+        else g->zero_state(nullptr, listener, 1);
+        HIP_CHECK(hipStreamSynchronize(nullptr));
+    });
+}
+
+int emagls_decode_group_info(const emagls_decode_group* g, int64_t* block, int64_t* partitions, int64_t* listeners,
+                             int64_t* state_bytes, int64_t* filter_bytes, int* launches_per_block) {
+    return guarded_call([&] {
+        if (!g) throw Error(EMAGLS_ERR_ARG, "null decode group");
+        if (block) *block = g->d.B;
+        if (partitions) *partitions = g->d.P;
+        if (listeners) *listeners = g->d.L;
+        if (state_bytes) *state_bytes = (int64_t)g->state_bytes();
+        if (filter_bytes) *filter_bytes = (int64_t)g->filter_bytes();
+        if (launches_per_block) *launches_per_block = 3;   // for the whole group: rotation, forward transform with the products, inverse
+    });
+}
+
+int emagls_decode_group_destroy(emagls_decode_group* g) {
+    return guarded_call([&] {
+        if (!g) return;
+        {
+            std::lock_guard<std::mutex> lk(g->mu);
+            if (g->ready) {
+                DeviceGuard dg(g->device);
+                (void)hipDeviceSynchronize();
+                g->release();
+            }
+        }
+        delete g;
     });
 }
 

@@ -26,6 +26,14 @@
 // the samples wait in between global memory and LDS) and accumulates with that set's spectra into the same sums.  Three equal
 // indices are one pass without a gain: the plain stream's arithmetic.  The indices of the two previous blocks live beside the ring
 // position and move on with it.
+//
+// A listener group: L listeners of one sound field, each with a state of their own (ring, hist, pos, sel, one
+// after the other in the same buffers) and all on one bank Wf.  The listener is one more grid dimension of the two kernels: a
+// workgroup forms its pointers from its listener index and the listener strides and then does what it does for a single stream.
+// A push without angles has the input stride 0: every listener reads the common block.  The listener form is instantiated beside
+// the single stream's (GROUP): folded into one, the pointer arithmetic ahead of the first loads cost the single stream 0.3 to
+// 0.6 us per block (profiles/r12_decode_group.md); with GROUP = false the kernels are the single stream's, instruction for
+// instruction, and a group of one listener runs those.
 #include "kernels.hpp"
 #include "lds_fft.hpp"
 
@@ -36,6 +44,12 @@ namespace {
 constexpr int DS_NT = 512;     // threads of every kernel here
 constexpr int DS_ELEMS = 4096; // elements of the transform buffer: DS_ELEMS / Nf transforms per round, 8 loads per thread
 enum { DS_G_ZERO = 0, DS_G_ONE = 1, DS_G_R = 2, DS_G_1MR = 3 };   // gain of a set over a block: 0, 1, r[i] = (i + 1) / B, 1 - r[i]
+
+// the listener strides of a group's launch: of the block (elements of its type; 0: the common block), of pos / sel, of the set
+// index, of the output; hist [L][C][B] and ring [L][2][P][B + 1] follow from the shapes.  A single stream's launch has none.
+struct DsListeners { int64_t lsx; int lpos, lset; int64_t lso; };
+struct DsSingle {};
+template <bool GROUP> using DsStrides = std::conditional_t<GROUP, DsListeners, DsSingle>;
 
 __device__ __forceinline__ void ds_twiddles(cplx* tws, int Nf) {
     for (int j = threadIdx.x; j < Nf / 2; j += DS_NT) {
@@ -85,14 +99,32 @@ __global__ void __launch_bounds__(DS_NT) ds_filter_kernel(const double* __restri
 // real channels (2p, 2p + 1).  KU: frequency bins per thread (B + 1 <= KU * DS_NT).  grid (P, 2)
 // BANK: Wf holds S sets; set_p: this block's index (null: the previous block's, 0 on a fresh stream), clamped into [0, S - 1] before
 // it forms an address; sel: the indices of the blocks t - 1 and t - 2 (-1: none yet, the block then does not fade).
-template <int KU, bool BANK>
-__global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restrict__ xnew, int x_cplx, int64_t ldx, const void* __restrict__ hist,
+// GROUP: grid (P, 2, L): listener l = blockIdx.z has its block at xnew + l lsx, its index at set_p + l lset, pos_p and sel at
+// + l lpos, and its part of hist and ring by the shapes.
+template <int KU, bool BANK, bool GROUP>
+__global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restrict__ xnew_, int x_cplx, int64_t ldx, const void* __restrict__ hist_,
                                                            int C, int planes2, const cplx* __restrict__ Wf, int B, int log2n, int P,
-                                                           const int* __restrict__ pos_p, cplx* __restrict__ ring,
-                                                           const int* __restrict__ set_p, const int* __restrict__ sel, int S) {
+                                                           const int* __restrict__ pos_p_, cplx* __restrict__ ring_,
+                                                           const int* __restrict__ set_p_, const int* __restrict__ sel_, int S,
+                                                           DsStrides<GROUP> ls) {
     constexpr int NLD = DS_ELEMS / DS_NT;
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     const int Nf = 2 * B, Pf = B + 1, mask = Nf - 1;
+    const double* xnew = reinterpret_cast<const double*>(xnew_);
+    const double* hist = reinterpret_cast<const double*>(hist_);
+    const int* pos_p = pos_p_;
+    const int* sel = sel_;
+    const int* set_p = set_p_;
+    cplx* ring = ring_;
+    if constexpr (GROUP) {
+        const int64_t l = blockIdx.z;               // the listener
+        xnew += l * ls.lsx * (x_cplx ? 2 : 1);      // (in doubles)
+        hist += l * C * B * (planes2 ? 2 : 1);
+        pos_p += l * ls.lpos;
+        if (BANK) sel += l * ls.lpos;
+        if (set_p) set_p += l * ls.lset;
+        ring += l * 2 * P * Pf;
+    }
     const int NTP = DS_ELEMS >> log2n;              // transforms per round
     cplx* buf = reinterpret_cast<cplx*>(dyn);      // [NTP][Nf], padded
     cplx* tws = buf + (DS_ELEMS + DS_ELEMS / 16);   // [Nf / 2]
@@ -103,9 +135,9 @@ __global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restric
     cplx acc[KU];
 #pragma unroll
     for (int u = 0; u < KU; ++u) acc[u] = mk(0, 0);
-    const double* xr = reinterpret_cast<const double*>(xnew);
+    const double* xr = xnew;
     const cplx* xc = reinterpret_cast<const cplx*>(xnew);
-    const double* hr = reinterpret_cast<const double*>(hist);
+    const double* hr = hist;
     const cplx* hc = reinterpret_cast<const cplx*>(hist);
     // a round's samples travel global -> registers -> LDS; the loads of round r + 1 are issued before the transforms of round r
     cplx xv[NLD];
@@ -219,20 +251,25 @@ __global__ void __launch_bounds__(DS_NT) ds_forward_kernel(const void* __restric
 // workgroup 0: out[i] (left), out[ldo + i] (right) = the last B samples of IFFT(ring slot `pos`) -- both ears in one packed
 // transform, Y_L + i Y_R with Y_e[N - k] = conj(Y_e[k]) -- and pos <- (pos + 1) mod P; with a bank (sel not null) the same thread
 // moves the selection on: sel <- (this block's index as the forward kernel took it, the previous block's).  The other workgroups:
-// hist <- the block
-__global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restrict__ ring, int B, int log2n, int P, int* __restrict__ pos_p,
-                                                           double* __restrict__ out, int64_t ldo, const void* __restrict__ xnew, int x_cplx,
-                                                           int64_t ldx, void* __restrict__ hist, int planes2, int C,
-                                                           const int* __restrict__ set_p, int* __restrict__ sel, int S) {
+// hist <- the block.  GROUP: grid (1 + ncopy, L): listener l = blockIdx.y, the pointers as in the forward kernel, out at + l lso
+template <bool GROUP>
+__global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restrict__ ring_, int B, int log2n, int P, int* __restrict__ pos_p_,
+                                                           double* __restrict__ out_, int64_t ldo, const void* __restrict__ xnew_, int x_cplx,
+                                                           int64_t ldx, void* __restrict__ hist_, int planes2, int C,
+                                                           const int* __restrict__ set_p_, int* __restrict__ sel_, int S, DsStrides<GROUP> ls) {
     const int tid = threadIdx.x;
+    int64_t l = 0;   // the listener
+    if constexpr (GROUP) l = blockIdx.y;
     if (blockIdx.x > 0) {
         const int64_t total = (int64_t)C * B;
-        const double* xr = reinterpret_cast<const double*>(xnew);
-        const cplx* xc = reinterpret_cast<const cplx*>(xnew);
+        const double* xr = reinterpret_cast<const double*>(xnew_);
+        double* hist = reinterpret_cast<double*>(hist_);
+        if constexpr (GROUP) { xr += l * ls.lsx * (x_cplx ? 2 : 1); hist += l * total * (planes2 ? 2 : 1); }
+        const cplx* xc = reinterpret_cast<const cplx*>(xr);
         for (int64_t idx = (int64_t)(blockIdx.x - 1) * DS_NT + tid; idx < total; idx += (int64_t)(gridDim.x - 1) * DS_NT) {
             const int64_t c = idx >> (log2n - 1), i = idx & (B - 1);
             if (planes2) reinterpret_cast<cplx*>(hist)[idx] = x_cplx ? xc[c * ldx + i] : mk(xr[c * ldx + i], 0.0);
-            else reinterpret_cast<double*>(hist)[idx] = xr[c * ldx + i];
+            else hist[idx] = xr[c * ldx + i];
         }
         return;
     }
@@ -240,6 +277,18 @@ __global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restric
     const int Nf = 2 * B, Pf = B + 1;
     cplx* buf = reinterpret_cast<cplx*>(dyn);      // [Nf], padded
     cplx* tws = buf + (Nf + Nf / 16);               // [Nf / 2]
+    const cplx* ring = ring_;
+    int* pos_p = pos_p_;
+    int* sel = sel_;
+    const int* set_p = set_p_;
+    double* out = out_;
+    if constexpr (GROUP) {
+        ring += l * 2 * P * Pf;
+        pos_p += l * ls.lpos;
+        if (sel) sel += l * ls.lpos;
+        if (set_p) set_p += l * ls.lset;
+        out += l * ls.lso;
+    }
     const int pos = *pos_p;
     int sel_new0 = 0, sel_new1 = 0;   // the selection after this block, read ahead of the transform
     if (sel) {
@@ -278,15 +327,15 @@ void ds_attributes() {
     if (!once.first()) return;
 #define EMAGLS_DS_ATTR(K) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024))
     EMAGLS_DS_ATTR(ds_filter_kernel);
-    EMAGLS_DS_ATTR(ds_inverse_kernel);
-    EMAGLS_DS_ATTR((ds_forward_kernel<1, false>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<2, false>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<3, false>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<5, false>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<1, true>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<2, true>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<3, true>));
-    EMAGLS_DS_ATTR((ds_forward_kernel<5, true>));
+    EMAGLS_DS_ATTR(ds_inverse_kernel<false>);
+    EMAGLS_DS_ATTR(ds_inverse_kernel<true>);
+#define EMAGLS_DS_ATTR_KU(KU) EMAGLS_DS_ATTR((ds_forward_kernel<KU, false, false>)); EMAGLS_DS_ATTR((ds_forward_kernel<KU, true, false>)); \
+                              EMAGLS_DS_ATTR((ds_forward_kernel<KU, false, true>)); EMAGLS_DS_ATTR((ds_forward_kernel<KU, true, true>))
+    EMAGLS_DS_ATTR_KU(1);
+    EMAGLS_DS_ATTR_KU(2);
+    EMAGLS_DS_ATTR_KU(3);
+    EMAGLS_DS_ATTR_KU(5);
+#undef EMAGLS_DS_ATTR_KU
 #undef EMAGLS_DS_ATTR
 }
 
@@ -307,24 +356,31 @@ void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B,
 }
 
 void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, const int* set, int standing, double* out,
-                                int64_t ldo, hipStream_t st) {
+                                int64_t ldo, hipStream_t st, int64_t lsx, int lset, int64_t lso) {
     ds_attributes();
     const int log2n = ds_log2(2 * s.B), Pf = s.B + 1, ku = (Pf + DS_NT - 1) / DS_NT;
-    const dim3 grid((unsigned)s.P, 2);
+    const bool group = s.L > 1;   // (a group of one listener is the single stream)
+    const dim3 grid((unsigned)s.P, 2, (unsigned)s.L);
     const size_t dyn = ds_forward_lds(s.B);
     int* sel = s.S > 1 ? s.pos + 1 : nullptr;   // (a bank of one set has no selection to keep)
+    const DsListeners ls{lsx, s.S > 1 ? 3 : 1 /* ints of a listener's position and selection */, lset, lso};
     // a window the host knows to meet one set alone runs the plain instance on that set's spectra: the same arithmetic, without
     // the selection's loads (the inverse kernel still moves the selection on)
     const cplx* Wf = s.Wf + (standing > 0 ? (int64_t)standing * 2 * s.P * (s.planes2 ? 2 * s.C : s.C) * Pf : 0);
-#define EMAGLS_DS_GO(KU, BANK) ds_forward_kernel<KU, BANK><<<grid, DS_NT, dyn, st>>>(x, x_cplx ? 1 : 0, ldx, s.hist, s.C, s.planes2 ? 1 : 0, Wf, s.B, log2n, s.P, s.pos, s.ring, set, sel, s.S)
-#define EMAGLS_DS_KU(BANK) if (ku == 1) EMAGLS_DS_GO(1, BANK); else if (ku == 2) EMAGLS_DS_GO(2, BANK); else if (ku == 3) EMAGLS_DS_GO(3, BANK); else EMAGLS_DS_GO(5, BANK)
-    if (sel && standing < 0) { EMAGLS_DS_KU(true); } else { EMAGLS_DS_KU(false); }
+#define EMAGLS_DS_GO(KU, BANK, GROUP, LS) ds_forward_kernel<KU, BANK, GROUP><<<grid, DS_NT, dyn, st>>>(x, x_cplx ? 1 : 0, ldx, s.hist, s.C, s.planes2 ? 1 : 0, Wf, s.B, log2n, s.P, s.pos, s.ring, set, sel, s.S, LS)
+#define EMAGLS_DS_KU(BANK, GROUP, LS) if (ku == 1) EMAGLS_DS_GO(1, BANK, GROUP, LS); else if (ku == 2) EMAGLS_DS_GO(2, BANK, GROUP, LS); else if (ku == 3) EMAGLS_DS_GO(3, BANK, GROUP, LS); else EMAGLS_DS_GO(5, BANK, GROUP, LS)
+    if (group) { if (sel) { EMAGLS_DS_KU(true, true, ls); } else { EMAGLS_DS_KU(false, true, ls); } }
+    else if (sel && standing < 0) { EMAGLS_DS_KU(true, false, DsSingle{}); } else { EMAGLS_DS_KU(false, false, DsSingle{}); }
 #undef EMAGLS_DS_KU
 #undef EMAGLS_DS_GO
     KERNEL_CHECK();
     const unsigned ncopy = (unsigned)std::min<int64_t>(32, ceil_div((int64_t)s.C * s.B, 4 * DS_NT));
-    ds_inverse_kernel<<<1 + ncopy, DS_NT, ds_single_lds(s.B), st>>>(s.ring, s.B, log2n, s.P, s.pos, out, ldo, x, x_cplx ? 1 : 0, ldx, s.hist,
-                                                                  s.planes2 ? 1 : 0, s.C, set, sel, s.S);
+    if (group)
+        ds_inverse_kernel<true><<<dim3(1 + ncopy, (unsigned)s.L), DS_NT, ds_single_lds(s.B), st>>>(s.ring, s.B, log2n, s.P, s.pos, out, ldo, x, x_cplx ? 1 : 0, ldx, s.hist,
+                                                                                             s.planes2 ? 1 : 0, s.C, set, sel, s.S, ls);
+    else
+        ds_inverse_kernel<false><<<1 + ncopy, DS_NT, ds_single_lds(s.B), st>>>(s.ring, s.B, log2n, s.P, s.pos, out, ldo, x, x_cplx ? 1 : 0, ldx, s.hist,
+                                                                         s.planes2 ? 1 : 0, s.C, set, sel, s.S, DsSingle{});
     KERNEL_CHECK();
 }
 

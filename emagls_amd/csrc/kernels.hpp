@@ -207,16 +207,19 @@ int rotate_order(int layout, int64_t C);
 // yaw rotation of in [C][n] (real, or interleaved complex): out [C][n], complex when in_cplx || cplx_basis.  yaw: device, one
 // angle (per_sample false) or n angles.  transpose: the filter-side form of a fixed angle (w Rot instead of x Rot^T).
 // ld_in / ld_out: elements between the channels of in / out (0: n) -- a block of a longer signal, decode_stream.hip
+// L listeners of the one signal `in` (a listener group): listener l takes its angles at yaw + l la and writes out + l lo (elements)
 void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
-                       bool transpose, void* out, hipStream_t st, int64_t ld_in = 0, int64_t ld_out = 0);
+                       bool transpose, void* out, hipStream_t st, int64_t ld_in = 0, int64_t ld_out = 0, int L = 1, int64_t la = 0,
+                       int64_t lo = 0);
 // ---- rotate3.hip
 int rotate3_max_order();   // 15: the largest SH order of the three-axis rotation
 // rotation R = Rz(yaw) Ry(pitch) Rx(roll) of the SH (ACN) signal in [C][n] (real, or interleaved complex): out [C][n], complex
 // when in_cplx || cplx_basis.  Each angle: device pointer, null (0), one value (*_ps false) or n values.  transpose: the
-// filter-side form of a fixed rotation (w M instead of x M^T).  C = (N+1)^2 with N <= 15, else Error.  ld_in / ld_out as above
+// filter-side form of a fixed rotation (w M instead of x M^T).  C = (N+1)^2 with N <= 15, else Error.  ld_in / ld_out as above.
+// L listeners as above, la[3]: the listener strides of yaw, pitch and roll (null: L = 1)
 void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch,
                     bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st, int64_t ld_in = 0,
-                    int64_t ld_out = 0);
+                    int64_t ld_out = 0, int L = 1, const int64_t* la = nullptr, int64_t lo = 0);
 // M [(N+1)^2 x (N+1)^2] column-major, out_row = in_row M^T; the same device code as launch_rotate3
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st);
 void rotate3_cache_clear();
@@ -234,20 +237,23 @@ struct DecodeStreamState {
     bool planes2 = false;   // the signal is decoded as 2C real planes [re x; im x] (complex signal, or complex basis with a rotation)
     int B = 0, P = 0;       // block size, partitions
     int S = 1;              // filter sets of the bank
-    cplx* Wf = nullptr;     // [S][2][P][Cp][B + 1] partition spectra, Cp = planes2 ? 2C : C
-    cplx* ring = nullptr;   // [2][P][B + 1] pending output spectra
-    void* hist = nullptr;   // [C][B] the previous block (cplx when planes2)
-    int* pos = nullptr;     // the ring slot of the next output block; with S > 1 followed by the set indices of the two previous
-                            // blocks (-1: none yet)
+    int L = 1;              // listeners (a listener group; a stream is the group of one)
+    cplx* Wf = nullptr;     // [S][2][P][Cp][B + 1] partition spectra, Cp = planes2 ? 2C : C: one bank for all listeners
+    cplx* ring = nullptr;   // [L][2][P][B + 1] pending output spectra
+    void* hist = nullptr;   // [L][C][B] the previous block (cplx when planes2)
+    int* pos = nullptr;     // [L][S > 1 ? 3 : 1] the ring slot of the next output block; with S > 1 followed by the set indices of
+                            // the two previous blocks (-1: none yet)
 };
 bool decode_stream_block_ok(int64_t B);   // a power of two from 64 to 2048
 // Wf from the real filter planes wpl [S][2][Cp][len] (device)
 void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, int64_t S, cplx* Wf, hipStream_t st);
 // one block: x + c ldx = channel c of the (rotated) block, B samples (cplx only when planes2); set: device, this block's set index
 // (null: the previous block's; not looked at when S == 1); standing: the set the host KNOWS this block and the two before it to be
-// on (their window then runs the plain kernel on that set), -1 when it does not know; out[i], out[ldo + i] = the two ears
+// on (their window then runs the plain kernel on that set), -1 when it does not know; out[i], out[ldo + i] = the two ears.
+// With s.L > 1 listeners (standing = -1): listener l reads its block at x + l lsx (elements; 0: every listener reads x), its
+// index at set + l lset, and writes its ears at out + l lso
 void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, const int* set, int standing, double* out,
-                                int64_t ldo, hipStream_t st);
+                                int64_t ldo, hipStream_t st, int64_t lsx = 0, int lset = 0, int64_t lso = 0);
 
 // ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables, resample.hip's taps and the decode family's work buffers
 void decode_family_cache_clear();

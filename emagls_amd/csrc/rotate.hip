@@ -31,13 +31,16 @@ __device__ __forceinline__ cplx widen(cplx v) { return v; }
 // one thread = one sample (row) of every channel; columns are channel planes of n values, so a wave's loads are contiguous
 // IC / OC: input / output complex (OC = IC || complex basis).  sgn = -1 applies the transpose of the real-basis rotation
 // (the decoding filters of a fixed angle: sum_i w_i * (x Rot^T)_i = sum_j (w Rot)_j * x_j); the complex basis is diagonal.
+// grid (., L): listener l = blockIdx.y turns the one signal by its angles, yaw_ + l la, into out_ + l lo (a listener group)
 template <bool IC, bool OC>
 __global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict__ in_, int64_t n, int N, int layout, int cb,
-                                                         const double* __restrict__ yaw, int per_sample, double sgn, void* __restrict__ out_, int64_t ldi, int64_t ldo) {
+                                                         const double* __restrict__ yaw_, int per_sample, double sgn, void* __restrict__ out_, int64_t ldi, int64_t ldo,
+                                                         int64_t la, int64_t lo) {
     using TI = typename Val<IC>::T;
     using TO = typename Val<OC>::T;
     const TI* __restrict__ in = reinterpret_cast<const TI*>(in_);
-    TO* __restrict__ out = reinterpret_cast<TO*>(out_);
+    TO* __restrict__ out = reinterpret_cast<TO*>(out_) + (int64_t)blockIdx.y * lo;
+    const double* __restrict__ yaw = yaw_ + (int64_t)blockIdx.y * la;
     const int nl = layout == 0 ? N + 1 : 1;   // channels of one |m|: SH orders n = m..N, CH one pair
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
         const double th = fmod(yaw[per_sample ? t : 0], 2.0 * kPi);
@@ -76,17 +79,17 @@ __global__ void __launch_bounds__(256) rotate_yaw_kernel(const void* __restrict_
 }  // namespace
 
 void launch_rotate_yaw(const void* in, bool in_cplx, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample,
-                       bool transpose, void* out, hipStream_t st, int64_t ld_in, int64_t ld_out) {
+                       bool transpose, void* out, hipStream_t st, int64_t ld_in, int64_t ld_out, int L, int64_t la, int64_t lo) {
     if (n <= 0) return;
     const int64_t ldi = ld_in ? ld_in : n, ldo = ld_out ? ld_out : n;
     const int N = rotate_order(layout, C);
     if (N < 0) throw Error(1, "rotate_yaw: the channel count fits neither (N+1)^2 (SH) nor 2N+1 (CH)");
-    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 256), 65536);
+    const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, 256), 65536), (unsigned)L);
     const double sgn = (transpose && !cplx_basis) ? -1.0 : 1.0;
     const int cb = cplx_basis ? 1 : 0, ps = per_sample ? 1 : 0;
-    if (in_cplx) rotate_yaw_kernel<true, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo);
-    else if (cplx_basis) rotate_yaw_kernel<false, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo);
-    else rotate_yaw_kernel<false, false><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo);
+    if (in_cplx) rotate_yaw_kernel<true, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo, la, lo);
+    else if (cplx_basis) rotate_yaw_kernel<false, true><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo, la, lo);
+    else rotate_yaw_kernel<false, false><<<grid, 256, 0, st>>>(in, n, N, layout, cb, yaw, ps, sgn, out, ldi, ldo, la, lo);
     KERNEL_CHECK();
 }
 

@@ -252,19 +252,26 @@ __device__ __forceinline__ void load_j(int N, double* J, const double* __restric
 // loads of the next order in flight; the trigonometry of zyz() needs about 120 VGPRs whatever NB is
 __host__ __device__ constexpr int r3_waves(int NB, bool cplx_v) { return NB <= 2 ? 4 : NB <= 4 ? (cplx_v ? 3 : 4) : NB <= 8 ? (cplx_v ? 2 : 3) : (cplx_v ? 1 : 2); }
 
+// grid (., L): listener blockIdx.y turns the one signal by its angles (each at + l la[.]) into out_ + l lo (a listener group)
+struct R3Listener { int64_t la[3], lo; };
+
 // NB: the largest order of the instantiation (buckets 2, 4, 8, 15), N the order of the call
 template <int NB, bool IC, bool CB>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(r3_waves(NB, IC || CB)))) rotate3_kernel(int N, const void* __restrict__ in_, int64_t n, const double* __restrict__ yaw, int yps,
                                                       const double* __restrict__ pitch, int pps, const double* __restrict__ roll, int rps,
-                                                      int transpose, const double* __restrict__ jpk, void* __restrict__ out_, int64_t ldi, int64_t ldo) {
+                                                      int transpose, const double* __restrict__ jpk, void* __restrict__ out_, int64_t ldi, int64_t ldo,
+                                                      R3Listener ls) {
     using TI = std::conditional_t<IC, cplx, double>;
     using V = std::conditional_t<IC || CB, cplx, double>;
     __shared__ double J[jpk_off(NB + 1)];
     load_j(N, J, jpk);
     const TI* __restrict__ in = reinterpret_cast<const TI*>(in_);
-    V* __restrict__ out = reinterpret_cast<V*>(out_);
+    const int64_t lis = blockIdx.y;   // the listener
+    V* __restrict__ out = reinterpret_cast<V*>(out_) + lis * ls.lo;
+    const int64_t oy = lis * ls.la[0], op = lis * ls.la[1], orl = lis * ls.la[2];
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        const Ang a = zyz(yaw ? yaw[yps ? t : 0] : 0.0, pitch ? pitch[pps ? t : 0] : 0.0, roll ? roll[rps ? t : 0] : 0.0, transpose != 0);
+        const Ang a = zyz(yaw ? yaw[oy + (yps ? t : 0)] : 0.0, pitch ? pitch[op + (pps ? t : 0)] : 0.0, roll ? roll[orl + (rps ? t : 0)] : 0.0,
+                          transpose != 0);
         rot_orders<0, NB, CB, V>(N, J, a, [&](int k) { return to_v(in[(int64_t)k * ldi + t], (V*)nullptr); },
                                 [&](int k, V v) { out[(int64_t)k * ldo + t] = v; });
     }
@@ -307,11 +314,12 @@ const double* j_pack(hipStream_t st) {
 }
 
 template <int NB> void launch_nb(int N, const void* in, bool ic, int64_t n, bool cb, const double* yaw, bool yps, const double* pitch,
-                                bool pps, const double* roll, bool rps, bool transpose, const double* jpk, void* out, hipStream_t st, int64_t ldi, int64_t ldo) {
-    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, 256), 1 << 20);   // one sample per lane up to 268 M samples
+                                bool pps, const double* roll, bool rps, bool transpose, const double* jpk, void* out, hipStream_t st, int64_t ldi, int64_t ldo,
+                                int L, const R3Listener& ls) {
+    const dim3 grid((unsigned)std::min<int64_t>(ceil_div(n, 256), 1 << 20), (unsigned)L);   // one sample per lane up to 268 M samples
     auto k = ic ? (cb ? rotate3_kernel<NB, true, true> : rotate3_kernel<NB, true, false>)
                 : (cb ? rotate3_kernel<NB, false, true> : rotate3_kernel<NB, false, false>);
-    k<<<grid, 256, 0, st>>>(N, in, n, yaw, yps, pitch, pps, roll, rps, transpose ? 1 : 0, jpk, out, ldi, ldo);
+    k<<<grid, 256, 0, st>>>(N, in, n, yaw, yps, pitch, pps, roll, rps, transpose ? 1 : 0, jpk, out, ldi, ldo, ls);
     KERNEL_CHECK();
 }
 
@@ -332,16 +340,18 @@ void check_order(int N) {
 int rotate3_max_order() { return R3_NMAX; }
 
 void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch,
-                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st, int64_t ld_in, int64_t ld_out) {
+                    bool pitch_ps, const double* roll, bool roll_ps, bool transpose, void* out, hipStream_t st, int64_t ld_in, int64_t ld_out, int L,
+                    const int64_t* la, int64_t lo) {
     if (n <= 0) return;
     const int64_t ldi = ld_in ? ld_in : n, ldo = ld_out ? ld_out : n;
     const int N = rotate_order(0, C);
     check_order(N);
     const double* jpk = j_pack(st);
-    if (N <= 2) launch_nb<2>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
-    else if (N <= 4) launch_nb<4>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
-    else if (N <= 8) launch_nb<8>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
-    else launch_nb<R3_NMAX>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo);
+    const R3Listener ls{{la ? la[0] : 0, la ? la[1] : 0, la ? la[2] : 0}, lo};
+    if (N <= 2) launch_nb<2>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
+    else if (N <= 4) launch_nb<4>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
+    else if (N <= 8) launch_nb<8>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
+    else launch_nb<R3_NMAX>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
 }
 
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st) {

@@ -364,6 +364,49 @@ int emagls_decode_stream_push_sets_device(emagls_decode_stream* s, const void* d
 /* The number of filter sets of the stream's bank. */
 int emagls_decode_stream_sets(const emagls_decode_stream* s, int64_t* n_sets);
 
+/* ---- a listener group: many listeners of one sound field in one push ----
+ * One bank of n_sets >= 1 filter sets, its spectra stored once, and n_listeners listeners, each with the state a decode stream has
+ * (ring, previous block, ring position, the two previous set indices).  One push takes one block of the common signal and, per
+ * listener, their angles and their set indices, and returns every listener's pair of ear signals.  DEFINING PROPERTY: listener l's
+ * output is, bit for bit, what a decode stream of the same bank returns when it is fed the same blocks with listener l's angles
+ * and set indices; the rotation convention, the cross-fade rule and the clamp of device indices are the stream's.  One choice is
+ * made per push and not per listener: the push takes the yaw rule when NO listener has a pitch or a roll (host entry: when every
+ * pitch and roll value of the push is 0), otherwise every listener goes through the three-axis rotation, as a stream does that is
+ * given pitch and roll arrays.  A block is at most three kernel launches for the whole group, whatever n_listeners is.
+ * 1 <= n_listeners <= 4096: below, EMAGLS_ERR_ARG; above, EMAGLS_ERR_UNSUPPORTED.  Every other argument and limit as
+ * emagls_decode_stream_create_bank; every argument is checked before the device is touched, and the object exists without a
+ * device.  emagls_cache_clear() does not touch a live group.  One push at a time per group. */
+typedef struct emagls_decode_group emagls_decode_group;
+int emagls_decode_group_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
+                               int in_is_complex, int layout, int basis, int64_t block, int64_t n_listeners, emagls_decode_group** g);
+
+/* in [nsamp x nch], the common signal, nsamp = k * block (else EMAGLS_ERR_ARG); out [L][nsamp x 2], L = n_listeners.  Every array
+ * is listener-major.  Each of n_yaw, n_pitch, n_roll is 0 (absent: 0), L (one value per listener, constant over this push) or
+ * L * nsamp ([L][nsamp]); n_set is 0 (every listener keeps their set; set 0 on a fresh listener), L (one index per listener for
+ * every block of the push) or L * nsamp / block ([L][nsamp / block]).  Any other count, a null array with a positive count, or an
+ * index outside [0, n_sets - 1] is EMAGLS_ERR_ARG.  Angles need what a stream's push needs of the layout and the order. */
+int emagls_decode_group_push(emagls_decode_group* g, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set, const double* yaw,
+                             int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll, double* out);
+
+/* emagls_decode_group_push on device arrays: enqueued on `stream` and NOT synchronised; no allocation (the rotated blocks of all
+ * listeners have a buffer sized at creation), no copy of state.  Device arrays are not read by the host: only absent pitch and
+ * roll make a push yaw-only, and the kernels clamp every set index into [0, n_sets - 1]. */
+int emagls_decode_group_push_device(emagls_decode_group* g, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
+                                    const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll,
+                                    int64_t n_roll, double* d_out, void* stream);
+
+/* listener = -1: every listener back to zero history.  0 .. L - 1: that listener alone (ring, overlap, position, selection) -- what
+ * a listener who joins gets: what follows equals a fresh stream bit for bit, and the others are untouched.  Anything else is
+ * EMAGLS_ERR_ARG.  Waits for the pushes in flight. */
+int emagls_decode_group_reset(emagls_decode_group* g, int64_t listener);
+
+/* block, partitions, listeners, state_bytes (grows with the listeners), filter_bytes (does not) and the kernel launches per block
+ * of the whole group (each output optional). */
+int emagls_decode_group_info(const emagls_decode_group* g, int64_t* block, int64_t* partitions, int64_t* listeners, int64_t* state_bytes,
+                             int64_t* filter_bytes, int* launches_per_block);
+
+int emagls_decode_group_destroy(emagls_decode_group* g);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

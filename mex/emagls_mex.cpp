@@ -69,6 +69,17 @@ emagls_decode_stream* stream_of(const mxArray* a, size_t* index = nullptr) {
     if (index) *index = i - 1;
     return g_streams[i - 1];
 }
+// listener groups likewise (mex/binauralDecodeGroup.m)
+std::vector<emagls_decode_group*> g_groups;
+struct GroupShape { mwSize nch; bool in_complex; mwSize listeners; };
+std::vector<GroupShape> g_group_shapes;
+emagls_decode_group* group_of(const mxArray* a, size_t* index = nullptr) {
+    const double v = (a && mxIsDouble(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
+    const size_t i = (v >= 1 && v <= (double)g_groups.size() && v == std::floor(v)) ? (size_t)v : 0;
+    if (!i || !g_groups[i - 1]) mexErrMsgIdAndTxt("eMagLS:arg", "invalid decode group handle");
+    if (index) *index = i - 1;
+    return g_groups[i - 1];
+}
 int layout_of(const mxArray* a) {
     if (!a || mxIsEmpty(a)) return EMAGLS_LAYOUT_SH;
     char buf[8] = {0};
@@ -77,9 +88,38 @@ int layout_of(const mxArray* a) {
     if (std::strcmp(buf, "sh")) mexErrMsgIdAndTxt("eMagLS:arg", "rotation domain must be 'sh' or 'ch'");
     return EMAGLS_LAYOUT_SH;
 }
+// the decoding filters of 'stream_create' / 'group_create', prhs[1] and prhs[2]: [len x nch], or [len x nch x numSets] -- column-major,
+// the sets of a bank lie one after the other as the library takes them
+struct FilterArgs { mwSize len, ch, nsets; bool wc; };
+FilterArgs filter_args(const mxArray* const* prhs) {
+    const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+    const mwSize* dims = mxGetDimensions(prhs[1]);
+    if (nd > 3) mexErrMsgIdAndTxt("eMagLS:arg", "the decoding filters must be [len x numChannels] or [len x numChannels x numSets]");
+    const FilterArgs f{mxGetM(prhs[1]), nd >= 2 ? dims[1] : 1, nd == 3 ? dims[2] : 1, (bool)mxIsComplex(prhs[1])};
+    bool same = mxIsDouble(prhs[1]) && mxIsDouble(prhs[2]) && mxGetNumberOfDimensions(prhs[2]) == nd;
+    for (mwSize i = 0; same && i < nd; ++i) same = mxGetDimensions(prhs[2])[i] == dims[i];
+    if (!same) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must be double arrays of equal size");
+    if (f.wc != (bool)mxIsComplex(prhs[2])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
+    return f;
+}
+bool truthy(const mxArray* a) { return mxIsLogicalScalarTrue(a) || (mxIsDouble(a) && !mxIsEmpty(a) && mxGetScalar(a) != 0); }
+// a ONE-based set index array as the library's zero-based int32
+std::vector<int32_t> zero_based(const mxArray* a) {
+    std::vector<int32_t> sets;
+    if (!a || mxIsEmpty(a)) return sets;
+    const double* v = dbl(a, "setIndex");
+    sets.resize(mxGetNumberOfElements(a));
+    for (size_t i = 0; i < sets.size(); ++i) {
+        if (!(v[i] >= 1.0 && v[i] <= 2147483647.0) || v[i] != std::floor(v[i]))
+            mexErrMsgIdAndTxt("eMagLS:arg", "setIndex must hold positive integers (the sets count from 1)");
+        sets[i] = (int32_t)v[i] - 1;
+    }
+    return sets;
+}
 // the plans the one-shot entry points cache (device buffers, captured graphs) are released when the MEX file is cleared
 void at_exit() {
     for (emagls_decode_stream*& s : g_streams) { if (s) emagls_decode_stream_destroy(s); s = nullptr; }
+    for (emagls_decode_group*& g : g_groups) { if (g) emagls_decode_group_destroy(g); g = nullptr; }
     emagls_cache_clear();
 }
 
@@ -98,6 +138,12 @@ void at_exit() {
 // out = emagls_mex('stream_push', h, in[, yawRad, pitchRad, rollRad, setIndex])   in [k*blockSize x nch]; each angle [], a scalar or one per
 //                                     sample; setIndex ONE-based: [] (keep the set), a scalar or one per block
 // emagls_mex('stream_reset', h)      emagls_mex('stream_destroy', h)
+// h = emagls_mex('group_create', wL, wR, blockSize, numListeners[, shDefinition, domain, complexInput])   a listener group
+//                                     (mex/binauralDecodeGroup.m): many listeners of one sound field in one push
+// out = emagls_mex('group_push', h, in[, yawRad, pitchRad, rollRad, setIndex])   in [k*blockSize x nch], the common signal; listeners run
+//                                     along the last dimension: out [n x 2 x L]; each angle [], [1 x L] or [n x L]; setIndex ONE-based,
+//                                     [], [1 x L] or [nBlocks x L]
+// emagls_mex('group_reset', h[, listener])   ONE-based; without it all listeners      emagls_mex('group_destroy', h)
 // emagls_mex('resample', x, p, q)   MATLAB's resample(x, p, q) (N = 10, bta = 5): a row vector along its length, else per column
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
 // emagls_mex('rotate3', in, yawRad, pitchRad, rollRad[, shDefinition])   three-axis rotation of an SH signal (orders 0-15)
@@ -161,18 +207,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     }
     if (c == "stream_create") {
         if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "stream_create needs (wL, wR, blockSize[, shDefinition, domain, complexInput])");
-        // [len x nch], or [len x nch x numSets]: column-major, the sets of a bank lie one after the other as the library takes them
-        const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
-        const mwSize* dims = mxGetDimensions(prhs[1]);
-        if (nd > 3) mexErrMsgIdAndTxt("eMagLS:arg", "the decoding filters must be [len x numChannels] or [len x numChannels x numSets]");
-        const mwSize len = mxGetM(prhs[1]), ch = nd >= 2 ? dims[1] : 1, nsets = nd == 3 ? dims[2] : 1;
-        const bool wc = mxIsComplex(prhs[1]);
-        bool same = mxIsDouble(prhs[1]) && mxIsDouble(prhs[2]) && mxGetNumberOfDimensions(prhs[2]) == nd;
-        for (mwSize i = 0; same && i < nd; ++i) same = mxGetDimensions(prhs[2])[i] == dims[i];
-        if (!same) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must be double arrays of equal size");
-        if (wc != (bool)mxIsComplex(prhs[2])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
+        const FilterArgs f = filter_args(prhs);
+        const mwSize len = f.len, ch = f.ch, nsets = f.nsets;
+        const bool wc = f.wc;
         const int basis = basis_of(nrhs > 4 ? prhs[4] : nullptr), layout = layout_of(nrhs > 5 ? prhs[5] : nullptr);
-        const int ic = nrhs > 6 && (mxIsLogicalScalarTrue(prhs[6]) || (mxIsDouble(prhs[6]) && !mxIsEmpty(prhs[6]) && mxGetScalar(prhs[6]) != 0));
+        const int ic = nrhs > 6 && truthy(prhs[6]);
         emagls_decode_stream* st = nullptr;
         const int rc = emagls_decode_stream_create_bank((int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic,
                                                         layout, basis, (int64_t)mxGetScalar(prhs[3]), &st);
@@ -200,16 +239,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (int i = 0; i < 3; ++i)
             if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) { ang[i] = dbl(prhs[3 + i], names[i]); cnt[i] = mxGetNumberOfElements(prhs[3 + i]); }
         // setIndex (prhs[6]): MATLAB counts the sets from 1, the library from 0
-        std::vector<int32_t> sets;
-        if (nrhs > 6 && !mxIsEmpty(prhs[6])) {
-            const double* v = dbl(prhs[6], "setIndex");
-            sets.resize(mxGetNumberOfElements(prhs[6]));
-            for (size_t i = 0; i < sets.size(); ++i) {
-                if (!(v[i] >= 1.0 && v[i] <= 2147483647.0) || v[i] != std::floor(v[i]))
-                    mexErrMsgIdAndTxt("eMagLS:arg", "setIndex must hold positive integers (the sets count from 1)");
-                sets[i] = (int32_t)v[i] - 1;
-            }
-        }
+        const std::vector<int32_t> sets = zero_based(nrhs > 6 ? prhs[6] : nullptr);
         plhs[0] = mxCreateDoubleMatrix(n, 2, mxREAL);
         const int rc = emagls_decode_stream_push_sets(st, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(),
                                                       ang[0], (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2], (int64_t)cnt[2],
@@ -223,6 +253,76 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         emagls_decode_stream* st = stream_of(prhs[1], &slot);
         const int rc = c == "stream_reset" ? emagls_decode_stream_reset(st) : emagls_decode_stream_destroy(st);
         if (c == "stream_destroy") g_streams[slot] = nullptr;
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "group_create") {
+        if (nrhs < 5) mexErrMsgIdAndTxt("eMagLS:arg", "group_create needs (wL, wR, blockSize, numListeners[, shDefinition, domain, complexInput])");
+        const FilterArgs f = filter_args(prhs);
+        const int basis = basis_of(nrhs > 5 ? prhs[5] : nullptr), layout = layout_of(nrhs > 6 ? prhs[6] : nullptr);
+        const int ic = nrhs > 7 && truthy(prhs[7]);
+        const double nl = mxGetScalar(prhs[4]);
+        if (!(nl == std::floor(nl)) || std::fabs(nl) > 1e9) mexErrMsgIdAndTxt("eMagLS:arg", "numListeners must be an integer");
+        emagls_decode_group* g = nullptr;
+        const int rc = emagls_decode_group_create((int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc, (int64_t)f.len, ic, layout,
+                                                  basis, (int64_t)mxGetScalar(prhs[3]), (int64_t)nl, &g);
+        if (rc) fail(rc);
+        size_t slot = 0;
+        while (slot < g_groups.size() && g_groups[slot]) ++slot;
+        if (slot == g_groups.size()) { g_groups.push_back(nullptr); g_group_shapes.push_back({0, false, 0}); }
+        g_groups[slot] = g;
+        g_group_shapes[slot] = {f.ch, ic != 0, (mwSize)nl};
+        plhs[0] = mxCreateDoubleScalar((double)(slot + 1));
+        return;
+    }
+    if (c == "group_push") {
+        // listeners run along the LAST dimension: column-major [n x L] is the library's listener-major [L][n]
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "group_push needs (handle, in[, yawRad, pitchRad, rollRad, setIndex])");
+        size_t slot = 0;
+        emagls_decode_group* g = group_of(prhs[1], &slot);
+        const GroupShape& gs = g_group_shapes[slot];
+        if (!mxIsDouble(prhs[2]) || mxGetN(prhs[2]) != gs.nch)
+            mexErrMsgIdAndTxt("eMagLS:arg", "in must be a double array with the filters' channel count (%d)", (int)gs.nch);
+        if ((bool)mxIsComplex(prhs[2]) != gs.in_complex)
+            mexErrMsgIdAndTxt("eMagLS:arg", "in must be %s, as the group was created", gs.in_complex ? "complex" : "real");
+        const mwSize n = mxGetM(prhs[2]);
+        // an array of one listener's worth of values but the wrong orientation would be read as another listener's: the last
+        // dimension must be the listeners
+        auto per_listener = [&](const mxArray* a, const char* what) {
+            if (mxGetNumberOfDimensions(a) > 2 || mxGetN(a) != gs.listeners)
+                mexErrMsgIdAndTxt("eMagLS:arg", "%s must have one column per listener (%d)", what, (int)gs.listeners);
+        };
+        const double* ang[3] = {nullptr, nullptr, nullptr};
+        mwSize cnt[3] = {0, 0, 0};
+        static const char* const names[3] = {"horRotAngleRad", "pitchRad", "rollRad"};
+        for (int i = 0; i < 3; ++i)
+            if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) {
+                per_listener(prhs[3 + i], names[i]);
+                ang[i] = dbl(prhs[3 + i], names[i]);
+                cnt[i] = mxGetNumberOfElements(prhs[3 + i]);
+            }
+        if (nrhs > 6 && !mxIsEmpty(prhs[6])) per_listener(prhs[6], "setIndex");
+        const std::vector<int32_t> sets = zero_based(nrhs > 6 ? prhs[6] : nullptr);   // [nBlocks x L], one-based
+        const mwSize dims[3] = {n, 2, gs.listeners};
+        plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+        const int rc = emagls_decode_group_push(g, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(), ang[0],
+                                                (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2], (int64_t)cnt[2], mxGetDoubles(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "group_reset" || c == "group_destroy") {
+        if (nrhs < 2) mexErrMsgIdAndTxt("eMagLS:arg", "%s needs (handle)", cmd);
+        size_t slot = 0;
+        emagls_decode_group* g = group_of(prhs[1], &slot);
+        int64_t listener = -1;   // 'group_reset', h, listener: ONE-based; [] or absent: all listeners
+        if (c == "group_reset" && nrhs > 2 && !mxIsEmpty(prhs[2])) {
+            const double v = mxGetScalar(prhs[2]);
+            if (!(v >= 1.0 && v <= 2147483647.0) || v != std::floor(v))
+                mexErrMsgIdAndTxt("eMagLS:arg", "listener must be a positive integer (the listeners count from 1)");
+            listener = (int64_t)v - 1;
+        }
+        const int rc = c == "group_reset" ? emagls_decode_group_reset(g, listener) : emagls_decode_group_destroy(g);
+        if (c == "group_destroy") g_groups[slot] = nullptr;
         if (rc) fail(rc);
         return;
     }

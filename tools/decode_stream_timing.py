@@ -10,6 +10,7 @@ Gates (exit status 1 when one fails): median (a) < median (b), and median (a) < 
 
     python tools/decode_stream_timing.py [--blocks 2000] [--warm 50] [--run 100] [--shapes 25,512,64 ...] [--stream-only]
                                          [--dry-run] [--out profiles/r10_decode_stream.md]
+                                         [--bank [--sets 3]] [--group [--listeners 1 8 64 256] [--sets 1]]
 --dry-run prints the shapes and the bytes a push moves, computed from the shapes, without a device.
 
 --bank times the bank of filter sets (emagls_decode_stream_create_bank / _push_sets_device) instead, without
@@ -26,6 +27,18 @@ rotation, per shape and alternating in one process, every side on streams of its
 spread = p90 - p10 of a side's run averages.  Gates: (a) median(const) <= median(plain) + its spread: a constant index is meant to
 be the plain stream's arithmetic; (b) median(switch) <= median(three) + the spread of `three`.  A shape that misses a gate is
 reported as such and the exit status is 1.
+
+--group times the listener group (emagls_decode_group_push_device) per shape, number of listeners
+(--listeners) and rotation, alternating in one process on one HIP stream:
+
+  group    one push of the common block for L listeners
+  loop     what a caller does without the group: L plain decode streams (bank streams with --sets > 1) pushed one after the other
+
+Every listener has angles of their own; with --sets S > 1 every listener switches to a new set in every block (indices in device
+memory).  --run pushes per run average (default 100), --blocks / --run run averages per side (default 2000 / 100 = 20); median and
+spread = p90 - p10 of the run averages.  Gates: L >= 8: median(loop) - median(group) > spread(loop) + spread(group); L == 1:
+median(group) <= median(loop) + spread(loop).  Also reported: loop / group, the listeners one device serves in real time at 48 kHz,
+block duration / (group time / L), and the traffic of a push of the whole group, from the shapes.
 """
 import argparse
 import ctypes as C
@@ -118,7 +131,8 @@ def run_shape(lib, L, torch, Cc, ln, B, rotated, blocks, warm, run, stream_only)
     res = {"shape": [Cc, ln, B], "rotation": "ypr" if rotated else "none", "block_us": round(B / FS * 1e6, 1),
            "bytes": push_bytes(Cc, ln, B, rotated)}
     for k, v in times.items():
-        res[k] = {"median_us": round(float(np.median(v)), 2), "p99_us": round(float(np.percentile(v, 99)), 2), "min_us": round(float(np.min(v)), 2)}
+        res[k] = {"median_us": round(float(np.median(v)), 2), "p99_us": round(float(np.percentile(v, 99)), 2), "min_us": round(float(np.min(v)), 2),
+                  "spread_us": round(float(np.percentile(v, 90) - np.percentile(v, 10)), 2)}
     if "window" in res:
         res["window_over_stream"] = round(res["window"]["median_us"] / res["stream"]["median_us"], 2)
     return res
@@ -219,6 +233,115 @@ def run_bank_shape(lib, L, torch, Cc, ln, B, S, blocks, warm, run):
     return res
 
 
+def group_bytes(Cc, ln, B, L, S, rotated):
+    """Bytes a push of the group moves, from the shapes (real signal).  `state`: per listener, L times -- ring read and written,
+    the previous block read, the block read twice and kept, the output; with a rotation the rotated block written and the three
+    angles read.  `filters`: the spectra of one set, which every listener's workgroups read but which are stored once (after the
+    first listener they can come from the caches).  `common`: the block itself, once."""
+    P, Pf = -(-ln // B), B + 1
+    filt = 16 * 2 * P * Cc * Pf
+    per = 2 * 16 * 2 * P * Pf + 8 * Cc * B * 4 + 8 * 2 * B + ((8 * Cc * B + 3 * 8 * B) if rotated else 0)
+    return {"filters_once": filt, "state": L * per, "common": 8 * Cc * B, "compulsory": filt + L * per + 8 * Cc * B,
+            "requested": L * filt + L * per + 8 * Cc * B}
+
+
+def run_group_shape(lib, L, torch, Cc, ln, B, nl, S, rotated, blocks, warm, run):
+    """The sides of --group for one shape, nl listeners."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(Cc + ln + B)
+    rnd = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)   # noqa: E731
+    wL, wR = rnd(S, Cc, ln), rnd(S, Cc, ln)                 # [S][C][len] row-major == S column-major [len x C] arrays
+    d_blk = rnd(Cc, B).to(dev)
+    ang = [(0.3 + 0.01 * torch.cumsum(rnd(nl, B), 1)).to(dev) for _ in range(3)]          # [L][B] per angle
+    d_idx = (torch.arange(S, dtype=torch.int32)[:, None] + torch.arange(nl, dtype=torch.int32)[None, :]).remainder(S).to(dev).contiguous()
+    out_g = torch.zeros((nl, 2, B), dtype=torch.float64, device=dev)
+    out_l = torch.zeros((nl, 2, B), dtype=torch.float64, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    st = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(st.cuda_stream)
+    sh, re = L.LAYOUT["sh"], L.BASIS["real"]
+    hg = C.c_void_p()
+    L.check(lib.emagls_decode_group_create(Cc, S, p(wL), p(wR), 0, ln, 0, sh, re, B, nl, C.byref(hg)))
+    hs = []
+    for _ in range(nl):
+        h = C.c_void_p()
+        L.check(lib.emagls_decode_stream_create_bank(Cc, S, p(wL), p(wR), 0, ln, 0, sh, re, B, C.byref(h)))
+        hs.append(h)
+    na_g, na_l = (nl * B, B) if rotated else (0, 0)
+    ag = [p(a) if rotated else None for a in ang]
+    al = [[C.c_void_p(a.data_ptr() + 8 * B * l) if rotated else None for a in ang] for l in range(nl)]
+    outs = [C.c_void_p(out_l.data_ptr() + 8 * 2 * B * l) for l in range(nl)]
+    count = [0, 0]
+
+    def side_group():
+        count[0] += 1
+        idx = C.c_void_p(d_idx.data_ptr() + 4 * nl * (count[0] % S)) if S > 1 else None   # row count % S: [L] indices, a new set each
+        L.check(lib.emagls_decode_group_push_device(hg, p(d_blk), B, idx, nl if S > 1 else 0, ag[0], na_g, ag[1], na_g, ag[2], na_g,
+                                                    p(out_g), sp))
+
+    def side_loop():
+        count[1] += 1
+        for l in range(nl):
+            idx = C.c_void_p(d_idx.data_ptr() + 4 * (nl * (count[1] % S) + l)) if S > 1 else None
+            L.check(lib.emagls_decode_stream_push_sets_device(hs[l], p(d_blk), B, idx, 1 if S > 1 else 0, al[l][0], na_l, al[l][1], na_l,
+                                                              al[l][2], na_l, outs[l], sp))
+
+    sides = [("group", side_group), ("loop", side_loop)]
+    times = {k: [] for k, _ in sides}
+    with torch.cuda.stream(st):
+        for _, f in sides:
+            for _ in range(warm):
+                f()
+        st.synchronize()
+        same = bool(torch.equal(out_g, out_l))              # equal histories so far: the two sides hold the same bits
+        for _ in range(max(1, blocks // run)):
+            for k, f in sides:                               # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(run):
+                    f()
+                e1.record(st)
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / run)   # us per block of the whole group
+    lib.emagls_decode_group_destroy(hg)
+    for h in hs:
+        lib.emagls_decode_stream_destroy(h)
+    res = {"shape": [Cc, ln, B], "listeners": nl, "sets": S, "rotation": "ypr" if rotated else "none", "block_us": round(B / FS * 1e6, 1),
+           "bits_equal": same, "bytes": group_bytes(Cc, ln, B, nl, S, rotated)}
+    for k, v in times.items():
+        res[k] = {"median_us": round(float(np.median(v)), 2), "min_us": round(float(np.min(v)), 2), "max_us": round(float(np.max(v)), 2),
+                  "spread_us": round(_spread(v), 2)}
+    gm, lm = res["group"]["median_us"], res["loop"]["median_us"]
+    res["loop_over_group"] = round(lm / gm, 2)
+    res["listeners_in_real_time"] = int(res["block_us"] / (gm / nl))
+    res["compulsory_gbps"] = round(res["bytes"]["compulsory"] / gm / 1e3, 1)
+    res["requested_gbps"] = round(res["bytes"]["requested"] / gm / 1e3, 1)
+    if nl >= 8:
+        res["gate"] = lm - gm > res["loop"]["spread_us"] + res["group"]["spread_us"]
+    elif nl == 1:
+        res["gate"] = gm <= lm + res["loop"]["spread_us"]
+    else:
+        res["gate"] = True
+    return res
+
+
+def group_markdown(rows, device):
+    lines = ["`python tools/decode_stream_timing.py --group` on %s: time per block of the WHOLE group in us, median of the run averages" % device,
+             "(spread = p90 - p10).  group: one push of `emagls_decode_group_push_device`; loop: L decode streams pushed one after the other",
+             "on the same HIP stream.  real time: the listeners one device serves at 48 kHz, block duration / (group / L).  GB/s: the",
+             "traffic of a push from the shapes over the group's time; compulsory counts the filter spectra once, requested once per",
+             "listener (what the workgroups load, most of it from the caches), against an HBM peak of %.0f GB/s." % HBM_PEAK_GBPS, "",
+             "| (C, len, B) | S | rotation | L | group | spread | loop | spread | loop / group | gate | real time | compulsory GB/s | requested GB/s | bits |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append("| %s | %d | %s | %d | %.1f | %.2f | %.1f | %.2f | %.2f | %s | %d | %.0f (%.1f %%) | %.0f (%.1f %%) | %s |" % (
+            tuple(r["shape"]), r["sets"], r["rotation"], r["listeners"], r["group"]["median_us"], r["group"]["spread_us"], r["loop"]["median_us"],
+            r["loop"]["spread_us"], r["loop_over_group"], "ok" if r["gate"] else "MISS", r["listeners_in_real_time"], r["compulsory_gbps"],
+            100 * r["compulsory_gbps"] / HBM_PEAK_GBPS, r["requested_gbps"], 100 * r["requested_gbps"] / HBM_PEAK_GBPS,
+            "equal" if r["bits_equal"] else "DIFFER"))
+    return "\n".join(lines) + "\n"
+
+
 def bank_markdown(rows, device):
     lines = ["`python tools/decode_stream_timing.py --bank` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
              "plain: the plain stream; const: a bank stream with a constant index from device memory; keep: a bank stream pushed without",
@@ -258,8 +381,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default=None, help="markdown table")
     ap.add_argument("--bank", action="store_true", help="time the bank of filter sets (see above)")
-    ap.add_argument("--sets", type=int, default=3, help="--bank: filter sets of the bank stream (at least 3)")
+    ap.add_argument("--sets", type=int, default=None, help="--bank: filter sets of the bank stream (at least 3; default 3); --group: default 1")
+    ap.add_argument("--group", action="store_true", help="time the listener group against a loop over streams (see above)")
+    ap.add_argument("--listeners", type=int, nargs="*", default=[1, 8, 64, 256], help="--group: numbers of listeners")
     a = ap.parse_args()
+    if a.sets is None:
+        a.sets = 1 if a.group else 3
     if a.blocks < a.run or a.run < 1 or a.warm < 0:
         raise SystemExit("--blocks must be at least --run, --run at least 1")
     shapes = parse_shapes(a.shapes)
@@ -274,6 +401,22 @@ def main():
     from emagls_amd import _lib as L
     lib = L.load()
     rows, ok = [], True
+    if a.group:
+        if a.sets < 1 or any(nl < 1 or nl > 4096 for nl in a.listeners):
+            raise SystemExit("--sets must be at least 1, --listeners from 1 to 4096")
+        for s in shapes:
+            for r in rots:
+                for nl in a.listeners:
+                    res = run_group_shape(lib, L, torch, *s, nl, a.sets, r, a.blocks, a.warm, a.run)
+                    ok = ok and res["gate"] and res["bits_equal"]
+                    rows.append(res)
+                    print(json.dumps(res), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(group_markdown(rows, torch.cuda.get_device_name(0)))
+        print("gates:", "pass" if ok else "MISS")
+        return 0 if ok else 1
     if a.bank:
         if a.sets < 3:
             raise SystemExit("--sets must be at least 3")
