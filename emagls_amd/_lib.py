@@ -42,6 +42,7 @@ class Job(C.Structure):
 
 
 JOBS_SHARE_GEOMETRY = 1
+JOBS_INDEPENDENT = 2
 
 # name -> (restype, argtypes); every symbol include/emagls.h declares
 SYMBOLS = {
@@ -204,6 +205,9 @@ SYMBOLS = {
     "emagls_jobs_sweep_times": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "emagls_batch_set_geometry_sharing": (C.c_int, [C.c_void_p, C.c_int]),
     "emagls_batch_shares_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "emagls_batch_geometry_runs": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "emagls_jobs_geometry_runs": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "emagls_jobs_would_share_geometry": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "emagls_batch_set_side_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "emagls_batch_set_streams": (C.c_int, [C.c_void_p, C.c_int]),
     "emagls_batch_set_stage_order": (C.c_int, [C.c_void_p, C.c_int]),

@@ -282,7 +282,8 @@ struct emagls_plan {
     bool geo_skip = false;                   // (this execute: the geometry stages are skipped)
     uint64_t geo_done_version = ~0ull;       // atf_side_version of the last run whose flags came back clean
     uint64_t geo_run_version = ~0ull;        // ... of the last full run (promoted by plan_check_flags)
-    bool defer_hh = false;        // plan_execute: what the captured stages before the sweep were captured with
+    uint64_t solo_runs = 0;                  // executes of the plan on its own (they rewrite the geometry state a sharing batch keeps: batch_geo_version)
+    bool defer_hh = false;       // plan_execute: what the captured stages before the sweep were captured with
     bool alone = false;           // the plan of a one-shot call (the device to itself, like a plan with forked stages)
     hipStream_t hh_stream = nullptr;   // the stream of the stages that run next to the sweep
     hipStream_t sync_stream = nullptr;  // stream whose completion means this plan's results are ready
@@ -392,6 +393,15 @@ struct emagls_batch {
     bool magls = false;     // MagLS / MagLS-2D plans (HRIR sets on one or several grids): batch_execute_magls
     bool geo_want = false, geo_share = false, geo_inputs_same = false;
     uint64_t geo_checked_version = ~0ull;
+    // a sharing batch of array designs keeps its geometry stages between executes (batch_execute_geo): the "cold" form runs plan 0's
+    // whole pipeline and hands its factors to the subjects, the "warm" form only what an HRIR set enters, for every plan
+    uint64_t geo_kept_version = ~0ull;         // batch_geo_version of the last cold run whose status flags came back clean
+    uint64_t geo_ran_version = ~0ull;          // ... of the last cold run enqueued (promoted by emagls_batch_get_filters)
+    bool geo_cold_pending = false;             // that run's flags have not been read yet
+    hipGraph_t warm_graph = nullptr;           // the warm form's stages before the sweep (the stages after it are the same in both forms)
+    hipGraphExec_t warm_exec = nullptr;
+    int last_form = 0;                         // the last execute: 0 independent designs (or another kind of batch), 1 cold, 2 warm
+    long long geo_cold_runs = 0, geo_warm_runs = 0;
     int* cmp_flag = nullptr;
     int nstreams = 1;                          // lane mode: streams the stages before the sweep fork onto (emagls_batch_set_streams)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
@@ -443,6 +453,8 @@ struct emagls_batch {
         if (post_graph) hipGraphDestroy(post_graph);
         if (graph2_exec) hipGraphExecDestroy(graph2_exec);
         if (graph2) hipGraphDestroy(graph2);
+        if (warm_exec) hipGraphExecDestroy(warm_exec);
+        if (warm_graph) hipGraphDestroy(warm_graph);
         for (int i = 0; i < 2; ++i) { if (graphx_exec[i]) hipGraphExecDestroy(graphx_exec[i]); if (graphx[i]) hipGraphDestroy(graphx[i]); }
         for (int i = 0; i < 4; ++i) {
             if (hh_stream[i]) { hipStreamSynchronize(hh_stream[i]); emagls::pool_stream_give(hh_stream[i]); }
@@ -2089,6 +2101,7 @@ void plan_execute(emagls_plan& p) {
             throw Error(EMAGLS_ERR_ARG, "microphone grid must be set before execute");
     }
     if (d.kind == EMAGLS_KIND_FROM_ATF && !p.have_atfs) throw Error(EMAGLS_ERR_ARG, "ATFs must be set before execute");
+    ++p.solo_runs;
     if (p.nstreams >= 2) p.need_sides(p.nstreams);   // (before any capture begins)
     const bool persist = d.kind != EMAGLS_KIND_LS && p.sweep_persist;
     if (p.prof_level == 0 && p.use_graph && persist) {
@@ -2455,6 +2468,27 @@ void batch_execute_atf(emagls_batch& b) {
 // least-squares rows (:94) and the sweep's magnitudes (:99-102).  Plan 0 runs the whole pipeline; the other plans run their
 // HRIR prologue, their least-squares rows on plan 0's factors, and sweep on plan 0's G_k / M_k (batch_sweep_stage).
 // ---------------------------------------------------------------------------------------------
+// A sharing batch KEEPS its geometry state between executes (the <= 32-channel counterpart of a wide plan's geo_keep): after one clean
+// "cold" run -- plan 0's whole pipeline, its factors handed to the subjects -- the "warm" form enqueues only what an HRIR set enters,
+// for every plan of the batch, plan 0 included (batch_geo_stage).  What the kept state was computed from: every plan's grids
+// (atf_side_version) and the plans' own executes in between (plan_execute rewrites a plan's copies of the factors).
+// EMAGLS_GEO_KEEP=0: every sharing execute is a cold one.
+uint64_t batch_geo_version(const emagls_batch& b) {
+    uint64_t ver = 0;
+    for (const emagls_plan* p : b.plans) ver = (ver * 1000003ull + p->atf_side_version) * 1000003ull + p->solo_runs;
+    return ver;
+}
+void batch_geo_forget(emagls_batch& b) {
+    b.geo_kept_version = ~0ull;
+    b.geo_cold_pending = false;
+}
+// the form the next sharing execute takes while nothing else changes (also asked by the job scheduler: slot_will_capture)
+bool batch_geo_next_is_warm(const emagls_batch& b) {
+    static const bool keep = [] { const char* e = getenv("EMAGLS_GEO_KEEP"); return !(e && e[0] == '0'); }();
+    if (!keep || !b.geo_share || b.geo_kept_version == ~0ull || b.geo_kept_version != batch_geo_version(b)) return false;
+    for (const emagls_plan* p : b.plans) if (p->prof_level > 0) return false;   // (a profiled plan shows the stages of a whole design)
+    return true;
+}
 void batch_geo_decide_sharing(emagls_batch& b) {
     bool share = false;
     if (b.geo_want && b.plans.size() > 1) {
@@ -2491,6 +2525,7 @@ void batch_geo_decide_sharing(emagls_batch& b) {
     if (share != b.geo_share) {   // (the two modes enqueue different stages: nothing captured for the other one may be replayed)
         for (auto* p : b.plans) drop_plan_graphs(*p);
         drop_batch_graphs(b);
+        batch_geo_forget(b);
         b.geo_share = share;
     }
 }
@@ -2553,23 +2588,58 @@ void emagls_subject_rows(emagls_plan& p, emagls_plan& g) {
 // One stream for the whole batch (the subjects' stages are short and the sweep chain is what bounds a batch of HRIR sets), so
 // that the stages before and after the sweep are two single-stream graphs: issued eagerly, the ~250 launches of a 16-set batch
 // cost 11 ms of host time (measured: 1380 sets/s whatever the number of batches in flight).
+// part 0: the cold form's stages before the sweep, 1: the warm form's, 2: the stages after the sweep (the same in both forms)
+//
+// What a warm run relies on (DESIGN.md section 6 has the audit): it reads plan 0's route, sv, cond_ok, Tn, bn, bsc, Pm, Mw / Mt, smap, G
+// and Yri, and every plan's own copies of Yc, R / Rc, Vws, Nw, tauw, cond_ok, G and Mw of the least-squares bins -- all written by plan
+// 0's geometry stages and broadcast_lanes only.  The HRIR-dependent stages write flag, W, tw, dirsum, grpd, Hc, HcT, Habs, Hyp, Hq,
+// Rinv / Rinvc (from R: the same values every time), Z (from Vws, Nw, tauw: the same values every time; read by nobody afterwards),
+// Usw and Winit; the sweep writes ll, Wpart, W and Usw; the stages after it W, wL and wR.  Every plan buffer is a range of its own
+// in the arena (batch_try_lanes), so none of these aliases a kept one.  A warm run does NOT pass through plan_pre_stage, which would
+// zero plan 0's route.
 void batch_geo_stage(emagls_batch& b, int part) {
     emagls_plan& p0 = *b.plans[0];
     std::vector<hipStream_t> keep;
     for (auto* p : b.plans) { keep.push_back(p->stream); p->stream = b.stream; }
     auto restore = [&] { for (size_t j = 0; j < b.plans.size(); ++j) b.plans[j]->stream = keep[j]; };
-    const int nsub = (int)b.plans.size() - 1;
+    const int n = (int)b.plans.size();
+    // what an HRIR set enters, for the plans first .. n-1 on plan 0's geometry: the subjects of a cold run (plan 0 has just run its
+    // whole pipeline), every plan of a warm run.  Plan 0 takes the same kernels on the same operands here as inside its own pipeline
+    // (emagls_pre_sweep: blk_prologue, blk_rows, blk_back, blk_tail; synth_winit_kernel is block 0 of synth_mt_kernel), so its
+    // filters have the same bits in both forms.
+    auto hrir_side = [&](int first) {
+        if (first >= n) return;
+        if (b.lanes) {
+            emagls_plan& pf = *b.plans[first];
+            BatchScope sc(n - first, b.stride);
+            emagls_subject_prologue(pf, p0);
+            pf.geo_from = &p0;   // (synthesising designs: plan 0's coefficients, Pm and M_k for every lane)
+            try { emagls_subject_rows(pf, pf); } catch (...) { pf.geo_from = nullptr; throw; }
+            pf.geo_from = nullptr;
+            if (p0.synth)   // every set's own start value of the microphone-domain chain, on plan 0's Pm
+                launch_synth_winit(pf.get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, pf.get("Winit"), b.stream, true);
+        } else {
+            for (int j = first; j < n; ++j) {
+                emagls_subject_prologue(*b.plans[j], p0);
+                emagls_subject_rows(*b.plans[j], p0);
+                if (p0.synth)
+                    launch_synth_winit(b.plans[j]->get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, b.plans[j]->get("Winit"),
+                                       b.stream, true);
+            }
+        }
+    };
     try {
-        if (part == 0) {
+        if (part == 1) {
+            hrir_side(0);
+        } else if (part == 0) {
             plan_pre_stage(p0);
-            if (b.lanes && nsub > 0) {
+            if (b.lanes && n > 1) {
                 // lane batch: the subjects' stages are ONE launch per kernel for all of them (plans 1.. at the arena stride).  The
                 // few geometry operands those kernels read (conj(Y), R, the Householder-route factors, M_k and G_k of the
                 // least-squares bins: ~40 MB) are copied into the subjects' own slots first, so that every pointer of a launch
                 // moves by the same stride; the large ones (G_k, M_k of the swept bins) are only read by the sweep, through
-                // plan 0's pointers.
+                // plan 0's pointers.  The copies stay: a warm run reads them again.
                 emagls_plan& g = p0;
-                emagls_plan& p1 = *b.plans[1];
                 const bool cb = g.cplx_basis;
                 const int gf = g.gram_from, hh_end = g.hh_end, ldSh = g.ldS_h;
                 const int ls_end = std::min(g.kcut0, g.P);
@@ -2577,7 +2647,7 @@ void batch_geo_stage(emagls_batch& b, int part) {
                 auto bc = [&](const char* name, size_t off, size_t bytes) {
                     if (!g.has(name) || bytes == 0) return;
                     bytes = std::min(bytes, g.bufs[name].bytes - off);
-                    launch_broadcast_lanes(g.get<char>(name) + off, bytes, b.stride, nsub, b.stream);
+                    launch_broadcast_lanes(g.get<char>(name) + off, bytes, b.stride, n - 1, b.stream);
                 };
                 if (hh_end > 1) {
                     bc("Yc", 0, g.bufs["Yc"].bytes);
@@ -2591,24 +2661,10 @@ void batch_geo_stage(emagls_batch& b, int part) {
                     bc("G", (size_t)(gf - g.g0) * g_stride_b, (size_t)(ls_end - gf) * g_stride_b);
                     bc("Mw", 0, sizeof(cplx) * (size_t)ls_end * g.C * g.C);
                 }
-                BatchScope sc(nsub, b.stride);
-                emagls_subject_prologue(p1, p0);
-                p1.geo_from = &p0;   // (synthesising designs: plan 0's coefficients, Pm and M_k for every lane)
-                try { emagls_subject_rows(p1, p1); } catch (...) { p1.geo_from = nullptr; throw; }
-                p1.geo_from = nullptr;
-                if (p0.synth)   // every set's own start value of the microphone-domain chain, on plan 0's Pm
-                    launch_synth_winit(p1.get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, p1.get("Winit"), b.stream, true);
-            } else {
-                for (size_t j = 1; j < b.plans.size(); ++j) {
-                    emagls_subject_prologue(*b.plans[j], p0);
-                    emagls_subject_rows(*b.plans[j], p0);
-                    if (p0.synth)
-                        launch_synth_winit(b.plans[j]->get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, b.plans[j]->get("Winit"),
-                                           b.stream, true);
-                }
             }
+            hrir_side(1);
         } else if (b.lanes) {
-            BatchScope sc((int)b.plans.size(), b.stride);
+            BatchScope sc(n, b.stride);
             p0.geo_from = &p0;   // (the filters' rows of every lane from plan 0's Pm and M_k)
             try { emagls_post_sweep(p0); } catch (...) { p0.geo_from = nullptr; throw; }
             p0.geo_from = nullptr;
@@ -2628,12 +2684,20 @@ void batch_geo_stage(emagls_batch& b, int part) {
 void batch_execute_geo(emagls_batch& b) {
     emagls_plan& p0 = *b.plans[0];
     const bool replay = b.use_graph && b.eager_runs >= 1;
-    if (replay && !b.graph_exec) {
-        capture_into(b.stream, &b.graph, &b.graph_exec, [&] { batch_geo_stage(b, 0); });
-        capture_into(b.stream, &b.post_graph, &b.post_exec, [&] { batch_geo_stage(b, 2); });
+    const bool warm = batch_geo_next_is_warm(b);
+    // the cold and the warm form each have a captured graph of their stages before the sweep, captured the first time the form runs
+    // with replays on -- a batch's second execute is normally its first warm one, so the warm form needs no eager run of its own
+    hipGraph_t* gr = warm ? &b.warm_graph : &b.graph;
+    hipGraphExec_t* ge = warm ? &b.warm_exec : &b.graph_exec;
+    if (replay && !*ge) capture_into(b.stream, gr, ge, [&] { batch_geo_stage(b, warm ? 1 : 0); });
+    if (replay && !b.post_exec) capture_into(b.stream, &b.post_graph, &b.post_exec, [&] { batch_geo_stage(b, 2); });
+    if (!warm) {   // (this run rewrites the kept state: it counts again once its flags have come back clean)
+        b.geo_kept_version = ~0ull;
+        b.geo_ran_version = batch_geo_version(b);
+        b.geo_cold_pending = true;
     }
     b.used = 0;
-    if (replay) HIP_CHECK(hipGraphLaunch(b.graph_exec, b.stream)); else batch_geo_stage(b, 0);
+    if (replay) HIP_CHECK(hipGraphLaunch(*ge, b.stream)); else batch_geo_stage(b, warm ? 1 : 0);
     batch_sweep_stage(b);   // (never captured: see SweepChain)
     if (replay) HIP_CHECK(hipGraphLaunch(b.post_exec, b.stream)); else batch_geo_stage(b, 2);
     for (auto* p : b.plans) {
@@ -2641,6 +2705,8 @@ void batch_execute_geo(emagls_batch& b) {
         p->sweep_launches = p0.sweep_persist ? 1 : p0.P - std::max(p0.kcut0, 1);
     }
     if (!replay) ++b.eager_runs;
+    b.last_form = warm ? 2 : 1;
+    ++(warm ? b.geo_warm_runs : b.geo_cold_runs);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2675,6 +2741,7 @@ void batch_magls_decide_sharing(emagls_batch& b) {
     if (share != b.geo_share) {
         for (auto* p : b.plans) drop_plan_graphs(*p);
         drop_batch_graphs(b);
+        batch_geo_forget(b);
         b.geo_share = share;
     }
 }
@@ -2736,7 +2803,7 @@ void batch_execute_magls(emagls_batch& b) {
     bool persist = true;
     for (auto* p : b.plans) persist = persist && p->sweep_persist;
     if (!persist) {   // (an ill-conditioned basis or a sweep that did not become resident: the designs one at a time, launch-per-bin sweeps)
-        if (b.geo_share) { for (auto* p : b.plans) drop_plan_graphs(*p); drop_batch_graphs(b); b.geo_share = false; }
+        if (b.geo_share) { for (auto* p : b.plans) drop_plan_graphs(*p); drop_batch_graphs(b); batch_geo_forget(b); b.geo_share = false; }
         for (auto* p : b.plans) {
             hipStream_t keep = p->stream;
             p->stream = b.stream;
@@ -2763,6 +2830,7 @@ void batch_execute_magls(emagls_batch& b) {
 void batch_execute(emagls_batch& b) {
     for (auto* p : b.plans)
         if (!p) throw Error(EMAGLS_ERR_ARG, "a plan of this batch has been destroyed");
+    b.last_form = 0;
     if (b.atf) { batch_execute_atf(b); return; }
     if (b.magls) { batch_execute_magls(b); return; }
     for (auto* p : b.plans)
@@ -2816,6 +2884,8 @@ void drop_batch_graphs(emagls_batch& b) {
     if (b.post_graph) { HIP_CHECK(hipGraphDestroy(b.post_graph)); b.post_graph = nullptr; }
     if (b.graph2_exec) { HIP_CHECK(hipGraphExecDestroy(b.graph2_exec)); b.graph2_exec = nullptr; }
     if (b.graph2) { HIP_CHECK(hipGraphDestroy(b.graph2)); b.graph2 = nullptr; }
+    if (b.warm_exec) { HIP_CHECK(hipGraphExecDestroy(b.warm_exec)); b.warm_exec = nullptr; }
+    if (b.warm_graph) { HIP_CHECK(hipGraphDestroy(b.warm_graph)); b.warm_graph = nullptr; }
     for (int i = 0; i < 2; ++i) {
         if (b.graphx_exec[i]) { HIP_CHECK(hipGraphExecDestroy(b.graphx_exec[i])); b.graphx_exec[i] = nullptr; }
         if (b.graphx[i]) { HIP_CHECK(hipGraphDestroy(b.graphx[i])); b.graphx[i] = nullptr; }
@@ -3056,6 +3126,7 @@ void batch_redo(emagls_batch& b, const std::vector<int>& flags) {
         drop_plan_graphs(*q);
     }
     drop_batch_graphs(b);
+    batch_geo_forget(b);   // (routes, sweep form or lane layout change: a sharing batch runs its geometry stages again)
     {
         const std::vector<int64_t> before = [&] { std::vector<int64_t> v; for (auto* q : b.plans) v.push_back(q->total_bytes); return v; }();
         batch_unify_synth(b);
@@ -3761,6 +3832,15 @@ int emagls_batch_get_filters(emagls_batch* b, void* const* wL, void* const* wR) 
         for (auto* q : b->plans)   // (a MagLS re-run on the launch-per-bin sweeps is done: the next execute starts on the persistent form again)
             if (q->persist_suspended) { q->persist_suspended = false; q->sweep_persist = true; }
         for (size_t j = 0; j < n; ++j) throw_fatal_flags(&flags[NFLAG * j]);
+        // clean: the geometry state of a sharing batch's cold run serves its next executes (batch_execute_geo)
+        if (b->geo_cold_pending) { b->geo_kept_version = b->geo_ran_version; b->geo_cold_pending = false; }
+    });
+}
+int emagls_batch_geometry_runs(emagls_batch* b, long long* cold, long long* warm) {
+    return guarded([&] {
+        if (!b || !cold || !warm) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *cold = b->geo_cold_runs;
+        *warm = b->geo_warm_runs;
     });
 }
 int emagls_batch_lane_mode(emagls_batch* b, int* lanes) {
@@ -3784,6 +3864,7 @@ int emagls_batch_set_geometry_sharing(emagls_batch* b, int enable) {
         HIP_CHECK(hipStreamSynchronize(b->stream));
         b->geo_want = enable != 0;
         b->geo_checked_version = ~0ull;
+        batch_geo_forget(*b);   // (the next sharing execute runs the geometry stages)
     });
 }
 int emagls_batch_shares_geometry(emagls_batch* b, int* shared) {
@@ -4210,11 +4291,38 @@ void job_shape(const emagls_design_desc& d, std::string& out) {
 bool slot_will_capture(const JobSlot& s) {
     if (s.batch) {
         const emagls_batch& b = *s.batch;
-        return b.use_graph && b.eager_runs >= 1 && !b.graph_exec && !(b.plans.size() && b.plans[0]->pre_exec);
+        if (!b.use_graph || b.eager_runs < 1) return false;
+        // a sharing batch of array designs captures each of its two forms the first time that form runs (batch_execute_geo)
+        if (b.geo_share && !b.atf && !b.magls) return !b.post_exec || !(batch_geo_next_is_warm(b) ? b.warm_exec : b.graph_exec);
+        return !b.graph_exec && !(b.plans.size() && b.plans[0]->pre_exec);
     }
     for (const emagls_plan* p : s.plans)
         if (p->use_graph && p->prof_level == 0 && p->eager_runs >= 1 && !p->pre_exec && !p->graph_exec) return true;
     return false;
+}
+std::atomic<long long> g_jobs_geo_runs[3];   // chunk executes since emagls_cache_clear: independent designs, cold, warm (emagls_jobs_geometry_runs)
+// The scheduler's own rule for sharing geometry (needs no device: descriptors and host grids alone): every job of the chunk has the same
+// descriptor, byte for byte, of a kind batch_geo_decide_sharing accepts -- eMagLS / eMagLS2 / EMAinCH, at most 32 channels, no
+// covariance constraint, built-in basis -- and the same grids.  The batch's comparison on the device stays the final word.
+bool jobs_chunk_shares_geometry(const emagls_job* jobs, int n) {
+    if (!jobs || n < 2) return false;
+    const emagls_design_desc& d0 = jobs[0].desc;
+    if (d0.kind != EMAGLS_KIND_EMAGLS && d0.kind != EMAGLS_KIND_EMAGLS2 && d0.kind != EMAGLS_KIND_EMA_CH) return false;
+    if (d0.custom_basis || d0.diffuseness || d0.ndirs <= 0 || d0.nmics <= 0) return false;
+    const int64_t ch = d0.kind == EMAGLS_KIND_EMAGLS2 ? d0.nmics : d0.kind == EMAGLS_KIND_EMA_CH ? 2 * (int64_t)d0.order + 1 : (int64_t)(d0.order + 1) * (d0.order + 1);
+    if (ch > 32) return false;   // (the 33..64-channel path runs plan by plan: geo_keep)
+    auto same = [](const double* a, const double* b, int64_t m) {
+        if (a == b) return true;   // (also: both absent)
+        return a && b && memcmp(a, b, sizeof(double) * (size_t)m) == 0;
+    };
+    if (!jobs[0].hrir_azi || !jobs[0].mic_azi) return false;
+    for (int j = 1; j < n; ++j) {
+        const emagls_job& x = jobs[j];
+        if (memcmp(&x.desc, &d0, sizeof d0) != 0) return false;
+        if (!same(x.hrir_azi, jobs[0].hrir_azi, d0.ndirs) || !same(x.hrir_zen, jobs[0].hrir_zen, d0.ndirs) ||
+            !same(x.mic_azi, jobs[0].mic_azi, d0.nmics) || !same(x.mic_zen, jobs[0].mic_zen, d0.nmics)) return false;
+    }
+    return true;
 }
 void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool solo, uint64_t call) {
     DeviceGuard dg(device);
@@ -4253,7 +4361,7 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
     // stages around the sweep, and a capture next to another thread's uploads or launches is invalidated (hipErrorStreamCaptureInvalidated)
     // (decided from the objects' own state, not from the slot's run count: a batch whose graphs were dropped by a recovery --
     // drop_batch_graphs after a flagged bin or a lanes rebuild -- captures again on a later run)
-    const bool capturing = slot && slot_will_capture(*slot);
+    const bool was_resident = slot != nullptr;
     std::shared_lock<std::shared_timed_mutex> shared(g_jobs_warm_mu, std::defer_lock);
     std::unique_lock<std::shared_timed_mutex> alone(g_jobs_warm_mu, std::defer_lock);
     // (the exclusive lock only around the execute that captures: the uploads before it and the wait for the filters after it run next to
@@ -4357,15 +4465,25 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
     } else {
         for (int j = 0; j < n; ++j) check_rc(emagls_plan_set_hrirs(slot->plans[(size_t)j], jobs[j].hL, jobs[j].hR));
     }
-    if (slot->batch && (flags & EMAGLS_JOBS_SHARE_GEOMETRY)) {
-        // HRIR sets on one geometry: the geometry stages once per chunk (the library compares the grids on the device, and a chunk whose
-        // designs do not agree runs them as independent designs -- emagls_batch_set_geometry_sharing)
+    if (slot->batch) {
+        // HRIR sets on one geometry: the geometry stages once per chunk, and kept by the chunk's batch between runs (batch_execute_geo).
+        // Decided here without being asked (jobs_chunk_shares_geometry: EMAGLS_JOBS_INDEPENDENT / EMAGLS_JOBS_AUTO_SHARE=0 switch that
+        // off); with EMAGLS_JOBS_SHARE_GEOMETRY the batch is asked whatever the rule says (MagLS / LS sets on one grid).  Either way the
+        // library compares the grids on the device, and a chunk whose designs do not agree runs them as independent designs.
+        static const bool auto_env = [] { const char* e = getenv("EMAGLS_JOBS_AUTO_SHARE"); return !(e && e[0] == '0'); }();
         const int kind = jobs[0].desc.kind;
-        if (kind != EMAGLS_KIND_FROM_ATF && kind != EMAGLS_KIND_EMA_SH) check_rc(emagls_batch_set_geometry_sharing(slot->batch, 1));
+        bool want = false;
+        if (flags & EMAGLS_JOBS_SHARE_GEOMETRY) want = kind != EMAGLS_KIND_FROM_ATF && kind != EMAGLS_KIND_EMA_SH;
+        else if (auto_env && !(flags & EMAGLS_JOBS_INDEPENDENT)) want = jobs_chunk_shares_geometry(jobs, n);
+        // (only when it changes: the call makes the batch compare its grids again and run its geometry stages again)
+        if (want != slot->batch->geo_want) check_rc(emagls_batch_set_geometry_sharing(slot->batch, want ? 1 : 0));
     }
     // (designs of the 33..64-channel path run plan by plan: with the flag a plan keeps its geometry stages from its last clean run while
     // its own grids stay the same -- plan_execute)
     if (!slot->batch) for (auto* q : slot->plans) q->geo_keep = (flags & EMAGLS_JOBS_SHARE_GEOMETRY) != 0;
+    // (decided here, from the objects' state AFTER this run's grids and sharing switch are in: a replaced grid takes a sharing batch back
+    // to its cold form, whose graph may not exist yet)
+    const bool capturing = was_resident && slot_will_capture(*slot);
     {
         if (slot->batch) {
             std::vector<void*> wl((size_t)n), wr((size_t)n);
@@ -4374,8 +4492,10 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
             if (capturing) { shared.unlock(); alone.lock(); }
             check_rc(emagls_batch_execute(slot->batch));
             if (capturing) { alone.unlock(); shared.lock(); }
+            ++g_jobs_geo_runs[slot->batch->last_form];
             check_rc(emagls_batch_get_filters(slot->batch, wl.data(), wr.data()));
         } else {
+            ++g_jobs_geo_runs[0];
             if (capturing) { shared.unlock(); alone.lock(); }
             for (int j = 0; j < n; ++j) check_rc(emagls_plan_execute(slot->plans[(size_t)j]));
             if (capturing) { alone.unlock(); shared.lock(); }
@@ -4402,6 +4522,19 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
 void emagls_jobs_cache_clear_internal() {
     std::lock_guard<std::mutex> lk(g_jobs_mu);
     g_jobs_free.clear();
+    for (auto& c : g_jobs_geo_runs) c.store(0);
+}
+int emagls_jobs_geometry_runs(long long* independent, long long* cold, long long* warm) {
+    return guarded([&] {
+        if (!independent || !cold || !warm) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *independent = g_jobs_geo_runs[0].load(); *cold = g_jobs_geo_runs[1].load(); *warm = g_jobs_geo_runs[2].load();
+    });
+}
+int emagls_jobs_would_share_geometry(const emagls_job* jobs, int njobs, int* share) {
+    return guarded([&] {
+        if (!jobs || !share || njobs < 0) throw Error(EMAGLS_ERR_ARG, "invalid argument");
+        *share = jobs_chunk_shares_geometry(jobs, njobs) ? 1 : 0;
+    });
 }
 
 int emagls_jobs_set_profiling(int level) {

@@ -62,20 +62,44 @@ class JobList:
     def __len__(self):
         return len(self._jobs)
 
-    def run(self, batch_size=0, in_flight=0, share_geometry=False, devices=None):
-        """Runs every job added so far; returns when all filters are in place.  `devices`: HIP ordinals of the GPUs of this process to
-        split the list over (emagls_jobs_run_devices: one host thread per device, host arrays in and out, no gather); None: the
-        current device."""
+    def run(self, batch_size=0, in_flight=0, share_geometry=None, devices=None):
+        """Runs every job added so far; returns when all filters are in place.  `share_geometry`: None -- the library decides per chunk
+        (jobs of one descriptor on the same grids share their geometry stages and keep them between runs); True -- every batch is
+        asked for sharing (EMAGLS_JOBS_SHARE_GEOMETRY); False -- independent designs (EMAGLS_JOBS_INDEPENDENT).  `devices`: HIP
+        ordinals of the GPUs of this process to split the list over (emagls_jobs_run_devices: one host thread per device, host arrays
+        in and out, no gather); None: the current device."""
         n = len(self._jobs)
         if n == 0:
             return
         arr = (L.Job * n)(*self._jobs)
-        flags = L.JOBS_SHARE_GEOMETRY if share_geometry else 0
+        flags = 0 if share_geometry is None else (L.JOBS_SHARE_GEOMETRY if share_geometry else L.JOBS_INDEPENDENT)
         if devices is None:
             L.check(L.load().emagls_jobs_run(arr, n, int(batch_size), int(in_flight), flags))
         else:
             dev = (C.c_int * len(devices))(*[int(d) for d in devices])
             L.check(L.load().emagls_jobs_run_devices(arr, n, dev, len(devices), int(batch_size), int(in_flight), flags))
+
+    def replace(self, index, **inputs):
+        """New input arrays for job `index` (hL, hR, hrir_azi, hrir_zen, mic_azi, mic_zen): the same descriptor, so a resident chunk serves it."""
+        for name, a in inputs.items():
+            if name not in ("hL", "hR", "hrir_azi", "hrir_zen", "mic_azi", "mic_zen"):
+                raise ValueError(name)
+            setattr(self._jobs[index], name, self._ptr(a))
+
+    @staticmethod
+    def geometry_runs():
+        """(independent, cold, warm): chunk executes of every job list since the last cache clear (emagls_jobs_geometry_runs)."""
+        v = [C.c_longlong(0) for _ in range(3)]
+        L.check(L.load().emagls_jobs_geometry_runs(*[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def would_share_geometry(self, first=0, count=None):
+        """The scheduler's sharing rule for the jobs first .. first + count - 1 as one chunk (needs no GPU)."""
+        jobs = self._jobs[first:] if count is None else self._jobs[first:first + count]
+        arr = (L.Job * max(len(jobs), 1))(*jobs)
+        v = C.c_int(0)
+        L.check(L.load().emagls_jobs_would_share_geometry(arr, len(jobs), C.byref(v)))
+        return bool(v.value)
 
     def shard(self, world, max_batch=16):
         """(rank of every job, its position in the rank's share, the simulation order its lane batch is laid out for) -- the split of

@@ -168,6 +168,12 @@ class Batch:
         L.check(self._lib.emagls_batch_shares_geometry(self._h, C.byref(v)))
         return bool(v.value)
 
+    def geometry_runs(self):
+        """(cold, warm): sharing executes that ran the geometry stages / that ran on the kept ones (emagls_batch_geometry_runs)."""
+        cold, warm = C.c_longlong(0), C.c_longlong(0)
+        L.check(self._lib.emagls_batch_geometry_runs(self._h, C.byref(cold), C.byref(warm)))
+        return cold.value, warm.value
+
     def set_streams(self, n):
         """Lane mode: fork the stages before the sweep onto n (1..4) streams (see emagls_batch_set_streams)."""
         L.check(self._lib.emagls_batch_set_streams(self._h, int(n)))

@@ -587,6 +587,11 @@ int emagls_set_batch_max(int max_designs, int* previous);
  * emagls_batch_shares_geometry reports what the last execute did. */
 int emagls_batch_set_geometry_sharing(emagls_batch* batch, int enable);
 int emagls_batch_shares_geometry(emagls_batch* batch, int* shared);
+/* A sharing batch keeps its geometry stages between executes: the first sharing execute (and the first after a grid was replaced, a
+ * recovery, emagls_batch_set_geometry_sharing or an execute of one of its plans on its own) is "cold", the others "warm" -- only what
+ * the HRIRs enter, for every plan.  A run becomes the kept one when emagls_batch_get_filters has read its status flags clean.
+ * Executes of each form so far (EMAGLS_GEO_KEEP=0 in the environment: every sharing execute is cold). */
+int emagls_batch_geometry_runs(emagls_batch* batch, long long* cold, long long* warm);
 /* ---- job lists ---------------------------------------------------------------------------------------------------
  * Independent designs are the unit of parallelism of the reference's users: the loop over array radii, HRIR sets or subjects
  * around one of its functions (testEMagLs.m:75-95, testEMagLsFromAtfs.m:72-73).  One job = one design: its descriptor, its inputs
@@ -612,11 +617,20 @@ typedef struct emagls_job {
  * upload and collection at any time, each driven by a thread of the library, so that uploads, launches and the collection of
  * results overlap with the GPU's work on the other chunks.  Plans and batches of chunks whose descriptors repeat stay resident
  * between calls (emagls_cache_clear releases them).  Same filters as the single calls.
- * flags: EMAGLS_JOBS_SHARE_GEOMETRY -- the designs of a chunk that agree in everything but their HRIRs (checked on the device) compute
- * the geometry stages once (emagls_batch_set_geometry_sharing; the filters are bit-identical to the independent designs').  eMagLS /
- * eMagLS2 designs with 33..64 channels run plan by plan: with the flag they are cut one per chunk and a plan keeps G_k, the per-bin
- * factors and Y_reg_inv_k from its last clean run while its own grids stay the same (a 64-capsule array: 31 -> 8 ms per set). */
+ * HRIR sets on one geometry: a chunk whose jobs all have the same descriptor (byte for byte; eMagLS / eMagLS2 / EMAinCH up to 32
+ * channels, built-in basis, no covariance constraint) and the same grids (compared on the host, then by the batch on the device) shares
+ * its geometry stages WITHOUT being asked: they run once per chunk (emagls_batch_set_geometry_sharing), and a resident chunk keeps
+ * them between calls -- after one clean run it enqueues only what an HRIR set enters until a grid is replaced, a run needs a recovery
+ * or emagls_cache_clear is called.  A chunk whose jobs do not all agree runs as independent designs.  The shared filters equal the
+ * independent designs' to 1e-9 relative (a lane batch warm-starts the Jacobi runs of its per-bin factors by the launch's size;
+ * measured at the benchmark's shape: 1.3e-13), and every run of a chunk on the same inputs returns the same bits.
+ * flags: EMAGLS_JOBS_INDEPENDENT -- no sharing unless asked: every design computes its own geometry stages.  (EMAGLS_JOBS_AUTO_SHARE=0
+ * in the environment does the same.)  EMAGLS_JOBS_SHARE_GEOMETRY -- asks every batch for sharing, also the kinds the scheduler's own
+ * rule leaves alone (MagLS / LS sets on one grid); for the designs above it is redundant.  eMagLS / eMagLS2 designs with 33..64
+ * channels run plan by plan: with this flag they are cut one per chunk and a plan keeps G_k, the per-bin factors and Y_reg_inv_k
+ * from its last clean run while its own grids stay the same (a 64-capsule array: 31 -> 8 ms per set). */
 #define EMAGLS_JOBS_SHARE_GEOMETRY 1
+#define EMAGLS_JOBS_INDEPENDENT 2
 int emagls_jobs_run(const emagls_job* jobs, int64_t njobs, int batch_size, int in_flight, int flags);
 /* ---- job lists over several GPUs ------------------------------------------------------------------------------------------
  * Independent jobs shard without any collective on the data path.  emagls_jobs_shard is the split every runner of this
@@ -645,6 +659,12 @@ int emagls_design_out_shape(const emagls_design_desc* desc, int64_t* rows, int64
  * the duration of its LAST sweep launch (ms) and the designs it covered (count: chunks available, capacity: room in the arrays). */
 int emagls_jobs_set_profiling(int level);
 int emagls_jobs_sweep_times(double* ms, int* designs, int capacity, int* count);
+/* Which form the chunks of the job lists ran in, counted per chunk execute since the last emagls_cache_clear: as independent designs,
+ * sharing with the geometry stages run ("cold"), sharing on kept geometry ("warm"). */
+int emagls_jobs_geometry_runs(long long* independent, long long* cold, long long* warm);
+/* The scheduler's rule for sharing a chunk's geometry, on descriptors and host grids alone (needs no GPU): *share = 1 when the
+ * `njobs` jobs would run as one sharing chunk. */
+int emagls_jobs_would_share_geometry(const emagls_job* jobs, int njobs, int* share);
 
 /* HRIR sets on ONE grid (and, for the array kinds, ONE array) in one call -- the loop
  *     for i = 1:nsets, [wL(:,:,i), wR(:,:,i)] = getEMagLsFilters(hL(:,:,i), hR(:,:,i), grid..., array..., order, fs, len, shDefinition); end
