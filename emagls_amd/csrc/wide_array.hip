@@ -677,6 +677,183 @@ __global__ void __launch_bounds__(512) wa_qr_tall_kernel(cplx* __restrict__ B, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Taller still: 3072 < rows <= 4096 (FromAtf's dense route at 9..32 microphones on HRIR grids of that size).  At 64 rows per lane a
+// column of complex FP64 is 256 registers -- the whole budget of a wave in a 512-thread workgroup -- so TWO waves share a column:
+// wave h of a pair holds the rows lane + 64 (2 i + h), NRH = 32 per lane (128 registers), forms its half of v^H a, and the halves
+// meet in LDS (summed in one order by both waves, so both apply the same w).  Otherwise the tall forms: the reflector of a step in
+// LDS, zero outside its rows; a column loaded once per step with all its loads in flight.
+//   wa_back_pair_kernel  a pair keeps one column through all reflectors; a workgroup = 4 columns of a bin
+//   wa_qr_pair_kernel    the four pairs take the trailing columns of a step in turn (every wave runs every turn: the barrier
+//                        between the halves is the workgroup's)
+// ---------------------------------------------------------------------------------------------
+constexpr int WA_PAIR = 32;     // rows per lane and wave: up to 4096 rows per pair
+template <int NRH>
+__global__ void __launch_bounds__(512) wa_back_pair_kernel(const cplx* __restrict__ Vw, const double* __restrict__ tauw, const cplx* __restrict__ Nw, int S,
+                                                           int C, int ldS, cplx* __restrict__ Z) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    cplx* vs = reinterpret_cast<cplx*>(dyn);              // [128 NRH]
+    __shared__ double tau_s[WA_CMAX];
+    __shared__ cplx part[2][4][2];                        // [step parity][pair][half]
+    const cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS;
+    const cplx* N = Nw + (int64_t)blockIdx.x * C * C;
+    cplx* Zk = Z + (int64_t)blockIdx.x * C * ldS;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, pair = wave >> 1, h = wave & 1;   // (wave: known uniform)
+    const int c = 4 * blockIdx.y + pair;
+    const bool active = c < C;
+    if (tid < C) tau_s[tid] = tauw[(int64_t)blockIdx.x * C + tid];
+    cplx x[NRH];
+#pragma unroll
+    for (int i = 0; i < NRH; ++i) {
+        const int s = lane + 64 * (2 * i + h);
+        x[i] = (active && s < C && s < S) ? conj(N[s * C + c]) : mk(0.0, 0.0);   // X[s][c] = conj(N[s][c])
+    }
+    constexpr int NST = 128 * NRH / 512;   // staged values per thread and step
+    cplx r[NST];
+    auto fetch = [&](int j) __attribute__((always_inline)) {
+        const cplx* vj = Vk + (int64_t)j * ldS;
+#pragma unroll
+        for (int q = 0; q < NST; ++q) {
+            const int s = tid + 512 * q;
+            r[q] = (s >= j && s < S) ? vj[s] : mk(0.0, 0.0);
+        }
+    };
+    fetch(C - 1);
+    for (int j = C - 1; j >= 0; --j) {
+        __syncthreads();   // (the readers of step j + 1 are done)
+#pragma unroll
+        for (int q = 0; q < NST; ++q) vs[tid + 512 * q] = r[q];
+        __syncthreads();
+        if (j > 0) fetch(j - 1);
+        cplx w0 = mk(0.0, 0.0), w1 = mk(0.0, 0.0);
+#pragma unroll
+        for (int i0 = 0; i0 < NRH; i0 += 4) {
+#pragma unroll
+            for (int i = i0; i < i0 + 4; i += 2) {
+                cfma_conj(w0, vs[lane + 64 * (2 * i + h)], x[i]);
+                cfma_conj(w1, vs[lane + 64 * (2 * i + 2 + h)], x[i + 1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        cplx w = wave_sum(w0 + w1);
+        if (lane == 0) part[j & 1][pair][h] = w;
+        __syncthreads();
+        w = part[j & 1][pair][0] + part[j & 1][pair][1];
+        const double tau = tau_s[j];
+        w = mk(w.x * tau, w.y * tau);
+#pragma unroll
+        for (int i0 = 0; i0 < NRH; i0 += 4) {
+#pragma unroll
+            for (int i = i0; i < i0 + 4; ++i) { cplx t = mk(0.0, 0.0); cfma(t, vs[lane + 64 * (2 * i + h)], w); x[i] = x[i] - t; }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int i = 0; i < NRH; ++i) {
+        const int s = lane + 64 * (2 * i + h);
+        if (s < ldS) Zk[(int64_t)c * ldS + s] = s < S ? conj(x[i]) : mk(0.0, 0.0);
+    }
+}
+
+template <int NRH>
+__global__ void __launch_bounds__(512) wa_qr_pair_kernel(cplx* __restrict__ B, cplx* __restrict__ Vw, int S, int C, int ldS, double* __restrict__ tauw,
+                                                         cplx* __restrict__ R2w) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    cplx* vs = reinterpret_cast<cplx*>(dyn);              // [128 NRH]  v_j, zero outside rows j .. S-1
+    __shared__ double red[8];
+    __shared__ cplx s_alpha;
+    __shared__ double s_tau;
+    __shared__ cplx part[2][4][2];                        // [turn parity][pair][half]
+    cplx* Bk = B + (int64_t)blockIdx.x * C * ldS;
+    cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, pair = wave >> 1, h = wave & 1;   // (wave: known uniform)
+    constexpr int NST = 128 * NRH / 512;
+    for (int j = 0; j < C; ++j) {
+        cplx* aj = Bk + (int64_t)j * ldS;
+        // column j (as the earlier steps left it) into LDS, its norm on the way
+        cplx r[NST];
+        double n2 = 0.0;
+#pragma unroll
+        for (int q = 0; q < NST; ++q) {
+            const int s = tid + 512 * q;
+            r[q] = (s >= j && s < S) ? aj[s] : mk(0.0, 0.0);
+            n2 += norm2(r[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < NST; ++q) vs[tid + 512 * q] = r[q];
+        n2 = block_sum(n2, red);   // (contains the barriers that complete vs)
+        if (tid == 0) {
+            const cplx x0 = vs[j];
+            const double nx = sqrt(n2), ax = cabs(x0);
+            cplx alpha = mk(-nx, 0.0);
+            if (ax > 0.0) alpha = mk(-x0.x / ax * nx, -x0.y / ax * nx);
+            const double nv2 = 2.0 * nx * (nx + ax);          // |x - alpha e_1|^2
+            s_alpha = alpha;
+            s_tau = nv2 > 0.0 ? 2.0 / nv2 : 0.0;
+            vs[j] = x0 - alpha;
+            tauw[(int64_t)blockIdx.x * C + j] = s_tau;
+        }
+        __syncthreads();
+        const cplx alpha = s_alpha;
+        const double tau = s_tau;
+        // v_j to memory (the back-transform reads it), column j itself: alpha on the diagonal, zeros below
+        cplx* vj = Vk + (int64_t)j * ldS;
+#pragma unroll
+        for (int q = 0; q < NST; ++q) {
+            const int s = tid + 512 * q;
+            if (s >= j && s < S) { vj[s] = vs[s]; aj[s] = s == j ? alpha : mk(0.0, 0.0); }
+        }
+        // columns k > j: a_k -= tau v (v^H a_k); a pair of waves per column, each half once through registers
+        const int turns = (C - 1 - j + 3) >> 2;
+        for (int it = 0; it < turns; ++it) {
+            const int k = j + 1 + 4 * it + pair;
+            const bool act = k < C;                          // (an idle pair still meets the barrier)
+            cplx* ak = Bk + (int64_t)(act ? k : j) * ldS;
+            // (whole 64-row groups, a group beyond ldS folded onto the last one: the addresses are wave-uniform plus the lane, no per-row
+            //  masks to keep.  Rows above j keep their values -- v_j is zero there, so they neither count nor change.)
+            cplx a[NRH];
+#pragma unroll
+            for (int i = 0; i < NRH; ++i) {
+                const int rb = 64 * (2 * i + h);
+                const cplx v = ak[min(rb, ldS - 64) + lane];
+                a[i] = rb + lane < S ? v : mk(0.0, 0.0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            cplx w0 = mk(0.0, 0.0), w1 = mk(0.0, 0.0);
+#pragma unroll
+            for (int i0 = 0; i0 < NRH; i0 += 4) {
+#pragma unroll
+                for (int i = i0; i < i0 + 4; i += 2) {
+                    cfma_conj(w0, vs[lane + 64 * (2 * i + h)], a[i]);
+                    cfma_conj(w1, vs[lane + 64 * (2 * i + 2 + h)], a[i + 1]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            cplx w = wave_sum(w0 + w1);
+            if (lane == 0) part[it & 1][pair][h] = w;
+            __syncthreads();
+            w = part[it & 1][pair][0] + part[it & 1][pair][1];
+            w = mk(w.x * tau, w.y * tau);
+#pragma unroll
+            for (int i0 = 0; i0 < NRH; i0 += 4) {
+#pragma unroll
+                for (int i = i0; i < i0 + 4; ++i) {
+                    const int rb = 64 * (2 * i + h);
+                    if (act && rb < ldS) { cplx t = mk(0.0, 0.0); cfma(t, vs[rb + lane], w); ak[rb + lane] = a[i] - t; }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __syncthreads();   // (vs is rewritten by the next step; the trailing columns are complete in memory for this workgroup)
+    }
+    cplx* R2 = R2w + (int64_t)blockIdx.x * C * C;
+    for (int idx = tid; idx < C * C; idx += 512) {
+        const int i = idx / C, k = idx % C;
+        R2[idx] = (i <= k && i < S) ? Bk[(int64_t)k * ldS + i] : mk(0.0, 0.0);
+    }
+}
+
 // least-squares rows: W[e][kb][c] = sum_d Hc[e][kb][d] Yri[kb][c][d]   (kb < n_c)
 __global__ void __launch_bounds__(256) wa_ls_kernel(const cplx* __restrict__ Hc, int64_t ldH, int n_c, const cplx* __restrict__ Yri, int64_t ldD, int D, int C,
                                                     int P, int kb_first, cplx* __restrict__ W) {
@@ -734,8 +911,10 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
     const char* e_reg = getenv("EMAGLS_WA_REG");   // =0: the forms that walk the columns through L2
     const bool reg7 = ldS <= 64 * 7 && !(e_reg && e_reg[0] == '0');
     const char* e_tall = getenv("EMAGLS_WA_TALL");   // =0: the plain forms for the tall problems
-    const bool tall = !reg7 && S <= 64 * WA_TALL && !(e_tall && e_tall[0] == '0');
-    const size_t dyn_tall = sizeof(cplx) * 64 * WA_TALL;
+    const bool tall_on = !reg7 && !(e_tall && e_tall[0] == '0');
+    const bool tall = tall_on && S <= 64 * WA_TALL;
+    const bool pairf = tall_on && !tall && S <= 128 * WA_PAIR;   // (two waves per column)
+    const size_t dyn_tall = sizeof(cplx) * 64 * WA_TALL, dyn_pair = sizeof(cplx) * 128 * WA_PAIR;
     if (tall) {
         static PerDeviceOnce tall_once;
         if (tall_once.first()) {
@@ -743,8 +922,16 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
             HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_tall_kernel<WA_TALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         }
     }
+    if (pairf) {
+        static PerDeviceOnce pair_once;
+        if (pair_once.first()) {
+            HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_pair_kernel<WA_PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+            HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_pair_kernel<WA_PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        }
+    }
     if (reg7) wa_qr_reg_kernel<7><<<nbins, 1024, 0, st>>>((const cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
     else if (tall) wa_qr_tall_kernel<WA_TALL><<<nbins, 512, dyn_tall, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
+    else if (pairf) wa_qr_pair_kernel<WA_PAIR><<<nbins, 512, dyn_pair, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
     else wa_qr_kernel<<<nbins, 512, 0, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
     KERNEL_CHECK();
     const int Cp = (C + 1) & ~1;
@@ -756,6 +943,7 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
     KERNEL_CHECK();
     if (reg7) wa_back_reg_kernel<7><<<dim3(nbins, (unsigned)ceil_div(C, 32)), 512, 0, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
     else if (tall) wa_back_tall_kernel<WA_TALL><<<dim3(nbins, (unsigned)ceil_div(C, 8)), 512, dyn_tall, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
+    else if (pairf) wa_back_pair_kernel<WA_PAIR><<<dim3(nbins, (unsigned)ceil_div(C, 4)), 512, dyn_pair, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
     else wa_back_kernel<<<nbins, 512, 0, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
     KERNEL_CHECK();
 }

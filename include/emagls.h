@@ -148,7 +148,11 @@ int emagls_get_emagls_filters_ema_in_sh(const double* hL, const double* hR, int6
                                         double fs, int64_t len, int basis, void* wL, void* wR);
 
 /* atf_irs [atf_taps x nmics x natf]; outputs real [filter_len x nmics];
- * mean_grid_dev_deg (optional) receives the value the reference prints (getEMagLsFiltersFromAtf.m:96). */
+ * mean_grid_dev_deg (optional) receives the value the reference prints (getEMagLsFiltersFromAtf.m:96).
+ * Up to 64 microphones.  Up to 32, a bin whose matched ATF matrix is well conditioned (cond < 3e4) is solved from its M x M Gram
+ * matrix; where a bin is not -- clean or simulated ATFs of a sphere-mounted array at low frequencies -- the bins up to it are
+ * factored from the matrix itself (Householder QR + Jacobi SVD, the reference's 1 % clip), at any width and up to 4096 matched
+ * directions (EMAGLS_ERR_UNSUPPORTED above).  The first execute of such a set runs twice; a plan keeps the moved route. */
 int emagls_get_emagls_filters_from_atf(const double* hL, const double* hR, int64_t nsamp, int64_t ndirs,
                                        const double* hrir_azi, const double* hrir_zen, const double* atf_irs,
                                        int64_t atf_taps, int64_t nmics, int64_t natf, const double* atf_azi,
@@ -680,7 +684,8 @@ int emagls_design_hrir_sets(int kind, const double* hL, const double* hR, int64_
 /* The HRTF subjects of ONE ATF set in one call (BASELINE config 5: the loop over subjects around
  * lib/getEMagLsFiltersFromAtf.m:1): hL, hR [nsamp x ndirs x nsets], the other arguments as emagls_get_emagls_filters_from_atf;
  * wL, wR [filter_len x nmics x nsets].  The ATF set is uploaded once and its side (spectra, matching, per-bin factors) computed
- * once per batch of up to 16 subjects; one resident sweep launch per batch.  The same filters as nsets single calls. */
+ * once per batch of up to 16 subjects; one resident sweep launch per batch.  The same filters as nsets single calls -- also for
+ * ATF sets whose low bins need the dense route (any width up to 32 microphones), whose subjects run plan by plan. */
 int emagls_from_atf_hrir_sets(const double* hL, const double* hR, int64_t nsamp, int64_t ndirs, int64_t nsets, const double* hrir_azi,
                               const double* hrir_zen, const double* atf_irs, int64_t atf_taps, int64_t nmics, int64_t natf, const double* atf_azi,
                               const double* atf_zen, double fs, int64_t filter_len, double f_trans, double* wL, double* wR, double* mean_dev);
