@@ -773,14 +773,16 @@ void plan_setup(emagls_plan& p) {
         p.C = (int)d.nmics;
         // up to 32 microphones on the Gram route (the M x M factors of the persistent sweep's form); the dense route behind its
         // conditioning flag -- QR + Jacobi of the Dm x M matrix itself -- in factor.hip's register tiles up to 8 columns at this row
-        // count, in wide_array.hip's tall forms from 9 on (from_atf_shared_stage)
+        // count, in wide_array.hip's tall forms from 9 on, and in its tiled form (row blocks + a tree step) at every width above 4096
+        // matched directions (from_atf_shared_stage)
         // (33..64 microphones: the plain per-bin path of wide_array.hip on the matched ATF matrices themselves, one subject at a time)
         if (p.C > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 64 ATF microphones is not supported in this build");
         p.wide = p.C > 32;
         p.hrir_smaller = d.ndirs <= d.natf;  // min([a b]) returns the first index on ties (FromAtf.m:62)
         p.Dm = p.hrir_smaller ? d.ndirs : d.natf;
         // (up to 3072 matched directions: resident sweep; above: the Gram route with one launch per bin, sweep_half_kernel walking
-        // several slabs per workgroup; the dense route -- QR of the Dm x M matrix itself -- holds 4096 rows)
+        // several slabs per workgroup; the dense route -- QR of the Dm x M matrix itself -- in one workgroup per bin up to 4096 rows and
+        // in row blocks above)
         if (p.Dm > 65536) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 65536 matched directions is not supported in this build");
         if (p.Dm < p.C) throw Error(EMAGLS_ERR_UNSUPPORTED, "fewer directions than microphones");
     }
@@ -1883,12 +1885,17 @@ void from_atf_subject_stage(emagls_plan& p) {   // grid matching (cheap; the pro
     stage_prologue(p, 1, p.hrir_smaller ? nullptr : p.get<int64_t>("match_idx"), p.Dm);
 }
 constexpr int FROM_ATF_DENSE_REG = 8;   // microphones the dense route factors in factor.hip's register tiles (C 64 <= 512 threads)
-// the dense route's copy of its bins' matrices at 9..32 microphones: allocated when a conditioning flag first moves the route, for
-// the dense bins only (a well-conditioned plan never holds it)
+constexpr int FROM_ATF_DENSE_ROWS = 4096;   // matched directions one workgroup factors; above: the tiled form at every width
+bool from_atf_dense_tiled(const emagls_plan& p) { return !p.wide && p.Dm > FROM_ATF_DENSE_ROWS; }
+// the dense route's copy of its bins' matrices at 9..32 microphones or more than 4096 matched directions, and the tiled form's
+// workspace (the row blocks' triangles, the tree step's stack, reflectors and T_i): allocated when a conditioning flag first moves
+// the route, for the dense bins only (a well-conditioned plan never holds them)
 void from_atf_alloc_dense(emagls_plan& p) {
-    if (p.wide || p.C <= FROM_ATF_DENSE_REG || p.gram_from == 1) return;
+    const bool tiled = from_atf_dense_tiled(p);
+    if (p.wide || (p.C <= FROM_ATF_DENSE_REG && !tiled) || p.gram_from == 1) return;
     const int dense_end = p.gram_from > 0 ? p.gram_from : p.P;
     p.alloc("Bd", sizeof(cplx) * (size_t)(dense_end - 1) * p.C * p.ldD, false);
+    if (tiled) p.alloc("Td", wa_tiling((int)p.Dm, p.C, dense_end - 1).bytes, false);
 }
 void from_atf_shared_stage(emagls_plan& p) {    // ATF spectra on the matched directions and the per-bin factors
     hipStream_t st = p.stream;
@@ -1927,14 +1934,20 @@ void from_atf_shared_stage(emagls_plan& p) {    // ATF spectra on the matched di
         a.Hq = p.get<cplx>("Hc"); a.ldHq = p.ldD; a.hq_estride = (int64_t)ls_end * p.ldD; a.ls_end = std::min(ls_end, dense_end);
         a.W = p.get<cplx>("W"); a.sweeps_out = p.get<int>("jsweeps");
         a.tauw = p.get<double>("tauw"); a.R2w = p.get<cplx>("R2w"); a.Nw = p.get<cplx>("Nw");
-        if (M <= FROM_ATF_DENSE_REG) {
+        const bool tiled = from_atf_dense_tiled(p);
+        if (M <= FROM_ATF_DENSE_REG && !tiled) {
             launch_factor(a, dense_end - 1, true, st);
         } else {
             // 9..32 microphones: factor.hip's register tiles end at 8 columns of this height; wide_array.hip's tall forms factor a copy
             // of the dense bins' matrices (their QR works in place, the sweep still reads X) and write Y_reg_inv where the sweep
             // expects it.  Workspace slots 0 .. dense_end - 2: the Gram-route bins use the slots from gram_from - 1 on.
+            // More than 4096 matched directions, 1..32 microphones: the same in row blocks (launch_wa_factor_tiled).
             cplx* X = p.get<cplx>("X");
             HIP_CHECK(hipMemcpyAsync(p.get("Bd"), X + g_stride, sizeof(cplx) * (size_t)(dense_end - 1) * g_stride, hipMemcpyDeviceToDevice, st));
+            if (tiled)
+                launch_wa_factor_tiled(p.get("Bd"), p.get("Vws"), (int)p.Dm, M, (int)p.ldD, dense_end - 1, SVD_REGUL_CONST, a.tauw, a.R2w, a.Nw,
+                                       a.sv + M, a.sweeps_out + 1, a.Z + g_stride, p.get("Td"), st);
+            else
             launch_wa_factor(p.get("Bd"), p.get("Vws"), (int)p.Dm, M, (int)p.ldD, dense_end - 1, SVD_REGUL_CONST, a.tauw, a.R2w, a.Nw, a.sv + M,
                              a.sweeps_out + 1, a.Z + g_stride, st);
             launch_wa_ls(p.get("Hc"), p.ldD, ls_end, a.Z + g_stride, p.ldD, (int)p.Dm, M, p.P, 1, a.ls_end, p.get("W"), st);
@@ -2009,8 +2022,8 @@ void execute_from_atf_wide(emagls_plan& p) {
 
 void execute_from_atf(emagls_plan& p) {
     if (p.wide) { execute_from_atf_wide(p); return; }
-    // (eager / profiled executes; plan_execute captures the stages around the sweep otherwise.  More matched directions than the
-    // dense route's QR holds: the Gram route as well, emagls_run_sweep then launches bin by bin)
+    // (eager / profiled executes; plan_execute captures the stages around the sweep otherwise.  More than 4096 matched directions:
+    // the Gram route first as well, emagls_run_sweep then launches bin by bin; flagged bins take the dense route's tiled form)
     // (9..32 microphones without the resident sweep on more rows than factor.hip's 32-column tiles hold, e.g. more than 3072 matched
     // directions: the Gram route first as well, the flagged bins on the dense route of that width)
     if (p.sweep_persist || p.Dm > 4096 || (p.C > FROM_ATF_DENSE_REG && p.Dm > 768)) {
@@ -2933,9 +2946,6 @@ bool plan_recover(emagls_plan& p, const int* flag, bool apply) {
         // Householder route then covers more bins and, at their higher kr, more orders: plan_routes refuses beyond its tile)
         if (p.gram_from == 0 || flag[3] < p.gram_from)
             throw Error(EMAGLS_ERR_NUMERIC, "internal: Gram-route conditioning flag outside the route (stale graph)");
-        if (p.d.kind == EMAGLS_KIND_FROM_ATF && p.Dm > 4096)
-            throw Error(EMAGLS_ERR_UNSUPPORTED, "the ATF matrices of some bins are too ill-conditioned for the Gram route (cond > 3e4) and the "
-                                                "dense route holds at most 4096 matched directions in this build");
         if (apply && p.d.kind == EMAGLS_KIND_FROM_ATF) {
             // measured ATFs: the bins up to the offending one take the dense route (QR + Jacobi of the matched ATF matrix itself)
             p.gram_from = flag[3] + 1 < p.P ? flag[3] + 1 : 0;

@@ -529,25 +529,51 @@ __global__ void __launch_bounds__(256) wa_yri_mfma_kernel(const double* __restri
 //                        lane), a workgroup = 8 columns of a bin; v_{j-1} is requested before step j's arithmetic
 //   wa_qr_tall_kernel    a wave takes the trailing columns of a step in turn: whole column -> registers, dot, update, store
 // ---------------------------------------------------------------------------------------------
+// A workgroup of the tall forms below factors a ROW BLOCK ("leaf") of its bin's matrix: rows r0 .. r0 + S of every column, column
+// stride ldS as before.  The whole matrix is the one-leaf case (leaf_h >= S, one leaf per bin): r0 = 0, the bin's S and ldS.  With
+// several leaves per bin (the tiled form, launch_wa_factor_tiled) every leaf but the last is leaf_h rows, a multiple of 64, so the
+// 64-row groups a wave reads and writes never reach into the next leaf; the last one owns the rows up to ldS.  tau / R2 slot of a
+// leaf: bin * leaves + leaf.
+// The kernels are compiled twice: LEAF = false is the one-leaf case with these values known at compile time (the code of the whole-
+// matrix forms as it was: they run at 256 registers, where a few more live values mean scratch), LEAF = true reads them from the grid.
+struct WaRows { int r0, S, ext; int64_t slot; };
+template <bool LEAF>
+__device__ __forceinline__ WaRows wa_rows(int bin, int leaf, int nleaf, int leaf_h, int S, int ldS) {
+    WaRows w;
+    if (!LEAF) { w.r0 = 0; w.S = S; w.ext = ldS; w.slot = bin; return w; }
+    w.r0 = leaf * leaf_h;
+    w.S = min(leaf_h, S - w.r0);
+    w.ext = leaf + 1 < nleaf ? leaf_h : ldS - w.r0;      // rows this leaf may touch (written as zeros beyond S)
+    w.slot = (int64_t)bin * nleaf + leaf;
+    return w;
+}
+// Where a back-transform finds N(s, c) of its (bin, leaf): the row-major C x C blocks of wa_jacobi_kernel ({C C, 0, C, 1}), or the
+// C x C block of rows leaf C .. of the tree step's Z (element (c, s) of a [C][ldT] bin: {C ldT, C, 1, ldT}).
+struct WaNAt { int64_t bin; int leaf, s, c; };
+template <bool LEAF>
+__device__ __forceinline__ WaNAt wa_nat(WaNAt nat, int C) { return LEAF ? nat : WaNAt{(int64_t)C * C, 0, C, 1}; }
 constexpr int WA_TALL = 48;     // rows per lane: up to 3072 rows
-template <int NRT>
-__global__ void __launch_bounds__(512) wa_back_tall_kernel(const cplx* __restrict__ Vw, const double* __restrict__ tauw, const cplx* __restrict__ Nw, int S,
-                                                           int C, int ldS, cplx* __restrict__ Z) {
+template <int NRT, bool LEAF>
+__global__ void __launch_bounds__(512) wa_back_tall_kernel(const cplx* __restrict__ Vw, const double* __restrict__ tauw, const cplx* __restrict__ Nw, WaNAt nat_,
+                                                           int Sall, int C, int ldS, int leaf_h, cplx* __restrict__ Z) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     cplx* vs = reinterpret_cast<cplx*>(dyn);              // [64 NRT]
     __shared__ double tau_s[WA_CMAX];
-    const cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS;
-    const cplx* N = Nw + (int64_t)blockIdx.x * C * C;
-    cplx* Zk = Z + (int64_t)blockIdx.x * C * ldS;
+    const WaRows rw = wa_rows<LEAF>(blockIdx.x, blockIdx.z, gridDim.z, leaf_h, Sall, ldS);
+    const WaNAt nat = wa_nat<LEAF>(nat_, C);
+    const int S = rw.S;
+    const cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS + rw.r0;
+    const cplx* N = Nw + (int64_t)blockIdx.x * nat.bin + (int64_t)blockIdx.z * nat.leaf;
+    cplx* Zk = Z + (int64_t)blockIdx.x * C * ldS + rw.r0;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int c = 8 * blockIdx.y + wave;
     const bool active = c < C;
-    if (tid < C) tau_s[tid] = tauw[(int64_t)blockIdx.x * C + tid];
+    if (tid < C) tau_s[tid] = tauw[rw.slot * C + tid];
     cplx x[NRT];
 #pragma unroll
     for (int i = 0; i < NRT; ++i) {
         const int s = lane + 64 * i;
-        x[i] = (active && s < C && s < S) ? conj(N[s * C + c]) : mk(0.0, 0.0);   // X[s][c] = conj(N[s][c])
+        x[i] = (active && s < C && s < S) ? conj(N[s * nat.s + c * nat.c]) : mk(0.0, 0.0);   // X[s][c] = conj(N[s][c])
     }
     constexpr int NST = 64 * NRT / 512;   // staged values per thread and step
     cplx r[NST];
@@ -588,20 +614,22 @@ __global__ void __launch_bounds__(512) wa_back_tall_kernel(const cplx* __restric
 #pragma unroll
     for (int i = 0; i < NRT; ++i) {
         const int s = lane + 64 * i;
-        if (s < ldS) Zk[(int64_t)c * ldS + s] = s < S ? conj(x[i]) : mk(0.0, 0.0);
+        if (s < rw.ext) Zk[(int64_t)c * ldS + s] = s < S ? conj(x[i]) : mk(0.0, 0.0);
     }
 }
 
-template <int NRT>
-__global__ void __launch_bounds__(512) wa_qr_tall_kernel(cplx* __restrict__ B, cplx* __restrict__ Vw, int S, int C, int ldS, double* __restrict__ tauw,
-                                                         cplx* __restrict__ R2w) {
+template <int NRT, bool LEAF>
+__global__ void __launch_bounds__(512) wa_qr_tall_kernel(cplx* __restrict__ B, cplx* __restrict__ Vw, int Sall, int C, int ldS, int leaf_h,
+                                                         double* __restrict__ tauw, cplx* __restrict__ R2w) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     cplx* vs = reinterpret_cast<cplx*>(dyn);              // [64 NRT]  v_j, zero outside rows j .. S-1
     __shared__ double red[8];
     __shared__ cplx s_alpha;
     __shared__ double s_tau;
-    cplx* Bk = B + (int64_t)blockIdx.x * C * ldS;
-    cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS;
+    const WaRows rw = wa_rows<LEAF>(blockIdx.x, blockIdx.y, gridDim.y, leaf_h, Sall, ldS);
+    const int S = rw.S;
+    cplx* Bk = B + (int64_t)blockIdx.x * C * ldS + rw.r0;
+    cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS + rw.r0;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     constexpr int NST = 64 * NRT / 512;
     for (int j = 0; j < C; ++j) {
@@ -627,7 +655,7 @@ __global__ void __launch_bounds__(512) wa_qr_tall_kernel(cplx* __restrict__ B, c
             s_alpha = alpha;
             s_tau = nv2 > 0.0 ? 2.0 / nv2 : 0.0;
             vs[j] = x0 - alpha;
-            tauw[(int64_t)blockIdx.x * C + j] = s_tau;
+            tauw[rw.slot * C + j] = s_tau;
         }
         __syncthreads();
         const cplx alpha = s_alpha;
@@ -670,7 +698,7 @@ __global__ void __launch_bounds__(512) wa_qr_tall_kernel(cplx* __restrict__ B, c
         }
         __syncthreads();   // (vs is rewritten by the next step; the trailing columns are complete in memory for this workgroup)
     }
-    cplx* R2 = R2w + (int64_t)blockIdx.x * C * C;
+    cplx* R2 = R2w + rw.slot * C * C;
     for (int idx = tid; idx < C * C; idx += 512) {
         const int i = idx / C, k = idx % C;
         R2[idx] = (i <= k && i < S) ? Bk[(int64_t)k * ldS + i] : mk(0.0, 0.0);
@@ -688,25 +716,29 @@ __global__ void __launch_bounds__(512) wa_qr_tall_kernel(cplx* __restrict__ B, c
 //                        between the halves is the workgroup's)
 // ---------------------------------------------------------------------------------------------
 constexpr int WA_PAIR = 32;     // rows per lane and wave: up to 4096 rows per pair
-template <int NRH>
-__global__ void __launch_bounds__(512) wa_back_pair_kernel(const cplx* __restrict__ Vw, const double* __restrict__ tauw, const cplx* __restrict__ Nw, int S,
-                                                           int C, int ldS, cplx* __restrict__ Z) {
+constexpr int WA_LEAF_ROWS = 64 * WA_TALL;   // tiled form: most rows of a leaf (launch_wa_factor_tiled)
+template <int NRH, bool LEAF>
+__global__ void __launch_bounds__(512) wa_back_pair_kernel(const cplx* __restrict__ Vw, const double* __restrict__ tauw, const cplx* __restrict__ Nw, WaNAt nat_,
+                                                           int Sall, int C, int ldS, int leaf_h, cplx* __restrict__ Z) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     cplx* vs = reinterpret_cast<cplx*>(dyn);              // [128 NRH]
     __shared__ double tau_s[WA_CMAX];
     __shared__ cplx part[2][4][2];                        // [step parity][pair][half]
-    const cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS;
-    const cplx* N = Nw + (int64_t)blockIdx.x * C * C;
-    cplx* Zk = Z + (int64_t)blockIdx.x * C * ldS;
+    const WaRows rw = wa_rows<LEAF>(blockIdx.x, blockIdx.z, gridDim.z, leaf_h, Sall, ldS);
+    const WaNAt nat = wa_nat<LEAF>(nat_, C);
+    const int S = rw.S;
+    const cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS + rw.r0;
+    const cplx* N = Nw + (int64_t)blockIdx.x * nat.bin + (int64_t)blockIdx.z * nat.leaf;
+    cplx* Zk = Z + (int64_t)blockIdx.x * C * ldS + rw.r0;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, pair = wave >> 1, h = wave & 1;   // (wave: known uniform)
     const int c = 4 * blockIdx.y + pair;
     const bool active = c < C;
-    if (tid < C) tau_s[tid] = tauw[(int64_t)blockIdx.x * C + tid];
+    if (tid < C) tau_s[tid] = tauw[rw.slot * C + tid];
     cplx x[NRH];
 #pragma unroll
     for (int i = 0; i < NRH; ++i) {
         const int s = lane + 64 * (2 * i + h);
-        x[i] = (active && s < C && s < S) ? conj(N[s * C + c]) : mk(0.0, 0.0);   // X[s][c] = conj(N[s][c])
+        x[i] = (active && s < C && s < S) ? conj(N[s * nat.s + c * nat.c]) : mk(0.0, 0.0);   // X[s][c] = conj(N[s][c])
     }
     constexpr int NST = 128 * NRH / 512;   // staged values per thread and step
     cplx r[NST];
@@ -752,21 +784,23 @@ __global__ void __launch_bounds__(512) wa_back_pair_kernel(const cplx* __restric
 #pragma unroll
     for (int i = 0; i < NRH; ++i) {
         const int s = lane + 64 * (2 * i + h);
-        if (s < ldS) Zk[(int64_t)c * ldS + s] = s < S ? conj(x[i]) : mk(0.0, 0.0);
+        if (s < rw.ext) Zk[(int64_t)c * ldS + s] = s < S ? conj(x[i]) : mk(0.0, 0.0);
     }
 }
 
-template <int NRH>
-__global__ void __launch_bounds__(512) wa_qr_pair_kernel(cplx* __restrict__ B, cplx* __restrict__ Vw, int S, int C, int ldS, double* __restrict__ tauw,
-                                                         cplx* __restrict__ R2w) {
+template <int NRH, bool LEAF>
+__global__ void __launch_bounds__(512) wa_qr_pair_kernel(cplx* __restrict__ B, cplx* __restrict__ Vw, int Sall, int C, int ldS, int leaf_h,
+                                                         double* __restrict__ tauw, cplx* __restrict__ R2w) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     cplx* vs = reinterpret_cast<cplx*>(dyn);              // [128 NRH]  v_j, zero outside rows j .. S-1
     __shared__ double red[8];
     __shared__ cplx s_alpha;
     __shared__ double s_tau;
     __shared__ cplx part[2][4][2];                        // [turn parity][pair][half]
-    cplx* Bk = B + (int64_t)blockIdx.x * C * ldS;
-    cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS;
+    const WaRows rw = wa_rows<LEAF>(blockIdx.x, blockIdx.y, gridDim.y, leaf_h, Sall, ldS);
+    const int S = rw.S, ext = rw.ext;
+    cplx* Bk = B + (int64_t)blockIdx.x * C * ldS + rw.r0;
+    cplx* Vk = Vw + (int64_t)blockIdx.x * C * ldS + rw.r0;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, pair = wave >> 1, h = wave & 1;   // (wave: known uniform)
     constexpr int NST = 128 * NRH / 512;
     for (int j = 0; j < C; ++j) {
@@ -792,7 +826,7 @@ __global__ void __launch_bounds__(512) wa_qr_pair_kernel(cplx* __restrict__ B, c
             s_alpha = alpha;
             s_tau = nv2 > 0.0 ? 2.0 / nv2 : 0.0;
             vs[j] = x0 - alpha;
-            tauw[(int64_t)blockIdx.x * C + j] = s_tau;
+            tauw[rw.slot * C + j] = s_tau;
         }
         __syncthreads();
         const cplx alpha = s_alpha;
@@ -810,13 +844,13 @@ __global__ void __launch_bounds__(512) wa_qr_pair_kernel(cplx* __restrict__ B, c
             const int k = j + 1 + 4 * it + pair;
             const bool act = k < C;                          // (an idle pair still meets the barrier)
             cplx* ak = Bk + (int64_t)(act ? k : j) * ldS;
-            // (whole 64-row groups, a group beyond ldS folded onto the last one: the addresses are wave-uniform plus the lane, no per-row
+            // (whole 64-row groups, a group beyond the leaf's extent folded onto the last one: the addresses are wave-uniform plus the lane, no per-row
             //  masks to keep.  Rows above j keep their values -- v_j is zero there, so they neither count nor change.)
             cplx a[NRH];
 #pragma unroll
             for (int i = 0; i < NRH; ++i) {
                 const int rb = 64 * (2 * i + h);
-                const cplx v = ak[min(rb, ldS - 64) + lane];
+                const cplx v = ak[min(rb, ext - 64) + lane];
                 a[i] = rb + lane < S ? v : mk(0.0, 0.0);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -840,17 +874,29 @@ __global__ void __launch_bounds__(512) wa_qr_pair_kernel(cplx* __restrict__ B, c
 #pragma unroll
                 for (int i = i0; i < i0 + 4; ++i) {
                     const int rb = 64 * (2 * i + h);
-                    if (act && rb < ldS) { cplx t = mk(0.0, 0.0); cfma(t, vs[rb + lane], w); ak[rb + lane] = a[i] - t; }
+                    if (act && rb < ext) { cplx t = mk(0.0, 0.0); cfma(t, vs[rb + lane], w); ak[rb + lane] = a[i] - t; }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         __syncthreads();   // (vs is rewritten by the next step; the trailing columns are complete in memory for this workgroup)
     }
-    cplx* R2 = R2w + (int64_t)blockIdx.x * C * C;
+    cplx* R2 = R2w + rw.slot * C * C;
     for (int idx = tid; idx < C * C; idx += 512) {
         const int i = idx / C, k = idx % C;
         R2[idx] = (i <= k && i < S) ? Bk[(int64_t)k * ldS + i] : mk(0.0, 0.0);
+    }
+}
+
+// Tree step of the tiled form: the leaves' triangles R_i (row major [i][k], slot bin * leaves + leaf) one below the other as the
+// (leaves C) x C matrix of the bin, columns [k][ldT] like every matrix the QR forms take; rows from leaves C up to ldT zero.
+__global__ void __launch_bounds__(256) wa_stack_kernel(const cplx* __restrict__ Ri, int nleaf, int C, int ldT, cplx* __restrict__ St) {
+    const int bin = blockIdx.x, k = blockIdx.y;
+    const cplx* R = Ri + (int64_t)bin * nleaf * C * C;
+    cplx* out = St + ((int64_t)bin * C + k) * ldT;
+    for (int r = threadIdx.x; r < ldT; r += 256) {
+        const int leaf = r / C, i = r % C;
+        out[r] = leaf < nleaf ? R[((int64_t)leaf * C + i) * C + k] : mk(0.0, 0.0);
     }
 }
 
@@ -900,6 +946,26 @@ void launch_wa_assemble(const void* Tn, const void* bn, int nOrd, int S, int C, 
     wa_assemble_kernel<<<dim3(nbins, C), 256, 0, st>>>((const double*)Tn, (const cplx*)bn, nOrd, S, C, ldS, P, kb0, (cplx*)B);
     KERNEL_CHECK();
 }
+namespace {
+void wa_tall_attrs() {
+    static PerDeviceOnce tall_once;
+    if (tall_once.first()) {
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_tall_kernel<WA_TALL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_tall_kernel<WA_TALL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_tall_kernel<WA_TALL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_tall_kernel<WA_TALL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    }
+}
+void wa_pair_attrs() {
+    static PerDeviceOnce pair_once;
+    if (pair_once.first()) {
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_pair_kernel<WA_PAIR, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_pair_kernel<WA_PAIR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_pair_kernel<WA_PAIR, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_pair_kernel<WA_PAIR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    }
+}
+}  // namespace
 void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, double reg_c, double* tauw, void* R2w, void* Nw, double* sv, int* sweeps,
                       void* Z, hipStream_t st) {
     if (nbins <= 0) return;
@@ -915,23 +981,12 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
     const bool tall = tall_on && S <= 64 * WA_TALL;
     const bool pairf = tall_on && !tall && S <= 128 * WA_PAIR;   // (two waves per column)
     const size_t dyn_tall = sizeof(cplx) * 64 * WA_TALL, dyn_pair = sizeof(cplx) * 128 * WA_PAIR;
-    if (tall) {
-        static PerDeviceOnce tall_once;
-        if (tall_once.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_tall_kernel<WA_TALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_tall_kernel<WA_TALL>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        }
-    }
-    if (pairf) {
-        static PerDeviceOnce pair_once;
-        if (pair_once.first()) {
-            HIP_CHECK(hipFuncSetAttribute((const void*)wa_qr_pair_kernel<WA_PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            HIP_CHECK(hipFuncSetAttribute((const void*)wa_back_pair_kernel<WA_PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        }
-    }
+    if (tall) wa_tall_attrs();
+    if (pairf) wa_pair_attrs();
+    const WaNAt nat{};   // (one leaf per bin: N of wa_jacobi_kernel)
     if (reg7) wa_qr_reg_kernel<7><<<nbins, 1024, 0, st>>>((const cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
-    else if (tall) wa_qr_tall_kernel<WA_TALL><<<nbins, 512, dyn_tall, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
-    else if (pairf) wa_qr_pair_kernel<WA_PAIR><<<nbins, 512, dyn_pair, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
+    else if (tall) wa_qr_tall_kernel<WA_TALL, false><<<nbins, 512, dyn_tall, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, ldS, tauw, (cplx*)R2w);
+    else if (pairf) wa_qr_pair_kernel<WA_PAIR, false><<<nbins, 512, dyn_pair, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, ldS, tauw, (cplx*)R2w);
     else wa_qr_kernel<<<nbins, 512, 0, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, tauw, (cplx*)R2w);
     KERNEL_CHECK();
     const int Cp = (C + 1) & ~1;
@@ -942,9 +997,70 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
     wa_jacobi_kernel<<<nbins, 1024, dyn, st>>>((const cplx*)R2w, C, reg_c, (cplx*)Nw, sv, sweeps, flag2);
     KERNEL_CHECK();
     if (reg7) wa_back_reg_kernel<7><<<dim3(nbins, (unsigned)ceil_div(C, 32)), 512, 0, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
-    else if (tall) wa_back_tall_kernel<WA_TALL><<<dim3(nbins, (unsigned)ceil_div(C, 8)), 512, dyn_tall, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
-    else if (pairf) wa_back_pair_kernel<WA_PAIR><<<dim3(nbins, (unsigned)ceil_div(C, 4)), 512, dyn_pair, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
+    else if (tall) wa_back_tall_kernel<WA_TALL, false><<<dim3(nbins, (unsigned)ceil_div(C, 8)), 512, dyn_tall, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, nat, S, C, ldS, ldS, (cplx*)Z);
+    else if (pairf) wa_back_pair_kernel<WA_PAIR, false><<<dim3(nbins, (unsigned)ceil_div(C, 4)), 512, dyn_pair, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, nat, S, C, ldS, ldS, (cplx*)Z);
     else wa_back_kernel<<<nbins, 512, 0, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
+    KERNEL_CHECK();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tiled form (TSQR) for matrices taller than one workgroup holds: S > 4096 rows, e.g. FromAtf's dense route on HRIR grids of 5810,
+// 11950 or 16384 directions.  (No Gram-type shortcut such as CholeskyQR: these bins are on the dense route because the SQUARED
+// condition number is out of FP64's reach.)
+//   leaves   the rows of a bin cut into `leaves` blocks, every block factored in place by a workgroup of the tall or the pair form
+//            (grid = bins x leaves): reflectors and tau per leaf, triangles R_i
+//   tree     the R_i of a bin one below the other ((leaves C) x C, wa_stack_kernel) through launch_wa_factor: QR of the stack = the
+//            bin's R, Jacobi + clipping on it (wa_jacobi_kernel, unchanged), and the stack's own back-transform of [N; 0], which
+//            leaves a C x C block T_i per leaf in its Z
+//   back     every leaf's back-transform with its T_i in the place of N writes its rows of Z
+// Cutting rule: leaves = ceil(S / WA_LEAF_ROWS); leaf height h = ceil(S / leaves) rounded up to a multiple of 64 (balanced leaves; a
+// wave's 64-row groups then end with its leaf); the last leaf takes the remaining S - (leaves - 1) h rows.  It is the shortest one, by
+// less than 64 (leaves - 1) rows: at least 1085 rows for S > 4096 -- never fewer rows than columns, so every R_i is a full triangle.
+// No atomics, every sum in a fixed order: equal inputs give equal bits.
+// ---------------------------------------------------------------------------------------------
+WaTiling wa_tiling(int S, int C, int nbins) {
+    static const int leaf_rows = [] {   // EMAGLS_WA_LEAF_ROWS: another upper bound of the leaf height (1024 .. 4096; the measurements)
+        const char* e = getenv("EMAGLS_WA_LEAF_ROWS");
+        const int v = e ? atoi(e) : WA_LEAF_ROWS;
+        return v >= 1024 && v <= 128 * WA_PAIR ? v / 64 * 64 : WA_LEAF_ROWS;
+    }();
+    WaTiling t{};
+    t.leaves = (int)ceil_div(S, leaf_rows);
+    t.leaf_h = (int)ceil_div(ceil_div(S, t.leaves), 64) * 64;
+    t.ldT = (int)ceil_div(t.leaves * C, 64) * 64;
+    if (S - (t.leaves - 1) * t.leaf_h < C) throw Error(2, "tiled QR: a leaf with fewer rows than columns");
+    const size_t nb = (size_t)std::max(nbins, 0);
+    t.off_stack = sizeof(cplx) * nb * t.leaves * C * C;                    // behind the R_i
+    t.off_vt = t.off_stack + sizeof(cplx) * nb * C * t.ldT;               // the stack's reflectors
+    t.off_zt = t.off_vt + sizeof(cplx) * nb * C * t.ldT;                  // the stack's Z: the T_i
+    t.off_tau = t.off_zt + sizeof(cplx) * nb * C * t.ldT;                 // the leaves' tau
+    t.bytes = t.off_tau + sizeof(double) * nb * t.leaves * C;
+    return t;
+}
+void launch_wa_factor_tiled(void* B, void* Vw, int S, int C, int ldS, int nbins, double reg_c, double* tauw, void* R2w, void* Nw, double* sv,
+                            int* sweeps, void* Z, void* ws, hipStream_t st) {
+    if (nbins <= 0) return;
+    if (C > 32) throw Error(2, "tiled QR: at most 32 columns");
+    const WaTiling t = wa_tiling(S, C, nbins);
+    char* w = (char*)ws;
+    cplx* Ri = (cplx*)w;
+    cplx* St = (cplx*)(w + t.off_stack);
+    cplx* Vt = (cplx*)(w + t.off_vt);
+    cplx* Zt = (cplx*)(w + t.off_zt);
+    double* tau_l = (double*)(w + t.off_tau);
+    const bool tall = t.leaf_h <= 64 * WA_TALL;
+    const size_t dyn_tall = sizeof(cplx) * 64 * WA_TALL, dyn_pair = sizeof(cplx) * 128 * WA_PAIR;
+    if (tall) wa_tall_attrs(); else wa_pair_attrs();
+    const dim3 gq(nbins, t.leaves);
+    if (tall) wa_qr_tall_kernel<WA_TALL, true><<<gq, 512, dyn_tall, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, t.leaf_h, tau_l, Ri);
+    else wa_qr_pair_kernel<WA_PAIR, true><<<gq, 512, dyn_pair, st>>>((cplx*)B, (cplx*)Vw, S, C, ldS, t.leaf_h, tau_l, Ri);
+    KERNEL_CHECK();
+    wa_stack_kernel<<<dim3(nbins, C), 256, 0, st>>>(Ri, t.leaves, C, t.ldT, St);
+    KERNEL_CHECK();
+    launch_wa_factor(St, Vt, t.leaves * C, C, t.ldT, nbins, reg_c, tauw, R2w, Nw, sv, sweeps, Zt, st);
+    const WaNAt nat{(int64_t)C * t.ldT, C, 1, t.ldT};   // T_i(s, c) = Zt[c][leaf C + s]
+    if (tall) wa_back_tall_kernel<WA_TALL, true><<<dim3(nbins, (unsigned)ceil_div(C, 8), t.leaves), 512, dyn_tall, st>>>((const cplx*)Vw, tau_l, Zt, nat, S, C, ldS, t.leaf_h, (cplx*)Z);
+    else wa_back_pair_kernel<WA_PAIR, true><<<dim3(nbins, (unsigned)ceil_div(C, 4), t.leaves), 512, dyn_pair, st>>>((const cplx*)Vw, tau_l, Zt, nat, S, C, ldS, t.leaf_h, (cplx*)Z);
     KERNEL_CHECK();
 }
 void launch_wa_yri(const void* Q, int64_t ldQ, const void* Z, int S, int C, int ldS, int D, int64_t ldD, int nbins, void* Yri, hipStream_t st) {

@@ -151,8 +151,8 @@ int emagls_get_emagls_filters_ema_in_sh(const double* hL, const double* hR, int6
  * mean_grid_dev_deg (optional) receives the value the reference prints (getEMagLsFiltersFromAtf.m:96).
  * Up to 64 microphones.  Up to 32, a bin whose matched ATF matrix is well conditioned (cond < 3e4) is solved from its M x M Gram
  * matrix; where a bin is not -- clean or simulated ATFs of a sphere-mounted array at low frequencies -- the bins up to it are
- * factored from the matrix itself (Householder QR + Jacobi SVD, the reference's 1 % clip), at any width and up to 4096 matched
- * directions (EMAGLS_ERR_UNSUPPORTED above).  The first execute of such a set runs twice; a plan keeps the moved route. */
+ * factored from the matrix itself (Householder QR + Jacobi SVD, the reference's 1 % clip), at any width and any supported number of
+ * matched directions (above 4096 in row blocks with a tree step over their triangles).  The first execute of such a set runs twice; a plan keeps the moved route. */
 int emagls_get_emagls_filters_from_atf(const double* hL, const double* hR, int64_t nsamp, int64_t ndirs,
                                        const double* hrir_azi, const double* hrir_zen, const double* atf_irs,
                                        int64_t atf_taps, int64_t nmics, int64_t natf, const double* atf_azi,
