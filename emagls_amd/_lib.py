@@ -13,6 +13,7 @@ BASIS = {"real": 0, "complex": 1}
 KIND_LS, KIND_MAGLS, KIND_EMAGLS, KIND_EMAGLS2, KIND_FROM_ATF, KIND_EMA_CH, KIND_MAGLS_2D, KIND_EMA_SH = range(8)
 RADIAL = {"tikhonov": 0, "softlimit": 1, "full": 2, "none": 3}
 LAYOUT = {"sh": 0, "ch": 1}
+MODEL = {"sh": 0, "emagls": 1, "emagls2": 2, "atf": 3}
 
 c_dp = C.POINTER(C.c_double)
 c_i64 = C.c_int64
@@ -160,6 +161,9 @@ SYMBOLS = {
     "emagls_ch_basis": (C.c_int, [C.c_int, c_i64, C.c_void_p, C.c_int, C.c_void_p]),
     "emagls_get_smair_matrix": (C.c_int, [C.c_int, C.c_double, c_i64, C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_int,
                                           C.c_int, C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_int)]),
+    "emagls_rendered_hrtfs": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, c_i64, c_i64, c_i64, C.c_void_p, C.c_void_p, c_i64, C.c_double,
+                                        C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i64, c_i64, C.c_void_p,
+                                        C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "emagls_eq_filter_nfft": (c_i64, [c_i64]),
     "emagls_get_magls_spherical_head_filter": (C.c_int, [C.c_double, C.c_int, C.c_double, c_i64, C.c_void_p, C.c_void_p]),
     "emagls_get_magls_array_diffuse_filter": (C.c_int, [C.c_double, C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_double, c_i64, C.c_int,

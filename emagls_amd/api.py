@@ -18,6 +18,7 @@ hL/hR are [numSamples x numDirections]; filters come back [len x numChannels].
     getMagLsArrayDiffuseFilter   lib/getMagLsArrayDiffuseFilter.m:1
     getSH / sphModalCoeffs  the un-vendored third-party functions the above call
     getCH / getSMAIRMatrix  dependencies/getCH.m:1, dependencies/getSMAIRMatrix.m:1 (the array model materialised)
+    getRenderedHrtfs        this project's: what a filter set renders per direction, and its error metrics
 
 A custom `shFunction` (a callable with getSH's signature: shFunction(N, [azi zen], shDefinition) -> [dirs x (N+1)^2]) cannot
 cross the C ABI as a handle: it is evaluated here, at the simulation order the library reports, and its matrices go through the
@@ -1099,3 +1100,111 @@ def getMagLsArrayDiffuseFilter(micRadius, micGridAziRad, micGridZenRad, order, f
     L.check(L.load().emagls_get_magls_array_diffuse_filter(float(micRadius), pa, pz, azi.size, int(order), float(fs), int(len), b,
                                                            pY, pw))
     return w
+
+
+class RenderedHrtfs:
+    """Result of getRenderedHrtfs.  For one filter set: H [P x D x 2] complex (None with returnResponse=False), and, when reference
+    HRIRs were given, mag_err_db [P x 2], ild_err_db [P], cov_hat / cov_ref [P x 4] = (R_LL, R_RR, Re R_LR, Im R_LR) and
+    coherence_hat / coherence_ref [P] = |R_LR| / sqrt(R_LL R_RR).  For a list of sets every array has a leading set dimension."""
+    __slots__ = ("H", "mag_err_db", "ild_err_db", "cov_hat", "cov_ref", "coherence_hat", "coherence_ref", "nfft")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _stack_sets(a, name):
+    """One [rows x cols] array, or a list / 3-D array of them -> ([nsets x cols x rows] C-order == each set column-major, was_list)."""
+    many = isinstance(a, (list, tuple)) or np.ndim(a) == 3
+    arrs = [np.asarray(x) for x in (a if many else [a])]
+    if not arrs or any(x.ndim != 2 or x.shape != arrs[0].shape for x in arrs):
+        raise ValueError("%s must be [rows x cols] arrays of equal shape" % name)
+    cplx = any(np.iscomplexobj(x) for x in arrs)
+    out = np.ascontiguousarray(np.stack([x.T for x in arrs]), dtype=np.complex128 if cplx else np.float64)
+    return out, many, cplx
+
+
+def getRenderedHrtfs(wL, wR, model, dirsAziZenRad, fs, *, order=None, micRadius=None, micGridAziZenRad=None, atfIrs=None, nfft=None,
+                     shDefinition="real", hL=None, hR=None, weights=None, returnResponse=True):
+    """What the decoding filters wL, wR ([len x C], or a list of such sets) render for a plane wave from each direction of
+    dirsAziZenRad [D x 2]: Hhat_e(k, d) = sum_c fft(w_e, nfft)(k, c) pwGrid_k(c, d) on the bins 0..nfft/2, with pwGrid_k the operand
+    of the matching reference design -- model 'sh' (LS / MagLS: order), 'emagls' (order, micRadius, micGridAziZenRad), 'emagls2'
+    (micRadius, micGridAziZenRad) or 'atf' (atfIrs [taps x numMics x D], given on the evaluation directions).  nfft defaults to
+    min(2048, 2*len).  With reference HRIRs hL, hR ([numSamples x D], one pair or one per filter set) the error metrics of
+    include/emagls.h (emagls_rendered_hrtfs) are returned too; weights [D] are direction weights (uniform if absent).
+    returnResponse=False computes the metrics alone."""
+    if model not in L.MODEL:
+        raise ValueError("model must be one of %s" % ", ".join(sorted(L.MODEL)))
+    b, _ = _basis(shDefinition)
+    WL, many, cL = _stack_sets(wL, "wL")
+    WR, manyR, cR = _stack_sets(wR, "wR")
+    if WL.shape != WR.shape or many != manyR:
+        raise ValueError("wL and wR must have equal shape")
+    w_cplx = cL or cR
+    if w_cplx:
+        WL, WR = WL.astype(np.complex128), WR.astype(np.complex128)
+    nsets, Cc, ln = WL.shape
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    azi = zen = maz = mzn = atf = None
+    M = taps = 0
+    if model == "atf":
+        if atfIrs is None:
+            raise ValueError("model 'atf' needs atfIrs")
+        atf, _p = _f(atfIrs)
+        if atf.ndim != 3:
+            raise ValueError("atfIrs must be [taps x numMics x numDirections]")
+        taps, M, D = atf.shape
+        if dirsAziZenRad is not None and np.asarray(dirsAziZenRad).shape[0] != D:
+            raise ValueError("atfIrs must be given on the evaluation directions")
+    else:
+        dirs = np.asarray(dirsAziZenRad, dtype=np.float64)
+        D = dirs.shape[0]
+        azi, _p = _vec(dirs[:, 0])
+        zen, _p = _vec(dirs[:, 1])
+        if model in ("sh", "emagls") and order is None:
+            raise ValueError("model %r needs order" % model)
+        if model != "sh":
+            if micRadius is None or micGridAziZenRad is None:
+                raise ValueError("model %r needs micRadius and micGridAziZenRad" % model)
+            grid = np.asarray(micGridAziZenRad, dtype=np.float64)
+            maz, _p = _vec(grid[:, 0])
+            mzn, _p = _vec(grid[:, 1])
+            M = maz.size
+    n_fft = int(nfft) if nfft else min(2048, 2 * ln)
+    P = n_fft // 2 + 1
+    H = nh = wts = None
+    nsamp = 0
+    if (hL is None) != (hR is None):
+        raise ValueError("hL and hR go together")
+    have_ref = hL is not None
+    if have_ref:
+        HL, _m, c1 = _stack_sets(hL, "hL")
+        HR, _m, c2 = _stack_sets(hR, "hR")
+        if c1 or c2 or HL.shape != HR.shape or HL.shape[1] != D:
+            raise ValueError("hL and hR must be real [numSamples x %d] arrays of equal shape" % D)
+        nh, nsamp = HL.shape[0], HL.shape[2]
+        if weights is not None:
+            wts, _p = _vec(weights, D, "weights")
+    elif not returnResponse:
+        raise ValueError("nothing to compute: no reference HRIRs and returnResponse=False")
+    if returnResponse:
+        H = np.zeros((nsets, 2, P, D), dtype=np.complex128)
+    mag = np.zeros((nsets, P, 2)) if have_ref else None
+    ild = np.zeros((nsets, P)) if have_ref else None
+    ch = np.zeros((nsets, P, 4)) if have_ref else None
+    cr = np.zeros((nsets, P, 4)) if have_ref else None
+    L.check(L.load().emagls_rendered_hrtfs(L.MODEL[model], vp(WL), vp(WR), 1 if w_cplx else 0, ln, Cc, nsets, vp(azi), vp(zen), D, float(fs),
+                                           int(order) if order is not None else 0, b, float(micRadius) if micRadius is not None else 0.0,
+                                           vp(maz), vp(mzn), M, vp(atf), taps, n_fft, vp(HL) if have_ref else None,
+                                           vp(HR) if have_ref else None, nsamp, nh if have_ref else 0, vp(wts), vp(H), vp(mag), vp(ild),
+                                           vp(ch), vp(cr)))
+    res = dict(nfft=n_fft)
+    if returnResponse:
+        res["H"] = np.ascontiguousarray(H.transpose(0, 2, 3, 1))          # [set][P][D][ear]
+    if have_ref:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            coh = lambda c: np.hypot(c[..., 2], c[..., 3]) / np.sqrt(c[..., 0] * c[..., 1])   # noqa: E731
+            res.update(mag_err_db=mag, ild_err_db=ild, cov_hat=ch, cov_ref=cr, coherence_hat=coh(ch), coherence_ref=coh(cr))
+    if not many:
+        res = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
+    return RenderedHrtfs(**res)

@@ -289,6 +289,33 @@ void launch_smair(const void* E, bool e_cplx, int ldS, const void* bn, int nOrd,
                   hipStream_t st);
 void launch_sh_encode(const double* sig, int64_t n, int M, const void* Z, int ldZ, int nOut, bool out_cplx, void* out, hipStream_t st);
 
+// ---- response.hip: rendered HRTFs of a design and their error metrics
+int rh_num_metrics();            // values per (set, bin) of the reduced metrics: |dB| L, R, |ILD error|, cov_hat [4], cov_ref [4]
+int rh_bins_padded(int P);       // bins per set of the product's left operand (whole workgroup tiles)
+int rh_gemm_tiles(int64_t D);    // direction tiles of `partial` that launch_rh_gemm / launch_rh_atf write
+int rh_atf_tiles(int64_t D);
+// complex columns in [ncols][len] -> real planes out [ncols][2][len]; and W[i] = F[2 i] + i F[2 i + 1] for their spectra
+void launch_rh_split(const void* in, int64_t ncols, int64_t len, double* out, hipStream_t st);
+void launch_rh_join(const void* F, int64_t n, void* W, hipStream_t st);
+// Tt [Kpad][ldR] (K = S, or 2 S with a complex basis; the rows K .. Kpad are the caller's to zero) from W [nsets][2][P][C]:
+// T = (W A) b_n with A [C][ldA] (null: T = W) and bn [P][nOrd] (null: 1); ldR >= 4 nsets rh_bins_padded(P)
+void launch_rh_modes(const void* W, int C, int P, int nsets, const void* A, bool a_cplx, int ldA, const void* bn, int nOrd, int S, bool y_cplx,
+                     double* Tt, int64_t ldR, hipStream_t st);
+void launch_rh_interleave(const void* Y, int64_t ldi, int S, int64_t D, double* Yk, int64_t ldo, hipStream_t st);
+struct RhOut {
+    const void* H = nullptr;       // reference spectra [hset][2][P][D] complex (null: no metrics)
+    int64_t hset_stride = 0;       // 2 P D, or 0 when one HRIR set serves every filter set
+    const double* w = nullptr;     // [D] normalised direction weights
+    void* Hhat = nullptr;          // [set][2][P][D] complex (null: not stored)
+    double* partial = nullptr;     // [set][P][tiles][rh_num_metrics()]
+};
+// Yk [Kpad][ldY] with ldY a multiple of 64 >= D and zeros beyond D and K
+void launch_rh_gemm(const double* Tt, int64_t ldR, const double* Yk, int64_t ldY, int K, int P, int64_t D, int nsets, const RhOut& o,
+                    hipStream_t st);
+// W [nsets][2][P][M], A [P][M][D] complex
+void launch_rh_atf(const void* W, const void* A, int M, int P, int64_t D, int nsets, const RhOut& o, hipStream_t st);
+void launch_rh_reduce(const double* partial, int64_t nrows, int ntile, double* out, hipStream_t st);
+
 // ---- capi.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool)
 hipStream_t pool_stream_take();
 void pool_stream_give(hipStream_t st);

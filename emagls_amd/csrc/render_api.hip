@@ -5,6 +5,7 @@
 
 #include "../../include/emagls.h"
 #include "kernels.hpp"
+#include "scratch.hpp"
 
 using namespace emagls;
 
@@ -12,30 +13,6 @@ namespace {
 
 constexpr double C_SOUND = 343.0;     // dependencies/getRadialFilter.m:31, lib/getMagLsSphericalHeadFilter.m:26
 constexpr int NFFT_MAX_LEN = 2048;    // lib/getMagLsSphericalHeadFilter.m:23
-
-// device scratch of one call, freed on every exit path
-struct Scratch {
-    std::vector<void*> ptrs;
-    hipStream_t st = nullptr;
-    Scratch() { st = pool_stream_take(); }
-    ~Scratch() {
-        for (void* p : ptrs) hipFree(p);
-        pool_stream_give(st);
-    }
-    template <typename T = void> T* get(size_t bytes, bool zero = false) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16));
-        ptrs.push_back(p);
-        if (zero) HIP_CHECK(hipMemsetAsync(p, 0, bytes, st));
-        return reinterpret_cast<T*>(p);
-    }
-    template <typename T> T* put(const T* host, size_t count) {
-        T* p = get<T>(sizeof(T) * count);
-        HIP_CHECK(hipMemcpyAsync(p, host, sizeof(T) * count, hipMemcpyHostToDevice, st));
-        return p;
-    }
-    void sync() { HIP_CHECK(hipStreamSynchronize(st)); }
-};
 
 bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 

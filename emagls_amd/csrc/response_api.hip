@@ -1,0 +1,255 @@
+// C ABI of the rendered HRTFs of a design (include/emagls.h, emagls_rendered_hrtfs).  Host arrays in, host
+// arrays out; every argument is checked before the device is touched, and every array operation runs in the kernels of
+// response.hip, fft.hip (the spectra), sh_basis.hip, modal.hip and factor.hip (pinv(Y_lo)).  No CPU fallback.
+#include <cmath>
+#include <vector>
+
+#include "../../include/emagls.h"
+#include "kernels.hpp"
+#include "scratch.hpp"
+
+using namespace emagls;
+
+namespace {
+
+constexpr double C_SOUND = 343.0;          // dependencies/getSMAIRMatrix.m:95
+constexpr int RH_NFFT_MAX = 2048;          // the designs' own limit (lib/getEMagLsFilters.m:41)
+constexpr int RH_SIM_ORDER_MAX = 85;
+constexpr int64_t RH_DIRS_MAX = 65536;
+constexpr size_t RH_SCRATCH_MAX = (size_t)24 << 30;
+
+// spectra of real columns x [ncols][L] at out[k ldo + (j / inner) ld_inner + j % inner]
+void real_spectra(Scratch& s, const double* x, int64_t L, int64_t ncols, const int64_t* colidx, int nfft, const cplx* tw, cplx* out, int64_t ldo,
+                  int64_t inner, int64_t ld_inner) {
+    launch_real_fft_gather(x, L, ncols, colidx, nfft, tw, out, ldo, inner, ld_inner, s.st);
+}
+
+}  // namespace
+
+extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, int w_is_complex, int64_t len, int64_t nchan, int64_t nsets,
+                                     const double* dir_azi, const double* dir_zen, int64_t ndirs, double fs, int order, int basis,
+                                     double mic_radius, const double* mic_azi, const double* mic_zen, int64_t nmics, const double* atf,
+                                     int64_t atf_taps, int64_t nfft_in, const double* hL, const double* hR, int64_t nsamp,
+                                     int64_t nhrir_sets, const double* weights, void* Hhat, double* mag_err_db, double* ild_err_db,
+                                     double* cov_hat, double* cov_ref) {
+    return guarded_call([&] {
+        // ---- arguments (nothing below this block fails on what the caller passed)
+        if (model < EMAGLS_MODEL_SH || model > EMAGLS_MODEL_ATF) throw Error(EMAGLS_ERR_ARG, "unknown model");
+        const bool is_sh = model == EMAGLS_MODEL_SH, is_atf = model == EMAGLS_MODEL_ATF, is_array = !is_sh && !is_atf;
+        const bool raw = model == EMAGLS_MODEL_EMAGLS2;
+        if (!wL || !wR) throw Error(EMAGLS_ERR_ARG, "null pointer: decoding filters");
+        if (!is_atf && (!dir_azi || !dir_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: evaluation directions");
+        if (is_array && (!mic_azi || !mic_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: microphone grid");
+        if (is_atf && !atf) throw Error(EMAGLS_ERR_ARG, "null pointer: ATFs");
+        const bool metrics = mag_err_db || ild_err_db || cov_hat || cov_ref;
+        if (!Hhat && !metrics) throw Error(EMAGLS_ERR_ARG, "null pointer: no output is asked for");
+        if (metrics && (!hL || !hR)) throw Error(EMAGLS_ERR_ARG, "null pointer: the metrics need reference HRIRs");
+        if (len < 1 || nchan < 1 || nsets < 1 || ndirs < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        if (nsets > 65535) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 65535 filter sets in one call are not supported");
+        if (ndirs > RH_DIRS_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 65536 evaluation directions are not supported");
+        const int64_t nfft64 = nfft_in > 0 ? nfft_in : std::min<int64_t>(RH_NFFT_MAX, 2 * len);
+        if (nfft_in < 0) throw Error(EMAGLS_ERR_ARG, "nfft must be positive (0: min(2048, 2*len))");
+        if (nfft64 % 2) throw Error(EMAGLS_ERR_ARG, "nfft must be even");
+        if (len > nfft64) throw Error(EMAGLS_ERR_ARG, "len exceeds nfft");
+        if (nfft64 < 8) throw Error(EMAGLS_ERR_UNSUPPORTED, "nfft below 8 is not supported");
+        if (nfft64 > RH_NFFT_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "nfft above 2048 is not supported in this build");
+        const int nfft = (int)nfft64, P = nfft / 2 + 1;
+        const bool cb = basis == EMAGLS_BASIS_COMPLEX;
+        if (!is_atf && basis != EMAGLS_BASIS_REAL && basis != EMAGLS_BASIS_COMPLEX) throw Error(EMAGLS_ERR_ARG, "shDefinition must be 'real' or 'complex'");
+        int C = 0, S = 0, simOrder = 0, nOut = 0, M = 0;
+        if (is_sh) {
+            if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
+            if (order > 15) throw Error(EMAGLS_ERR_UNSUPPORTED, "SH order above 15 is not supported for the sh model");
+            C = S = (order + 1) * (order + 1);
+        } else {
+            if (nmics < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nmics");
+            if (nmics > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 64 microphones are not supported");
+            M = (int)nmics;
+            C = M;
+        }
+        if (is_array) {
+            if (!(fs > 0) || !(mic_radius > 0)) throw Error(EMAGLS_ERR_ARG, "fs and micRadius must be positive");
+            int ord = 4;                                      // lib/getEMagLs2Filters.m:51-63 leaves params.order at its default
+            if (!raw) {
+                if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
+                if (order > 4)
+                    throw Error(EMAGLS_ERR_UNSUPPORTED, "the emagls model is limited to SH order 4 (pinv(Y_lo) of emagls_get_smair_matrix); orders 5..7 are not supported");
+                ord = order;
+                nOut = (order + 1) * (order + 1);
+                if (M < nOut) throw Error(EMAGLS_ERR_UNSUPPORTED, "fewer microphones than SH channels");
+                C = nOut;
+            }
+            simOrder = std::max(ord, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));     // getSMAIRMatrix.m:95
+            if (simOrder > RH_SIM_ORDER_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "simulation order above 85 is not supported");
+            S = (simOrder + 1) * (simOrder + 1);
+        }
+        if (is_atf) {
+            if (atf_taps < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: atf_taps");
+            if (atf_taps > nfft) throw Error(EMAGLS_ERR_ARG, "atf_taps exceeds nfft");
+        }
+        if (nchan != C) throw Error(EMAGLS_ERR_ARG, "the filters' channel count does not match the model");
+        if (hL || hR) {
+            if (!hL || !hR) throw Error(EMAGLS_ERR_ARG, "null pointer: one of hL, hR");
+            if (nsamp < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nsamp");
+            if (nsamp > nfft) throw Error(EMAGLS_ERR_ARG, "nsamp exceeds nfft");
+            if (nhrir_sets != 1 && nhrir_sets != nsets) throw Error(EMAGLS_ERR_ARG, "the number of HRIR sets must be 1 or nsets");
+        }
+        const int64_t D = ndirs;
+        std::vector<double> wn;
+        if (metrics) {
+            wn.assign((size_t)D, 1.0 / (double)D);
+            if (weights) {
+                double sum = 0.0;
+                for (int64_t d = 0; d < D; ++d) {
+                    if (!(weights[d] >= 0.0) || !std::isfinite(weights[d])) throw Error(EMAGLS_ERR_ARG, "direction weights must be non-negative and finite");
+                    sum += weights[d];
+                }
+                if (!(sum > 0.0) || !std::isfinite(sum)) throw Error(EMAGLS_ERR_ARG, "direction weights must not all be zero");
+                for (int64_t d = 0; d < D; ++d) wn[(size_t)d] = weights[d] / sum;
+            }
+        }
+        // ---- sizes
+        const int NM = rh_num_metrics(), Pp = rh_bins_padded(P);
+        const int K = (cb && !is_atf) ? 2 * S : S, Kpad = (int)(ceil_div(K, 4) * 4);
+        const int64_t ldR = (int64_t)nsets * Pp * 4, ldY = ceil_div(D, 64) * 64;
+        const int ntile = is_atf ? rh_atf_tiles(D) : rh_gemm_tiles(D);
+        const size_t nW = (size_t)nsets * 2 * P * C;
+        const size_t need = nW * 16 * (w_is_complex ? 4 : 2) + (is_atf ? (size_t)P * M * D * 16 + (size_t)atf_taps * M * D * 8
+                                                                        : (size_t)Kpad * (ldR + ldY) * 8 + (cb ? (size_t)S * D * 16 : 0)) +
+                            (metrics ? (size_t)nhrir_sets * 2 * D * (nsamp * 8 + (size_t)P * 16) + (size_t)nsets * P * ntile * NM * 8 : 0) +
+                            (Hhat ? (size_t)nsets * 2 * P * D * 16 : 0);
+        if (need > RH_SCRATCH_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "the call needs more than 24 GiB of device memory; split the filter sets over several calls");
+
+        // ---- device
+        Scratch s;
+        cplx* tw = s.get<cplx>(sizeof(cplx) * (size_t)nfft);
+        launch_twiddles(nfft, tw, s.st);
+        // 1. filter spectra W [set][2][P][C]: columns (set, ear, c[, re/im]) of one real array
+        cplx* W = s.get<cplx>(sizeof(cplx) * nW);
+        {
+            const size_t esz_w = w_is_complex ? sizeof(cplx) : sizeof(double);
+            const size_t per_ear = (size_t)C * len;
+            char* taps = s.get<char>(esz_w * (size_t)nsets * 2 * per_ear);
+            for (int64_t i = 0; i < nsets; ++i)
+                for (int e = 0; e < 2; ++e)
+                    HIP_CHECK(hipMemcpyAsync(taps + esz_w * ((size_t)i * 2 + e) * per_ear, (const char*)(e ? wR : wL) + esz_w * (size_t)i * per_ear,
+                                             esz_w * per_ear, hipMemcpyHostToDevice, s.st));
+            const int64_t ncols = (int64_t)nsets * 2 * C;
+            if (!w_is_complex) {
+                real_spectra(s, (const double*)taps, len, ncols, nullptr, nfft, tw, W, C, C, (int64_t)P * C);
+            } else {
+                double* planes = s.get<double>(sizeof(double) * (size_t)ncols * 2 * len);
+                cplx* F = s.get<cplx>(sizeof(cplx) * nW * 2);
+                launch_rh_split(taps, ncols, len, planes, s.st);
+                real_spectra(s, planes, len, 2 * ncols, nullptr, nfft, tw, F, 2 * C, 2 * C, (int64_t)P * 2 * C);
+                launch_rh_join(F, (int64_t)nW, W, s.st);
+            }
+        }
+        // reference spectra H [hset][2][P][D], weights, partial sums
+        RhOut o{};
+        double* d_red = nullptr;
+        if (metrics) {
+            const size_t per_ear = (size_t)D * nsamp;
+            double* h = s.get<double>(sizeof(double) * (size_t)nhrir_sets * 2 * per_ear);
+            for (int64_t i = 0; i < nhrir_sets; ++i)
+                for (int e = 0; e < 2; ++e)
+                    HIP_CHECK(hipMemcpyAsync(h + ((size_t)i * 2 + e) * per_ear, (e ? hR : hL) + (size_t)i * per_ear, sizeof(double) * per_ear,
+                                             hipMemcpyHostToDevice, s.st));
+            cplx* H = s.get<cplx>(sizeof(cplx) * (size_t)nhrir_sets * 2 * P * D);
+            real_spectra(s, h, nsamp, nhrir_sets * 2 * D, nullptr, nfft, tw, H, D, D, (int64_t)P * D);
+            o.H = H;
+            o.hset_stride = nhrir_sets > 1 ? (int64_t)2 * P * D : 0;
+            o.w = s.put(wn.data(), (size_t)D);
+            o.partial = s.get<double>(sizeof(double) * (size_t)nsets * P * ntile * NM);
+            d_red = s.get<double>(sizeof(double) * (size_t)nsets * P * NM);
+        }
+        const size_t hhat_bytes = sizeof(cplx) * (size_t)nsets * 2 * P * D;
+        if (Hhat) o.Hhat = s.get(hhat_bytes);
+
+        if (is_atf) {
+            // pwGrid_k(m, d) = fft(atfIrs, nfft)(k, m, d): A [P][M][D] through a column gather (atfIrs is [taps x M x D])
+            const double* d_atf = s.put(atf, (size_t)atf_taps * M * D);
+            std::vector<int64_t> colidx((size_t)M * D);
+            for (int m = 0; m < M; ++m)
+                for (int64_t d = 0; d < D; ++d) colidx[(size_t)m * D + d] = d * M + m;
+            const int64_t* d_col = s.put(colidx.data(), colidx.size());
+            cplx* A = s.get<cplx>(sizeof(cplx) * (size_t)P * M * D);
+            real_spectra(s, d_atf, atf_taps, (int64_t)M * D, d_col, nfft, tw, A, (int64_t)M * D, (int64_t)M * D, 0);
+            launch_rh_atf(W, A, M, P, D, (int)nsets, o, s.st);
+            s.sync();   // (colidx lives on the host until its copy has run)
+        } else {
+            // conj(Y(dirs)) as real rows Yk [Kpad][ldY]
+            const int N = is_sh ? order : simOrder;
+            const double* d_azi = s.put(dir_azi, (size_t)D);
+            const double* d_zen = s.put(dir_zen, (size_t)D);
+            double* tab = s.get<double>(sizeof(double) * sh_coeff_count(N));
+            launch_sh_coeff(N, tab, s.st);
+            double* Yk = s.get<double>(sizeof(double) * (size_t)Kpad * ldY, true);
+            if (!cb) {
+                launch_sh_basis(N, D, d_azi, d_zen, tab, false, Yk, ldY, s.st);
+            } else {
+                void* Yc = s.get(sizeof(cplx) * (size_t)S * D);
+                launch_sh_basis(N, D, d_azi, d_zen, tab, true, Yc, D, s.st);
+                launch_rh_interleave(Yc, D, S, D, Yk, ldY, s.st);
+            }
+            // 2. mode coefficients
+            double* Tt = s.get<double>(sizeof(double) * (size_t)Kpad * ldR);
+            if (Kpad > K) HIP_CHECK(hipMemsetAsync(Tt + (size_t)K * ldR, 0, sizeof(double) * (size_t)(Kpad - K) * ldR, s.st));
+            if (is_sh) {
+                launch_rh_modes(W, C, P, (int)nsets, nullptr, false, 0, nullptr, 0, S, cb, Tt, ldR, s.st);
+            } else {
+                // E = pinv(Y_lo) Y_mic, or Y_mic for raw microphone signals: the steps of emagls_get_smair_matrix (getSMAIRMatrix.m:102, :119-121)
+                const int ldM = (int)(ceil_div(M, 64) * 64), ldS = (int)(ceil_div(S, 64) * 64);
+                const double* m_azi = s.put(mic_azi, (size_t)M);
+                const double* m_zen = s.put(mic_zen, (size_t)M);
+                void* Ycm = s.get(esz(cb) * (size_t)S * M);
+                void* Yrm = s.get(esz(cb) * (size_t)ldM * ldS, true);
+                launch_sh_basis(simOrder, M, m_azi, m_zen, tab, cb, Ycm, M, s.st);
+                launch_transpose_conj(Ycm, M, S, M, Yrm, M, ldS, cb, false, s.st);
+                const void* E = Yrm;
+                if (!raw) {
+                    cplx* Yc = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
+                    cplx* Z = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
+                    cplx* V = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
+                    double* tau = s.get<double>(sizeof(double) * nOut);
+                    cplx* R2 = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
+                    cplx* Nw = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
+                    launch_widen(Ycm, M, cb, Yc, ldM, nOut, M, false, false, s.st);
+                    FactorArgs a{};
+                    a.S = M; a.C = nOut; a.ldS = ldM; a.kb0 = 0; a.P = 2;
+                    a.Xd = Yc; a.xd_stride = 0;
+                    a.reg_mode = 1; a.tol_dim = (double)std::max(M, nOut);
+                    a.Z = Z; a.Vws = V; a.tauw = tau; a.R2w = R2; a.Nw = Nw;
+                    launch_factor(a, 1, true, s.st);
+                    void* Em = s.get(esz(cb) * (size_t)nOut * ldS, true);
+                    launch_small_gemm(Z, ldM, true, Yrm, ldS, cb, Em, ldS, cb, nOut, S, M, s.st);
+                    E = Em;
+                }
+                cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)P * (simOrder + 1));
+                const double kr_step = 2.0 * kPi * ((fs / 2.0) / (double)(P - 1)) / C_SOUND * mic_radius;
+                launch_modal_bn(simOrder, P, nullptr, kr_step, -1.0, bn, simOrder + 1, 1, s.st);     // bnAll = -sphModalCoeffs(...)  (:107)
+                launch_rh_modes(W, C, P, (int)nsets, E, cb, ldS, bn, simOrder + 1, S, cb, Tt, ldR, s.st);
+            }
+            // 3. the product and its epilogue
+            launch_rh_gemm(Tt, ldR, Yk, ldY, Kpad, P, D, (int)nsets, o, s.st);
+        }
+        // 5. direction tiles in tile order
+        std::vector<double> red;
+        if (metrics) {
+            launch_rh_reduce(o.partial, (int64_t)nsets * P, ntile, d_red, s.st);
+            red.resize((size_t)nsets * P * NM);
+            HIP_CHECK(hipMemcpyAsync(red.data(), d_red, sizeof(double) * red.size(), hipMemcpyDeviceToHost, s.st));
+        }
+        if (Hhat) HIP_CHECK(hipMemcpyAsync(Hhat, o.Hhat, hhat_bytes, hipMemcpyDeviceToHost, s.st));
+        s.sync();
+        for (size_t r = 0; metrics && r < (size_t)nsets * P; ++r) {
+            const double* v = red.data() + r * NM;
+            if (mag_err_db) { mag_err_db[2 * r] = v[0]; mag_err_db[2 * r + 1] = v[1]; }
+            if (ild_err_db) ild_err_db[r] = v[2];
+            for (int j = 0; j < 4; ++j) {
+                if (cov_hat) cov_hat[4 * r + j] = v[3 + j];
+                if (cov_ref) cov_ref[4 * r + j] = v[7 + j];
+            }
+        }
+    });
+}

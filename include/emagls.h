@@ -478,6 +478,45 @@ int emagls_get_magls_spherical_head_filter(double mic_radius, int order, double 
 int emagls_get_magls_array_diffuse_filter(double mic_radius, const double* mic_azi, const double* mic_zen, int64_t nmics, int order,
                                           double fs, int64_t len, int basis, const void* Y_hi, double* w_adf);
 
+/* ---- rendered HRTFs of a design (the definition is this project's, the operands are the reference's) ----
+ * What a set of decoding filters renders for a plane wave from each of ndirs directions, and how far that is from the HRTFs it
+ * was designed against.  With nfft even, len <= nfft (0: min(2048, 2*len)), P = nfft/2+1 and W_e = fft(w_e, nfft) on bins 0..P-1:
+ *     Hhat_e(k, d) = sum_c W_e(k, c) pwGrid_k(c, d)
+ * -- the product inside the residual the designs minimise (lib/getEMagLsFilters.m:87-103).  `model` fixes pwGrid_k [C x ndirs]:
+ *   EMAGLS_MODEL_SH       getSH(order, dirs, shDefinition)' (lib/getMagLsFilters.m), the same for every k; C = (order+1)^2, order <= 15
+ *   EMAGLS_MODEL_EMAGLS   smairMat(:,:,k) * getSH(simOrder, dirs, shDefinition)' with getSMAIRMatrix called as
+ *                         lib/getEMagLsFilters.m:51-63 calls it (irLen = nfft, oversampling 1, radialFilter 'none', rigid sphere,
+ *                         plane wave, real(Bn) in the Nyquist bin, simOrder = max(order, ceil(fs*pi*r/343)) <= 85); C = (order+1)^2,
+ *                         order <= 4 (the limit of emagls_get_smair_matrix; above: EMAGLS_ERR_UNSUPPORTED)
+ *   EMAGLS_MODEL_EMAGLS2  the same with returnRawMicSigs and params.order left at 4 (lib/getEMagLs2Filters.m:51-63; `order` is not
+ *                         looked at); C = nmics <= 64
+ *   EMAGLS_MODEL_ATF      pwGrid_k(m, d) = fft(atfIrs, nfft)(k, m, d), atf [atf_taps x nmics x ndirs] column-major GIVEN ON the
+ *                         evaluation directions (the caller has matched the grids); C = nmics <= 64, atf_taps <= nfft; dir_azi,
+ *                         dir_zen, basis are not looked at
+ * smairMat is never formed: the call works on its factors.  Arguments a model does not use may be NULL / 0.
+ * wL, wR: nsets >= 1 filter sets back to back, each [len x nchan] column-major as the designs return them, real, or interleaved
+ * complex with w_is_complex; nchan must equal the model's C.  ndirs <= 65536.
+ * Hhat (optional): interleaved complex [nsets][2 ears][P][ndirs], ndirs fastest.  When it is NULL the response never leaves
+ * the kernel that computes it.
+ * Metrics (each optional) need reference HRIRs hL, hR [nsamp x ndirs] column-major, nsamp <= nfft, on the same directions:
+ * nhrir_sets = 1 (one set for all filter sets) or nsets sets back to back.  With H_e = fft(h_e, nfft), w_d = weights / sum(weights)
+ * (non-negative; NULL: uniform) and magnitudes clamped below at DBL_MIN before a logarithm, per set and bin k:
+ *   mag_err_db [nsets][P][2]   sum_d w_d |20 log10(|Hhat_e| / |H_e|)|
+ *   ild_err_db [nsets][P]      sum_d w_d |20 log10(|Hhat_L| / |Hhat_R|) - 20 log10(|H_L| / |H_R|)|
+ *   cov_hat, cov_ref [nsets][P][4]   (R_LL, R_RR, Re R_LR, Im R_LR), R_ab = sum_d w_d X_a conj(X_b): the 2 x 2 ear covariances
+ *                              of Hhat and of H (interaural coherence = |R_LR| / sqrt(R_LL R_RR))
+ * Sums run in a fixed order without atomics: equal calls give equal bits, and set i of a call gives the bits of the call with
+ * that set alone.  Every argument is checked before the device is touched. */
+#define EMAGLS_MODEL_SH 0
+#define EMAGLS_MODEL_EMAGLS 1
+#define EMAGLS_MODEL_EMAGLS2 2
+#define EMAGLS_MODEL_ATF 3
+int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, int w_is_complex, int64_t len, int64_t nchan, int64_t nsets,
+                          const double* dir_azi, const double* dir_zen, int64_t ndirs, double fs, int order, int basis,
+                          double mic_radius, const double* mic_azi, const double* mic_zen, int64_t nmics, const double* atf,
+                          int64_t atf_taps, int64_t nfft, const double* hL, const double* hR, int64_t nsamp, int64_t nhrir_sets,
+                          const double* weights, void* Hhat, double* mag_err_db, double* ild_err_db, double* cov_hat, double* cov_ref);
+
 /* ---- plan API: inputs resident in HBM, repeated execution (benchmarks, batches) ------------- */
 
 typedef struct emagls_plan emagls_plan;

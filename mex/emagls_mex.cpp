@@ -10,6 +10,7 @@
 // The build image has neither mex.h nor MATLAB: there the file is compiled against a test stand-in for mex.h and driven
 // by tests/test_mex_gateway.py (tests/mexstub/).  It is a thin adapter: argument checks, pointer hand-over, mxArray
 // allocation, error forwarding.
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstring>
@@ -628,6 +629,91 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         int rc = emagls_get_smair_matrix(order, fs, irLen, ovs, r, dbl(prhs[6], "micAzi"), dbl(prhs[7], "micZen"), M, basis, raw,
                                          radial_type(prhs[10]), mxGetScalar(prhs[11]), mxGetScalar(prhs[12]), mxGetComplexDoubles(plhs[0]), nullptr);
         if (rc) fail(rc);
+        return;
+    }
+    if (c == "rendered_hrtfs") {   // (wL, wR, model, dirsAziZenRad, fs, order, micRadius, micGridAziZenRad, atfIrs, nfft, shDefinition, hL, hR, weights, returnResponse)
+        // [] for what a model does not use.  [H, magErrDb, ildErrDb, covHat, covRef] = ...: H [P x D x 2 x numSets], the metrics
+        // [P x 2 x numSets], [P x numSets], [P x 4 x numSets] (empty without hL, hR; H empty with returnResponse false)
+        if (nrhs < 16) mexErrMsgIdAndTxt("eMagLS:arg", "rendered_hrtfs needs 15 arguments ([] for those the model does not use)");
+        const FilterArgs f = filter_args(prhs);
+        char mbuf[16] = {0};
+        mxGetString(prhs[3], mbuf, sizeof mbuf);
+        const std::string mname(mbuf);
+        const int model = mname == "sh" ? EMAGLS_MODEL_SH : mname == "emagls" ? EMAGLS_MODEL_EMAGLS : mname == "emagls2" ? EMAGLS_MODEL_EMAGLS2
+                        : mname == "atf" ? EMAGLS_MODEL_ATF : -1;
+        if (model < 0) mexErrMsgIdAndTxt("eMagLS:arg", "model must be 'sh', 'emagls', 'emagls2' or 'atf'");
+        auto given = [&](int i) { return prhs[i] && !mxIsEmpty(prhs[i]); };
+        auto grid = [&](int i, const char* what, mwSize* n) -> const double* {
+            if (!given(i)) { *n = 0; return nullptr; }
+            if (mxGetN(prhs[i]) != 2) mexErrMsgIdAndTxt("eMagLS:arg", "%s must be [n x 2] (azimuth, zenith)", what);
+            *n = mxGetM(prhs[i]);
+            return dbl(prhs[i], what);
+        };
+        mwSize D = 0, M = 0, taps = 0;
+        const double* dirs = grid(4, "dirsAziZenRad", &D);
+        const double* mics = grid(8, "micGridAziZenRad", &M);
+        const double* atf = nullptr;
+        if (given(9)) {
+            atf = dbl(prhs[9], "atfIrs");
+            const mwSize nd = mxGetNumberOfDimensions(prhs[9]);
+            const mwSize* d = mxGetDimensions(prhs[9]);
+            if (nd != 3) mexErrMsgIdAndTxt("eMagLS:arg", "atfIrs must be [taps x numMics x numDirections]");
+            if (D && d[2] != D) mexErrMsgIdAndTxt("eMagLS:arg", "atfIrs must be given on the evaluation directions");
+            taps = d[0]; M = d[1]; D = d[2];
+        }
+        const double fs = given(5) ? mxGetScalar(prhs[5]) : 0.0, radius = given(7) ? mxGetScalar(prhs[7]) : 0.0;
+        const int order = given(6) ? (int)mxGetScalar(prhs[6]) : 0, basis = basis_of(prhs[11]);
+        const int64_t nfft = given(10) ? (int64_t)mxGetScalar(prhs[10]) : (int64_t)std::min<mwSize>(2048, 2 * f.len);
+        const mwSize P = (mwSize)(nfft / 2 + 1);
+        const double *hL = nullptr, *hR = nullptr, *wts = nullptr;
+        mwSize nsamp = 0, nh = 0;
+        if (given(12) != given(13)) mexErrMsgIdAndTxt("eMagLS:arg", "hL and hR go together");
+        if (given(12)) {
+            hL = dbl(prhs[12], "hL"); hR = dbl(prhs[13], "hR");
+            const mwSize nd = mxGetNumberOfDimensions(prhs[12]);
+            const mwSize* d = mxGetDimensions(prhs[12]);
+            bool same = nd <= 3 && mxGetNumberOfDimensions(prhs[13]) == nd;
+            for (mwSize i = 0; same && i < nd; ++i) same = mxGetDimensions(prhs[13])[i] == d[i];
+            if (!same || d[1] != D) mexErrMsgIdAndTxt("eMagLS:arg", "hL and hR must be [numSamples x numDirections (x numSets)] arrays of equal size");
+            nsamp = d[0]; nh = nd == 3 ? d[2] : 1;
+            if (given(14)) {
+                if (mxGetNumberOfElements(prhs[14]) != D) mexErrMsgIdAndTxt("eMagLS:arg", "weights must have one element per direction");
+                wts = dbl(prhs[14], "weights");
+            }
+        }
+        const bool want_h = truthy(prhs[15]);
+        std::vector<double> H, mag, ild, ch, cr;
+        if (want_h) H.resize((size_t)2 * f.nsets * 2 * P * D);
+        if (hL) { mag.resize((size_t)f.nsets * P * 2); ild.resize((size_t)f.nsets * P); ch.resize((size_t)f.nsets * P * 4); cr.resize(ch.size()); }
+        auto ptr = [](std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
+        const int rc = emagls_rendered_hrtfs(model, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc ? 1 : 0, (int64_t)f.len, (int64_t)f.ch, (int64_t)f.nsets, dirs,
+                                             dirs ? dirs + D : nullptr, (int64_t)D, fs, order, basis, radius, mics, mics ? mics + M : nullptr,
+                                             (int64_t)M, atf, (int64_t)taps, nfft, hL, hR, (int64_t)nsamp, (int64_t)nh, wts, ptr(H), ptr(mag), ptr(ild),
+                                             ptr(ch), ptr(cr));
+        if (rc) fail(rc);
+        // the library's [set][ear][k][d] / [set][k][j] -> MATLAB's [k, d, ear, set] / [k, j, set]
+        const mwSize hd[4] = {want_h ? P : 0, want_h ? D : 0, want_h ? (mwSize)2 : 0, want_h ? f.nsets : 0};
+        plhs[0] = mxCreateNumericArray(4, hd, mxDOUBLE_CLASS, mxCOMPLEX);
+        if (want_h) {
+            double* o = (double*)mxGetComplexDoubles(plhs[0]);
+            for (size_t se = 0; se < (size_t)2 * f.nsets; ++se)
+                for (size_t k = 0; k < P; ++k)
+                    for (size_t d = 0; d < D; ++d) {
+                        const size_t src = (se * P + k) * D + d, dst = k + P * (d + D * se);
+                        o[2 * dst] = H[2 * src]; o[2 * dst + 1] = H[2 * src + 1];
+                    }
+        }
+        auto metric = [&](int idx, const std::vector<double>& v, mwSize cols) {
+            if (nlhs <= idx) return;
+            const mwSize md[3] = {v.empty() ? 0 : P, v.empty() ? 0 : cols, v.empty() ? 0 : f.nsets};
+            plhs[idx] = mxCreateNumericArray(3, md, mxDOUBLE_CLASS, mxREAL);
+            double* o = mxGetDoubles(plhs[idx]);
+            for (size_t i = 0; i < v.size(); ++i) {
+                const size_t j = i % cols, k = (i / cols) % P, set = i / (cols * P);
+                o[k + P * (j + cols * set)] = v[i];
+            }
+        };
+        metric(1, mag, 2); metric(2, ild, 1); metric(3, ch, 4); metric(4, cr, 4);
         return;
     }
     if (c == "encode") {
