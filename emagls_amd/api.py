@@ -580,6 +580,20 @@ def binauralDecode(sig, inFs, decodingFilterLeft, decodingFilterRight, decodingF
     return out
 
 
+def _encoder(encoder, numChannels):
+    """encoder [numChannels x numMics] as a column-major array, its pointer, whether it is complex, and numMics."""
+    e_c = np.iscomplexobj(encoder)
+    enc = np.asfortranarray(np.asarray(encoder, dtype=np.complex128 if e_c else np.float64))
+    if enc.ndim != 2 or enc.shape[0] != numChannels:
+        raise ValueError("encoder must be [numChannels x numMics] with the filters' channel count (%d) of rows" % numChannels)
+    return enc, enc.ctypes.data_as(C.c_void_p), e_c, enc.shape[1]
+
+
+def _real_mic_block(is_complex, what):
+    if is_complex:
+        raise L.EmaglsError(L.ERR_ARG, "an encoded %s takes real microphone blocks" % what)
+
+
 class BinauralDecodeStream:
     """binauralDecode a block at a time, for a listener whose head moves while the sound plays.  Created
     once from the decoding filters [len x numChannels] (real or complex); then `push` takes consecutive blocks of the SH (or CH)
@@ -595,9 +609,17 @@ class BinauralDecodeStream:
     with the gain (i + 1) / blockSize and to the old one with the rest; the first block after creation or reset does not fade.
     The outputs equal sum_s binauralDecode(g_s * x, wL[s], wR[s]) with g_s the gain of set s per sample; a constant index gives
     the bits of the plain stream on that set.  For designs on raw microphone signals, which no rotation can turn, a bank of
-    one set per head orientation (`designYawBank`, `yawBankIndex`) is what follows the head."""
+    one set per head orientation (`designYawBank`, `yawBankIndex`) is what follows the head.
+    An encoder: with encoder [numChannels x numMics] (real or complex; `arrayEncoder` makes the usual
+    ones) the stream takes blocks of REAL microphone signals [n x numMics] and returns what the plain stream returns for
+    block @ encoder.T, with the encoder inside the rotation launch: still three launches per block.  numChannels stays the
+    filters' channel count; 1 <= numMics, numChannels <= 64.  A complex encoder makes the stream run as one with complexInput.
+    A renderer that never turns needs no encoded stream: fold the encoder into the filters yourself,
+    w2 = np.einsum("...tc,cm->...tm", w, encoder), and push the microphone blocks to a plain stream of w2.  The library does not
+    do so by itself, because the stream's history would change domain between a push with angles and one without."""
 
-    def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition="real", rotationDomain="sh", complexInput=False):
+    def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition="real", rotationDomain="sh", complexInput=False,
+                 encoder=None):
         self._h = None
         self._basis, self._cb = _basis(shDefinition)
         self._layout = _layout(rotationDomain)
@@ -617,10 +639,19 @@ class BinauralDecodeStream:
         else:
             ln, self.numChannels = wL.shape
         self.blockSize, self.complexInput = int(blockSize), bool(complexInput)
+        self.numMics = None
         h = C.c_void_p()
-        L.check(L.load().emagls_decode_stream_create_bank(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
-                                                          wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
-                                                          self._layout, self._basis, self.blockSize, C.byref(h)))
+        if encoder is not None:
+            if complexInput:
+                raise ValueError("an encoded stream takes real microphone blocks: complexInput must be False")
+            enc, pe, e_c, self.numMics = _encoder(encoder, self.numChannels)
+            L.check(L.load().emagls_decode_stream_create_encoded(self.numMics, pe, 1 if e_c else 0, self.numChannels, self.numSets,
+                                                                 wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0,
+                                                                 ln, self._layout, self._basis, self.blockSize, C.byref(h)))
+        else:
+            L.check(L.load().emagls_decode_stream_create_bank(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
+                                                              wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
+                                                              self._layout, self._basis, self.blockSize, C.byref(h)))
         self._h = h
 
     @property
@@ -664,6 +695,8 @@ class BinauralDecodeStream:
         h = self._handle()
         if type(block).__module__.split(".")[0] == "torch":
             return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
+        if self.numMics is not None:
+            _real_mic_block(np.iscomplexobj(block), "stream")
         if np.iscomplexobj(block) and not self.complexInput:
             raise ValueError("the stream was created for real blocks (complexInput=False)")
         x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
@@ -681,7 +714,10 @@ class BinauralDecodeStream:
         return out
 
     def _check_block(self, shape, ndim):
-        if ndim != 2 or shape[1] != self.numChannels:
+        if self.numMics is not None:
+            if ndim != 2 or shape[1] != self.numMics:
+                raise ValueError("block must be [numSamples x numMics] matching the encoder's microphone count (%d)" % self.numMics)
+        elif ndim != 2 or shape[1] != self.numChannels:
             raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
         if shape[0] % self.blockSize:
             raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
@@ -692,6 +728,8 @@ class BinauralDecodeStream:
         n = self._check_block(tuple(block.shape), block.dim())
         if not block.is_cuda:
             raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        if self.numMics is not None:
+            _real_mic_block(block.is_complex(), "stream")
         if block.is_complex() and not self.complexInput:
             raise ValueError("the stream was created for real blocks (complexInput=False)")
         size = lambda a: a.numel() if torch.is_tensor(a) else np.asarray(a).size   # noqa: E731
@@ -761,10 +799,12 @@ class BinauralDecodeGroup:
     what a BinauralDecodeStream of the same filters returns when it is fed the same blocks with listener l's angles and indices;
     a block costs at most three kernel launches for the whole group.  One choice is made per push rather than per listener: the
     push takes the yaw rule when no listener has a pitch or a roll, otherwise every listener goes through the three-axis rotation.
-    Filters [len x numChannels] or [numSets x len x numChannels]; everything else as BinauralDecodeStream.  1 <= numListeners <= 4096."""
+    Filters [len x numChannels] or [numSets x len x numChannels]; everything else as BinauralDecodeStream.  1 <= numListeners <= 4096.
+    With encoder [numChannels x numMics] the common block is one of real microphone signals [n x numMics], encoded inside the
+    rotation launch: listener l equals, bit for bit, an encoded BinauralDecodeStream of its own."""
 
     def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition="real", rotationDomain="sh",
-                 complexInput=False):
+                 complexInput=False, encoder=None):
         self._h = None
         self._basis, self._cb = _basis(shDefinition)
         self._layout = _layout(rotationDomain)
@@ -784,10 +824,19 @@ class BinauralDecodeGroup:
         else:
             ln, self.numChannels = wL.shape
         self.blockSize, self.numListeners, self.complexInput = int(blockSize), int(numListeners), bool(complexInput)
+        self.numMics = None
         h = C.c_void_p()
-        L.check(L.load().emagls_decode_group_create(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
-                                                    wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
-                                                    self._layout, self._basis, self.blockSize, self.numListeners, C.byref(h)))
+        if encoder is not None:
+            if complexInput:
+                raise ValueError("an encoded group takes real microphone blocks: complexInput must be False")
+            enc, pe, e_c, self.numMics = _encoder(encoder, self.numChannels)
+            L.check(L.load().emagls_decode_group_create_encoded(self.numMics, pe, 1 if e_c else 0, self.numChannels, self.numSets,
+                                                                wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0,
+                                                                ln, self._layout, self._basis, self.blockSize, self.numListeners, C.byref(h)))
+        else:
+            L.check(L.load().emagls_decode_group_create(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
+                                                        wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
+                                                        self._layout, self._basis, self.blockSize, self.numListeners, C.byref(h)))
         self._h = h
 
     def info(self):
@@ -802,7 +851,10 @@ class BinauralDecodeGroup:
         return self._h
 
     def _check_block(self, shape, ndim):
-        if ndim != 2 or shape[1] != self.numChannels:
+        if self.numMics is not None:
+            if ndim != 2 or shape[1] != self.numMics:
+                raise ValueError("block must be [numSamples x numMics] matching the encoder's microphone count (%d)" % self.numMics)
+        elif ndim != 2 or shape[1] != self.numChannels:
             raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
         if shape[0] % self.blockSize:
             raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
@@ -834,6 +886,8 @@ class BinauralDecodeGroup:
         h = self._handle()
         if type(block).__module__.split(".")[0] == "torch":
             return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
+        if self.numMics is not None:
+            _real_mic_block(np.iscomplexobj(block), "group")
         if np.iscomplexobj(block) and not self.complexInput:
             raise ValueError("the group was created for real blocks (complexInput=False)")
         x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
@@ -865,6 +919,8 @@ class BinauralDecodeGroup:
         n = self._check_block(tuple(block.shape), block.dim())
         if not block.is_cuda:
             raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        if self.numMics is not None:
+            _real_mic_block(block.is_complex(), "group")
         if block.is_complex() and not self.complexInput:
             raise ValueError("the group was created for real blocks (complexInput=False)")
         xt = block.to(torch.complex128 if self.complexInput else torch.float64).t().contiguous()   # [numChannels][n]
@@ -1074,6 +1130,41 @@ def encodeSH(smaRecording, micGridAziRad, micGridZenRad, order, shDefinition="re
     out, po = _out(n, (int(order) + 1) ** 2, cplx)
     L.check(L.load().emagls_sh_encode(ps, n, M, pa, pz, int(order), b, po))
     return out
+
+
+def arrayEncoder(kind, order, micGridAziRad, micGridZenRad=None, shDefinition="real"):
+    """The encoder matrix [numChannels x numMics] of an array, for BinauralDecodeStream / BinauralDecodeGroup(encoder=...):
+    block @ arrayEncoder(...).T is the encoded signal.
+      'sma'     pinv(getSH(order, mics).T).T: the matrix encodeSH applies (verifyEMagLs.m:235-236), (order+1)^2 channels
+      'ema_ch'  pinv(getCH(order, micAzi).T).T: an equatorial array in circular harmonics (testEMagLs.m:98-105), 2 order + 1 channels
+      'ema_sh'  J @ the 'ema_ch' encoder, J [(order+1)^2 x (2 order + 1)] the CH -> SH expansion of
+                dependencies/getChToShExpansionMatrix.m: J[(n, m), m] = Y_n^m(pi/2, 0) / C_m(0) in the basis' own normalisation,
+                formed from getSH at the zenith pi/2 over getCH."""
+    N = int(order)
+    azi = np.asarray(micGridAziRad, dtype=np.float64).ravel()
+    if kind == "sma":
+        if micGridZenRad is None:
+            raise ValueError("an 'sma' encoder needs micGridZenRad")
+        zen = np.asarray(micGridZenRad, dtype=np.float64).ravel()
+        if zen.size != azi.size:
+            raise ValueError("micGridZenRad must have %d elements, got %d" % (azi.size, zen.size))
+        return np.linalg.pinv(getSH(N, np.column_stack([azi, zen]), shDefinition).T).T
+    if kind not in ("ema_ch", "ema_sh"):
+        raise ValueError("kind must be 'sma', 'ema_ch' or 'ema_sh'")
+    enc = np.linalg.pinv(getCH(N, azi, shDefinition).T).T
+    if kind == "ema_ch":
+        return enc
+    # Y_n^m(pi/2, a) = J[(n, m), m] C_m(a) for every a: one direction gives the ratio; in the real basis the direction is chosen
+    # so that neither cos(m a) nor sin(m a) vanishes for m <= order
+    a0 = 0.0 if shDefinition == "complex" else math.pi / (4 * N + 2)
+    Y = getSH(N, np.array([[a0, math.pi / 2]]), shDefinition)[0]
+    Cm = getCH(N, np.array([a0]), shDefinition)[0]
+    J = np.zeros(((N + 1) ** 2, 2 * N + 1), dtype=Y.dtype)
+    for n in range(N + 1):
+        for m in range(-n, n + 1):
+            col = 0 if m == 0 else (2 * m if m > 0 else -2 * m - 1)     # CH order [C_0, C_-1, C_1, ..., C_-N, C_N]
+            J[n * n + n + m, col] = Y[n * n + n + m] / Cm[col]
+    return J @ enc
 
 
 def getMagLsSphericalHeadFilter(micRadius, order, fs, len):

@@ -174,6 +174,16 @@ void launch_rotation(const Angles& a, const void* in, bool in_c, int64_t n, int 
                        a.n_roll ? a.roll : nullptr, a.n_roll > 1, transpose, out, st, ld_in, ld_out, L, la, lo);
 }
 
+// the same on the microphone block of an encoded stream: the encoder runs inside the rotation launch
+void launch_rotation_encoded(const Angles& a, const EncodeBlock& e, int64_t n, int nch, int layout, bool cb, void* out, hipStream_t st,
+                             int64_t ld_out, int L = 1, const int64_t* la = nullptr, int64_t lo = 0) {
+    if (a.yaw_only())
+        launch_rotate_yaw_encoded(e, n, nch, layout, cb, a.yaw, a.n_yaw > 1, out, st, ld_out, L, la ? la[0] : 0, lo);
+    else
+        launch_rotate3_encoded(e, n, nch, cb, a.n_yaw ? a.yaw : nullptr, a.n_yaw > 1, a.n_pitch ? a.pitch : nullptr, a.n_pitch > 1,
+                               a.n_roll ? a.roll : nullptr, a.n_roll > 1, out, st, ld_out, L, la, lo);
+}
+
 // The rotation before the decode.  A fixed one (every count <= 1) turns the decoding filters, sum_i w_i * (x Rot^T)_i =
 // sum_j (w Rot)_j * x_j; a trajectory is a pass over the signal into ROT_SIG.  The operands it replaces
 // are complex from here on in the complex basis.  (g_work.mu held)
@@ -489,7 +499,10 @@ struct emagls_decode_stream {
     std::mutex mu;
     int64_t nch = 0, len = 0;
     int layout = 0, basis = 0;
-    bool in_c = false;
+    bool in_c = false;            // the signal the rotation and the filters meet is complex (an encoded stream: its encoder is)
+    int64_t nmics = 0;            // an encoded stream: the microphones of a pushed block; 0: blocks are SH / CH
+    std::vector<double> enc_host; // [nch][nmics] row-major, interleaved complex when in_c
+    double* enc = nullptr;        // its device copy, owned like the spectra
     int device = -1;              // bound at the first use of the device (creation, when there is one)
     bool ready = false;
     std::vector<double> wpl;      // [S][2][Cp][len] the real filter planes [re w; -im w], until the device has their spectra
@@ -500,17 +513,22 @@ struct emagls_decode_stream {
     int known[2] = {-1, -1};      // what the host knows of the selection state on the device: the set indices of the two previous
                                   // blocks, -1: none yet, -2: not known (a push took its indices from device memory)
     int cp() const { return d.planes2 ? 2 * d.C : d.C; }
+    // a pushed block: [nsamp x block_cols()], complex when block_c()
+    int64_t block_cols() const { return nmics ? nmics : nch; }
+    bool block_c() const { return nmics ? false : in_c; }
+    size_t enc_bytes() const { return sizeof(double) * enc_host.size(); }
     // per listener:
     size_t ring_bytes() const { return sizeof(cplx) * 2 * (size_t)d.P * (d.B + 1); }
     size_t hist_bytes() const { return esz(d.planes2) * (size_t)d.C * d.B; }
     size_t pos_bytes() const { return sizeof(int) * (d.S > 1 ? 3 : 1); }   // the ring position; with a bank, the two previous set indices
     size_t state_bytes() const { return (size_t)d.L * (ring_bytes() + hist_bytes() + pos_bytes()); }
     // once, whatever the number of listeners:
-    size_t filter_bytes() const { return sizeof(cplx) * (size_t)d.S * 2 * (size_t)d.P * cp() * (d.B + 1); }
+    size_t filter_bytes() const { return sizeof(cplx) * (size_t)d.S * 2 * (size_t)d.P * cp() * (d.B + 1) + enc_bytes(); }
+    size_t spectra_bytes() const { return filter_bytes() - enc_bytes(); }
     void release() {
-        hipFree(d.Wf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos); hipFree(xrot);
+        hipFree(d.Wf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos); hipFree(xrot); hipFree(enc);
         for (void*& p : stage) { hipFree(p); p = nullptr; }
-        d.Wf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr; xrot = nullptr;
+        d.Wf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr; xrot = nullptr; enc = nullptr;
         ready = false;
     }
     // the listeners first .. first + count - 1 back to a fresh stream's state
@@ -528,12 +546,16 @@ struct emagls_decode_stream {
         if (ready) return;
         HIP_CHECK(hipGetDevice(&device));
         try {
-            HIP_CHECK(hipMalloc(&d.Wf, filter_bytes()));
+            HIP_CHECK(hipMalloc(&d.Wf, spectra_bytes()));
             HIP_CHECK(hipMalloc(&d.ring, d.L * ring_bytes()));
             HIP_CHECK(hipMalloc(&d.hist, d.L * hist_bytes()));
             HIP_CHECK(hipMalloc(&d.pos, d.L * pos_bytes()));
             HIP_CHECK(hipMalloc(&xrot, esz(d.planes2) * (size_t)d.L * d.C * d.B));   // (a rotated block is complex exactly when planes2)
             Scratch s;
+            if (nmics) {
+                HIP_CHECK(hipMalloc(&enc, enc_bytes()));
+                HIP_CHECK(hipMemcpyAsync(enc, enc_host.data(), enc_bytes(), hipMemcpyHostToDevice, s.st));
+            }
             launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.S, d.Wf, s.st);
             zero_state(s.st, 0, d.L);
             HIP_CHECK(hipStreamSynchronize(s.st));
@@ -575,12 +597,17 @@ void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp
     const bool cb = s->basis == EMAGLS_BASIS_COMPLEX;
     auto at = [&](const double* p, int64_t n, int64_t b) { return n > 1 ? p + b * B : p; };
     for (int64_t b = 0; b < nsamp / B; ++b) {
-        const void* x = (const char*)d_in + esz(s->in_c) * (size_t)(b * B);
+        const void* x = (const char*)d_in + esz(s->block_c()) * (size_t)(b * B);
         bool x_c = s->in_c;
         int64_t ldx = nsamp;
-        if (a.any()) {
-            const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
-                             at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
+        const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
+                         at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
+        if (s->nmics) {   // the encoder inside the rotation launch; without angles, alone: xrot is written either way
+            const EncodeBlock e{s->enc, s->in_c, (int)s->nmics, (const double*)x, nsamp};
+            if (a.any()) launch_rotation_encoded(blk, e, B, (int)s->nch, s->layout, cb, s->xrot, st, B);
+            else launch_encode_block(e, B, (int)s->nch, s->xrot, B, st);
+            x = s->xrot; x_c = x_c || (a.any() && cb); ldx = B;
+        } else if (a.any()) {
             launch_rotation(blk, x, x_c, B, (int)s->nch, s->layout, cb, false, s->xrot, st, nsamp, B);
             x = s->xrot; x_c = x_c || cb; ldx = B;
         }
@@ -600,9 +627,11 @@ void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp
 
 
 // The creation of a stream or of a listener group (T), every argument checked before the device is touched
+// nmics > 0: an encoded stream, enc [nch x nmics] column-major (interleaved complex when in_is_complex, which then says what the
+// ENCODED signal is; the pushed microphone blocks are real)
 template <typename T>
 T* stream_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
-                 int layout, int basis, int64_t block, int64_t listeners) {
+                 int layout, int basis, int64_t block, int64_t listeners, int64_t nmics = 0, const void* enc = nullptr) {
     if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
     if (n_sets < 1) throw Error(EMAGLS_ERR_ARG, "a decode stream needs at least one filter set");
     if (n_sets > kDecodeStreamMaxSets) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports banks of up to 65536 filter sets");
@@ -618,6 +647,15 @@ T* stream_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, in
     s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block); s->d.S = (int)n_sets; s->d.L = (int)listeners;
     // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
     s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
+    if (nmics > 0) {
+        const int k = s->in_c ? 2 : 1;
+        const double* e = reinterpret_cast<const double*>(enc);
+        s->nmics = nmics;
+        s->enc_host.resize((size_t)nch * nmics * k);
+        for (int64_t c = 0; c < nch; ++c)
+            for (int64_t m = 0; m < nmics; ++m)
+                for (int i = 0; i < k; ++i) s->enc_host[(size_t)(c * nmics + m) * k + i] = e[(size_t)(m * nch + c) * k + i];
+    }
     const int Cp = s->cp();
     const bool wc = filters_are_complex != 0;
     s->wpl.assign((size_t)n_sets * 2 * Cp * len, 0.0);
@@ -677,12 +715,17 @@ void group_push_blocks(emagls_decode_group* g, const void* d_in, int64_t nsamp, 
     const int64_t la[3] = {a.n_yaw > 1 ? nsamp : 1, a.n_pitch > 1 ? nsamp : 1, a.n_roll > 1 ? nsamp : 1};
     auto at = [&](const double* q, int64_t n, int64_t b) { return n > 1 ? q + b * B : q; };
     for (int64_t b = 0; b < nb; ++b) {
-        const void* x = (const char*)d_in + esz(g->in_c) * (size_t)(b * B);
+        const void* x = (const char*)d_in + esz(g->block_c()) * (size_t)(b * B);
         bool x_c = g->in_c;
         int64_t ldx = nsamp, lsx = 0;   // without angles every listener reads the common block
-        if (a.any()) {
-            const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
-                             at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
+        const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
+                         at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
+        if (g->nmics) {   // every listener's workgroups encode the common block themselves; without angles it is encoded once
+            const EncodeBlock e{g->enc, g->in_c, (int)g->nmics, (const double*)x, nsamp};
+            if (a.any()) launch_rotation_encoded(blk, e, B, (int)g->nch, g->layout, cb, g->xrot, st, B, g->d.L, la, C * B);
+            else launch_encode_block(e, B, (int)g->nch, g->xrot, B, st);
+            x = g->xrot; x_c = x_c || (a.any() && cb); ldx = B; lsx = a.any() ? C * B : 0;
+        } else if (a.any()) {
             launch_rotation(blk, x, x_c, B, (int)g->nch, g->layout, cb, false, g->xrot, st, nsamp, B, g->d.L, la, C * B);
             x = g->xrot; x_c = x_c || cb; ldx = B; lsx = C * B;
         }
@@ -707,6 +750,35 @@ int emagls_decode_stream_create_bank(int64_t nch, int64_t n_sets, const void* wL
         if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
         *out = nullptr;
         *out = stream_create<emagls_decode_stream>(nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, 1);
+    });
+}
+
+static void check_encoder(int64_t nmics, const void* enc, int64_t nch) {
+    if (nmics < 1 || nmics > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "an encoded decode stream supports 1 to 64 microphones");
+    if (nch < 1 || nch > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "an encoded decode stream supports 1 to 64 channels");
+    if (!enc) throw Error(EMAGLS_ERR_ARG, "null pointer");
+}
+
+int emagls_decode_stream_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
+                                        const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
+                                        emagls_decode_stream** out) {
+    return guarded_call([&] {
+        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *out = nullptr;
+        check_encoder(nmics, enc, nch);
+        *out = stream_create<emagls_decode_stream>(nch, n_sets, wL, wR, filters_are_complex, len, enc_is_complex, layout, basis, block, 1, nmics, enc);
+    });
+}
+
+int emagls_decode_group_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
+                                       const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
+                                       int64_t n_listeners, emagls_decode_group** out) {
+    return guarded_call([&] {
+        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *out = nullptr;
+        check_encoder(nmics, enc, nch);
+        *out = stream_create<emagls_decode_group>(nch, n_sets, wL, wR, filters_are_complex, len, enc_is_complex, layout, basis, block, n_listeners,
+                                                  nmics, enc);
     });
 }
 
@@ -751,7 +823,7 @@ int emagls_decode_stream_push_sets(emagls_decode_stream* s, const void* in, int6
         s->ensure_device();
         hipStream_t st = pool_stream_take();
         struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
-        const size_t bin = esz(s->in_c) * (size_t)nsamp * s->nch;
+        const size_t bin = esz(s->block_c()) * (size_t)nsamp * s->block_cols();
         char* d_in = s->staged<char>(0, bin);
         double* d_ang = s->staged<double>(1, sizeof(double) * 3 * (size_t)nsamp);
         double* d_out = s->staged<double>(2, sizeof(double) * 2 * (size_t)nsamp);
@@ -795,7 +867,7 @@ int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int
         if (partitions) *partitions = s->d.P;
         if (state_bytes) *state_bytes = (int64_t)s->state_bytes();
         if (filter_bytes) *filter_bytes = (int64_t)s->filter_bytes();
-        if (launches_per_block) *launches_per_block = 3;   // rotation, forward transform with the products, inverse transform
+        if (launches_per_block) *launches_per_block = 3;   // rotation (encoded: with the encoder, or the encoder alone), forward transform with the products, inverse transform
     });
 }
 
@@ -863,7 +935,7 @@ int emagls_decode_group_push(emagls_decode_group* g, const void* in, int64_t nsa
         g->ensure_device();
         hipStream_t st = pool_stream_take();
         struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
-        const size_t L = (size_t)g->d.L, bin = esz(g->in_c) * (size_t)nsamp * g->nch;
+        const size_t L = (size_t)g->d.L, bin = esz(g->block_c()) * (size_t)nsamp * g->block_cols();
         char* d_in = g->staged<char>(0, bin);
         double* d_ang = g->staged<double>(1, sizeof(double) * 3 * L * (size_t)nsamp);
         double* d_out = g->staged<double>(2, sizeof(double) * 2 * L * (size_t)nsamp);

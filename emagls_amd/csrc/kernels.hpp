@@ -228,6 +228,18 @@ void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_ba
 // M [(N+1)^2 x (N+1)^2] column-major, out_row = in_row M^T; the same device code as launch_rotate3
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st);
 void rotate3_cache_clear();
+// ---- the ENC forms of the two rotations (encode_tile.hpp): the array encoder of an encoded decode stream
+// inside the rotation launch.  enc [C][M] device, row-major (interleaved complex when enc_cplx), 1 <= M, C <= 64; x: the real
+// microphone block, microphone m at x + m ldx.  The encoded signal s_c[t] = sum_m enc[c][m] x[m][t] (fma from 0, m ascending;
+// complex when enc_cplx) is what the rotation turns: out, ld_out, L, la, lo as in launch_rotate_yaw / launch_rotate3.
+struct EncodeBlock { const double* enc; bool enc_cplx; int M; const double* x; int64_t ldx; };
+void launch_rotate_yaw_encoded(const EncodeBlock& e, int64_t n, int C, int layout, bool cplx_basis, const double* yaw, bool per_sample, void* out,
+                               hipStream_t st, int64_t ld_out = 0, int L = 1, int64_t la = 0, int64_t lo = 0);
+void launch_rotate3_encoded(const EncodeBlock& e, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch, bool pitch_ps,
+                            const double* roll, bool roll_ps, void* out, hipStream_t st, int64_t ld_out = 0, int L = 1, const int64_t* la = nullptr,
+                            int64_t lo = 0);
+// the encoder alone: out [C][ld_out] = the encoded block (complex when enc_cplx)
+void launch_encode_block(const EncodeBlock& e, int64_t n, int C, void* out, int64_t ld_out, hipStream_t st);
 // ---- resample.hip
 constexpr int64_t kResampleMaxRatio = 65536;   // the largest max(p, q) after reduction
 int64_t resample_length(int64_t n, int64_t p, int64_t q);   // ceil(n p / q)

@@ -12,6 +12,7 @@
 // The transposed form (w M instead of x M^T, for decoding filters): M^T = Z(-g) J Z(-b) J^T Z(-a) in the real basis and
 // U M_r^T U^H in the complex one, i.e. the same code with (a, b, g) -> (-g, -b, -a) and the conversions conjugated.
 #include "kernels.hpp"
+#include "encode_tile.hpp"
 
 namespace emagls {
 
@@ -277,6 +278,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(r3_wav
     }
 }
 
+// The ENC form (encode_tile.hpp): the workgroup encodes its tile of ENC_T samples of the microphone block
+// into LDS and its first ENC_T lanes turn the tile from there, one sample each, through the same rot_orders as the kernel above.
+// EC: complex encoder, so a complex encoded signal.  grid (n / ENC_T, L); dynamic LDS enc_lds_bytes(C, M, EC, true) beside J
+template <int NB, bool EC, bool CB>
+__global__ void __launch_bounds__(ENC_NT) __attribute__((amdgpu_waves_per_eu(r3_waves(NB, EC || CB)))) rotate3_enc_kernel(int N, EncIn e, int C, int64_t n, const double* __restrict__ yaw, int yps,
+                                                      const double* __restrict__ pitch, int pps, const double* __restrict__ roll, int rps,
+                                                      const double* __restrict__ jpk, void* __restrict__ out_, int64_t ldo, R3Listener ls) {
+    using TI = std::conditional_t<EC, cplx, double>;
+    using V = std::conditional_t<EC || CB, cplx, double>;
+    __shared__ double J[jpk_off(NB + 1)];
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    TI* enc_s = reinterpret_cast<TI*>(dyn);
+    TI* tile = enc_s + C * e.M;   // [C][ENC_T]
+    for (int i = threadIdx.x; i < jpk_off(N + 1); i += ENC_NT) J[i] = jpk[i];   // (the barriers of encode_tile cover it)
+    const int64_t t0 = (int64_t)blockIdx.x * ENC_T;
+    encode_tile<EC>(e, C, t0, n, enc_s, [&](int c, int t, TI v) { tile[c * ENC_T + t] = v; });
+    __syncthreads();
+    const int tl = threadIdx.x;
+    const int64_t t = t0 + tl;
+    if (tl >= ENC_T || t >= n) return;
+    const int64_t lis = blockIdx.y;   // the listener
+    V* __restrict__ out = reinterpret_cast<V*>(out_) + lis * ls.lo;
+    const int64_t oy = lis * ls.la[0], op = lis * ls.la[1], orl = lis * ls.la[2];
+    const Ang a = zyz(yaw ? yaw[oy + (yps ? t : 0)] : 0.0, pitch ? pitch[op + (pps ? t : 0)] : 0.0, roll ? roll[orl + (rps ? t : 0)] : 0.0, false);
+    rot_orders<0, NB, CB, V>(N, J, a, [&](int k) { return to_v(tile[k * ENC_T + tl], (V*)nullptr); },
+                            [&](int k, V v) { out[(int64_t)k * ldo + t] = v; });
+}
+
 // the matrix M itself, column j = the pass applied to e_j: out [(N+1)^2 x (N+1)^2] column-major, out_row = in_row M^T
 template <int NB, bool CB>
 __global__ void __launch_bounds__(256) rotate3_matrix_kernel(int N, double yaw, double pitch, double roll, const double* __restrict__ jpk,
@@ -323,6 +352,24 @@ template <int NB> void launch_nb(int N, const void* in, bool ic, int64_t n, bool
     KERNEL_CHECK();
 }
 
+template <int NB> void launch_nb_enc(int N, const EncodeBlock& e, int C, int64_t n, bool cb, const double* yaw, bool yps, const double* pitch, bool pps,
+                                    const double* roll, bool rps, const double* jpk, void* out, hipStream_t st, int64_t ldo, int L, const R3Listener& ls) {
+    static PerDeviceOnce once;
+    if (once.first()) {
+#define EMAGLS_R3_ATTR(K) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024))
+        EMAGLS_R3_ATTR((rotate3_enc_kernel<NB, true, true>));
+        EMAGLS_R3_ATTR((rotate3_enc_kernel<NB, true, false>));
+        EMAGLS_R3_ATTR((rotate3_enc_kernel<NB, false, true>));
+        EMAGLS_R3_ATTR((rotate3_enc_kernel<NB, false, false>));
+#undef EMAGLS_R3_ATTR
+    }
+    const dim3 grid((unsigned)ceil_div(n, ENC_T), (unsigned)L);
+    auto k = e.enc_cplx ? (cb ? rotate3_enc_kernel<NB, true, true> : rotate3_enc_kernel<NB, true, false>)
+                        : (cb ? rotate3_enc_kernel<NB, false, true> : rotate3_enc_kernel<NB, false, false>);
+    k<<<grid, ENC_NT, enc_lds_bytes(C, e.M, e.enc_cplx, true), st>>>(N, EncIn{e.enc, e.M, e.x, e.ldx}, C, n, yaw, yps, pitch, pps, roll, rps, jpk, out, ldo, ls);
+    KERNEL_CHECK();
+}
+
 template <int NB> void launch_mat(int N, bool cb, double yaw, double pitch, double roll, const double* jpk, void* out, hipStream_t st) {
     const unsigned grid = (unsigned)ceil_div((N + 1) * (N + 1), 256);
     if (cb) rotate3_matrix_kernel<NB, true><<<grid, 256, 0, st>>>(N, yaw, pitch, roll, jpk, out);
@@ -352,6 +399,20 @@ void launch_rotate3(const void* in, bool in_cplx, int64_t n, int C, bool cplx_ba
     else if (N <= 4) launch_nb<4>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
     else if (N <= 8) launch_nb<8>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
     else launch_nb<R3_NMAX>(N, in, in_cplx, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, transpose, jpk, out, st, ldi, ldo, L, ls);
+}
+
+void launch_rotate3_encoded(const EncodeBlock& e, int64_t n, int C, bool cplx_basis, const double* yaw, bool yaw_ps, const double* pitch, bool pitch_ps,
+                            const double* roll, bool roll_ps, void* out, hipStream_t st, int64_t ld_out, int L, const int64_t* la, int64_t lo) {
+    if (n <= 0) return;
+    if (e.M < 1 || e.M > ENC_MAX || C > ENC_MAX) throw Error(2, "the stream's encoder supports 1 to 64 microphones and 1 to 64 channels");
+    const int64_t ldo = ld_out ? ld_out : n;
+    const int N = rotate_order(0, C);
+    check_order(N);
+    const double* jpk = j_pack(st);
+    const R3Listener ls{{la ? la[0] : 0, la ? la[1] : 0, la ? la[2] : 0}, lo};
+    if (N <= 2) launch_nb_enc<2>(N, e, C, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, jpk, out, st, ldo, L, ls);
+    else if (N <= 4) launch_nb_enc<4>(N, e, C, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, jpk, out, st, ldo, L, ls);
+    else launch_nb_enc<8>(N, e, C, n, cplx_basis, yaw, yaw_ps, pitch, pitch_ps, roll, roll_ps, jpk, out, st, ldo, L, ls);   // (C <= 64: N <= 7)
 }
 
 void launch_rotate3_matrix(int N, bool cplx_basis, double yaw, double pitch, double roll, void* out, hipStream_t st) {

@@ -411,6 +411,29 @@ int emagls_decode_group_info(const emagls_decode_group* g, int64_t* block, int64
 
 int emagls_decode_group_destroy(emagls_decode_group* g);
 
+/* ---- the array encoder inside a decode stream or a listener group ----
+ * An ENCODED stream (group) is created with an encoder matrix enc [nch x nmics] (column-major like every array here; interleaved
+ * complex when enc_is_complex) and is pushed blocks of REAL microphone signals [nsamp x nmics]: the push, push_sets, push_device,
+ * push_sets_device and group_push entries above take such blocks on an encoded object, and reset, info, sets and destroy are
+ * shared.  DEFINING PROPERTY: its outputs equal, to rounding, those of the stream (group) of the same filters, bank, angles and set
+ * indices that is fed x enc^T; a complex enc makes the encoded signal complex, and the stream then runs as one created with
+ * in_is_complex.  The encoder runs inside the rotation launch (a push without angles runs it alone), so a block is still at most
+ * three launches: the head rotation sits between the encoder and the filters, which is why a head-tracked renderer cannot fold enc
+ * into its filters (one that never turns can: w'_m = sum_c enc[c, m] w_c, and a plain stream on nmics channels).
+ * The arithmetic is fixed: s_c[t] = sum_m enc[c, m] x[m][t], accumulated from 0 with fma, m ascending, in FP64, the real and the
+ * imaginary part as separate chains.  So an identity encoder returns the bits of the plain stream, listener l of an encoded group
+ * the bits of an encoded stream, and pushes of one block the bits of pushes of several.
+ * 1 <= nmics <= 64 and 1 <= nch <= 64, else EMAGLS_ERR_UNSUPPORTED; nch > nmics is allowed.  A null enc is EMAGLS_ERR_ARG.  nch is
+ * the channel count of the filters and of the rotation: a CH layout takes yaw only, pitch or roll needs nch = (N+1)^2.  Everything
+ * else as emagls_decode_stream_create_bank / emagls_decode_group_create.  enc is copied at creation and owned by the object
+ * (emagls_cache_clear() leaves it alone); info counts it in filter_bytes. */
+int emagls_decode_stream_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
+                                        const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
+                                        emagls_decode_stream** s);
+int emagls_decode_group_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
+                                       const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
+                                       int64_t n_listeners, emagls_decode_group** g);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

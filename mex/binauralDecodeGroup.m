@@ -1,7 +1,7 @@
 classdef binauralDecodeGroup < handle
 % Many listeners of one sound field in one push on the GPU (DESIGN.md section 9.5): one bank of filter sets, stored once, and
 % numListeners listeners, each with the state a binauralDecodeStream has.
-%   g = binauralDecodeGroup(decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition, rotationDomain, complexInput)
+%   g = binauralDecodeGroup(decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition, rotationDomain, complexInput, encoder)
 %   out = g.push(block, horRotAngleRad, pitchRad, rollRad, setIndex)    block [k*blockSize x numChannels], the common signal
 %   g.reset()  every listener back to zero history     g.reset(l)  listener l alone (who joins)     delete(g)
 % Listeners run along the LAST dimension: out [k*blockSize x 2 x numListeners]; each angle [] (0), [1 x numListeners] (constant
@@ -18,10 +18,11 @@ classdef binauralDecodeGroup < handle
         numListeners
     end
     methods
-        function g = binauralDecodeGroup(decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition, rotationDomain, complexInput)
+        function g = binauralDecodeGroup(decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition, rotationDomain, complexInput, encoder)
             if nargin < 5; shDefinition = 'real'; end
             if nargin < 6; rotationDomain = 'sh'; end
             if nargin < 7; complexInput = false; end
+            if nargin < 8; encoder = []; end   % [numChannels x numMics]: the common block is one of real microphone signals (DESIGN.md 9.6)
             if isreal(decodingFilterLeft) ~= isreal(decodingFilterRight)
                 decodingFilterLeft = complex(decodingFilterLeft); decodingFilterRight = complex(decodingFilterRight);
             end
@@ -29,7 +30,7 @@ classdef binauralDecodeGroup < handle
             g.numSets = size(decodingFilterLeft, 3);
             g.numListeners = numListeners;
             g.handle = emagls_mex('group_create', double(decodingFilterLeft), double(decodingFilterRight), double(blockSize), ...
-                                  double(numListeners), shDefinition, rotationDomain, logical(complexInput));
+                                  double(numListeners), shDefinition, rotationDomain, logical(complexInput), double(encoder));
         end
         function out = push(g, block, horRotAngleRad, pitchRad, rollRad, setIndex)
             if nargin < 3; horRotAngleRad = []; end

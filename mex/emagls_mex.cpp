@@ -103,6 +103,15 @@ FilterArgs filter_args(const mxArray* const* prhs) {
     if (f.wc != (bool)mxIsComplex(prhs[2])) mexErrMsgIdAndTxt("eMagLS:arg", "the two decoding filters must both be real or both complex");
     return f;
 }
+// the optional encoder of 'stream_create' / 'group_create' (DESIGN.md section 9.6): [] or absent: none; else [numChannels x numMics],
+// real or complex -- column-major, as the library takes it.  Returns the microphone count (0: none)
+mwSize encoder_arg(const mxArray* a, mwSize ch, bool complex_input) {
+    if (!a || mxIsEmpty(a)) return 0;
+    if (!mxIsDouble(a) || mxGetNumberOfDimensions(a) > 2 || mxGetM(a) != ch)
+        mexErrMsgIdAndTxt("eMagLS:arg", "encoder must be a double [numChannels x numMics] array with the filters' channel count (%d) of rows", (int)ch);
+    if (complex_input) mexErrMsgIdAndTxt("eMagLS:arg", "an encoder takes real microphone blocks: complexInput must be false");
+    return mxGetN(a);
+}
 bool truthy(const mxArray* a) { return mxIsLogicalScalarTrue(a) || (mxIsDouble(a) && !mxIsEmpty(a) && mxGetScalar(a) != 0); }
 // a ONE-based set index array as the library's zero-based int32
 std::vector<int32_t> zero_based(const mxArray* a) {
@@ -134,8 +143,9 @@ void at_exit() {
 // emagls_mex('emainch' | 'emainsh', hL, hR, azi, zen, micRadius, micAzi, order, fs, len, shDefinition)
 // emagls_mex('magls_dc' | 'emagls_dc' | 'emagls2_dc', <the arguments of 'magls' / 'emagls' / 'emagls2'>, applyDiffusenessConst)
 // emagls_mex('decode',  in, wL, wR, compensateDelay[, yawRad, signal, shDefinition, domain, pitchRad, rollRad])   real or complex in / filters; [out, imagAbsSum] = ...
-// h = emagls_mex('stream_create', wL, wR, blockSize[, shDefinition, domain, complexInput])   a decode stream (mex/binauralDecodeStream.m);
-//                                     wL / wR [len x nch], or [len x nch x numSets]: a bank of filter sets
+// h = emagls_mex('stream_create', wL, wR, blockSize[, shDefinition, domain, complexInput, encoder])   a decode stream (mex/binauralDecodeStream.m);
+//                                     wL / wR [len x nch], or [len x nch x numSets]: a bank of filter sets; encoder [nch x numMics]: the
+//                                     stream is pushed real microphone blocks [n x numMics] (also on 'group_create', after complexInput)
 // out = emagls_mex('stream_push', h, in[, yawRad, pitchRad, rollRad, setIndex])   in [k*blockSize x nch]; each angle [], a scalar or one per
 //                                     sample; setIndex ONE-based: [] (keep the set), a scalar or one per block
 // emagls_mex('stream_reset', h)      emagls_mex('stream_destroy', h)
@@ -213,15 +223,19 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const bool wc = f.wc;
         const int basis = basis_of(nrhs > 4 ? prhs[4] : nullptr), layout = layout_of(nrhs > 5 ? prhs[5] : nullptr);
         const int ic = nrhs > 6 && truthy(prhs[6]);
+        const mxArray* enc = nrhs > 7 ? prhs[7] : nullptr;
+        const mwSize nmics = encoder_arg(enc, ch, ic != 0);
         emagls_decode_stream* st = nullptr;
-        const int rc = emagls_decode_stream_create_bank((int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic,
-                                                        layout, basis, (int64_t)mxGetScalar(prhs[3]), &st);
+        const int rc = nmics ? emagls_decode_stream_create_encoded((int64_t)nmics, in_ptr(enc), mxIsComplex(enc), (int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]),
+                                                                   in_ptr(prhs[2]), wc, (int64_t)len, layout, basis, (int64_t)mxGetScalar(prhs[3]), &st)
+                             : emagls_decode_stream_create_bank((int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic,
+                                                                layout, basis, (int64_t)mxGetScalar(prhs[3]), &st);
         if (rc) fail(rc);
         size_t slot = 0;
         while (slot < g_streams.size() && g_streams[slot]) ++slot;
         if (slot == g_streams.size()) { g_streams.push_back(nullptr); g_stream_shapes.push_back({0, false}); }
         g_streams[slot] = st;
-        g_stream_shapes[slot] = {ch, ic != 0};
+        g_stream_shapes[slot] = {nmics ? nmics : ch, ic != 0};   // (an encoded stream is pushed [n x numMics] blocks)
         plhs[0] = mxCreateDoubleScalar((double)(slot + 1));
         return;
     }
@@ -264,15 +278,19 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const int ic = nrhs > 7 && truthy(prhs[7]);
         const double nl = mxGetScalar(prhs[4]);
         if (!(nl == std::floor(nl)) || std::fabs(nl) > 1e9) mexErrMsgIdAndTxt("eMagLS:arg", "numListeners must be an integer");
+        const mxArray* enc = nrhs > 8 ? prhs[8] : nullptr;
+        const mwSize nmics = encoder_arg(enc, f.ch, ic != 0);
         emagls_decode_group* g = nullptr;
-        const int rc = emagls_decode_group_create((int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc, (int64_t)f.len, ic, layout,
-                                                  basis, (int64_t)mxGetScalar(prhs[3]), (int64_t)nl, &g);
+        const int rc = nmics ? emagls_decode_group_create_encoded((int64_t)nmics, in_ptr(enc), mxIsComplex(enc), (int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]),
+                                                                  in_ptr(prhs[2]), f.wc, (int64_t)f.len, layout, basis, (int64_t)mxGetScalar(prhs[3]), (int64_t)nl, &g)
+                             : emagls_decode_group_create((int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc, (int64_t)f.len, ic, layout,
+                                                          basis, (int64_t)mxGetScalar(prhs[3]), (int64_t)nl, &g);
         if (rc) fail(rc);
         size_t slot = 0;
         while (slot < g_groups.size() && g_groups[slot]) ++slot;
         if (slot == g_groups.size()) { g_groups.push_back(nullptr); g_group_shapes.push_back({0, false, 0}); }
         g_groups[slot] = g;
-        g_group_shapes[slot] = {f.ch, ic != 0, (mwSize)nl};
+        g_group_shapes[slot] = {nmics ? nmics : f.ch, ic != 0, (mwSize)nl};
         plhs[0] = mxCreateDoubleScalar((double)(slot + 1));
         return;
     }

@@ -11,6 +11,7 @@ Gates (exit status 1 when one fails): median (a) < median (b), and median (a) < 
     python tools/decode_stream_timing.py [--blocks 2000] [--warm 50] [--run 100] [--shapes 25,512,64 ...] [--stream-only]
                                          [--dry-run] [--out profiles/r10_decode_stream.md]
                                          [--bank [--sets 3]] [--group [--listeners 1 8 64 256] [--sets 1]]
+                                         [--encoded [--enc-shapes 32,25,512,64 ...] [--listeners 1 8 64]]
 --dry-run prints the shapes and the bytes a push moves, computed from the shapes, without a device.
 
 --bank times the bank of filter sets (emagls_decode_stream_create_bank / _push_sets_device) instead, without
@@ -39,6 +40,17 @@ memory).  --run pushes per run average (default 100), --blocks / --run run avera
 spread = p90 - p10 of the run averages.  Gates: L >= 8: median(loop) - median(group) > spread(loop) + spread(group); L == 1:
 median(group) <= median(loop) + spread(loop).  Also reported: loop / group, the listeners one device serves in real time at 48 kHz,
 block duration / (group time / L), and the traffic of a push of the whole group, from the shapes.
+
+--encoded times the encoder inside the stream (emagls_decode_stream_create_encoded / emagls_decode_group_create_encoded, DESIGN.md
+section 9.6) per shape (M, C, len, B) (--enc-shapes) and number of listeners (--listeners; 1: a stream), with three-axis
+trajectories, alternating in one process on one HIP stream:
+
+  encoded  the encoded stream (group) pushed the microphone block [M][B]
+  matmul   what a caller does without it: torch.matmul(enc, block) and a push of the result on a plain stream (group)
+  plain    the plain stream (group) alone, pushed an SH block: the instances this feature leaves untouched
+
+Median and spread = p90 - p10 of the run averages.  Expected, reported and not gated: median(matmul) - median(encoded) >
+spread(matmul) + spread(encoded) at the launch-bound shapes.
 """
 import argparse
 import ctypes as C
@@ -342,6 +354,85 @@ def group_markdown(rows, device):
     return "\n".join(lines) + "\n"
 
 
+def run_encoded_shape(lib, L, torch, M, Cc, ln, B, nl, blocks, warm, run):
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(M + Cc + ln + B + nl)
+    rnd = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)   # noqa: E731
+    wL, wR = rnd(Cc, ln), rnd(Cc, ln)                       # [C][len] row-major == [len x C] column-major
+    enc = rnd(Cc, M) / M ** 0.5                             # [C][M]; the library takes [C x M] column-major: its transpose's memory
+    enc_cm = enc.t().contiguous()
+    d_enc = enc.to(dev)
+    d_mic = rnd(M, B).to(dev)                               # [M][B] == [B x M] column-major
+    d_sh = torch.matmul(d_enc, d_mic)
+    ang = [(0.3 + 0.01 * torch.cumsum(rnd(nl, B), 1)).to(dev) for _ in range(3)]
+    d_out = [torch.zeros((nl, 2, B), dtype=torch.float64, device=dev) for _ in range(3)]
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    hp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    sh, real = L.LAYOUT["sh"], L.BASIS["real"]
+    h = [C.c_void_p() for _ in range(3)]                    # encoded, the plain one behind the matmul, plain
+    if nl == 1:
+        L.check(lib.emagls_decode_stream_create_encoded(M, hp(enc_cm), 0, Cc, 1, hp(wL), hp(wR), 0, ln, sh, real, B, C.byref(h[0])))
+        for k in (1, 2):
+            L.check(lib.emagls_decode_stream_create(Cc, hp(wL), hp(wR), 0, ln, 0, sh, real, B, C.byref(h[k])))
+    else:
+        L.check(lib.emagls_decode_group_create_encoded(M, hp(enc_cm), 0, Cc, 1, hp(wL), hp(wR), 0, ln, sh, real, B, nl, C.byref(h[0])))
+        for k in (1, 2):
+            L.check(lib.emagls_decode_group_create(Cc, 1, hp(wL), hp(wR), 0, ln, 0, sh, real, B, nl, C.byref(h[k])))
+    st = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(st.cuda_stream)
+    na = nl * B
+    aa = [p(a) for a in ang]
+
+    def push(k, x):
+        if nl == 1:
+            L.check(lib.emagls_decode_stream_push_device(h[k], p(x), B, aa[0], na, aa[1], na, aa[2], na, p(d_out[k]), sp))
+        else:
+            L.check(lib.emagls_decode_group_push_device(h[k], p(x), B, None, 0, aa[0], na, aa[1], na, aa[2], na, p(d_out[k]), sp))
+
+    def side_matmul():
+        push(1, torch.matmul(d_enc, d_mic))
+
+    sides = [("encoded", lambda: push(0, d_mic)), ("matmul", side_matmul), ("plain", lambda: push(2, d_sh))]
+    times = {k: [] for k, _ in sides}
+    with torch.cuda.stream(st):
+        for _, f in sides:
+            for _ in range(warm):
+                f()
+        st.synchronize()
+        for _ in range(max(1, blocks // run)):
+            for k, f in sides:                       # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(run):
+                    f()
+                e1.record(st)
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / run)   # us per block
+    st.synchronize()
+    err = float((d_out[0] - d_out[1]).abs().max() / d_out[1].abs().max())   # (both sides have seen the same pushes)
+    for k in range(3):
+        L.check((lib.emagls_decode_stream_destroy if nl == 1 else lib.emagls_decode_group_destroy)(h[k]))
+    res = {"shape": [M, Cc, ln, B], "listeners": nl, "block_us": round(B / FS * 1e6, 1), "encoded_vs_matmul_rel": err}
+    for k, v in times.items():
+        res[k] = {"median_us": round(float(np.median(v)), 2), "spread_us": round(float(np.percentile(v, 90) - np.percentile(v, 10)), 2)}
+    res["gain_us"] = round(res["matmul"]["median_us"] - res["encoded"]["median_us"], 2)
+    res["beyond_spreads"] = res["gain_us"] > res["matmul"]["spread_us"] + res["encoded"]["spread_us"]
+    return res
+
+
+def encoded_markdown(rows, device):
+    lines = ["`python tools/decode_stream_timing.py --encoded` on %s: time per block in us, median of the run averages (spread = p90 - p10)," % device,
+             "three-axis trajectories.  encoded: the encoded stream (group) pushed the microphone block; matmul: torch.matmul(enc, block) and",
+             "a push on a plain stream (group), on the same HIP stream; plain: the plain stream (group) alone.", "",
+             "| (M, C, len, B) | listeners | encoded | spread | matmul | spread | matmul - encoded | beyond the spreads | plain | spread |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append("| %s | %d | %.1f | %.2f | %.1f | %.2f | %.2f | %s | %.1f | %.2f |" % (
+            tuple(r["shape"]), r["listeners"], r["encoded"]["median_us"], r["encoded"]["spread_us"], r["matmul"]["median_us"],
+            r["matmul"]["spread_us"], r["gain_us"], "yes" if r["beyond_spreads"] else "no", r["plain"]["median_us"], r["plain"]["spread_us"]))
+    return "\n".join(lines) + "\n"
+
+
 def bank_markdown(rows, device):
     lines = ["`python tools/decode_stream_timing.py --bank` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
              "plain: the plain stream; const: a bank stream with a constant index from device memory; keep: a bank stream pushed without",
@@ -383,10 +474,14 @@ def main():
     ap.add_argument("--bank", action="store_true", help="time the bank of filter sets (see above)")
     ap.add_argument("--sets", type=int, default=None, help="--bank: filter sets of the bank stream (at least 3; default 3); --group: default 1")
     ap.add_argument("--group", action="store_true", help="time the listener group against a loop over streams (see above)")
-    ap.add_argument("--listeners", type=int, nargs="*", default=[1, 8, 64, 256], help="--group: numbers of listeners")
+    ap.add_argument("--listeners", type=int, nargs="*", default=None, help="--group: numbers of listeners (default 1 8 64 256); --encoded: default 1")
+    ap.add_argument("--encoded", action="store_true", help="time the encoder inside the stream against matmul + plain stream (see above)")
+    ap.add_argument("--enc-shapes", nargs="*", default=["32,25,512,64", "32,25,512,256", "64,64,2048,128"], help="--encoded: M,C,len,B ...")
     a = ap.parse_args()
     if a.sets is None:
         a.sets = 1 if a.group else 3
+    if a.listeners is None:
+        a.listeners = [1] if a.encoded else [1, 8, 64, 256]
     if a.blocks < a.run or a.run < 1 or a.warm < 0:
         raise SystemExit("--blocks must be at least --run, --run at least 1")
     shapes = parse_shapes(a.shapes)
@@ -401,6 +496,21 @@ def main():
     from emagls_amd import _lib as L
     lib = L.load()
     rows, ok = [], True
+    if a.encoded:
+        for it in a.enc_shapes:
+            M, Cc, ln, B = (int(v) for v in it.split(","))
+            parse_shapes(["%d,%d,%d" % (Cc, ln, B)])
+            if not (1 <= M <= 64 and 1 <= Cc <= 64) or any(nl < 1 or nl > 4096 for nl in a.listeners):
+                raise SystemExit("--encoded: 1 <= M, C <= 64, --listeners from 1 to 4096")
+            for nl in a.listeners:
+                res = run_encoded_shape(lib, L, torch, M, Cc, ln, B, nl, a.blocks, a.warm, a.run)
+                rows.append(res)
+                print(json.dumps(res), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(encoded_markdown(rows, torch.cuda.get_device_name(0)))
+        return 0
     if a.group:
         if a.sets < 1 or any(nl < 1 or nl > 4096 for nl in a.listeners):
             raise SystemExit("--sets must be at least 1, --listeners from 1 to 4096")
