@@ -594,7 +594,167 @@ def _real_mic_block(is_complex, what):
         raise L.EmaglsError(L.ERR_ARG, "an encoded %s takes real microphone blocks" % what)
 
 
-class BinauralDecodeStream:
+_ANGLE_NAMES = ("horRotAngleRad", "pitchRad", "rollRad")
+
+
+class _DecodeObject:
+    """What BinauralDecodeStream and BinauralDecodeGroup share, which is the library's one object behind both: the filters and the
+    encoder of the creation, the checks of a pushed block, the host and the torch push, and the handle's life.  A subclass names
+    its kind (_what) and the C entries it calls (_create, _create_encoded, _push, _push_device, _destroy), shapes the angles and
+    the set indices of a push (_shape_angles, _shape_sets) and makes the output (_new_out)."""
+
+    def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition, rotationDomain, complexInput, encoder,
+                 numListeners=None):
+        self._h = None
+        self._basis, self._cb = _basis(shDefinition)
+        self._layout = _layout(rotationDomain)
+        w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
+        wL = np.asfortranarray(np.asarray(decodingFilterLeft, dtype=np.complex128 if w_c else np.float64))
+        wR = np.asfortranarray(np.asarray(decodingFilterRight, dtype=np.complex128 if w_c else np.float64))
+        if wL.ndim not in (2, 3) or wL.shape != wR.shape:
+            raise ValueError("filters must be [len x numChannels] or [numSets x len x numChannels] arrays of equal shape")
+        if int(blockSize) != blockSize or (numListeners is not None and int(numListeners) != numListeners):
+            raise ValueError("blockSize must be an integer" if numListeners is None else "blockSize and numListeners must be integers")
+        self.numSets = wL.shape[0] if wL.ndim == 3 else 1
+        if self.numSets < 1:
+            raise ValueError("a bank needs at least one filter set")
+        if wL.ndim == 3:    # the library takes the sets one after the other, each column-major [len x numChannels]
+            wL, wR = (np.ascontiguousarray(w.transpose(0, 2, 1)) for w in (wL, wR))
+            ln, self.numChannels = wL.shape[2], wL.shape[1]
+        else:
+            ln, self.numChannels = wL.shape
+        self.blockSize, self.complexInput = int(blockSize), bool(complexInput)
+        listeners = ()
+        if numListeners is not None:
+            self.numListeners = int(numListeners)
+            listeners = (self.numListeners,)
+        self.numMics = None
+        h = C.c_void_p()
+        filters = (wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln)
+        if encoder is not None:
+            if complexInput:
+                raise ValueError("an encoded %s takes real microphone blocks: complexInput must be False" % self._what)
+            enc, pe, e_c, self.numMics = _encoder(encoder, self.numChannels)
+            L.check(getattr(L.load(), self._create_encoded)(self.numMics, pe, 1 if e_c else 0, self.numChannels, self.numSets, *filters,
+                                                            self._layout, self._basis, self.blockSize, *listeners, C.byref(h)))
+        else:
+            L.check(getattr(L.load(), self._create)(self.numChannels, self.numSets, *filters, 1 if complexInput else 0, self._layout,
+                                                    self._basis, self.blockSize, *listeners, C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the decode %s is closed" % self._what)
+        return self._h
+
+    def _check_block(self, shape, ndim):
+        if self.numMics is not None:
+            if ndim != 2 or shape[1] != self.numMics:
+                raise ValueError("block must be [numSamples x numMics] matching the encoder's microphone count (%d)" % self.numMics)
+        elif ndim != 2 or shape[1] != self.numChannels:
+            raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
+        if shape[0] % self.blockSize:
+            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
+        return shape[0]
+
+    def _check_complex(self, is_complex):
+        if self.numMics is not None:
+            _real_mic_block(is_complex, self._what)
+        if is_complex and not self.complexInput:
+            raise ValueError("the %s was created for real blocks (complexInput=False)" % self._what)
+
+    def _check_three_axis(self, turned):
+        """turned: the push has a pitch or a roll."""
+        if turned:
+            if self._layout != L.LAYOUT["sh"]:
+                raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
+            _sh_order(self.numChannels)
+
+    def _set_index(self, setIndex, n, device=None):
+        """setIndex in the shape of the push, as int32 (None: None): a host array checked against the bank or, with `device`, a
+        tensor there.  A tensor that is given is not read on the host."""
+        if setIndex is None:
+            return None
+        nb = n // self.blockSize
+        if device is not None:
+            import torch
+            if torch.is_tensor(setIndex):
+                if setIndex.dtype != torch.int32:
+                    raise ValueError("a setIndex tensor must be int32")
+                return self._shape_sets(setIndex.to(device=device), nb, torch).contiguous()
+        a = np.asarray(setIndex)
+        if a.dtype.kind not in "iu":
+            raise ValueError("setIndex must be an integer or integers")
+        a = self._shape_sets(a, nb, np)
+        if a.size and (a.min() < 0 or a.max() >= self.numSets):
+            raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        return a if device is None else torch.as_tensor(a, device=device)
+
+    def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None, setIndex=None):
+        h = self._handle()
+        if type(block).__module__.split(".")[0] == "torch":
+            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
+        self._check_complex(np.iscomplexobj(block))
+        x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
+        n = self._check_block(x.shape, x.ndim)
+        given = [None if a is None else np.asarray(a, dtype=np.float64) for a in (horRotAngleRad, pitchRad, rollRad)]
+        yaw, pitch, roll = (None if a is None else np.ascontiguousarray(a) for a in self._shape_angles(n, given, np))
+        self._check_three_axis(any(a is not None and np.any(a != 0) for a in (pitch, roll)))
+        sets = self._set_index(setIndex, n)
+        out, result = self._new_out(n, np.zeros)
+        L.check(getattr(L.load(), self._push)(h, x.ctypes.data_as(C.c_void_p), n, *_vp(sets), *_vp(yaw), *_vp(pitch), *_vp(roll),
+                                              out.ctypes.data_as(C.c_void_p)))
+        return result
+
+    def _push_torch(self, h, block, hor, pitch, roll, setIndex):
+        import torch
+        n = self._check_block(tuple(block.shape), block.dim())
+        if not block.is_cuda:
+            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        self._check_complex(block.is_complex())
+        xt = block.to(torch.complex128 if self.complexInput else torch.float64).t().contiguous()   # [numChannels][n]: column-major
+
+        def dev(a):
+            if a is None:
+                return None
+            if torch.is_tensor(a):
+                return a.to(device=block.device, dtype=torch.float64)
+            return torch.as_tensor(np.asarray(a, dtype=np.float64), device=block.device)
+        ty, tp, tr = (None if t is None else t.contiguous() for t in self._shape_angles(n, [dev(a) for a in (hor, pitch, roll)], torch))
+        count = lambda t: 0 if t is None else t.numel()   # noqa: E731
+        self._check_three_axis(count(tp) or count(tr))
+        ts = self._set_index(setIndex, n, block.device)
+        out, result = self._new_out(n, lambda shape: torch.empty(shape, dtype=torch.float64, device=block.device))
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(block.device):
+            st = torch.cuda.current_stream().cuda_stream
+            L.check(getattr(L.load(), self._push_device)(h, p(xt), n, p(ts), count(ts), p(ty), count(ty), p(tp), count(tp), p(tr), count(tr),
+                                                         p(out), C.c_void_p(st)))
+        for t in (xt, ty, tp, tr, ts):      # (their memory may be reused only after the stream has passed the enqueued kernels)
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(block.device))
+        return result
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L.check(getattr(L.load(), self._destroy)(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BinauralDecodeStream(_DecodeObject):
     """binauralDecode a block at a time, for a listener whose head moves while the sound plays.  Created
     once from the decoding filters [len x numChannels] (real or complex); then `push` takes consecutive blocks of the SH (or CH)
     signal, each with the head orientation for that block, and returns the two ear signals of that block, [n x 2].  With x the
@@ -618,41 +778,13 @@ class BinauralDecodeStream:
     w2 = np.einsum("...tc,cm->...tm", w, encoder), and push the microphone blocks to a plain stream of w2.  The library does not
     do so by itself, because the stream's history would change domain between a push with angles and one without."""
 
+    _what = "stream"
+    _create, _create_encoded, _push, _push_device, _destroy = (
+        "emagls_decode_stream_" + e for e in ("create_bank", "create_encoded", "push_sets", "push_sets_device", "destroy"))
+
     def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition="real", rotationDomain="sh", complexInput=False,
                  encoder=None):
-        self._h = None
-        self._basis, self._cb = _basis(shDefinition)
-        self._layout = _layout(rotationDomain)
-        w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
-        wL = np.asfortranarray(np.asarray(decodingFilterLeft, dtype=np.complex128 if w_c else np.float64))
-        wR = np.asfortranarray(np.asarray(decodingFilterRight, dtype=np.complex128 if w_c else np.float64))
-        if wL.ndim not in (2, 3) or wL.shape != wR.shape:
-            raise ValueError("filters must be [len x numChannels] or [numSets x len x numChannels] arrays of equal shape")
-        if int(blockSize) != blockSize:
-            raise ValueError("blockSize must be an integer")
-        self.numSets = wL.shape[0] if wL.ndim == 3 else 1
-        if self.numSets < 1:
-            raise ValueError("a bank needs at least one filter set")
-        if wL.ndim == 3:    # the library takes the sets one after the other, each column-major [len x numChannels]
-            wL, wR = (np.ascontiguousarray(w.transpose(0, 2, 1)) for w in (wL, wR))
-            ln, self.numChannels = wL.shape[2], wL.shape[1]
-        else:
-            ln, self.numChannels = wL.shape
-        self.blockSize, self.complexInput = int(blockSize), bool(complexInput)
-        self.numMics = None
-        h = C.c_void_p()
-        if encoder is not None:
-            if complexInput:
-                raise ValueError("an encoded stream takes real microphone blocks: complexInput must be False")
-            enc, pe, e_c, self.numMics = _encoder(encoder, self.numChannels)
-            L.check(L.load().emagls_decode_stream_create_encoded(self.numMics, pe, 1 if e_c else 0, self.numChannels, self.numSets,
-                                                                 wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0,
-                                                                 ln, self._layout, self._basis, self.blockSize, C.byref(h)))
-        else:
-            L.check(L.load().emagls_decode_stream_create_bank(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
-                                                              wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
-                                                              self._layout, self._basis, self.blockSize, C.byref(h)))
-        self._h = h
+        super().__init__(decodingFilterLeft, decodingFilterRight, blockSize, shDefinition, rotationDomain, complexInput, encoder)
 
     @property
     def info(self):
@@ -660,30 +792,22 @@ class BinauralDecodeStream:
         L.check(L.load().emagls_decode_stream_info(self._handle(), C.byref(b), C.byref(p), C.byref(sb), C.byref(fb), C.byref(nl)))
         return {"block": b.value, "partitions": p.value, "state_bytes": sb.value, "filter_bytes": fb.value, "launches_per_block": nl.value}
 
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the decode stream is closed")
-        return self._h
+    def _shape_angles(self, n, angles, xp):
+        """The argument errors of binauralDecode, in its wording; each angle as a vector of 1 or n values."""
+        for a, name in zip(angles, _ANGLE_NAMES):
+            if a is not None and math.prod(a.shape) not in (1, n):
+                raise ValueError("%s must be a scalar or have one angle per input sample (%d), not %d" % (name, n, math.prod(a.shape)))
+        return [None if a is None else a.reshape(-1) for a in angles]
 
-    def _check_angles(self, n, hor, pitch, roll, size):
-        """The argument errors of binauralDecode, in its wording; `size` gives the number of values of an angle argument."""
-        for a, name in ((hor, "horRotAngleRad"), (pitch, "pitchRad"), (roll, "rollRad")):
-            if a is not None and size(a) not in (1, n):
-                raise ValueError("%s must be a scalar or have one angle per input sample (%d), not %d" % (name, n, size(a)))
-
-    def _set_index(self, setIndex, n):
-        """setIndex as an int32 array of 1 or n / blockSize values, checked against the bank (None: None)."""
-        if setIndex is None:
-            return None
-        a = np.asarray(setIndex)
-        if a.dtype.kind not in "iu":
-            raise ValueError("setIndex must be an integer or integers")
+    def _shape_sets(self, a, nb, xp):
         a = a.reshape(-1)
-        if a.size not in (1, n // self.blockSize):
-            raise ValueError("setIndex must be an integer or have one index per block (%d), not %d" % (n // self.blockSize, a.size))
-        if a.size and (a.min() < 0 or a.max() >= self.numSets):
-            raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
-        return np.ascontiguousarray(a, dtype=np.int32)
+        if math.prod(a.shape) not in (1, nb):
+            raise ValueError("setIndex must be an integer or have one index per block (%d), not %d" % (nb, math.prod(a.shape)))
+        return a
+
+    def _new_out(self, n, new):
+        out = new((2, n))   # the library's column-major [n x 2]
+        return out, out.T
 
     def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None, setIndex=None):
         """block [n x numChannels], n a multiple of blockSize: a NumPy array (host entry; returns a NumPy array), or a torch tensor
@@ -692,107 +816,14 @@ class BinauralDecodeStream:
         setIndex: None (every block keeps the set of the block before it; set 0 on a fresh stream), an int (every block of this
         push) or one int per block; with torch blocks also a device int32 tensor, which is not read on the host: the kernels then
         clamp its values into [0, numSets - 1]."""
-        h = self._handle()
-        if type(block).__module__.split(".")[0] == "torch":
-            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
-        if self.numMics is not None:
-            _real_mic_block(np.iscomplexobj(block), "stream")
-        if np.iscomplexobj(block) and not self.complexInput:
-            raise ValueError("the stream was created for real blocks (complexInput=False)")
-        x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
-        n = self._check_block(x.shape, x.ndim)
-        self._check_angles(n, horRotAngleRad, pitchRad, rollRad, lambda a: np.asarray(a).size)
-        yaw, pitch, roll = (_angles(a, n, "angle") for a in (horRotAngleRad, pitchRad, rollRad))
-        if any(a is not None and np.any(a != 0) for a in (pitch, roll)):
-            if self._layout != L.LAYOUT["sh"]:
-                raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
-            _sh_order(self.numChannels)
-        sets = self._set_index(setIndex, n)
-        out, po = _out(n, 2, False)
-        ps, ns = (None, 0) if sets is None else (sets.ctypes.data_as(C.c_void_p), sets.size)
-        L.check(L.load().emagls_decode_stream_push_sets(h, x.ctypes.data_as(C.c_void_p), n, ps, ns, *_vp(yaw), *_vp(pitch), *_vp(roll), po))
-        return out
-
-    def _check_block(self, shape, ndim):
-        if self.numMics is not None:
-            if ndim != 2 or shape[1] != self.numMics:
-                raise ValueError("block must be [numSamples x numMics] matching the encoder's microphone count (%d)" % self.numMics)
-        elif ndim != 2 or shape[1] != self.numChannels:
-            raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
-        if shape[0] % self.blockSize:
-            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
-        return shape[0]
-
-    def _push_torch(self, h, block, hor, pitch, roll, setIndex=None):
-        import torch
-        n = self._check_block(tuple(block.shape), block.dim())
-        if not block.is_cuda:
-            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
-        if self.numMics is not None:
-            _real_mic_block(block.is_complex(), "stream")
-        if block.is_complex() and not self.complexInput:
-            raise ValueError("the stream was created for real blocks (complexInput=False)")
-        size = lambda a: a.numel() if torch.is_tensor(a) else np.asarray(a).size   # noqa: E731
-        self._check_angles(n, hor, pitch, roll, size)
-        dt = torch.complex128 if self.complexInput else torch.float64
-        xt = block.to(dt).t().contiguous()                  # [numChannels][n]: the library's column-major [n x numChannels]
-
-        def dev(a):
-            if a is None:
-                return None, 0
-            t = a.to(device=block.device, dtype=torch.float64).reshape(-1).contiguous() if torch.is_tensor(a) else \
-                torch.as_tensor(np.asarray(a, dtype=np.float64).reshape(-1), device=block.device)
-            return t, t.numel()
-        (ty, ny), (tp, npi), (tr, nr) = dev(hor), dev(pitch), dev(roll)
-        if (npi or nr) and self._layout != L.LAYOUT["sh"]:
-            raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
-        if npi or nr:
-            _sh_order(self.numChannels)
-        ts, ns = None, 0
-        if torch.is_tensor(setIndex):
-            if setIndex.dtype != torch.int32:
-                raise ValueError("a setIndex tensor must be int32")
-            ts = setIndex.to(device=block.device).reshape(-1).contiguous()
-            ns = ts.numel()
-            if ns not in (1, n // self.blockSize):
-                raise ValueError("setIndex must be an integer or have one index per block (%d), not %d" % (n // self.blockSize, ns))
-        elif setIndex is not None:
-            ts = torch.as_tensor(self._set_index(setIndex, n), device=block.device)
-            ns = ts.numel()
-        out = torch.empty((2, n), dtype=torch.float64, device=block.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-        with torch.cuda.device(block.device):
-            st = torch.cuda.current_stream().cuda_stream
-            L.check(L.load().emagls_decode_stream_push_sets_device(h, p(xt), n, p(ts), ns, p(ty), ny, p(tp), npi, p(tr), nr, p(out),
-                                                                   C.c_void_p(st)))
-        for t in (xt, ty, tp, tr, ts):      # (their memory may be reused only after the stream has passed the enqueued kernels)
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(block.device))
-        return out.t()
+        return super().push(block, horRotAngleRad, pitchRad, rollRad, setIndex)
 
     def reset(self):
         """Zero history: what follows equals a fresh stream bit for bit."""
         L.check(L.load().emagls_decode_stream_reset(self._handle()))
 
-    def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            L.check(L.load().emagls_decode_stream_destroy(h))
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BinauralDecodeGroup:
+class BinauralDecodeGroup(_DecodeObject):
     """Many listeners of one sound field in one push: one bank of filter sets, stored once, and
     `numListeners` listeners, each with the state a BinauralDecodeStream has.  `push` takes one block of the common signal and, per
     listener, their head orientation and their set index, and returns [numListeners x n x 2].  Listener l's output is, bit for bit,
@@ -803,41 +834,14 @@ class BinauralDecodeGroup:
     With encoder [numChannels x numMics] the common block is one of real microphone signals [n x numMics], encoded inside the
     rotation launch: listener l equals, bit for bit, an encoded BinauralDecodeStream of its own."""
 
+    _what = "group"
+    _create, _create_encoded, _push, _push_device, _destroy = (
+        "emagls_decode_group_" + e for e in ("create", "create_encoded", "push", "push_device", "destroy"))
+
     def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, numListeners, shDefinition="real", rotationDomain="sh",
                  complexInput=False, encoder=None):
-        self._h = None
-        self._basis, self._cb = _basis(shDefinition)
-        self._layout = _layout(rotationDomain)
-        w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
-        wL = np.asfortranarray(np.asarray(decodingFilterLeft, dtype=np.complex128 if w_c else np.float64))
-        wR = np.asfortranarray(np.asarray(decodingFilterRight, dtype=np.complex128 if w_c else np.float64))
-        if wL.ndim not in (2, 3) or wL.shape != wR.shape:
-            raise ValueError("filters must be [len x numChannels] or [numSets x len x numChannels] arrays of equal shape")
-        if int(blockSize) != blockSize or int(numListeners) != numListeners:
-            raise ValueError("blockSize and numListeners must be integers")
-        self.numSets = wL.shape[0] if wL.ndim == 3 else 1
-        if self.numSets < 1:
-            raise ValueError("a bank needs at least one filter set")
-        if wL.ndim == 3:    # the library takes the sets one after the other, each column-major [len x numChannels]
-            wL, wR = (np.ascontiguousarray(w.transpose(0, 2, 1)) for w in (wL, wR))
-            ln, self.numChannels = wL.shape[2], wL.shape[1]
-        else:
-            ln, self.numChannels = wL.shape
-        self.blockSize, self.numListeners, self.complexInput = int(blockSize), int(numListeners), bool(complexInput)
-        self.numMics = None
-        h = C.c_void_p()
-        if encoder is not None:
-            if complexInput:
-                raise ValueError("an encoded group takes real microphone blocks: complexInput must be False")
-            enc, pe, e_c, self.numMics = _encoder(encoder, self.numChannels)
-            L.check(L.load().emagls_decode_group_create_encoded(self.numMics, pe, 1 if e_c else 0, self.numChannels, self.numSets,
-                                                                wL.ctypes.data_as(C.c_void_p), wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0,
-                                                                ln, self._layout, self._basis, self.blockSize, self.numListeners, C.byref(h)))
-        else:
-            L.check(L.load().emagls_decode_group_create(self.numChannels, self.numSets, wL.ctypes.data_as(C.c_void_p),
-                                                        wR.ctypes.data_as(C.c_void_p), 1 if w_c else 0, ln, 1 if complexInput else 0,
-                                                        self._layout, self._basis, self.blockSize, self.numListeners, C.byref(h)))
-        self._h = h
+        super().__init__(decodingFilterLeft, decodingFilterRight, blockSize, shDefinition, rotationDomain, complexInput, encoder,
+                         numListeners=numListeners)
 
     def info(self):
         b, p, nl, sb, fb, k = L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), C.c_int(0)
@@ -845,25 +849,8 @@ class BinauralDecodeGroup:
         return {"block": b.value, "partitions": p.value, "listeners": nl.value, "state_bytes": sb.value, "filter_bytes": fb.value,
                 "launches_per_block": k.value}
 
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the decode group is closed")
-        return self._h
-
-    def _check_block(self, shape, ndim):
-        if self.numMics is not None:
-            if ndim != 2 or shape[1] != self.numMics:
-                raise ValueError("block must be [numSamples x numMics] matching the encoder's microphone count (%d)" % self.numMics)
-        elif ndim != 2 or shape[1] != self.numChannels:
-            raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
-        if shape[0] % self.blockSize:
-            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
-        return shape[0]
-
     def _per_listener(self, a, per, name, what, xp):
-        """An argument of push as [L] or [L x per] (None: None): a scalar is the same for every listener."""
-        if a is None:
-            return None
+        """An argument of push as [L] or [L x per]: a scalar is the same for every listener."""
         nl = self.numListeners
         shape = tuple(a.shape)
         if len(shape) == 0 or (len(shape) == 1 and shape[0] == 1):
@@ -876,6 +863,16 @@ class BinauralDecodeGroup:
             return a.reshape(1, per)
         raise ValueError("%s must be a scalar, [numListeners] or [numListeners x %s] = [%d x %d], not %s" % (name, what, nl, per, list(shape)))
 
+    def _shape_angles(self, n, angles, xp):
+        return [None if a is None else self._per_listener(a, n, name, "n", xp) for a, name in zip(angles, _ANGLE_NAMES)]
+
+    def _shape_sets(self, a, nb, xp):
+        return self._per_listener(a, nb, "setIndex", "n / blockSize", xp)
+
+    def _new_out(self, n, new):
+        out = new((self.numListeners, 2, n))
+        return out, out.swapaxes(1, 2)
+
     def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None, setIndex=None):
         """block [n x numChannels], the common signal, n a multiple of blockSize: a NumPy array (host entry) or a torch tensor on
         the group's device (device entry on torch's current stream, not synchronised).  Each angle: None (0), a scalar (every
@@ -883,106 +880,12 @@ class BinauralDecodeGroup:
         set; set 0 on a fresh listener), an int (every listener), [numListeners] or [numListeners x n / blockSize]; a device int32
         tensor is not read on the host: the kernels then clamp its values into [0, numSets - 1].
         Returns [numListeners x n x 2]."""
-        h = self._handle()
-        if type(block).__module__.split(".")[0] == "torch":
-            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
-        if self.numMics is not None:
-            _real_mic_block(np.iscomplexobj(block), "group")
-        if np.iscomplexobj(block) and not self.complexInput:
-            raise ValueError("the group was created for real blocks (complexInput=False)")
-        x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
-        n = self._check_block(x.shape, x.ndim)
-        names = ("horRotAngleRad", "pitchRad", "rollRad")
-        yaw, pitch, roll = (None if a is None else np.ascontiguousarray(self._per_listener(np.asarray(a, dtype=np.float64), n, nm, "n", np))
-                            for a, nm in zip((horRotAngleRad, pitchRad, rollRad), names))
-        if any(a is not None and np.any(a != 0) for a in (pitch, roll)):
-            if self._layout != L.LAYOUT["sh"]:
-                raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
-            _sh_order(self.numChannels)
-        sets = None
-        if setIndex is not None:
-            a = np.asarray(setIndex)
-            if a.dtype.kind not in "iu":
-                raise ValueError("setIndex must be an integer or integers")
-            a = self._per_listener(a, n // self.blockSize, "setIndex", "n / blockSize", np)
-            if a.size and (a.min() < 0 or a.max() >= self.numSets):
-                raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
-            sets = np.ascontiguousarray(a, dtype=np.int32)
-        out = np.zeros((self.numListeners, 2, n))
-        ps, ns = (None, 0) if sets is None else (sets.ctypes.data_as(C.c_void_p), sets.size)
-        L.check(L.load().emagls_decode_group_push(h, x.ctypes.data_as(C.c_void_p), n, ps, ns, *_vp(yaw), *_vp(pitch), *_vp(roll),
-                                                  out.ctypes.data_as(C.c_void_p)))
-        return out.transpose(0, 2, 1)
-
-    def _push_torch(self, h, block, hor, pitch, roll, setIndex):
-        import torch
-        n = self._check_block(tuple(block.shape), block.dim())
-        if not block.is_cuda:
-            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
-        if self.numMics is not None:
-            _real_mic_block(block.is_complex(), "group")
-        if block.is_complex() and not self.complexInput:
-            raise ValueError("the group was created for real blocks (complexInput=False)")
-        xt = block.to(torch.complex128 if self.complexInput else torch.float64).t().contiguous()   # [numChannels][n]
-
-        def dev(a, name):
-            if a is None:
-                return None, 0
-            t = a.to(device=block.device, dtype=torch.float64) if torch.is_tensor(a) else \
-                torch.as_tensor(np.asarray(a, dtype=np.float64), device=block.device)
-            t = self._per_listener(t, n, name, "n", torch).contiguous()
-            return t, t.numel()
-        (ty, ny), (tp, npi), (tr, nr) = dev(hor, "horRotAngleRad"), dev(pitch, "pitchRad"), dev(roll, "rollRad")
-        if (npi or nr) and self._layout != L.LAYOUT["sh"]:
-            raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
-        if npi or nr:
-            _sh_order(self.numChannels)
-        ts, ns = None, 0
-        if torch.is_tensor(setIndex):
-            if setIndex.dtype != torch.int32:
-                raise ValueError("a setIndex tensor must be int32")
-            ts = self._per_listener(setIndex.to(device=block.device), n // self.blockSize, "setIndex", "n / blockSize", torch).contiguous()
-        elif setIndex is not None:
-            a = np.asarray(setIndex)
-            if a.dtype.kind not in "iu":
-                raise ValueError("setIndex must be an integer or integers")
-            a = self._per_listener(a, n // self.blockSize, "setIndex", "n / blockSize", np)
-            if a.size and (a.min() < 0 or a.max() >= self.numSets):
-                raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
-            ts = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32), device=block.device)
-        if ts is not None:
-            ns = ts.numel()
-        out = torch.empty((self.numListeners, 2, n), dtype=torch.float64, device=block.device)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-        with torch.cuda.device(block.device):
-            st = torch.cuda.current_stream().cuda_stream
-            L.check(L.load().emagls_decode_group_push_device(h, p(xt), n, p(ts), ns, p(ty), ny, p(tp), npi, p(tr), nr, p(out), C.c_void_p(st)))
-        for t in (xt, ty, tp, tr, ts):      # (their memory may be reused only after the stream has passed the enqueued kernels)
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(block.device))
-        return out.transpose(1, 2)
+        return super().push(block, horRotAngleRad, pitchRad, rollRad, setIndex)
 
     def reset(self, listener=None):
         """Zero history for one listener (what a listener who joins gets; the others are untouched) or, with None, for all: what
         follows equals a fresh stream bit for bit."""
         L.check(L.load().emagls_decode_group_reset(self._handle(), -1 if listener is None else int(listener)))
-
-    def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            L.check(L.load().emagls_decode_group_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def designYawBank(kind, hL, hR, hrirGridAziRad, hrirGridZenRad, yawRad, *, order=4, fs=48000.0, len=512, shDefinition="real",

@@ -491,9 +491,10 @@ int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, do
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// The decode stream (decode_stream.hip; DESIGN.md sections 9.3 and 9.4) and the listener group (section 9.5), which is the same
-// object with d.L listeners: the per-listener state L times over, the bank once.  The object owns its device buffers:
-// emagls_cache_clear() does not reach them.
+// The decode stream (decode_stream.hip; DESIGN.md sections 9.3 and 9.4) and the listener group (section 9.5): one object with d.L
+// listeners, the per-listener state L times over, the bank once, and one host path for both.  A stream is the object with
+// d.L == 1; emagls_decode_group is the ABI's second name for it, and the two sets of entry points differ in the wording of
+// some errors (Kind) and in nothing else.  The object owns its device buffers: emagls_cache_clear() does not reach them.
 // ---------------------------------------------------------------------------------------------
 struct emagls_decode_stream {
     std::mutex mu;
@@ -510,8 +511,8 @@ struct emagls_decode_stream {
     void* xrot = nullptr;         // [L][nch][B] the rotated block of every listener (cplx when the signal or the basis is complex)
     void* stage[4] = {};          // host entry: the push's input, angles, output and set indices on the device, grown on demand and kept
     size_t stage_cap[4] = {};
-    int known[2] = {-1, -1};      // what the host knows of the selection state on the device: the set indices of the two previous
-                                  // blocks, -1: none yet, -2: not known (a push took its indices from device memory)
+    int known[2] = {-1, -1};      // d.L == 1: what the host knows of the selection state on the device: the set indices of the two
+                                  // previous blocks, -1: none yet, -2: not known (a push took its indices from device memory)
     int cp() const { return d.planes2 ? 2 * d.C : d.C; }
     // a pushed block: [nsamp x block_cols()], complex when block_c()
     int64_t block_cols() const { return nmics ? nmics : nch; }
@@ -532,7 +533,7 @@ struct emagls_decode_stream {
         ready = false;
     }
     // the listeners first .. first + count - 1 back to a fresh stream's state
-    void zero_state(hipStream_t st, int64_t first = 0, int64_t count = 1) {
+    void zero_state(hipStream_t st, int64_t first, int64_t count) {
         const size_t n = (size_t)count, pb = pos_bytes();
         HIP_CHECK(hipMemsetAsync((char*)d.ring + (size_t)first * ring_bytes(), 0, n * ring_bytes(), st));
         HIP_CHECK(hipMemsetAsync((char*)d.hist + (size_t)first * hist_bytes(), 0, n * hist_bytes(), st));
@@ -570,316 +571,181 @@ struct emagls_decode_stream {
     }
 };
 
-struct emagls_decode_group : emagls_decode_stream {};   // (d.L listeners; the host's copy of the selection, `known`, is not used)
-
 namespace {
 
 constexpr int64_t kDecodeStreamMaxSets = 65536;
 constexpr int64_t kDecodeGroupMaxListeners = 4096;   // well under the grid's limit; keeps xrot and the rings of large shapes bounded
 
-// the set indices of a push: 0 values (the set of the previous block), 1 (every block of the push) or one per block
-struct Sets { const int32_t* p = nullptr; int64_t n = 0; const int32_t* host = nullptr; /* the same values, where the host has them */ };
+// The two names of the object, where their errors differ (the texts and their order are part of the ABI).  angle_count: a wrong
+// angle count is reported by check_push, in the group's wording; null: a stream's is left to check_args, in the rotation's.
+struct Kind { const char* null_handle; const char* set_count; const char* angle_count; const char* outside_bank; };
+const Kind kStream{"null decode stream", "a push takes 0 set indices, 1, or one per block", nullptr, "set index outside the stream's bank"};
+const Kind kGroup{"null decode group", "a group push takes 0 set indices, one per listener, or one per listener and block",
+                  "a group push takes no value of an angle, one per listener, or one per listener and sample",
+                  "set index outside the group's bank"};
 
-void stream_check_push(const emagls_decode_stream* s, const void* in, const void* out, int64_t nsamp, const Angles& a, const Sets& sets = {}) {
-    if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
-    if (nsamp < 0 || nsamp % s->d.B) throw Error(EMAGLS_ERR_ARG, "a push needs a multiple of the block size of samples");
-    if (sets.n != 0 && sets.n != 1 && sets.n != nsamp / s->d.B)
-        throw Error(EMAGLS_ERR_ARG, "a push takes 0 set indices, 1, or one per block");
-    if (sets.n && !sets.p) throw Error(EMAGLS_ERR_ARG, "null pointer");
-    check_args(true, {in, out}, nsamp, s->nch, s->len, 0, s->layout, s->basis, a);
-}
+emagls_decode_stream* object_of(emagls_decode_group* g) { return reinterpret_cast<emagls_decode_stream*>(g); }
+const emagls_decode_stream* object_of(const emagls_decode_group* g) { return reinterpret_cast<const emagls_decode_stream*>(g); }
 
-// k blocks in order on st; device pointers; not synchronised (s->mu held, device current)
-void stream_push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const Angles& a, const Sets& sets, double* d_out,
-                        hipStream_t st) {
-    s->ensure_device();
-    const int64_t B = s->d.B;
-    const bool cb = s->basis == EMAGLS_BASIS_COMPLEX;
-    auto at = [&](const double* p, int64_t n, int64_t b) { return n > 1 ? p + b * B : p; };
-    for (int64_t b = 0; b < nsamp / B; ++b) {
-        const void* x = (const char*)d_in + esz(s->block_c()) * (size_t)(b * B);
-        bool x_c = s->in_c;
-        int64_t ldx = nsamp;
-        const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
-                         at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
-        if (s->nmics) {   // the encoder inside the rotation launch; without angles, alone: xrot is written either way
-            const EncodeBlock e{s->enc, s->in_c, (int)s->nmics, (const double*)x, nsamp};
-            if (a.any()) launch_rotation_encoded(blk, e, B, (int)s->nch, s->layout, cb, s->xrot, st, B);
-            else launch_encode_block(e, B, (int)s->nch, s->xrot, B, st);
-            x = s->xrot; x_c = x_c || (a.any() && cb); ldx = B;
-        } else if (a.any()) {
-            launch_rotation(blk, x, x_c, B, (int)s->nch, s->layout, cb, false, s->xrot, st, nsamp, B);
-            x = s->xrot; x_c = x_c || cb; ldx = B;
-        }
-        // the host's copy of the selection, moved on as the kernels move theirs: three equal known indices are a standing set
-        int cur = -2, standing = -1;
-        if (sets.n == 0) cur = s->known[0] == -2 ? -2 : std::max(s->known[0], 0);
-        else if (sets.host) cur = sets.host[sets.n > 1 ? b : 0];
-        if (cur >= 0) {
-            const int s1 = s->known[0] == -1 ? cur : s->known[0], s2 = s->known[1] == -1 ? s1 : s->known[1];
-            if (s1 == cur && s2 == cur) standing = cur;
-        }
-        s->known[1] = s->known[0] == -1 ? cur : s->known[0];
-        s->known[0] = cur;
-        launch_decode_stream_block(s->d, x, x_c, ldx, sets.n > 1 ? sets.p + b : sets.p, standing, d_out + b * B, nsamp, st);
-    }
-}
+// the set indices of a push; host: the same values, where the host has them
+struct Sets { const int32_t* p = nullptr; int64_t n = 0; const int32_t* host = nullptr; };
 
-
-// The creation of a stream or of a listener group (T), every argument checked before the device is touched
-// nmics > 0: an encoded stream, enc [nch x nmics] column-major (interleaved complex when in_is_complex, which then says what the
-// ENCODED signal is; the pushed microphone blocks are real)
-template <typename T>
-T* stream_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
-                 int layout, int basis, int64_t block, int64_t listeners, int64_t nmics = 0, const void* enc = nullptr) {
-    if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
-    if (n_sets < 1) throw Error(EMAGLS_ERR_ARG, "a decode stream needs at least one filter set");
-    if (n_sets > kDecodeStreamMaxSets) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports banks of up to 65536 filter sets");
-    if (listeners < 1) throw Error(EMAGLS_ERR_ARG, "a listener group needs at least one listener");
-    if (listeners > kDecodeGroupMaxListeners) throw Error(EMAGLS_ERR_UNSUPPORTED, "a listener group supports up to 4096 listeners");
-    if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
-    check_basis(basis);
-    if (!decode_stream_block_ok(block))
-        throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports block sizes 64, 128, 256, 512, 1024 and 2048");
-    if (len > 16384) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports filters of up to 16384 taps");
-    std::unique_ptr<T> s(new T);
-    s->nch = nch; s->len = len; s->layout = layout; s->basis = basis; s->in_c = in_is_complex != 0;
-    s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block); s->d.S = (int)n_sets; s->d.L = (int)listeners;
-    // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
-    s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
-    if (nmics > 0) {
-        const int k = s->in_c ? 2 : 1;
-        const double* e = reinterpret_cast<const double*>(enc);
-        s->nmics = nmics;
-        s->enc_host.resize((size_t)nch * nmics * k);
-        for (int64_t c = 0; c < nch; ++c)
-            for (int64_t m = 0; m < nmics; ++m)
-                for (int i = 0; i < k; ++i) s->enc_host[(size_t)(c * nmics + m) * k + i] = e[(size_t)(m * nch + c) * k + i];
-    }
-    const int Cp = s->cp();
-    const bool wc = filters_are_complex != 0;
-    s->wpl.assign((size_t)n_sets * 2 * Cp * len, 0.0);
-    for (int64_t set = 0; set < n_sets; ++set)
-        for (int e = 0; e < 2; ++e) {
-            const double* w = reinterpret_cast<const double*>(e ? wR : wL) + (size_t)set * nch * len * (wc ? 2 : 1);
-            double* pl = s->wpl.data() + ((size_t)set * 2 + e) * Cp * len;
-            for (int64_t c = 0; c < nch; ++c)
-                for (int64_t t = 0; t < len; ++t) {
-                    const size_t i = (size_t)(c * len + t);
-                    pl[(size_t)c * len + t] = wc ? w[2 * i] : w[i];
-                    if (wc && s->d.planes2) pl[(size_t)(nch + c) * len + t] = -w[2 * i + 1];
-                }
-        }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
-        std::lock_guard<std::mutex> lk(s->mu);
-        s->ensure_device();
-    } else {
-        (void)hipGetLastError();
-    }
-    return s.release();
-}
-
-// ---- the listener group: one push of the common block for all listeners (device pointers; arrays listener-major)
-// A count of a push: 0, L (one value per listener) or L * per (per = nsamp for an angle, nsamp / block for a set index)
-int64_t group_count(int64_t n, int64_t L, int64_t per, const void* p, const char* what) {
-    if (n != 0 && n != L && n != L * per) throw Error(EMAGLS_ERR_ARG, std::string("a group push takes ") + what);
+// A count of a push, arrays listener-major: 0, L (one value per listener) or L * per (per = nsamp for an angle, nsamp / block for
+// a set index).  With L == 1 that is a stream's 0, 1 or one per sample / per block.  Returns what one listener has.
+int64_t push_count(int64_t n, int64_t L, int64_t per, const void* p, const char* wrong) {
+    if (n != 0 && n != L && n != L * per) throw Error(EMAGLS_ERR_ARG, wrong);
     if (n > 0 && !p) throw Error(EMAGLS_ERR_ARG, "null pointer");
-    return n == 0 ? 0 : (per != 1 && n == L * per) ? per : 1;   // what one listener has
+    return n == 0 ? 0 : (per != 1 && n == L * per) ? per : 1;
 }
 
-// what one listener has of each array, and the checks of a stream's push on that
-struct GroupPush { Angles one; int64_t set_per = 0; };
+// what one listener has of each array of a push
+struct Push { Angles one; int64_t set_per = 0; };
 
-GroupPush group_check_push(const emagls_decode_group* g, const void* in, const void* out, int64_t nsamp, const Angles& a, const Sets& sets) {
-    if (!g) throw Error(EMAGLS_ERR_ARG, "null decode group");
-    const int64_t B = g->d.B, L = g->d.L;
+Push check_push(const Kind& k, const emagls_decode_stream* s, const void* in, const void* out, int64_t nsamp, const Angles& a, const Sets& sets) {
+    if (!s) throw Error(EMAGLS_ERR_ARG, k.null_handle);
+    const int64_t B = s->d.B, L = s->d.L;
     if (nsamp < 0 || nsamp % B) throw Error(EMAGLS_ERR_ARG, "a push needs a multiple of the block size of samples");
-    static const char* const kAngleCount = "no value of an angle, one per listener, or one per listener and sample";
-    GroupPush r;
-    r.set_per = group_count(sets.n, L, nsamp / B, sets.p, "0 set indices, one per listener, or one per listener and block");
-    r.one = {a.yaw, group_count(a.n_yaw, L, nsamp, a.yaw, kAngleCount), a.pitch, group_count(a.n_pitch, L, nsamp, a.pitch, kAngleCount), a.roll,
-             group_count(a.n_roll, L, nsamp, a.roll, kAngleCount)};
-    check_args(true, {in, out}, nsamp, g->nch, g->len, 0, g->layout, g->basis, r.one);
+    Push r;
+    r.set_per = push_count(sets.n, L, nsamp / B, sets.p, k.set_count);
+    r.one = a;
+    if (k.angle_count) {
+        r.one.n_yaw = push_count(a.n_yaw, L, nsamp, a.yaw, k.angle_count);
+        r.one.n_pitch = push_count(a.n_pitch, L, nsamp, a.pitch, k.angle_count);
+        r.one.n_roll = push_count(a.n_roll, L, nsamp, a.roll, k.angle_count);
+    }
+    check_args(true, {in, out}, nsamp, s->nch, s->len, 0, s->layout, s->basis, r.one);
     return r;
 }
 
-// k blocks in order on st, at most three launches each whatever L is; not synchronised (g->mu held, device current)
-void group_push_blocks(emagls_decode_group* g, const void* d_in, int64_t nsamp, const GroupPush& p, const Sets& sets, double* d_out,
-                       hipStream_t st) {
-    g->ensure_device();
-    const int64_t B = g->d.B, C = g->d.C, nb = nsamp / B;
-    const bool cb = g->basis == EMAGLS_BASIS_COMPLEX;
+// The blocks of a push in order on st, at most three launches each whatever L is; device pointers; not synchronised (s->mu held,
+// device current).  Per-sample angles are [L][nsamp], set indices per block [L][nsamp / B], d_out [L][2][nsamp].
+void push_blocks(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const Push& p, const Sets& sets, double* d_out, hipStream_t st) {
+    s->ensure_device();
+    const int64_t B = s->d.B, C = s->d.C, nb = nsamp / B;
+    const int L = s->d.L;
+    const bool cb = s->basis == EMAGLS_BASIS_COMPLEX;
     const Angles& a = p.one;
-    // per-sample angles are [L][nsamp]: block b of listener l at + l nsamp + b B; one value per listener: [L]
+    const bool turned = a.any();
+    // block b of listener l's angles at + l nsamp + b B; one value per listener: [L]  (the kernels index by the listener: 0 when L == 1)
     const int64_t la[3] = {a.n_yaw > 1 ? nsamp : 1, a.n_pitch > 1 ? nsamp : 1, a.n_roll > 1 ? nsamp : 1};
     auto at = [&](const double* q, int64_t n, int64_t b) { return n > 1 ? q + b * B : q; };
     for (int64_t b = 0; b < nb; ++b) {
-        const void* x = (const char*)d_in + esz(g->block_c()) * (size_t)(b * B);
-        bool x_c = g->in_c;
+        const void* x = (const char*)d_in + esz(s->block_c()) * (size_t)(b * B);
+        bool x_c = s->in_c;
         int64_t ldx = nsamp, lsx = 0;   // without angles every listener reads the common block
         const Angles blk{at(a.yaw, a.n_yaw, b), a.n_yaw > 1 ? B : a.n_yaw, at(a.pitch, a.n_pitch, b), a.n_pitch > 1 ? B : a.n_pitch,
                          at(a.roll, a.n_roll, b), a.n_roll > 1 ? B : a.n_roll};
-        if (g->nmics) {   // every listener's workgroups encode the common block themselves; without angles it is encoded once
-            const EncodeBlock e{g->enc, g->in_c, (int)g->nmics, (const double*)x, nsamp};
-            if (a.any()) launch_rotation_encoded(blk, e, B, (int)g->nch, g->layout, cb, g->xrot, st, B, g->d.L, la, C * B);
-            else launch_encode_block(e, B, (int)g->nch, g->xrot, B, st);
-            x = g->xrot; x_c = x_c || (a.any() && cb); ldx = B; lsx = a.any() ? C * B : 0;
-        } else if (a.any()) {
-            launch_rotation(blk, x, x_c, B, (int)g->nch, g->layout, cb, false, g->xrot, st, nsamp, B, g->d.L, la, C * B);
-            x = g->xrot; x_c = x_c || cb; ldx = B; lsx = C * B;
+        if (s->nmics) {   // the encoder inside the rotation launch, in every listener's workgroups; without angles, alone and once
+            const EncodeBlock e{s->enc, s->in_c, (int)s->nmics, (const double*)x, nsamp};
+            if (turned) launch_rotation_encoded(blk, e, B, (int)C, s->layout, cb, s->xrot, st, B, L, la, C * B);
+            else launch_encode_block(e, B, (int)C, s->xrot, B, st);
+            x = s->xrot; x_c = x_c || (turned && cb); ldx = B; lsx = turned ? C * B : 0;
+        } else if (turned) {
+            launch_rotation(blk, x, x_c, B, (int)C, s->layout, cb, false, s->xrot, st, nsamp, B, L, la, C * B);
+            x = s->xrot; x_c = x_c || cb; ldx = B; lsx = C * B;
         }
-        // with a bank the kernels decide for every listener whether their set stands (section 9.4: the same bits either way)
-        const int* set = p.set_per > 1 ? sets.p + b : sets.p;
-        launch_decode_stream_block(g->d, x, x_c, ldx, p.set_per ? set : nullptr, -1, d_out + b * B, nsamp, st, lsx,
-                                   (int)(p.set_per > 1 ? nb : 1), 2 * nsamp);
+        // One listener: the host's copy of the selection, moved on as the kernels move theirs; three equal known indices are a
+        // standing set, which runs the plain instance.  More: the kernels decide for every listener (section 9.4: the same bits)
+        int standing = -1;
+        if (L == 1) {
+            int cur = -2;
+            if (p.set_per == 0) cur = s->known[0] == -2 ? -2 : std::max(s->known[0], 0);
+            else if (sets.host) cur = sets.host[p.set_per > 1 ? b : 0];
+            if (cur >= 0) {
+                const int s1 = s->known[0] == -1 ? cur : s->known[0], s2 = s->known[1] == -1 ? s1 : s->known[1];
+                if (s1 == cur && s2 == cur) standing = cur;
+            }
+            s->known[1] = s->known[0] == -1 ? cur : s->known[0];
+            s->known[0] = cur;
+        }
+        const int32_t* set = p.set_per > 1 ? sets.p + b : p.set_per ? sets.p : nullptr;
+        launch_decode_stream_block(s->d, x, x_c, ldx, set, standing, d_out + b * B, nsamp, st, lsx, (int)(p.set_per > 1 ? nb : 1), 2 * nsamp);
     }
 }
-}  // namespace
 
-extern "C" {
-
-int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
-                                int layout, int basis, int64_t block, emagls_decode_stream** out) {
-    return emagls_decode_stream_create_bank(nch, 1, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, out);
-}
-
-int emagls_decode_stream_create_bank(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
-                                     int in_is_complex, int layout, int basis, int64_t block, emagls_decode_stream** out) {
+// A push of device arrays on the caller's stream (the kernels clamp the indices: the host never sees them)
+int device_push(const Kind& k, emagls_decode_stream* s, const void* d_in, int64_t nsamp, const Sets& sets, const Angles& a, double* d_out,
+                void* stream) {
     return guarded_call([&] {
-        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        *out = nullptr;
-        *out = stream_create<emagls_decode_stream>(nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, 1);
-    });
-}
-
-static void check_encoder(int64_t nmics, const void* enc, int64_t nch) {
-    if (nmics < 1 || nmics > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "an encoded decode stream supports 1 to 64 microphones");
-    if (nch < 1 || nch > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "an encoded decode stream supports 1 to 64 channels");
-    if (!enc) throw Error(EMAGLS_ERR_ARG, "null pointer");
-}
-
-int emagls_decode_stream_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
-                                        const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
-                                        emagls_decode_stream** out) {
-    return guarded_call([&] {
-        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        *out = nullptr;
-        check_encoder(nmics, enc, nch);
-        *out = stream_create<emagls_decode_stream>(nch, n_sets, wL, wR, filters_are_complex, len, enc_is_complex, layout, basis, block, 1, nmics, enc);
-    });
-}
-
-int emagls_decode_group_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
-                                       const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
-                                       int64_t n_listeners, emagls_decode_group** out) {
-    return guarded_call([&] {
-        if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        *out = nullptr;
-        check_encoder(nmics, enc, nch);
-        *out = stream_create<emagls_decode_group>(nch, n_sets, wL, wR, filters_are_complex, len, enc_is_complex, layout, basis, block, n_listeners,
-                                                  nmics, enc);
-    });
-}
-
-int emagls_decode_stream_push_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const double* d_yaw, int64_t n_yaw,
-                                     const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll, double* d_out,
-                                     void* stream) {
-    return emagls_decode_stream_push_sets_device(s, d_in, nsamp, nullptr, 0, d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll, d_out, stream);
-}
-
-int emagls_decode_stream_push_sets_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
-                                          const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll,
-                                          int64_t n_roll, double* d_out, void* stream) {
-    return guarded_call([&] {
-        const Angles a{d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll};
-        const Sets sets{d_set, n_set};
-        stream_check_push(s, d_in, d_out, nsamp, a, sets);
+        const Push p = check_push(k, s, d_in, d_out, nsamp, a, sets);
         if (nsamp == 0) return;
         std::lock_guard<std::mutex> lk(s->mu);
         DeviceGuard dg(s->device);
-        stream_push_blocks(s, d_in, nsamp, a, sets, d_out, (hipStream_t)stream);   // (the kernels clamp the indices: the host never sees them)
+        push_blocks(s, d_in, nsamp, p, sets, d_out, (hipStream_t)stream);
     });
 }
 
-int emagls_decode_stream_push(emagls_decode_stream* s, const void* in, int64_t nsamp, const double* yaw, int64_t n_yaw, const double* pitch,
-                              int64_t n_pitch, const double* roll, int64_t n_roll, double* out) {
-    return emagls_decode_stream_push_sets(s, in, nsamp, nullptr, 0, yaw, n_yaw, pitch, n_pitch, roll, n_roll, out);
-}
-
-int emagls_decode_stream_push_sets(emagls_decode_stream* s, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set,
-                                   const double* yaw, int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll,
-                                   int64_t n_roll, double* out) {
+// A push of host arrays: staged on a pool stream, pushed, the result back, synchronised
+int host_push(const Kind& k, emagls_decode_stream* s, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set, Angles a, double* out) {
     return guarded_call([&] {
-        Angles a{yaw, n_yaw, pitch, n_pitch, roll, n_roll};
-        auto counted = [&](int64_t n) { return n >= 0 && (n <= 1 || n == nsamp); };
-        if (counted(n_pitch) && counted(n_roll)) a = host_angles(a);   // (zeros in a count that does not fit are reported, not dropped)
-        stream_check_push(s, in, out, nsamp, a, {set, n_set});
+        if (s) {   // (zeros in a count that does not fit are reported, not dropped)
+            auto counted = [&](int64_t n) { return n == 0 || n == s->d.L || n == s->d.L * nsamp; };
+            if (counted(a.n_pitch) && counted(a.n_roll)) a = host_angles(a);
+        }
+        const Push p = check_push(k, s, in, out, nsamp, a, {set, n_set});
         for (int64_t i = 0; i < n_set; ++i)
-            if (set[i] < 0 || set[i] >= s->d.S) throw Error(EMAGLS_ERR_ARG, "set index outside the stream's bank");
+            if (set[i] < 0 || set[i] >= s->d.S) throw Error(EMAGLS_ERR_ARG, k.outside_bank);
         if (nsamp == 0) return;
         std::lock_guard<std::mutex> lk(s->mu);
         DeviceGuard dg(s->device);
         s->ensure_device();
         hipStream_t st = pool_stream_take();
         struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
-        const size_t bin = esz(s->block_c()) * (size_t)nsamp * s->block_cols();
+        const size_t L = (size_t)s->d.L, bin = esz(s->block_c()) * (size_t)nsamp * s->block_cols();
         char* d_in = s->staged<char>(0, bin);
-        double* d_ang = s->staged<double>(1, sizeof(double) * 3 * (size_t)nsamp);
-        double* d_out = s->staged<double>(2, sizeof(double) * 2 * (size_t)nsamp);
+        double* d_ang = s->staged<double>(1, sizeof(double) * 3 * L * (size_t)nsamp);
+        double* d_out = s->staged<double>(2, sizeof(double) * 2 * L * (size_t)nsamp);
         HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
-        auto up = [&](const double* p, int64_t n, int slot) -> const double* {
+        auto up = [&](const double* q, int64_t n, int slot) -> const double* {
             if (!n) return nullptr;
-            double* dst = d_ang + (size_t)slot * nsamp;
-            HIP_CHECK(hipMemcpyAsync(dst, p, sizeof(double) * n, hipMemcpyHostToDevice, st));
+            double* dst = d_ang + (size_t)slot * L * nsamp;
+            HIP_CHECK(hipMemcpyAsync(dst, q, sizeof(double) * n, hipMemcpyHostToDevice, st));
             return dst;
         };
-        const Angles da{up(a.yaw, a.n_yaw, 0), a.n_yaw, up(a.pitch, a.n_pitch, 1), a.n_pitch, up(a.roll, a.n_roll, 2), a.n_roll};
+        Push dp = p;
+        dp.one.yaw = up(a.yaw, a.n_yaw, 0); dp.one.pitch = up(a.pitch, a.n_pitch, 1); dp.one.roll = up(a.roll, a.n_roll, 2);
         Sets dsets{nullptr, n_set, set};
         if (n_set) {
             int32_t* d_set = s->staged<int32_t>(3, sizeof(int32_t) * (size_t)n_set);
             HIP_CHECK(hipMemcpyAsync(d_set, set, sizeof(int32_t) * (size_t)n_set, hipMemcpyHostToDevice, st));
             dsets.p = d_set;
         }
-        stream_push_blocks(s, d_in, nsamp, da, dsets, d_out, st);
-        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * nsamp, hipMemcpyDeviceToHost, st));
+        push_blocks(s, d_in, nsamp, dp, dsets, d_out, st);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * L * nsamp, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
     });
 }
 
-int emagls_decode_stream_reset(emagls_decode_stream* s) {
+// listener: one listener, or -1: all of them
+int reset_object(const Kind& k, emagls_decode_stream* s, int64_t listener) {
     return guarded_call([&] {
-        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+        if (!s) throw Error(EMAGLS_ERR_ARG, k.null_handle);
+        if (listener < -1 || listener >= s->d.L) throw Error(EMAGLS_ERR_ARG, "listener outside the group (-1: all of them)");
         std::lock_guard<std::mutex> lk(s->mu);
         DeviceGuard dg(s->device);
         s->ensure_device();
         HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
-        s->zero_state(nullptr);
+        if (listener < 0) s->zero_state(nullptr, 0, s->d.L);
+        else s->zero_state(nullptr, listener, 1);
         HIP_CHECK(hipStreamSynchronize(nullptr));
     });
 }
 
-int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int64_t* partitions, int64_t* state_bytes, int64_t* filter_bytes,
-                              int* launches_per_block) {
+int info_object(const Kind& k, const emagls_decode_stream* s, int64_t* block, int64_t* partitions, int64_t* listeners, int64_t* state_bytes,
+                int64_t* filter_bytes, int* launches_per_block) {
     return guarded_call([&] {
-        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+        if (!s) throw Error(EMAGLS_ERR_ARG, k.null_handle);
         if (block) *block = s->d.B;
         if (partitions) *partitions = s->d.P;
+        if (listeners) *listeners = s->d.L;
         if (state_bytes) *state_bytes = (int64_t)s->state_bytes();
         if (filter_bytes) *filter_bytes = (int64_t)s->filter_bytes();
-        if (launches_per_block) *launches_per_block = 3;   // rotation (encoded: with the encoder, or the encoder alone), forward transform with the products, inverse transform
+        // for all listeners: rotation (encoded: with the encoder, or the encoder alone), forward transform with the products, inverse transform
+        if (launches_per_block) *launches_per_block = 3;
     });
 }
 
-int emagls_decode_stream_sets(const emagls_decode_stream* s, int64_t* n_sets) {
-    return guarded_call([&] {
-        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
-        if (!n_sets) throw Error(EMAGLS_ERR_ARG, "null pointer");
-        *n_sets = s->d.S;
-    });
-}
-
-int emagls_decode_stream_destroy(emagls_decode_stream* s) {
+int destroy_object(emagls_decode_stream* s) {
     return guarded_call([&] {
         if (!s) return;
         {
@@ -894,112 +760,160 @@ int emagls_decode_stream_destroy(emagls_decode_stream* s) {
     });
 }
 
-// ---- the listener group
-int emagls_decode_group_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
-                               int in_is_complex, int layout, int basis, int64_t block, int64_t n_listeners, emagls_decode_group** out) {
+// The creation of the object, every argument checked before the device is touched
+// encoded: nmics microphones, enc [nch x nmics] column-major (interleaved complex when in_is_complex, which then says what the
+// ENCODED signal is; the pushed microphone blocks are real)
+int create_object(bool encoded, int64_t nmics, const void* enc, int64_t nch, int64_t n_sets, const void* wL, const void* wR,
+                  int filters_are_complex, int64_t len, int in_is_complex, int layout, int basis, int64_t block, int64_t listeners,
+                  emagls_decode_stream** out) {
     return guarded_call([&] {
         if (!wL || !wR || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
         *out = nullptr;
-        *out = stream_create<emagls_decode_group>(nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block,
-                                                  n_listeners);
+        if (encoded) {
+            if (nmics < 1 || nmics > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "an encoded decode stream supports 1 to 64 microphones");
+            if (nch < 1 || nch > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "an encoded decode stream supports 1 to 64 channels");
+            if (!enc) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        }
+        if (nch < 1 || len < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        if (n_sets < 1) throw Error(EMAGLS_ERR_ARG, "a decode stream needs at least one filter set");
+        if (n_sets > kDecodeStreamMaxSets) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports banks of up to 65536 filter sets");
+        if (listeners < 1) throw Error(EMAGLS_ERR_ARG, "a listener group needs at least one listener");
+        if (listeners > kDecodeGroupMaxListeners) throw Error(EMAGLS_ERR_UNSUPPORTED, "a listener group supports up to 4096 listeners");
+        if (layout != EMAGLS_LAYOUT_SH && layout != EMAGLS_LAYOUT_CH) throw Error(EMAGLS_ERR_ARG, "layout must be EMAGLS_LAYOUT_SH or EMAGLS_LAYOUT_CH");
+        check_basis(basis);
+        if (!decode_stream_block_ok(block))
+            throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports block sizes 64, 128, 256, 512, 1024 and 2048");
+        if (len > 16384) throw Error(EMAGLS_ERR_UNSUPPORTED, "the decode stream supports filters of up to 16384 taps");
+        std::unique_ptr<emagls_decode_stream> s(new emagls_decode_stream);
+        s->nch = nch; s->len = len; s->layout = layout; s->basis = basis; s->in_c = in_is_complex != 0;
+        s->d.C = (int)nch; s->d.B = (int)block; s->d.P = (int)ceil_div(len, block); s->d.S = (int)n_sets; s->d.L = (int)listeners;
+        // a rotation in the complex basis makes a real signal complex: such a stream runs on 2C planes from the start
+        s->d.planes2 = s->in_c || (basis == EMAGLS_BASIS_COMPLEX && rotate_order(layout, nch) >= 0);
+        if (encoded) {
+            const int k = s->in_c ? 2 : 1;
+            const double* e = reinterpret_cast<const double*>(enc);
+            s->nmics = nmics;
+            s->enc_host.resize((size_t)nch * nmics * k);
+            for (int64_t c = 0; c < nch; ++c)
+                for (int64_t m = 0; m < nmics; ++m)
+                    for (int i = 0; i < k; ++i) s->enc_host[(size_t)(c * nmics + m) * k + i] = e[(size_t)(m * nch + c) * k + i];
+        }
+        const int Cp = s->cp();
+        const bool wc = filters_are_complex != 0;
+        s->wpl.assign((size_t)n_sets * 2 * Cp * len, 0.0);
+        for (int64_t set = 0; set < n_sets; ++set)
+            for (int e = 0; e < 2; ++e) {
+                const double* w = reinterpret_cast<const double*>(e ? wR : wL) + (size_t)set * nch * len * (wc ? 2 : 1);
+                double* pl = s->wpl.data() + ((size_t)set * 2 + e) * Cp * len;
+                for (int64_t c = 0; c < nch; ++c)
+                    for (int64_t t = 0; t < len; ++t) {
+                        const size_t i = (size_t)(c * len + t);
+                        pl[(size_t)c * len + t] = wc ? w[2 * i] : w[i];
+                        if (wc && s->d.planes2) pl[(size_t)(nch + c) * len + t] = -w[2 * i + 1];
+                    }
+            }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
+            std::lock_guard<std::mutex> lk(s->mu);
+            s->ensure_device();
+        } else {
+            (void)hipGetLastError();
+        }
+        *out = s.release();
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int emagls_decode_stream_create(int64_t nch, const void* wL, const void* wR, int filters_are_complex, int64_t len, int in_is_complex,
+                                int layout, int basis, int64_t block, emagls_decode_stream** out) {
+    return create_object(false, 0, nullptr, nch, 1, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, 1, out);
+}
+
+int emagls_decode_stream_create_bank(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
+                                     int in_is_complex, int layout, int basis, int64_t block, emagls_decode_stream** out) {
+    return create_object(false, 0, nullptr, nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, 1, out);
+}
+
+int emagls_decode_stream_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
+                                        const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
+                                        emagls_decode_stream** out) {
+    return create_object(true, nmics, enc, nch, n_sets, wL, wR, filters_are_complex, len, enc_is_complex, layout, basis, block, 1, out);
+}
+
+int emagls_decode_group_create(int64_t nch, int64_t n_sets, const void* wL, const void* wR, int filters_are_complex, int64_t len,
+                               int in_is_complex, int layout, int basis, int64_t block, int64_t n_listeners, emagls_decode_group** out) {
+    return create_object(false, 0, nullptr, nch, n_sets, wL, wR, filters_are_complex, len, in_is_complex, layout, basis, block, n_listeners,
+                         reinterpret_cast<emagls_decode_stream**>(out));
+}
+
+int emagls_decode_group_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
+                                       const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
+                                       int64_t n_listeners, emagls_decode_group** out) {
+    return create_object(true, nmics, enc, nch, n_sets, wL, wR, filters_are_complex, len, enc_is_complex, layout, basis, block, n_listeners,
+                         reinterpret_cast<emagls_decode_stream**>(out));
+}
+
+int emagls_decode_stream_push_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const double* d_yaw, int64_t n_yaw,
+                                     const double* d_pitch, int64_t n_pitch, const double* d_roll, int64_t n_roll, double* d_out,
+                                     void* stream) {
+    return device_push(kStream, s, d_in, nsamp, {}, {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, d_out, stream);
+}
+
+int emagls_decode_stream_push_sets_device(emagls_decode_stream* s, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
+                                          const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll,
+                                          int64_t n_roll, double* d_out, void* stream) {
+    return device_push(kStream, s, d_in, nsamp, {d_set, n_set}, {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, d_out, stream);
 }
 
 int emagls_decode_group_push_device(emagls_decode_group* g, const void* d_in, int64_t nsamp, const int32_t* d_set, int64_t n_set,
                                     const double* d_yaw, int64_t n_yaw, const double* d_pitch, int64_t n_pitch, const double* d_roll,
                                     int64_t n_roll, double* d_out, void* stream) {
-    return guarded_call([&] {
-        const Sets sets{d_set, n_set};
-        const GroupPush p = group_check_push(g, d_in, d_out, nsamp, {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, sets);
-        if (nsamp == 0) return;
-        std::lock_guard<std::mutex> lk(g->mu);
-        DeviceGuard dg(g->device);
-        group_push_blocks(g, d_in, nsamp, p, sets, d_out, (hipStream_t)stream);   // (the kernels clamp the indices: the host never sees them)
-    });
+    return device_push(kGroup, object_of(g), d_in, nsamp, {d_set, n_set}, {d_yaw, n_yaw, d_pitch, n_pitch, d_roll, n_roll}, d_out, stream);
+}
+
+int emagls_decode_stream_push(emagls_decode_stream* s, const void* in, int64_t nsamp, const double* yaw, int64_t n_yaw, const double* pitch,
+                              int64_t n_pitch, const double* roll, int64_t n_roll, double* out) {
+    return host_push(kStream, s, in, nsamp, nullptr, 0, {yaw, n_yaw, pitch, n_pitch, roll, n_roll}, out);
+}
+
+int emagls_decode_stream_push_sets(emagls_decode_stream* s, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set,
+                                   const double* yaw, int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll,
+                                   int64_t n_roll, double* out) {
+    return host_push(kStream, s, in, nsamp, set, n_set, {yaw, n_yaw, pitch, n_pitch, roll, n_roll}, out);
 }
 
 int emagls_decode_group_push(emagls_decode_group* g, const void* in, int64_t nsamp, const int32_t* set, int64_t n_set, const double* yaw,
                              int64_t n_yaw, const double* pitch, int64_t n_pitch, const double* roll, int64_t n_roll, double* out) {
-    return guarded_call([&] {
-        Angles a{yaw, n_yaw, pitch, n_pitch, roll, n_roll};
-        if (g) {   // (zeros in a count that does not fit are reported, not dropped)
-            auto counted = [&](int64_t n) { return n == 0 || n == g->d.L || n == g->d.L * nsamp; };
-            if (counted(n_pitch) && counted(n_roll)) a = host_angles(a);
-        }
-        const GroupPush p = group_check_push(g, in, out, nsamp, a, {set, n_set});
-        for (int64_t i = 0; i < n_set; ++i)
-            if (set[i] < 0 || set[i] >= g->d.S) throw Error(EMAGLS_ERR_ARG, "set index outside the group's bank");
-        if (nsamp == 0) return;
-        std::lock_guard<std::mutex> lk(g->mu);
-        DeviceGuard dg(g->device);
-        g->ensure_device();
-        hipStream_t st = pool_stream_take();
-        struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
-        const size_t L = (size_t)g->d.L, bin = esz(g->block_c()) * (size_t)nsamp * g->block_cols();
-        char* d_in = g->staged<char>(0, bin);
-        double* d_ang = g->staged<double>(1, sizeof(double) * 3 * L * (size_t)nsamp);
-        double* d_out = g->staged<double>(2, sizeof(double) * 2 * L * (size_t)nsamp);
-        HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
-        auto up = [&](const double* q, int64_t n, int slot) -> const double* {
-            if (!n) return nullptr;
-            double* dst = d_ang + (size_t)slot * L * nsamp;
-            HIP_CHECK(hipMemcpyAsync(dst, q, sizeof(double) * n, hipMemcpyHostToDevice, st));
-            return dst;
-        };
-        GroupPush dp = p;
-        dp.one.yaw = up(a.yaw, a.n_yaw, 0); dp.one.pitch = up(a.pitch, a.n_pitch, 1); dp.one.roll = up(a.roll, a.n_roll, 2);
-        Sets dsets{nullptr, n_set};
-        if (n_set) {
-            int32_t* d_set = g->staged<int32_t>(3, sizeof(int32_t) * (size_t)n_set);
-            HIP_CHECK(hipMemcpyAsync(d_set, set, sizeof(int32_t) * (size_t)n_set, hipMemcpyHostToDevice, st));
-            dsets.p = d_set;
-        }
-        group_push_blocks(g, d_in, nsamp, dp, dsets, d_out, st);
-        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * L * nsamp, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    });
+    return host_push(kGroup, object_of(g), in, nsamp, set, n_set, {yaw, n_yaw, pitch, n_pitch, roll, n_roll}, out);
 }
 
-int emagls_decode_group_reset(emagls_decode_group* g, int64_t listener) {
-    return guarded_call([&] {
-        if (!g) throw Error(EMAGLS_ERR_ARG, "null decode group");
-        if (listener < -1 || listener >= g->d.L) throw Error(EMAGLS_ERR_ARG, "listener outside the group (-1: all of them)");
-        std::lock_guard<std::mutex> lk(g->mu);
-        DeviceGuard dg(g->device);
-        g->ensure_device();
-        HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
-        if (listener < 0) g->zero_state(nullptr, 0, g->d.L);
-        else g->zero_state(nullptr, listener, 1);
-        HIP_CHECK(hipStreamSynchronize(nullptr));
-    });
+int emagls_decode_stream_reset(emagls_decode_stream* s) { return reset_object(kStream, s, -1); }
+
+int emagls_decode_group_reset(emagls_decode_group* g, int64_t listener) { return reset_object(kGroup, object_of(g), listener); }
+
+int emagls_decode_stream_info(const emagls_decode_stream* s, int64_t* block, int64_t* partitions, int64_t* state_bytes, int64_t* filter_bytes,
+                              int* launches_per_block) {
+    return info_object(kStream, s, block, partitions, nullptr, state_bytes, filter_bytes, launches_per_block);
 }
 
 int emagls_decode_group_info(const emagls_decode_group* g, int64_t* block, int64_t* partitions, int64_t* listeners,
                              int64_t* state_bytes, int64_t* filter_bytes, int* launches_per_block) {
+    return info_object(kGroup, object_of(g), block, partitions, listeners, state_bytes, filter_bytes, launches_per_block);
+}
+
+int emagls_decode_stream_sets(const emagls_decode_stream* s, int64_t* n_sets) {
     return guarded_call([&] {
-        if (!g) throw Error(EMAGLS_ERR_ARG, "null decode group");
-        if (block) *block = g->d.B;
-        if (partitions) *partitions = g->d.P;
-        if (listeners) *listeners = g->d.L;
-        if (state_bytes) *state_bytes = (int64_t)g->state_bytes();
-        if (filter_bytes) *filter_bytes = (int64_t)g->filter_bytes();
-        if (launches_per_block) *launches_per_block = 3;   // for the whole group: rotation, forward transform with the products, inverse
+        if (!s) throw Error(EMAGLS_ERR_ARG, "null decode stream");
+        if (!n_sets) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *n_sets = s->d.S;
     });
 }
 
-int emagls_decode_group_destroy(emagls_decode_group* g) {
-    return guarded_call([&] {
-        if (!g) return;
-        {
-            std::lock_guard<std::mutex> lk(g->mu);
-            if (g->ready) {
-                DeviceGuard dg(g->device);
-                (void)hipDeviceSynchronize();
-                g->release();
-            }
-        }
-        delete g;
-    });
-}
+int emagls_decode_stream_destroy(emagls_decode_stream* s) { return destroy_object(s); }
+
+int emagls_decode_group_destroy(emagls_decode_group* g) { return destroy_object(object_of(g)); }
 
 }  // extern "C"

@@ -59,27 +59,53 @@ int radial_type(const mxArray* a) {
     mexErrMsgIdAndTxt("eMagLS:arg", "Unkown radialFilter parameter \"%s\".", buf);
     return 0;
 }
-// decode streams live in a table; MATLAB holds the 1-based index (mex/binauralDecodeStream.m)
-std::vector<emagls_decode_stream*> g_streams;
-struct StreamShape { mwSize nch; bool in_complex; };
-std::vector<StreamShape> g_stream_shapes;   // what 'stream_push' checks its block against
-emagls_decode_stream* stream_of(const mxArray* a, size_t* index = nullptr) {
-    const double v = (a && mxIsDouble(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
-    const size_t i = (v >= 1 && v <= (double)g_streams.size() && v == std::floor(v)) ? (size_t)v : 0;
-    if (!i || !g_streams[i - 1]) mexErrMsgIdAndTxt("eMagLS:arg", "invalid decode stream handle");
-    if (index) *index = i - 1;
-    return g_streams[i - 1];
+// decode streams and listener groups live in a table each; MATLAB holds the 1-based index (mex/binauralDecodeStream.m,
+// mex/binauralDecodeGroup.m).  what: the kind's word in the messages
+template <typename H> struct HandleTable {
+    struct Entry { H* h; mwSize cols; bool in_complex; mwSize listeners; };   // with what a push checks its block against
+    const char* what;
+    std::vector<Entry> entries;
+    Entry& of(const mxArray* a) {
+        const double v = (a && mxIsDouble(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
+        const size_t i = (v >= 1 && v <= (double)entries.size() && v == std::floor(v)) ? (size_t)v : 0;
+        if (!i || !entries[i - 1].h) mexErrMsgIdAndTxt("eMagLS:arg", "invalid decode %s handle", what);
+        return entries[i - 1];
+    }
+    mxArray* add(const Entry& e) {   // into the first free slot
+        size_t slot = 0;
+        while (slot < entries.size() && entries[slot].h) ++slot;
+        if (slot == entries.size()) entries.push_back(e);
+        else entries[slot] = e;
+        return mxCreateDoubleScalar((double)(slot + 1));
+    }
+    // the block of a push: [n x cols], real or complex as the object was created
+    void check_block(const Entry& e, const mxArray* in) const {
+        if (!mxIsDouble(in) || mxGetN(in) != e.cols)
+            mexErrMsgIdAndTxt("eMagLS:arg", "in must be a double array with the filters' channel count (%d)", (int)e.cols);
+        if ((bool)mxIsComplex(in) != e.in_complex)
+            mexErrMsgIdAndTxt("eMagLS:arg", "in must be %s, as the %s was created", e.in_complex ? "complex" : "real", what);
+    }
+};
+HandleTable<emagls_decode_stream> g_streams{"stream"};
+HandleTable<emagls_decode_group> g_groups{"group"};
+// an array of one listener's worth of values but the wrong orientation would be read as another listener's: the last dimension
+// must be the listeners
+void per_listener(const mxArray* a, const char* what, mwSize listeners) {
+    if (mxGetNumberOfDimensions(a) > 2 || mxGetN(a) != listeners)
+        mexErrMsgIdAndTxt("eMagLS:arg", "%s must have one column per listener (%d)", what, (int)listeners);
 }
-// listener groups likewise (mex/binauralDecodeGroup.m)
-std::vector<emagls_decode_group*> g_groups;
-struct GroupShape { mwSize nch; bool in_complex; mwSize listeners; };
-std::vector<GroupShape> g_group_shapes;
-emagls_decode_group* group_of(const mxArray* a, size_t* index = nullptr) {
-    const double v = (a && mxIsDouble(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
-    const size_t i = (v >= 1 && v <= (double)g_groups.size() && v == std::floor(v)) ? (size_t)v : 0;
-    if (!i || !g_groups[i - 1]) mexErrMsgIdAndTxt("eMagLS:arg", "invalid decode group handle");
-    if (index) *index = i - 1;
-    return g_groups[i - 1];
+// the three optional angles of a push, prhs[3..5]: [] or absent: none.  listeners > 0: a group's, one column per listener
+struct PushAngles { const double* p[3] = {nullptr, nullptr, nullptr}; int64_t n[3] = {0, 0, 0}; };
+PushAngles push_angles(int nrhs, const mxArray* const* prhs, mwSize listeners) {
+    static const char* const names[3] = {"horRotAngleRad", "pitchRad", "rollRad"};
+    PushAngles a;
+    for (int i = 0; i < 3; ++i)
+        if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) {
+            if (listeners) per_listener(prhs[3 + i], names[i], listeners);
+            a.p[i] = dbl(prhs[3 + i], names[i]);
+            a.n[i] = (int64_t)mxGetNumberOfElements(prhs[3 + i]);
+        }
+    return a;
 }
 int layout_of(const mxArray* a) {
     if (!a || mxIsEmpty(a)) return EMAGLS_LAYOUT_SH;
@@ -128,8 +154,8 @@ std::vector<int32_t> zero_based(const mxArray* a) {
 }
 // the plans the one-shot entry points cache (device buffers, captured graphs) are released when the MEX file is cleared
 void at_exit() {
-    for (emagls_decode_stream*& s : g_streams) { if (s) emagls_decode_stream_destroy(s); s = nullptr; }
-    for (emagls_decode_group*& g : g_groups) { if (g) emagls_decode_group_destroy(g); g = nullptr; }
+    for (auto& e : g_streams.entries) { if (e.h) emagls_decode_stream_destroy(e.h); e.h = nullptr; }
+    for (auto& e : g_groups.entries) { if (e.h) emagls_decode_group_destroy(e.h); e.h = nullptr; }
     emagls_cache_clear();
 }
 
@@ -149,7 +175,7 @@ void at_exit() {
 // out = emagls_mex('stream_push', h, in[, yawRad, pitchRad, rollRad, setIndex])   in [k*blockSize x nch]; each angle [], a scalar or one per
 //                                     sample; setIndex ONE-based: [] (keep the set), a scalar or one per block
 // emagls_mex('stream_reset', h)      emagls_mex('stream_destroy', h)
-// h = emagls_mex('group_create', wL, wR, blockSize, numListeners[, shDefinition, domain, complexInput])   a listener group
+// h = emagls_mex('group_create', wL, wR, blockSize, numListeners[, shDefinition, domain, complexInput, encoder])   a listener group
 //                                     (mex/binauralDecodeGroup.m): many listeners of one sound field in one push
 // out = emagls_mex('group_push', h, in[, yawRad, pitchRad, rollRad, setIndex])   in [k*blockSize x nch], the common signal; listeners run
 //                                     along the last dimension: out [n x 2 x L]; each angle [], [1 x L] or [n x L]; setIndex ONE-based,
@@ -217,62 +243,46 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         return;
     }
     if (c == "stream_create") {
-        if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "stream_create needs (wL, wR, blockSize[, shDefinition, domain, complexInput])");
+        if (nrhs < 4) mexErrMsgIdAndTxt("eMagLS:arg", "stream_create needs (wL, wR, blockSize[, shDefinition, domain, complexInput, encoder])");
         const FilterArgs f = filter_args(prhs);
-        const mwSize len = f.len, ch = f.ch, nsets = f.nsets;
-        const bool wc = f.wc;
         const int basis = basis_of(nrhs > 4 ? prhs[4] : nullptr), layout = layout_of(nrhs > 5 ? prhs[5] : nullptr);
         const int ic = nrhs > 6 && truthy(prhs[6]);
         const mxArray* enc = nrhs > 7 ? prhs[7] : nullptr;
-        const mwSize nmics = encoder_arg(enc, ch, ic != 0);
+        const mwSize nmics = encoder_arg(enc, f.ch, ic != 0);
         emagls_decode_stream* st = nullptr;
-        const int rc = nmics ? emagls_decode_stream_create_encoded((int64_t)nmics, in_ptr(enc), mxIsComplex(enc), (int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]),
-                                                                   in_ptr(prhs[2]), wc, (int64_t)len, layout, basis, (int64_t)mxGetScalar(prhs[3]), &st)
-                             : emagls_decode_stream_create_bank((int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), wc, (int64_t)len, ic,
+        const int rc = nmics ? emagls_decode_stream_create_encoded((int64_t)nmics, in_ptr(enc), mxIsComplex(enc), (int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]),
+                                                                   in_ptr(prhs[2]), f.wc, (int64_t)f.len, layout, basis, (int64_t)mxGetScalar(prhs[3]), &st)
+                             : emagls_decode_stream_create_bank((int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc, (int64_t)f.len, ic,
                                                                 layout, basis, (int64_t)mxGetScalar(prhs[3]), &st);
         if (rc) fail(rc);
-        size_t slot = 0;
-        while (slot < g_streams.size() && g_streams[slot]) ++slot;
-        if (slot == g_streams.size()) { g_streams.push_back(nullptr); g_stream_shapes.push_back({0, false}); }
-        g_streams[slot] = st;
-        g_stream_shapes[slot] = {nmics ? nmics : ch, ic != 0};   // (an encoded stream is pushed [n x numMics] blocks)
-        plhs[0] = mxCreateDoubleScalar((double)(slot + 1));
+        plhs[0] = g_streams.add({st, nmics ? nmics : f.ch, ic != 0, 0});   // (an encoded stream is pushed [n x numMics] blocks)
         return;
     }
     if (c == "stream_push") {
         if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "stream_push needs (handle, in[, yawRad, pitchRad, rollRad, setIndex])");
-        size_t slot = 0;
-        emagls_decode_stream* st = stream_of(prhs[1], &slot);
-        if (!mxIsDouble(prhs[2]) || mxGetN(prhs[2]) != g_stream_shapes[slot].nch)
-            mexErrMsgIdAndTxt("eMagLS:arg", "in must be a double array with the filters' channel count (%d)", (int)g_stream_shapes[slot].nch);
-        if ((bool)mxIsComplex(prhs[2]) != g_stream_shapes[slot].in_complex)
-            mexErrMsgIdAndTxt("eMagLS:arg", "in must be %s, as the stream was created", g_stream_shapes[slot].in_complex ? "complex" : "real");
+        const auto& e = g_streams.of(prhs[1]);
+        g_streams.check_block(e, prhs[2]);
         const mwSize n = mxGetM(prhs[2]);
-        const double* ang[3] = {nullptr, nullptr, nullptr};
-        mwSize cnt[3] = {0, 0, 0};
-        static const char* const names[3] = {"horRotAngleRad", "pitchRad", "rollRad"};
-        for (int i = 0; i < 3; ++i)
-            if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) { ang[i] = dbl(prhs[3 + i], names[i]); cnt[i] = mxGetNumberOfElements(prhs[3 + i]); }
+        const PushAngles a = push_angles(nrhs, prhs, 0);
         // setIndex (prhs[6]): MATLAB counts the sets from 1, the library from 0
         const std::vector<int32_t> sets = zero_based(nrhs > 6 ? prhs[6] : nullptr);
         plhs[0] = mxCreateDoubleMatrix(n, 2, mxREAL);
-        const int rc = emagls_decode_stream_push_sets(st, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(),
-                                                      ang[0], (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2], (int64_t)cnt[2],
-                                                      mxGetDoubles(plhs[0]));
+        const int rc = emagls_decode_stream_push_sets(e.h, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(),
+                                                      a.p[0], a.n[0], a.p[1], a.n[1], a.p[2], a.n[2], mxGetDoubles(plhs[0]));
         if (rc) fail(rc);
         return;
     }
     if (c == "stream_reset" || c == "stream_destroy") {
         if (nrhs < 2) mexErrMsgIdAndTxt("eMagLS:arg", "%s needs (handle)", cmd);
-        size_t slot = 0;
-        emagls_decode_stream* st = stream_of(prhs[1], &slot);
-        const int rc = c == "stream_reset" ? emagls_decode_stream_reset(st) : emagls_decode_stream_destroy(st);
-        if (c == "stream_destroy") g_streams[slot] = nullptr;
+        auto& e = g_streams.of(prhs[1]);
+        const int rc = c == "stream_reset" ? emagls_decode_stream_reset(e.h) : emagls_decode_stream_destroy(e.h);
+        if (c == "stream_destroy") e.h = nullptr;
         if (rc) fail(rc);
         return;
     }
     if (c == "group_create") {
-        if (nrhs < 5) mexErrMsgIdAndTxt("eMagLS:arg", "group_create needs (wL, wR, blockSize, numListeners[, shDefinition, domain, complexInput])");
+        if (nrhs < 5)
+            mexErrMsgIdAndTxt("eMagLS:arg", "group_create needs (wL, wR, blockSize, numListeners[, shDefinition, domain, complexInput, encoder])");
         const FilterArgs f = filter_args(prhs);
         const int basis = basis_of(nrhs > 5 ? prhs[5] : nullptr), layout = layout_of(nrhs > 6 ? prhs[6] : nullptr);
         const int ic = nrhs > 7 && truthy(prhs[7]);
@@ -286,53 +296,28 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                              : emagls_decode_group_create((int64_t)f.ch, (int64_t)f.nsets, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc, (int64_t)f.len, ic, layout,
                                                           basis, (int64_t)mxGetScalar(prhs[3]), (int64_t)nl, &g);
         if (rc) fail(rc);
-        size_t slot = 0;
-        while (slot < g_groups.size() && g_groups[slot]) ++slot;
-        if (slot == g_groups.size()) { g_groups.push_back(nullptr); g_group_shapes.push_back({0, false, 0}); }
-        g_groups[slot] = g;
-        g_group_shapes[slot] = {nmics ? nmics : f.ch, ic != 0, (mwSize)nl};
-        plhs[0] = mxCreateDoubleScalar((double)(slot + 1));
+        plhs[0] = g_groups.add({g, nmics ? nmics : f.ch, ic != 0, (mwSize)nl});
         return;
     }
     if (c == "group_push") {
         // listeners run along the LAST dimension: column-major [n x L] is the library's listener-major [L][n]
         if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "group_push needs (handle, in[, yawRad, pitchRad, rollRad, setIndex])");
-        size_t slot = 0;
-        emagls_decode_group* g = group_of(prhs[1], &slot);
-        const GroupShape& gs = g_group_shapes[slot];
-        if (!mxIsDouble(prhs[2]) || mxGetN(prhs[2]) != gs.nch)
-            mexErrMsgIdAndTxt("eMagLS:arg", "in must be a double array with the filters' channel count (%d)", (int)gs.nch);
-        if ((bool)mxIsComplex(prhs[2]) != gs.in_complex)
-            mexErrMsgIdAndTxt("eMagLS:arg", "in must be %s, as the group was created", gs.in_complex ? "complex" : "real");
+        const auto& e = g_groups.of(prhs[1]);
+        g_groups.check_block(e, prhs[2]);
         const mwSize n = mxGetM(prhs[2]);
-        // an array of one listener's worth of values but the wrong orientation would be read as another listener's: the last
-        // dimension must be the listeners
-        auto per_listener = [&](const mxArray* a, const char* what) {
-            if (mxGetNumberOfDimensions(a) > 2 || mxGetN(a) != gs.listeners)
-                mexErrMsgIdAndTxt("eMagLS:arg", "%s must have one column per listener (%d)", what, (int)gs.listeners);
-        };
-        const double* ang[3] = {nullptr, nullptr, nullptr};
-        mwSize cnt[3] = {0, 0, 0};
-        static const char* const names[3] = {"horRotAngleRad", "pitchRad", "rollRad"};
-        for (int i = 0; i < 3; ++i)
-            if (nrhs > 3 + i && !mxIsEmpty(prhs[3 + i])) {
-                per_listener(prhs[3 + i], names[i]);
-                ang[i] = dbl(prhs[3 + i], names[i]);
-                cnt[i] = mxGetNumberOfElements(prhs[3 + i]);
-            }
-        if (nrhs > 6 && !mxIsEmpty(prhs[6])) per_listener(prhs[6], "setIndex");
+        const PushAngles a = push_angles(nrhs, prhs, e.listeners);
+        if (nrhs > 6 && !mxIsEmpty(prhs[6])) per_listener(prhs[6], "setIndex", e.listeners);
         const std::vector<int32_t> sets = zero_based(nrhs > 6 ? prhs[6] : nullptr);   // [nBlocks x L], one-based
-        const mwSize dims[3] = {n, 2, gs.listeners};
+        const mwSize dims[3] = {n, 2, e.listeners};
         plhs[0] = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
-        const int rc = emagls_decode_group_push(g, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(), ang[0],
-                                                (int64_t)cnt[0], ang[1], (int64_t)cnt[1], ang[2], (int64_t)cnt[2], mxGetDoubles(plhs[0]));
+        const int rc = emagls_decode_group_push(e.h, in_ptr(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(), (int64_t)sets.size(), a.p[0],
+                                                a.n[0], a.p[1], a.n[1], a.p[2], a.n[2], mxGetDoubles(plhs[0]));
         if (rc) fail(rc);
         return;
     }
     if (c == "group_reset" || c == "group_destroy") {
         if (nrhs < 2) mexErrMsgIdAndTxt("eMagLS:arg", "%s needs (handle)", cmd);
-        size_t slot = 0;
-        emagls_decode_group* g = group_of(prhs[1], &slot);
+        auto& e = g_groups.of(prhs[1]);
         int64_t listener = -1;   // 'group_reset', h, listener: ONE-based; [] or absent: all listeners
         if (c == "group_reset" && nrhs > 2 && !mxIsEmpty(prhs[2])) {
             const double v = mxGetScalar(prhs[2]);
@@ -340,8 +325,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                 mexErrMsgIdAndTxt("eMagLS:arg", "listener must be a positive integer (the listeners count from 1)");
             listener = (int64_t)v - 1;
         }
-        const int rc = c == "group_reset" ? emagls_decode_group_reset(g, listener) : emagls_decode_group_destroy(g);
-        if (c == "group_destroy") g_groups[slot] = nullptr;
+        const int rc = c == "group_reset" ? emagls_decode_group_reset(e.h, listener) : emagls_decode_group_destroy(e.h);
+        if (c == "group_destroy") e.h = nullptr;
         if (rc) fail(rc);
         return;
     }
