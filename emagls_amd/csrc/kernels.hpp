@@ -1,4 +1,4 @@
-// Launcher declarations shared by the kernel translation units and the C ABI (capi.hip, decode_api.hip, render_api.hip).
+// Launcher declarations shared by the kernel translation units and the C ABI (capi.hip and jobs.hip over host_internal.hpp, decode_api.hip, render_api.hip).
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -328,10 +328,10 @@ void launch_rh_gemm(const double* Tt, int64_t ldR, const double* Yk, int64_t ldY
 void launch_rh_atf(const void* W, const void* A, int M, int P, int64_t D, int nsets, const RhOut& o, hipStream_t st);
 void launch_rh_reduce(const double* partial, int64_t nrows, int ntile, double* out, hipStream_t st);
 
-// ---- capi.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool)
+// ---- host_pools.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool in host_internal.hpp)
 hipStream_t pool_stream_take();
 void pool_stream_give(hipStream_t st);
-// ---- capi.hip: runs f, maps exceptions to the C status codes and records the message for emagls_last_error()
+// ---- host_pools.hip: runs f, maps exceptions to the C status codes and records the message for emagls_last_error()
 int guarded_call(const std::function<void()>& f);
 
 }  // namespace emagls
