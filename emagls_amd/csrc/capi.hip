@@ -2932,6 +2932,14 @@ int emagls_self_test(int which, double* max_err) {
     });
 }
 
+int emagls_debug_synth_operand(const void* bsc, int nbins, int nord_pad, const double* x, int64_t nx, int gs, void* g_plus, void* g_minus) {
+    return guarded([&] { synth_operand_debug(bsc, nbins, nord_pad, x, nx, gs, g_plus, g_minus); });
+}
+
+int emagls_debug_synth_cosines(const double* dir_azi, const double* dir_zen, int64_t ndirs, const double* mic_azi, const double* mic_zen, int nmics, double* x2) {
+    return guarded([&] { synth_cosines_debug(dir_azi, dir_zen, ndirs, mic_azi, mic_zen, nmics, x2); });
+}
+
 int emagls_fp64_peak_tflops_ex(int which, int burst, double* tflops, double* shader_mhz) {
     return guarded([&] {
         if (!tflops || which < 0 || which > 2) throw Error(EMAGLS_ERR_ARG, "invalid argument");

@@ -121,6 +121,10 @@ int synth_ls_chunks(int D);
 void launch_synth_ls(const void* Hc, int64_t ldH, int n_c, const void* bsc, int nord_pad, const double* dir_azi, const double* dir_zen, const double* mic_azi,
                      const double* mic_zen, const int* smap, int D, int M, int P, int kb_lo, int kb_hi, void* Upart, hipStream_t st, bool shared_geometry = false);
 void launch_sweep_synth(const HalfSweepMulti& m, hipStream_t st);
+// ---- synth_debug.hip: synth_group<gs> on host arrays (bsc [nbins][nord_pad], x [nx]): g_plus / g_minus [nbins][nx] = E + O / E - O; synchronous
+// x2 [ndirs][nmics] = synth_x2 (twice the cosine between direction and microphone, as the sweeps form it) on host arrays; synchronous
+void synth_cosines_debug(const double* dir_azi, const double* dir_zen, int64_t ndirs, const double* mic_azi, const double* mic_zen, int nmics, double* x2);
+void synth_operand_debug(const void* bsc, int nbins, int nord_pad, const double* x, int64_t nx, int gs, void* g_plus, void* g_minus);
 // ---- sweep_reg.hip: the synthesising sweep with the operand in registers (a lane = a direction; no slab in LDS).  Units = antipodal
 // microphone pairs + single microphones (smap[32] + smap[33]); argument blocks in device memory (store_sweep_args)
 int reg_sweep_max_units();

@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int dgi = dir_of(tid, s) < D ? dir_of(tid, s) : D - 1;
-            sincos(a.dir_zen[dgi], &sd[s], &cd[s]);
+            synth_zen(a.dir_zen[dgi], sd[s], cd[s]);
             daz[s] = a.dir_azi[dgi];
         }
 #pragma unroll 1
@@ -256,9 +256,8 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3)
             if (u < nun) {
                 const int jm = smap[u < npr ? 2 * u : 2 * npr + (u - npr)];
                 double sm, cm;
-                sincos(a.mic_zen ? a.mic_zen[jm] : 1.5707963267948966, &sm, &cm);
-                v = fma((s ? sd[1] : sd[0]) * sm, cos((s ? daz[1] : daz[0]) - a.mic_azi[jm]), (s ? cd[1] : cd[0]) * cm);
-                v = 2.0 * fmin(1.0, fmax(-1.0, v));   // (2x: the factor of the Chebyshev recurrence)
+                synth_zen(a.mic_zen ? a.mic_zen[jm] : 1.5707963267948966, sm, cm);
+                v = synth_x2(s ? sd[1] : sd[0], s ? cd[1] : cd[0], sm, cm, (s ? daz[1] : daz[0]) - a.mic_azi[jm]);
             }
             xs[i * NT + tid] = v;
         }

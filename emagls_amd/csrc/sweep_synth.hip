@@ -122,10 +122,9 @@ __global__ void __launch_bounds__(SY_NT) sweep_synth_kernel(HalfSweepMulti m, in
                     const int64_t dg = d0 + dd < a.D ? d0 + dd : a.D - 1;
                     const int jm = smap[unit_row(u)];
                     double sd, cd, sm, cm;
-                    sincos(a.dir_zen[dg], &sd, &cd);
-                    sincos(a.mic_zen ? a.mic_zen[jm] : 1.5707963267948966, &sm, &cm);
-                    const double v = fma(sd * sm, cos(a.dir_azi[dg] - a.mic_azi[jm]), cd * cm);
-                    scratch[q] = 2.0 * fmin(1.0, fmax(-1.0, v));   // (2x: the factor of the Chebyshev recurrence)
+                    synth_zen(a.dir_zen[dg], sd, cd);
+                    synth_zen(a.mic_zen ? a.mic_zen[jm] : 1.5707963267948966, sm, cm);
+                    scratch[q] = synth_x2(sd, cd, sm, cm, a.dir_azi[dg] - a.mic_azi[jm]);
                 }
             }
 #pragma unroll
@@ -502,7 +501,7 @@ __global__ void __launch_bounds__(256) synth_ls_kernel(const cplx* __restrict__ 
     const bool paired = u < npr;
     const int jm = smap[row];
     double sm, cm;
-    sincos(mic_zen[jm], &sm, &cm);
+    synth_zen(mic_zen[jm], sm, cm);
     const double maz = mic_azi[jm];
     double x2[SL_DIRS];
     int dd[SL_DIRS];
@@ -512,9 +511,8 @@ __global__ void __launch_bounds__(256) synth_ls_kernel(const cplx* __restrict__ 
         dd[i] = d < D ? d : -1;
         const int dc = d < D ? d : D - 1;
         double sd, cd;
-        sincos(dir_zen[dc], &sd, &cd);
-        const double v = fma(sd * sm, cos(dir_azi[dc] - maz), cd * cm);
-        x2[i] = 2.0 * fmin(1.0, fmax(-1.0, v));
+        synth_zen(dir_zen[dc], sd, cd);
+        x2[i] = synth_x2(sd, cd, sm, cm, dir_azi[dc] - maz);
     }
     for (int kb = kb_lo; kb < kb_hi; ++kb) {
         __syncthreads();   // (the previous bin's readers of bs / red are done)

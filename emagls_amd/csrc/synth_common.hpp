@@ -24,6 +24,23 @@ __device__ __forceinline__ void lds_wait2(d2_t& a0, d2_t& a1, double& anchor) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(anchor));
 }
 
+// Sine and cosine of a zenith as the SH matrices take them (sh_basis.hip, MATLAB's legendre): the cosine, and the sine FROM it,
+// sqrt(1 - cos^2) >= 0 in the same FP64 steps.  The materialised operand and the reference are built on these two numbers, so the
+// synthesised operand is too: a zenith a rounding beyond pi (pi kept in single precision: 3.14159274) is the direction mirrored
+// back inside, and next to a pole, where 1 - cos^2 keeps few digits (the sine of that zenith is 1.5 % off), both forms mean the
+// same direction.  With sincos the operand of that direction was 2.2e-6 of its size away from the materialised one (signed sine:
+// the direction beyond the pole), with |sin| still 6.8e-9; elsewhere the two sines differ by u cos^2 / sin^2 relative.
+__device__ __forceinline__ void synth_zen(double zen, double& s, double& c) {
+    c = cos(zen);
+    s = sqrt(fmax(0.0, 1.0 - c * c));
+}
+// Twice the cosine of the angle between a direction (sd, cd of synth_zen) and a microphone (sm, cm), dazi the difference of their
+// azimuths -- the argument of the recurrence below (2x: its factor)
+__device__ __forceinline__ double synth_x2(double sd, double cd, double sm, double cm, double dazi) {
+    const double v = fma(sd * sm, cos(dazi), cd * cm);
+    return 2.0 * fmin(1.0, fmax(-1.0, v));
+}
+
 // one group of GS units (a direction and ONE microphone, or a direction and TWO antipodal microphones j, j' with
 // x_dj' = -x_dj): E = sum_{m even} c[m] T_m(x), O = sum_{m odd} c[m] T_m(x) with the Chebyshev recurrence
 // T_{m+1} = 2x T_m - T_{m-1} -- ONE fused operation per term and unit for the basis, two for the complex sums (the Legendre

@@ -83,6 +83,16 @@ int emagls_fp64_peak_tflops_ex(int which, int burst, double* tflops, double* sha
  * the register-resident sweep (v_mfma_f64_4x4x4_4b in the sweep's quad layout against a host sum; max_err: largest absolute difference); which = 1 / 2:
  * the LDS-staged Gram tile on v_mfma_f64_16x16x4 / on v_mfma_f64_4x4x4_4b against a host sum (max_err relative to the largest element). */
 int emagls_self_test(int which, double* max_err);
+/* The operand synthesis of the resident sweeps on the caller's data: bsc [nbins][nord_pad] (interleaved complex) are Chebyshev
+ * coefficients, x [nx] the arguments (the kernel doubles them as the sweeps do; no clamping), gs = 2, 3 or 4 the group size of the
+ * evaluation.  The kernel stages one bin's row in LDS and calls the sweeps' own evaluation; with E / O the even / odd part of
+ * sum_m bsc[k][m] T_m(x): g_plus [nbins][nx] = E + O = g(x) and g_minus [nbins][nx] = E - O = g(-x), what an antipodal microphone
+ * pair receives.  nord_pad even, 2 ... 96; nbins 1 ... 65535; nx 1 ... 2^24; otherwise EMAGLS_ERR_ARG.  Host pointers, synchronous. */
+int emagls_debug_synth_operand(const void* bsc, int nbins, int nord_pad, const double* x, int64_t nx, int gs, void* g_plus, void* g_minus);
+/* The argument of that evaluation as the sweeps form it from the angles: x2 [ndirs][nmics] = 2 cos(angle between HRIR direction d and
+ * microphone j), clamped to [-2, 2].  A zenith enters through cos(zen) and sqrt(1 - cos^2(zen)), as it enters the SH matrices: a value a
+ * rounding outside [0, pi] is the direction mirrored back.  ndirs 1 ... 2^20, nmics 1 ... 64; host pointers, synchronous. */
+int emagls_debug_synth_cosines(const double* dir_azi, const double* dir_zen, int64_t ndirs, const double* mic_azi, const double* mic_zen, int nmics, double* x2);
 
 /* ---- kernel-level entry points ------------------------------------------------------------- */
 

@@ -88,3 +88,24 @@ def test_design_out_shape_needs_no_gpu(lib):
     bad = L.DesignDesc(99, 0, 1, 48000.0, 16, 16, 10, 0.0, 0, 0.0, 0, 0, 0, 0, 0)
     r, c, z = C.c_int64(0), C.c_int64(0), C.c_int(0)
     assert lib.emagls_design_out_shape(C.byref(bad), C.byref(r), C.byref(c), C.byref(z)) != 0
+
+
+def test_debug_synth_operand_rejects_bad_arguments(lib):
+    """emagls_debug_synth_operand validates before it touches the device: the row length is even, 2 ... 96 (SY_NORD), the group
+    size 2, 3 or 4, the counts positive, the pointers set."""
+    from emagls_amd import _lib as L
+    bsc = np.zeros((1, 98), dtype=np.complex128)
+    x = np.zeros(4)
+    gp, gm = np.zeros((1, 4), dtype=np.complex128), np.zeros((1, 4), dtype=np.complex128)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+
+    def call(nbins=1, nord_pad=4, nx=4, gs=3, a=bsc, b=x, c=gp, d=gm):
+        return lib.emagls_debug_synth_operand(p(a) if a is not None else None, nbins, nord_pad, p(b) if b is not None else None, nx, gs,
+                                              p(c) if c is not None else None, p(d) if d is not None else None)
+    for kw in (dict(nord_pad=0), dict(nord_pad=-2), dict(nord_pad=3), dict(nord_pad=95), dict(nord_pad=98), dict(gs=1), dict(gs=5), dict(nbins=0),
+               dict(nbins=65536), dict(nx=0), dict(nx=(1 << 24) + 1), dict(a=None), dict(b=None), dict(c=None), dict(d=None)):
+        assert call(**kw) == L.ERR_ARG, kw
+    assert call(nord_pad=3) == L.ERR_ARG and b"nord_pad" in lib.emagls_last_error()
+    ang, out = np.zeros(4), np.zeros(16)
+    for nd, nm, a in ((0, 4, ang), ((1 << 20) + 1, 4, ang), (4, 0, ang), (4, 65, ang), (4, 4, None)):
+        assert lib.emagls_debug_synth_cosines(p(a) if a is not None else None, p(ang), nd, p(ang), p(ang), nm, p(out)) == L.ERR_ARG

@@ -75,8 +75,9 @@ def test_sweep_variants_agree(grids, thin, monkeypatch, mode):
     when all workgroups of a design share an XCD), the same with write-through stores (any placement), and one launch per
     bin (shapes the persistent kernel does not cover).  They sum the per-workgroup partials in different fixed
     orders, so they agree to rounding; each is bitwise reproducible.  The synthesising sweep (sweep_synth.hip) evaluates
-    pwGrid from the angles between directions and microphones instead of the SH matrices: the same operand to 1e-15, the
-    same filters to what the bins' conditioning makes of that (measured 1e-8; the tolerance of the design path is 1e-6)."""
+    pwGrid from the angles between directions and microphones instead of the SH matrices: the same operand to 1.9e-14 of its largest
+    value (measured, tests/test_gpu_synth_operand.py), the same filters to what the bins' conditioning makes of that (measured 1e-8; the tolerance of the design
+    path is 1e-6)."""
     from emagls_amd import Plan, _lib as L
     monkeypatch.setenv("EMAGLS_SWEEP_SYNTH", "0")
 
