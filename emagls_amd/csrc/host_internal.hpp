@@ -1,5 +1,5 @@
-// Internal header of the host translation units (host_pools.hip, capi.hip, jobs.hip): the plan and batch structs, the pools they
-// draw from, and the declarations of what one of these files calls in another.
+// Internal header of the host translation units (host_pools.hip, plan_setup.hip, plan_run.hip, batch_run.hip, capi.hip, jobs.hip): the
+// plan and batch structs, the pools they draw from, and the declarations of what one of these files calls in another.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -183,6 +183,37 @@ static inline bool array_kind(int k) { return k == EMAGLS_KIND_EMAGLS || k == EM
 // evaluation points of the SH rotation fit (emash.hip): enough to resolve order N exactly
 static inline int ema_sh_npts(int C) { return 4 * C + 8; }
 
+// A captured graph and its executable instance, owned together (non-copyable).  The only place on the host side that begins a
+// capture, instantiates a graph or destroys one: a struct that holds such a member needs no line of its own for it.
+struct CapturedGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    CapturedGraph() = default;
+    CapturedGraph(const CapturedGraph&) = delete;
+    CapturedGraph& operator=(const CapturedGraph&) = delete;
+    ~CapturedGraph() { if (exec) hipGraphExecDestroy(exec); if (graph) hipGraphDestroy(graph); }   // (never throws)
+    explicit operator bool() const { return exec != nullptr; }
+    // what `body` enqueues on `st`, captured and instantiated; a body that throws ends the capture and leaves nothing behind
+    template <typename F> void capture(hipStream_t st, F&& body) {
+        HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        try {
+            body();
+        } catch (...) {
+            hipGraph_t tmp = nullptr;
+            hipStreamEndCapture(st, &tmp);
+            if (tmp) hipGraphDestroy(tmp);
+            throw;
+        }
+        HIP_CHECK(hipStreamEndCapture(st, &graph));
+        HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    }
+    void launch(hipStream_t st) const { HIP_CHECK(hipGraphLaunch(exec, st)); }
+    void reset() {
+        if (exec) { HIP_CHECK(hipGraphExecDestroy(exec)); exec = nullptr; }
+        if (graph) { HIP_CHECK(hipGraphDestroy(graph)); graph = nullptr; }
+    }
+};
+
 }  // namespace emagls
 
 struct emagls_plan {
@@ -268,12 +299,10 @@ struct emagls_plan {
     int sweep_launches = 0;
     bool executed = false;
     // hipGraph replay of the whole design (launch-bound: ~520 small kernels per execute)
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    CapturedGraph graph;
     int eager_runs = 0;
     bool use_graph = true;
-    hipGraph_t pre_graph = nullptr;          // batches: stages before the sweep, captured on the plan's own stream
-    hipGraphExec_t pre_exec = nullptr;
+    CapturedGraph pre;                       // stages before the sweep, captured on the plan's own stream (its own executes and stream-mode batches)
     int nstreams = 1;
     int stage_order = 0;          // order of the stages before the sweep (emagls_pre_sweep): 0 branches, 1 / 2 the complementary single-stream orders of lane groups
     int pre_phase = 0;            // emagls_pre_sweep: 0 everything, 1 only what the sweep needs, 2 the rest (plan_defers_hh_route)
@@ -325,10 +354,6 @@ struct emagls_plan {
         for (auto e : sync_events) hipEventDestroy(e);
         for (auto st : side) StreamPool::get().give(st);
         StreamPool::get().give(hh_stream);
-        if (graph_exec) hipGraphExecDestroy(graph_exec);
-        if (graph) hipGraphDestroy(graph);
-        if (pre_exec) hipGraphExecDestroy(pre_exec);
-        if (pre_graph) hipGraphDestroy(pre_graph);
         if (owns_stream) StreamPool::get().give(stream);
     }
     void* alloc(const std::string& name, size_t bytes, bool zero = true) {
@@ -399,28 +424,22 @@ struct emagls_batch {
     uint64_t geo_kept_version = ~0ull;         // batch_geo_version of the last cold run whose status flags came back clean
     uint64_t geo_ran_version = ~0ull;          // ... of the last cold run enqueued (promoted by emagls_batch_get_filters)
     bool geo_cold_pending = false;             // that run's flags have not been read yet
-    hipGraph_t warm_graph = nullptr;           // the warm form's stages before the sweep (the stages after it are the same in both forms)
-    hipGraphExec_t warm_exec = nullptr;
+    CapturedGraph warm;                        // the warm form's stages before the sweep (the stages after it are the same in both forms)
     int last_form = 0;                         // the last execute: 0 independent designs (or another kind of batch), 1 cold, 2 warm
     long long geo_cold_runs = 0, geo_warm_runs = 0;
     int* cmp_flag = nullptr;
     int nstreams = 1;                          // lane mode: streams the stages before the sweep fork onto (emagls_batch_set_streams)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    // the stages before the sweep, one graph per lane group (on `stream`, side[0], side[1], side[2]: batch_execute_lanes); [0] is also
+    // those stages of the atf / magls / geo-cold forms and the captured launch-per-bin sweep of a batch without lanes
+    CapturedGraph group[4];
     int prof_level = 0;
     hipEvent_t sweep_ev[2] = {nullptr, nullptr};
-    hipGraph_t post_graph = nullptr;           // lane mode: the stages after the sweep (the sweep is launched directly)
-    hipGraphExec_t post_exec = nullptr;
+    CapturedGraph post;                        // lane mode: the stages after the sweep (the sweep is launched directly)
     bool side0_external = false;               // side[0] belongs to the caller (emagls_batch_set_side_stream)
     int order_hint = 0;                        // single-group batches: 1 / 2 = stage order of emagls_pre_sweep the caller asks for (emagls_batch_set_stage_order)
     int groups = 1;                            // lane groups before the sweep (ceil(designs / 8), up to 4: batch_execute_lanes)
-    hipGraph_t graph2 = nullptr;               // the second lane group's stages before the sweep (on side[0])
-    hipGraphExec_t graph2_exec = nullptr;
-    hipGraph_t graphx[2] = {nullptr, nullptr};             // the third and fourth groups' (on side[1], side[2])
-    hipGraphExec_t graphx_exec[2] = {nullptr, nullptr};
-    hipGraph_t graph_hh[4] = {nullptr, nullptr, nullptr, nullptr};   // per lane group: the stages the sweep does not need (plan_defers_hh_route), next to the sweep
-    hipGraphExec_t graph_hh_exec[4] = {nullptr, nullptr, nullptr, nullptr};
+    CapturedGraph group_hh[4];                 // per lane group: the stages the sweep does not need (plan_defers_hh_route), next to the sweep
     hipStream_t hh_stream[4] = {nullptr, nullptr, nullptr, nullptr};
     bool defer_hh = false;                     // what the captured graphs were captured with (batch_execute_lanes)
     bool alone = true;                         // the batch has the device to itself: the default of emagls_batch_create; the job scheduler clears it for the chunks of a list that keeps several in flight
@@ -445,23 +464,12 @@ struct emagls_batch {
     }
     ~emagls_batch() {
         // a batch may still be in flight on a caller-owned stream (emagls_batch_set_stream): its graph execs and events must
-        // outlive it (pool-owned streams are synchronised again when they are handed back)
+        // outlive it (pool-owned streams are synchronised again when they are handed back).  The graphs are members: they are
+        // destroyed after this body, hence after the synchronisation of `stream` here and of the hh_streams below.
         if (stream) hipStreamSynchronize(stream);
         for (auto e : events) hipEventDestroy(e);
-        if (graph_exec) hipGraphExecDestroy(graph_exec);
-        if (graph) hipGraphDestroy(graph);
-        if (post_exec) hipGraphExecDestroy(post_exec);
-        if (post_graph) hipGraphDestroy(post_graph);
-        if (graph2_exec) hipGraphExecDestroy(graph2_exec);
-        if (graph2) hipGraphDestroy(graph2);
-        if (warm_exec) hipGraphExecDestroy(warm_exec);
-        if (warm_graph) hipGraphDestroy(warm_graph);
-        for (int i = 0; i < 2; ++i) { if (graphx_exec[i]) hipGraphExecDestroy(graphx_exec[i]); if (graphx[i]) hipGraphDestroy(graphx[i]); }
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i)
             if (hh_stream[i]) { hipStreamSynchronize(hh_stream[i]); emagls::pool_stream_give(hh_stream[i]); }
-            if (graph_hh_exec[i]) hipGraphExecDestroy(graph_hh_exec[i]);
-            if (graph_hh[i]) hipGraphDestroy(graph_hh[i]);
-        }
         for (auto e : sweep_ev) if (e) hipEventDestroy(e);
         if (stream && own_stream) emagls::pool_stream_give(stream);
         for (int i = 0; i < 3; ++i) if (side[i] && !(i == 0 && side0_external)) { hipStreamSynchronize(side[i]); emagls::pool_stream_give(side[i]); }
@@ -478,10 +486,70 @@ template <typename F> int guarded(F&& f) {
     return guarded_call([&] { f(); });
 }
 
-// ---- defined in capi.hip, called by jobs.hip
+// First bin of the Gram route: cond(B_k) is governed by the ratio of the lowest to the highest modal coefficient the C
+// output channels can carry, |b_0 / b_n| ~ (2n+1)!! / (kr)^n with n = ceil(sqrt(C)) - 1; the route starts where that
+// estimate falls below GRAM_COND_EST (the Jacobi kernel verifies cond < 10x that and asks for a re-run otherwise).  The
+// route's error is eps cond^2 <= 2e-7 eps-relative at the verification limit 3e4, i.e. 2e-8 on M_k: two orders inside the
+// 1e-6 parity tolerance.  With 3e3 the Householder route of the em32 design ends at 1 kHz (bin 21 of 513), where 16 orders are
+// above the noise floor: 256 rows, the register tile with which its kernels fit next to a resident sweep workgroup.
+constexpr double GRAM_COND_EST = 3.0e3;
+
+// Graphs are captured from ONE stream only.  A capture whose stages fork onto side streams yields a graph with parallel branches,
+// and hipGraphLaunch of such graphs faults inside the HIP 7.0 runtime bundled with torch (hip::Graph::UpdateStreams): in long
+// sessions (StreamPool above), and on the first replay of a lone job chunk's forked lane batch when the process has two hardware
+// queues.  Forked stages therefore run eagerly on their streams; everything on one stream keeps its graphs.
+inline bool forks_streams(const emagls_plan& p) { return p.nstreams >= 2; }
+
+// ---- defined in plan_setup.hip
 extern thread_local hipStream_t g_plan_stream_shared;   // set by the job scheduler around the creation of a chunk's plans
+void plan_routes(emagls_plan& p);
+void synth_pairing(const double* azi, const double* zen, int M, int* smap);
+void plan_alloc_routes(emagls_plan& p);
+void plan_setup(emagls_plan& p);
+
+// ---- defined in plan_run.hip
+void stage_prologue(emagls_plan& p, int mode, const int64_t* didx, int64_t Dh);
+void execute_ls(emagls_plan& p);
+void magls_post_sweep(emagls_plan& p);
+bool plan_defers_hh_route(const emagls_plan& p);
+void emagls_pre_sweep(emagls_plan& p);
+HalfSweepArgs emagls_half_args(emagls_plan& p);
+// the gate every resident sweep of a device passes through (one per process and device: mutex() and state() are defined once)
+struct SweepGate {
+    struct Entry { hipEvent_t ev; int slots; };
+    struct State { std::deque<Entry> inflight; std::vector<hipEvent_t> pool; int capacity = 0; };
+    static std::mutex& mutex();
+    static State& state();   // (call with the mutex held)
+    std::unique_lock<std::mutex> lock;
+    hipStream_t st;
+    int slots;
+    SweepGate(hipStream_t s, int slots_per_xcd);   // slots_per_xcd <= 0: the whole device
+    ~SweepGate();
+};
+bool reg_sweep_wanted(emagls_plan* const* plans, int n);
+void reg_args_upload(const HalfSweepArgs* host, int n, void* dev, std::vector<char>& last, hipStream_t st);
+void emagls_post_sweep(emagls_plan& p);
+void from_atf_subject_stage(emagls_plan& p);
+void from_atf_ls_rows(emagls_plan& p, emagls_plan& sh, hipStream_t st);
+void from_atf_post_sweep(emagls_plan& p);
+void plan_pre_stage(emagls_plan& p);
+void plan_execute(emagls_plan& p);
+void drop_plan_graphs(emagls_plan& p);
+bool plan_recover(emagls_plan& p, const int* flag, bool apply);
+void throw_fatal_flags(const int* flag);
+
+// ---- defined in batch_run.hip
+void batch_geo_forget(emagls_batch& b);
 bool batch_geo_next_is_warm(const emagls_batch& b);
+void batch_execute(emagls_batch& b);
 void drop_batch_graphs(emagls_batch& b);
+void batch_unify_synth(emagls_batch& b);
+void batch_decide_residency(emagls_batch& b);
+void batch_try_lanes(emagls_batch& b);
+void batch_redo(emagls_batch& b, const std::vector<int>& flags);
+void plan_check_flags(emagls_plan& p);
+
+// ---- defined in capi.hip, called by jobs.hip
 bool same_desc(const emagls_design_desc& a, const emagls_design_desc& b);
 extern thread_local int g_batch_max_override;   // emagls_design_hrir_sets builds batches of 16 of its own whatever the caller's limit is
 

@@ -197,11 +197,11 @@ bool slot_will_capture(const JobSlot& s) {
         const emagls_batch& b = *s.batch;
         if (!b.use_graph || b.eager_runs < 1) return false;
         // a sharing batch of array designs captures each of its two forms the first time that form runs (batch_execute_geo)
-        if (b.geo_share && !b.atf && !b.magls) return !b.post_exec || !(batch_geo_next_is_warm(b) ? b.warm_exec : b.graph_exec);
-        return !b.graph_exec && !(b.plans.size() && b.plans[0]->pre_exec);
+        if (b.geo_share && !b.atf && !b.magls) return !b.post || !(batch_geo_next_is_warm(b) ? b.warm : b.group[0]);
+        return !b.group[0] && !(b.plans.size() && b.plans[0]->pre);
     }
     for (const emagls_plan* p : s.plans)
-        if (p->use_graph && p->prof_level == 0 && p->eager_runs >= 1 && !p->pre_exec && !p->graph_exec) return true;
+        if (p->use_graph && p->prof_level == 0 && p->eager_runs >= 1 && !p->pre && !p->graph) return true;
     return false;
 }
 std::atomic<long long> g_jobs_geo_runs[3];   // chunk executes since emagls_cache_clear: independent designs, cold, warm (emagls_jobs_geometry_runs)
@@ -328,7 +328,7 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
         }
         if (slot->batch) {
             slot->batch->alone = solo;   // (chunks in flight next to each other keep the orthonormal route before their sweeps: batch_defers_hh)
-            if (!solo && slot->batch->graph_exec) { HIP_CHECK(hipStreamSynchronize(slot->batch->stream)); drop_batch_graphs(*slot->batch); }
+            if (!solo && slot->batch->group[0]) { HIP_CHECK(hipStreamSynchronize(slot->batch->stream)); drop_batch_graphs(*slot->batch); }
         }
         lap("batch created");
     } else if (slot->batch) {

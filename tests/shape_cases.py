@@ -54,7 +54,7 @@ for (D, taps, ln, natf, M, ataps, ft) in [(450, 64, 64, 450, 1, 32, 1000.0), (45
     CASES.append(("atf", D, taps, ln, 48000.0, natf, M, ataps, ft))
 
 # fewer HRIR directions than simulated SH channels (D < (N_sim+1)^2, the reference's SVD takes them as they come): fine as long
-# as the orders of the orthonormal route are covered (capi.hip, plan_routes); found by tools/fuzz_random.py
+# as the orders of the orthonormal route are covered (plan_setup.hip, plan_routes); found by tools/fuzz_random.py
 D_BELOW_S = len(CASES)
 CASES.append(("emagls2", 590, 128, 342, 48000.0, 0.05603182265749108, 6, 4, "real"))     # simulation order 25: S = 676
 CASES.append(("emagls", 486, 64, 248, 96000.0, 0.027496569985500114, 30, 4, "real"))     # simulation order 25
