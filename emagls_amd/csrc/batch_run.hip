@@ -73,30 +73,29 @@ bool batch_defers_hh(const emagls_batch& b) {
 }
 void batch_lanes_part(emagls_batch& b, int part, int first, int count, hipStream_t st, int group = 0) {
     emagls_plan& p0 = *b.plans[first];
-    hipStream_t keep = p0.stream, keep_side[3] = {p0.side[0], p0.side[1], p0.side[2]};
-    const int keep_streams = p0.nstreams, keep_order = p0.stage_order;
-    p0.stream = st;
-    p0.nstreams = (part == 0 && b.groups == 1) ? b.nstreams : 1;
-    p0.stage_order = 0;
-    if (part == 0 && p0.nstreams == 1) {
+    const int ns = (part == 0 && b.groups == 1) ? b.nstreams : 1;
+    int order = 0;
+    if (part == 0 && ns == 1) {
         const int sm = stagger_mode();
-        if (sm == 1) p0.stage_order = b.groups > 1 ? 1 + group % 2 : (b.order_hint ? 1 + (b.order_hint - 1) % 2 : 0);
-        else if (sm >= 10) p0.stage_order = group == 0 ? sm / 10 % 10 : sm % 10;   // (experiments: "12", "21", "11", "22")
+        if (sm == 1) order = b.groups > 1 ? 1 + group % 2 : (b.order_hint ? 1 + (b.order_hint - 1) % 2 : 0);
+        else if (sm >= 10) order = group == 0 ? sm / 10 % 10 : sm % 10;   // (experiments: "12", "21", "11", "22")
     }
-    if (p0.nstreams > 1) for (int i = 0; i < 3; ++i) p0.side[i] = b.side[i];
-    const int keep_phase = p0.pre_phase;
+    // plan `first` stands for its lanes: on the group's stream, with the batch's side streams when the stages fork
+    Scoped stream(p0.stream, st);
+    Scoped nstreams(p0.nstreams, ns);
+    Scoped stage_order(p0.stage_order, order);
+    Scoped side0(p0.side[0], ns > 1 ? b.side[0] : p0.side[0]), side1(p0.side[1], ns > 1 ? b.side[1] : p0.side[1]),
+        side2(p0.side[2], ns > 1 ? b.side[2] : p0.side[2]);
     // part 0 of a batch that runs the orthonormal route next to its sweep: only what the sweep needs; part 3: the rest
-    p0.pre_phase = part == 3 ? 2 : (part == 0 && b.defer_hh) ? 1 : 0;
-    auto restore = [&] { p0.stream = keep; p0.nstreams = keep_streams; p0.stage_order = keep_order; p0.pre_phase = keep_phase; for (int i = 0; i < 3; ++i) p0.side[i] = keep_side[i]; };
-    try {
-        BatchScope sc(count, b.stride);
-        if (part == 0) plan_pre_stage(p0); else if (part == 3) emagls_pre_sweep(p0); else emagls_post_sweep(p0);
-    } catch (...) {
-        restore();
-        throw;
-    }
-    restore();
+    Scoped pre_phase(p0.pre_phase, part == 3 ? 2 : (part == 0 && b.defer_hh) ? 1 : 0);
+    BatchScope sc(count, b.stride);
+    if (part == 0) plan_pre_stage(p0); else if (part == 3) emagls_pre_sweep(p0); else emagls_post_sweep(p0);
 }
+// what an execute leaves in its plans: `launches` sweep launches each
+void mark_executed(emagls_batch& b, int launches) {
+    for (auto* p : b.plans) { p->executed = true; p->sweep_launches = launches; }
+}
+int sweep_launch_count(const emagls_plan& p0) { return p0.sweep_persist ? 1 : p0.P - std::max(p0.kcut0, 1); }
 // Lane GROUPS: a batch of more than 8 designs runs the stages before its sweep as two half-batches on two streams (each one
 // launch of every kernel for its lanes, each a captured single-stream graph) and then ONE resident sweep launch for all designs.
 // Sixteen lanes in one launch sequence take about twice as long per kernel as eight (the bandwidth-bound kernels scale with
@@ -154,49 +153,89 @@ void batch_execute_lanes(emagls_batch& b) {
         }
     }
     if (replay) b.post.launch(b.stream); else batch_lanes_part(b, 2, 0, n, b.stream);
+    mark_executed(b, sweep_launch_count(*b.plans[0]));
+    if (!replay) ++b.eager_runs;
+}
+
+// ---- what the sharing forms and the per-plan form have in common
+// Do the buffers `names` of every plan hold the same words as plan 0's?  Compared on the device, and only when a plan's grids or ATF
+// set were replaced since the last comparison (atf_side_version); `same` keeps the answer in between.
+bool batch_inputs_same(emagls_batch& b, std::initializer_list<const char*> names, uint64_t& checked_version, bool& same) {
+    uint64_t ver = 0;
+    for (auto* p : b.plans) ver = ver * 1000003ull + p->atf_side_version;
+    if (ver == checked_version) return same;
+    if (!b.cmp_flag) HIP_CHECK(hipMalloc(&b.cmp_flag, 16));
+    HIP_CHECK(hipStreamSynchronize(b.stream));
+    HIP_CHECK(hipMemsetAsync(b.cmp_flag, 0, 16, b.stream));
     emagls_plan& p0 = *b.plans[0];
-    for (auto* p : b.plans) {
-        p->executed = true;
-        p->sweep_launches = p0.sweep_persist ? 1 : p0.P - std::max(p0.kcut0, 1);
+    for (size_t j = 1; j < b.plans.size(); ++j)
+        for (const char* name : names) launch_compare_words(p0.get(name), b.plans[j]->get(name), p0.bufs[name].bytes, b.cmp_flag, b.stream);
+    int differ = 0;
+    HIP_CHECK(hipMemcpyAsync(&differ, b.cmp_flag, sizeof differ, hipMemcpyDeviceToHost, b.stream));
+    HIP_CHECK(hipStreamSynchronize(b.stream));
+    checked_version = ver;
+    return same = differ == 0;
+}
+// the two modes enqueue different stages: nothing captured for the other one may be replayed (and a batch that shares its geometry,
+// or stops doing so, runs its geometry stages again)
+void batch_set_sharing(emagls_batch& b, bool& field, bool share) {
+    if (share == field) return;
+    for (auto* p : b.plans) drop_plan_graphs(*p);
+    drop_batch_graphs(b);
+    if (&field == &b.geo_share) batch_geo_forget(b);
+    field = share;
+}
+// The whole batch as two single-stream graphs around the resident sweep: `stage(b, pre_part)` before it and `stage(b, 2)` after it on
+// the batch's stream, eagerly on the first execute, captured (`pre`, b.post) when first needed afterwards; the sweep between them is
+// never captured (SweepGate).
+void batch_run_two_graphs(emagls_batch& b, CapturedGraph& pre, void (*stage)(emagls_batch&, int), int pre_part, int launches) {
+    const bool replay = b.use_graph && b.eager_runs >= 1;
+    if (replay && !pre) pre.capture(b.stream, [&] { stage(b, pre_part); });
+    if (replay && !b.post) b.post.capture(b.stream, [&] { stage(b, 2); });
+    b.used = 0;
+    if (replay) pre.launch(b.stream); else stage(b, pre_part);
+    batch_sweep_stage(b);
+    if (replay) b.post.launch(b.stream); else stage(b, 2);
+    mark_executed(b, launches);
+    if (!replay) ++b.eager_runs;
+}
+// A batch as separate graphs on separate streams (one hipGraph executes its nodes in order, so parallel branches inside ONE graph
+// would serialize): per-plan `pre` stages (graphs, on replays) on the plans' own streams, the shared sweep on the batch's stream
+// (captured only in its launch-per-bin form), per-plan `post` stages, ordered by events outside the graphs.
+template <typename Pre> void batch_run_per_plan(emagls_batch& b, bool replay, Pre pre, void (*post)(emagls_plan&), int launches) {
+    emagls_plan& p0 = *b.plans[0];
+    if (replay && !p0.pre) {
+        for (auto* p : b.plans) p->pre.capture(p->stream, [&] { pre(*p); });
+        if (!p0.sweep_persist) b.group[0].capture(b.stream, [&] { batch_sweep_stage(b); });
     }
+    b.used = 0;
+    for (auto* p : b.plans) b.depend(p->stream, b.stream);   // (the previous sweep of this batch is done with the plans' buffers)
+    for (auto* p : b.plans) {
+        if (replay) p->pre.launch(p->stream); else pre(*p);
+        b.depend(b.stream, p->stream);
+    }
+    if (b.atf_share)   // (FromAtf subjects only) least-squares bins of the other subjects on plan 0's operands
+        for (size_t j = 1; j < b.plans.size(); ++j) from_atf_ls_rows(*b.plans[j], p0, b.stream);
+    if (p0.sweep_persist) batch_sweep_stage(b);   // (never captured: see SweepGate)
+    else if (replay) b.group[0].launch(b.stream); else batch_sweep_stage(b);
+    for (auto* p : b.plans) {
+        b.depend(p->stream, b.stream);
+        post(*p);
+        b.depend(b.stream, p->stream);  // batch stream completion == all results ready
+    }
+    mark_executed(b, launches);
     if (!replay) ++b.eager_runs;
 }
 
 // FromAtf subjects share their ATF side when every plan holds the same grids and ATF set and no bin needs the dense route
 void batch_atf_decide_sharing(emagls_batch& b) {
-    uint64_t ver = 0;
-    for (auto* p : b.plans) ver = ver * 1000003ull + p->atf_side_version;
-    bool same = true;
-    if (ver != b.atf_checked_version) {
-        if (!b.cmp_flag) HIP_CHECK(hipMalloc(&b.cmp_flag, 16));
-        HIP_CHECK(hipStreamSynchronize(b.stream));
-        HIP_CHECK(hipMemsetAsync(b.cmp_flag, 0, 16, b.stream));
-        emagls_plan& p0 = *b.plans[0];
-        for (size_t j = 1; j < b.plans.size(); ++j)
-            for (const char* name : {"atf", "atf_azi", "atf_zen", "hrir_azi", "hrir_zen"})
-                launch_compare_words(p0.get(name), b.plans[j]->get(name), p0.bufs[name].bytes, b.cmp_flag, b.stream);
-        int differ = 0;
-        HIP_CHECK(hipMemcpyAsync(&differ, b.cmp_flag, sizeof differ, hipMemcpyDeviceToHost, b.stream));
-        HIP_CHECK(hipStreamSynchronize(b.stream));
-        b.atf_checked_version = ver;
-        same = differ == 0;
-    } else {
-        same = b.atf_inputs_same;   // (nothing was replaced since the last comparison)
-    }
-    b.atf_inputs_same = same;
+    const bool same = batch_inputs_same(b, {"atf", "atf_azi", "atf_zen", "hrir_azi", "hrir_zen"}, b.atf_checked_version, b.atf_inputs_same);
     bool routes_ok = true;
     for (auto* p : b.plans) routes_ok = routes_ok && p->gram_from == 1 && p->sweep_persist == b.plans[0]->sweep_persist;
-    const bool share = same && routes_ok && b.plans.size() > 1;
-    if (share != b.atf_share) {   // the captured per-plan stages differ between the two modes
-        for (auto* p : b.plans) drop_plan_graphs(*p);
-        drop_batch_graphs(b);
-        b.atf_share = share;
-    }
+    batch_set_sharing(b, b.atf_share, same && routes_ok && b.plans.size() > 1);
 }
 void from_atf_subject_pre_stage(emagls_plan& p) {   // a subject of a sharing batch: everything but the ATF side
-    p.stage_names.clear();
-    launch_zero(p.get("flag"), sizeof(int) * NFLAG, p.stream);
-    launch_zero(p.get("W"), p.bufs["W"].bytes, p.stream);
+    subject_reset(p, p.stream);
     from_atf_subject_stage(p);
 }
 // Subjects of ONE ATF set on ONE HRIR grid (checked on the device): the whole batch as two single-stream graphs around the
@@ -206,75 +245,35 @@ void from_atf_subject_pre_stage(emagls_plan& p) {   // a subject of a sharing ba
 // per batch of BASELINE config 5, of which 3.3 ms are the sweep and ~4 ms kernels that could overlap.
 void batch_atf_shared_stage(emagls_batch& b, int part) {
     emagls_plan& p0 = *b.plans[0];
-    std::vector<hipStream_t> keep;
-    for (auto* p : b.plans) { keep.push_back(p->stream); p->stream = b.stream; }
-    auto restore = [&] { for (size_t j = 0; j < b.plans.size(); ++j) b.plans[j]->stream = keep[j]; };
-    try {
-        if (part == 0) {
-            plan_pre_stage(p0);
-            for (size_t j = 1; j < b.plans.size(); ++j) {
-                emagls_plan& p = *b.plans[j];
-                p.stage_names.clear();
-                launch_zero(p.get("flag"), sizeof(int) * NFLAG, b.stream);
-                launch_zero(p.get("W"), p.bufs["W"].bytes, b.stream);
-                // (the subject keeps its own copy of the match: emagls_plan_get_info and the debug buffers read it per plan)
-                // (plain device-to-device copies: match_idx holds 64-bit integers)
-                HIP_CHECK(hipMemcpyAsync(p.get("match_idx"), p0.get("match_idx"), sizeof(int64_t) * (size_t)p.Dm, hipMemcpyDeviceToDevice, b.stream));
-                HIP_CHECK(hipMemcpyAsync(p.get("match_dev"), p0.get("match_dev"), sizeof(double) * (size_t)p.Dm, hipMemcpyDeviceToDevice, b.stream));
-                HIP_CHECK(hipMemcpyAsync(p.get("mean_dev"), p0.get("mean_dev"), sizeof(double), hipMemcpyDeviceToDevice, b.stream));
-                stage_prologue(p, 1, p.hrir_smaller ? nullptr : p.get<int64_t>("match_idx"), p.Dm);
-                from_atf_ls_rows(p, p0, b.stream);
-            }
-        } else {
-            for (auto* p : b.plans) from_atf_post_sweep(*p);
-        }
-    } catch (...) { restore(); throw; }
-    restore();
+    StreamLoan loan(b.plans, b.stream);
+    if (part == 2) {
+        for (auto* p : b.plans) from_atf_post_sweep(*p);
+        return;
+    }
+    plan_pre_stage(p0);
+    for (size_t j = 1; j < b.plans.size(); ++j) {
+        emagls_plan& p = *b.plans[j];
+        subject_reset(p, b.stream);
+        // (the subject keeps its own copy of the match: emagls_plan_get_info and the debug buffers read it per plan)
+        // (plain device-to-device copies: match_idx holds 64-bit integers)
+        HIP_CHECK(hipMemcpyAsync(p.get("match_idx"), p0.get("match_idx"), sizeof(int64_t) * (size_t)p.Dm, hipMemcpyDeviceToDevice, b.stream));
+        HIP_CHECK(hipMemcpyAsync(p.get("match_dev"), p0.get("match_dev"), sizeof(double) * (size_t)p.Dm, hipMemcpyDeviceToDevice, b.stream));
+        HIP_CHECK(hipMemcpyAsync(p.get("mean_dev"), p0.get("mean_dev"), sizeof(double), hipMemcpyDeviceToDevice, b.stream));
+        stage_prologue(p, 1, p.hrir_smaller ? nullptr : p.get<int64_t>("match_idx"), p.Dm);
+        from_atf_ls_rows(p, p0, b.stream);
+    }
 }
 void batch_execute_atf(emagls_batch& b) {
     for (auto* p : b.plans)
         if (!p->have_hrirs || !p->have_hrir_grid || !p->have_atfs)
             throw Error(EMAGLS_ERR_ARG, "every plan of the batch needs its HRIRs, its grid and the ATFs");
     batch_atf_decide_sharing(b);
-    const bool replay = b.use_graph && b.eager_runs >= 1;
     emagls_plan& p0 = *b.plans[0];
     static const bool one_stream = [] { const char* e = getenv("EMAGLS_ATF_ONE_STREAM"); return !(e && e[0] == '0'); }();
-    if (b.atf_share && p0.sweep_persist && one_stream) {
-        if (replay && !b.group[0]) {
-            b.group[0].capture(b.stream, [&] { batch_atf_shared_stage(b, 0); });
-            b.post.capture(b.stream, [&] { batch_atf_shared_stage(b, 2); });
-        }
-        b.used = 0;
-        if (replay) b.group[0].launch(b.stream); else batch_atf_shared_stage(b, 0);
-        batch_sweep_stage(b);   // (never captured: see SweepChain)
-        if (replay) b.post.launch(b.stream); else batch_atf_shared_stage(b, 2);
-        for (auto* p : b.plans) { p->executed = true; p->sweep_launches = 1; }
-        if (!replay) ++b.eager_runs;
-        return;
-    }
-    auto pre = [&](emagls_plan& p) { if (b.atf_share && &p != &p0) from_atf_subject_pre_stage(p); else plan_pre_stage(p); };
-    if (replay && !p0.pre) {
-        for (auto* p : b.plans) p->pre.capture(p->stream, [&] { pre(*p); });
-        if (!p0.sweep_persist) b.group[0].capture(b.stream, [&] { batch_sweep_stage(b); });
-    }
-    b.used = 0;
-    for (auto* p : b.plans) b.depend(p->stream, b.stream);   // (the previous execute of this batch is done with the buffers)
-    for (auto* p : b.plans) {
-        if (replay) p->pre.launch(p->stream); else pre(*p);
-        b.depend(b.stream, p->stream);
-    }
-    if (b.atf_share)   // least-squares bins of the other subjects on plan 0's operands
-        for (size_t j = 1; j < b.plans.size(); ++j) from_atf_ls_rows(*b.plans[j], p0, b.stream);
-    if (p0.sweep_persist) batch_sweep_stage(b);   // (never captured: see SweepChain)
-    else if (replay) b.group[0].launch(b.stream); else batch_sweep_stage(b);
-    for (auto* p : b.plans) {
-        b.depend(p->stream, b.stream);
-        from_atf_post_sweep(*p);
-        b.depend(b.stream, p->stream);  // batch stream completion == all results ready
-        p->executed = true;
-        p->sweep_launches = p0.sweep_persist ? 1 : p0.P - std::max(p0.kcut0, 1);
-    }
-    if (!replay) ++b.eager_runs;
+    if (b.atf_share && p0.sweep_persist && one_stream) { batch_run_two_graphs(b, b.group[0], batch_atf_shared_stage, 0, 1); return; }
+    batch_run_per_plan(b, b.use_graph && b.eager_runs >= 1,
+                       [&](emagls_plan& p) { if (b.atf_share && &p != &p0) from_atf_subject_pre_stage(p); else plan_pre_stage(p); },
+                       from_atf_post_sweep, sweep_launch_count(p0));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -308,87 +307,25 @@ void batch_geo_decide_sharing(emagls_batch& b) {
                        p->real_internal == p0.real_internal && p->gram_from == p0.gram_from && p->hh_end == p0.hh_end && p->n_h == p0.n_h &&
                        p->g0 == p0.g0 && p->sweep_persist == p0.sweep_persist;
         }
-        if (eligible) {
-            uint64_t ver = 0;
-            for (auto* p : b.plans) ver = ver * 1000003ull + p->atf_side_version;
-            if (ver != b.geo_checked_version) {
-                if (!b.cmp_flag) HIP_CHECK(hipMalloc(&b.cmp_flag, 16));
-                HIP_CHECK(hipStreamSynchronize(b.stream));
-                HIP_CHECK(hipMemsetAsync(b.cmp_flag, 0, 16, b.stream));
-                for (size_t j = 1; j < b.plans.size(); ++j)
-                    for (const char* name : {"hrir_azi", "hrir_zen", "mic_azi", "mic_zen"})
-                        launch_compare_words(p0.get(name), b.plans[j]->get(name), p0.bufs[name].bytes, b.cmp_flag, b.stream);
-                int differ = 0;
-                HIP_CHECK(hipMemcpyAsync(&differ, b.cmp_flag, sizeof differ, hipMemcpyDeviceToHost, b.stream));
-                HIP_CHECK(hipStreamSynchronize(b.stream));
-                b.geo_checked_version = ver;
-                b.geo_inputs_same = differ == 0;
-            }
-            share = b.geo_inputs_same;
-        }
+        share = eligible && batch_inputs_same(b, {"hrir_azi", "hrir_zen", "mic_azi", "mic_zen"}, b.geo_checked_version, b.geo_inputs_same);
     }
-    if (share != b.geo_share) {   // (the two modes enqueue different stages: nothing captured for the other one may be replayed)
-        for (auto* p : b.plans) drop_plan_graphs(*p);
-        drop_batch_graphs(b);
-        batch_geo_forget(b);
-        b.geo_share = share;
-    }
+    batch_set_sharing(b, b.geo_share, share);
 }
-// a subject of a geometry-sharing batch, first part: what needs its HRIRs only (lib/getEMagLsFilters.m:72-81)
-void emagls_subject_prologue(emagls_plan& p, const emagls_plan& g) {
-    const emagls_design_desc& d = p.d;
-    hipStream_t st = p.stream;
-    const int ls_end = std::min(g.kcut0, g.P);
-    p.stage_names.clear();
-    p.sync_used = 0;
-    launch_zero(p.get("flag"), sizeof(int) * NFLAG, st);
-    launch_zero(p.get("W"), p.bufs["W"].bytes, st);
-    launch_twiddles(p.nfft, p.get("tw"), st);
-    launch_hrir_grpdelay(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, d.ndirs, p.nfft, p.get("tw"), p.get<double>("dirsum"),
-                         p.get<double>("grpd"), st);
-    launch_hrir_fft(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, p.D, nullptr, p.nfft, p.get("tw"), p.get<double>("grpd"), 0, ls_end,
-                    p.kcut0, p.get("Hc"), p.get<double>("Habs"), p.ldD, st, ls_end > 0 ? p.get<double>("HcT") : nullptr,
-                    round_up(4 * std::max(ls_end, 1), 64));
-}
-// second part, behind plan g's stages: the least-squares bins (:94) on g's factors -- H conj(Q) R^-1 rows and the
-// back-transform of the Householder-route bins (into the subject's own Z), G_k / M_k of g for the Gram-route bins
-void emagls_subject_rows(emagls_plan& p, emagls_plan& g) {
-    hipStream_t st = p.stream;
-    const bool cb = g.cplx_basis;
-    const int gf = g.gram_from, hh_end = g.hh_end, Sh = g.S_h, ldSh = g.ldS_h, nOrdH = g.n_h + 1, nOrd = g.simOrder + 1;
-    const int ls_end = std::min(g.kcut0, g.P);
-    const int ls_h = std::min(ls_end, hh_end);
-    const int64_t g_stride = (int64_t)g.C * g.ldD;
-    if (hh_end > 1) {
-        launch_hy_conj_mfma(p.get<double>("HcT"), round_up(4 * std::max(ls_end, 1), 64), ls_end, g.get("Yc"), g.ldS, cb, (int)g.D, Sh,
-                            p.get<double>("Hyp"), p.get("Hq"), ldSh, st);
-        launch_qform(p.get("Hq"), g.get(cb ? "R" : "Rc"), p.get(cb ? "Rinv" : "Rinvc"), Sh, 2 * (int64_t)std::max(ls_end, 1), ldSh, true, p.get("Hq"), st);
-        FactorArgs fa{};
-        fa.S = Sh; fa.C = g.C; fa.ldS = ldSh; fa.kb0 = 1; fa.P = g.P;
-        fa.Tn = g.get("Tn"); fa.bn = g.get<cplx>("bn"); fa.nOrders = nOrdH; fa.bn_stride = nOrd;
-        fa.reg_mode = 0; fa.reg_c = SVD_REGUL_CONST;
-        fa.Z = p.get<cplx>("Z");
-        fa.Mw = g.get<cplx>("Mw");
-        fa.Vws = g.get<cplx>("Vws"); fa.sv = g.get<double>("sv");
-        fa.Hq = p.get<cplx>("Hq"); fa.ldHq = ldSh; fa.hq_estride = (int64_t)ls_end * ldSh; fa.ls_end = ls_h;
-        fa.hq_conj = 1;
-        fa.route = g.get<int>("route"); fa.status = p.get<int>("flag");
-        fa.cond_limit = 10.0 * GRAM_COND_EST;
-        fa.W = p.get<cplx>("W"); fa.sweeps_out = nullptr;
-        fa.tauw = g.get<double>("tauw"); fa.R2w = g.get<cplx>("R2w"); fa.Nw = g.get<cplx>("Nw");
-        fa.cond_ok = g.get<double>("cond_ok");
-        launch_factor(fa, hh_end - 1, cb, st, 2);
+// What the HRIR set of plan h enters, on plan 0's geometry (lib/getEMagLsFilters.m:72-81, :94): its spectra; behind plan 0's stages
+// the least-squares bins -- H conj(Q) R^-1 rows and the back-transform of the Householder-route bins (into h's own Z), G_k / M_k for the
+// Gram-route bins --; a synthesising design's start value of the microphone-domain chain.  g: where the launches read the
+// geometry's operands -- plan 0, or in a lane launch the lanes' own copies (then every pointer of a launch moves by the same stride);
+// plan 0's coefficients, Pm and M_k serve every lane of a synthesising design.
+void geo_hrir_side(emagls_plan& h, emagls_plan& g, emagls_plan& p0, hipStream_t st) {
+    subject_reset(h, st);
+    h.sync_used = 0;
+    hrir_spectra(h, p0, st);
+    if (g.hh_end > 1) {
+        hrir_hh_rows(h, g, st);
+        hrir_hh_back(hh_factor_args(h, g, nullptr, g.get<double>("cond_ok")), g, st);
     }
-    if (gf > 0 && gf < ls_end) {
-        if (g.synth) {   // (lane launches: the subject's own copies of the grids and of the row order, plan 0's coefficients, Pm and M_k)
-            const emagls_plan& g0p = g.geo_from ? *g.geo_from : g;
-            launch_synth_ls(p.get("Hc"), p.ldD, ls_end, g0p.bufs.at("bsc").p, synth_nord_pad(nOrd), p.get<double>("hrir_azi"), p.get<double>("hrir_zen"),
-                            p.get<double>("mic_azi"), p.get<double>("mic_zen"), p.get<int>("smap"), (int)g.D, (int)g.d.nmics, g.P, gf, ls_end, p.get("Usw"), st, true);
-            launch_synth_rows(p.get("Usw"), synth_ls_chunks((int)g.D), g0p.bufs.at("Pm").p, g0p.bufs.at("Mw").p, g.C, (int)g.d.nmics, gf, ls_end, g.P, p.get("W"), st, true);
-        } else
-        launch_ls_gram(p.get("Hc"), p.ldD, ls_end, g.get<cplx>("G") - (int64_t)g.g0 * g_stride, g_stride, g.ldD, g.get("Mw"), (int)g.D, g.C, g.P, gf,
-                       ls_end, p.get("W"), st);
-    }
+    hrir_gram_ls_rows(h, g, p0, true, st);
+    if (p0.synth) launch_synth_winit(h.get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, h.get("Winit"), st, true);
 }
 // One stream for the whole batch (the subjects' stages are short and the sweep chain is what bounds a batch of HRIR sets), so
 // that the stages before and after the sweep are two single-stream graphs: issued eagerly, the ~250 launches of a 16-set batch
@@ -404,111 +341,76 @@ void emagls_subject_rows(emagls_plan& p, emagls_plan& g) {
 // zero plan 0's route.
 void batch_geo_stage(emagls_batch& b, int part) {
     emagls_plan& p0 = *b.plans[0];
-    std::vector<hipStream_t> keep;
-    for (auto* p : b.plans) { keep.push_back(p->stream); p->stream = b.stream; }
-    auto restore = [&] { for (size_t j = 0; j < b.plans.size(); ++j) b.plans[j]->stream = keep[j]; };
+    StreamLoan loan(b.plans, b.stream);
     const int n = (int)b.plans.size();
     // what an HRIR set enters, for the plans first .. n-1 on plan 0's geometry: the subjects of a cold run (plan 0 has just run its
-    // whole pipeline), every plan of a warm run.  Plan 0 takes the same kernels on the same operands here as inside its own pipeline
-    // (emagls_pre_sweep: blk_prologue, blk_rows, blk_back, blk_tail; synth_winit_kernel is block 0 of synth_mt_kernel), so its
-    // filters have the same bits in both forms.
+    // whole pipeline), every plan of a warm run.  Plan 0 CALLS the same functions here as inside its own pipeline (plan_run.hip:
+    // hrir_spectra, hrir_hh_rows, hh_factor_args, hrir_hh_back, hrir_gram_ls_rows from emagls_pre_sweep's blk_prologue, blk_rows,
+    // blk_back, blk_tail; synth_winit_kernel is block 0 of synth_mt_kernel), so its filters have the same bits in both forms.
     auto hrir_side = [&](int first) {
         if (first >= n) return;
         if (b.lanes) {
-            emagls_plan& pf = *b.plans[first];
             BatchScope sc(n - first, b.stride);
-            emagls_subject_prologue(pf, p0);
-            pf.geo_from = &p0;   // (synthesising designs: plan 0's coefficients, Pm and M_k for every lane)
-            try { emagls_subject_rows(pf, pf); } catch (...) { pf.geo_from = nullptr; throw; }
-            pf.geo_from = nullptr;
-            if (p0.synth)   // every set's own start value of the microphone-domain chain, on plan 0's Pm
-                launch_synth_winit(pf.get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, pf.get("Winit"), b.stream, true);
+            geo_hrir_side(*b.plans[first], *b.plans[first], p0, b.stream);
         } else {
-            for (int j = first; j < n; ++j) {
-                emagls_subject_prologue(*b.plans[j], p0);
-                emagls_subject_rows(*b.plans[j], p0);
-                if (p0.synth)
-                    launch_synth_winit(b.plans[j]->get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, b.plans[j]->get("Winit"),
-                                       b.stream, true);
-            }
+            for (int j = first; j < n; ++j) geo_hrir_side(*b.plans[j], p0, p0, b.stream);
         }
     };
-    try {
-        if (part == 1) {
-            hrir_side(0);
-        } else if (part == 0) {
-            plan_pre_stage(p0);
-            if (b.lanes && n > 1) {
-                // lane batch: the subjects' stages are ONE launch per kernel for all of them (plans 1.. at the arena stride).  The
-                // few geometry operands those kernels read (conj(Y), R, the Householder-route factors, M_k and G_k of the
-                // least-squares bins: ~40 MB) are copied into the subjects' own slots first, so that every pointer of a launch
-                // moves by the same stride; the large ones (G_k, M_k of the swept bins) are only read by the sweep, through
-                // plan 0's pointers.  The copies stay: a warm run reads them again.
-                emagls_plan& g = p0;
-                const bool cb = g.cplx_basis;
-                const int gf = g.gram_from, hh_end = g.hh_end, ldSh = g.ldS_h;
-                const int ls_end = std::min(g.kcut0, g.P);
-                const size_t g_stride_b = sizeof(cplx) * (size_t)g.C * g.ldD;
-                auto bc = [&](const char* name, size_t off, size_t bytes) {
-                    if (!g.has(name) || bytes == 0) return;
-                    bytes = std::min(bytes, g.bufs[name].bytes - off);
-                    launch_broadcast_lanes(g.get<char>(name) + off, bytes, b.stride, n - 1, b.stream);
-                };
-                if (hh_end > 1) {
-                    bc("Yc", 0, g.bufs["Yc"].bytes);
-                    bc(cb ? "R" : "Rc", 0, g.bufs[cb ? "R" : "Rc"].bytes);
-                    bc("Vws", 0, sizeof(cplx) * (size_t)(hh_end - 1) * g.C * ldSh);
-                    bc("Nw", 0, sizeof(cplx) * (size_t)(hh_end - 1) * g.C * g.C);
-                    bc("tauw", 0, sizeof(double) * (size_t)(hh_end - 1) * g.C);
-                    bc("cond_ok", 0, sizeof(double) * (size_t)g.P);
-                }
-                if (gf > 0 && gf < ls_end) {
-                    bc("G", (size_t)(gf - g.g0) * g_stride_b, (size_t)(ls_end - gf) * g_stride_b);
-                    bc("Mw", 0, sizeof(cplx) * (size_t)ls_end * g.C * g.C);
-                }
+    if (part == 1) {
+        hrir_side(0);
+    } else if (part == 0) {
+        plan_pre_stage(p0);
+        if (b.lanes && n > 1) {
+            // lane batch: the subjects' stages are ONE launch per kernel for all of them (plans 1.. at the arena stride).  The
+            // few geometry operands those kernels read (conj(Y), R, the Householder-route factors, M_k and G_k of the
+            // least-squares bins: ~40 MB) are copied into the subjects' own slots first, so that every pointer of a launch
+            // moves by the same stride; the large ones (G_k, M_k of the swept bins) are only read by the sweep, through
+            // plan 0's pointers.  The copies stay: a warm run reads them again.
+            emagls_plan& g = p0;
+            const bool cb = g.cplx_basis;
+            const int gf = g.gram_from, hh_end = g.hh_end, ldSh = g.ldS_h;
+            const int ls_end = std::min(g.kcut0, g.P);
+            const size_t g_stride_b = sizeof(cplx) * (size_t)g.C * g.ldD;
+            auto bc = [&](const char* name, size_t off, size_t bytes) {
+                if (!g.has(name) || bytes == 0) return;
+                bytes = std::min(bytes, g.bufs[name].bytes - off);
+                launch_broadcast_lanes(g.get<char>(name) + off, bytes, b.stride, n - 1, b.stream);
+            };
+            if (hh_end > 1) {
+                bc("Yc", 0, g.bufs["Yc"].bytes);
+                bc(cb ? "R" : "Rc", 0, g.bufs[cb ? "R" : "Rc"].bytes);
+                bc("Vws", 0, sizeof(cplx) * (size_t)(hh_end - 1) * g.C * ldSh);
+                bc("Nw", 0, sizeof(cplx) * (size_t)(hh_end - 1) * g.C * g.C);
+                bc("tauw", 0, sizeof(double) * (size_t)(hh_end - 1) * g.C);
+                bc("cond_ok", 0, sizeof(double) * (size_t)g.P);
             }
-            hrir_side(1);
-        } else if (b.lanes) {
-            BatchScope sc(n, b.stride);
-            p0.geo_from = &p0;   // (the filters' rows of every lane from plan 0's Pm and M_k)
-            try { emagls_post_sweep(p0); } catch (...) { p0.geo_from = nullptr; throw; }
-            p0.geo_from = nullptr;
-        } else {
-            for (auto* p : b.plans) {
-                p->geo_from = &p0;
-                try { emagls_post_sweep(*p); } catch (...) { p->geo_from = nullptr; throw; }
-                p->geo_from = nullptr;
+            if (gf > 0 && gf < ls_end) {
+                bc("G", (size_t)(gf - g.g0) * g_stride_b, (size_t)(ls_end - gf) * g_stride_b);
+                bc("Mw", 0, sizeof(cplx) * (size_t)ls_end * g.C * g.C);
             }
         }
-    } catch (...) {
-        restore();
-        throw;
+        hrir_side(1);
+    } else if (b.lanes) {
+        BatchScope sc(n, b.stride);
+        Scoped from(p0.geo_from, &p0);   // (the filters' rows of every lane from plan 0's Pm and M_k)
+        emagls_post_sweep(p0);
+    } else {
+        for (auto* p : b.plans) {
+            Scoped from(p->geo_from, &p0);
+            emagls_post_sweep(*p);
+        }
     }
-    restore();
 }
 void batch_execute_geo(emagls_batch& b) {
-    emagls_plan& p0 = *b.plans[0];
-    const bool replay = b.use_graph && b.eager_runs >= 1;
     const bool warm = batch_geo_next_is_warm(b);
-    // the cold and the warm form each have a captured graph of their stages before the sweep, captured the first time the form runs
-    // with replays on -- a batch's second execute is normally its first warm one, so the warm form needs no eager run of its own
-    CapturedGraph& pre = warm ? b.warm : b.group[0];
-    if (replay && !pre) pre.capture(b.stream, [&] { batch_geo_stage(b, warm ? 1 : 0); });
-    if (replay && !b.post) b.post.capture(b.stream, [&] { batch_geo_stage(b, 2); });
     if (!warm) {   // (this run rewrites the kept state: it counts again once its flags have come back clean)
         b.geo_kept_version = ~0ull;
         b.geo_ran_version = batch_geo_version(b);
         b.geo_cold_pending = true;
     }
-    b.used = 0;
-    if (replay) pre.launch(b.stream); else batch_geo_stage(b, warm ? 1 : 0);
-    batch_sweep_stage(b);   // (never captured: see SweepChain)
-    if (replay) b.post.launch(b.stream); else batch_geo_stage(b, 2);
-    for (auto* p : b.plans) {
-        p->executed = true;
-        p->sweep_launches = p0.sweep_persist ? 1 : p0.P - std::max(p0.kcut0, 1);
-    }
-    if (!replay) ++b.eager_runs;
+    // the cold and the warm form each have a captured graph of their stages before the sweep, captured the first time the form runs
+    // with replays on -- a batch's second execute is normally its first warm one, so the warm form needs no eager run of its own
+    batch_run_two_graphs(b, warm ? b.warm : b.group[0], batch_geo_stage, warm ? 1 : 0, sweep_launch_count(*b.plans[0]));
     b.last_form = warm ? 2 : 1;
     ++(warm ? b.geo_warm_runs : b.geo_cold_runs);
 }
@@ -520,61 +422,32 @@ void batch_execute_geo(emagls_batch& b) {
 // G = Y_conj and M = R^-1 R^-H are the same for every set) plan 0 computes that side and the other plans run their HRIR
 // prologue and least-squares bins on it.
 // ---------------------------------------------------------------------------------------------
-void batch_magls_decide_sharing(emagls_batch& b) {
+// sweep_needed: a resident sweep is a precondition of sharing (LS has no sweep)
+void batch_magls_decide_sharing(emagls_batch& b, bool sweep_needed) {
     bool share = false;
     emagls_plan& p0 = *b.plans[0];
-    if (b.geo_want && b.plans.size() > 1 && !p0.custom_basis && !p0.diffuse && p0.sweep_persist) {
-        uint64_t ver = 0;
-        for (auto* p : b.plans) ver = ver * 1000003ull + p->atf_side_version;
-        if (ver != b.geo_checked_version) {
-            if (!b.cmp_flag) HIP_CHECK(hipMalloc(&b.cmp_flag, 16));
-            HIP_CHECK(hipStreamSynchronize(b.stream));
-            HIP_CHECK(hipMemsetAsync(b.cmp_flag, 0, 16, b.stream));
-            for (size_t j = 1; j < b.plans.size(); ++j)
-                for (const char* name : {"hrir_azi", "hrir_zen"})
-                    launch_compare_words(p0.get(name), b.plans[j]->get(name), p0.bufs[name].bytes, b.cmp_flag, b.stream);
-            int differ = 0;
-            HIP_CHECK(hipMemcpyAsync(&differ, b.cmp_flag, sizeof differ, hipMemcpyDeviceToHost, b.stream));
-            HIP_CHECK(hipStreamSynchronize(b.stream));
-            b.geo_checked_version = ver;
-            b.geo_inputs_same = differ == 0;
-        }
-        share = b.geo_inputs_same;
+    if (b.geo_want && b.plans.size() > 1 && !p0.custom_basis && !p0.diffuse && (p0.sweep_persist || !sweep_needed)) {
+        share = batch_inputs_same(b, {"hrir_azi", "hrir_zen"}, b.geo_checked_version, b.geo_inputs_same);
         for (auto* p : b.plans) share = share && !p->custom_basis && p->d.fs == p0.d.fs;
     }
-    if (share != b.geo_share) {
-        for (auto* p : b.plans) drop_plan_graphs(*p);
-        drop_batch_graphs(b);
-        batch_geo_forget(b);
-        b.geo_share = share;
-    }
+    batch_set_sharing(b, b.geo_share, share);
 }
 void batch_magls_stage(emagls_batch& b, int part) {
     emagls_plan& g = *b.plans[0];
-    std::vector<hipStream_t> keep;
-    for (auto* p : b.plans) { keep.push_back(p->stream); p->stream = b.stream; }
-    auto restore = [&] { for (size_t j = 0; j < b.plans.size(); ++j) b.plans[j]->stream = keep[j]; };
-    try {
-        if (part == 0) {
-            for (size_t j = 0; j < b.plans.size(); ++j) {
-                emagls_plan& p = *b.plans[j];
-                if (j == 0 || !b.geo_share) { plan_pre_stage(p); continue; }
-                // a subject of plan 0's grid: spectra, least-squares bins on plan 0's pinv(Y_conj)
-                p.stage_names.clear();
-                launch_zero(p.get("flag"), sizeof(int) * NFLAG, b.stream);
-                launch_zero(p.get("W"), p.bufs["W"].bytes, b.stream);
-                stage_prologue(p, 0, nullptr, p.D);
-                launch_ls_apply(p.get("Hc"), p.ldD, std::min(p.kcut0, p.P), g.get("Ypinv"), g.cplx_basis, g.ldD, (int)p.D, p.C, p.P, 0,
-                                std::min(p.kcut0, p.P), p.get("W"), b.stream);
-            }
-        } else {
-            for (auto* p : b.plans) magls_post_sweep(*p);
-        }
-    } catch (...) {
-        restore();
-        throw;
+    StreamLoan loan(b.plans, b.stream);
+    if (part == 2) {
+        for (auto* p : b.plans) magls_post_sweep(*p);
+        return;
     }
-    restore();
+    for (size_t j = 0; j < b.plans.size(); ++j) {
+        emagls_plan& p = *b.plans[j];
+        if (j == 0 || !b.geo_share) { plan_pre_stage(p); continue; }
+        // a subject of plan 0's grid: spectra, least-squares bins on plan 0's pinv(Y_conj)
+        subject_reset(p, b.stream);
+        stage_prologue(p, 0, nullptr, p.D);
+        launch_ls_apply(p.get("Hc"), p.ldD, std::min(p.kcut0, p.P), g.get("Ypinv"), g.cplx_basis, g.ldD, (int)p.D, p.C, p.P, 0,
+                        std::min(p.kcut0, p.P), p.get("W"), b.stream);
+    }
 }
 void batch_execute_magls(emagls_batch& b) {
     emagls_plan& p0 = *b.plans[0];
@@ -584,22 +457,17 @@ void batch_execute_magls(emagls_batch& b) {
     if (p0.d.kind == EMAGLS_KIND_LS) {
         // getLsFilters (lib/getLsFilters.m:30-34) has no sweep: wLs = h pinv(Y).  Sets on one grid: pinv(Y) once (plan 0), one
         // small product per set; otherwise every plan's own pipeline, all on the batch's stream.
-        bool keep_persist = p0.sweep_persist;
-        p0.sweep_persist = true;                 // (the sharing decision only asks for it on behalf of the sweep; LS has none)
-        try { batch_magls_decide_sharing(b); } catch (...) { p0.sweep_persist = keep_persist; throw; }
-        p0.sweep_persist = keep_persist;
+        batch_magls_decide_sharing(b, false);
         for (size_t j = 0; j < b.plans.size(); ++j) {
             emagls_plan& p = *b.plans[j];
-            hipStream_t keep = p.stream;
-            p.stream = b.stream;
-            try {
+            {
+                Scoped stream(p.stream, b.stream);
                 p.stage_names.clear();
                 launch_zero(p.get("flag"), sizeof(int) * NFLAG, b.stream);
                 if (j == 0 || !b.geo_share) execute_ls(p);
                 else launch_ls_filters(p.get<double>("hL"), p.get<double>("hR"), p.d.nsamp, (int)p.D, p0.get("Ypinv"), p0.cplx_basis, p0.ldD, p.C,
                                        p.get("wL"), p.get("wR"), b.stream);
-            } catch (...) { p.stream = keep; throw; }
-            p.stream = keep;
+            }
             p.executed = true;
         }
         return;
@@ -607,28 +475,15 @@ void batch_execute_magls(emagls_batch& b) {
     bool persist = true;
     for (auto* p : b.plans) persist = persist && p->sweep_persist;
     if (!persist) {   // (an ill-conditioned basis or a sweep that did not become resident: the designs one at a time, launch-per-bin sweeps)
-        if (b.geo_share) { for (auto* p : b.plans) drop_plan_graphs(*p); drop_batch_graphs(b); batch_geo_forget(b); b.geo_share = false; }
+        batch_set_sharing(b, b.geo_share, false);
         for (auto* p : b.plans) {
-            hipStream_t keep = p->stream;
-            p->stream = b.stream;
-            try { plan_execute(*p); } catch (...) { p->stream = keep; throw; }
-            p->stream = keep;
+            Scoped stream(p->stream, b.stream);
+            plan_execute(*p);
         }
         return;
     }
-    batch_magls_decide_sharing(b);
-    const bool replay = b.use_graph && b.eager_runs >= 1;
-    if (replay && !b.group[0]) {
-        b.group[0].capture(b.stream, [&] { batch_magls_stage(b, 0); });
-        b.post.capture(b.stream, [&] { batch_magls_stage(b, 2); });
-    }
-    b.used = 0;
-    if (replay) b.group[0].launch(b.stream); else batch_magls_stage(b, 0);
-    batch_sweep_stage(b);   // (never captured: see SweepChain)
-    if (replay) b.post.launch(b.stream); else batch_magls_stage(b, 2);
-    for (auto* p : b.plans) { p->executed = true; p->sweep_launches = 1; }
-    (void)p0;
-    if (!replay) ++b.eager_runs;
+    batch_magls_decide_sharing(b, true);
+    batch_run_two_graphs(b, b.group[0], batch_magls_stage, 0, 1);
 }
 // re-run a whole batch after one of its designs raised a recoverable flag: in lane mode all designs share the captured
 // graphs, so every plan of the batch changes its configuration together
@@ -695,9 +550,6 @@ bool batch_geo_next_is_warm(const emagls_batch& b) {
     return true;
 }
 
-// A batch runs as separate graphs on separate streams (one hipGraph executes its nodes in order, so
-// parallel branches inside ONE graph would serialize): per-plan "pre" graphs on the plans' own streams,
-// the shared sweep graph on the batch stream, ordered by events outside the graphs.
 void batch_execute(emagls_batch& b) {
     for (auto* p : b.plans)
         if (!p) throw Error(EMAGLS_ERR_ARG, "a plan of this batch has been destroyed");
@@ -714,28 +566,7 @@ void batch_execute(emagls_batch& b) {
         return;
     }
     const bool replay = b.use_graph && b.eager_runs >= 1 && std::none_of(b.plans.begin(), b.plans.end(), [](const emagls_plan* p) { return forks_streams(*p); });
-    if (replay && !b.plans[0]->pre) {
-        for (auto* p : b.plans) p->pre.capture(p->stream, [&] { plan_pre_stage(*p); });
-        if (!b.plans[0]->sweep_persist) b.group[0].capture(b.stream, [&] { batch_sweep_stage(b); });
-    }
-    b.used = 0;
-    // the previous sweep of this batch must be done before a plan's buffers are rewritten
-    for (auto* p : b.plans) b.depend(p->stream, b.stream);
-    for (auto* p : b.plans) {
-        if (replay) p->pre.launch(p->stream); else plan_pre_stage(*p);
-        b.depend(b.stream, p->stream);
-    }
-    if (b.plans[0]->sweep_persist) batch_sweep_stage(b);   // (never captured: see SweepChain)
-    else if (replay) b.group[0].launch(b.stream); else batch_sweep_stage(b);
-    emagls_plan& p0 = *b.plans[0];
-    for (auto* p : b.plans) {
-        b.depend(p->stream, b.stream);
-        emagls_post_sweep(*p);
-        b.depend(b.stream, p->stream);  // batch stream completion == all results ready
-        p->executed = true;
-        p->sweep_launches = p0.P - std::max(p0.kcut0, 1);
-    }
-    if (!replay) ++b.eager_runs;
+    batch_run_per_plan(b, replay, plan_pre_stage, emagls_post_sweep, b.plans[0]->P - std::max(b.plans[0]->kcut0, 1));
 }
 void drop_batch_graphs(emagls_batch& b) {
     for (auto& g : b.group) g.reset();

@@ -12,6 +12,7 @@
 #include <shared_mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/emagls.h"
@@ -213,6 +214,18 @@ struct CapturedGraph {
         if (graph) { HIP_CHECK(hipGraphDestroy(graph)); graph = nullptr; }
     }
 };
+
+// A value lent to a variable for one scope (non-copyable): the old one comes back when the scope ends, by return or by exception.
+// Every temporary override of plan or batch state is one of these (a batch lending its stream to all its plans: StreamLoan below).
+template <typename T> struct Scoped {
+    T& var;
+    T old;
+    template <typename U> Scoped(T& v, U&& value) : var(v), old(v) { var = std::forward<U>(value); }
+    Scoped(const Scoped&) = delete;
+    Scoped& operator=(const Scoped&) = delete;
+    ~Scoped() { var = old; }
+};
+template <typename T, typename U> Scoped(T&, U&&) -> Scoped<T>;
 
 }  // namespace emagls
 
@@ -481,6 +494,19 @@ struct emagls_batch {
 
 namespace emagls {
 
+// one stream lent to every plan of a batch for a scope (the single-stream forms enqueue all their plans' stages on the batch's stream)
+struct StreamLoan {
+    const std::vector<emagls_plan*>& plans;
+    std::vector<hipStream_t> keep;
+    StreamLoan(const std::vector<emagls_plan*>& ps, hipStream_t st) : plans(ps) {
+        keep.reserve(ps.size());
+        for (auto* p : ps) { keep.push_back(p->stream); p->stream = st; }
+    }
+    StreamLoan(const StreamLoan&) = delete;
+    StreamLoan& operator=(const StreamLoan&) = delete;
+    ~StreamLoan() { for (size_t j = 0; j < keep.size(); ++j) plans[j]->stream = keep[j]; }
+};
+
 // guarded_call for a callable of any type (the lambdas of the C entry points)
 template <typename F> int guarded(F&& f) {
     return guarded_call([&] { f(); });
@@ -512,6 +538,14 @@ void stage_prologue(emagls_plan& p, int mode, const int64_t* didx, int64_t Dh);
 void execute_ls(emagls_plan& p);
 void magls_post_sweep(emagls_plan& p);
 bool plan_defers_hh_route(const emagls_plan& p);
+// the HRIR-side stages of an array design, for the plan h that owns the HRIR set on the geometry of plan g (h itself inside its own
+// pipeline): the ONE definition that emagls_pre_sweep and the geometry-sharing batch form (batch_geo_stage) both call
+void hrir_spectra(emagls_plan& h, const emagls_plan& g, hipStream_t st);
+FactorArgs hh_factor_args(emagls_plan& h, emagls_plan& g, int* sweeps_out, double* cond_ok);
+void hrir_hh_rows(emagls_plan& h, emagls_plan& g, hipStream_t st);
+void hrir_hh_back(const FactorArgs& fa, const emagls_plan& g, hipStream_t st);
+void hrir_gram_ls_rows(emagls_plan& h, emagls_plan& g, const emagls_plan& src, bool lanes_share, hipStream_t st);
+void subject_reset(emagls_plan& p, hipStream_t st);
 void emagls_pre_sweep(emagls_plan& p);
 HalfSweepArgs emagls_half_args(emagls_plan& p);
 // the gate every resident sweep of a device passes through (one per process and device: mutex() and state() are defined once)

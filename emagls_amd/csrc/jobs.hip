@@ -88,13 +88,12 @@ int emagls_design_hrir_sets(int kind, const double* hL, const double* hR, int64_
                         // batches (emagls_batch_create): their chunk runs plan by plan, same filters as nsets single calls
                         // (EMAinSH -- lib/getEMagLsFiltersEMAinSH.m:32 -- has no lane batches either: plan by plan)
                         if (n > 1 && !c->plans[0]->wide && kind != EMAGLS_KIND_EMA_SH) {
-                            g_batch_max_override = SWEEP_MULTI_MAX;
-                            const int r = emagls_batch_create(c->plans.data(), n, &c->batch);
-                            g_batch_max_override = 0;
+                            int r;
+                            { Scoped limit(g_batch_max_override, SWEEP_MULTI_MAX); r = emagls_batch_create(c->plans.data(), n, &c->batch); }
                             req(r);
                             req(emagls_batch_set_geometry_sharing(c->batch, 1));
                         }
-                    } catch (...) { g_batch_max_override = 0; c->release(); throw; }
+                    } catch (...) { c->release(); throw; }
                     c->desc = d; c->device = dev; c->n = n;
                 }
                 auto same = [](const std::vector<double>& have, const double* now, size_t cnt) {
@@ -314,9 +313,8 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
     }
     lap("inputs set");
     if (n > 1 && !slot->batch && !slot->runs) {
-        g_batch_max_override = REG_SWEEP_MAX;
-        const int rc = emagls_batch_create(slot->plans.data(), n, &slot->batch);
-        g_batch_max_override = 0;
+        int rc;
+        { Scoped limit(g_batch_max_override, REG_SWEEP_MAX); rc = emagls_batch_create(slot->plans.data(), n, &slot->batch); }
         if (rc != EMAGLS_OK && rc != EMAGLS_ERR_UNSUPPORTED) check_rc(rc);   // (unsupported as a batch -- e.g. more than 32 channels: plan by plan)
         if (rc != EMAGLS_OK) slot->batch = nullptr;
         if (slot->batch && solo && slot->batch->lanes) {
@@ -720,12 +718,11 @@ int emagls_from_atf_hrir_sets(const double* hL, const double* hR, int64_t nsamp,
                         c->plans.push_back(p);
                     }
                     if (n > 1) {
-                        g_batch_max_override = SWEEP_MULTI_MAX;
-                        const int r = emagls_batch_create(c->plans.data(), n, &c->batch);
-                        g_batch_max_override = 0;
+                        int r;
+                        { Scoped limit(g_batch_max_override, SWEEP_MULTI_MAX); r = emagls_batch_create(c->plans.data(), n, &c->batch); }
                         req(r);
                     }
-                } catch (...) { g_batch_max_override = 0; c->release(); throw; }
+                } catch (...) { c->release(); throw; }
                 c->desc = d; c->device = dev; c->n = n;
             }
             try {

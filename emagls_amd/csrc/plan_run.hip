@@ -159,7 +159,6 @@ void ema_sh_operands(emagls_plan& p) {
     const int ls_end = std::min(p.kcut0, p.P);
     const int npts = ema_sh_npts(p.C), ldP = round_up(npts, 64);
     const int64_t ldA = round_up((int64_t)(p.D + 1) * npts, 64);
-    const int64_t g_stride = (int64_t)p.C * p.ldD;
     p.sync_used = 0;
     // ---- HRIR prologue
     launch_twiddles(p.nfft, p.get("tw"), st);
@@ -600,10 +599,8 @@ void stage_prologue(emagls_plan& p, int mode, const int64_t* didx, int64_t Dh) {
     // group delay from the sum over ALL HRIR directions (lib/getEMagLsFilters.m:74-75)
     launch_hrir_grpdelay(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, d.ndirs, p.nfft, p.get("tw"),
                          p.get<double>("dirsum"), p.get<double>("grpd"), st);
-    const int n_c = std::max(std::min(p.kcut0, p.P), 1);
     launch_hrir_fft(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, Dh, didx, p.nfft, p.get("tw"), p.get<double>("grpd"),
                     mode, std::min(p.kcut0, p.P), p.kcut0, p.get("Hc"), p.get<double>("Habs"), p.ldD, st);
-    (void)n_c;
     if (p.diffuse && mode == 0)
         launch_hrir_fft(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, Dh, didx, p.nfft, p.get("tw"), p.get<double>("grpd"),
                         0, p.P, p.P, p.get("Hfull"), p.get<double>("Habs"), p.ldD, st);
@@ -639,6 +636,76 @@ bool plan_defers_hh_route(const emagls_plan& p) {
     const int k0 = std::max(p.kcut0, 1);
     return on && p.synth && !p.diffuse && p.prof_level == 0 && p.d.kind != EMAGLS_KIND_EMA_SH && p.gram_from > 0 && p.hh_end > 1 && p.hh_end <= k0 - 1;
 }
+// ---- The HRIR-side stages of an array design (lib/getEMagLsFilters.m:72-81, :94), for the plan h that owns the HRIR set on the
+// geometry of plan g.  emagls_pre_sweep calls them with g = h; a geometry-sharing batch (batch_geo_stage) with plan 0 as g, or, in
+// lane mode, with the lanes' own copies of plan 0's operands.  Both forms CALL these functions: that is what gives plan 0's filters
+// the same bits in a cold, a warm and a single-plan execute.
+// the spectra: H of the least-squares bins (and its transpose HcT for the rows below), |H| of the swept bins, the group delays
+void hrir_spectra(emagls_plan& h, const emagls_plan& g, hipStream_t st) {
+    const emagls_design_desc& d = h.d;
+    const int ls_end = std::min(g.kcut0, g.P);
+    launch_twiddles(h.nfft, h.get("tw"), st);
+    launch_hrir_grpdelay(h.get<double>("hL"), h.get<double>("hR"), d.nsamp, d.ndirs, h.nfft, h.get("tw"), h.get<double>("dirsum"),
+                         h.get<double>("grpd"), st);
+    launch_hrir_fft(h.get<double>("hL"), h.get<double>("hR"), d.nsamp, h.D, nullptr, h.nfft, h.get("tw"), h.get<double>("grpd"), 0, ls_end,
+                    h.kcut0, h.get("Hc"), h.get<double>("Habs"), h.ldD, st, ls_end > 0 ? h.get<double>("HcT") : nullptr,
+                    round_up(4 * std::max(ls_end, 1), 64));
+}
+// arguments of the Householder route's launches (factor.hip): Z, Hq, W and the status words are the HRIR set's, everything else the
+// geometry's.  sweeps_out: jsweeps in a plan's own pipeline, null for a subject; cond_ok: null until launch_cond_flags has written it
+FactorArgs hh_factor_args(emagls_plan& h, emagls_plan& g, int* sweeps_out, double* cond_ok) {
+    const int ls_end = std::min(g.kcut0, g.P);
+    FactorArgs fa{};
+    fa.S = g.S_h; fa.C = g.C; fa.ldS = g.ldS_h; fa.kb0 = 1; fa.P = g.P;
+    fa.Tn = g.get("Tn"); fa.bn = g.get<cplx>("bn"); fa.nOrders = g.n_h + 1; fa.bn_stride = g.simOrder + 1;
+    fa.reg_mode = 0; fa.reg_c = SVD_REGUL_CONST;
+    fa.Z = h.get<cplx>("Z");
+    fa.Mw = g.get<cplx>("Mw");
+    fa.Vws = g.get<cplx>("Vws"); fa.sv = g.get<double>("sv");
+    fa.Hq = h.get<cplx>("Hq"); fa.ldHq = g.ldS_h; fa.hq_estride = (int64_t)ls_end * g.ldS_h; fa.ls_end = std::min(ls_end, g.hh_end);
+    fa.hq_conj = 1;
+    fa.route = g.get<int>("route"); fa.status = h.get<int>("flag");
+    fa.cond_limit = 10.0 * GRAM_COND_EST;   // (not the env override: the forced-estimate test must trip this check)
+    fa.W = h.get<cplx>("W"); fa.sweeps_out = sweeps_out;
+    fa.tauw = g.get<double>("tauw"); fa.R2w = g.get<cplx>("R2w"); fa.Nw = g.get<cplx>("Nw");
+    fa.cond_ok = cond_ok;
+    return fa;
+}
+// the least-squares right-hand sides H conj(Q) of the Householder-route bins.  Q itself is never formed: H conj(Q) is
+// conj( conj(H conj(Yc)) R^-1 ), one D-long product and a row solve for the least-squares rows
+void hrir_hh_rows(emagls_plan& h, emagls_plan& g, hipStream_t st) {
+    const bool cb = g.cplx_basis;
+    const int ls_end = std::min(g.kcut0, g.P);
+    launch_hy_conj_mfma(h.get<double>("HcT"), round_up(4 * std::max(ls_end, 1), 64), ls_end, g.get("Yc"), g.ldS, cb, (int)g.D, g.S_h,
+                        h.get<double>("Hyp"), h.get("Hq"), g.ldS_h, st);
+    // (also forms the inverses of R's diagonal blocks, which the ill-conditioned swept bins need: at least one row)
+    launch_qform(h.get("Hq"), g.get(cb ? "R" : "Rc"), h.get(cb ? "Rinv" : "Rinvc"), g.S_h, 2 * (int64_t)std::max(ls_end, 1), g.ldS_h, true, h.get("Hq"), st);
+}
+// back-transform + least-squares bins of the Householder route (into the HRIR set's own Z and W)
+void hrir_hh_back(const FactorArgs& fa, const emagls_plan& g, hipStream_t st) { launch_factor(fa, g.hh_end - 1, g.cplx_basis, st, 2); }
+// least-squares bins on the Gram route.  Synthesising designs: u(k) = H(k,:) conj(g_k) from the angles (the HRIR set's own copies of
+// the grids and of the row order), then W(k,:) = (u Pm^T) conj(M_k) like the swept bins' rows, on the coefficients, Pm and M_k of
+// `src`; lanes_share: `src` is ONE design's for every lane of the launch.  Otherwise on g's G_k and M_k.
+void hrir_gram_ls_rows(emagls_plan& h, emagls_plan& g, const emagls_plan& src, bool lanes_share, hipStream_t st) {
+    const int gf = g.gram_from, ls_end = std::min(g.kcut0, g.P), M = (int)g.d.nmics;
+    if (!(gf > 0 && gf < ls_end)) return;
+    if (g.synth) {
+        launch_synth_ls(h.get("Hc"), h.ldD, ls_end, src.bufs.at("bsc").p, synth_nord_pad(g.simOrder + 1), h.get<double>("hrir_azi"), h.get<double>("hrir_zen"),
+                        h.get<double>("mic_azi"), h.get<double>("mic_zen"), h.get<int>("smap"), (int)g.D, M, g.P, gf, ls_end, h.get("Usw"), st, lanes_share);
+        launch_synth_rows(h.get("Usw"), synth_ls_chunks((int)g.D), src.bufs.at("Pm").p, src.bufs.at("Mw").p, g.C, M, gf, ls_end, g.P, h.get("W"), st, lanes_share);
+    } else {
+        const int64_t g_stride = (int64_t)g.C * g.ldD;
+        launch_ls_gram(h.get("Hc"), h.ldD, ls_end, g.get<cplx>("G") - (int64_t)g.g0 * g_stride, g_stride, g.ldD, g.get("Mw"), (int)g.D, g.C, g.P, gf,
+                       ls_end, h.get("W"), st);
+    }
+}
+// what every execute of a design begins with: no stage marks, clean status words, zero filters' rows
+void subject_reset(emagls_plan& p, hipStream_t st) {
+    p.stage_names.clear();
+    launch_zero(p.get("flag"), sizeof(int) * NFLAG, st);
+    launch_zero(p.get("W"), p.bufs["W"].bytes, st);
+}
+
 void emagls_pre_sweep(emagls_plan& p) {
     if (p.d.kind == EMAGLS_KIND_EMA_SH) { ema_sh_pre_sweep(p); return; }
     const emagls_design_desc& d = p.d;
@@ -652,13 +719,10 @@ void emagls_pre_sweep(emagls_plan& p) {
     hipStream_t s0 = p.stream, s1 = p.nstreams >= 2 ? p.side[0] : s0, s2 = p.nstreams >= 3 ? p.side[1] : s0;
     hipStream_t s3 = p.nstreams >= 4 ? p.side[2] : s0;   // the Gram route of the per-bin factors (needs Gy, E, b_n; not the Cholesky factor)
     const int nOrd = p.simOrder + 1;
-    const int ls_end = std::min(p.kcut0, p.P);
     const int k0 = std::max(p.kcut0, 1);
     // routes (plan_routes): Householder bins [1, hh_end) on the orders 0..n_h, Gram-route bins [gf, P) on all orders
+    // (the least-squares bins among them: below min(k_cut, hh_end) on the Householder route, the others on the Gram route)
     const int gf = p.gram_from, hh_end = p.hh_end, Sh = p.S_h, ldSh = p.ldS_h, nOrdH = p.n_h + 1;
-    const int ls_h = std::min(ls_end, hh_end);     // least-squares bins [1, ls_h) on the Householder route, [ls_h, ls_end) on the Gram route
-    const int64_t g_stride = (int64_t)p.C * p.ldD;
-    cplx* Gk = p.get<cplx>("G") - (int64_t)p.g0 * g_stride;   // indexed by kb
     const int phase = plan_defers_hh_route(p) ? p.pre_phase : 0;
     if (phase != 2) p.sync_used = 0;
 
@@ -674,7 +738,6 @@ void emagls_pre_sweep(emagls_plan& p) {
     // two groups in complementary orders hide one's chains behind the other's bandwidth-bound kernels.
     const int order = (s1 == s0 && s2 == s0 && s3 == s0) ? p.stage_order : 0;
     hipEvent_t e_E = nullptr, e_Yc = nullptr, e_Gy = nullptr, e_R = nullptr;
-    FactorArgs fa{};
 
     auto blk_array = [&] {
     // s1: array model  E = Y_mic (raw) or pinv(Y_mic(:,1:nOut)) Y_mic   (getSMAIRMatrix.m:101-102,119-121), b_n(kr)
@@ -708,12 +771,7 @@ void emagls_pre_sweep(emagls_plan& p) {
 
     auto blk_prologue = [&] {
     // s2: HRIR prologue
-        launch_twiddles(p.nfft, p.get("tw"), s2);
-        launch_hrir_grpdelay(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, d.ndirs, p.nfft, p.get("tw"),
-                             p.get<double>("dirsum"), p.get<double>("grpd"), s2);
-        launch_hrir_fft(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, p.D, nullptr, p.nfft, p.get("tw"),
-                        p.get<double>("grpd"), 0, ls_end, p.kcut0, p.get("Hc"), p.get<double>("Habs"), p.ldD, s2,
-                        ls_end > 0 ? p.get<double>("HcT") : nullptr, round_up(4 * std::max(ls_end, 1), 64));
+        hrir_spectra(p, p, s2);
         if (p.diffuse)   // the target covariance needs the complex HRTFs of all bins (the sweep only keeps |H| above k_cut)
             launch_hrir_fft(p.get<double>("hL"), p.get<double>("hR"), d.nsamp, p.D, nullptr, p.nfft, p.get("tw"),
                             p.get<double>("grpd"), 0, p.P, p.P, p.get("Hfull"), p.get<double>("Habs"), p.ldD, s2);
@@ -757,33 +815,18 @@ void emagls_pre_sweep(emagls_plan& p) {
     }
     };
     auto blk_rows = [&] {
-    // s2 (after the prologue): the least-squares right-hand sides H conj(Q) of the Householder-route bins.  Q itself is never
-    // formed: H conj(Q) is conj( conj(H conj(Yc)) R^-1 ), one D-long product and a row solve for the least-squares rows.
+    // s2 (after the prologue): the least-squares right-hand sides H conj(Q) of the Householder-route bins
     if (s2 != s0) HIP_CHECK(hipStreamWaitEvent(s2, e_R, 0));
     if (hh_end > 1) {
         // (real basis: the rows are complex all the same, so R is widened to a complex copy for the row solves)
         if (!cb) launch_widen(p.get("R"), Sh, false, p.get("Rc"), Sh, Sh, Sh, false, /*upper_only=*/true, s2);
-        launch_hy_conj_mfma(p.get<double>("HcT"), round_up(4 * std::max(ls_end, 1), 64), ls_end, p.get("Yc"), p.ldS, cb, (int)p.D, Sh,
-                            p.get<double>("Hyp"), p.get("Hq"), ldSh, s2);
-        // (also forms the inverses of R's diagonal blocks, which the ill-conditioned swept bins need: at least one row)
-        launch_qform(p.get("Hq"), p.get(cb ? "R" : "Rc"), p.get(cb ? "Rinv" : "Rinvc"), Sh, 2 * (int64_t)std::max(ls_end, 1), ldSh, true, p.get("Hq"), s2);
+        hrir_hh_rows(p, p, s2);
     }
     };
 
     // s0: per-bin factors.  Gram route first (needs E, b_n, Gy): K matrices, one GEMM over the bins, direct inverses
     // (on a stream of its own with four streams: it does not need the Cholesky factor, the Householder route does)
-    fa.S = Sh; fa.C = p.C; fa.ldS = ldSh; fa.kb0 = 1; fa.P = p.P;
-    fa.Tn = p.get("Tn"); fa.bn = p.get<cplx>("bn"); fa.nOrders = nOrdH; fa.bn_stride = nOrd;
-    fa.reg_mode = 0; fa.reg_c = SVD_REGUL_CONST;
-    fa.Z = p.get<cplx>("Z");
-    fa.Mw = p.get<cplx>("Mw");
-    fa.Vws = p.get<cplx>("Vws"); fa.sv = p.get<double>("sv");
-    fa.Hq = p.get<cplx>("Hq"); fa.ldHq = ldSh; fa.hq_estride = (int64_t)ls_end * ldSh; fa.ls_end = ls_h;
-    fa.hq_conj = 1;
-    fa.route = p.get<int>("route"); fa.status = p.get<int>("flag");
-    fa.cond_limit = 10.0 * GRAM_COND_EST;   // (not the env override: the forced-estimate test must trip this check)
-    fa.W = p.get<cplx>("W"); fa.sweeps_out = p.get<int>("jsweeps");
-    fa.tauw = p.get<double>("tauw"); fa.R2w = p.get<cplx>("R2w"); fa.Nw = p.get<cplx>("Nw");
+    FactorArgs fa = hh_factor_args(p, p, p.get<int>("jsweeps"), nullptr);   // (cond_ok: blk_flags)
     // single-stream sequences, EMAGLS_JACOBI_PAIR=1: the two Jacobi steps (Gram-route bins, Householder-route bins) as ONE launch --
     // each lasts as long as its slowest bin (216 us) and on one stream they add up.  Off by default: with four batches in flight the
     // shorter chain changes nothing (three runs each, 20 / 128 steps: 1831-1904 / 2260-2394 merged, 1789-1952 / 2334-2498 not)
@@ -833,21 +876,13 @@ void emagls_pre_sweep(emagls_plan& p) {
     auto blk_back = [&] {
     // join s2 (Hq, spectra, group delays): back-transform + least-squares bins of the Householder route
     p.depend(s0, s2);
-    if (hh_end > 1) launch_factor(fa, hh_end - 1, cb, s0, 2);
+    if (hh_end > 1) hrir_hh_back(fa, p, s0);
     p.mark("factor_back+ls_bins");
     };
     auto blk_tail = [&] {
     // join s1 (G)
     p.depend(s0, s1);
-    // least-squares bins on the Gram route
-    if (gf > 0 && gf < ls_end) {
-        if (p.synth) {   // u(k) = H(k,:) conj(g_k) from the angles, then W(k,:) = (u Pm^T) conj(M_k) like the swept bins' rows
-            launch_synth_ls(p.get("Hc"), p.ldD, ls_end, p.get("bsc"), synth_nord_pad(nOrd), p.get<double>("hrir_azi"), p.get<double>("hrir_zen"),
-                            p.get<double>("mic_azi"), p.get<double>("mic_zen"), p.get<int>("smap"), (int)p.D, M, p.P, gf, ls_end, p.get("Usw"), s0);
-            launch_synth_rows(p.get("Usw"), synth_ls_chunks((int)p.D), p.get("Pm"), p.get("Mw"), p.C, M, gf, ls_end, p.P, p.get("W"), s0);
-        } else
-        launch_ls_gram(p.get("Hc"), p.ldD, ls_end, Gk, g_stride, p.ldD, p.get("Mw"), (int)p.D, p.C, p.P, gf, ls_end, p.get("W"), s0);
-    }
+    hrir_gram_ls_rows(p, p, p, false, s0);   // least-squares bins on the Gram route
     // ill-conditioned swept bins (Householder route only): Y_reg_inv_k = conj(Q) Z_k = conj(Yc) (Z_k R^-H); the flagged bins'
     // Z rows are solved in place first
     if (hh_end > k0) {
@@ -1022,7 +1057,6 @@ void reg_args_upload(const HalfSweepArgs* host, int n, void* dev, std::vector<ch
 }
 
 void emagls_post_sweep(emagls_plan& p) {
-    const bool cb = p.cplx_basis;
     const bool raw = p.d.kind == EMAGLS_KIND_EMAGLS2;
     const int conj_mode = !p.req_cplx || raw ? 0 : (p.d.kind == EMAGLS_KIND_EMA_CH ? 2 : 1);   // Hermitian mirror / SH rule / CH rule
     if (p.synth) {   // the chain stored the microphone-domain totals u(k): W(k,:) = (u(k) Pm^T) conj(M_k) for the swept bins
@@ -1034,7 +1068,6 @@ void emagls_post_sweep(emagls_plan& p) {
         launch_diffuse_constraint(p.get("W"), p.get("G"), true, (int64_t)p.C * p.ldD, p.g0, p.get("Hfull"), (int)p.D, p.C, p.ldD, p.P,
                                   p.stream);
     if (p.real_internal && !raw) launch_sh_rows_to_complex(p.get("W"), p.C, 2 * p.P, (int)p.d.order, p.stream);   // W_c = W_r T_N
-    (void)cb;
     launch_filter_epilogue(p.get("W"), p.C, p.nfft, (int)p.d.len, p.get("tw"), p.get<double>("grpd"), conj_mode, 1, 0,
                            p.out_cplx ? 1 : 0, p.get("wL"), p.get("wR"), p.stream);
     p.mark("epilogue");
@@ -1089,28 +1122,28 @@ void plan_execute(emagls_plan& p) {
     if (p.nstreams >= 2) p.need_sides(p.nstreams);   // (before any capture begins)
     const bool persist = d.kind != EMAGLS_KIND_LS && p.sweep_persist;
     if (p.prof_level == 0 && p.use_graph && persist) {
-        // the persistent sweep is launched directly (SweepChain); the stages before it are captured from the second
+        // the persistent sweep is launched directly (SweepGate); the stages before it are captured from the second
         // execute on (the first runs eagerly: one-time function attributes, lazy module load)
         // a design with forked stages (it has the device to itself) runs what its sweep does not need -- Cholesky factor, orthonormal
         // route of the low bins: plan_defers_hh_route -- NEXT to the sweep, eagerly on a stream of its own (a dozen launches)
         if (!p.pre) p.defer_hh = (p.nstreams >= 2 || p.alone) && array_kind(d.kind) && plan_defers_hh_route(p);
-        p.pre_phase = p.defer_hh ? 1 : 0;
-        try {
+        {
+            Scoped phase(p.pre_phase, p.defer_hh ? 1 : 0);
             if (!p.pre && p.eager_runs >= 1 && !forks_streams(p)) p.pre.capture(p.stream, [&] { plan_pre_stage(p); });
             if (p.pre) p.pre.launch(p.stream); else plan_pre_stage(p);
-        } catch (...) { p.pre_phase = 0; throw; }
-        p.pre_phase = 0;
+        }
         if (p.defer_hh) {
             if (!p.hh_stream) p.hh_stream = StreamPool::get().take();
             p.depend(p.hh_stream, p.stream);   // (behind the stages the sweep needs, before the sweep is enqueued)
         }
         emagls_run_sweep(p);
         if (p.defer_hh) {
-            hipStream_t keep = p.stream;
-            const int keep_n = p.nstreams;
-            p.stream = p.hh_stream; p.nstreams = 1; p.pre_phase = 2;
-            try { emagls_pre_sweep(p); } catch (...) { p.stream = keep; p.nstreams = keep_n; p.pre_phase = 0; throw; }
-            p.stream = keep; p.nstreams = keep_n; p.pre_phase = 0;
+            {
+                Scoped st(p.stream, p.hh_stream);
+                Scoped one(p.nstreams, 1);
+                Scoped phase(p.pre_phase, 2);
+                emagls_pre_sweep(p);
+            }
             p.depend(p.stream, p.hh_stream);   // (the epilogue reads the rows of every bin)
         }
         if (d.kind == EMAGLS_KIND_FROM_ATF) from_atf_post_sweep(p);
@@ -1124,9 +1157,10 @@ void plan_execute(emagls_plan& p) {
     // on these grids; such an execute runs eagerly (a thousand launches of 12 us each: the host stays ahead)
     if (p.geo_keep && p.wide && p.prof_level == 0 && (d.kind == EMAGLS_KIND_EMAGLS || d.kind == EMAGLS_KIND_EMAGLS2) &&
         p.geo_done_version == p.atf_side_version) {
-        p.geo_skip = true;
-        try { run_pipeline(p); } catch (...) { p.geo_skip = false; throw; }
-        p.geo_skip = false;
+        {
+            Scoped skip(p.geo_skip, true);
+            run_pipeline(p);
+        }
         p.executed = true;
         return;
     }
@@ -1147,10 +1181,8 @@ void plan_execute(emagls_plan& p) {
 
 // the stages before the sweep of a plan on its own stream (its own executes and every batch form that runs them per plan)
 void plan_pre_stage(emagls_plan& p) {
-    p.stage_names.clear();
-    launch_zero(p.get("flag"), sizeof(int) * NFLAG, p.stream);
+    subject_reset(p, p.stream);
     if (p.has("route")) launch_zero(p.get("route"), p.bufs["route"].bytes, p.stream);
-    launch_zero(p.get("W"), p.bufs["W"].bytes, p.stream);
     if (p.d.kind == EMAGLS_KIND_FROM_ATF) from_atf_pre_sweep(p);
     else if (magls_kind(p.d.kind)) magls_pre_sweep(p);
     else emagls_pre_sweep(p);
