@@ -13,7 +13,7 @@ BASIS = {"real": 0, "complex": 1}
 KIND_LS, KIND_MAGLS, KIND_EMAGLS, KIND_EMAGLS2, KIND_FROM_ATF, KIND_EMA_CH, KIND_MAGLS_2D, KIND_EMA_SH = range(8)
 RADIAL = {"tikhonov": 0, "softlimit": 1, "full": 2, "none": 3}
 LAYOUT = {"sh": 0, "ch": 1}
-MODEL = {"sh": 0, "emagls": 1, "emagls2": 2, "atf": 3}
+MODEL = {"sh": 0, "emagls": 1, "emagls2": 2, "atf": 3, "ema_ch": 5, "ema_sh": 6}
 
 c_dp = C.POINTER(C.c_double)
 c_i64 = C.c_int64

@@ -1123,7 +1123,10 @@ def getRenderedHrtfs(wL, wR, model, dirsAziZenRad, fs, *, order=None, micRadius=
     """What the decoding filters wL, wR ([len x C], or a list of such sets) render for a plane wave from each direction of
     dirsAziZenRad [D x 2]: Hhat_e(k, d) = sum_c fft(w_e, nfft)(k, c) pwGrid_k(c, d) on the bins 0..nfft/2, with pwGrid_k the operand
     of the matching reference design -- model 'sh' (LS / MagLS: order), 'emagls' (order, micRadius, micGridAziZenRad), 'emagls2'
-    (micRadius, micGridAziZenRad) or 'atf' (atfIrs [taps x numMics x D], given on the evaluation directions).  nfft defaults to
+    (micRadius, micGridAziZenRad), 'atf' (atfIrs [taps x numMics x D], given on the evaluation directions), or, for an equatorial
+    array, 'ema_ch' (getEMagLsFiltersEMAinCH: 2*order+1 circular-harmonic channels) and 'ema_sh' (getEMagLsFiltersEMAinSH:
+    (order+1)^2 channels); these two take order, micRadius and micGridAziZenRad as [M] azimuths, or [M x 2] with every zenith
+    pi/2.  nfft defaults to
     min(2048, 2*len).  With reference HRIRs hL, hR ([numSamples x D], one pair or one per filter set) the error metrics of
     include/emagls.h (emagls_rendered_hrtfs) are returned too; weights [D] are direction weights (uniform if absent).
     returnResponse=False computes the metrics alone."""
@@ -1155,14 +1158,23 @@ def getRenderedHrtfs(wL, wR, model, dirsAziZenRad, fs, *, order=None, micRadius=
         D = dirs.shape[0]
         azi, _p = _vec(dirs[:, 0])
         zen, _p = _vec(dirs[:, 1])
-        if model in ("sh", "emagls") and order is None:
+        if model in ("sh", "emagls", "ema_ch", "ema_sh") and order is None:
             raise ValueError("model %r needs order" % model)
         if model != "sh":
             if micRadius is None or micGridAziZenRad is None:
                 raise ValueError("model %r needs micRadius and micGridAziZenRad" % model)
             grid = np.asarray(micGridAziZenRad, dtype=np.float64)
-            maz, _p = _vec(grid[:, 0])
-            mzn, _p = _vec(grid[:, 1])
+            if model in ("ema_ch", "ema_sh"):          # an equatorial array: azimuths alone (the library does not look at zeniths)
+                if grid.ndim == 2 and grid.shape[1] == 2 and np.all(grid[:, 1] == np.pi / 2):
+                    grid = grid[:, 0]
+                elif grid.ndim == 2 and grid.shape[1] == 1:
+                    grid = grid[:, 0]
+                if grid.ndim != 1:
+                    raise ValueError("model %r needs micGridAziZenRad as [M] azimuths, or [M x 2] with every zenith pi/2" % model)
+                maz, _p = _vec(grid)
+            else:
+                maz, _p = _vec(grid[:, 0])
+                mzn, _p = _vec(grid[:, 1])
             M = maz.size
     n_fft = int(nfft) if nfft else min(2048, 2 * ln)
     P = n_fft // 2 + 1

@@ -317,6 +317,9 @@ void launch_rh_join(const void* F, int64_t n, void* W, hipStream_t st);
 // T = (W A) b_n with A [C][ldA] (null: T = W) and bn [P][nOrd] (null: 1); ldR >= 4 nsets rh_bins_padded(P)
 void launch_rh_modes(const void* W, int C, int P, int nsets, const void* A, bool a_cplx, int ldA, const void* bn, int nOrd, int S, bool y_cplx,
                      double* Tt, int64_t ldR, hipStream_t st);
+// Tt [Kpad][ldR], K = nOrd C (2 nOrd C with complex order terms): row n C + c = W(k, c) b_n(k), against the UNconjugated right operand
+// QT' [nOrd][C][ld] of the EMAinSH model; C <= 64, nOrd <= 86
+void launch_rh_order_rows(const void* W, int C, int P, int nsets, const void* bn, int nOrd, bool q_cplx, double* Tt, int64_t ldR, hipStream_t st);
 void launch_rh_interleave(const void* Y, int64_t ldi, int S, int64_t D, double* Yk, int64_t ldo, hipStream_t st);
 struct RhOut {
     const void* H = nullptr;       // reference spectra [hset][2][P][D] complex (null: no metrics)

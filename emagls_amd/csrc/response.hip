@@ -2,7 +2,8 @@
 // ear, and the error metrics against reference HRTFs, reduced in the product's epilogue.
 //   rh_split / rh_join   complex taps as two real planes through the real FFTs of fft.hip, and back
 //   rh_modes             T(k, s) = (sum_c W(k, c) A(c, s)) b_n(s)(k), written as the K-major real operand of the product
-//   rh_interleave        conj(Y) of a complex basis as real rows [2 s + re/im][d]
+//   rh_order_rows        T(k, (n, c)) = W(k, c) b_n(k): the left operand against the rotated order terms QT' of the EMAinSH model
+//   rh_interleave        a complex right operand as real rows [2 s + re/im][d]
 //   rh_gemm              Hhat = T conj(Y) on v_mfma_f64_16x16x4_f64 with the metric epilogue
 //   rh_atf               the [2 x M] [M x D] product of the ATF model, thread = direction, the same epilogue
 //   rh_reduce            partial sums over direction tiles, in tile order (no floating-point atomics anywhere)
@@ -76,6 +77,45 @@ __global__ void __launch_bounds__(256) rh_modes_kernel(const cplx* __restrict__ 
         } else {
             Tt[(int64_t)(2 * s) * ldR + row] = part ? v.y : v.x;
             Tt[(int64_t)(2 * s + 1) * ldR + row] = part ? -v.x : v.y;
+        }
+    }
+}
+
+// Left operand of the EMAinSH model (emash.hip): Hhat(k, d) = sum_n b_n(k) sum_c W(k, c) QT'_n(c, d), so row j = n C + c of the product
+// holds W(k, c) b_n(k) in the row layout of rh_modes_kernel, bn as there.  QT' enters the product as it is, NOT conjugated like Y:
+//   Re Hhat = Re T Re Q - Im T Im Q,   Im Hhat = Im T Re Q + Re T Im Q,
+// so with a complex basis row 2 j + 1 (the one that meets Im Q_j) carries the opposite sign of rh_modes_kernel's.
+// Workgroup = one tile of one set; the bins past P are written as zeros.
+constexpr int RH_OR_CMAX = 64, RH_OR_NMAX = 86;   // SH order 7; simulation order 85, the entry point's limit
+__global__ void __launch_bounds__(256) rh_order_rows_kernel(const cplx* __restrict__ W, int C, int P, int Pp, const cplx* __restrict__ bn, int nOrd,
+                                                            int q_cplx, double* __restrict__ Tt, int64_t ldR) {
+    __shared__ cplx Ws[8 * RH_OR_CMAX];
+    __shared__ cplx Bs[4 * RH_OR_NMAX];
+    const int tile = blockIdx.x, set = blockIdx.y, k0 = 4 * tile;
+    for (int i = threadIdx.x; i < 8 * C; i += blockDim.x) {
+        const int c = i % C, qe = i / C, q = qe >> 1, ear = qe & 1, k = k0 + q;
+        Ws[i] = k < P ? W[(((int64_t)set * 2 + ear) * P + k) * C + c] : mk(0.0, 0.0);
+    }
+    for (int i = threadIdx.x; i < 4 * nOrd; i += blockDim.x) {
+        const int n = i % nOrd, k = k0 + i / nOrd;
+        cplx b = k < P ? bn[(size_t)k * nOrd + n] : mk(0.0, 0.0);
+        if (k == P - 1) b.y = 0.0;
+        Bs[i] = b;
+    }
+    __syncthreads();
+    const int r16 = threadIdx.x & 15, q = r16 & 3, comp = r16 >> 2, ear = comp >> 1, part = comp & 1;
+    const cplx* w = Ws + (q * 2 + ear) * C;
+    const cplx* b = Bs + q * nOrd;
+    const int64_t row = ((int64_t)set * (Pp / 4) + tile) * 16 + r16;
+    const int J = nOrd * C;
+    for (int j = threadIdx.x >> 4; j < J; j += 16) {
+        const int n = j / C, c = j - n * C;
+        const cplx v = w[c] * b[n];
+        if (!q_cplx) {
+            Tt[(int64_t)j * ldR + row] = part ? v.y : v.x;
+        } else {
+            Tt[(int64_t)(2 * j) * ldR + row] = part ? v.y : v.x;
+            Tt[(int64_t)(2 * j + 1) * ldR + row] = part ? v.x : -v.y;
         }
     }
 }
@@ -267,6 +307,13 @@ void launch_rh_modes(const void* W, int C, int P, int nsets, const void* A, bool
         rh_modes_kernel<cplx><<<grid, 256, 0, st>>>((const cplx*)W, C, P, Pp, (const cplx*)A, ldA, (const cplx*)bn, nOrd, S, y_cplx ? 1 : 0, Tt, ldR);
     else
         rh_modes_kernel<double><<<grid, 256, 0, st>>>((const cplx*)W, C, P, Pp, (const double*)A, ldA, (const cplx*)bn, nOrd, S, y_cplx ? 1 : 0, Tt, ldR);
+    KERNEL_CHECK();
+}
+
+void launch_rh_order_rows(const void* W, int C, int P, int nsets, const void* bn, int nOrd, bool q_cplx, double* Tt, int64_t ldR, hipStream_t st) {
+    if (C > RH_OR_CMAX || nOrd > RH_OR_NMAX) throw Error(2, "rendered HRTFs: order rows of more than 64 channels or 86 orders");
+    const int Pp = rh_bins_padded(P);
+    rh_order_rows_kernel<<<dim3(Pp / 4, nsets), 256, 0, st>>>((const cplx*)W, C, P, Pp, (const cplx*)bn, nOrd, q_cplx ? 1 : 0, Tt, ldR);
     KERNEL_CHECK();
 }
 

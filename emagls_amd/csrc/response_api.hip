@@ -1,6 +1,7 @@
 // C ABI of the rendered HRTFs of a design (include/emagls.h, emagls_rendered_hrtfs).  Host arrays in, host
 // arrays out; every argument is checked before the device is touched, and every array operation runs in the kernels of
-// response.hip, fft.hip (the spectra), sh_basis.hip, modal.hip and factor.hip (pinv(Y_lo)).  No CPU fallback.
+// response.hip, fft.hip (the spectra), sh_basis.hip, modal.hip and factor.hip (pinv(Y_lo)); the equatorial-array models take their
+// operands from the design's own kernels (emash.hip, dspace.hip, wide_array.hip).  No CPU fallback.
 #include <cmath>
 #include <vector>
 
@@ -17,6 +18,8 @@ constexpr int RH_NFFT_MAX = 2048;          // the designs' own limit (lib/getEMa
 constexpr int RH_SIM_ORDER_MAX = 85;
 constexpr int64_t RH_DIRS_MAX = 65536;
 constexpr size_t RH_SCRATCH_MAX = (size_t)24 << 30;
+constexpr size_t RH_QT_LDS = (size_t)150 * 1024;   // launch_qt: four rows of conj(Y) per workgroup at the least
+inline int ema_sh_npts(int C) { return 4 * C + 8; }   // points of the rotation fit (host_internal.hpp, oracle.shRotationForElevation)
 
 // spectra of real columns x [ncols][L] at out[k ldo + (j / inner) ld_inner + j % inner]
 void real_spectra(Scratch& s, const double* x, int64_t L, int64_t ncols, const int64_t* colidx, int nfft, const cplx* tw, cplx* out, int64_t ldo,
@@ -34,12 +37,13 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
                                      double* cov_hat, double* cov_ref) {
     return guarded_call([&] {
         // ---- arguments (nothing below this block fails on what the caller passed)
-        if (model < EMAGLS_MODEL_SH || model > EMAGLS_MODEL_ATF) throw Error(EMAGLS_ERR_ARG, "unknown model");
+        const bool ema_ch = model == EMAGLS_MODEL_EMA_CH, ema_sh = model == EMAGLS_MODEL_EMA_SH, is_ema = ema_ch || ema_sh;
+        if ((model < EMAGLS_MODEL_SH || model > EMAGLS_MODEL_ATF) && !is_ema) throw Error(EMAGLS_ERR_ARG, "unknown model");
         const bool is_sh = model == EMAGLS_MODEL_SH, is_atf = model == EMAGLS_MODEL_ATF, is_array = !is_sh && !is_atf;
         const bool raw = model == EMAGLS_MODEL_EMAGLS2;
         if (!wL || !wR) throw Error(EMAGLS_ERR_ARG, "null pointer: decoding filters");
         if (!is_atf && (!dir_azi || !dir_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: evaluation directions");
-        if (is_array && (!mic_azi || !mic_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: microphone grid");
+        if (is_array && (!mic_azi || (!mic_zen && !is_ema))) throw Error(EMAGLS_ERR_ARG, "null pointer: microphone grid");
         if (is_atf && !atf) throw Error(EMAGLS_ERR_ARG, "null pointer: ATFs");
         const bool metrics = mag_err_db || ild_err_db || cov_hat || cov_ref;
         if (!Hhat && !metrics) throw Error(EMAGLS_ERR_ARG, "null pointer: no output is asked for");
@@ -70,7 +74,16 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
         if (is_array) {
             if (!(fs > 0) || !(mic_radius > 0)) throw Error(EMAGLS_ERR_ARG, "fs and micRadius must be positive");
             int ord = 4;                                      // lib/getEMagLs2Filters.m:51-63 leaves params.order at its default
-            if (!raw) {
+            if (is_ema) {
+                // lib/getEMagLsFiltersEMAinCH.m:52-65, lib/getEMagLsFiltersEMAinSH.m:66-100: 2 order + 1 circular harmonics of the microphones
+                if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
+                if (ema_ch && order > 15) throw Error(EMAGLS_ERR_UNSUPPORTED, "the ema_ch model is limited to order 15 (31 circular harmonics)");
+                if (ema_sh && order > 7) throw Error(EMAGLS_ERR_UNSUPPORTED, "the ema_sh model is limited to SH order 7");
+                ord = order;
+                nOut = 2 * order + 1;
+                if (M < nOut) throw Error(EMAGLS_ERR_UNSUPPORTED, "fewer microphones than circular harmonics (2*order+1)");
+                C = ema_ch ? nOut : (order + 1) * (order + 1);
+            } else if (!raw) {
                 if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
                 if (order > 4)
                     throw Error(EMAGLS_ERR_UNSUPPORTED, "the emagls model is limited to SH order 4 (pinv(Y_lo) of emagls_get_smair_matrix); orders 5..7 are not supported");
@@ -82,6 +95,9 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
             simOrder = std::max(ord, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));     // getSMAIRMatrix.m:95
             if (simOrder > RH_SIM_ORDER_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "simulation order above 85 is not supported");
             S = (simOrder + 1) * (simOrder + 1);
+            if (ema_sh && 4 * esz(cb) * (size_t)(S + 1) > RH_QT_LDS)
+                throw Error(EMAGLS_ERR_UNSUPPORTED, cb ? "the ema_sh model is limited to simulation order 47 with a complex basis (the order terms' tile)"
+                                                       : "the ema_sh model is limited to simulation order 68 (the order terms' tile)");
         }
         if (is_atf) {
             if (atf_taps < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: atf_taps");
@@ -95,7 +111,14 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
             if (nhrir_sets != 1 && nhrir_sets != nsets) throw Error(EMAGLS_ERR_ARG, "the number of HRIR sets must be 1 or nsets");
         }
         const int64_t D = ndirs;
-        std::vector<double> wn;
+        std::vector<double> wn, equator, na;
+        if (is_ema) equator.assign((size_t)std::max<int64_t>(M, ema_sh ? std::max<int64_t>(D, C) : 0), kPi / 2.0);   // an EMA's microphones; the projected grid
+        for (int c = 0; ema_sh && c < C; ++c) {   // one azimuth per channel at which its circular harmonic is 1 (or sqrt 2): launch_ema_sh_e0
+            int n = 0;
+            while ((n + 1) * (n + 1) <= c) ++n;
+            const int m = c - n * n - n;
+            na.push_back((!cb && m < 0) ? kPi / (2.0 * -m) : 0.0);
+        }
         if (metrics) {
             wn.assign((size_t)D, 1.0 / (double)D);
             if (weights) {
@@ -110,12 +133,19 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
         }
         // ---- sizes
         const int NM = rh_num_metrics(), Pp = rh_bins_padded(P);
-        const int K = (cb && !is_atf) ? 2 * S : S, Kpad = (int)(ceil_div(K, 4) * 4);
+        // inner dimension of the product: the SH channels of the simulation, or (ema_sh) the order terms of every output channel
+        const int nOrd = simOrder + 1, Kre = ema_sh ? nOrd * C : S;
+        const int K = (cb && !is_atf) ? 2 * Kre : Kre, Kpad = (int)(ceil_div(K, 4) * 4);
         const int64_t ldR = (int64_t)nsets * Pp * 4, ldY = ceil_div(D, 64) * 64;
         const int ntile = is_atf ? rh_atf_tiles(D) : rh_gemm_tiles(D);
         const size_t nW = (size_t)nsets * 2 * P * C;
+        // ema_sh: the rotation fit (rotated points, their SH matrix, Rot), conj(Y) of the projected grid twice, complex order terms
+        const int npts = ema_sh_npts(C);
+        const int64_t ldA = ceil_div((int64_t)(D + 1) * npts, 64) * 64, ldSs = ceil_div((int64_t)S, 64) * 64;
+        const size_t need_ema = !ema_sh ? 0 : esz(cb) * ((size_t)C * ldA + (size_t)D * C * C + (size_t)S * ldY + (size_t)D * ldSs) +
+                                                  (size_t)ldA * 16 + (cb ? (size_t)Kre * ldY * 16 : 0);
         const size_t need = nW * 16 * (w_is_complex ? 4 : 2) + (is_atf ? (size_t)P * M * D * 16 + (size_t)atf_taps * M * D * 8
-                                                                        : (size_t)Kpad * (ldR + ldY) * 8 + (cb ? (size_t)S * D * 16 : 0)) +
+                                                                        : (size_t)Kpad * (ldR + ldY) * 8 + (cb && !ema_sh ? (size_t)S * D * 16 : 0)) + need_ema +
                             (metrics ? (size_t)nhrir_sets * 2 * D * (nsamp * 8 + (size_t)P * 16) + (size_t)nsets * P * ntile * NM * 8 : 0) +
                             (Hhat ? (size_t)nsets * 2 * P * D * 16 : 0);
         if (need > RH_SCRATCH_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "the call needs more than 24 GiB of device memory; split the filter sets over several calls");
@@ -178,16 +208,16 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
             launch_rh_atf(W, A, M, P, D, (int)nsets, o, s.st);
             s.sync();   // (colidx lives on the host until its copy has run)
         } else {
-            // conj(Y(dirs)) as real rows Yk [Kpad][ldY]
+            // conj(Y(dirs)) as real rows Yk [Kpad][ldY]  (ema_sh: the rotated order terms QT' in their place, below)
             const int N = is_sh ? order : simOrder;
             const double* d_azi = s.put(dir_azi, (size_t)D);
             const double* d_zen = s.put(dir_zen, (size_t)D);
             double* tab = s.get<double>(sizeof(double) * sh_coeff_count(N));
             launch_sh_coeff(N, tab, s.st);
             double* Yk = s.get<double>(sizeof(double) * (size_t)Kpad * ldY, true);
-            if (!cb) {
+            if (!ema_sh && !cb) {
                 launch_sh_basis(N, D, d_azi, d_zen, tab, false, Yk, ldY, s.st);
-            } else {
+            } else if (!ema_sh) {
                 void* Yc = s.get(sizeof(cplx) * (size_t)S * D);
                 launch_sh_basis(N, D, d_azi, d_zen, tab, true, Yc, D, s.st);
                 launch_rh_interleave(Yc, D, S, D, Yk, ldY, s.st);
@@ -201,7 +231,7 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
                 // E = pinv(Y_lo) Y_mic, or Y_mic for raw microphone signals: the steps of emagls_get_smair_matrix (getSMAIRMatrix.m:102, :119-121)
                 const int ldM = (int)(ceil_div(M, 64) * 64), ldS = (int)(ceil_div(S, 64) * 64);
                 const double* m_azi = s.put(mic_azi, (size_t)M);
-                const double* m_zen = s.put(mic_zen, (size_t)M);
+                const double* m_zen = s.put(is_ema ? equator.data() : mic_zen, (size_t)M);
                 void* Ycm = s.get(esz(cb) * (size_t)S * M);
                 void* Yrm = s.get(esz(cb) * (size_t)ldM * ldS, true);
                 launch_sh_basis(simOrder, M, m_azi, m_zen, tab, cb, Ycm, M, s.st);
@@ -214,7 +244,8 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
                     double* tau = s.get<double>(sizeof(double) * nOut);
                     cplx* R2 = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
                     cplx* Nw = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
-                    launch_widen(Ycm, M, cb, Yc, ldM, nOut, M, false, false, s.st);
+                    if (is_ema) launch_ch_basis(order, M, m_azi, cb, Yc, ldM, s.st);   // pinv(getCH(order, micAzi))  (EMAinCH.m:70)
+                    else launch_widen(Ycm, M, cb, Yc, ldM, nOut, M, false, false, s.st);
                     FactorArgs a{};
                     a.S = M; a.C = nOut; a.ldS = ldM; a.kb0 = 0; a.P = 2;
                     a.Xd = Yc; a.xd_stride = 0;
@@ -228,7 +259,56 @@ extern "C" int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, 
                 cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)P * (simOrder + 1));
                 const double kr_step = 2.0 * kPi * ((fs / 2.0) / (double)(P - 1)) / C_SOUND * mic_radius;
                 launch_modal_bn(simOrder, P, nullptr, kr_step, -1.0, bn, simOrder + 1, 1, s.st);     // bnAll = -sphModalCoeffs(...)  (:107)
-                launch_rh_modes(W, C, P, (int)nsets, E, cb, ldS, bn, simOrder + 1, S, cb, Tt, ldR, s.st);
+                if (!ema_sh) {
+                    launch_rh_modes(W, C, P, (int)nsets, E, cb, ldS, bn, simOrder + 1, S, cb, Tt, ldR, s.st);
+                } else {
+                    // E0 = J E (circular -> spherical harmonics, EMAinSH.m:77-82) and the per-direction rotations (:85-100): the
+                    // design's own sequence (ema_sh_operands, plan_run.hip)
+                    const int ldP = (int)(ceil_div(npts, 64) * 64);
+                    const double* zen_eq = s.put(equator.data(), (size_t)std::max<int64_t>(D, C));
+                    double* tab_lo = s.get<double>(sizeof(double) * sh_coeff_count(order));
+                    void* Ypts = s.get(esz(cb) * (size_t)C * C);
+                    void* E0 = s.get(esz(cb) * (size_t)C * ldS, true);
+                    launch_sh_coeff(order, tab_lo, s.st);
+                    launch_sh_basis(order, C, s.put(na.data(), (size_t)C), zen_eq, tab_lo, cb, Ypts, C, s.st);
+                    launch_ema_sh_e0(E, ldS, Ypts, C, S, cb, E0, s.st);
+                    double* rot_azi = s.get<double>(sizeof(double) * (size_t)ldA);
+                    double* rot_zen = s.get<double>(sizeof(double) * (size_t)ldA);
+                    char* Arot = s.get<char>(esz(cb) * (size_t)C * ldA);
+                    launch_rot_points(d_azi, d_zen, (int)D, npts, rot_azi, rot_zen, s.st);
+                    launch_sh_basis(order, (D + 1) * npts, rot_azi, rot_zen, tab_lo, cb, Arot, ldA, s.st);
+                    cplx* Bc = s.get<cplx>(sizeof(cplx) * (size_t)C * ldP, true);
+                    cplx* Zb = s.get<cplx>(sizeof(cplx) * (size_t)C * ldP, true);
+                    cplx* Vb = s.get<cplx>(sizeof(cplx) * (size_t)C * ldP, true);
+                    double* tau_b = s.get<double>(sizeof(double) * C);
+                    cplx* R2_b = s.get<cplx>(sizeof(cplx) * (size_t)C * C);
+                    cplx* N_b = s.get<cplx>(sizeof(cplx) * (size_t)C * C);
+                    launch_widen(Arot + esz(cb) * (size_t)D * npts, ldA, cb, Bc, ldP, C, npts, false, false, s.st);   // the unrotated point set
+                    if (C > 32) {   // orders 5..7: wide_array.hip's QR + one-sided Jacobi, no clipping
+                        double* sv = s.get<double>(sizeof(double) * C);
+                        int* sweeps = s.get<int>(sizeof(int) * 4);
+                        launch_wa_factor(Bc, Vb, npts, C, ldP, 1, 0.0, tau_b, R2_b, N_b, sv, sweeps, Zb, s.st);
+                    } else {
+                        FactorArgs a{};
+                        a.S = npts; a.C = C; a.ldS = ldP; a.kb0 = 0; a.P = 2;
+                        a.Xd = Bc; a.xd_stride = 0;
+                        a.reg_mode = 1; a.tol_dim = (double)std::max(npts, C);
+                        a.Z = Zb; a.Vws = Vb; a.tauw = tau_b; a.R2w = R2_b; a.Nw = N_b;
+                        launch_factor(a, 1, true, s.st);
+                    }
+                    void* Rot = s.get(esz(cb) * (size_t)D * C * C);
+                    launch_rot_from_points(Arot, ldA, Zb, ldP, C, npts, d_zen, (int)D, cb, Rot, s.st);
+                    // order terms of pwGrid.' on the horizontal projection of the grid, every direction's row rotated: QT' [nOrd][C][ldY]
+                    void* Yh = s.get(esz(cb) * (size_t)S * ldY);
+                    void* Yc = s.get(esz(cb) * (size_t)D * ldS);
+                    launch_sh_basis(simOrder, D, d_azi, zen_eq, tab, cb, Yh, ldY, s.st);
+                    launch_transpose_conj(Yh, D, S, ldY, Yc, D, ldS, cb, true, s.st);
+                    void* QT = cb ? s.get(sizeof(cplx) * (size_t)Kre * ldY, true) : (void*)Yk;   // (real basis: Yk itself, zero beyond D and K)
+                    launch_qt(Yc, ldS, E0, ldS, (int)D, S, C, nOrd, cb, QT, ldY, s.st);
+                    launch_qt_rotate(QT, ldY, nOrd, C, order, (int)D, Rot, cb, s.st);
+                    if (cb) launch_rh_interleave(QT, ldY, Kre, D, Yk, ldY, s.st);
+                    launch_rh_order_rows(W, C, P, (int)nsets, bn, nOrd, cb, Tt, ldR, s.st);
+                }
             }
             // 3. the product and its epilogue
             launch_rh_gemm(Tt, ldR, Yk, ldY, Kpad, P, D, (int)nsets, o, s.st);

@@ -526,6 +526,17 @@ int emagls_get_magls_array_diffuse_filter(double mic_radius, const double* mic_a
  *   EMAGLS_MODEL_ATF      pwGrid_k(m, d) = fft(atfIrs, nfft)(k, m, d), atf [atf_taps x nmics x ndirs] column-major GIVEN ON the
  *                         evaluation directions (the caller has matched the grids); C = nmics <= 64, atf_taps <= nfft; dir_azi,
  *                         dir_zen, basis are not looked at
+ *   EMAGLS_MODEL_EMA_CH   pinv(getCH(order, micAzi)) * smairMat(:,:,k) * getSH(simOrder, dirs, shDefinition)' with getSMAIRMatrix called
+ *                         as lib/getEMagLsFiltersEMAinCH.m:52-65 calls it (raw microphone signals, params.order = order, the microphones at
+ *                         zenith pi/2, otherwise as for EMAGLS_MODEL_EMAGLS); C = 2*order+1 in getCH's channel order, order <= 15
+ *   EMAGLS_MODEL_EMA_SH   pwGrid_k(:, d) = Rot_d.' * J * pinv(getCH(order, micAzi)) * smairMat(:,:,k) * conj(getSH(simOrder, [azi_d, pi/2])).'
+ *                         (lib/getEMagLsFiltersEMAinSH.m:66-100): the same array on the HORIZONTAL projection of the directions, J =
+ *                         getChToShExpansionMatrix, Rot_d the SH rotation to the direction's elevation that emagls_get_emagls_filters_ema_in_sh
+ *                         uses (the identity where zen_d == pi/2 exactly); C = (order+1)^2, order <= 7, simOrder <= 68 (47 with a complex basis)
+ *                         Both EMA models: nmics >= 2*order+1 (fewer: EMAGLS_ERR_UNSUPPORTED); mic_zen is not looked at and may be NULL.
+ *                         Value 4 is not assigned.  The scratch of EMAGLS_MODEL_EMA_SH grows with ndirs * C^2 (the rotation fit): the
+ *                         24 GiB estimate refuses 65536 directions at order 7 with a complex basis; with a real basis that size
+ *                         passes the estimate (about 12 GB) but has NOT been run -- the largest call run is 2702 directions.
  * smairMat is never formed: the call works on its factors.  Arguments a model does not use may be NULL / 0.
  * wL, wR: nsets >= 1 filter sets back to back, each [len x nchan] column-major as the designs return them, real, or interleaved
  * complex with w_is_complex; nchan must equal the model's C.  ndirs <= 65536.
@@ -544,6 +555,8 @@ int emagls_get_magls_array_diffuse_filter(double mic_radius, const double* mic_a
 #define EMAGLS_MODEL_EMAGLS 1
 #define EMAGLS_MODEL_EMAGLS2 2
 #define EMAGLS_MODEL_ATF 3
+#define EMAGLS_MODEL_EMA_CH 5
+#define EMAGLS_MODEL_EMA_SH 6
 int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, int w_is_complex, int64_t len, int64_t nchan, int64_t nsets,
                           const double* dir_azi, const double* dir_zen, int64_t ndirs, double fs, int order, int basis,
                           double mic_radius, const double* mic_azi, const double* mic_zen, int64_t nmics, const double* atf,

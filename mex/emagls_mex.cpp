@@ -643,8 +643,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         mxGetString(prhs[3], mbuf, sizeof mbuf);
         const std::string mname(mbuf);
         const int model = mname == "sh" ? EMAGLS_MODEL_SH : mname == "emagls" ? EMAGLS_MODEL_EMAGLS : mname == "emagls2" ? EMAGLS_MODEL_EMAGLS2
-                        : mname == "atf" ? EMAGLS_MODEL_ATF : -1;
-        if (model < 0) mexErrMsgIdAndTxt("eMagLS:arg", "model must be 'sh', 'emagls', 'emagls2' or 'atf'");
+                        : mname == "atf" ? EMAGLS_MODEL_ATF : mname == "ema_ch" ? EMAGLS_MODEL_EMA_CH : mname == "ema_sh" ? EMAGLS_MODEL_EMA_SH : -1;
+        if (model < 0) mexErrMsgIdAndTxt("eMagLS:arg", "model must be 'sh', 'emagls', 'emagls2', 'atf', 'ema_ch' or 'ema_sh'");
+        const bool ema = model == EMAGLS_MODEL_EMA_CH || model == EMAGLS_MODEL_EMA_SH;
         auto given = [&](int i) { return prhs[i] && !mxIsEmpty(prhs[i]); };
         auto grid = [&](int i, const char* what, mwSize* n) -> const double* {
             if (!given(i)) { *n = 0; return nullptr; }
@@ -654,7 +655,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         };
         mwSize D = 0, M = 0, taps = 0;
         const double* dirs = grid(4, "dirsAziZenRad", &D);
-        const double* mics = grid(8, "micGridAziZenRad", &M);
+        // (an equatorial array: a vector of azimuths, or [M x 2] with every zenith pi/2; the library does not look at the zeniths)
+        const bool azi_only = ema && given(8) && mxGetN(prhs[8]) != 2 && (mxGetM(prhs[8]) == 1 || mxGetN(prhs[8]) == 1);
+        const double* mics = azi_only ? dbl(prhs[8], "micGridAziZenRad") : grid(8, "micGridAziZenRad", &M);
+        if (azi_only) M = mxGetNumberOfElements(prhs[8]);
+        for (mwSize i = 0; ema && mics && !azi_only && i < M; ++i)
+            if (mics[M + i] != 1.5707963267948966) mexErrMsgIdAndTxt("eMagLS:arg", "an equatorial array's micGridAziZenRad must have every zenith at pi/2");
         const double* atf = nullptr;
         if (given(9)) {
             atf = dbl(prhs[9], "atfIrs");
@@ -690,7 +696,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (hL) { mag.resize((size_t)f.nsets * P * 2); ild.resize((size_t)f.nsets * P); ch.resize((size_t)f.nsets * P * 4); cr.resize(ch.size()); }
         auto ptr = [](std::vector<double>& v) { return v.empty() ? nullptr : v.data(); };
         const int rc = emagls_rendered_hrtfs(model, in_ptr(prhs[1]), in_ptr(prhs[2]), f.wc ? 1 : 0, (int64_t)f.len, (int64_t)f.ch, (int64_t)f.nsets, dirs,
-                                             dirs ? dirs + D : nullptr, (int64_t)D, fs, order, basis, radius, mics, mics ? mics + M : nullptr,
+                                             dirs ? dirs + D : nullptr, (int64_t)D, fs, order, basis, radius, mics, mics && !azi_only ? mics + M : nullptr,
                                              (int64_t)M, atf, (int64_t)taps, nfft, hL, hR, (int64_t)nsamp, (int64_t)nh, wts, ptr(H), ptr(mag), ptr(ild),
                                              ptr(ch), ptr(cr));
         if (rc) fail(rc);

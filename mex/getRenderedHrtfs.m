@@ -5,7 +5,10 @@ function [H, metrics] = getRenderedHrtfs(wL, wR, model, dirsAziZenRad, fs, varar
 %   [H, metrics] = getRenderedHrtfs(wL, wR, model, dirsAziZenRad, fs, 'name', value, ...)
 %   wL, wR   [len x numChannels] or [len x numChannels x numSets]
 %   model    'sh' (order) | 'emagls' (order, micRadius, micGridAziZenRad) | 'emagls2' (micRadius, micGridAziZenRad) |
-%            'atf' (atfIrs [taps x numMics x numDirections], given ON the evaluation directions)
+%            'atf' (atfIrs [taps x numMics x numDirections], given ON the evaluation directions) |
+%            'ema_ch' | 'ema_sh' (order, micRadius, micGridAziZenRad): an equatorial array as getEMagLsFiltersEMAinCH (2*order+1
+%            circular-harmonic channels, order <= 15) and getEMagLsFiltersEMAinSH ((order+1)^2 channels, order <= 7) model it;
+%            micGridAziZenRad is then a vector of azimuths, or [numMics x 2] with every zenith pi/2
 %   further names: nfft (default min(2048, 2*len)), shDefinition ('real'), hL, hR ([numSamples x numDirections (x numSets)]),
 %   weights ([numDirections], uniform if absent), returnResponse (true)
 %   H        [nfft/2+1 x numDirections x 2 x numSets] ([] with returnResponse false)
