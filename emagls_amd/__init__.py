@@ -4,12 +4,12 @@ The Python layer mirrors the reference's MATLAB entry points over the C ABI in i
 Importing the package does not need a GPU; calling any function needs emagls_amd/lib/libemagls.so
 (python -m emagls_amd.build) and an MI355X -- there is no CPU fallback.
 """
-from .api import (BinauralDecodeStream, BinauralDecodeGroup, arrayEncoder, designYawBank, yawBankIndex, applyRadialFilter, binauralDecode, designHrirSets, encodeSH, fromAtfHrirSets, getEMagLs2Filters, getEMagLsFilters, getEMagLsFiltersEMAinCH, getEMagLsFiltersEMAinSH,
+from .api import (BinauralDecodeStream, BinauralDecodeGroup, SourceFieldStream, arrayEncoder, designYawBank, yawBankIndex, applyRadialFilter, binauralDecode, designHrirSets, encodeSH, fromAtfHrirSets, getEMagLs2Filters, getEMagLsFilters, getEMagLsFiltersEMAinCH, getEMagLsFiltersEMAinSH,
                   getEMagLsFiltersFromAtf, getLsFilters, getMagLsArrayDiffuseFilter, getMagLsFilters, getMagLsFilters2D,
                   getMagLsSphericalHeadFilter, getCH, getRadialFilter, getRenderedHrtfs, getSH, getSMAIRMatrix, RenderedHrtfs, resample, rotateSH, rotateYaw, shRotationMatrix,
                   sphModalCoeffs)
 from .plan import Batch, Plan
 
 __all__ = ["getLsFilters", "getMagLsFilters", "getEMagLsFilters", "getEMagLs2Filters", "getEMagLsFiltersEMAinCH", "getEMagLsFiltersEMAinSH", "getEMagLsFiltersFromAtf",
-           "binauralDecode", "BinauralDecodeStream", "BinauralDecodeGroup", "arrayEncoder", "designYawBank", "yawBankIndex", "resample", "rotateYaw", "rotateSH", "shRotationMatrix", "getSH", "getCH", "getSMAIRMatrix", "getRenderedHrtfs", "RenderedHrtfs", "sphModalCoeffs", "getMagLsFilters2D", "getRadialFilter", "applyRadialFilter", "encodeSH",
+           "binauralDecode", "BinauralDecodeStream", "BinauralDecodeGroup", "SourceFieldStream", "arrayEncoder", "designYawBank", "yawBankIndex", "resample", "rotateYaw", "rotateSH", "shRotationMatrix", "getSH", "getCH", "getSMAIRMatrix", "getRenderedHrtfs", "RenderedHrtfs", "sphModalCoeffs", "getMagLsFilters2D", "getRadialFilter", "applyRadialFilter", "encodeSH",
            "getMagLsSphericalHeadFilter", "getMagLsArrayDiffuseFilter", "designHrirSets", "fromAtfHrirSets", "Plan", "Batch"]

@@ -149,6 +149,13 @@ SYMBOLS = {
                                                       C.c_int, c_i64, C.POINTER(C.c_void_p)]),
     "emagls_decode_group_create_encoded": (C.c_int, [c_i64, C.c_void_p, C.c_int, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int, c_i64, C.c_int,
                                                      C.c_int, c_i64, c_i64, C.POINTER(C.c_void_p)]),
+    "emagls_field_stream_create": (C.c_int, [c_i64, c_i64, C.c_void_p, C.c_int, c_i64, c_i64, C.POINTER(C.c_void_p)]),
+    "emagls_field_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p]),
+    "emagls_field_stream_push_device": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "emagls_field_stream_reset": (C.c_int, [C.c_void_p]),
+    "emagls_field_stream_info": (C.c_int, [C.c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64),
+                                           C.POINTER(C.c_int)]),
+    "emagls_field_stream_destroy": (C.c_int, [C.c_void_p]),
     "emagls_get_magls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_double, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_get_emagls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_double,

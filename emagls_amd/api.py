@@ -760,7 +760,8 @@ class BinauralDecodeStream(_DecodeObject):
     signal, each with the head orientation for that block, and returns the two ear signals of that block, [n x 2].  With x the
     concatenation of the pushed blocks and the angles concatenated per sample, the concatenated outputs equal
     binauralDecode(x, fs, wL, wR, fs, False, horRotAngleRad=yaw, pitchRad=pitch, rollRad=roll, shDefinition=..., rotationDomain=...)
-    to rounding: no delay cut (offset your read by len/2 - 1 yourself), no resampling, no source signal; for complex signals or
+    to rounding: no delay cut (offset your read by len/2 - 1 yourself), no resampling; a dry source signal goes through
+    a SourceFieldStream first (whose torch output a push here takes as it lies); for complex signals or
     filters the output is the real part and the discarded imaginary sum is not reported.
     blockSize: a power of two from 64 to 2048.  complexInput: the pushed blocks are complex.  Uniformly partitioned overlap-save
     with its state on the GPU; `info` gives block, partitions, state_bytes, filter_bytes and launches_per_block.
@@ -886,6 +887,109 @@ class BinauralDecodeGroup(_DecodeObject):
         """Zero history for one listener (what a listener who joins gets; the others are untouched) or, with None, for all: what
         follows equals a fresh stream bit for bit."""
         L.check(L.load().emagls_decode_group_reset(self._handle(), -1 if listener is None else int(listener)))
+
+
+class SourceFieldStream:
+    """Dry source signals through array room responses, a block at a time: what the reference's harness
+    does offline with fftfilt(srir.rir, sig) (testEMagLs.m:66-70), for a head that moves while the sound plays.  Created once from
+    rirs [nr x numChannels] (one source) or [numSources x nr x numChannels], real or complex, and a block size (a power of two
+    from 64 to 2048); `push` takes consecutive blocks of the real source signals and returns the field block [n x numChannels].
+    With s_q everything pushed for source q, the concatenated outputs equal sum_q fftfilt(rirs[q][:, c], s_q) to rounding; nothing
+    is held back.  A complex response gives complex output: feed it to a stream created with complexInput=True.
+    The output of a torch push lies as BinauralDecodeStream.push and BinauralDecodeGroup.push read their block: they take it
+    without a copy, and the chain source -> room -> rotation -> filters runs on the device without a host synchronisation.
+    numSources <= 16, numChannels <= 256, nr <= 1048576, response spectra <= 4 GiB; `info` gives block, partitions, state_bytes,
+    response_bytes and launches_per_block."""
+
+    def __init__(self, rirs, blockSize):
+        self._h = None
+        r_c = np.iscomplexobj(rirs)
+        r = np.asarray(rirs, dtype=np.complex128 if r_c else np.float64)
+        if r.ndim == 2:
+            r = r[None]
+        if r.ndim != 3:
+            raise ValueError("rirs must be [nr x numChannels] or [numSources x nr x numChannels]")
+        if int(blockSize) != blockSize:
+            raise ValueError("blockSize must be an integer")
+        self.numSources, nr, self.numChannels = r.shape
+        self.blockSize, self.complexOutput = int(blockSize), bool(r_c)
+        r = np.ascontiguousarray(r.transpose(0, 2, 1))   # the sources one after the other, each column-major [nr x numChannels]
+        h = C.c_void_p()
+        L.check(L.load().emagls_field_stream_create(self.numSources, self.numChannels, r.ctypes.data_as(C.c_void_p), 1 if r_c else 0, nr,
+                                                    self.blockSize, C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the field stream is closed")
+        return self._h
+
+    @property
+    def info(self):
+        b, p, sb, rb, nl = L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), C.c_int(0)
+        L.check(L.load().emagls_field_stream_info(self._handle(), C.byref(b), C.byref(p), C.byref(sb), C.byref(rb), C.byref(nl)))
+        return {"block": b.value, "partitions": p.value, "state_bytes": sb.value, "response_bytes": rb.value, "launches_per_block": nl.value}
+
+    def _check_block(self, shape):
+        if len(shape) == 1 and self.numSources == 1:
+            shape = (shape[0], 1)
+        if len(shape) != 2 or shape[1] != self.numSources:
+            raise ValueError("block must be [n] (one source) or [n x numSources] matching the responses' source count (%d)" % self.numSources)
+        if shape[0] % self.blockSize:
+            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
+        return shape[0]
+
+    def push(self, block):
+        """block [n] or [n x numSources], real, n a multiple of blockSize: a NumPy array (host entry; returns a NumPy array
+        [n x numChannels]), or a torch tensor on the stream's device (device entry on torch's current stream, not synchronised;
+        returns a tensor [n x numChannels] that is the transposed view of the [numChannels][n] buffer the kernel wrote)."""
+        h = self._handle()
+        if type(block).__module__.split(".")[0] == "torch":
+            return self._push_torch(h, block)
+        if np.iscomplexobj(block):
+            raise ValueError("a field stream takes real source signals")
+        x = np.asarray(block, dtype=np.float64)
+        n = self._check_block(x.shape)
+        x = np.asfortranarray(x.reshape(n, self.numSources))
+        out = np.zeros((self.numChannels, n), dtype=np.complex128 if self.complexOutput else np.float64)
+        L.check(L.load().emagls_field_stream_push(h, x.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))
+        return out.T
+
+    def _push_torch(self, h, block):
+        import torch
+        n = self._check_block(tuple(block.shape))
+        if not block.is_cuda:
+            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        if block.is_complex():
+            raise ValueError("a field stream takes real source signals")
+        xt = block.to(torch.float64).reshape(n, self.numSources).t().contiguous()   # [numSources][n]: column-major
+        out = torch.empty((self.numChannels, n), dtype=torch.complex128 if self.complexOutput else torch.float64, device=block.device)
+        with torch.cuda.device(block.device):
+            st = torch.cuda.current_stream().cuda_stream
+            L.check(L.load().emagls_field_stream_push_device(h, C.c_void_p(xt.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(st)))
+        xt.record_stream(torch.cuda.current_stream(block.device))   # (its memory may be reused only after the stream has passed the kernels)
+        return out.t()
+
+    def reset(self):
+        """Zero history: what follows equals a fresh object bit for bit."""
+        L.check(L.load().emagls_field_stream_reset(self._handle()))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L.check(L.load().emagls_field_stream_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def designYawBank(kind, hL, hR, hrirGridAziRad, hrirGridZenRad, yawRad, *, order=4, fs=48000.0, len=512, shDefinition="real",

@@ -35,14 +35,12 @@
 // 0.6 us per block (profiles/r12_decode_group.md); with GROUP = false the kernels are the single stream's, instruction for
 // instruction, and a group of one listener runs those.
 #include "kernels.hpp"
-#include "lds_fft.hpp"
+#include "stream_fft.hpp"
 
 namespace emagls {
 
 namespace {
 
-constexpr int DS_NT = 512;     // threads of every kernel here
-constexpr int DS_ELEMS = 4096; // elements of the transform buffer: DS_ELEMS / Nf transforms per round, 8 loads per thread
 enum { DS_G_ZERO = 0, DS_G_ONE = 1, DS_G_R = 2, DS_G_1MR = 3 };   // gain of a set over a block: 0, 1, r[i] = (i + 1) / B, 1 - r[i]
 
 // the listener strides of a group's launch: of the block (elements of its type; 0: the common block), of pos / sel, of the set
@@ -51,22 +49,9 @@ struct DsListeners { int64_t lsx; int lpos, lset; int64_t lso; };
 struct DsSingle {};
 template <bool GROUP> using DsStrides = std::conditional_t<GROUP, DsListeners, DsSingle>;
 
-__device__ __forceinline__ void ds_twiddles(cplx* tws, int Nf) {
-    for (int j = threadIdx.x; j < Nf / 2; j += DS_NT) {
-        double sn, cs;
-        sincospi(-2.0 * (double)j / (double)Nf, &sn, &cs);   // (exact at the multiples of 1/4: Nf is a power of two)
-        tws[j] = mk(cs, sn);
-    }
-}
-
-// Z = FFT(a + i b) with real a, b:  A[k] = (Z[k] + conj(Z[N-k])) / 2,  B[k] = (Z[k] - conj(Z[N-k])) / (2i)
-__device__ __forceinline__ void ds_unpack(cplx z, cplx zr /* conj(Z[N-k]) */, cplx& pa, cplx& pb) {
-    pa = mk(0.5 * (z.x + zr.x), 0.5 * (z.y + zr.y));
-    pb = mk(0.5 * (z.y - zr.y), -0.5 * (z.x - zr.x));
-}
-
 // Wf[z][p][c][k] (k <= B) = FFT([w_z,c(pB .. pB + B - 1), 0])[k], z = 2 set + ear; wpl [Z][Cp][len] real planes.
-// grid (pairs of planes, P, Z): Z = the (set, ear) pairs of this launch (the launcher cuts a large bank into several)
+// grid (pairs of planes, P, Z): Z = the (set, ear) pairs of this launch (the launcher cuts a large bank into several); the field
+// stream's response spectra are the same thing with Z = its sources (field_stream.hip)
 __global__ void __launch_bounds__(DS_NT) ds_filter_kernel(const double* __restrict__ wpl, int Cp, int64_t len, int B, int log2n, int P,
                                                           cplx* __restrict__ Wf) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
@@ -318,10 +303,6 @@ __global__ void __launch_bounds__(DS_NT) ds_inverse_kernel(const cplx* __restric
     }
 }
 
-size_t ds_forward_lds(int B) { return sizeof(cplx) * ((size_t)DS_ELEMS + DS_ELEMS / 16 + (size_t)B); }
-size_t ds_single_lds(int B) { const size_t Nf = 2 * (size_t)B; return sizeof(cplx) * (Nf + Nf / 16 + Nf / 2); }
-int ds_log2(int Nf) { int l = 0; while ((1 << l) < Nf) ++l; return l; }
-
 void ds_attributes() {
     static PerDeviceOnce once;
     if (!once.first()) return;
@@ -343,16 +324,20 @@ void ds_attributes() {
 
 bool decode_stream_block_ok(int64_t B) { return B >= 64 && B <= 2048 && (B & (B - 1)) == 0; }
 
-void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, int64_t S, cplx* Wf, hipStream_t st) {
+void launch_partition_spectra(const double* wpl, int Cp, int64_t len, int B, int P, int64_t Z, cplx* Wf, hipStream_t st) {
     ds_attributes();
-    // the kernel's "ear" index runs over the 2 S (set, ear) pairs: wpl [S][2] and Wf [S][2] are both laid out that way
-    constexpr int64_t kPairs = 32768;   // (set, ear) pairs per launch: grid.z stays below 65536
-    for (int64_t z0 = 0; z0 < 2 * S; z0 += kPairs) {
-        const dim3 grid((unsigned)((Cp + 1) / 2), (unsigned)P, (unsigned)std::min<int64_t>(kPairs, 2 * S - z0));
+    constexpr int64_t kPerLaunch = 32768;   // sets of planes per launch: grid.z stays below 65536
+    for (int64_t z0 = 0; z0 < Z; z0 += kPerLaunch) {
+        const dim3 grid((unsigned)((Cp + 1) / 2), (unsigned)P, (unsigned)std::min<int64_t>(kPerLaunch, Z - z0));
         ds_filter_kernel<<<grid, DS_NT, ds_single_lds(B), st>>>(wpl + z0 * Cp * len, Cp, len, B, ds_log2(2 * B), P,
                                                                Wf + z0 * P * Cp * (int64_t)(B + 1));
         KERNEL_CHECK();
     }
+}
+
+void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, int64_t S, cplx* Wf, hipStream_t st) {
+    // the kernel's "ear" index runs over the 2 S (set, ear) pairs: wpl [S][2] and Wf [S][2] are both laid out that way
+    launch_partition_spectra(wpl, Cp, len, B, P, 2 * S, Wf, st);
 }
 
 void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, const int* set, int standing, double* out,

@@ -1,0 +1,197 @@
+// C ABI of the field stream (include/emagls.h: emagls_field_stream_*): the argument check, host staging and
+// the object's buffers, in the style of the decode stream's host side (decode_api.hip).  The kernels are field_stream.hip's and, for
+// the response spectra, decode_stream.hip's.  The object owns its device buffers: emagls_cache_clear() does not reach them.
+// No CPU fallback.
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "../../include/emagls.h"
+#include "kernels.hpp"
+#include "scratch.hpp"
+
+using namespace emagls;
+
+struct emagls_field_stream {
+    std::mutex mu;
+    int64_t nch = 0, nr = 0;
+    int device = -1;              // bound at the first use of the device (creation, when there is one)
+    bool ready = false;
+    std::vector<double> rpl;      // [nsrc][planes][nr] the real response planes, until the device has their spectra
+    FieldStreamState d;
+    void* stage[2] = {};          // host entry: the push's input and output on the device, grown on demand and kept
+    size_t stage_cap[2] = {};
+    size_t ring_bytes() const { return sizeof(cplx) * (size_t)d.nsrc * d.P * (d.B + 1); }
+    size_t hist_bytes() const { return sizeof(double) * (size_t)d.nsrc * d.B; }
+    size_t state_bytes() const { return ring_bytes() + hist_bytes() + sizeof(int); }
+    size_t response_bytes() const { return sizeof(cplx) * (size_t)d.nsrc * d.P * d.planes * (d.B + 1); }
+    size_t out_esz() const { return esz(d.out_c); }
+    void release() {
+        hipFree(d.Rf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos);
+        for (int i = 0; i < 2; ++i) { hipFree(stage[i]); stage[i] = nullptr; stage_cap[i] = 0; }
+        d.Rf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr;
+        ready = false;
+    }
+    void zero_state(hipStream_t st) {
+        HIP_CHECK(hipMemsetAsync(d.ring, 0, ring_bytes(), st));
+        HIP_CHECK(hipMemsetAsync(d.hist, 0, hist_bytes(), st));
+        HIP_CHECK(hipMemsetAsync(d.pos, 0, sizeof(int), st));
+    }
+    // the device side, once: buffers, the partition spectra, zero history (mu held)
+    void ensure_device() {
+        if (ready) return;
+        HIP_CHECK(hipGetDevice(&device));
+        try {
+            HIP_CHECK(hipMalloc(&d.Rf, response_bytes()));
+            HIP_CHECK(hipMalloc(&d.ring, ring_bytes()));
+            HIP_CHECK(hipMalloc(&d.hist, hist_bytes()));
+            HIP_CHECK(hipMalloc(&d.pos, sizeof(int)));
+            Scratch s;
+            launch_partition_spectra(s.put(rpl.data(), rpl.size()), d.planes, nr, d.B, d.P, d.nsrc, d.Rf, s.st);
+            zero_state(s.st);
+            s.sync();
+        } catch (...) { release(); device = -1; throw; }
+        rpl = std::vector<double>();
+        ready = true;
+    }
+    template <typename T> T* staged(int i, size_t bytes) {
+        bytes = std::max<size_t>(bytes, 16);
+        if (bytes > stage_cap[i]) { hipFree(stage[i]); stage[i] = nullptr; stage_cap[i] = 0; HIP_CHECK(hipMalloc(&stage[i], bytes)); stage_cap[i] = bytes; }
+        return reinterpret_cast<T*>(stage[i]);
+    }
+};
+
+namespace {
+
+constexpr int64_t kFieldMaxSources = 16, kFieldMaxChannels = 256, kFieldMaxTaps = 1048576;
+constexpr uint64_t kFieldMaxSpectraBytes = 4ull << 30;
+
+void check_push(const emagls_field_stream* f, const void* src, const void* out, int64_t nsamp) {
+    if (!f) throw Error(EMAGLS_ERR_ARG, "null field stream");
+    if (!src || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+    if (nsamp < 0 || nsamp % f->d.B) throw Error(EMAGLS_ERR_ARG, "a push needs a multiple of the block size of samples");
+}
+
+// The blocks of a push in order on st, two launches each; device pointers; not synchronised (f->mu held, device current).
+// d_src [nsrc][nsamp], d_out [nch][nsamp]
+void push_blocks(emagls_field_stream* f, const double* d_src, int64_t nsamp, void* d_out, hipStream_t st) {
+    f->ensure_device();
+    const int64_t B = f->d.B;
+    for (int64_t b = 0; b < nsamp / B; ++b)
+        launch_field_stream_block(f->d, d_src + b * B, nsamp, (char*)d_out + f->out_esz() * (size_t)(b * B), nsamp, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int emagls_field_stream_create(int64_t nsrc, int64_t nch, const void* rir, int rir_is_complex, int64_t nr, int64_t block,
+                               emagls_field_stream** out) {
+    return guarded_call([&] {
+        if (!rir || !out) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        *out = nullptr;
+        if (nsrc < 1 || nch < 1 || nr < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape");
+        if (nsrc > kFieldMaxSources) throw Error(EMAGLS_ERR_UNSUPPORTED, "the field stream supports 1 to 16 sources");
+        if (nch > kFieldMaxChannels) throw Error(EMAGLS_ERR_UNSUPPORTED, "the field stream supports 1 to 256 channels");
+        if (nr > kFieldMaxTaps) throw Error(EMAGLS_ERR_UNSUPPORTED, "the field stream supports responses of up to 1048576 taps");
+        if (!decode_stream_block_ok(block))
+            throw Error(EMAGLS_ERR_UNSUPPORTED, "the field stream supports block sizes 64, 128, 256, 512, 1024 and 2048");
+        const bool rc = rir_is_complex != 0;
+        const int64_t P = ceil_div(nr, block), planes = rc ? 2 * nch : nch;
+        if ((uint64_t)nsrc * (uint64_t)P * (uint64_t)planes * (uint64_t)(block + 1) * sizeof(cplx) > kFieldMaxSpectraBytes)
+            throw Error(EMAGLS_ERR_UNSUPPORTED, "the field stream supports response spectra of up to 4 GiB (nsrc ceil(nr / block) planes (block + 1) 16 bytes)");
+        std::unique_ptr<emagls_field_stream> f(new emagls_field_stream);
+        f->nch = nch; f->nr = nr;
+        f->d.nsrc = (int)nsrc; f->d.planes = (int)planes; f->d.out_c = rc; f->d.B = (int)block; f->d.P = (int)P;
+        // [nr x nch] column-major is [nch][nr] planes as it lies; a complex response is parted into plane 2c = re, 2c + 1 = im
+        const double* r = reinterpret_cast<const double*>(rir);
+        const size_t total = (size_t)nsrc * nch * nr;
+        if (!rc) f->rpl.assign(r, r + total);
+        else {
+            f->rpl.resize(2 * total);
+            for (size_t col = 0; col < (size_t)nsrc * nch; ++col)
+                for (int64_t t = 0; t < nr; ++t) {
+                    f->rpl[(2 * col) * nr + t] = r[2 * (col * nr + t)];
+                    f->rpl[(2 * col + 1) * nr + t] = r[2 * (col * nr + t) + 1];
+                }
+        }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
+            std::lock_guard<std::mutex> lk(f->mu);
+            f->ensure_device();
+        } else {
+            (void)hipGetLastError();
+        }
+        *out = f.release();
+    });
+}
+
+int emagls_field_stream_push_device(emagls_field_stream* f, const double* d_src, int64_t nsamp, void* d_out, void* stream) {
+    return guarded_call([&] {
+        check_push(f, d_src, d_out, nsamp);
+        if (nsamp == 0) return;
+        std::lock_guard<std::mutex> lk(f->mu);
+        DeviceGuard dg(f->device);
+        push_blocks(f, d_src, nsamp, d_out, (hipStream_t)stream);
+    });
+}
+
+int emagls_field_stream_push(emagls_field_stream* f, const double* src, int64_t nsamp, void* out) {
+    return guarded_call([&] {
+        check_push(f, src, out, nsamp);
+        if (nsamp == 0) return;
+        std::lock_guard<std::mutex> lk(f->mu);
+        DeviceGuard dg(f->device);
+        f->ensure_device();
+        hipStream_t st = pool_stream_take();
+        struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
+        const size_t bin = sizeof(double) * (size_t)nsamp * f->d.nsrc, bout = f->out_esz() * (size_t)nsamp * f->nch;
+        double* d_src = f->staged<double>(0, bin);
+        char* d_out = f->staged<char>(1, bout);
+        HIP_CHECK(hipMemcpyAsync(d_src, src, bin, hipMemcpyHostToDevice, st));
+        push_blocks(f, d_src, nsamp, d_out, st);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+
+int emagls_field_stream_reset(emagls_field_stream* f) {
+    return guarded_call([&] {
+        if (!f) throw Error(EMAGLS_ERR_ARG, "null field stream");
+        std::lock_guard<std::mutex> lk(f->mu);
+        DeviceGuard dg(f->device);
+        f->ensure_device();
+        HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
+        f->zero_state(nullptr);
+        HIP_CHECK(hipStreamSynchronize(nullptr));
+    });
+}
+
+int emagls_field_stream_info(const emagls_field_stream* f, int64_t* block, int64_t* partitions, int64_t* state_bytes, int64_t* response_bytes,
+                             int* launches_per_block) {
+    return guarded_call([&] {
+        if (!f) throw Error(EMAGLS_ERR_ARG, "null field stream");
+        if (block) *block = f->d.B;
+        if (partitions) *partitions = f->d.P;
+        if (state_bytes) *state_bytes = (int64_t)f->state_bytes();
+        if (response_bytes) *response_bytes = (int64_t)f->response_bytes();
+        if (launches_per_block) *launches_per_block = kFieldStreamLaunches;   // the sources' forward transform; the products with the inverse
+    });
+}
+
+int emagls_field_stream_destroy(emagls_field_stream* f) {
+    return guarded_call([&] {
+        if (!f) return;
+        {
+            std::lock_guard<std::mutex> lk(f->mu);
+            if (f->ready) {
+                DeviceGuard dg(f->device);
+                (void)hipDeviceSynchronize();
+                f->release();
+            }
+        }
+        delete f;
+    });
+}
+
+}  // extern "C"

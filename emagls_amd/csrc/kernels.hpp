@@ -268,6 +268,8 @@ struct DecodeStreamState {
 bool decode_stream_block_ok(int64_t B);   // a power of two from 64 to 2048
 // Wf from the real filter planes wpl [S][2][Cp][len] (device)
 void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B, int P, int64_t S, cplx* Wf, hipStream_t st);
+// the same kernel on Z sets of Cp real planes of len taps: Wf [Z][P][Cp][B + 1] from wpl [Z][Cp][len] (device)
+void launch_partition_spectra(const double* wpl, int Cp, int64_t len, int B, int P, int64_t Z, cplx* Wf, hipStream_t st);
 // one block: x + c ldx = channel c of the (rotated) block, B samples (cplx only when planes2); set: device, this block's set index
 // (null: the previous block's; not looked at when S == 1); standing: the set the host KNOWS this block and the two before it to be
 // on (their window then runs the plain kernel on that set), -1 when it does not know; out[i], out[ldo + i] = the two ears.
@@ -275,6 +277,21 @@ void launch_decode_stream_filters(const double* wpl, int Cp, int64_t len, int B,
 // index at set + l lset, and writes its ears at out + l lso
 void launch_decode_stream_block(const DecodeStreamState& s, const void* x, bool x_cplx, int64_t ldx, const int* set, int standing, double* out,
                                 int64_t ldo, hipStream_t st, int64_t lsx = 0, int lset = 0, int64_t lso = 0);
+
+// ---- field_stream.hip: source signals through room responses, a block at a time
+struct FieldStreamState {
+    int nsrc = 0;           // sources
+    int planes = 0;         // real output planes: nch, or 2 nch for a complex response (plane 2c = re, 2c + 1 = im of channel c)
+    bool out_c = false;     // the output is interleaved complex: a pair of planes is one column
+    int B = 0, P = 0;       // block size, partitions
+    cplx* Rf = nullptr;     // [nsrc][P][planes][B + 1] partition spectra of the responses
+    cplx* ring = nullptr;   // [nsrc][P][B + 1] the spectra of the last P windows [previous block, block] of every source
+    double* hist = nullptr; // [nsrc][B] the previous block
+    int* pos = nullptr;     // the ring slot of the block pushed last
+};
+// one block: src + q lds = source q's B samples; out + c ldo = channel c's B samples (doubles, or cplx when s.out_c).  Two launches
+void launch_field_stream_block(const FieldStreamState& s, const double* src, int64_t lds, void* out, int64_t ldo, hipStream_t st);
+constexpr int kFieldStreamLaunches = 2;
 
 // ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables, resample.hip's taps and the decode family's work buffers
 void decode_family_cache_clear();

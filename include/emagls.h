@@ -299,7 +299,8 @@ int emagls_binaural_decode_render_fs_device(const void* d_in, int in_is_complex,
  * output depends only on samples already pushed).  With x the concatenation of all pushed blocks and yaw / pitch / roll the
  * concatenation of their per-sample angles, the concatenated outputs equal, to rounding,
  * emagls_binaural_decode_render_ypr(x, ..., compensate_delay = 0, yaw, pitch, roll, no signal): the per-sample rotation of the
- * signal, then sum_c fftfilt(w_c, x_c).  No delay cut (the caller offsets its read), no resampling, no source signal.
+ * signal, then sum_c fftfilt(w_c, x_c).  No delay cut (the caller offsets its read), no resampling; a dry source signal goes
+ * through its room response in a field stream (emagls_field_stream_*, below), whose output a push here takes as it lies.
  * For complex signals or filters the output is the real part (dependencies/binauralDecode.m:59-64); the stream does NOT report
  * the discarded imaginary sum.
  * Uniformly partitioned overlap-save: block = B samples, a power of two from 64 to 2048 (anything else
@@ -443,6 +444,51 @@ int emagls_decode_stream_create_encoded(int64_t nmics, const void* enc, int enc_
 int emagls_decode_group_create_encoded(int64_t nmics, const void* enc, int enc_is_complex, int64_t nch, int64_t n_sets, const void* wL,
                                        const void* wR, int filters_are_complex, int64_t len, int layout, int basis, int64_t block,
                                        int64_t n_listeners, emagls_decode_group** g);
+
+/* ---- the field stream: source signals through array room responses, a block at a time ----
+ * The auralisation use of the toolbox (testEMagLs.m:66-70, testEMagLsFromAtfs.m:67: fftfilt(srir.rir, sig)) for a head that moves: the
+ * rotation sits between the room response and the decoding filters, so the source has to meet the room BEFORE the decode stream.
+ * A field stream is created from nsrc room responses rir_q [nr x nch] (q = 0 .. nsrc - 1, one after the other, column-major like
+ * every array here; real, or interleaved complex for a complex-SH response) and a block size, and is then fed consecutive blocks
+ * of the nsrc REAL source signals, src [nsamp x nsrc] with nsamp = k * block; every push returns the field block [nsamp x nch].
+ * DEFINING PROPERTY: with s_q the concatenation of everything pushed for source q, the concatenated outputs equal, to rounding,
+ *     x(:, c) = sum_q fftfilt(rir_q(:, c), s_q);
+ * nothing is held back, and the output depends only on samples already pushed.  A complex response gives interleaved complex
+ * output: its real taps and its imaginary taps each convolved with the real source.  Fed to a decode stream or a listener group
+ * (created with in_is_complex in the complex case; responses in the microphone domain feed an encoded one) the chain is
+ * source -> room -> rotation -> filters.
+ * Uniformly partitioned overlap-save with the state on the device: P = ceil(nr / block) partitions, their spectra written once
+ * (response_bytes = nsrc P planes (block + 1) 16, planes = nch, or 2 nch for a complex response), a ring of the last P INPUT
+ * spectra per source, the previous block and the ring position (state_bytes).  Two kernel launches per block, no hipFFT, no atomics;
+ * the order of every sum is fixed (field_stream.hip), so equal pushes on fresh objects give equal bits, how blocks are grouped into
+ * pushes does not change a bit, and pushes of one size differ only in the caller's pointers.
+ * Limits, all checked before the device is touched: block a power of two from 64 to 2048; nsrc <= 16; nch <= 256; nr <= 1048576;
+ * response_bytes <= 4 GiB -- beyond any of them EMAGLS_ERR_UNSUPPORTED; a count below 1, a null pointer, or nsamp that is not a
+ * multiple of block: EMAGLS_ERR_ARG.  The object is bound to the device that is current at creation (without a device it still
+ * exists, so that argument errors can be reported and info read, and its first push fails with EMAGLS_ERR_HIP).  It owns its
+ * buffers: emagls_cache_clear() leaves it alone.  One push at a time per object. */
+typedef struct emagls_field_stream emagls_field_stream;
+int emagls_field_stream_create(int64_t nsrc, int64_t nch, const void* rir, int rir_is_complex, int64_t nr, int64_t block,
+                               emagls_field_stream** f);
+
+/* src [nsamp x nsrc] host array; out [nsamp x nch], interleaved complex for a complex response.  k = nsamp / block blocks are run in
+ * order inside the call; synchronised on return. */
+int emagls_field_stream_push(emagls_field_stream* f, const double* src, int64_t nsamp, void* out);
+
+/* The same on device arrays: enqueued on `stream` (hipStream_t, NULL = default) and NOT synchronised; no allocation, no copy of
+ * state.  d_out is [nsamp x nch] with the leading dimension nsamp: the d_in of emagls_decode_stream_push_device and
+ * emagls_decode_group_push_device as it stands. */
+int emagls_field_stream_push_device(emagls_field_stream* f, const double* d_src, int64_t nsamp, void* d_out, void* stream);
+
+/* Zero history: what follows equals a fresh object bit for bit.  Waits for the pushes in flight. */
+int emagls_field_stream_reset(emagls_field_stream* f);
+
+/* block, partitions = ceil(nr / block), state_bytes (ring, previous blocks and position), response_bytes (the partition spectra,
+ * written once) and the kernel launches per block (each output optional). */
+int emagls_field_stream_info(const emagls_field_stream* f, int64_t* block, int64_t* partitions, int64_t* state_bytes,
+                             int64_t* response_bytes, int* launches_per_block);
+
+int emagls_field_stream_destroy(emagls_field_stream* f);
 
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's

@@ -5,7 +5,7 @@ classdef binauralDecodeStream < handle
 %   s.reset()    zero history        delete(s)    releases the device memory
 % Concatenating the pushed blocks into x and the angles per sample, the concatenated outputs equal
 % binauralDecode(x, fs, wL, wR, fs, false, [], [], yaw, shDefinition, rotationDomain, pitch, roll) to rounding: no delay cut, no
-% resampling, no source signal.  blockSize: a power of two from 64 to 2048.  Each angle: [] (0), a scalar (constant over the push)
+% resampling; a dry source signal goes through a sourceFieldStream first.  blockSize: a power of two from 64 to 2048.  Each angle: [] (0), a scalar (constant over the push)
 % or one value per sample.  For complex signals or filters the output is the real part; the discarded sum is not reported.
 % A bank of filter sets (DESIGN.md section 9.4): filters [len x numChannels x numSets] make a stream of numSets sets (s.numSets), and
 % setIndex chooses the set per block, ONE-based as MATLAB counts: [] (every block keeps the set of the block before it; set 1 on a

@@ -65,10 +65,11 @@ template <typename H> struct HandleTable {
     struct Entry { H* h; mwSize cols; bool in_complex; mwSize listeners; };   // with what a push checks its block against
     const char* what;
     std::vector<Entry> entries;
+    const char* family = "decode";   // "invalid <family> <what> handle"
     Entry& of(const mxArray* a) {
         const double v = (a && mxIsDouble(a) && mxGetNumberOfElements(a) == 1) ? mxGetScalar(a) : 0.0;
         const size_t i = (v >= 1 && v <= (double)entries.size() && v == std::floor(v)) ? (size_t)v : 0;
-        if (!i || !entries[i - 1].h) mexErrMsgIdAndTxt("eMagLS:arg", "invalid decode %s handle", what);
+        if (!i || !entries[i - 1].h) mexErrMsgIdAndTxt("eMagLS:arg", "invalid %s %s handle", family, what);
         return entries[i - 1];
     }
     mxArray* add(const Entry& e) {   // into the first free slot
@@ -88,6 +89,9 @@ template <typename H> struct HandleTable {
 };
 HandleTable<emagls_decode_stream> g_streams{"stream"};
 HandleTable<emagls_decode_group> g_groups{"group"};
+// field streams (mex/sourceFieldStream.m): an entry's cols are the sources of a pushed block, in_complex says that the OUTPUT is
+// complex (a complex response), and listeners holds the output's channel count
+HandleTable<emagls_field_stream> g_fields{"stream", {}, "field"};
 // an array of one listener's worth of values but the wrong orientation would be read as another listener's: the last dimension
 // must be the listeners
 void per_listener(const mxArray* a, const char* what, mwSize listeners) {
@@ -156,6 +160,7 @@ std::vector<int32_t> zero_based(const mxArray* a) {
 void at_exit() {
     for (auto& e : g_streams.entries) { if (e.h) emagls_decode_stream_destroy(e.h); e.h = nullptr; }
     for (auto& e : g_groups.entries) { if (e.h) emagls_decode_group_destroy(e.h); e.h = nullptr; }
+    for (auto& e : g_fields.entries) { if (e.h) emagls_field_stream_destroy(e.h); e.h = nullptr; }
     emagls_cache_clear();
 }
 
@@ -181,6 +186,10 @@ void at_exit() {
 //                                     along the last dimension: out [n x 2 x L]; each angle [], [1 x L] or [n x L]; setIndex ONE-based,
 //                                     [], [1 x L] or [nBlocks x L]
 // emagls_mex('group_reset', h[, listener])   ONE-based; without it all listeners      emagls_mex('group_destroy', h)
+// h = emagls_mex('field_create', rirs, blockSize)   a field stream (mex/sourceFieldStream.m): rirs [nr x nch], or [nr x nch x numSources],
+//                                     real or complex: dry sources through room responses, a block at a time
+// out = emagls_mex('field_push', h, src)   src [k*blockSize x numSources] real; out [k*blockSize x nch], complex for a complex response
+// emagls_mex('field_reset', h)       emagls_mex('field_destroy', h)
 // emagls_mex('resample', x, p, q)   MATLAB's resample(x, p, q) (N = 10, bta = 5): a row vector along its length, else per column
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
 // emagls_mex('rotate3', in, yawRad, pitchRad, rollRad[, shDefinition])   three-axis rotation of an SH signal (orders 0-15)
@@ -277,6 +286,41 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         auto& e = g_streams.of(prhs[1]);
         const int rc = c == "stream_reset" ? emagls_decode_stream_reset(e.h) : emagls_decode_stream_destroy(e.h);
         if (c == "stream_destroy") e.h = nullptr;
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "field_create") {
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "field_create needs (rirs, blockSize)");
+        const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
+        const mwSize* dims = mxGetDimensions(prhs[1]);
+        if (!mxIsDouble(prhs[1]) || nd > 3)
+            mexErrMsgIdAndTxt("eMagLS:arg", "rirs must be a double [nr x numChannels] or [nr x numChannels x numSources] array");
+        const mwSize nr = dims[0], ch = nd >= 2 ? dims[1] : 1, nsrc = nd == 3 ? dims[2] : 1;
+        const double bs = mxGetScalar(prhs[2]);
+        if (!(bs == std::floor(bs)) || std::fabs(bs) > 1e9) mexErrMsgIdAndTxt("eMagLS:arg", "blockSize must be an integer");
+        const bool rc_ = mxIsComplex(prhs[1]);
+        emagls_field_stream* f = nullptr;
+        const int rc = emagls_field_stream_create((int64_t)nsrc, (int64_t)ch, in_ptr(prhs[1]), rc_, (int64_t)nr, (int64_t)bs, &f);
+        if (rc) fail(rc);
+        plhs[0] = g_fields.add({f, nsrc, rc_, ch});
+        return;
+    }
+    if (c == "field_push") {
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "field_push needs (handle, src)");
+        const auto& e = g_fields.of(prhs[1]);
+        if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]) || mxGetNumberOfDimensions(prhs[2]) > 2 || mxGetN(prhs[2]) != e.cols)
+            mexErrMsgIdAndTxt("eMagLS:arg", "src must be a real double array with the responses' source count (%d) of columns", (int)e.cols);
+        const mwSize n = mxGetM(prhs[2]);
+        plhs[0] = mxCreateDoubleMatrix(n, e.listeners, e.in_complex ? mxCOMPLEX : mxREAL);
+        const int rc = emagls_field_stream_push(e.h, mxGetDoubles(prhs[2]), (int64_t)n, out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "field_reset" || c == "field_destroy") {
+        if (nrhs < 2) mexErrMsgIdAndTxt("eMagLS:arg", "%s needs (handle)", cmd);
+        auto& e = g_fields.of(prhs[1]);
+        const int rc = c == "field_reset" ? emagls_field_stream_reset(e.h) : emagls_field_stream_destroy(e.h);
+        if (c == "field_destroy") e.h = nullptr;
         if (rc) fail(rc);
         return;
     }

@@ -12,6 +12,7 @@ Gates (exit status 1 when one fails): median (a) < median (b), and median (a) < 
                                          [--dry-run] [--out profiles/r10_decode_stream.md]
                                          [--bank [--sets 3]] [--group [--listeners 1 8 64 256] [--sets 1]]
                                          [--encoded [--enc-shapes 32,25,512,64 ...] [--listeners 1 8 64]]
+                                         [--field [--field-shapes 1,25,48000,64,1 ...]]
 --dry-run prints the shapes and the bytes a push moves, computed from the shapes, without a device.
 
 --bank times the bank of filter sets (emagls_decode_stream_create_bank / _push_sets_device) instead, without
@@ -51,6 +52,18 @@ trajectories, alternating in one process on one HIP stream:
 
 Median and spread = p90 - p10 of the run averages.  Expected, reported and not gated: median(matmul) - median(encoded) >
 spread(matmul) + spread(encoded) at the launch-bound shapes.
+
+--field times the field stream (emagls_field_stream_push_device) per shape (nsrc, nch, nr, B, listeners)
+(--field-shapes), alternating in one process on one HIP stream:
+
+  field    the field stream alone: its two launches per block
+  chain    the field stream into a decode stream (listeners == 1) or a listener group of 512-tap filters with a three-axis
+           trajectory per listener, the field block handed over on the device
+
+Median and spread = p90 - p10 of the run averages.  The one condition: median(chain) < B / 48000 s, the block's own duration; a
+shape that misses it is reported as such and the exit status is 1.  Also reported: the share of the block's duration the chain
+takes, and the bytes of the response spectra Rf the product kernel streams per block over the time of `field` (both launches: a
+lower bound of that kernel's own rate), as a share of the HBM peak.
 """
 import argparse
 import ctypes as C
@@ -433,6 +446,119 @@ def encoded_markdown(rows, device):
     return "\n".join(lines) + "\n"
 
 
+FIELD_SHAPES = ["1,25,48000,64,1", "1,25,96000,256,1", "4,64,48000,128,1", "1,25,48000,64,8"]
+FIELD_DECODE_TAPS = 512
+
+
+def field_bytes(nsrc, nch, nr, B):
+    """Bytes one block of the field stream moves, from the shapes (real response): the response spectra once, the ring read by
+    every pair of planes (stored once: `ring_once`) and one slot written, the blocks and the previous blocks, the output."""
+    P, Pf = -(-nr // B), B + 1
+    rf = 16 * nsrc * P * nch * Pf
+    ring = 16 * nsrc * P * Pf
+    return {"response": rf, "ring_once": ring, "ring_requested": ring * ((nch + 1) // 2), "slot": 16 * nsrc * Pf, "signal": 8 * nsrc * B * 3,
+            "output": 8 * nch * B, "compulsory": rf + ring + 16 * nsrc * Pf + 8 * nsrc * B * 3 + 8 * nch * B}
+
+
+def run_field_shape(lib, L, torch, nsrc, nch, nr, B, nl, blocks, warm, run):
+    """The sides of --field for one shape."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(nsrc + nch + nr + B + nl)
+    rnd = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)   # noqa: E731
+    rir = rnd(nsrc, nch, nr) / nr ** 0.5                    # [nsrc][nch][nr] row-major == nsrc column-major [nr x nch] arrays
+    ln = FIELD_DECODE_TAPS
+    wL, wR = rnd(nch, ln), rnd(nch, ln)
+    d_src = rnd(nsrc, B).to(dev)
+    ang = [(0.3 + 0.01 * torch.cumsum(rnd(nl, B), 1)).to(dev) for _ in range(3)]
+    d_field = [torch.zeros((nch, B), dtype=torch.float64, device=dev) for _ in range(2)]
+    d_out = torch.zeros((nl, 2, B), dtype=torch.float64, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    sh, real = L.LAYOUT["sh"], L.BASIS["real"]
+    hf = [C.c_void_p(), C.c_void_p()]                       # a field stream per side: a side's history is its own
+    for h in hf:
+        L.check(lib.emagls_field_stream_create(nsrc, nch, p(rir), 0, nr, B, C.byref(h)))
+    hd = C.c_void_p()
+    if nl == 1:
+        L.check(lib.emagls_decode_stream_create(nch, p(wL), p(wR), 0, ln, 0, sh, real, B, C.byref(hd)))
+    else:
+        L.check(lib.emagls_decode_group_create(nch, 1, p(wL), p(wR), 0, ln, 0, sh, real, B, nl, C.byref(hd)))
+    st = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(st.cuda_stream)
+    na = nl * B
+    aa = [p(a) for a in ang]
+
+    def side_field():
+        L.check(lib.emagls_field_stream_push_device(hf[0], p(d_src), B, p(d_field[0]), sp))
+
+    def side_chain():
+        L.check(lib.emagls_field_stream_push_device(hf[1], p(d_src), B, p(d_field[1]), sp))
+        if nl == 1:
+            L.check(lib.emagls_decode_stream_push_device(hd, p(d_field[1]), B, aa[0], na, aa[1], na, aa[2], na, p(d_out), sp))
+        else:
+            L.check(lib.emagls_decode_group_push_device(hd, p(d_field[1]), B, None, 0, aa[0], na, aa[1], na, aa[2], na, p(d_out), sp))
+
+    sides = [("field", side_field), ("chain", side_chain)]
+    times = {k: [] for k, _ in sides}
+    with torch.cuda.stream(st):
+        for _, f in sides:
+            for _ in range(warm):
+                f()
+        st.synchronize()
+        for _ in range(max(1, blocks // run)):
+            for k, f in sides:                       # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(run):
+                    f()
+                e1.record(st)
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / run)   # us per block
+    st.synchronize()
+    same = bool(torch.equal(d_field[0], d_field[1]))        # (both field streams have seen the same pushes)
+    for h in hf:
+        L.check(lib.emagls_field_stream_destroy(h))
+    L.check((lib.emagls_decode_stream_destroy if nl == 1 else lib.emagls_decode_group_destroy)(hd))
+    res = {"shape": [nsrc, nch, nr, B], "listeners": nl, "partitions": -(-nr // B), "block_us": round(B / FS * 1e6, 1), "bits_equal": same,
+           "bytes": field_bytes(nsrc, nch, nr, B)}
+    for k, v in times.items():
+        res[k] = {"median_us": round(float(np.median(v)), 2), "min_us": round(float(np.min(v)), 2), "max_us": round(float(np.max(v)), 2),
+                  "spread_us": round(_spread(v), 2)}
+    res["chain_share_of_block"] = round(res["chain"]["median_us"] / res["block_us"], 4)
+    res["response_gbps"] = round(res["bytes"]["response"] / res["field"]["median_us"] / 1e3, 1)
+    res["response_share_of_hbm_peak"] = round(res["response_gbps"] / HBM_PEAK_GBPS, 4)
+    res["gate_realtime"] = res["chain"]["median_us"] < res["block_us"]
+    return res
+
+
+def field_markdown(rows, device):
+    lines = ["`python tools/decode_stream_timing.py --field` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
+             "field: `emagls_field_stream_push_device` alone (two launches); chain: the same into a decode stream, or a listener group of L",
+             "listeners, of %d-tap filters with a three-axis trajectory per listener.  share: chain over the block's duration at 48 kHz" % FIELD_DECODE_TAPS,
+             "(the condition: below 100 %).  Rf GB/s: the bytes of the response spectra the product kernel streams per block over the time",
+             "of `field` (both launches, so a lower bound of that kernel's rate), against an HBM peak of %.0f GB/s." % HBM_PEAK_GBPS, "",
+             "| (nsrc, nch, nr, B) | L | P | block us | field | spread | chain | spread | share | real time | Rf MB | Rf GB/s | of HBM peak |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append("| %s | %d | %d | %.0f | %.1f | %.2f | %.1f | %.2f | %.1f %% | %s | %.1f | %.0f | %.1f %% |" % (
+            tuple(r["shape"]), r["listeners"], r["partitions"], r["block_us"], r["field"]["median_us"], r["field"]["spread_us"],
+            r["chain"]["median_us"], r["chain"]["spread_us"], 100 * r["chain_share_of_block"], "ok" if r["gate_realtime"] else "MISS",
+            r["bytes"]["response"] / 1e6, r["response_gbps"], 100 * r["response_share_of_hbm_peak"]))
+    return "\n".join(lines) + "\n"
+
+
+def parse_field_shapes(items):
+    out = []
+    for it in items:
+        nsrc, nch, nr, b, nl = (int(v) for v in it.split(","))
+        parse_shapes(["%d,%d,%d" % (nch, nr, b)])
+        if not (1 <= nsrc <= 16 and nch <= 256 and nr <= 1048576 and 1 <= nl <= 4096):
+            raise SystemExit("--field-shapes: 1 <= nsrc <= 16, nch <= 256, nr <= 1048576, listeners from 1 to 4096")
+        if int(round(nch ** 0.5)) ** 2 != nch or nch > 256:
+            raise SystemExit("--field-shapes: the chain's rotation needs (N+1)^2 channels, N <= 15")
+        out.append((nsrc, nch, nr, b, nl))
+    return out
+
+
 def bank_markdown(rows, device):
     lines = ["`python tools/decode_stream_timing.py --bank` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
              "plain: the plain stream; const: a bank stream with a constant index from device memory; keep: a bank stream pushed without",
@@ -477,6 +603,8 @@ def main():
     ap.add_argument("--listeners", type=int, nargs="*", default=None, help="--group: numbers of listeners (default 1 8 64 256); --encoded: default 1")
     ap.add_argument("--encoded", action="store_true", help="time the encoder inside the stream against matmul + plain stream (see above)")
     ap.add_argument("--enc-shapes", nargs="*", default=["32,25,512,64", "32,25,512,256", "64,64,2048,128"], help="--encoded: M,C,len,B ...")
+    ap.add_argument("--field", action="store_true", help="time the field stream alone and its chain into a decode stream (see above)")
+    ap.add_argument("--field-shapes", nargs="*", default=FIELD_SHAPES, help="--field: nsrc,nch,nr,B,listeners ...")
     a = ap.parse_args()
     if a.sets is None:
         a.sets = 1 if a.group else 3
@@ -484,6 +612,28 @@ def main():
         a.listeners = [1] if a.encoded else [1, 8, 64, 256]
     if a.blocks < a.run or a.run < 1 or a.warm < 0:
         raise SystemExit("--blocks must be at least --run, --run at least 1")
+    if a.field:
+        fshapes = parse_field_shapes(a.field_shapes)
+        if a.dry_run:
+            for nsrc, nch, nr, b, nl in fshapes:
+                print(json.dumps({"shape": [nsrc, nch, nr, b], "listeners": nl, "partitions": -(-nr // b), "block_us": round(b / FS * 1e6, 1),
+                                  "bytes": field_bytes(nsrc, nch, nr, b)}))
+            return 0
+        import torch
+        from emagls_amd import _lib as L
+        lib = L.load()
+        rows, ok = [], True
+        for fs_ in fshapes:
+            res = run_field_shape(lib, L, torch, *fs_, a.blocks, a.warm, a.run)
+            ok = ok and res["gate_realtime"] and res["bits_equal"]
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(field_markdown(rows, torch.cuda.get_device_name(0)))
+        print("condition:", "met" if ok else "MISSED")
+        return 0 if ok else 1
     shapes = parse_shapes(a.shapes)
     rots = {"both": (False, True), "none": (False,), "ypr": (True,)}[a.rotation]
     if a.dry_run:
