@@ -194,3 +194,162 @@ def eval_points(grids, ndirs=64, nrandom=300, seed=20):
     special = np.array([1.0, -1.0, inner, -inner, 0.0, 0.5, -0.5, np.nextafter(1.0, 2.0)])
     rnd = np.random.default_rng(seed).uniform(-1.0, 1.0, nrandom)
     return np.concatenate([special, cosines(azi, zen, grids["mic_azi"], grids["mic_zen"]).ravel(), rnd])
+
+
+# ---- one bin step of the resident sweeps (sweep_synth.hip, sweep_reg.hip) in longdouble, with an a-priori bound for the FP64 kernels
+#
+# The chain of a design runs in the microphone domain, rows in the order of `smap` (npr antipodal pairs in rows 2u, 2u + 1, then nsg
+# single microphones).  With the totals u(k-1) [ear][row] the chain stored, Mt(k-1) = Pm^T M(k-1) Pm, |H(k)| and the operand
+# g_k[d][row] one bin is
+#     w' = u(k-1) conj(Mt(k-1)),    p_d = sum_j w'_j g_k[d][j],    t_d = |H_d| p_d / |p_d|,    u(k)_j = sum_d t_d conj(g_k[d][j])
+# (the first swept bin takes w' = Winit as it stands; the Nyquist bin keeps the real part of t; p_d = 0 gives t_d = |H_d|:
+# unit_phase of persist_common.hpp).  A unit's operand is E + O (first row) and E - O (second row of a pair) with E, O the even and odd
+# part of the series at the FIRST microphone's cosine: the second row is g(-x) at that same x.
+#
+# bound_step, per element of u(k), on |kernel - longdouble step| (moduli of complex numbers).  eps = 2^-52; gamma_n = n eps / (1 - n eps).
+# A sum of n complex products, in any order, with or without fused operations, has 2 n real products per component: each component is
+# within gamma^u_{2n} = gamma_n (u = eps / 2) times the sum of the moduli, the modulus within sqrt(2) gamma_n <= gamma_{2n+2}.
+#   operand   dg = bound_g of the bin: the series is evaluated at the kernel's own arguments (the GPU test reads 2 cos(direction,
+#             microphone) as the sweeps form it, synth_x2, and holds it to `cosines` within the tolerance of the operand test), so what
+#             is left is the evaluation.  bound_g covers E and O together (its recurrence part is per term, its factor 8 the roundings
+#             of E +- O), so |dE| + |dO| <= dg as well.
+#   w'        dw'_j = gamma_{2M+2} sum_i |u_i| |Mt_ij|   (M products; zero for the first swept bin).
+#   p_d       the register form multiplies E and O apart, with the weights w'_A + w'_B and w'_A - w'_B of a pair (both w' for a single
+#             microphone): 2 units products, each weight one rounding more, and the moduli that enter are
+#                 A_d = sum_units (|w'_A| + |w'_B|) (|E_d| + |O_d|)   >=   sum_j |w'_j| |g_dj|   (what the slab form sums),
+#             so  dp_d = gamma_{4 units + 2} A_d + sum_units (|w'_A| + |w'_B|) dg + sum_units (dw'_A + dw'_B) (|E_d| + |O_d|).
+#             (gamma_{2M+2} sum_j |w'_j| |g_dj| would hold for the slab form alone: with E and O apart a pair whose g(x) is small against
+#             E and O has a larger rounding error than that, and an array without pairs has 2 M products.)
+#   phase     two unit vectors whose directions p, p + dp differ by r = dp / |p| < 1 are 2 sin(asin(r) / 2) apart at most (= r to first
+#             order), any two by 2:  dphi_d = that, and dt_d = |H_d| (dphi_d + 4 eps): |p|^2 two roundings (one after the square root),
+#             the reciprocal square root 2 u (fast_rsqrt), the products with |H| and with p one each: 5 u < 4 eps.  A direction with a
+#             tiny |p_d| widens the bound through its own dphi_d; none is left out.
+#   sum       du_j = gamma_{D+c} sum_d |H_d| m_dj + sum_d dt_d m_dj + sum_d |H_d| dg,   m_dj = |E_d| + |O_d| of row j's unit (>= |g_dj|;
+#             the register form sums t conj(E) and t conj(O) and adds or subtracts them at the end), c = ceil((sqrt(2) - 1) D) + 4:
+#             D products and one more addition per component (gamma_{D+1}), sqrt(2) for the modulus.
+# Second-order terms (a gamma times a gamma) are left to the margins above (eps where u would do for the roundings of single values).
+
+def gamma(n):
+    return n * EPS64 / (1.0 - n * EPS64)
+
+
+def f64(a):
+    return np.asarray(a).astype(np.float64)
+
+
+def unit_rows(npr, nsg):
+    """(first row, second row or -1) of every unit in the chain's row order"""
+    a = np.array([2 * u for u in range(npr)] + [2 * npr + s for s in range(nsg)], dtype=int)
+    b = np.array([2 * u + 1 for u in range(npr)] + [-1] * nsg, dtype=int)
+    return a, b
+
+
+def step_operand(bsc, x, smap):
+    """The operand of the bins `bsc` holds rows of, in the chain's row order: g [k][D][M] (clongdouble), m [k][D][M] = |E| + |O| of the
+    row's unit, dg [k][D][M] the operand term of bound_step, and (npr, nsg).  The series is the kernel's own (its FP64 rows taken as
+    exact, chebyshev_sum); x [D][units]: the cosine between direction and FIRST microphone of every unit (smap[unit_rows(...)[0]])."""
+    smap = np.asarray(smap)
+    npr, nsg = int(smap[32]), int(smap[33])
+    M = 2 * npr + nsg
+    ra, rb = unit_rows(npr, nsg)
+    x = np.asarray(x, dtype=np.float64)
+    D, U = x.shape
+    assert U == ra.size
+    bsc = np.atleast_2d(bsc)
+    gp = chebyshev_sum(bsc, x.ravel()).reshape(-1, D, U)
+    gm = chebyshev_sum(bsc, -x.ravel()).reshape(-1, D, U)
+    mu = (np.abs(gp + gm) / 2 + np.abs(gp - gm) / 2).astype(np.float64)
+    g = np.zeros((bsc.shape[0], D, M), dtype=CLD)
+    m = np.zeros((bsc.shape[0], D, M))
+    g[:, :, ra] = gp
+    m[:, :, ra] = mu
+    pr = rb >= 0
+    g[:, :, rb[pr]] = gm[:, :, pr]
+    m[:, :, rb[pr]] = mu[:, :, pr]
+    dg = np.broadcast_to(bound_g(bsc)[:, None, None], m.shape)
+    return g, m, dg, (npr, nsg)
+
+
+def sweep_step(u_prev, Mt_prev, habs_k, g_k, nyquist=False, w_start=None):
+    """One bin in clongdouble: u_prev [2][M], Mt_prev [M][M], habs_k [2][D], g_k [D][M] -> (u_k [2][M], w' [2][M], p [2][D], t [2][D]).
+    w_start: the first swept bin, whose w' is the start value as it stands (u_prev and Mt_prev are not read)."""
+    g = g_k if g_k.dtype == CLD else to_cld(g_k)
+    w = to_cld(w_start) if w_start is not None else to_cld(u_prev) @ np.conj(to_cld(Mt_prev))
+    p = w @ g.T
+    a = np.abs(p)
+    h = np.asarray(habs_k, dtype=np.float64).astype(LD)
+    t = np.zeros(p.shape, dtype=CLD)
+    nz = a > 0
+    t[nz] = h[nz] * p[nz] / a[nz]
+    t[~nz] = h[~nz]
+    if nyquist:
+        t.imag = 0
+    return t @ np.conj(g), w, p, t
+
+
+def bound_step(u_prev, Mt_prev, habs_k, g_k, m_k, dg_k, units, nyquist=False, w_start=None, step=None):
+    """[2][M], float64: the a-priori bound derived above on |FP64 kernel - sweep_step| per element of u_k.  m_k, dg_k [D][M] and units =
+    (npr, nsg) from step_operand; step: the tuple sweep_step returned for the same arguments (computed when omitted)."""
+    if step is None:
+        step = sweep_step(u_prev, Mt_prev, habs_k, g_k, nyquist, w_start)
+    _, w, p, _ = step
+    D, M = m_k.shape
+    ra, rb = unit_rows(*units)
+    nun = ra.size
+    h = np.asarray(habs_k, dtype=np.float64)
+    aw = f64(np.abs(w))
+    dw = np.zeros_like(aw) if w_start is not None else gamma(2 * M + 2) * (np.abs(np.asarray(u_prev)).astype(np.float64) @ np.abs(np.asarray(Mt_prev)).astype(np.float64))
+    pr = rb >= 0
+    ws, dws = aw[:, ra].copy(), dw[:, ra].copy()
+    ws[:, pr] += aw[:, rb[pr]]
+    dws[:, pr] += dw[:, rb[pr]]
+    mu, dgu = m_k[:, ra], dg_k[:, ra]                                           # [D][units]
+    dp = gamma(4 * nun + 2) * (ws @ mu.T) + ws @ dgu.T + dws @ mu.T              # [2][D]
+    ap = f64(np.abs(p))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(ap > 0, dp / ap, np.inf)
+    dphi = np.where(r < 1.0, 2.0 * np.sin(0.5 * np.arcsin(np.minimum(r, 1.0))), 2.0)
+    dt = h * (dphi + 4 * EPS64)
+    c = int(np.ceil((np.sqrt(2.0) - 1.0) * D)) + 4
+    return gamma(D + c) * (h @ m_k) + dt @ m_k + h @ dg_k
+
+
+def step_ratio(u_got, u_ref, bound):
+    """|u_got - u_ref| / bound, element by element (inf where a zero bound is missed)"""
+    err = f64(np.abs(to_cld(u_got) - u_ref))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0))
+
+
+def mt_from(Mk, Pm):
+    """Pm^T M Pm in clongdouble (synth_mt_kernel: M Pm first) and its bound gamma_{2C+2} (|Pm|^T |M Pm| + |Pm|^T |M| |Pm|): two sums of C
+    products of a complex and a real factor each, the first one's error carried through the second.  Mk [C][C], Pm [C][M] real."""
+    C = Mk.shape[0]
+    P = np.asarray(Pm, dtype=np.float64).astype(LD)
+    tmp = to_cld(Mk) @ P
+    aP = np.abs(np.asarray(Pm, dtype=np.float64))
+    gm = gamma(2 * C + 2)
+    return P.T @ tmp, gm * (aP.T @ f64(np.abs(tmp)) + aP.T @ (np.abs(np.asarray(Mk)).astype(np.float64) @ aP))
+
+
+def rows_from_totals(u_k, Pm, Mk):
+    """W(k,:) = (u_k Pm^T) conj(M_k) in clongdouble (synth_rows_kernel) and its bound gamma_{2C+2} |u Pm^T| |M| + gamma_{2M+2} (|u| |Pm|^T) |M|.
+    u_k [2][M], Pm [C][M] real, Mk [C][C]."""
+    C, M = np.asarray(Pm).shape
+    P = np.asarray(Pm, dtype=np.float64).astype(LD)
+    v = to_cld(u_k) @ P.T
+    aM = np.abs(np.asarray(Mk)).astype(np.float64)
+    dv = gamma(2 * M + 2) * (np.abs(np.asarray(u_k)).astype(np.float64) @ np.abs(np.asarray(Pm, dtype=np.float64)).T)
+    return v @ np.conj(to_cld(Mk)), gamma(2 * C + 2) * (f64(np.abs(v)) @ aM) + dv @ aM
+
+
+def jittered_array(n, seed=None):
+    """An array of n microphones without an antipodal pair: a jittered spherical Fibonacci lattice (well conditioned; the arrays of
+    tests/test_gpu_sweep_reg_mfma.py)"""
+    i = np.arange(n) + 0.5
+    zen = np.arccos(1 - 2 * i / n)
+    azi = np.mod(np.pi * (1 + 5 ** 0.5) * i, 2 * np.pi)
+    rng = np.random.default_rng(2000 + n if seed is None else seed)
+    azi = azi + 0.05 * rng.standard_normal(n)
+    zen = np.clip(zen + 0.05 * rng.standard_normal(n), 0.05, np.pi - 0.05)
+    return azi, zen

@@ -109,3 +109,187 @@ def test_gpu_test_inputs_are_well_inside_the_bounds(grids, order):
     # and the coefficient bound against the coefficients' own scale
     bb = R.bound_bsc(beta)
     assert np.all(bb.sum(axis=1) <= 1e-12 * np.abs(beta).astype(np.float64).sum(axis=1))
+
+
+# ---- the longdouble bin step (synth_reference.sweep_step) and its a-priori bound, on host-made inputs of the GPU tests' geometries
+
+def microphone_map(maz, mzn):
+    """smap as synth_pairing (plan_setup.hip) orders the rows: antipodal pairs (unit vectors cancel to 8 eps) first, then the singles"""
+    M = len(maz)
+    u = np.stack([np.sin(mzn) * np.cos(maz), np.sin(mzn) * np.sin(maz), np.cos(mzn)], axis=1)
+    partner = [-1] * M
+    for j in range(M):
+        if partner[j] >= 0:
+            continue
+        for k in range(j + 1, M):
+            if partner[k] < 0 and np.abs(u[j] + u[k]).max() <= 8 * R.EPS64:
+                partner[j], partner[k] = k, j
+                break
+    smap = np.zeros(34, dtype=np.int32)
+    rows = [x for j in range(M) if partner[j] > j for x in (j, partner[j])]
+    singles = [j for j in range(M) if partner[j] < 0]
+    smap[:M] = rows + singles
+    smap[32], smap[33] = len(rows) // 2, len(singles)
+    return smap
+
+
+def ordered_sum(a, axis, order):
+    """sum over `axis` in plain FP64, in a fixed order: forward, reversed, or pairwise (neighbours first)"""
+    a = np.moveaxis(a, axis, 0)
+    if order == "forward":
+        return np.cumsum(a, axis=0)[-1]
+    if order == "reversed":
+        return np.cumsum(a[::-1], axis=0)[-1]
+    while a.shape[0] > 1:
+        if a.shape[0] & 1:
+            a = np.concatenate([a, np.zeros_like(a[:1])], axis=0)
+        a = a[0::2] + a[1::2]
+    return a[0]
+
+
+def fp64_step(u_prev, Mt_prev, habs, g, order, nyquist=False):
+    """the step in complex128, every sum in the given order"""
+    w = ordered_sum(u_prev[:, :, None] * np.conj(Mt_prev)[None, :, :], 1, order)             # [2][M]
+    p = ordered_sum(w[:, None, :] * g[None, :, :], 2, order)                                  # [2][D]
+    a = np.sqrt(p.real * p.real + p.imag * p.imag)
+    t = np.where(a > 0, habs * p / np.where(a > 0, a, 1.0), habs + 0j)
+    if nyquist:
+        t = t.real + 0j
+    return ordered_sum(t[:, :, None] * np.conj(g)[None, :, :], 1, order)                     # [2][M]
+
+
+STEP_GEOMETRIES = {
+    # name: (microphones, directions, radius, simulation order, first swept bin) -- the direction-count edge case of
+    # tests/test_gpu_sweep_step.py (12 microphones without a pair, order-5 radius, f_cut 7.5 kHz, one direction more than a workgroup of
+    # four waves), a seven-microphone slab case, and the em32 at its own radius on the thin grid (order 19, 15 pairs and 2 singles)
+    "12 microphones, 129 directions": (12, 129, R.RADIUS_OF_ORDER[5], 5, 39),
+    "7 microphones, 65 directions": (7, 65, 0.042, 19, 5),
+    "em32, 901 directions": (32, 901, R.RADIUS_OF_ORDER[19], 19, 10),
+}
+
+
+@pytest.fixture(scope="module")
+def step_inputs(grids):
+    """name -> the inputs of every selected swept bin, from an FP64 chain over the swept bins: totals of the previous bin, Mt of the
+    previous bin (the regularised inverse Gram matrix of its operand, as the oracle clips the singular values at 0.01 of the
+    largest), |H|, the longdouble operand with its moduli and operand bound.  Computed once."""
+    from emagls_amd import synth
+    R.require_longdouble()
+    out = {}
+    for name, (M, D, radius, order, kfirst) in STEP_GEOMETRIES.items():
+        if M == 32:
+            sub = slice(0, 2702, 3)
+            azi, zen, maz, mzn = grids["azi"][sub], grids["zen"][sub], grids["mic_azi"], grids["mic_zen"]
+        else:
+            (azi, zen), (maz, mzn) = synth.fibonacci_grid(D), R.jittered_array(M)
+        assert azi.size == D and O.emagls2_simulation_order(R.FS, radius) == order
+        hL, hR = synth.rigid_sphere_hrirs(azi, zen)
+        habs = np.abs(np.stack([np.fft.rfft(hL, 2 * R.TAPS, axis=0), np.fft.rfft(hR, 2 * R.TAPS, axis=0)]))   # [2][P][D]
+        H = np.stack([np.fft.rfft(hL, 2 * R.TAPS, axis=0), np.fft.rfft(hR, 2 * R.TAPS, axis=0)])
+        smap = microphone_map(maz, mzn)
+        assert (int(smap[32]), int(smap[33])) == ((15, 2) if M == 32 else (0, M))
+        bn = -O.sphModalCoeffs(order, R.plan_kr(radius))
+        nord_pad = (order + 2) & ~1
+        bsc = np.zeros((R.NBINS, nord_pad), dtype=np.complex128)     # the kernel's rows: FP64, zero padded
+        bsc[:, :order + 1] = R.legendre_to_chebyshev(R.beta_of_bn(bn, nyquist_last=True)).astype(np.complex128)
+        P = R.NBINS
+        bins = np.array(sorted({k for k in R.selected_bins(P) if k >= kfirst} | {kfirst, P - 1}))
+        # the FP64 chain: operand and Mt of every bin from kfirst - 1 on, the totals from the least-squares bin kfirst - 1
+        ra, rb = R.unit_rows(int(smap[32]), int(smap[33]))
+        xu = R.cosines(azi, zen, maz[smap[ra]], mzn[smap[ra]])     # [D][units]: to the first microphone of every unit
+
+        def g64(k):
+            g = np.zeros((D, M), dtype=np.complex128)
+            cheb = np.polynomial.chebyshev.chebval
+            g[:, ra] = cheb(xu, bsc[k].real) + 1j * cheb(xu, bsc[k].imag)
+            gm = cheb(-xu, bsc[k].real) + 1j * cheb(-xu, bsc[k].imag)
+            g[:, rb[rb >= 0]] = gm[:, rb >= 0]
+            return g
+
+        def mt64(g):
+            U, s, _ = np.linalg.svd(g.T, full_matrices=False)
+            return np.conj((U / (s * np.maximum(s, 0.01 * s[0]))[None, :]) @ U.conj().T)
+
+        gk = g64(kfirst - 1)
+        u = H[:, kfirst - 1, :] @ np.conj(gk)
+        prev, Mt = {}, mt64(gk)
+        for k in range(kfirst, P):
+            prev[k] = (u, Mt)
+            gk = g64(k)
+            u = fp64_step(u, Mt, habs[:, k, :], gk, "forward", nyquist=(k == P - 1))
+            Mt = mt64(gk)
+        g, m, dg, units = R.step_operand(bsc[bins], xu, smap)
+        out[name] = dict(bins=bins, P=P, units=units, D=D, M=M,
+                         steps=[dict(k=int(k), u_prev=prev[k][0], Mt_prev=prev[k][1], habs=habs[:, k, :], g=g[i], m=m[i], dg=dg[i], nyquist=(k == P - 1))
+                                for i, k in enumerate(bins)])
+    return out
+
+
+@pytest.mark.parametrize("name", ["12 microphones, 129 directions", "em32, 901 directions"])
+def test_step_bound_holds_for_fp64_in_three_summation_orders(step_inputs, name):
+    """Validity: the step in plain FP64 NumPy with every sum forward, reversed and pairwise lies within bound_step of the longdouble
+    step, element by element, in every selected swept bin (the first and the Nyquist bin included)."""
+    d = step_inputs[name]
+    worst = {}
+    for s in d["steps"]:
+        ref = R.sweep_step(s["u_prev"], s["Mt_prev"], s["habs"], s["g"], nyquist=s["nyquist"])
+        bound = R.bound_step(s["u_prev"], s["Mt_prev"], s["habs"], s["g"], s["m"], s["dg"], d["units"], nyquist=s["nyquist"], step=ref)
+        assert np.all(np.isfinite(bound)) and np.all(bound > 0)
+        g64 = s["g"].astype(np.complex128)
+        for order in ("forward", "reversed", "pairwise"):
+            ratio = R.step_ratio(fp64_step(s["u_prev"], s["Mt_prev"], s["habs"], g64, order, s["nyquist"]), ref[0], bound)
+            worst[order] = max(worst.get(order, 0.0), float(ratio.max()))
+            assert np.all(ratio <= 1.0), (name, s["k"], order, float(ratio.max()))
+    print(f"{name}: FP64 step / bound_step over {len(d['steps'])} bins, largest: " + ", ".join(f"{o} {v:.4f}" for o, v in worst.items()))
+    assert min(worst.values()) > 0    # (the three orders do differ from the longdouble step)
+
+
+@pytest.mark.parametrize("name", ["12 microphones, 129 directions", "7 microphones, 65 directions"])
+def test_step_bound_is_sharp_enough_to_reject_injected_errors(step_inputs, name):
+    """Sharpness: a u_k in which one direction's t_d is 1e-9 relative off (one ear, a direction in the middle of the grid), a u_k
+    in which one unit's contribution of the last direction entered with the wrong sign, and a u_k whose every t_d is 1e-10 relative too
+    long (a normalisation p / |p| that far off) each miss the bound in at least 90 % of the selected swept bins.  This is a condition on the inputs: a geometry whose conditioning or direction count makes bound_step too wide
+    to see 1e-9 in one of D directions does not belong here (the em32 on 901 directions does not: D gamma_D alone is 2e-10 there)."""
+    d = step_inputs[name]
+    D, M = d["D"], d["M"]
+    dmid, ulast = D // 2, R.unit_rows(*d["units"])[0][-1]
+    hit_t = hit_s = hit_n = 0
+    least_t = least_s = np.inf
+    for s in d["steps"]:
+        u, w, p, t = R.sweep_step(s["u_prev"], s["Mt_prev"], s["habs"], s["g"], nyquist=s["nyquist"])
+        bound = R.bound_step(s["u_prev"], s["Mt_prev"], s["habs"], s["g"], s["m"], s["dg"], d["units"], nyquist=s["nyquist"], step=(u, w, p, t))
+        bad_t = u.copy()
+        bad_t[0] += R.LD(1e-9) * t[0, dmid] * np.conj(s["g"][dmid])
+        bad_s = u.copy()
+        bad_s[:, ulast] -= 2 * t[:, D - 1] * np.conj(s["g"][D - 1, ulast])
+        rt, rs = R.step_ratio(bad_t, u, bound).max(), R.step_ratio(bad_s, u, bound).max()
+        hit_t += rt > 1.0
+        hit_s += rs > 1.0
+        hit_n += R.step_ratio(u * (1 + R.LD(1e-10)), u, bound).max() > 1.0
+        least_t, least_s = min(least_t, rt), min(least_s, rs)
+        assert R.step_ratio(u, u, bound).max() == 0.0
+    n = len(d["steps"])
+    print(f"{name}: t_d off by 1e-9 rejected in {hit_t} of {n} bins (smallest error / bound {least_t:.2f}); wrong sign of the last direction "
+          f"rejected in {hit_s} of {n} (smallest {least_s:.3g}); every t_d 1e-10 too long rejected in {hit_n} of {n}")
+    assert n >= 20 and hit_t >= 0.9 * n and hit_s >= 0.9 * n and hit_n >= 0.9 * n
+
+
+def test_rows_and_mt_references_against_fp64():
+    """mt_from and rows_from_totals: FP64 NumPy products lie within their bounds of the longdouble ones, and a single flipped sign in Pm
+    does not."""
+    R.require_longdouble()
+    rng = np.random.default_rng(5)
+    C, M = 25, 32
+    Mk = rng.standard_normal((C, C)) + 1j * rng.standard_normal((C, C))
+    Pm = rng.standard_normal((C, M))
+    u = rng.standard_normal((2, M)) + 1j * rng.standard_normal((2, M))
+    mt, bmt = R.mt_from(Mk, Pm)
+    w, bw = R.rows_from_totals(u, Pm, Mk)
+    assert mt.shape == (M, M) and w.shape == (2, C)
+    r_mt = R.step_ratio(Pm.T @ (Mk @ Pm), mt, bmt).max()
+    r_w = R.step_ratio((u @ Pm.T) @ np.conj(Mk), w, bw).max()
+    print(f"FP64 / bound: Pm^T M Pm {r_mt:.4f}, rows from totals {r_w:.4f}")
+    assert 0 < r_mt <= 1.0 and 0 < r_w <= 1.0
+    Pb = Pm.copy()
+    Pb[3, 7] = -Pb[3, 7]
+    assert R.step_ratio(Pb.T @ (Mk @ Pb), mt, bmt).max() > 1e6 and R.step_ratio((u @ Pb.T) @ np.conj(Mk), w, bw).max() > 1e6
