@@ -53,33 +53,24 @@ void batch_sweep_stage(emagls_batch& b) {
     launch_sweep_half_finalize(h, q0.P - 1, b.stream);
 }
 
-// lane mode: the pipeline of plan `first` is enqueued once on `st` with grid.z = `count` designs (plans first .. first + count - 1)
-// part 0: stages before the sweep, part 2: stages after it
-// EMAGLS_STAGGER (default 1): the two lane groups of a batch issue the stages before the sweep in complementary orders
-// (emagls_pre_sweep, orders 1 and 2); 0: both in the order of a single design
-static int stagger_mode() {
-    static const int m = [] { const char* e = getenv("EMAGLS_STAGGER"); return e ? atoi(e) : 1; }();
-    return m;
-}
 // a lane batch whose designs all keep the orthonormal route of their low bins off the path to the sweep (plan_defers_hh_route)
 bool batch_defers_hh(const emagls_batch& b) {
     // Only a batch that has the device to itself (a job list of ONE chunk: b.alone, set with its forked streams): there the stages are
     // the path to the sweep -- 2570-2620 -> 2810-2880 sets/s at 20 steps although the sweep itself runs 10 % longer next to them.  With
     // four chunks in flight the same work only moves, and the slower sweeps cost 6 % (3470 -> 3270 at 128 steps).
-    static const int defer_mode = [] { const char* e = getenv("EMAGLS_DEFER_HH"); return e ? atoi(e) : 1; }();   // (2: every lane batch -- experiments)
-    if (!b.lanes || !(b.alone || defer_mode == 2) || b.geo_share || b.atf_share) return false;
+    if (!b.lanes || !(b.alone || sw_int<Sw::DEFER_HH>() == 2) || b.geo_share || b.atf_share) return false;
     for (const emagls_plan* p : b.plans) if (!p || !plan_defers_hh_route(*p)) return false;
     return true;
 }
+// lane mode: the pipeline of plan `first` is enqueued once on `st` with grid.z = `count` designs (plans first .. first + count - 1)
+// part 0: stages before the sweep, part 2: stages after it
 void batch_lanes_part(emagls_batch& b, int part, int first, int count, hipStream_t st, int group = 0) {
     emagls_plan& p0 = *b.plans[first];
     const int ns = (part == 0 && b.groups == 1) ? b.nstreams : 1;
     int order = 0;
-    if (part == 0 && ns == 1) {
-        const int sm = stagger_mode();
-        if (sm == 1) order = b.groups > 1 ? 1 + group % 2 : (b.order_hint ? 1 + (b.order_hint - 1) % 2 : 0);
-        else if (sm >= 10) order = group == 0 ? sm / 10 % 10 : sm % 10;   // (experiments: "12", "21", "11", "22")
-    }
+    // the two lane groups of a batch issue the stages before the sweep in complementary orders (emagls_pre_sweep, orders 1 and 2);
+    // EMAGLS_STAGGER=0: both in the order of a single design
+    if (part == 0 && ns == 1 && sw_on<Sw::STAGGER>()) order = b.groups > 1 ? 1 + group % 2 : (b.order_hint ? 1 + (b.order_hint - 1) % 2 : 0);
     // plan `first` stands for its lanes: on the group's stream, with the batch's side streams when the stages fork
     Scoped stream(p0.stream, st);
     Scoped nstreams(p0.nstreams, ns);
@@ -269,8 +260,7 @@ void batch_execute_atf(emagls_batch& b) {
             throw Error(EMAGLS_ERR_ARG, "every plan of the batch needs its HRIRs, its grid and the ATFs");
     batch_atf_decide_sharing(b);
     emagls_plan& p0 = *b.plans[0];
-    static const bool one_stream = [] { const char* e = getenv("EMAGLS_ATF_ONE_STREAM"); return !(e && e[0] == '0'); }();
-    if (b.atf_share && p0.sweep_persist && one_stream) { batch_run_two_graphs(b, b.group[0], batch_atf_shared_stage, 0, 1); return; }
+    if (b.atf_share && p0.sweep_persist) { batch_run_two_graphs(b, b.group[0], batch_atf_shared_stage, 0, 1); return; }
     batch_run_per_plan(b, b.use_graph && b.eager_runs >= 1,
                        [&](emagls_plan& p) { if (b.atf_share && &p != &p0) from_atf_subject_pre_stage(p); else plan_pre_stage(p); },
                        from_atf_post_sweep, sweep_launch_count(p0));
@@ -513,7 +503,7 @@ bool batch_unify_routes_once(emagls_batch& b) {
             plan_routes(*p);
             plan_alloc_routes(*p);
         } catch (const Error& e) {   // (e.g. more Householder-route orders than the register tile holds: keep the plan's own routes)
-            if (getenv("EMAGLS_DEBUG_LANES")) fprintf(stderr, "common routes refused: %s\n", e.what());
+            if (sw_on<Sw::DEBUG_LANES>()) fprintf(stderr, "common routes refused: %s\n", e.what());
             p->gram_floor = keep_floor; p->nh_floor = keep_nh;
             plan_routes(*p);
             plan_alloc_routes(*p);
@@ -544,8 +534,7 @@ void batch_geo_forget(emagls_batch& b) {
 }
 // the form the next sharing execute takes while nothing else changes (also asked by the job scheduler: slot_will_capture)
 bool batch_geo_next_is_warm(const emagls_batch& b) {
-    static const bool keep = [] { const char* e = getenv("EMAGLS_GEO_KEEP"); return !(e && e[0] == '0'); }();
-    if (!keep || !b.geo_share || b.geo_kept_version == ~0ull || b.geo_kept_version != batch_geo_version(b)) return false;
+    if (!sw_on<Sw::GEO_KEEP>() || !b.geo_share || b.geo_kept_version == ~0ull || b.geo_kept_version != batch_geo_version(b)) return false;
     for (const emagls_plan* p : b.plans) if (p->prof_level > 0) return false;   // (a profiled plan shows the stages of a whole design)
     return true;
 }
@@ -605,7 +594,7 @@ void batch_decide_residency(emagls_batch& b) {
 }
 
 void batch_try_lanes(emagls_batch& b) {
-    if (const char* e = getenv("EMAGLS_BATCH_LANES")) if (e[0] == '0') return;
+    if (!sw_on<Sw::BATCH_LANES>()) return;
     emagls_plan& q = *b.plans[0];
     if (!q.sweep_persist) return;
     for (auto* p : b.plans)
@@ -614,7 +603,7 @@ void batch_try_lanes(emagls_batch& b) {
     batch_unify_routes(b);
     trace_mark("lanes: routes unified");
     batch_unify_synth(b);
-    const bool dbg = getenv("EMAGLS_DEBUG_LANES") != nullptr;
+    const bool dbg = sw_on<Sw::DEBUG_LANES>();
     for (auto* p : b.plans) {
         if (p->S != q.S || p->simOrder != q.simOrder || p->nOut != q.nOut || p->nfft != q.nfft || p->ldS != q.ldS || p->ldD != q.ldD ||
             p->Dpad != q.Dpad || p->k_cut != q.k_cut || p->cplx_basis != q.cplx_basis || p->out_cplx != q.out_cplx ||
@@ -681,9 +670,7 @@ void batch_try_lanes(emagls_batch& b) {
     {   // more than 8 designs: two lane groups before the sweep (EMAGLS_BATCH_GROUPS=1 keeps one launch sequence for all lanes, 3 / 4
         // allow groups of 8 for 17 ... 32 designs: measured with 32-design batches, 3125 / 3345 sets/s at 128 / 512 steps with four
         // groups against 3296 / 3499 with two, and the same 2070 at 20 steps)
-        const char* e = getenv("EMAGLS_BATCH_GROUPS");
-        const int cap = e ? std::max(1, std::min(4, atoi(e))) : 2;
-        b.groups = std::max(1, std::min(cap, (int)ceil_div((int64_t)b.plans.size(), 8)));
+        b.groups = std::max(1, std::min(sw_int<Sw::BATCH_GROUPS>(), (int)ceil_div((int64_t)b.plans.size(), 8)));
     }
 }
 

@@ -22,11 +22,6 @@ std::mutex g_cache_mu;
 std::vector<CachedPlan> g_cache;
 uint64_t g_cache_tick = 0;
 
-size_t plan_cache_capacity() {
-    static const size_t cap = [] { const char* e = getenv("EMAGLS_PLAN_CACHE"); return e ? (size_t)std::max(0, atoi(e)) : (size_t)4; }();
-    return cap;
-}
-
 int one_shot(const emagls_design_desc& desc, const double* hL, const double* hR, const double* azi, const double* zen,
              const double* mic_azi, const double* mic_zen, const double* atf, const double* atf_azi, const double* atf_zen,
              void* wL, void* wR, double* mean_dev, const void* Y_hrir = nullptr, const void* Y_mic = nullptr) {
@@ -50,8 +45,7 @@ int one_shot(const emagls_design_desc& desc, const double* hL, const double* hR,
                 // ~4 ms in a plan), but a MULTI-stream capture is what both hipGraphLaunch crashes of this round had in common
                 // (StreamPool above; again with the pool in place after a lane batch of the same shape) and a cached one-shot plan
                 // is captured and replayed inside whatever session the caller runs.  EMAGLS_ONESHOT_STREAMS=3 restores the forks.
-                const char* e = getenv("EMAGLS_ONESHOT_STREAMS");
-                fresh->nstreams = e ? std::max(1, std::min(3, atoi(e))) : 1;
+                fresh->nstreams = sw_int<Sw::ONESHOT_STREAMS>();
                 fresh->alone = true;   // (a one-shot call has the device to itself: the orthonormal route of the low bins runs next to the sweep)
             }
             p = fresh.get();
@@ -65,14 +59,14 @@ int one_shot(const emagls_design_desc& desc, const double* hL, const double* hR,
                         else g_cache.erase(g_cache.begin() + i);   // a failed call leaves the plan in an unknown state: drop it
                         break;
                     }
-            } else if (ok && plan_cache_capacity() > 0) {
-                if (g_cache.size() >= plan_cache_capacity()) {   // evict the least recently used idle plan
+            } else if (ok && sw_int<Sw::PLAN_CACHE>() > 0) {
+                if (g_cache.size() >= (size_t)sw_int<Sw::PLAN_CACHE>()) {   // evict the least recently used idle plan
                     size_t victim = g_cache.size();
                     for (size_t i = 0; i < g_cache.size(); ++i)
                         if (!g_cache[i].busy && (victim == g_cache.size() || g_cache[i].last_use < g_cache[victim].last_use)) victim = i;
                     if (victim < g_cache.size()) g_cache.erase(g_cache.begin() + victim);
                 }
-                if (g_cache.size() < plan_cache_capacity()) {
+                if (g_cache.size() < (size_t)sw_int<Sw::PLAN_CACHE>()) {
                     CachedPlan c;
                     c.plan = std::move(fresh);
                     c.desc = desc; c.device = dev; c.busy = false; c.last_use = ++g_cache_tick;
@@ -106,7 +100,8 @@ int one_shot(const emagls_design_desc& desc, const double* hL, const double* hR,
 }
 
 // designs per batch: 8 by default (one per XCD in the resident sweep), up to 16 (two per XCD) after emagls_set_batch_max / EMAGLS_BATCH_MAX
-std::atomic<int> g_batch_max{[] { const char* e = getenv("EMAGLS_BATCH_MAX"); return e ? std::max(1, std::min(REG_SWEEP_MAX, atoi(e))) : 8; }()};
+static_assert(REG_SWEEP_MAX == 32, "the clamp of EMAGLS_BATCH_MAX in switches.hpp");
+std::atomic<int> g_batch_max{sw_int<Sw::BATCH_MAX>()};   // (initialised at load time: the switch table is usable then, see switches.hpp)
 }  // namespace
 
 namespace emagls {
@@ -537,7 +532,7 @@ int emagls_batch_create(emagls_plan** plans, int nplans, emagls_batch** batch) {
         b->device = b->plans[0]->device;
         DeviceGuard dg(b->device);
         b->stream = StreamPool::get().take();
-        if (const char* ng = getenv("EMAGLS_NO_GRAPH")) b->use_graph = !(ng[0] == '1');
+        b->use_graph = !sw_on<Sw::NO_GRAPH>();
         // one persistent sweep launch keeps designs x nWG workgroups resident: one per CU up to 8 designs (one design per XCD),
         // two per CU beyond (77 KB of LDS and 5 waves per workgroup)
         // (up to 8 designs: 16 CUs stay free of sweep workgroups, so that kernels of other batches which need a whole CU keep

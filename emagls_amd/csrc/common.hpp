@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "switches.hpp"
+
 namespace emagls {
 
 // ---------------------------------------------------------------------------------------------
@@ -103,8 +105,6 @@ struct BatchScope {
 
 #ifdef __HIPCC__
 inline dim3 bgrid(dim3 g) { g.z = (unsigned)batch_ctx().n; return g; }
-// EMAGLS_XCD_RUNS=0: the kernels that take an XCD-aware tile order (xcd_run_index) keep the dispatch order
-inline int xcd_runs_enabled() { static const int on = [] { const char* e = getenv("EMAGLS_XCD_RUNS"); return (e && e[0] == '0') ? 0 : 1; }(); return on; }
 // (byte arithmetic on the pointer itself: a round trip through an integer hides the address space from the compiler and
 // every access through the result becomes a flat_* instruction, which also counts on lgkmcnt and so couples with LDS waits)
 template <typename T> __device__ __forceinline__ T* boffz(T* p, size_t stride, unsigned z) {

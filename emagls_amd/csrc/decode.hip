@@ -653,22 +653,17 @@ void decode_cache_clear() {
     g_decode[1].release();
 }
 
-// EMAGLS_DECODE_FUSED=0: always the hipFFT passes
-static bool decode_fused_enabled() { const char* e = getenv("EMAGLS_DECODE_FUSED"); return !(e && e[0] == '0'); }
-
 // true when binaural_decode_real takes the wave-private transforms for filters of `len` taps (ols_wave_kernel): the complex render
 // then hands over its interleaved signal as it is (sigc) instead of splitting it into planes first
 bool decode_wave_form(int64_t len) {
-    const char* e_rr = getenv("EMAGLS_DECODE_REGFFT");
-    const char* e_wave = getenv("EMAGLS_DECODE_WAVE");
-    return len <= 2048 && decode_fused_enabled() && 2 * len > WF_N / 2 && 2 * len <= WF_N && !(e_rr && e_rr[0] == '0') && !(e_wave && e_wave[0] == '0');
+    return len <= 2048 && sw_on<Sw::DECODE_FUSED>() && 2 * len > WF_N / 2 && 2 * len <= WF_N && sw_on<Sw::DECODE_REGFFT>() && sw_on<Sw::DECODE_WAVE>();
 }
 
 void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL, const double* wR, int64_t len,
                           double* out, hipStream_t st, const cplx* sigc) {
     if (n <= 0) return;
     if (sigc && !decode_wave_form(len)) throw Error(3, "binaural_decode_real: an interleaved complex signal needs the wave form");
-    if (len <= 2048 && decode_fused_enabled()) {
+    if (len <= 2048 && sw_on<Sw::DECODE_FUSED>()) {
         // block length ~ filter length: twice the transforms of the 4x blocks below, but every one of them stays in LDS
         int Nf = 256, log2n = 8;
         while (Nf < 2 * len) { Nf <<= 1; ++log2n; }
@@ -676,12 +671,10 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
         const int64_t nblocks = ceil_div(n, B);
         std::lock_guard<std::mutex> lk(g_decode_mu);
         DecodeWork& w = decode_work(C, 0, Nf);
-        const char* e_rr = getenv("EMAGLS_DECODE_REGFFT");   // (read at every call: a test switches forms inside one process)
-        const bool use_rr = !(e_rr && e_rr[0] == '0');
-        const char* e_wave = getenv("EMAGLS_DECODE_WAVE");
-        const bool wave_form = use_rr && Nf == WF_N && !(e_wave && e_wave[0] == '0');
-        const char* e_ft = getenv("EMAGLS_DECODE_FILTER_FFT");   // =hipfft: the filter side of the wave form through hipFFT + ols_wave_tables_kernel
-        const bool own_filter_side = wave_form && !(e_ft && e_ft[0] == 'h');
+        const bool use_rr = sw_on<Sw::DECODE_REGFFT>();
+        const bool wave_form = use_rr && Nf == WF_N && sw_on<Sw::DECODE_WAVE>();
+        // EMAGLS_DECODE_FILTER_FFT=hipfft: the filter side of the wave form through hipFFT + ols_wave_tables_kernel
+        const bool own_filter_side = wave_form && !sw_on<Sw::DECODE_FILTER_FFT>();
         if (!own_filter_side) {
             fft_check(hipfftSetStream(w.pw, st), "set stream");
             ols_padfilt_kernel<<<256, 256, 0, st>>>(wL, wR, C, len, Nf, w.wpad);

@@ -361,12 +361,6 @@ __device__ __forceinline__ void factor_jacobi_body(FactorArgs a, const int blk, 
     }
 }
 __global__ void __launch_bounds__(256) factor_jacobi_kernel(FactorArgs a, size_t bstride) { factor_jacobi_body(a, (int)blockIdx.x, bstride); }
-// two independent sets of bins in one launch (the Gram-route bins whose 1 % clipping is active and the Householder-route bins of
-// one design: each set is as long as its slowest bin's sweeps, so two launches on one stream cost twice that)
-__global__ void __launch_bounds__(256) factor_jacobi_pair_kernel(FactorArgs a, FactorArgs b, int na, size_t bstride) {
-    if ((int)blockIdx.x < na) factor_jacobi_body(a, (int)blockIdx.x, bstride);
-    else factor_jacobi_body(b, (int)blockIdx.x - na, bstride);
-}
 
 // =============================================================================================
 // kernel 3: Z_k = conj(Q2 [N; 0]) by applying the stored reflectors backwards; least-squares bins.
@@ -481,7 +475,7 @@ __global__ void __launch_bounds__(MAXT) factor_back_kernel(FactorArgs a, size_t 
 
 // The form of rounds 1-4 (every thread reads its rows of v_j from global memory): kept for the tall problems (more than 256 rows:
 // config 4's large radii), where the rows of B alone fill the registers a 1024-thread workgroup may have and the compiler spills
-// less around global loads than around the staged form's LDS reads (EMAGLS_BACK_LDS=1 takes the staged form there too).
+// less around global loads than around the staged form's LDS reads.
 template <int NCH, int RPT, int MAXT>
 __global__ void __launch_bounds__(MAXT)
 __attribute__((amdgpu_waves_per_eu(4, 8))) factor_back_global_kernel(FactorArgs a, size_t bstride) {
@@ -566,18 +560,15 @@ static void launch_one(const FactorArgs& a, int nbins, hipStream_t st, int phase
     if (phases & 1) {
         factor_qr_kernel<TT, NCH, RPT, MAXT><<<bgrid(nbins), threads, dyn, st>>>(a, batch_ctx().stride);
         KERNEL_CHECK();
-        if (!(phases & 8)) {   // (8: the caller launches the Jacobi step itself, launch_factor_jacobi_pair)
-            FactorArgs aj = a;
-            aj.nbins = nbins;
-            aj.jsplit = nbins;   // one workgroup per bin: the full SVDs of the ill-conditioned bins are the long pole
-            aj.jrun = 1;
-            factor_jacobi_kernel<<<bgrid(nbins), 256, 0, st>>>(aj, batch_ctx().stride);
-            KERNEL_CHECK();
-        }
+        FactorArgs aj = a;
+        aj.nbins = nbins;
+        aj.jsplit = nbins;   // one workgroup per bin: the full SVDs of the ill-conditioned bins are the long pole
+        aj.jrun = 1;
+        factor_jacobi_kernel<<<bgrid(nbins), 256, 0, st>>>(aj, batch_ctx().stride);
+        KERNEL_CHECK();
     }
     if (phases & 2) {
-        static const bool lds_tall = [] { const char* e = getenv("EMAGLS_BACK_LDS"); return e && e[0] == '1'; }();
-        if (RPT <= 8 || lds_tall) {
+        if constexpr (RPT <= 8) {
             static PerDeviceOnce back_once;
             if (back_once.first())
                 HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(factor_back_kernel<NCH, RPT, MAXT>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
@@ -623,21 +614,7 @@ void launch_factor_jacobi_gram(const FactorArgs& a, int nbins, hipStream_t st) {
     KERNEL_CHECK();
 }
 
-// The Jacobi steps of the Gram-route bins (launch_factor_jacobi_gram's arguments) and of the Householder-route bins (launch_factor's,
-// after its QR with phases = 1 | 8) as one launch.
-void launch_factor_jacobi_pair(const FactorArgs& gram, int nb_gram, const FactorArgs& hh, int nb_hh, hipStream_t st) {
-    if (gram.C > CPMAX || hh.C > CPMAX) throw Error(2, "factor: more than 32 output channels is not supported in this build");
-    FactorArgs ag = gram, ah = hh;
-    ag.nbins = nb_gram;
-    const int jr = ag.jrun > 0 ? ag.jrun : 1;
-    ag.jsplit = 0;
-    const int na = (nb_gram + jr - 1) / jr;
-    ah.nbins = nb_hh; ah.jsplit = nb_hh; ah.jrun = 1;
-    factor_jacobi_pair_kernel<<<bgrid(na + nb_hh), 256, 0, st>>>(ag, ah, na, batch_ctx().stride);
-    KERNEL_CHECK();
-}
-
-// phases: 1 = QR + Jacobi (| 8: QR only), 2 = back-transform (+ least-squares bins), 3 = both
+// phases: 1 = QR + Jacobi, 2 = back-transform (+ least-squares bins), 3 = both
 void launch_factor(const FactorArgs& a0, int nbins, bool tn_cplx, hipStream_t st, int phases) {
     if (nbins <= 0) return;
     const FactorArgs& a = a0;

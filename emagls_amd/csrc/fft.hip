@@ -700,9 +700,6 @@ void launch_hrir_grpdelay(const double* hL, const double* hR, int64_t L, int64_t
     KERNEL_CHECK();
 }
 
-// EMAGLS_HRIR_FFT_WAVE=0: the LDS radix-2^2 form at every length (read per call: a test compares the two in one process)
-static bool hrir_fft_wave_enabled() { const char* e = getenv("EMAGLS_HRIR_FFT_WAVE"); return !(e && e[0] == '0'); }
-
 void launch_hrir_fft(const double* hL, const double* hR, int64_t L, int64_t D, const int64_t* didx, int nfft,
                      const void* tw, const double* grpd, int mode, int n_c, int kabs0, void* Hc, double* Habs,
                      int64_t ldD, hipStream_t st, double* HcT, int ldT) {
@@ -718,7 +715,7 @@ void launch_hrir_fft(const double* hL, const double* hR, int64_t L, int64_t D, c
     const int log2n = ilog2(nfft);
     const int P = nfft / 2 + 1;
     if (P > HF_MAXS * 512) throw Error(2, "HRIR FFT: nfft above 2048 is not supported");
-    if (nfft == WF_N && L <= WF_N && hrir_fft_wave_enabled()) {   // wave-private transforms
+    if (nfft == WF_N && L <= WF_N && sw_on<Sw::HRIR_FFT_WAVE>()) {   // wave-private transforms
         const size_t smw = sizeof(cplx) * (WF_TABLES + (size_t)HW_TD * HW_STRIDE);
         static PerDeviceOnce wave_once;
         if (wave_once.first())
@@ -736,7 +733,7 @@ void launch_hrir_fft(const double* hL, const double* hR, int64_t L, int64_t D, c
     // (nfft = 2048 -- configs 4 and 5 -- gets two directions per sub-tile, 98 KB: nothing fits next to the round-4 sweep's twin
     // workgroups anyway, and four sub-tiles instead of eight are 2-3 % of a config 4 / 5 batch)
     size_t budget = (nfft >= 2048 ? 110 : 83) * 1024;
-    if (const char* e = getenv("EMAGLS_HRIR_FFT_LDS_KB")) budget = (size_t)std::max(40, std::min(158, atoi(e))) * 1024;
+    if (const int kb = sw_int<Sw::HRIR_FFT_LDS_KB>()) budget = (size_t)kb * 1024;
     const size_t shared = (size_t)2 * P * 16;
     int TS = HF_TD;
     while (TS > 1 && (size_t)TS * nfft * 16 + shared > budget) TS >>= 1;

@@ -347,7 +347,7 @@ void launch_gram_gemm(const void* bn, int nOrd, int P, int kb0, int nbins, doubl
     const int K = (nOrd * nOrd + 3) / 4 * 4;
     const int mtiles = (nbins + 63) / 64;
     gemm_tn_f64_kernel<<<bgrid(dim3(mtiles, (C * C + 63) / 64)), 256, 0, st>>>(Cf, ldC, Kmat, ldK, K, Apk, ldA, nbins, C * C, mtiles, 0,
-                                                                               batch_ctx().stride, xcd_runs_enabled());
+                                                                               batch_ctx().stride, sw_on<Sw::XCD_RUNS>());
     KERNEL_CHECK();
 }
 
@@ -387,7 +387,7 @@ void launch_hy_conj_mfma(const double* HcT, int ldT, int n_c, const void* Yc, in
     const int64_t pstride = (int64_t)(ceil_div(M, 64) * 64) * ldP;
     const int kc = hym_kslice(D);                            // rows D .. HYM_KS kc of both operands are zero (padded buffers)
     gemm_tn_f64_kernel<<<bgrid(dim3(mtiles * HYM_KS, (N + 63) / 64)), 256, 0, st>>>(HcT, ldT, (const double*)Yc, ldb, kc, Pw, ldP, M, N, mtiles,
-                                                                                    pstride, batch_ctx().stride, xcd_runs_enabled());
+                                                                                    pstride, batch_ctx().stride, sw_on<Sw::XCD_RUNS>());
     KERNEL_CHECK();
     hy_combine_kernel<<<bgrid(dim3((unsigned)ceil_div(S, 256), 2 * n_c)), 256, 0, st>>>(Pw, ldP, pstride, 2 * n_c, S, y_cplx ? 1 : 0, (cplx*)out, ldS,
                                                                                       batch_ctx().stride);

@@ -34,7 +34,6 @@ constexpr int SMAIR_DEFAULT_ORDER = 4;    // dependencies/getSMAIRMatrix.m:39-41
 
 // ---- defined in host_pools.hip
 extern thread_local std::string g_last_error;   // what emagls_last_error() returns: written by guarded_call only
-bool trace_on();
 void trace_mark(const char* what);
 
 // Streams are recycled through a process-wide pool and never destroyed.  A design plan owns three and a long session creates
@@ -46,7 +45,6 @@ struct StreamPool {
     std::mutex mu;
     std::map<int, std::vector<hipStream_t>> idle;   // per device
     static StreamPool& get() { static StreamPool* p = new StreamPool; return *p; }   // (never destroyed: outlives every plan)
-    static bool enabled() { static const bool on = [] { const char* e = getenv("EMAGLS_STREAM_POOL"); return !(e && e[0] == '0'); }(); return on; }
     hipStream_t take() {
         int dev = 0;
         HIP_CHECK(hipGetDevice(&dev));
@@ -55,14 +53,14 @@ struct StreamPool {
             // set-up), so a lone chunk's batch would fork its stages onto exactly those first streams -- and ran 8 % slower that way
             // (2400-2470 against 2590-2670 sets/s at 20 steps, A/B on one box, profiles/r06_stream_warm.md; any number of parked streams
             // from 4 to 80 restores it).  So the pool parks 8 streams before it hands the first one out (EMAGLS_STREAM_WARM=n; 0: none).
-            static const int warm = [] { const char* e = getenv("EMAGLS_STREAM_WARM"); return e ? atoi(e) : 8; }();
+            const int warm = sw_int<Sw::STREAM_WARM>();
             static std::once_flag once;
             if (warm > 0) std::call_once(once, [&] {
                 std::lock_guard<std::mutex> lk(mu);
                 for (int i = 0; i < warm; ++i) { hipStream_t st = nullptr; if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) idle[dev].push_back(st); }
             });
         }
-        if (enabled()) {
+        if (sw_on<Sw::STREAM_POOL>()) {
             std::lock_guard<std::mutex> lk(mu);
             auto& v = idle[dev];
             if (!v.empty()) { hipStream_t st = v.back(); v.pop_back(); return st; }
@@ -73,7 +71,7 @@ struct StreamPool {
     }
     void give(hipStream_t st) {
         if (!st) return;
-        if (!enabled()) { hipStreamDestroy(st); return; }
+        if (!sw_on<Sw::STREAM_POOL>()) { hipStreamDestroy(st); return; }
         hipStreamSynchronize(st);
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) { hipStreamDestroy(st); return; }
@@ -100,8 +98,7 @@ struct BlockPool {
         // (128 GB of the 288: a rank's share of BASELINE config 4 holds two arenas of 21 GB -- the small radii keep materialised
         // operands, 1.5 GB per design -- plus as much again in released plan slabs while the next chunks are being built; with 64 GB the
         // arenas were freed and every list of new radii allocated them afresh, 0.3 ms ... 5 s per hipMalloc)
-        static const size_t c = [] { const char* e = getenv("EMAGLS_POOL_GB"); return (size_t)(e ? std::max(0, atoi(e)) : 128) << 30; }();
-        return c;
+        return (size_t)sw_int<Sw::POOL_GB>() << 30;
     }
     // Sizes of large blocks (batch arenas: gigabytes) come in classes -- multiples of an eighth of the power of two below them -- so that
     // the arenas of similar chunks (other array radii: routes, hence buffer sizes, a few per cent apart) are the SAME size and one
@@ -136,7 +133,7 @@ struct BlockPool {
         void* p = nullptr;
         const auto t_alloc0 = std::chrono::steady_clock::now();
         hipError_t e = hipMalloc(&p, alloc_bytes);
-        if (trace_on() && alloc_bytes >= ((size_t)256 << 20)) {
+        if (sw_on<Sw::JOBS_TRACE>() && alloc_bytes >= ((size_t)256 << 20)) {
             std::lock_guard<std::mutex> lk(mu);
             std::string have;
             for (auto& kv : free_[dev]) if (kv.first >= ((size_t)256 << 20)) have += " " + std::to_string(kv.first >> 20);
@@ -249,8 +246,7 @@ struct emagls_plan {
             Slab sl{nullptr, (std::max(bytes, SLAB_BYTES) + SLAB_BYTES - 1) / SLAB_BYTES * SLAB_BYTES, 0};
             sl.base = static_cast<char*>(BlockPool::get().take(sl.size, &sl.size));
             // (one fill per slab instead of one per buffer: 66 hipMemsetAsync calls were 1.9 ms of a plan's set-up)
-            static const bool fill = [] { const char* e = getenv("EMAGLS_SLAB_FILL"); return !(e && e[0] == '0'); }();
-            if (!fill || hipMemsetAsync(sl.base, 0, sl.size, stream) != hipSuccess) { (void)hipGetLastError(); slab_zeroed = false; } else slab_zeroed = true;
+            if (hipMemsetAsync(sl.base, 0, sl.size, stream) != hipSuccess) { (void)hipGetLastError(); slab_zeroed = false; } else slab_zeroed = true;
             slabs.push_back(sl);
         }
         void* p = slabs.back().base + slabs.back().used;

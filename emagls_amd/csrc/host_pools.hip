@@ -6,9 +6,8 @@ namespace emagls {
 
 thread_local std::string g_last_error;
 // EMAGLS_JOBS_TRACE=1: wall-clock marks of the job lists' host-side phases on stderr
-bool trace_on() { static const bool t = getenv("EMAGLS_JOBS_TRACE") != nullptr; return t; }
 void trace_mark(const char* what) {
-    if (!trace_on()) return;
+    if (!sw_on<Sw::JOBS_TRACE>()) return;
     static const auto t0 = std::chrono::steady_clock::now();
     fprintf(stderr, "emagls trace: %-44s %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }

@@ -229,7 +229,7 @@ bool jobs_chunk_shares_geometry(const emagls_job* jobs, int n) {
 }
 void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool solo, uint64_t call) {
     DeviceGuard dg(device);
-    static const bool trace = getenv("EMAGLS_JOBS_TRACE") != nullptr;
+    const bool trace = sw_on<Sw::JOBS_TRACE>();
     const auto t_begin = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (trace) fprintf(stderr, "emagls jobs: chunk of %d, %s at %.3f ms\n", n, what,
@@ -274,8 +274,7 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
         slot.reset(new JobSlot);
         slot->key = key; slot->shape = shape; slot->device = device;
         slot->grids.resize((size_t)n);
-        static const bool share_stream = [] { const char* e = getenv("EMAGLS_JOBS_SHARED_STREAM"); return !(e && e[0] == '0'); }();
-        if (share_stream) slot->stream = emagls::pool_stream_take();
+        slot->stream = emagls::pool_stream_take();
         struct SharedStream { SharedStream(hipStream_t st) { g_plan_stream_shared = st; } ~SharedStream() { g_plan_stream_shared = nullptr; } } shared_stream(slot->stream);
         for (int j = 0; j < n; ++j) {
             emagls_plan* p = nullptr;
@@ -318,8 +317,7 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
         if (rc != EMAGLS_OK && rc != EMAGLS_ERR_UNSUPPORTED) check_rc(rc);   // (unsupported as a batch -- e.g. more than 32 channels: plan by plan)
         if (rc != EMAGLS_OK) slot->batch = nullptr;
         if (slot->batch && solo && slot->batch->lanes) {
-            static const int fork = [] { const char* e = getenv("EMAGLS_JOBS_FORK"); return e ? std::max(1, std::min(4, atoi(e))) : 3; }();
-            if (fork >= 2) {
+            if (const int fork = sw_int<Sw::JOBS_FORK>(); fork >= 2) {
                 if (slot->batch->groups != 1) { HIP_CHECK(hipStreamSynchronize(slot->batch->stream)); drop_batch_graphs(*slot->batch); slot->batch->groups = 1; }
                 check_rc(emagls_batch_set_streams(slot->batch, fork));
             }
@@ -372,11 +370,10 @@ void jobs_run_chunk(const emagls_job* jobs, int n, int device, int flags, bool s
         // Decided here without being asked (jobs_chunk_shares_geometry: EMAGLS_JOBS_INDEPENDENT / EMAGLS_JOBS_AUTO_SHARE=0 switch that
         // off); with EMAGLS_JOBS_SHARE_GEOMETRY the batch is asked whatever the rule says (MagLS / LS sets on one grid).  Either way the
         // library compares the grids on the device, and a chunk whose designs do not agree runs them as independent designs.
-        static const bool auto_env = [] { const char* e = getenv("EMAGLS_JOBS_AUTO_SHARE"); return !(e && e[0] == '0'); }();
         const int kind = jobs[0].desc.kind;
         bool want = false;
         if (flags & EMAGLS_JOBS_SHARE_GEOMETRY) want = kind != EMAGLS_KIND_FROM_ATF && kind != EMAGLS_KIND_EMA_SH;
-        else if (auto_env && !(flags & EMAGLS_JOBS_INDEPENDENT)) want = jobs_chunk_shares_geometry(jobs, n);
+        else if (sw_on<Sw::JOBS_AUTO_SHARE>() && !(flags & EMAGLS_JOBS_INDEPENDENT)) want = jobs_chunk_shares_geometry(jobs, n);
         // (only when it changes: the call makes the batch compare its grids again and run its geometry stages again)
         if (want != slot->batch->geo_want) check_rc(emagls_batch_set_geometry_sharing(slot->batch, want ? 1 : 0));
     }
@@ -469,7 +466,7 @@ int emagls_jobs_run(const emagls_job* jobs, int64_t njobs, int batch_size, int i
         if (in_flight <= 0) in_flight = 4;
         batch_size = std::min(batch_size, REG_SWEEP_MAX);
         g_jobs_resident_max.store(std::max((size_t)8 * REG_SWEEP_MAX, (size_t)2 * batch_size * (size_t)in_flight));   // (EMAGLS_JOBS_RESIDENT overrides)
-        if (const char* e = getenv("EMAGLS_JOBS_RESIDENT")) { const long v = atol(e); if (v > 0) g_jobs_resident_max.store((size_t)v); }
+        if (const int v = sw_int<Sw::JOBS_RESIDENT>(); v > 0) g_jobs_resident_max.store((size_t)v);
         int device = 0;
         HIP_CHECK(hipGetDevice(&device));
         // chunks: consecutive jobs of one shape; more than 16 designs per chunk only where the register-resident sweep takes them

@@ -144,8 +144,7 @@ void execute_magls(emagls_plan& p) {
 // chunks in flight next to each other (128 / 512 steps): 3474-3494 / 3537-3639 with 4, 3471-3497 / 3550-3597 with 2, 3375-3465 /
 // 3544-3572 with 1.  So: single bins where the stages before the sweep are forked (latency mode), runs of 2 in lane groups.
 int jacobi_run_length(const emagls_plan& p) {
-    static const int forced = [] { const char* e = getenv("EMAGLS_JACOBI_RUN"); return e ? std::max(1, atoi(e)) : 0; }();
-    if (forced) return forced;
+    if (const int forced = sw_int<Sw::JACOBI_RUN>()) return forced;
     return (batch_ctx().n >= 2 && p.nstreams <= 1) ? 2 : 1;
 }
 
@@ -253,10 +252,6 @@ void ema_sh_pre_sweep(emagls_plan& p) {
                        p.P, 1, ls_end, p.get("W"), st);
     p.mark("ls_bins");
 }
-
-// EMAGLS_SWEEP_REG=0: the synthesising sweep keeps its slab form (sweep_synth.hip) for every design; 2: the register-resident form for
-// launches of any size (read at every launch)
-static int reg_sweep_mode() { const char* e = getenv("EMAGLS_SWEEP_REG"); return e ? atoi(e) : 1; }
 
 // getEMagLsFiltersEMAinSH at orders 5..7 (36 / 49 / 64 channels; lib/getEMagLsFiltersEMAinSH.m:66-143): the per-direction rotations leave
 // no common S-space, so pwGrid_k.' = G_k (D x C) is factored itself -- Householder QR, one-sided Jacobi on the triangular factor, 1 %
@@ -632,9 +627,8 @@ void magls_post_sweep(emagls_plan& p) {
 // filters' rows, i.e. the epilogue AFTER the sweep -- 0.9 ms of the 3 ms a lone 20-design chunk spent before its sweep.  A batch
 // therefore runs them next to the sweep on a stream of their own (batch_execute_lanes).  EMAGLS_DEFER_HH=0: everything before the sweep.
 bool plan_defers_hh_route(const emagls_plan& p) {
-    static const bool on = [] { const char* e = getenv("EMAGLS_DEFER_HH"); return !(e && e[0] == '0'); }();
     const int k0 = std::max(p.kcut0, 1);
-    return on && p.synth && !p.diffuse && p.prof_level == 0 && p.d.kind != EMAGLS_KIND_EMA_SH && p.gram_from > 0 && p.hh_end > 1 && p.hh_end <= k0 - 1;
+    return sw_int<Sw::DEFER_HH>() != 0 && p.synth && !p.diffuse && p.prof_level == 0 && p.d.kind != EMAGLS_KIND_EMA_SH && p.gram_from > 0 && p.hh_end > 1 && p.hh_end <= k0 - 1;
 }
 // ---- The HRIR-side stages of an array design (lib/getEMagLsFilters.m:72-81, :94), for the plan h that owns the HRIR set on the
 // geometry of plan g.  emagls_pre_sweep calls them with g = h; a geometry-sharing batch (batch_geo_stage) with plan 0 as g, or, in
@@ -827,12 +821,6 @@ void emagls_pre_sweep(emagls_plan& p) {
     // s0: per-bin factors.  Gram route first (needs E, b_n, Gy): K matrices, one GEMM over the bins, direct inverses
     // (on a stream of its own with four streams: it does not need the Cholesky factor, the Householder route does)
     FactorArgs fa = hh_factor_args(p, p, p.get<int>("jsweeps"), nullptr);   // (cond_ok: blk_flags)
-    // single-stream sequences, EMAGLS_JACOBI_PAIR=1: the two Jacobi steps (Gram-route bins, Householder-route bins) as ONE launch --
-    // each lasts as long as its slowest bin (216 us) and on one stream they add up.  Off by default: with four batches in flight the
-    // shorter chain changes nothing (three runs each, 20 / 128 steps: 1831-1904 / 2260-2394 merged, 1789-1952 / 2334-2498 not)
-    const char* e_jp = getenv("EMAGLS_JACOBI_PAIR");
-    const bool merge_jacobi = s3 == s0 && p.nb_gram > 0 && hh_end > 1 && e_jp && e_jp[0] == '1';
-    FactorArgs fg_deferred{};
     auto blk_gram_route = [&] {
     if (s1 != s0) HIP_CHECK(hipStreamWaitEvent(s0, e_E, 0));
     if (s3 != s0) { HIP_CHECK(hipStreamWaitEvent(s3, e_Gy, 0)); HIP_CHECK(hipStreamWaitEvent(s3, e_E, 0)); }
@@ -851,8 +839,7 @@ void emagls_pre_sweep(emagls_plan& p) {
         // batches have workgroups to spare: a Jacobi workgroup walks a run of neighbouring bins, each warm-started from the
         // previous one (a third of the sweeps); a single design keeps one bin per workgroup (shortest critical path)
         fg.jrun = jacobi_run_length(p);
-        if (merge_jacobi) { fg_deferred = fg; }   // (one launch with the Householder-route bins: blk_hh_route)
-        else launch_factor_jacobi_gram(fg, p.nb_gram, s3);
+        launch_factor_jacobi_gram(fg, p.nb_gram, s3);
         p.mark("gram_route");
     }
     };
@@ -861,8 +848,7 @@ void emagls_pre_sweep(emagls_plan& p) {
     if (hh_end > 1) {
         launch_tn(p.get("R"), p.get("E"), Sh, p.C, p.ldS, nOrdH, cb, p.get("Tn"), ldSh, s0);
         p.mark("array_model+tn");
-        launch_factor(fa, hh_end - 1, cb, s0, merge_jacobi ? (1 | 8) : 1);
-        if (merge_jacobi) launch_factor_jacobi_pair(fg_deferred, p.nb_gram, fa, hh_end - 1, s0);
+        launch_factor(fa, hh_end - 1, cb, s0, 1);
     }
     };
     auto blk_flags = [&] {
@@ -953,12 +939,9 @@ HalfSweepArgs emagls_half_args(emagls_plan& p) {
     a.abort_flag = p.get<int>("flag") + 1;
     a.skip_flag = magls_kind(p.d.kind) ? p.get<int>("flag") + 4 : nullptr;
     a.timing = p.has("sweep_timing") ? p.get<long long>("sweep_timing") : nullptr;
-    const char* fg = getenv("EMAGLS_PERSIST_GLOBAL");
-    a.force_global = (fg && fg[0] == '1') ? 1 : 0;
-    static const int fetch_mode = [] { const char* e = getenv("EMAGLS_SWEEP_FETCH"); return e ? std::max(0, std::min(4, atoi(e))) : 0; }();
-    a.fetch_mode = fetch_mode;
-    static const long long wait_ticks = [] { const char* e = getenv("EMAGLS_SWEEP_WAIT_MS"); return (long long)(e ? std::max(1, atoi(e)) : 20) * 100000ll; }();
-    a.wait_ticks = wait_ticks;
+    a.force_global = sw_on<Sw::PERSIST_GLOBAL>() ? 1 : 0;
+    a.fetch_mode = sw_int<Sw::SWEEP_FETCH>();
+    a.wait_ticks = (long long)sw_int<Sw::SWEEP_WAIT_MS>() * 100000ll;
     if (p.synth) {   // the chain's channels are the microphones (sweep_synth.hip)
         const int M = (int)p.d.nmics;
         a.C = M;
@@ -968,10 +951,8 @@ HalfSweepArgs emagls_half_args(emagls_plan& p) {
         a.mic_azi = p.get<double>("mic_azi"); a.mic_zen = p.get<double>("mic_zen");
         a.smap = p.get<int>("smap");
         a.bsc = p.get<cplx>("bsc"); a.nord_pad = synth_nord_pad(p.simOrder + 1);
-        static const int split = [] { const char* e = getenv("EMAGLS_SYNTH_SPLIT"); return e ? atoi(e) : 67; }();
-        a.synth_split = split;
-        static const int prio = [] { const char* e = getenv("EMAGLS_SYNTH_PRIO"); return e ? std::max(0, std::min(5, atoi(e))) : 5; }();
-        a.synth_prio = prio;
+        a.synth_split = sw_int<Sw::SYNTH_SPLIT>();
+        a.synth_prio = sw_int<Sw::SYNTH_PRIO>();
         a.Winit = p.get<cplx>("Winit"); a.U = p.get<cplx>("Usw");
     }
     return a;
@@ -997,8 +978,6 @@ SweepGate::State& SweepGate::state() {   // (call with the mutex held)
 SweepGate::SweepGate(hipStream_t s, int slots_per_xcd) : lock(mutex()), st(s), slots(0) {
     State& g = state();
     slots = slots_per_xcd <= 0 ? g.capacity : std::min(slots_per_xcd, g.capacity);
-    static const bool serial = [] { const char* e = getenv("EMAGLS_SWEEP_SERIAL"); return e && e[0] == '1'; }();
-    if (serial) slots = g.capacity;
     // finished launches no longer hold slots (anywhere in the queue: launches of different sizes finish out of order)
     for (auto it = g.inflight.begin(); it != g.inflight.end();) {
         if (hipEventQuery(it->ev) == hipSuccess) { g.pool.push_back(it->ev); it = g.inflight.erase(it); }
@@ -1038,9 +1017,8 @@ SweepGate::~SweepGate() {   // (the lock is held from the waits to the record: n
 // device to itself anyway; from 9 designs on the register-resident form wins (16 designs: 3.8 against 3.4 ms next to each other, but
 // 32 designs in 5.2 ms and room for other kernels).
 bool reg_sweep_wanted(emagls_plan* const* plans, int n) {
-    const int mode = reg_sweep_mode();
-    static const int reg_min = [] { const char* e = getenv("EMAGLS_SWEEP_REG_MIN"); return e ? std::max(1, atoi(e)) : 9; }();   // (experiments)
-    if (mode == 0 || n < 1 || (mode == 1 && n < reg_min)) return false;
+    const int mode = sw_int<Sw::SWEEP_REG>();
+    if (mode == 0 || n < 1 || (mode == 1 && n < 9)) return false;
     const emagls_plan& q = *plans[0];
     for (int j = 0; j < n; ++j) {
         const emagls_plan& p = *plans[j];

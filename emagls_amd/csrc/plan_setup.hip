@@ -40,13 +40,9 @@ int orders_above_noise(double x, int nmax) {
     }
     return nmax;
 }
-// EMAGLS_SWEEP_SYNTH=0: every design on the materialised operands (dspace_g + sweep_persist_kernel)
-// (read when a plan is created: a test switches forms inside one process)
-static bool synth_enabled() { const char* e = getenv("EMAGLS_SWEEP_SYNTH"); return !(e && e[0] == '0'); }
 static bool plan_persist_possible(const emagls_plan& p) {
     const int64_t Dh = (p.d.kind == EMAGLS_KIND_FROM_ATF) ? p.Dm : p.D;
-    if (const char* e = getenv("EMAGLS_SWEEP_PERSIST")) if (e[0] == '0') return false;
-    return !p.wide && persist_sweep_fits((int)Dh, p.C, 1);
+    return sw_on<Sw::SWEEP_PERSIST>() && !p.wide && persist_sweep_fits((int)Dh, p.C, 1);
 }
 // Is the synthesising sweep in effect?  Needs the persistent form (all workgroups resident) and every swept bin on the Gram
 // route (the ill-conditioned swept bins of tiny arrays read Y_reg_inv_k from memory: they keep the materialised operands).
@@ -56,20 +52,16 @@ void plan_update_synth(emagls_plan& p) {
               synth_sweep_fits((int)p.D, (int)p.d.nmics, p.simOrder + 1, 1);
 }
 // first bin of the Gram route (GRAM_COND_EST and what it stands for: host_internal.hpp)
-double gram_cond_est() {
-    if (const char* e = getenv("EMAGLS_GRAM_COND_EST")) return atof(e);   // (tests force the re-run path with a huge limit)
-    return GRAM_COND_EST;
-}
+static_assert(GRAM_COND_EST == 3.0e3, "the default of EMAGLS_GRAM_COND_EST in switches.hpp");
 int emagls_gram_from(const emagls_plan& p) {
-    if (!p.gram_route || p.d.mic_radius <= 0.0) return 0;
-    if (const char* e = getenv("EMAGLS_GRAM_ROUTE")) if (e[0] == '0') return 0;
+    if (!p.gram_route || p.d.mic_radius <= 0.0 || !sw_on<Sw::GRAM_ROUTE>()) return 0;
     int n = 0;
     if (p.d.kind == EMAGLS_KIND_EMA_CH) n = p.d.order;   // 2N+1 circular harmonics reach order N
     else while ((n + 1) * (n + 1) < p.C) ++n;
     if (n < 1) return 0;
     double dfact = 1.0;
     for (int i = 3; i <= 2 * n + 1; i += 2) dfact *= i;
-    const double est_limit = gram_cond_est();
+    const double est_limit = sw_real<Sw::GRAM_COND_EST>();   // (tests force the re-run path with a huge limit)
     const double kr_min = std::pow(dfact / est_limit, 1.0 / n);
     const double df = p.d.fs / p.nfft;
     const int kb = (int)std::ceil(kr_min * C_SOUND / (2.0 * kPi * p.d.mic_radius) / df);
@@ -113,14 +105,13 @@ void plan_routes(emagls_plan& p) {
 // cos(d, j') = -cos(d, j) then holds to the rounding error of either cosine, and one polynomial evaluation serves both.
 // EMAGLS_SYNTH_PAIRS=0: no pairing.
 void synth_pairing(const double* azi, const double* zen, int M, int* smap) {
-    static const bool pairs_on = [] { const char* e = getenv("EMAGLS_SYNTH_PAIRS"); return !(e && e[0] == '0'); }();
     std::vector<double> u((size_t)3 * M);
     for (int j = 0; j < M; ++j) {
         u[3 * j] = std::sin(zen[j]) * std::cos(azi[j]); u[3 * j + 1] = std::sin(zen[j]) * std::sin(azi[j]); u[3 * j + 2] = std::cos(zen[j]);
     }
     std::vector<int> partner((size_t)M, -1);
     const double tol = 8.0 * 2.220446049250313e-16;
-    if (pairs_on && M <= 32)
+    if (sw_on<Sw::SYNTH_PAIRS>() && M <= 32)
         for (int j = 0; j < M; ++j) {
             if (partner[j] >= 0) continue;
             for (int k = j + 1; k < M; ++k) {
@@ -199,10 +190,9 @@ void plan_setup(emagls_plan& p) {
     // streams of a multi-stream execute are taken when one first asks for them)
     if (g_plan_stream_shared) { p.stream = g_plan_stream_shared; p.owns_stream = false; }
     else p.stream = StreamPool::get().take();
-    if (const char* ng = getenv("EMAGLS_NO_GRAPH")) p.use_graph = !(ng[0] == '1');
-    if (const char* es = getenv("EMAGLS_EAGER_SIDES")) if (es[0] == '1') p.need_sides(4);   // (experiments: round 5's four streams per plan)
+    p.use_graph = !sw_on<Sw::NO_GRAPH>();
     const auto t_setup1 = std::chrono::steady_clock::now();
-    if (const char* ns = getenv("EMAGLS_STREAMS")) p.nstreams = std::max(1, std::min(4, atoi(ns)));
+    if (const int ns = sw_int<Sw::STREAMS>()) p.nstreams = ns;
     p.req_cplx = d.basis == EMAGLS_BASIS_COMPLEX;
     // Complex-basis eMagLS / eMagLS2 designs run in real arithmetic.  With Y_c = Y_r T (T unitary, block diagonal per order)
     // smair_c = T_N^H smair_r T and pwGrid_c = T_N^H pwGrid_r, hence Y_reg_inv_c = Y_reg_inv_r T_N, the angles
@@ -217,7 +207,7 @@ void plan_setup(emagls_plan& p) {
         throw Error(EMAGLS_ERR_UNSUPPORTED, "caller-supplied SH matrices are available for LS, MagLS, eMagLS and eMagLS2 designs");
     // (a caller-supplied complex basis need not be ours rotated by T: it takes the complex-arithmetic pipeline)
     p.real_internal = p.req_cplx && !p.custom_basis && (d.kind == EMAGLS_KIND_EMAGLS || d.kind == EMAGLS_KIND_EMAGLS2);
-    if (const char* e = getenv("EMAGLS_REAL_INTERNAL")) if (e[0] == '0') p.real_internal = false;
+    if (!sw_on<Sw::REAL_INTERNAL>()) p.real_internal = false;
     p.cplx_basis = p.req_cplx && !p.real_internal;
     p.D = d.ndirs;
     p.ldD = round_up(p.D, 64);
@@ -453,7 +443,7 @@ void plan_setup(emagls_plan& p) {
         p.alloc("route", sizeof(int) * (size_t)p.P);
         p.alloc("Gy", esz(cb) * (size_t)p.S * p.S);                    // Gram matrix of conj(Y) (upper block triangle)
         p.sweep_persist = plan_persist_possible(p);
-        p.synth_want = synth_enabled() && !cb && !p.custom_basis && !p.diffuse && d.kind != EMAGLS_KIND_EMA_SH &&
+        p.synth_want = sw_on<Sw::SWEEP_SYNTH>() && !cb && !p.custom_basis && !p.diffuse && d.kind != EMAGLS_KIND_EMA_SH &&
                        synth_sweep_supported((int)p.D, (int)d.nmics, p.simOrder + 1) && persist_sweep_supported((int)p.D, (int)d.nmics);
         plan_routes(p);
         plan_alloc_routes(p);
@@ -465,7 +455,7 @@ void plan_setup(emagls_plan& p) {
         p.alloc("Mw", sizeof(cplx) * ((size_t)p.P * p.C * p.C + 1024));
         p.alloc("cond_ok", sizeof(double) * (size_t)p.P);
         p.alloc("QT", esz(cb) * (size_t)(p.simOrder + 1) * p.C * p.ldD);
-        if (getenv("EMAGLS_SWEEP_TIMING")) p.alloc("sweep_timing", sizeof(long long) * 16 * (size_t)p.P);
+        if (sw_on<Sw::SWEEP_TIMING>()) p.alloc("sweep_timing", sizeof(long long) * 16 * (size_t)p.P);
         }
     }
     if (d.kind == EMAGLS_KIND_FROM_ATF) {
@@ -524,7 +514,7 @@ void plan_setup(emagls_plan& p) {
     p.alloc("wR", (p.out_cplx ? sizeof(cplx) : sizeof(double)) * (size_t)p.out_rows * p.out_cols);
     const auto t_setup2 = std::chrono::steady_clock::now();
     HIP_CHECK(hipStreamSynchronize(p.stream));
-    if (trace_on()) {
+    if (sw_on<Sw::JOBS_TRACE>()) {
         const auto t_setup3 = std::chrono::steady_clock::now();
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "emagls trace: plan setup: streams %.3f ms, %zu buffers in %zu slabs %.3f ms, final sync %.3f ms\n", ms(t_setup0, t_setup1), p.bufs.size(),

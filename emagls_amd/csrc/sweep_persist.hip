@@ -455,9 +455,6 @@ size_t persist_sweep_ll_bytes(int D, int C) {
     return sizeof(u64) * ((size_t)2 * nprod * 8 * C + (size_t)2 * 8 * C + 64);
 }
 
-// EMAGLS_SWEEP_TWIN=0: launches of 9-16 designs as two independent 256-thread workgroups per CU (the earlier form)
-// (read at every launch: a test switches forms inside one process)
-static bool sweep_twin_enabled() { const char* e = getenv("EMAGLS_SWEEP_TWIN"); return !(e && e[0] == '0'); }
 static void persist_set_attributes() {
     static PerDeviceOnce attr_once;   // (function attributes are per device)
     if (attr_once.first()) {
@@ -485,7 +482,7 @@ int sweep_cu_budget() {
     int dev = 0, n = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    if (const char* e = getenv("EMAGLS_CU_BUDGET")) { const int b = atoi(e); if (b > 0 && b < n) n = b; }
+    if (const int b = sw_int<Sw::CU_BUDGET>(); b > 0 && b < n) n = b;
     return n;
 }
 // Can `ndesigns` designs' workgroups of the resident sweep all be on the device at once?  The runtime's occupancy figure for the
@@ -494,7 +491,7 @@ int sweep_cu_budget() {
 bool persist_sweep_fits(int D, int C, int ndesigns) {
     if (!persist_sweep_supported(D, C) || ndesigns < 1 || ndesigns > SWEEP_MULTI_MAX) return false;
     persist_set_attributes();
-    const bool twin = ndesigns > 8 && sweep_twin_enabled();
+    const bool twin = ndesigns > 8 && sw_on<Sw::SWEEP_TWIN>();
     const int nh = twin ? 2 : 1, dpw = persist_sweep_dpw(D), ni = persist_ni(C);
     const int nWG = (int)ceil_div(persist_sweep_nwg(D), nh);
     int occ = 0;
@@ -507,7 +504,7 @@ void launch_sweep_persist(const HalfSweepMulti& m, hipStream_t st) {
     const HalfSweepArgs& a = m.a[0];
     const int nSlab = persist_sweep_nwg(a.D);
     if (!persist_sweep_supported(a.D, a.C) || m.n > SWEEP_MULTI_MAX || a.P > PS_PMAX) throw Error(2, "persistent sweep: shape not supported");
-    const bool twin = m.n > 8 && sweep_twin_enabled();
+    const bool twin = m.n > 8 && sw_on<Sw::SWEEP_TWIN>();
     const int nh = twin ? 2 : 1;
     const int nWG = (int)ceil_div(nSlab, nh);
     const unsigned nblocks = 8u * (unsigned)nWG * (m.n > 8 ? 2u : 1u);

@@ -583,8 +583,7 @@ int reg_sweep_slots_per_xcd() { return 3 * (sweep_cu_budget() / 8); }
 int reg_sweep_pick_waves(int D, int ndesigns) {
     if (ndesigns < 1 || ndesigns > REG_SWEEP_MAX) return 0;
     const int nsub = (int)ceil_div(ndesigns, 8), cus = sweep_cu_budget() / 8;
-    if (const char* e = getenv("EMAGLS_REG_WAVES")) {   // (experiments: 4 ... 12 whenever it fits)
-        const int nw = atoi(e);
+    if (const int nw = sw_int<Sw::REG_WAVES>()) {   // (4 ... 12 whenever it fits)
         if ((nw == 4 || nw == 6 || nw == 8 || nw == 10 || nw == 12) && nsub * reg_nwg(D, nw) * reg_wg_cost(nw) <= 3 * cus && reg_occupancy(nw) >= (nw == 4 ? 3 : 1)) return nw;
     }
     for (int nw : RG_WAVES) if (nsub * reg_nwg(D, nw) <= cus && reg_occupancy(nw) >= 1) return nw;
@@ -593,9 +592,8 @@ int reg_sweep_pick_waves(int D, int ndesigns) {
 // Waves per workgroup when the designs of a launch are spread over all XCDs (0: not spread): taken when it gives every workgroup a
 // CU of its own with FEWER waves than the XCD-local layout needs (EMAGLS_REG_SPREAD=0: never, =1: whenever it fits).
 int reg_sweep_spread_waves(int D, int ndesigns) {
-    const char* es = getenv("EMAGLS_REG_SPREAD");   // (read at every launch: a test switches layouts inside one process)
-    const int mode = es ? atoi(es) : 2;
-    if (mode == 0 || ndesigns < 1 || ndesigns > REG_SWEEP_MAX || getenv("EMAGLS_REG_WAVES")) return 0;
+    const int mode = sw_int<Sw::REG_SPREAD>();
+    if (mode == 0 || ndesigns < 1 || ndesigns > REG_SWEEP_MAX || sw_int<Sw::REG_WAVES>() != 0) return 0;
     const int cus = sweep_cu_budget(), local = reg_sweep_pick_waves(D, ndesigns);
     for (int nw : RG_WAVES)
         if (ndesigns * reg_nwg(D, nw) <= cus && reg_occupancy(nw) >= 1) return (mode == 1 || local == 0 || nw < local) ? nw : 0;
@@ -624,7 +622,7 @@ void launch_sweep_reg(const HalfSweepArgs* args_dev, const HalfSweepArgs& a0, in
     const unsigned nblocks = spread ? (unsigned)(n * nWG) : 8u * (unsigned)nWG * (unsigned)ceil_div(n, 8);
     const size_t dyn = reg_dyn_bytes(RG_NUL, nw);
     reg_set_attributes();
-    static const int prio = [] { const char* e = getenv("EMAGLS_REG_PRIO"); return e ? atoi(e) : 1; }();
+    const int prio = sw_int<Sw::REG_PRIO>();
     switch (nw) {
         case 4: sweep_reg_kernel<RG_NUL, 4><<<dim3(nblocks), 256, dyn, st>>>(args_dev, n, nWG, spread, prio); break;
         case 6: sweep_reg_kernel<RG_NUL, 6><<<dim3(nblocks), 384, dyn, st>>>(args_dev, n, nWG, spread, prio); break;

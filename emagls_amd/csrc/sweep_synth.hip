@@ -597,7 +597,7 @@ void launch_synth_ls(const void* Hc, int64_t ldH, int n_c, const void* bsc, int 
     if (kb_hi <= kb_lo) return;
     synth_ls_kernel<<<bgrid(dim3((unsigned)M, (unsigned)synth_ls_chunks(D))), 256, 0, st>>>((const cplx*)Hc, ldH, n_c, (const cplx*)bsc, nord_pad, dir_azi, dir_zen,
                                                                                           mic_azi, mic_zen, smap, D, P, kb_lo, kb_hi, (cplx*)Upart, batch_ctx().stride,
-                                                                                          shared_geometry ? 0 : batch_ctx().stride, xcd_runs_enabled());
+                                                                                          shared_geometry ? 0 : batch_ctx().stride, sw_on<Sw::XCD_RUNS>());
     KERNEL_CHECK();
 }
 void launch_synth_rows(const void* U, int nchunks, const void* Pm, const void* Mw, int nOut, int M, int k_lo, int k_hi, int P, void* W, hipStream_t st,

@@ -974,10 +974,8 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
     // times left singular vectors that LAPACK's rounding alone determines -- its own result changes with the SVD driver.  The path
     // for up to 32 channels returns the part that is determined; this one refuses.)
     if (S < C) throw Error(2, "33..64 channels with fewer simulated SH channels than channels (rank-deficient array model: the reference's clipped inverse is rounding noise there) is not supported");
-    const char* e_reg = getenv("EMAGLS_WA_REG");   // =0: the forms that walk the columns through L2
-    const bool reg7 = ldS <= 64 * 7 && !(e_reg && e_reg[0] == '0');
-    const char* e_tall = getenv("EMAGLS_WA_TALL");   // =0: the plain forms for the tall problems
-    const bool tall_on = !reg7 && !(e_tall && e_tall[0] == '0');
+    const bool reg7 = ldS <= 64 * 7 && sw_on<Sw::WA_REG>();       // =0: the forms that walk the columns through L2
+    const bool tall_on = !reg7 && sw_on<Sw::WA_TALL>();           // =0: the plain forms for the tall problems
     const bool tall = tall_on && S <= 64 * WA_TALL;
     const bool pairf = tall_on && !tall && S <= 128 * WA_PAIR;   // (two waves per column)
     const size_t dyn_tall = sizeof(cplx) * 64 * WA_TALL, dyn_pair = sizeof(cplx) * 128 * WA_PAIR;
@@ -993,7 +991,7 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
     const size_t dyn = sizeof(cplx) * (size_t)2 * Cp * (Cp + 1);
     static PerDeviceOnce attr_once;
     if (attr_once.first()) HIP_CHECK(hipFuncSetAttribute((const void*)wa_jacobi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    static const double flag2 = [] { const char* e = getenv("EMAGLS_WA_JACOBI_FLAG"); const double f = e ? atof(e) : 1e-14; return f * f; }();
+    const double flag = sw_real<Sw::WA_JACOBI_FLAG>(), flag2 = flag * flag;
     wa_jacobi_kernel<<<nbins, 1024, dyn, st>>>((const cplx*)R2w, C, reg_c, (cplx*)Nw, sv, sweeps, flag2);
     KERNEL_CHECK();
     if (reg7) wa_back_reg_kernel<7><<<dim3(nbins, (unsigned)ceil_div(C, 32)), 512, 0, st>>>((const cplx*)Vw, tauw, (const cplx*)Nw, S, C, ldS, (cplx*)Z);
@@ -1019,11 +1017,9 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
 // No atomics, every sum in a fixed order: equal inputs give equal bits.
 // ---------------------------------------------------------------------------------------------
 WaTiling wa_tiling(int S, int C, int nbins) {
-    static const int leaf_rows = [] {   // EMAGLS_WA_LEAF_ROWS: another upper bound of the leaf height (1024 .. 4096; the measurements)
-        const char* e = getenv("EMAGLS_WA_LEAF_ROWS");
-        const int v = e ? atoi(e) : WA_LEAF_ROWS;
-        return v >= 1024 && v <= 128 * WA_PAIR ? v / 64 * 64 : WA_LEAF_ROWS;
-    }();
+    // EMAGLS_WA_LEAF_ROWS: another upper bound of the leaf height (1024 .. 4096; the measurements)
+    const int v = sw_int<Sw::WA_LEAF_ROWS>();
+    const int leaf_rows = v >= 1024 && v <= 128 * WA_PAIR ? v / 64 * 64 : WA_LEAF_ROWS;
     WaTiling t{};
     t.leaves = (int)ceil_div(S, leaf_rows);
     t.leaf_h = (int)ceil_div(ceil_div(S, t.leaves), 64) * 64;
@@ -1065,8 +1061,7 @@ void launch_wa_factor_tiled(void* B, void* Vw, int S, int C, int ldS, int nbins,
 }
 void launch_wa_yri(const void* Q, int64_t ldQ, const void* Z, int S, int C, int ldS, int D, int64_t ldD, int nbins, void* Yri, hipStream_t st) {
     if (nbins <= 0) return;
-    const char* e = getenv("EMAGLS_WA_YRI_MFMA");   // =0: the scalar form
-    if (e && e[0] == '0') wa_yri_kernel<<<dim3((unsigned)ceil_div(D, 64), nbins), 256, 0, st>>>((const double*)Q, ldQ, (const cplx*)Z, S, C, ldS, D, ldD, (cplx*)Yri);
+    if (!sw_on<Sw::WA_YRI_MFMA>()) wa_yri_kernel<<<dim3((unsigned)ceil_div(D, 64), nbins), 256, 0, st>>>((const double*)Q, ldQ, (const cplx*)Z, S, C, ldS, D, ldD, (cplx*)Yri);
     else wa_yri_mfma_kernel<<<dim3((unsigned)ceil_div(D, 64), nbins), 256, 0, st>>>((const double*)Q, ldQ, (const cplx*)Z, S, C, ldS, D, ldD, (cplx*)Yri);
     KERNEL_CHECK();
 }

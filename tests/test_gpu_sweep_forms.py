@@ -123,8 +123,8 @@ def test_synthesising_sweep_on_other_arrays(grids, thin, monkeypatch, nmics, pai
     """sweep_synth.hip evaluates pwGrid from the angles between HRIR directions and microphones; antipodal microphone pairs share
     one polynomial evaluation (g(-x) from the even and odd parts of g(x)).  Arrays with every, some and no antipodal pair, 7 to 32
     microphones (8-, 16- and 32-row slabs): against the oracle, against the materialised operands (EMAGLS_SWEEP_SYNTH=0) and
-    with the pairing switched off (EMAGLS_SYNTH_PAIRS=0 is read once per process, so that comparison runs in the default
-    process only through the plan's unit count)."""
+    with the pairing switched off (EMAGLS_SYNTH_PAIRS is a "process" switch -- DESIGN.md section 8 gives every switch's read time --,
+    so that comparison runs in the default process only through the plan's unit count)."""
     import emagls_amd as E
     from emagls_amd import Plan, _lib as L
     rng = np.random.default_rng(1000 + nmics)
