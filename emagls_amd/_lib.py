@@ -42,6 +42,17 @@ class Job(C.Structure):
                 ("wL", C.c_void_p), ("wR", C.c_void_p)]
 
 
+class DebugFactorArgs(C.Structure):
+    """emagls_debug_factor_args: the factor chain on the caller's matrices (emagls_debug_factor)."""
+    _fields_ = [("S", C.c_int), ("C", C.c_int), ("ldS", C.c_int), ("nbins", C.c_int), ("kb0", C.c_int), ("P", C.c_int),
+                ("Xd", C.c_void_p), ("xd_stride", c_i64), ("Tn", C.c_void_p), ("tn_cplx", C.c_int), ("bn", C.c_void_p), ("nOrders", C.c_int),
+                ("reg_mode", C.c_int), ("reg_c", C.c_double), ("tol_dim", C.c_double), ("Hq", C.c_void_p), ("ldHq", c_i64),
+                ("ls_end", C.c_int), ("hq_conj", C.c_int), ("phases", C.c_int), ("path", C.c_int), ("Z", C.c_void_p), ("sv", C.c_void_p),
+                ("sweeps", C.c_void_p), ("N", C.c_void_p), ("R2", C.c_void_p), ("tau", C.c_void_p), ("W", C.c_void_p)]
+
+
+DEBUG_SENTINEL_BITS = 0x7ff8dead0000beef
+
 JOBS_SHARE_GEOMETRY = 1
 JOBS_INDEPENDENT = 2
 
@@ -58,6 +69,9 @@ SYMBOLS = {
     "emagls_self_test": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
     "emagls_debug_synth_operand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_debug_synth_cosines": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "emagls_debug_factor": (C.c_int, [C.POINTER(DebugFactorArgs)]),
+    "emagls_debug_factor_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "emagls_sh_basis": (C.c_int, [C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "emagls_sh_basis_device": (C.c_int, [C.c_int, c_i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_modal_bn": (C.c_int, [C.c_int, c_i64, C.c_void_p, C.c_void_p]),

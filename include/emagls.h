@@ -93,6 +93,50 @@ int emagls_debug_synth_operand(const void* bsc, int nbins, int nord_pad, const d
  * microphone j), clamped to [-2, 2].  A zenith enters through cos(zen) and sqrt(1 - cos^2(zen)), as it enters the SH matrices: a value a
  * rounding outside [0, pi] is the direction mirrored back.  ndirs 1 ... 2^20, nmics 1 ... 64; host pointers, synchronous. */
 int emagls_debug_synth_cosines(const double* dir_azi, const double* dir_zen, int64_t ndirs, const double* mic_azi, const double* mic_zen, int nmics, double* x2);
+/* The per-bin factor chain on the caller's matrices: the launchers the designs use (assemble or load B_k, Householder QR, one-sided Jacobi,
+ * back-transform to Z_k = conj(U) diag(s_reg) V^T with B_k = U S V^H), with their own choice of kernel for the shape and their own refusals
+ * (EMAGLS_ERR_UNSUPPORTED).  All arrays are host arrays, complex ones interleaved; the call is synchronous.
+ *   path 0: the forms for up to 32 columns and 4096 rows; path 1: the forms for up to 64 columns (dense input, reg_mode 0, phases 3, no
+ *   Hq, ldS a multiple of 64; these write zeros into the rows S ... ldS-1 of Z).
+ *   Input, dense: Xd [nbins][C][ldS], xd_stride = C ldS, or 0 for one matrix read by every bin; kb0 = 0.  Input, assembled (Xd null):
+ *   B_k = sum_n bn[k][n] Tn[n], Tn [nOrders][C][ldS] real (tn_cplx = 0) or complex, bn [P][nOrders], for the bins k = kb0 ... kb0+nbins-1;
+ *   row s takes the orders n with (n+1)^2 > s only, and bin P-1 (Nyquist) the real part of bn.
+ *   reg_mode 0: s_reg = 1 / max(s, reg_c s_max); reg_mode 1: s_reg = 1 / s above tol_dim eps(s_max) and 0 below (MATLAB pinv).
+ *   Hq (optional) [2][nbins][ldHq], ldHq >= S: W[e][k][c] = sum_s Hq[e][k-kb0][s] Z_k[c][s] for k < ls_end (hq_conj != 0: Hq holds the
+ *   conjugate of those rows).  phases 3: one call of the launcher; 12: its phase 1 (QR, Jacobi) and phase 2 (back-transform) in two calls.
+ *   Outputs: Z [nbins][C][ldS] (required) and W [2][P][C] are filled with the quiet NaN of bits EMAGLS_DEBUG_SENTINEL_BITS before the
+ *   launch, so what the kernels leave alone shows; optional sv [nbins][C] (unsorted), sweeps [nbins], N and R2 [nbins][C][C], tau [nbins][C].
+ * 1 <= S <= ldS <= 4096, 1 <= C <= 64, 1 <= nbins <= 4096, kb0 + nbins <= P <= 8192; otherwise EMAGLS_ERR_ARG before the device is touched. */
+#define EMAGLS_DEBUG_SENTINEL_BITS 0x7ff8dead0000beefULL
+typedef struct {
+    int S, C, ldS, nbins, kb0, P;
+    const void* Xd;
+    int64_t xd_stride;
+    const void* Tn;
+    int tn_cplx;
+    const void* bn;
+    int nOrders;
+    int reg_mode;
+    double reg_c, tol_dim;
+    const void* Hq;
+    int64_t ldHq;
+    int ls_end, hq_conj;
+    int phases, path;
+    void* Z;
+    double* sv;
+    int* sweeps;
+    void* N;
+    void* R2;
+    double* tau;
+    void* W;
+} emagls_debug_factor_args;
+int emagls_debug_factor(const emagls_debug_factor_args* args);
+/* The Jacobi kernel of that chain in its Gram form, as the Gram route of the designs runs it: A [nbins][C][C] = B_k^H B_k, full Hermitian;
+ * route [nbins] = 1 (factor this bin) or 2 (skip it: its M keeps the sentinel, sweeps = -1); a workgroup walks jrun (1 ... 16) neighbouring
+ * bins and starts each from the rotations of the one before.  M [nbins][C][C] = V diag(s_reg / s) V^H with s = sqrt(eig(A)) and
+ * s_reg = 1 / max(s, reg_c s_max); sv [nbins][C], sweeps [nbins]; status [4]: [2] = 1 and [3] = the highest bin with s_max > cond_limit s_min. */
+int emagls_debug_factor_gram(const void* A, int nbins, int C, const int* route, int jrun, double reg_c, double cond_limit, void* M, double* sv, int* sweeps,
+                             int* status);
 
 /* ---- kernel-level entry points ------------------------------------------------------------- */
 

@@ -109,3 +109,42 @@ def test_debug_synth_operand_rejects_bad_arguments(lib):
     ang, out = np.zeros(4), np.zeros(16)
     for nd, nm, a in ((0, 4, ang), ((1 << 20) + 1, 4, ang), (4, 0, ang), (4, 65, ang), (4, 4, None)):
         assert lib.emagls_debug_synth_cosines(p(a) if a is not None else None, p(ang), nd, p(ang), p(ang), nm, p(out)) == L.ERR_ARG
+
+
+def test_debug_factor_rejects_bad_arguments(lib):
+    """emagls_debug_factor and emagls_debug_factor_gram validate before they touch the device (no GPU is needed to be refused): one input
+    form, the sizes within their ranges, the modes and selectors among their values, the wide path's restrictions, the pointers set."""
+    from emagls_amd import _lib as L
+    S, Cc, ldS = 6, 3, 8
+    X = np.zeros((1, Cc, ldS), dtype=np.complex128)
+    Z = np.zeros((1, Cc, ldS), dtype=np.complex128)
+    Tn = np.zeros((2, Cc, ldS)); bn = np.zeros((1, 2), dtype=np.complex128)
+    Hq = np.zeros((2, 1, ldS), dtype=np.complex128); W = np.zeros((2, 1, Cc), dtype=np.complex128)
+    p = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+
+    def call(**kw):
+        d = dict(S=S, C=Cc, ldS=ldS, nbins=1, kb0=0, P=1, Xd=p(X), xd_stride=Cc * ldS, Tn=None, tn_cplx=0, bn=None, nOrders=0, reg_mode=0,
+                 reg_c=0.01, tol_dim=0.0, Hq=None, ldHq=0, ls_end=0, hq_conj=0, phases=3, path=0, Z=p(Z))
+        d.update(kw)
+        return lib.emagls_debug_factor(C.byref(L.DebugFactorArgs(**d)))
+    for kw in (dict(Z=None), dict(Xd=None), dict(Tn=p(Tn), bn=p(bn), nOrders=2), dict(path=2), dict(path=-1), dict(phases=1), dict(phases=2), dict(phases=0),
+               dict(S=0), dict(C=0), dict(C=65), dict(ldS=S - 1), dict(ldS=4097), dict(nbins=0), dict(nbins=4097), dict(P=0), dict(kb0=-1), dict(kb0=1, P=2),
+               dict(P=8193), dict(reg_mode=2), dict(reg_c=-0.1), dict(reg_c=1.5), dict(reg_c=float("nan")), dict(tol_dim=-1.0), dict(xd_stride=5),
+               dict(Xd=None, Tn=p(Tn), bn=None, nOrders=2), dict(Xd=None, Tn=p(Tn), bn=p(bn), nOrders=0), dict(Xd=None, Tn=p(Tn), bn=p(bn), nOrders=1025),
+               dict(Hq=p(Hq), W=None, ldHq=ldS, ls_end=1), dict(Hq=p(Hq), W=p(W), ldHq=S - 1, ls_end=1), dict(Hq=p(Hq), W=p(W), ldHq=ldS, ls_end=2),
+               dict(path=1), dict(path=1, ldS=64, reg_mode=1), dict(path=1, ldS=64, phases=12), dict(path=1, ldS=64, Hq=p(Hq), W=p(W), ldHq=64, ls_end=1),
+               dict(path=1, ldS=64, Xd=None, Tn=p(Tn), bn=p(bn), nOrders=2)):
+        assert call(**kw) == L.ERR_ARG, kw
+    assert call(phases=1) == L.ERR_ARG and b"phases" in lib.emagls_last_error()
+    assert lib.emagls_debug_factor(None) == L.ERR_ARG
+
+    A = np.zeros((2, Cc, Cc), dtype=np.complex128); M = np.zeros_like(A)
+    route = np.ones(2, dtype=np.int32); sv = np.zeros((2, Cc)); sw = np.zeros(2, dtype=np.int32); status = np.zeros(4, dtype=np.int32)
+
+    def gram(nbins=2, Cn=Cc, jrun=1, reg_c=0.01, cond_limit=1e5, a=A, r=route, m=M, s=sv, w=sw, t=status):
+        return lib.emagls_debug_factor_gram(p(a), nbins, Cn, p(r), jrun, reg_c, cond_limit, p(m), p(s), p(w), p(t))
+    bad_route = np.array([1, 0], dtype=np.int32)
+    for kw in (dict(nbins=0), dict(nbins=4097), dict(Cn=0), dict(Cn=65), dict(jrun=0), dict(jrun=17), dict(reg_c=-1.0), dict(reg_c=2.0), dict(cond_limit=0.5),
+               dict(cond_limit=float("nan")), dict(r=bad_route), dict(a=None), dict(r=None), dict(m=None), dict(s=None), dict(w=None), dict(t=None)):
+        assert gram(**kw) == L.ERR_ARG, kw
+    assert gram(r=bad_route) == L.ERR_ARG and b"route" in lib.emagls_last_error()
