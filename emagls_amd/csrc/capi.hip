@@ -182,6 +182,25 @@ int emagls_debug_synth_cosines(const double* dir_azi, const double* dir_zen, int
     return guarded([&] { synth_cosines_debug(dir_azi, dir_zen, ndirs, mic_azi, mic_zen, nmics, x2); });
 }
 
+int emagls_debug_twiddles(int nfft, void* tw) {
+    return guarded([&] { twiddles_debug(nfft, tw); });
+}
+
+int emagls_debug_filter_epilogue(const void* W, int C, int nfft, int len, const double* grpd, int conj_mode, int dc_rule, int shift_mode, int out_cplx,
+                                 int n_ears, double fade_rel, void* outL, void* outR) {
+    return guarded([&] { filter_epilogue_debug(W, C, nfft, len, grpd, conj_mode, dc_rule, shift_mode, out_cplx, n_ears, fade_rel, outL, outR); });
+}
+
+int emagls_debug_hrir_spectra(const double* hL, const double* hR, int64_t L, int64_t D_src, int64_t D, const int64_t* didx, int nfft, int mode, int n_c,
+                              int kabs0, const double* grpd_in, int64_t ldD, int ldT, double* grpd_out, void* phs, void* Hc, double* Habs, double* HcT) {
+    return guarded([&] { hrir_spectra_debug(hL, hR, L, D_src, D, didx, nfft, mode, n_c, kabs0, grpd_in, ldD, ldT, grpd_out, phs, Hc, Habs, HcT); });
+}
+
+int emagls_debug_real_spectra(const double* x, int64_t L, int64_t ncols_src, int64_t ncols, const int64_t* colidx, int nfft, int64_t ldo, int64_t inner,
+                              int64_t ld_inner, void* out) {
+    return guarded([&] { real_spectra_debug(x, L, ncols_src, ncols, colidx, nfft, ldo, inner, ld_inner, out); });
+}
+
 int emagls_fp64_peak_tflops_ex(int which, int burst, double* tflops, double* shader_mhz) {
     return guarded([&] {
         if (!tflops || which < 0 || which > 2) throw Error(EMAGLS_ERR_ARG, "invalid argument");

@@ -2,54 +2,16 @@
 // launch_wa_factor and launch_factor_jacobi_gram, with their dispatch and their refusals -- on matrices the caller supplies, so that a test
 // can hold Z_k, the singular values and M_k against a factorisation of higher precision shape by shape.  No kernel is launched from here
 // and no dispatch is repeated here: an entry validates, allocates, copies, calls the launcher, synchronises, copies back and frees.
-#include <cstring>
-#include <vector>
-
 #include "../../include/emagls.h"
 #include "args.hpp"
+#include "debug_common.hpp"
 #include "kernels.hpp"
 
 namespace emagls {
 
-namespace {
-
-// what the outputs hold where the launcher wrote nothing: a quiet NaN with a payload of its own (EMAGLS_DEBUG_SENTINEL_BITS)
-double sentinel() {
-    const uint64_t bits = 0x7ff8dead0000beefULL;
-    double v;
-    std::memcpy(&v, &bits, sizeof v);
-    return v;
-}
-void fill_sentinel(void* p, size_t ndoubles) {
-    const double v = sentinel();
-    double* d = static_cast<double*>(p);
-    for (size_t i = 0; i < ndoubles; ++i) d[i] = v;
-}
-
-// device buffers of one call: freed together, whatever happens
-struct Bufs {
-    std::vector<void*> all;
-    ~Bufs() { for (void* p : all) hipFree(p); }
-    template <typename T> T* get(size_t n) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        all.push_back(p);
-        return static_cast<T*>(p);
-    }
-    template <typename T> T* filled(size_t n, double v) {   // n values of T, every double of them = v
-        std::vector<double> h(std::max<size_t>(n, 1) * sizeof(T) / sizeof(double), v);
-        T* p = get<T>(n);
-        HIP_CHECK(hipMemcpy(p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-        return p;
-    }
-    template <typename T> T* copy(const void* src, size_t n) {
-        T* p = get<T>(n);
-        HIP_CHECK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-        return p;
-    }
-};
-
-}  // namespace
+using debug::Bufs;
+using debug::fill_sentinel;
+using debug::sentinel;
 
 void factor_debug(const emagls_debug_factor_args& g) {
     const int S = g.S, C = g.C, ldS = g.ldS, nbins = g.nbins, kb0 = g.kb0, P = g.P;

@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(512) hrir_fft_kernel(const double* __restrict_
     const int P = nfft / 2 + 1;
     cplx* tws = reinterpret_cast<cplx*>(smem);  // nfft/2 twiddles while the stages run ...
     cplx* phs = tws;                            // ... [2][P] delay phase per ear and bin (mode 0) afterwards
-    cplx* buf = tws + 2 * P;                    // TS * nfft
+    cplx* buf = tws + 2 * P;                    // TS * nfft, then the 2 HF_TD flags `live`
     const int64_t d0 = (int64_t)blockIdx.x * HF_TD;
     const int nt = (int)min((int64_t)HF_TD, D - d0);
     const double gL = grpd[0], gR = grpd[1];
@@ -202,6 +202,12 @@ __global__ void __launch_bounds__(512) hrir_fft_kernel(const double* __restrict_
     for (int s = 0; s < HF_MAXS; ++s)
 #pragma unroll
         for (int t = 0; t < HF_TD; ++t) habs[s][0][t] = habs[s][1][t] = 0.0;
+    // Both ears share one transform and are separated as (z_k +- conj z_{nfft-k}) / 2: rounding error of one ear reaches the other
+    // (about 1e-16 of it).  An ear without a signal has no spectrum: live[2 t + e] is raised by the first non-zero tap of ear e of
+    // direction t, and the rows of an ear that raised nothing are written as zeros.
+    int* live = reinterpret_cast<int*>(buf + (size_t)TS * nfft);   // 2 HF_TD flags behind the buffers
+    if (threadIdx.x < 2 * HF_TD) live[threadIdx.x] = 0;
+    __syncthreads();
 
 #pragma unroll
     for (int sub = 0; sub < HF_TD / TS; ++sub) {
@@ -219,6 +225,8 @@ __global__ void __launch_bounds__(512) hrir_fft_kernel(const double* __restrict_
             const double a = (nl < L) ? hL[dsrc * L + nl] : 0.0;
             const double c = (nr < L) ? hR[dsrc * L + nr] : 0.0;
             buf[(size_t)t * nfft + j] = mk(a, c);
+            if (a != 0.0) live[2 * (t0 + t)] = 1;       // (every thread that writes, writes 1)
+            if (c != 0.0) live[2 * (t0 + t) + 1] = 1;
         }
         __syncthreads();
         lds_fft_stages<false>(buf, tws, nfft, log2n, nts, zskip);   // (ends with a barrier: the twiddles are free)
@@ -249,6 +257,8 @@ __global__ void __launch_bounds__(512) hrir_fft_kernel(const double* __restrict_
                             HLv = HLv * phs[kb];
                             HRv = HRv * phs[P + kb];
                         }
+                        if (!live[2 * (t0 + t)]) HLv = mk(0.0, 0.0);
+                        if (!live[2 * (t0 + t) + 1]) HRv = mk(0.0, 0.0);
                         const int64_t d = d0 + t0 + t;
                         if (kb < n_c) {
                             Hc[((int64_t)0 * n_c + kb) * ldD + d] = HLv;
@@ -273,6 +283,8 @@ __global__ void __launch_bounds__(512) hrir_fft_kernel(const double* __restrict_
                 cplx HLv = mk(0.5 * (z.x + zc.x), 0.5 * (z.y + zc.y));
                 cplx HRv = mk(0.5 * (z.y - zc.y), -0.5 * (z.x - zc.x));
                 if (mode == 0) { HLv = HLv * phs[kb]; HRv = HRv * phs[P + kb]; }
+                if (!live[2 * (t0 + t)]) HLv = mk(0.0, 0.0);
+                if (!live[2 * (t0 + t) + 1]) HRv = mk(0.0, 0.0);
                 double* row = HcT + (int64_t)(d0 + t0 + t) * ldT;
                 row[2 * kb] = HLv.x; row[2 * kb + 1] = HLv.y;
                 row[2 * (n_c + kb)] = HRv.x; row[2 * (n_c + kb) + 1] = HRv.y;
@@ -348,6 +360,11 @@ __global__ void __launch_bounds__(64 * HW_TD) hrir_fft_wave_kernel(const double*
                 v[n1] = mk(nl < L ? pl[nl] : 0.0, nr < L ? pr[nr] : 0.0);
             }
         }
+        // an ear without a signal has no spectrum (see hrir_fft_kernel): every tap of the direction is in some lane's v
+        bool nzL = false, nzR = false;
+#pragma unroll
+        for (int n1 = 0; n1 < 16; ++n1) { nzL |= v[n1].x != 0.0; nzR |= v[n1].y != 0.0; }
+        const bool liveL = __any(nzL), liveR = __any(nzR);
         if (upper_zero) wave_fft1024<true>(v, tb, tables, l); else wave_fft1024<false>(v, tb, tables, l);
         wave_fft_store_natural(v, tb, l);
         wave_lds_fence();
@@ -364,6 +381,8 @@ __global__ void __launch_bounds__(64 * HW_TD) hrir_fft_wave_kernel(const double*
                     HLv = HLv * phs[kb];
                     HRv = HRv * phs[P + kb];
                 }
+                if (!liveL) HLv = mk(0.0, 0.0);
+                if (!liveR) HRv = mk(0.0, 0.0);
                 if (kb < n_c) {
                     Hc[((int64_t)0 * n_c + kb) * ldD + d] = HLv;
                     Hc[((int64_t)1 * n_c + kb) * ldD + d] = HRv;
@@ -734,7 +753,7 @@ void launch_hrir_fft(const double* hL, const double* hR, int64_t L, int64_t D, c
     // workgroups anyway, and four sub-tiles instead of eight are 2-3 % of a config 4 / 5 batch)
     size_t budget = (nfft >= 2048 ? 110 : 83) * 1024;
     if (const int kb = sw_int<Sw::HRIR_FFT_LDS_KB>()) budget = (size_t)kb * 1024;
-    const size_t shared = (size_t)2 * P * 16;
+    const size_t shared = (size_t)2 * P * 16 + 2 * HF_TD * sizeof(int);   // (the twiddle / phase region and the flags `live`)
     int TS = HF_TD;
     while (TS > 1 && (size_t)TS * nfft * 16 + shared > budget) TS >>= 1;
     const size_t sm = (size_t)TS * nfft * 16 + shared;

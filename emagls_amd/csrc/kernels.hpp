@@ -43,6 +43,14 @@ void launch_real_fft_gather(const double* x, int64_t L, int64_t ncols, const int
 void launch_filter_epilogue(const void* W, int C, int nfft, int len, const void* tw, const double* grpd, int conj_mode,
                             int dc_rule, int shift_mode, int out_cplx, void* outL, void* outR, hipStream_t st, int n_ears = 2,
                             double fade_rel = 0.15);
+// ---- fft_debug.hip: the launchers above on host arrays (include/emagls.h: emagls_debug_twiddles ... emagls_debug_real_spectra); synchronous
+void twiddles_debug(int nfft, void* tw);
+void filter_epilogue_debug(const void* W, int C, int nfft, int len, const double* grpd, int conj_mode, int dc_rule, int shift_mode, int out_cplx,
+                           int n_ears, double fade_rel, void* outL, void* outR);
+void hrir_spectra_debug(const double* hL, const double* hR, int64_t L, int64_t D_src, int64_t D, const int64_t* didx, int nfft, int mode, int n_c, int kabs0,
+                        const double* grpd_in, int64_t ldD, int ldT, double* grpd_out, void* phs, void* Hc, double* Habs, double* HcT);
+void real_spectra_debug(const double* x, int64_t L, int64_t ncols_src, int64_t ncols, const int64_t* colidx, int nfft, int64_t ldo, int64_t inner,
+                        int64_t ld_inner, void* out);
 
 // ---- gram_chol.hip
 int gram_ksplit(int64_t D, int S);

@@ -137,6 +137,33 @@ int emagls_debug_factor(const emagls_debug_factor_args* args);
  * s_reg = 1 / max(s, reg_c s_max); sv [nbins][C], sweeps [nbins]; status [4]: [2] = 1 and [3] = the highest bin with s_max > cond_limit s_min. */
 int emagls_debug_factor_gram(const void* A, int nbins, int C, const int* route, int jrun, double reg_c, double cond_limit, void* M, double* sv, int* sweeps,
                              int* status);
+/* The transforms at both ends of a design on the caller's arrays: the launchers the designs use, with their own choice of kernel for the
+ * shape (radix-2 in LDS for a power of two, wave-private at nfft 1024, direct sums otherwise) and the table of launch_twiddles.  Host
+ * arrays, complex ones interleaved; synchronous; every output is filled with the NaN of EMAGLS_DEBUG_SENTINEL_BITS before the launch.
+ * Arguments outside the ranges below: EMAGLS_ERR_ARG before the device is touched.
+ *   emagls_debug_twiddles: tw [nfft] = exp(-2 pi i j / nfft); 2 <= nfft <= 8192.
+ *   emagls_debug_filter_epilogue: W [n_ears][nfft/2+1][C] positive-frequency spectra -> outL, outR [C][len], real (out_cplx 0) or complex.
+ *     dc_rule 1: W(0) := Re W(1).  conj_mode 0: Hermitian mirror; 1: W(nfft-k,(n,m)) = (-1)^m conj(W(k,(n,-m))), C a square; 2:
+ *     W(nfft-k,m) = conj(W(k,-m)) on the channels [0,-1,+1,-2,+2,...], C odd.  shift_mode 0: delay by nfft/2 (left) and
+ *     (nfft/2 + grpd[1]) - grpd[0] (right) as a phase, the Nyquist phase real; 1: rotation by nfft/2.  The len samples around nfft/2 are
+ *     kept and faded with hann(2 round(fade_rel len)).  nfft even, 4 ... 4096; len even, 2 ... nfft; 1 <= C <= 1024; n_ears 1 (grpd and
+ *     outR may be null) or 2; 0 <= fade_rel <= 0.5.
+ *   emagls_debug_hrir_spectra: hL, hR [D_src][L] -> the two group delays (median over the bins of the delay of the sum over all D_src
+ *     directions), grpd_out [2], and the delay phases the median kernel leaves behind them, phs [2][nfft/2+1] complex; then the spectra
+ *     of the D directions didx [D] selects (null: the first D), delayed by -grpd (mode 0, a phase) or rotated by -round(grpd) (mode 1):
+ *     Hc [2][n_c][ldD] complex for the bins below n_c, Habs [2][nfft/2+1-kabs0][ldD] for the bins from kabs0, and optionally HcT [D][ldT],
+ *     HcT[d][2 (e n_c + k) + re/im].  Hc, Habs and HcT all null: the delays only (L up to 4096; the spectra take L <= nfft).
+ *     grpd_in [2] (optional): these delays instead of the computed ones, phs then keeps the sentinel; not taken at mode 0 with nfft 1024,
+ *     where a kernel form reads phs.  nfft even, 4 ... 2048; ldD a multiple of 8; ldT even, >= 4 n_c; |grpd_in| <= 2^20.
+ *   emagls_debug_real_spectra: x [ncols_src][L] real -> out [nfft/2+1][ldo] complex, column j = colidx[j] (null: j) of x, zero-padded or
+ *     cut to nfft, at (j / inner) ld_inner + j % inner.  nfft even, 4 ... 4096; L <= 8192. */
+int emagls_debug_twiddles(int nfft, void* tw);
+int emagls_debug_filter_epilogue(const void* W, int C, int nfft, int len, const double* grpd, int conj_mode, int dc_rule, int shift_mode, int out_cplx,
+                                 int n_ears, double fade_rel, void* outL, void* outR);
+int emagls_debug_hrir_spectra(const double* hL, const double* hR, int64_t L, int64_t D_src, int64_t D, const int64_t* didx, int nfft, int mode, int n_c,
+                              int kabs0, const double* grpd_in, int64_t ldD, int ldT, double* grpd_out, void* phs, void* Hc, double* Habs, double* HcT);
+int emagls_debug_real_spectra(const double* x, int64_t L, int64_t ncols_src, int64_t ncols, const int64_t* colidx, int nfft, int64_t ldo, int64_t inner,
+                              int64_t ld_inner, void* out);
 
 /* ---- kernel-level entry points ------------------------------------------------------------- */
 

@@ -148,3 +148,53 @@ def test_debug_factor_rejects_bad_arguments(lib):
                dict(cond_limit=float("nan")), dict(r=bad_route), dict(a=None), dict(r=None), dict(m=None), dict(s=None), dict(w=None), dict(t=None)):
         assert gram(**kw) == L.ERR_ARG, kw
     assert gram(r=bad_route) == L.ERR_ARG and b"route" in lib.emagls_last_error()
+
+
+def test_debug_fft_entries_reject_bad_arguments(lib):
+    """emagls_debug_filter_epilogue, emagls_debug_hrir_spectra, emagls_debug_real_spectra and emagls_debug_twiddles validate before they
+    touch the device (no GPU is needed to be refused): the sizes within their ranges, the modes among their values, the mirror rules'
+    channel counts, indices inside the input, the paddings large enough, the pointers set."""
+    from emagls_amd import _lib as L
+    p = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+    nfft, ln, Cc = 16, 8, 9
+    W = np.zeros((2, nfft // 2 + 1, 25), dtype=np.complex128)
+    g = np.array([1.5, -2.0])
+    oL, oR = np.zeros((25, nfft), dtype=np.complex128), np.zeros((25, nfft), dtype=np.complex128)
+
+    def epi(w=W, C_=Cc, n=nfft, length=ln, grpd=g, conj=0, dc=1, shift=0, cplx=0, ears=2, fade=0.15, a=oL, b=oR):
+        return lib.emagls_debug_filter_epilogue(p(w), C_, n, length, p(grpd), conj, dc, shift, cplx, ears, fade, p(a), p(b))
+    for kw in (dict(w=None), dict(a=None), dict(b=None), dict(grpd=None), dict(n=2), dict(n=15), dict(n=4098), dict(n=0), dict(length=0), dict(length=7),
+               dict(length=nfft + 2), dict(C_=0), dict(C_=1025), dict(conj=3), dict(conj=-1), dict(conj=1, C_=7), dict(conj=2, C_=4), dict(dc=2), dict(shift=2),
+               dict(shift=-1), dict(cplx=2), dict(ears=0), dict(ears=3), dict(fade=-0.01), dict(fade=0.51), dict(fade=float("nan")),
+               dict(grpd=np.array([np.inf, 0.0])), dict(grpd=np.array([0.0, np.nan]))):
+        assert epi(**kw) == L.ERR_ARG, kw
+    assert epi(conj=1, C_=7) == L.ERR_ARG and b"conj_mode 1" in lib.emagls_last_error()
+
+    Lt, D = 5, 3
+    hL, hR = np.zeros((D, Lt)), np.zeros((D, Lt))
+    P = nfft // 2 + 1
+    idx, bad_idx = np.array([0, 2, 2], dtype=np.int64), np.array([0, 3, 1], dtype=np.int64)
+    go, phs = np.zeros(2), np.zeros((2, P), dtype=np.complex128)
+    Hc, Ha, HT = np.zeros((2, P, 8), dtype=np.complex128), np.zeros((2, P, 8)), np.zeros((D, 4 * P))
+
+    def hrir(a=hL, b=hR, L_=Lt, Ds=D, D_=D, didx=None, n=nfft, mode=0, n_c=P, kabs0=0, gin=None, ldD=8, ldT=4 * P, gout=go, ph=phs, hc=Hc, ha=Ha, ht=HT):
+        return lib.emagls_debug_hrir_spectra(p(a), p(b), L_, Ds, D_, p(didx), n, mode, n_c, kabs0, p(gin), ldD, ldT, p(gout), p(ph), p(hc), p(ha), p(ht))
+    for kw in (dict(a=None), dict(b=None), dict(n=2), dict(n=15), dict(n=2050), dict(L_=0), dict(L_=4097), dict(L_=nfft + 1), dict(Ds=0), dict(Ds=65537), dict(D_=0),
+               dict(D_=D + 1), dict(didx=bad_idx), dict(didx=np.array([0, -1, 1], dtype=np.int64)), dict(mode=2), dict(mode=-1), dict(n_c=-1), dict(n_c=P + 1),
+               dict(kabs0=-1), dict(kabs0=P + 1), dict(ldD=D - 1), dict(ldD=12), dict(ldD=1 << 18), dict(ldT=4 * P - 2), dict(ldT=4 * P + 1), dict(ldT=8194),
+               dict(hc=None), dict(ha=None), dict(hc=None, ha=None, ht=None, gout=None), dict(hc=None, ha=None, ht=None, gin=g),
+               dict(gin=np.array([2.0 ** 21, 0.0])), dict(gin=np.array([0.0, np.nan])), dict(n=1024, gin=g, mode=0, n_c=0, kabs0=513, ht=None)):
+        assert hrir(**kw) == L.ERR_ARG, kw
+    assert hrir(n=1024, gin=g, mode=0, n_c=0, kabs0=513, ht=None) == L.ERR_ARG and b"1024" in lib.emagls_last_error()
+
+    x, out = np.zeros((4, Lt)), np.zeros((P, 8), dtype=np.complex128)
+
+    def real(a=x, L_=Lt, src=4, nc=4, ci=None, n=nfft, ldo=8, inner=4, ldi=4, o=out):
+        return lib.emagls_debug_real_spectra(p(a), L_, src, nc, p(ci), n, ldo, inner, ldi, p(o))
+    for kw in (dict(a=None), dict(o=None), dict(n=2), dict(n=15), dict(n=4098), dict(L_=0), dict(L_=8193), dict(src=0), dict(nc=0), dict(nc=5), dict(nc=65537, src=65537),
+               dict(nc=3, ci=np.array([0, 4, 1], dtype=np.int64)), dict(nc=3, ci=np.array([0, -1, 1], dtype=np.int64)), dict(inner=0), dict(inner=4, ldi=3),
+               dict(ldi=1 << 18, inner=1), dict(ldo=3), dict(inner=2, ldi=5, ldo=6), dict(ldo=(1 << 20) + 1)):
+        assert real(**kw) == L.ERR_ARG, kw
+    tw = np.zeros(16, dtype=np.complex128)
+    for n, t in ((1, tw), (8193, tw), (16, None)):
+        assert lib.emagls_debug_twiddles(n, p(t)) == L.ERR_ARG
