@@ -597,15 +597,72 @@ def _real_mic_block(is_complex, what):
 _ANGLE_NAMES = ("horRotAngleRad", "pitchRad", "rollRad")
 
 
-class _DecodeObject:
+class _BlockStreamObject:
+    """What the block-stream objects share: the handle's life, the NumPy-or-torch dispatch of a push, the block-multiple check and
+    the frame of a torch push.  A subclass names itself (_kind) and its C destroy entry (_destroy), sets blockSize and has
+    _push_numpy(h, block, ...) and _push_torch(h, block, ...)."""
+
+    _h = None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the %s is closed" % self._kind)
+        return self._h
+
+    def _check_multiple(self, n):
+        if n % self.blockSize:
+            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, n))
+        return n
+
+    def push(self, block, *args):
+        h = self._handle()
+        if type(block).__module__.split(".")[0] == "torch":
+            return self._push_torch(h, block, *args)
+        return self._push_numpy(h, block, *args)
+
+    @staticmethod
+    def _need_gpu(block):
+        if not block.is_cuda:
+            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+
+    @staticmethod
+    def _on_current_stream(block, inputs, call):
+        """call(stream) on torch's current stream of the block's device, not synchronised."""
+        import torch
+        with torch.cuda.device(block.device):
+            call(C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        for t in inputs:      # (their memory may be reused only after the stream has passed the enqueued kernels)
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(block.device))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            L.check(getattr(L.load(), self._destroy)(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DecodeObject(_BlockStreamObject):
     """What BinauralDecodeStream and BinauralDecodeGroup share, which is the library's one object behind both: the filters and the
-    encoder of the creation, the checks of a pushed block, the host and the torch push, and the handle's life.  A subclass names
+    encoder of the creation, the checks of a pushed block, and the host and the torch push.  A subclass names
     its kind (_what) and the C entries it calls (_create, _create_encoded, _push, _push_device, _destroy), shapes the angles and
     the set indices of a push (_shape_angles, _shape_sets) and makes the output (_new_out)."""
 
+    _kind = property(lambda self: "decode " + self._what)
+
     def __init__(self, decodingFilterLeft, decodingFilterRight, blockSize, shDefinition, rotationDomain, complexInput, encoder,
                  numListeners=None):
-        self._h = None
         self._basis, self._cb = _basis(shDefinition)
         self._layout = _layout(rotationDomain)
         w_c = np.iscomplexobj(decodingFilterLeft) or np.iscomplexobj(decodingFilterRight)
@@ -642,20 +699,13 @@ class _DecodeObject:
                                                     self._basis, self.blockSize, *listeners, C.byref(h)))
         self._h = h
 
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the decode %s is closed" % self._what)
-        return self._h
-
     def _check_block(self, shape, ndim):
         if self.numMics is not None:
             if ndim != 2 or shape[1] != self.numMics:
                 raise ValueError("block must be [numSamples x numMics] matching the encoder's microphone count (%d)" % self.numMics)
         elif ndim != 2 or shape[1] != self.numChannels:
             raise ValueError("block must be [numSamples x numChannels] matching the filters' channel count (%d)" % self.numChannels)
-        if shape[0] % self.blockSize:
-            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
-        return shape[0]
+        return self._check_multiple(shape[0])
 
     def _check_complex(self, is_complex):
         if self.numMics is not None:
@@ -691,10 +741,7 @@ class _DecodeObject:
         a = np.ascontiguousarray(a, dtype=np.int32)
         return a if device is None else torch.as_tensor(a, device=device)
 
-    def push(self, block, horRotAngleRad=None, pitchRad=None, rollRad=None, setIndex=None):
-        h = self._handle()
-        if type(block).__module__.split(".")[0] == "torch":
-            return self._push_torch(h, block, horRotAngleRad, pitchRad, rollRad, setIndex)
+    def _push_numpy(self, h, block, horRotAngleRad, pitchRad, rollRad, setIndex):
         self._check_complex(np.iscomplexobj(block))
         x = np.asfortranarray(np.asarray(block, dtype=np.complex128 if self.complexInput else np.float64))
         n = self._check_block(x.shape, x.ndim)
@@ -710,8 +757,7 @@ class _DecodeObject:
     def _push_torch(self, h, block, hor, pitch, roll, setIndex):
         import torch
         n = self._check_block(tuple(block.shape), block.dim())
-        if not block.is_cuda:
-            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        self._need_gpu(block)
         self._check_complex(block.is_complex())
         xt = block.to(torch.complex128 if self.complexInput else torch.float64).t().contiguous()   # [numChannels][n]: column-major
 
@@ -727,31 +773,9 @@ class _DecodeObject:
         ts = self._set_index(setIndex, n, block.device)
         out, result = self._new_out(n, lambda shape: torch.empty(shape, dtype=torch.float64, device=block.device))
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-        with torch.cuda.device(block.device):
-            st = torch.cuda.current_stream().cuda_stream
-            L.check(getattr(L.load(), self._push_device)(h, p(xt), n, p(ts), count(ts), p(ty), count(ty), p(tp), count(tp), p(tr), count(tr),
-                                                         p(out), C.c_void_p(st)))
-        for t in (xt, ty, tp, tr, ts):      # (their memory may be reused only after the stream has passed the enqueued kernels)
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(block.device))
+        self._on_current_stream(block, (xt, ty, tp, tr, ts), lambda st: L.check(getattr(L.load(), self._push_device)(
+            h, p(xt), n, p(ts), count(ts), p(ty), count(ty), p(tp), count(tp), p(tr), count(tr), p(out), st)))
         return result
-
-    def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            L.check(getattr(L.load(), self._destroy)(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class BinauralDecodeStream(_DecodeObject):
@@ -889,7 +913,7 @@ class BinauralDecodeGroup(_DecodeObject):
         L.check(L.load().emagls_decode_group_reset(self._handle(), -1 if listener is None else int(listener)))
 
 
-class SourceFieldStream:
+class SourceFieldStream(_BlockStreamObject):
     """Dry source signals through array room responses, a block at a time: what the reference's harness
     does offline with fftfilt(srir.rir, sig) (testEMagLs.m:66-70), for a head that moves while the sound plays.  Created once from
     rirs [nr x numChannels] (one source) or [numSources x nr x numChannels], real or complex, and a block size (a power of two
@@ -901,8 +925,9 @@ class SourceFieldStream:
     numSources <= 16, numChannels <= 256, nr <= 1048576, response spectra <= 4 GiB; `info` gives block, partitions, state_bytes,
     response_bytes and launches_per_block."""
 
+    _kind, _destroy = "field stream", "emagls_field_stream_destroy"
+
     def __init__(self, rirs, blockSize):
-        self._h = None
         r_c = np.iscomplexobj(rirs)
         r = np.asarray(rirs, dtype=np.complex128 if r_c else np.float64)
         if r.ndim == 2:
@@ -919,11 +944,6 @@ class SourceFieldStream:
                                                     self.blockSize, C.byref(h)))
         self._h = h
 
-    def _handle(self):
-        if self._h is None:
-            raise ValueError("the field stream is closed")
-        return self._h
-
     @property
     def info(self):
         b, p, sb, rb, nl = L.c_i64(0), L.c_i64(0), L.c_i64(0), L.c_i64(0), C.c_int(0)
@@ -935,17 +955,15 @@ class SourceFieldStream:
             shape = (shape[0], 1)
         if len(shape) != 2 or shape[1] != self.numSources:
             raise ValueError("block must be [n] (one source) or [n x numSources] matching the responses' source count (%d)" % self.numSources)
-        if shape[0] % self.blockSize:
-            raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, shape[0]))
-        return shape[0]
+        return self._check_multiple(shape[0])
 
     def push(self, block):
         """block [n] or [n x numSources], real, n a multiple of blockSize: a NumPy array (host entry; returns a NumPy array
         [n x numChannels]), or a torch tensor on the stream's device (device entry on torch's current stream, not synchronised;
         returns a tensor [n x numChannels] that is the transposed view of the [numChannels][n] buffer the kernel wrote)."""
-        h = self._handle()
-        if type(block).__module__.split(".")[0] == "torch":
-            return self._push_torch(h, block)
+        return super().push(block)
+
+    def _push_numpy(self, h, block):
         if np.iscomplexobj(block):
             raise ValueError("a field stream takes real source signals")
         x = np.asarray(block, dtype=np.float64)
@@ -958,38 +976,18 @@ class SourceFieldStream:
     def _push_torch(self, h, block):
         import torch
         n = self._check_block(tuple(block.shape))
-        if not block.is_cuda:
-            raise ValueError("a torch block must be on the GPU (pass a NumPy array for the host entry)")
+        self._need_gpu(block)
         if block.is_complex():
             raise ValueError("a field stream takes real source signals")
         xt = block.to(torch.float64).reshape(n, self.numSources).t().contiguous()   # [numSources][n]: column-major
         out = torch.empty((self.numChannels, n), dtype=torch.complex128 if self.complexOutput else torch.float64, device=block.device)
-        with torch.cuda.device(block.device):
-            st = torch.cuda.current_stream().cuda_stream
-            L.check(L.load().emagls_field_stream_push_device(h, C.c_void_p(xt.data_ptr()), n, C.c_void_p(out.data_ptr()), C.c_void_p(st)))
-        xt.record_stream(torch.cuda.current_stream(block.device))   # (its memory may be reused only after the stream has passed the kernels)
+        self._on_current_stream(block, (xt,), lambda st: L.check(L.load().emagls_field_stream_push_device(
+            h, C.c_void_p(xt.data_ptr()), n, C.c_void_p(out.data_ptr()), st)))
         return out.t()
 
     def reset(self):
         """Zero history: what follows equals a fresh object bit for bit."""
         L.check(L.load().emagls_field_stream_reset(self._handle()))
-
-    def close(self):
-        if self._h is not None:
-            h, self._h = self._h, None
-            L.check(L.load().emagls_field_stream_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def designYawBank(kind, hL, hR, hrirGridAziRad, hrirGridZenRad, yawRad, *, order=4, fs=48000.0, len=512, shDefinition="real",

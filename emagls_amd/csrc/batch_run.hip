@@ -38,11 +38,11 @@ void batch_sweep_stage(emagls_batch& b) {
             if (b.lanes) { BatchScope sc(nb, b.stride); launch_zero(q0.get("ll"), q0.bufs["ll"].bytes, ss); }   // (one launch for every lane)
             else for (auto* q : b.plans) launch_zero(q->get("ll"), q->bufs["ll"].bytes, ss);
             if (reg) {
-                if (!b.sweep_args_dev) HIP_CHECK(hipMalloc(&b.sweep_args_dev, sizeof(HalfSweepArgs) * (size_t)REG_SWEEP_MAX));
-                reg_args_upload(ha.data(), nb, b.sweep_args_dev, b.sweep_args_last, ss);
+                if (!b.sweep_args_dev.get()) b.sweep_args_dev.alloc(sizeof(HalfSweepArgs) * (size_t)REG_SWEEP_MAX);
+                reg_args_upload(ha.data(), nb, b.sweep_args_dev.get(), b.sweep_args_last, ss);
             }
             if (b.prof_level >= 1) HIP_CHECK(hipEventRecord(b.sweep_ev[0], ss));
-            if (reg) launch_sweep_reg(static_cast<const HalfSweepArgs*>(b.sweep_args_dev), ha[0], nb, ss);
+            if (reg) launch_sweep_reg(b.sweep_args_dev.get<const HalfSweepArgs>(), ha[0], nb, ss);
             else if (q0.synth) launch_sweep_synth(h, ss); else launch_sweep_persist(h, ss);
             if (b.prof_level >= 1) HIP_CHECK(hipEventRecord(b.sweep_ev[1], ss));
         }
@@ -155,14 +155,14 @@ bool batch_inputs_same(emagls_batch& b, std::initializer_list<const char*> names
     uint64_t ver = 0;
     for (auto* p : b.plans) ver = ver * 1000003ull + p->atf_side_version;
     if (ver == checked_version) return same;
-    if (!b.cmp_flag) HIP_CHECK(hipMalloc(&b.cmp_flag, 16));
+    if (!b.cmp_flag.get()) b.cmp_flag.alloc(16);
     HIP_CHECK(hipStreamSynchronize(b.stream));
-    HIP_CHECK(hipMemsetAsync(b.cmp_flag, 0, 16, b.stream));
+    HIP_CHECK(hipMemsetAsync(b.cmp_flag.get(), 0, 16, b.stream));
     emagls_plan& p0 = *b.plans[0];
     for (size_t j = 1; j < b.plans.size(); ++j)
-        for (const char* name : names) launch_compare_words(p0.get(name), b.plans[j]->get(name), p0.bufs[name].bytes, b.cmp_flag, b.stream);
+        for (const char* name : names) launch_compare_words(p0.get(name), b.plans[j]->get(name), p0.bufs[name].bytes, b.cmp_flag.get<int>(), b.stream);
     int differ = 0;
-    HIP_CHECK(hipMemcpyAsync(&differ, b.cmp_flag, sizeof differ, hipMemcpyDeviceToHost, b.stream));
+    HIP_CHECK(hipMemcpyAsync(&differ, b.cmp_flag.get(), sizeof differ, hipMemcpyDeviceToHost, b.stream));
     HIP_CHECK(hipStreamSynchronize(b.stream));
     checked_version = ver;
     return same = differ == 0;

@@ -214,22 +214,13 @@ int emagls_sh_basis(int order, int64_t ndirs, const double* azi, const double* z
         if (ndirs == 0) return;
         const bool cb = basis == EMAGLS_BASIS_COMPLEX;
         const size_t S = (size_t)(order + 1) * (order + 1);
-        double *d_azi = nullptr, *d_zen = nullptr, *d_tab = nullptr;
-        void* d_Y = nullptr;
-        auto cleanup = [&] { hipFree(d_azi); hipFree(d_zen); hipFree(d_tab); hipFree(d_Y); };
-        try {
-            HIP_CHECK(hipMalloc(&d_azi, sizeof(double) * ndirs));
-            HIP_CHECK(hipMalloc(&d_zen, sizeof(double) * ndirs));
-            HIP_CHECK(hipMalloc(&d_tab, sizeof(double) * sh_coeff_count(order)));
-            HIP_CHECK(hipMalloc(&d_Y, esz(cb) * S * ndirs));
-            HIP_CHECK(hipMemcpy(d_azi, azi, sizeof(double) * ndirs, hipMemcpyDefault));
-            HIP_CHECK(hipMemcpy(d_zen, zen, sizeof(double) * ndirs, hipMemcpyDefault));
-            launch_sh_coeff(order, d_tab, nullptr);
-            launch_sh_basis(order, ndirs, d_azi, d_zen, d_tab, cb, d_Y, ndirs, nullptr);
-            HIP_CHECK(hipDeviceSynchronize());
-            HIP_CHECK(hipMemcpy(Y, d_Y, esz(cb) * S * ndirs, hipMemcpyDefault));
-        } catch (...) { cleanup(); throw; }
-        cleanup();
+        DevMem d_azi(sizeof(double) * ndirs), d_zen(sizeof(double) * ndirs), d_tab(sizeof(double) * sh_coeff_count(order)), d_Y(esz(cb) * S * ndirs);
+        HIP_CHECK(hipMemcpy(d_azi.get(), azi, sizeof(double) * ndirs, hipMemcpyDefault));
+        HIP_CHECK(hipMemcpy(d_zen.get(), zen, sizeof(double) * ndirs, hipMemcpyDefault));
+        launch_sh_coeff(order, d_tab.get<double>(), nullptr);
+        launch_sh_basis(order, ndirs, d_azi.get<double>(), d_zen.get<double>(), d_tab.get<double>(), cb, d_Y.get(), ndirs, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(Y, d_Y.get(), esz(cb) * S * ndirs, hipMemcpyDefault));
     });
 }
 
@@ -238,7 +229,8 @@ int emagls_sh_basis_device(int order, int64_t ndirs, const double* d_azi, const 
     return guarded([&] {
         if (order < 0 || ndirs < 0 || !d_azi || !d_zen || !d_Y) throw Error(EMAGLS_ERR_ARG, "invalid argument");
         if (ndirs == 0) return;
-        // the recurrence table is tiny and depends only on the order: cached per (thread, order)
+        // the recurrence table is tiny and depends only on the order: cached per (thread, order).  A raw pointer on purpose, not a
+        // DevMem: nothing may free device memory while a thread's storage is destroyed (device_mem.hpp)
         thread_local int tab_order = -1;
         thread_local double* tab = nullptr;
         hipStream_t st = (hipStream_t)stream;
@@ -256,18 +248,11 @@ int emagls_modal_bn(int order, int64_t nfreq, const double* kr, void* bn) {
     return guarded([&] {
         if (order < 0 || nfreq < 0 || !kr || !bn) throw Error(EMAGLS_ERR_ARG, "invalid argument");
         if (nfreq == 0) return;
-        double* d_kr = nullptr;
-        void* d_bn = nullptr;
-        auto cleanup = [&] { hipFree(d_kr); hipFree(d_bn); };
-        try {
-            HIP_CHECK(hipMalloc(&d_kr, sizeof(double) * nfreq));
-            HIP_CHECK(hipMalloc(&d_bn, sizeof(cplx) * nfreq * (order + 1)));
-            HIP_CHECK(hipMemcpy(d_kr, kr, sizeof(double) * nfreq, hipMemcpyDefault));
-            launch_modal_bn(order, nfreq, d_kr, 1.0, 1.0, d_bn, 1, nfreq, nullptr);  // column-major [nfreq x (order+1)]
-            HIP_CHECK(hipDeviceSynchronize());
-            HIP_CHECK(hipMemcpy(bn, d_bn, sizeof(cplx) * nfreq * (order + 1), hipMemcpyDefault));
-        } catch (...) { cleanup(); throw; }
-        cleanup();
+        DevMem d_kr(sizeof(double) * nfreq), d_bn(sizeof(cplx) * nfreq * (order + 1));
+        HIP_CHECK(hipMemcpy(d_kr.get(), kr, sizeof(double) * nfreq, hipMemcpyDefault));
+        launch_modal_bn(order, nfreq, d_kr.get<double>(), 1.0, 1.0, d_bn.get(), 1, nfreq, nullptr);  // column-major [nfreq x (order+1)]
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(bn, d_bn.get(), sizeof(cplx) * nfreq * (order + 1), hipMemcpyDefault));
     });
 }
 

@@ -6,7 +6,7 @@
 #include <mutex>
 #include <type_traits>
 
-#include "kernels.hpp"
+#include "device_mem.hpp"
 #include "lds_fft.hpp"
 #include "reg_fft.hpp"
 #include "wave_fft.hpp"
@@ -587,19 +587,11 @@ namespace {
 struct DecodeWork {
     int C = 0, Nf = 0, device = -1;
     int64_t nblocks = 0;
-    double *seg = nullptr, *wpad = nullptr, *y = nullptr;
-    cplx *Xf = nullptr, *Wf = nullptr, *Yf = nullptr;
-    cplx *wtab = nullptr, *circle = nullptr;   // ols_wave_kernel: pair filters at the lanes' bins, exp(-2 pi i m / 1024)
-    hipfftHandle pf = 0, pw = 0, pi = 0;
-    void release() {
-        if (pf) hipfftDestroy(pf);
-        if (pw) hipfftDestroy(pw);
-        if (pi) hipfftDestroy(pi);
-        pf = pw = pi = 0;
-        hipFree(seg); hipFree(wpad); hipFree(y); hipFree(Xf); hipFree(Wf); hipFree(Yf); hipFree(wtab); hipFree(circle);
-        seg = wpad = y = nullptr; Xf = Wf = Yf = nullptr; wtab = circle = nullptr;
-        C = Nf = 0; nblocks = 0; device = -1;
-    }
+    FftPlan pf, pw, pi;        // (before the buffers: release() lets go of the members in this order)
+    DevMem seg, wpad, y;       // doubles
+    DevMem Xf, Wf, Yf;         // cplx
+    DevMem wtab, circle;       // cplx, ols_wave_kernel: pair filters at the lanes' bins, exp(-2 pi i m / 1024)
+    void release() { *this = DecodeWork(); }
     void ensure(int C_, int64_t nblocks_, int Nf_) {
         int dev = 0;
         HIP_CHECK(hipGetDevice(&dev));
@@ -608,49 +600,54 @@ struct DecodeWork {
         const int Pf = Nf_ / 2 + 1;
         try {
             int nn[1] = {Nf_};
-            HIP_CHECK(hipMalloc(&wpad, sizeof(double) * 2 * C_ * Nf_));
-            HIP_CHECK(hipMalloc(&Wf, sizeof(cplx) * 2 * C_ * Pf));
-            fft_check(hipfftPlanMany(&pw, 1, nn, nullptr, 1, Nf_, nullptr, 1, Pf, HIPFFT_D2Z, 2 * C_), "plan D2Z filters");
+            wpad.alloc(sizeof(double) * 2 * C_ * Nf_);
+            Wf.alloc(sizeof(cplx) * 2 * C_ * Pf);
+            fft_check(hipfftPlanMany(pw.fresh(), 1, nn, nullptr, 1, Nf_, nullptr, 1, Pf, HIPFFT_D2Z, 2 * C_), "plan D2Z filters");
             if (Nf_ == WF_N && nblocks_ == 0) {
-                HIP_CHECK(hipMalloc(&wtab, sizeof(cplx) * (size_t)((C_ + 1) / 2) * 16 * 2 * 64));
-                HIP_CHECK(hipMalloc(&circle, sizeof(cplx) * WF_N));
-                launch_twiddles(WF_N, circle, nullptr);
+                wtab.alloc(sizeof(cplx) * (size_t)((C_ + 1) / 2) * 16 * 2 * 64);
+                circle.alloc(sizeof(cplx) * WF_N);
+                launch_twiddles(WF_N, circle.get<cplx>(), nullptr);
                 HIP_CHECK(hipStreamSynchronize(nullptr));
             }
             if (nblocks_ > 0) {   // (0: the fused kernel keeps the signal side in LDS; only the filter spectra pass through hipFFT)
-                HIP_CHECK(hipMalloc(&seg, sizeof(double) * C_ * nblocks_ * Nf_));
-                HIP_CHECK(hipMalloc(&y, sizeof(double) * 2 * nblocks_ * Nf_));
-                HIP_CHECK(hipMalloc(&Xf, sizeof(cplx) * C_ * nblocks_ * Pf));
-                HIP_CHECK(hipMalloc(&Yf, sizeof(cplx) * 2 * nblocks_ * Pf));
-                fft_check(hipfftPlanMany(&pf, 1, nn, nullptr, 1, Nf_, nullptr, 1, Pf, HIPFFT_D2Z, (int)(C_ * nblocks_)), "plan D2Z signal");
-                fft_check(hipfftPlanMany(&pi, 1, nn, nullptr, 1, Pf, nullptr, 1, Nf_, HIPFFT_Z2D, (int)(2 * nblocks_)), "plan Z2D");
+                seg.alloc(sizeof(double) * C_ * nblocks_ * Nf_);
+                y.alloc(sizeof(double) * 2 * nblocks_ * Nf_);
+                Xf.alloc(sizeof(cplx) * C_ * nblocks_ * Pf);
+                Yf.alloc(sizeof(cplx) * 2 * nblocks_ * Pf);
+                fft_check(hipfftPlanMany(pf.fresh(), 1, nn, nullptr, 1, Nf_, nullptr, 1, Pf, HIPFFT_D2Z, (int)(C_ * nblocks_)), "plan D2Z signal");
+                fft_check(hipfftPlanMany(pi.fresh(), 1, nn, nullptr, 1, Pf, nullptr, 1, Nf_, HIPFFT_Z2D, (int)(2 * nblocks_)), "plan Z2D");
             }
         } catch (...) { release(); throw; }
         C = C_; nblocks = nblocks_; Nf = Nf_; device = dev;
     }
 };
-std::mutex g_decode_mu;
 // two shapes are kept: a render with a source signal alternates between the decode of the SH signal and the one-channel
-// convolution of its response (emagls_binaural_decode_render), and re-planning hipFFT at every call would cost more than both
-DecodeWork g_decode[2];
-int g_decode_last = 0;
-DecodeWork& decode_work(int C, int64_t nblocks, int Nf) {   // (g_decode_mu held)
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    for (int i = 0; i < 2; ++i) {
-        DecodeWork& w = g_decode[i];
-        if (w.C == C && w.nblocks == nblocks && w.Nf == Nf && w.device == dev) { g_decode_last = i; return w; }
+// convolution of its response (emagls_binaural_decode_render), and re-planning hipFFT at every call would cost more than both.
+// Never destroyed (device_mem.hpp): only decode_cache_clear() releases the slots
+struct DecodeCache {
+    std::mutex mu;
+    DecodeWork slot[2];
+    int last = 0;
+    static DecodeCache& get() { static DecodeCache* p = new DecodeCache; return *p; }
+    DecodeWork& work(int C, int64_t nblocks, int Nf) {   // (mu held)
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        for (int i = 0; i < 2; ++i) {
+            DecodeWork& w = slot[i];
+            if (w.C == C && w.nblocks == nblocks && w.Nf == Nf && w.device == dev) { last = i; return w; }
+        }
+        last ^= 1;   // the least recently used slot
+        slot[last].ensure(C, nblocks, Nf);
+        return slot[last];
     }
-    g_decode_last ^= 1;   // the least recently used slot
-    g_decode[g_decode_last].ensure(C, nblocks, Nf);
-    return g_decode[g_decode_last];
-}
+};
 }  // namespace
 
 void decode_cache_clear() {
-    std::lock_guard<std::mutex> lk(g_decode_mu);
-    g_decode[0].release();
-    g_decode[1].release();
+    DecodeCache& c = DecodeCache::get();
+    std::lock_guard<std::mutex> lk(c.mu);
+    c.slot[0].release();
+    c.slot[1].release();
 }
 
 // true when binaural_decode_real takes the wave-private transforms for filters of `len` taps (ols_wave_kernel): the complex render
@@ -669,17 +666,19 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
         while (Nf < 2 * len) { Nf <<= 1; ++log2n; }
         const int64_t B = Nf - (len - 1);
         const int64_t nblocks = ceil_div(n, B);
-        std::lock_guard<std::mutex> lk(g_decode_mu);
-        DecodeWork& w = decode_work(C, 0, Nf);
+        std::lock_guard<std::mutex> lk(DecodeCache::get().mu);
+        DecodeWork& w = DecodeCache::get().work(C, 0, Nf);
+        double* const wpad = w.wpad.get<double>();
+        cplx *const Wf = w.Wf.get<cplx>(), *const wtab = w.wtab.get<cplx>(), *const circle = w.circle.get<cplx>();
         const bool use_rr = sw_on<Sw::DECODE_REGFFT>();
         const bool wave_form = use_rr && Nf == WF_N && sw_on<Sw::DECODE_WAVE>();
         // EMAGLS_DECODE_FILTER_FFT=hipfft: the filter side of the wave form through hipFFT + ols_wave_tables_kernel
         const bool own_filter_side = wave_form && !sw_on<Sw::DECODE_FILTER_FFT>();
         if (!own_filter_side) {
             fft_check(hipfftSetStream(w.pw, st), "set stream");
-            ols_padfilt_kernel<<<256, 256, 0, st>>>(wL, wR, C, len, Nf, w.wpad);
+            ols_padfilt_kernel<<<256, 256, 0, st>>>(wL, wR, C, len, Nf, wpad);
             KERNEL_CHECK();
-            fft_check(hipfftExecD2Z(w.pw, w.wpad, (hipfftDoubleComplex*)w.Wf), "exec D2Z filters");
+            fft_check(hipfftExecD2Z(w.pw, wpad, (hipfftDoubleComplex*)Wf), "exec D2Z filters");
         }
         if (wave_form) {   // wave-private transforms
             static thread_local int ncu_w = 0;   // (per calling thread: one device query instead of one per call)
@@ -689,8 +688,8 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
                 HIP_CHECK(hipDeviceGetAttribute(&ncu_w, hipDeviceAttributeMultiprocessorCount, dev_w));
             }
             const int npairs = (C + 1) / 2;
-            if (own_filter_side) ols_wave_filter_kernel<<<npairs, 128, 0, st>>>(wL, wR, C, len, sigc ? 1 : 0, w.circle, w.wtab);
-            else ols_wave_tables_kernel<<<(unsigned)ceil_div((int64_t)npairs * 2048, 256), 256, 0, st>>>(w.Wf, C, sigc ? 1 : 0, w.wtab);
+            if (own_filter_side) ols_wave_filter_kernel<<<npairs, 128, 0, st>>>(wL, wR, C, len, sigc ? 1 : 0, circle, wtab);
+            else ols_wave_tables_kernel<<<(unsigned)ceil_div((int64_t)npairs * 2048, 256), 256, 0, st>>>(Wf, C, sigc ? 1 : 0, wtab);
             KERNEL_CHECK();
             const size_t dyn_w = sizeof(cplx) * (WF_TABLES + (size_t)OLSW_WAVES * WF_BUF);
             static PerDeviceOnce wave_once;
@@ -702,7 +701,7 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
             }
             // waves per block: as few as still give every CU a workgroup (8 / G blocks per workgroup)
             const int64_t cu = ncu_w;
-#define EMAGLS_OLSW_GO(G_) ols_wave_kernel<G_><<<(unsigned)ceil_div(nblocks, OLSW_WAVES / G_), 64 * OLSW_WAVES, dyn_w, st>>>(sig, sigc, n, C, w.wtab, w.circle, len, B, nblocks, out)
+#define EMAGLS_OLSW_GO(G_) ols_wave_kernel<G_><<<(unsigned)ceil_div(nblocks, OLSW_WAVES / G_), 64 * OLSW_WAVES, dyn_w, st>>>(sig, sigc, n, C, wtab, circle, len, B, nblocks, out)
             if (nblocks >= 8 * cu) EMAGLS_OLSW_GO(1);
             else if (nblocks >= 4 * cu) EMAGLS_OLSW_GO(2);
             else if (nblocks >= 2 * cu) EMAGLS_OLSW_GO(4);
@@ -729,8 +728,8 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
 #undef EMAGLS_RR_ATTR
             }
             const dim3 grid_rr((unsigned)nblocks);
-#define EMAGLS_RR_GO(A, B_) do { if (wide_blocks) ols_fused_rr_kernel<A, B_, 256><<<grid_rr, 256, dyn_rr, st>>>(sig, n, C, w.Wf, len, B, out); \
-                                 else ols_fused_rr_kernel<A, B_, 128><<<grid_rr, 128, dyn_rr, st>>>(sig, n, C, w.Wf, len, B, out); } while (0)
+#define EMAGLS_RR_GO(A, B_) do { if (wide_blocks) ols_fused_rr_kernel<A, B_, 256><<<grid_rr, 256, dyn_rr, st>>>(sig, n, C, Wf, len, B, out); \
+                                 else ols_fused_rr_kernel<A, B_, 128><<<grid_rr, 128, dyn_rr, st>>>(sig, n, C, Wf, len, B, out); } while (0)
             if (Nf == 1024) EMAGLS_RR_GO(32, 32); else if (Nf == 512) EMAGLS_RR_GO(16, 32); else EMAGLS_RR_GO(16, 16);
 #undef EMAGLS_RR_GO
             KERNEL_CHECK();
@@ -746,9 +745,9 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
             HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ols_fused_kernel<5, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
         }
         const dim3 grid((unsigned)nblocks);
-        if (ntp == 4) ols_fused_kernel<2, 4><<<grid, OLSF_NT, dyn, st>>>(sig, n, C, w.Wf, len, Nf, log2n, B, out);
-        else if (ntp == 2) ols_fused_kernel<3, 2><<<grid, OLSF_NT, dyn, st>>>(sig, n, C, w.Wf, len, Nf, log2n, B, out);
-        else ols_fused_kernel<5, 1><<<grid, OLSF_NT, dyn, st>>>(sig, n, C, w.Wf, len, Nf, log2n, B, out);
+        if (ntp == 4) ols_fused_kernel<2, 4><<<grid, OLSF_NT, dyn, st>>>(sig, n, C, Wf, len, Nf, log2n, B, out);
+        else if (ntp == 2) ols_fused_kernel<3, 2><<<grid, OLSF_NT, dyn, st>>>(sig, n, C, Wf, len, Nf, log2n, B, out);
+        else ols_fused_kernel<5, 1><<<grid, OLSF_NT, dyn, st>>>(sig, n, C, Wf, len, Nf, log2n, B, out);
         KERNEL_CHECK();
         HIP_CHECK(hipStreamSynchronize(st));
         return;
@@ -758,21 +757,23 @@ void binaural_decode_real(const double* sig, int64_t n, int C, const double* wL,
     const int64_t B = Nf - (len - 1);
     const int64_t nblocks = ceil_div(n, B);
     const int Pf = Nf / 2 + 1;
-    std::lock_guard<std::mutex> lk(g_decode_mu);
-    DecodeWork& w = decode_work(C, nblocks, Nf);
+    std::lock_guard<std::mutex> lk(DecodeCache::get().mu);
+    DecodeWork& w = DecodeCache::get().work(C, nblocks, Nf);
+    double *const seg = w.seg.get<double>(), *const wpad = w.wpad.get<double>(), *const y = w.y.get<double>();
+    cplx *const Xf = w.Xf.get<cplx>(), *const Wf = w.Wf.get<cplx>(), *const Yf = w.Yf.get<cplx>();
     fft_check(hipfftSetStream(w.pf, st), "set stream");
     fft_check(hipfftSetStream(w.pw, st), "set stream");
     fft_check(hipfftSetStream(w.pi, st), "set stream");
-    ols_pack_kernel<<<2048, 256, 0, st>>>(sig, n, C, nblocks, Nf, B, len, w.seg);
+    ols_pack_kernel<<<2048, 256, 0, st>>>(sig, n, C, nblocks, Nf, B, len, seg);
     KERNEL_CHECK();
-    ols_padfilt_kernel<<<256, 256, 0, st>>>(wL, wR, C, len, Nf, w.wpad);
+    ols_padfilt_kernel<<<256, 256, 0, st>>>(wL, wR, C, len, Nf, wpad);
     KERNEL_CHECK();
-    fft_check(hipfftExecD2Z(w.pf, w.seg, (hipfftDoubleComplex*)w.Xf), "exec D2Z signal");
-    fft_check(hipfftExecD2Z(w.pw, w.wpad, (hipfftDoubleComplex*)w.Wf), "exec D2Z filters");
-    ols_mac_kernel<<<2048, 256, 0, st>>>(w.Xf, w.Wf, C, nblocks, Pf, w.Yf);
+    fft_check(hipfftExecD2Z(w.pf, seg, (hipfftDoubleComplex*)Xf), "exec D2Z signal");
+    fft_check(hipfftExecD2Z(w.pw, wpad, (hipfftDoubleComplex*)Wf), "exec D2Z filters");
+    ols_mac_kernel<<<2048, 256, 0, st>>>(Xf, Wf, C, nblocks, Pf, Yf);
     KERNEL_CHECK();
-    fft_check(hipfftExecZ2D(w.pi, (hipfftDoubleComplex*)w.Yf, w.y), "exec Z2D");
-    ols_unpack_kernel<<<2048, 256, 0, st>>>(w.y, n, nblocks, Nf, B, len, out);
+    fft_check(hipfftExecZ2D(w.pi, (hipfftDoubleComplex*)Yf, y), "exec Z2D");
+    ols_unpack_kernel<<<2048, 256, 0, st>>>(y, n, nblocks, Nf, B, len, out);
     KERNEL_CHECK();
     HIP_CHECK(hipStreamSynchronize(st));
 }
@@ -860,42 +861,30 @@ void filter_channels_by_order(const double* sig, int64_t n_in, int64_t n, int C,
     const int64_t B = Nf - (len - 1);
     const int64_t nblocks = ceil_div(n, B);
     const int Pf = Nf / 2 + 1;
-    double *seg = nullptr, *wpad = nullptr;
-    cplx *Xf = nullptr, *Wf = nullptr;
-    hipfftHandle pf = 0, pw = 0, pi = 0;
-    auto cleanup = [&] {
-        if (pf) hipfftDestroy(pf);
-        if (pw) hipfftDestroy(pw);
-        if (pi) hipfftDestroy(pi);
-        hipFree(seg); hipFree(wpad); hipFree(Xf); hipFree(Wf);
-    };
-    try {
-        HIP_CHECK(hipMalloc(&seg, sizeof(double) * C * nblocks * Nf));
-        HIP_CHECK(hipMalloc(&wpad, sizeof(double) * nOrd * Nf));
-        HIP_CHECK(hipMalloc(&Xf, sizeof(cplx) * C * nblocks * Pf));
-        HIP_CHECK(hipMalloc(&Wf, sizeof(cplx) * nOrd * Pf));
-        int nn[1] = {Nf};
-        fft_check(hipfftPlanMany(&pf, 1, nn, nullptr, 1, Nf, nullptr, 1, Pf, HIPFFT_D2Z, (int)(C * nblocks)), "plan D2Z signal");
-        fft_check(hipfftPlanMany(&pw, 1, nn, nullptr, 1, Nf, nullptr, 1, Pf, HIPFFT_D2Z, nOrd), "plan D2Z filters");
-        fft_check(hipfftPlanMany(&pi, 1, nn, nullptr, 1, Pf, nullptr, 1, Nf, HIPFFT_Z2D, (int)(C * nblocks)), "plan Z2D");
-        fft_check(hipfftSetStream(pf, st), "set stream");
-        fft_check(hipfftSetStream(pw, st), "set stream");
-        fft_check(hipfftSetStream(pi, st), "set stream");
-        // (ols_pack_kernel reads in[c*n + src] for src < n: the channel stride is the true length, the padding comes from the bound)
-        ols_pack_kernel<<<2048, 256, 0, st>>>(sig, n_in, C, nblocks, Nf, B, len, seg);
-        KERNEL_CHECK();
-        olsc_padfilt_kernel<<<64, 256, 0, st>>>(ir, nOrd, len, Nf, wpad);
-        KERNEL_CHECK();
-        fft_check(hipfftExecD2Z(pf, seg, (hipfftDoubleComplex*)Xf), "exec D2Z signal");
-        fft_check(hipfftExecD2Z(pw, wpad, (hipfftDoubleComplex*)Wf), "exec D2Z filters");
-        olsc_mul_kernel<<<2048, 256, 0, st>>>(Xf, Wf, C, nblocks, Pf);
-        KERNEL_CHECK();
-        fft_check(hipfftExecZ2D(pi, (hipfftDoubleComplex*)Xf, seg), "exec Z2D");
-        olsc_unpack_kernel<<<2048, 256, 0, st>>>(seg, n, C, nblocks, Nf, B, len, skip, out);
-        KERNEL_CHECK();
-        HIP_CHECK(hipStreamSynchronize(st));
-    } catch (...) { cleanup(); throw; }
-    cleanup();
+    DevMem m_seg(sizeof(double) * C * nblocks * Nf), m_wpad(sizeof(double) * nOrd * Nf), m_Xf(sizeof(cplx) * C * nblocks * Pf), m_Wf(sizeof(cplx) * nOrd * Pf);
+    double *const seg = m_seg.get<double>(), *const wpad = m_wpad.get<double>();
+    cplx *const Xf = m_Xf.get<cplx>(), *const Wf = m_Wf.get<cplx>();
+    FftPlan pf, pw, pi;   // (after the buffers: destroyed before them)
+    int nn[1] = {Nf};
+    fft_check(hipfftPlanMany(pf.fresh(), 1, nn, nullptr, 1, Nf, nullptr, 1, Pf, HIPFFT_D2Z, (int)(C * nblocks)), "plan D2Z signal");
+    fft_check(hipfftPlanMany(pw.fresh(), 1, nn, nullptr, 1, Nf, nullptr, 1, Pf, HIPFFT_D2Z, nOrd), "plan D2Z filters");
+    fft_check(hipfftPlanMany(pi.fresh(), 1, nn, nullptr, 1, Pf, nullptr, 1, Nf, HIPFFT_Z2D, (int)(C * nblocks)), "plan Z2D");
+    fft_check(hipfftSetStream(pf, st), "set stream");
+    fft_check(hipfftSetStream(pw, st), "set stream");
+    fft_check(hipfftSetStream(pi, st), "set stream");
+    // (ols_pack_kernel reads in[c*n + src] for src < n: the channel stride is the true length, the padding comes from the bound)
+    ols_pack_kernel<<<2048, 256, 0, st>>>(sig, n_in, C, nblocks, Nf, B, len, seg);
+    KERNEL_CHECK();
+    olsc_padfilt_kernel<<<64, 256, 0, st>>>(ir, nOrd, len, Nf, wpad);
+    KERNEL_CHECK();
+    fft_check(hipfftExecD2Z(pf, seg, (hipfftDoubleComplex*)Xf), "exec D2Z signal");
+    fft_check(hipfftExecD2Z(pw, wpad, (hipfftDoubleComplex*)Wf), "exec D2Z filters");
+    olsc_mul_kernel<<<2048, 256, 0, st>>>(Xf, Wf, C, nblocks, Pf);
+    KERNEL_CHECK();
+    fft_check(hipfftExecZ2D(pi, (hipfftDoubleComplex*)Xf, seg), "exec Z2D");
+    olsc_unpack_kernel<<<2048, 256, 0, st>>>(seg, n, C, nblocks, Nf, B, len, skip, out);
+    KERNEL_CHECK();
+    HIP_CHECK(hipStreamSynchronize(st));
 }
 
 }  // namespace emagls

@@ -1,7 +1,8 @@
 // C ABI of binauralDecode, the SH rotations and the resampler (include/emagls.h: emagls_binaural_decode*, emagls_rotate_yaw,
 // emagls_rotate_sh, emagls_sh_rotation_matrix, emagls_resample*, emagls_decode_stream_*, emagls_decode_group_*): the argument check, host staging, the work buffers and the
 // choice of kernels, once for the whole family.  The kernels are decode.hip's, decode_stream.hip's, rotate.hip's, rotate3.hip's and
-// resample.hip's.
+// resample.hip's.  The stream and the group stand on the host skeleton they share with the field stream (BlockStreamObject,
+// block_stream.hpp); one-call scratch and the work buffers are device_mem.hpp's owners.
 // No CPU fallback.
 #include <algorithm>
 #include <initializer_list>
@@ -10,7 +11,7 @@
 #include <vector>
 
 #include "../../include/emagls.h"
-#include "kernels.hpp"
+#include "block_stream.hpp"
 
 using namespace emagls;
 
@@ -30,53 +31,31 @@ struct Angles {
     bool fixed() const { return n_yaw <= 1 && n_pitch <= 1 && n_roll <= 1; }
 };
 
-struct Scratch {   // device buffers and a pool stream of one host call, freed on every exit path
-    std::vector<void*> ptrs;
-    hipStream_t st = nullptr;
-    Scratch() { st = pool_stream_take(); }
-    ~Scratch() {
-        for (void* p : ptrs) hipFree(p);
-        pool_stream_give(st);
-    }
-    template <typename T = void> T* get(size_t bytes) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, bytes ? bytes : 16));
-        ptrs.push_back(p);
-        return reinterpret_cast<T*>(p);
-    }
-    template <typename T> const T* put(const T* host, size_t count) {   // a device copy of host[count]; null for none
-        if (!host || !count) return nullptr;
-        T* p = get<T>(sizeof(T) * count);
-        HIP_CHECK(hipMemcpyAsync(p, host, sizeof(T) * count, hipMemcpyDefault, st));
-        return p;
-    }
-    Angles put(const Angles& a) {
-        return {put(a.yaw, (size_t)a.n_yaw), a.n_yaw, put(a.pitch, (size_t)a.n_pitch), a.n_pitch, put(a.roll, (size_t)a.n_roll), a.n_roll};
-    }
-};
+Angles put_angles(Scratch& s, const Angles& a) {   // device copies of the angle arrays that are there
+    return {s.put_opt(a.yaw, (size_t)a.n_yaw), a.n_yaw, s.put_opt(a.pitch, (size_t)a.n_pitch), a.n_pitch, s.put_opt(a.roll, (size_t)a.n_roll), a.n_roll};
+}
 
 // work buffers of the device-resident body, grown on demand and kept (released by decode_family_cache_clear); one decode at a
-// time per process, like decode.hip's plans
+// time per process, like decode.hip's plans.  Never destroyed (device_mem.hpp)
 struct Work {
     enum { RS_SIG, RS_WL, RS_WR, ROT_SIG, ROT_WL, ROT_WR, SIG2, W2L, W2R, TMP, IR, YIM, NBUF };
     std::mutex mu;
     int device = -1;
-    void* p[NBUF] = {};
-    size_t cap[NBUF] = {};
+    DevMem buf[NBUF];
+    static Work& instance() { static Work* p = new Work; return *p; }
     void release() {
-        for (int i = 0; i < NBUF; ++i) { hipFree(p[i]); p[i] = nullptr; cap[i] = 0; }
+        for (DevMem& m : buf) m.reset();
         device = -1;
     }
     template <typename T = void> T* get(int i, size_t bytes) {
         int dev = 0;
         HIP_CHECK(hipGetDevice(&dev));
         if (dev != device) { release(); device = dev; }
-        bytes = std::max<size_t>(bytes, 16);
-        if (bytes > cap[i]) { hipFree(p[i]); p[i] = nullptr; cap[i] = 0; HIP_CHECK(hipMalloc(&p[i], bytes)); cap[i] = bytes; }
-        return reinterpret_cast<T*>(p[i]);
+        buf[i].grow(bytes);
+        return buf[i].get<T>();
     }
 };
-Work g_work;
+Work& g_work = Work::instance();
 
 // A sample-rate conversion of dependencies/binauralDecode.m:12-23, MATLAB's resample(x, p, q) with p / q reduced by their gcd
 struct Ratio {
@@ -293,7 +272,7 @@ int host_decode(const void* in, bool ic, int64_t nsamp, int64_t nch, const void*
         const void* d_wL = s.put((const char*)wL, esz(wc) * (size_t)len * nch);
         const void* d_wR = s.put((const char*)wR, esz(wc) * (size_t)len * nch);
         double* d_out = s.get<double>(sizeof(double) * 2 * nout);
-        decode_body(d_in, ic, nsamp, (int)nch, d_wL, d_wR, wc, len, layout, basis == EMAGLS_BASIS_COMPLEX, s.put(a), s.put(signal, (size_t)nsig),
+        decode_body(d_in, ic, nsamp, (int)nch, d_wL, d_wR, wc, len, layout, basis == EMAGLS_BASIS_COMPLEX, put_angles(s, a), s.put_opt(signal, (size_t)nsig),
                     nsig, cut, d_out, imag_abs_sum, s.st, rf, rs);
         if (rows > 0) {
             HIP_CHECK(hipMemcpyAsync(out, d_out + cut, sizeof(double) * rows, hipMemcpyDefault, s.st));
@@ -313,7 +292,7 @@ int host_rotate(const void* in, bool ic, int64_t nsamp, int64_t nch, int layout,
         Scratch s;
         const void* d_in = s.put((const char*)in, esz(ic) * (size_t)nsamp * nch);
         void* d_out = s.get(bout);
-        launch_rotation(s.put(a), d_in, ic, nsamp, (int)nch, layout, cb, false, d_out, s.st);
+        launch_rotation(put_angles(s, a), d_in, ic, nsamp, (int)nch, layout, cb, false, d_out, s.st);
         HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDefault, s.st));
         HIP_CHECK(hipStreamSynchronize(s.st));
     });
@@ -496,21 +475,18 @@ int emagls_sh_rotation_matrix(int order, int basis, double yaw, double pitch, do
 // d.L == 1; emagls_decode_group is the ABI's second name for it, and the two sets of entry points differ in the wording of
 // some errors (Kind) and in nothing else.  The object owns its device buffers: emagls_cache_clear() does not reach them.
 // ---------------------------------------------------------------------------------------------
-struct emagls_decode_stream {
-    std::mutex mu;
+struct emagls_decode_stream : BlockStreamObject<emagls_decode_stream, 4> {   // stage: the push's input, angles, output and set indices
     int64_t nch = 0, len = 0;
     int layout = 0, basis = 0;
     bool in_c = false;            // the signal the rotation and the filters meet is complex (an encoded stream: its encoder is)
     int64_t nmics = 0;            // an encoded stream: the microphones of a pushed block; 0: blocks are SH / CH
     std::vector<double> enc_host; // [nch][nmics] row-major, interleaved complex when in_c
-    double* enc = nullptr;        // its device copy, owned like the spectra
-    int device = -1;              // bound at the first use of the device (creation, when there is one)
-    bool ready = false;
     std::vector<double> wpl;      // [S][2][Cp][len] the real filter planes [re w; -im w], until the device has their spectra
-    DecodeStreamState d;
-    void* xrot = nullptr;         // [L][nch][B] the rotated block of every listener (cplx when the signal or the basis is complex)
-    void* stage[4] = {};          // host entry: the push's input, angles, output and set indices on the device, grown on demand and kept
-    size_t stage_cap[4] = {};
+    DecodeStreamState d;          // the launchers' view of mem
+    // xrot [L][nch][B]: the rotated block of every listener (cplx when the signal or the basis is complex); enc: enc_host's device copy
+    struct Mem { DevMem Wf, ring, hist, pos, xrot, enc; } mem;
+    void* xrot = nullptr;
+    double* enc = nullptr;
     int known[2] = {-1, -1};      // d.L == 1: what the host knows of the selection state on the device: the set indices of the two
                                   // previous blocks, -1: none yet, -2: not known (a push took its indices from device memory)
     int cp() const { return d.planes2 ? 2 * d.C : d.C; }
@@ -526,11 +502,9 @@ struct emagls_decode_stream {
     // once, whatever the number of listeners:
     size_t filter_bytes() const { return sizeof(cplx) * (size_t)d.S * 2 * (size_t)d.P * cp() * (d.B + 1) + enc_bytes(); }
     size_t spectra_bytes() const { return filter_bytes() - enc_bytes(); }
-    void release() {
-        hipFree(d.Wf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos); hipFree(xrot); hipFree(enc);
-        for (void*& p : stage) { hipFree(p); p = nullptr; }
-        d.Wf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr; xrot = nullptr; enc = nullptr;
-        ready = false;
+    void bind() {
+        d.Wf = mem.Wf.get<cplx>(); d.ring = mem.ring.get<cplx>(); d.hist = mem.hist.get(); d.pos = mem.pos.get<int>();
+        xrot = mem.xrot.get(); enc = mem.enc.get<double>();
     }
     // the listeners first .. first + count - 1 back to a fresh stream's state
     void zero_state(hipStream_t st, int64_t first, int64_t count) {
@@ -542,33 +516,24 @@ struct emagls_decode_stream {
         if (d.S > 1) HIP_CHECK(hipMemset2DAsync(pos + sizeof(int), pb, 0xff, 2 * sizeof(int), n, st));   // -1: no block yet
         known[0] = known[1] = -1;
     }
-    // the device side, once: buffers, the partition spectra, zero history (mu held)
-    void ensure_device() {
-        if (ready) return;
-        HIP_CHECK(hipGetDevice(&device));
-        try {
-            HIP_CHECK(hipMalloc(&d.Wf, spectra_bytes()));
-            HIP_CHECK(hipMalloc(&d.ring, d.L * ring_bytes()));
-            HIP_CHECK(hipMalloc(&d.hist, d.L * hist_bytes()));
-            HIP_CHECK(hipMalloc(&d.pos, d.L * pos_bytes()));
-            HIP_CHECK(hipMalloc(&xrot, esz(d.planes2) * (size_t)d.L * d.C * d.B));   // (a rotated block is complex exactly when planes2)
-            Scratch s;
-            if (nmics) {
-                HIP_CHECK(hipMalloc(&enc, enc_bytes()));
-                HIP_CHECK(hipMemcpyAsync(enc, enc_host.data(), enc_bytes(), hipMemcpyHostToDevice, s.st));
-            }
-            launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.S, d.Wf, s.st);
-            zero_state(s.st, 0, d.L);
-            HIP_CHECK(hipStreamSynchronize(s.st));
-        } catch (...) { release(); device = -1; throw; }
+    void build_device() {
+        mem.Wf.alloc(spectra_bytes());
+        mem.ring.alloc(d.L * ring_bytes());
+        mem.hist.alloc(d.L * hist_bytes());
+        mem.pos.alloc(d.L * pos_bytes());
+        mem.xrot.alloc(esz(d.planes2) * (size_t)d.L * d.C * d.B);   // (a rotated block is complex exactly when planes2)
+        Scratch s;
+        if (nmics) {
+            mem.enc.alloc(enc_bytes());
+            HIP_CHECK(hipMemcpyAsync(mem.enc.get(), enc_host.data(), enc_bytes(), hipMemcpyHostToDevice, s.st));
+        }
+        bind();
+        launch_decode_stream_filters(s.put(wpl.data(), wpl.size()), cp(), len, d.B, d.P, d.S, d.Wf, s.st);
+        zero_state(s.st, 0, d.L);
+        s.sync();
         wpl = std::vector<double>();
-        ready = true;
     }
-    template <typename T> T* staged(int i, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        if (bytes > stage_cap[i]) { hipFree(stage[i]); stage[i] = nullptr; stage_cap[i] = 0; HIP_CHECK(hipMalloc(&stage[i], bytes)); stage_cap[i] = bytes; }
-        return reinterpret_cast<T*>(stage[i]);
-    }
+    void drop_device() { mem = Mem(); bind(); }
 };
 
 namespace {
@@ -669,9 +634,7 @@ int device_push(const Kind& k, emagls_decode_stream* s, const void* d_in, int64_
     return guarded_call([&] {
         const Push p = check_push(k, s, d_in, d_out, nsamp, a, sets);
         if (nsamp == 0) return;
-        std::lock_guard<std::mutex> lk(s->mu);
-        DeviceGuard dg(s->device);
-        push_blocks(s, d_in, nsamp, p, sets, d_out, (hipStream_t)stream);
+        s->device_frame([&] { push_blocks(s, d_in, nsamp, p, sets, d_out, (hipStream_t)stream); });
     });
 }
 
@@ -686,33 +649,29 @@ int host_push(const Kind& k, emagls_decode_stream* s, const void* in, int64_t ns
         for (int64_t i = 0; i < n_set; ++i)
             if (set[i] < 0 || set[i] >= s->d.S) throw Error(EMAGLS_ERR_ARG, k.outside_bank);
         if (nsamp == 0) return;
-        std::lock_guard<std::mutex> lk(s->mu);
-        DeviceGuard dg(s->device);
-        s->ensure_device();
-        hipStream_t st = pool_stream_take();
-        struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
-        const size_t L = (size_t)s->d.L, bin = esz(s->block_c()) * (size_t)nsamp * s->block_cols();
-        char* d_in = s->staged<char>(0, bin);
-        double* d_ang = s->staged<double>(1, sizeof(double) * 3 * L * (size_t)nsamp);
-        double* d_out = s->staged<double>(2, sizeof(double) * 2 * L * (size_t)nsamp);
-        HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
-        auto up = [&](const double* q, int64_t n, int slot) -> const double* {
-            if (!n) return nullptr;
-            double* dst = d_ang + (size_t)slot * L * nsamp;
-            HIP_CHECK(hipMemcpyAsync(dst, q, sizeof(double) * n, hipMemcpyHostToDevice, st));
-            return dst;
-        };
-        Push dp = p;
-        dp.one.yaw = up(a.yaw, a.n_yaw, 0); dp.one.pitch = up(a.pitch, a.n_pitch, 1); dp.one.roll = up(a.roll, a.n_roll, 2);
-        Sets dsets{nullptr, n_set, set};
-        if (n_set) {
-            int32_t* d_set = s->staged<int32_t>(3, sizeof(int32_t) * (size_t)n_set);
-            HIP_CHECK(hipMemcpyAsync(d_set, set, sizeof(int32_t) * (size_t)n_set, hipMemcpyHostToDevice, st));
-            dsets.p = d_set;
-        }
-        push_blocks(s, d_in, nsamp, dp, dsets, d_out, st);
-        HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * L * nsamp, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
+        s->host_frame([&](hipStream_t st) {
+            const size_t L = (size_t)s->d.L, bin = esz(s->block_c()) * (size_t)nsamp * s->block_cols();
+            char* d_in = s->staged<char>(0, bin);
+            double* d_ang = s->staged<double>(1, sizeof(double) * 3 * L * (size_t)nsamp);
+            double* d_out = s->staged<double>(2, sizeof(double) * 2 * L * (size_t)nsamp);
+            HIP_CHECK(hipMemcpyAsync(d_in, in, bin, hipMemcpyHostToDevice, st));
+            auto up = [&](const double* q, int64_t n, int slot) -> const double* {
+                if (!n) return nullptr;
+                double* dst = d_ang + (size_t)slot * L * nsamp;
+                HIP_CHECK(hipMemcpyAsync(dst, q, sizeof(double) * n, hipMemcpyHostToDevice, st));
+                return dst;
+            };
+            Push dp = p;
+            dp.one.yaw = up(a.yaw, a.n_yaw, 0); dp.one.pitch = up(a.pitch, a.n_pitch, 1); dp.one.roll = up(a.roll, a.n_roll, 2);
+            Sets dsets{nullptr, n_set, set};
+            if (n_set) {
+                int32_t* d_set = s->staged<int32_t>(3, sizeof(int32_t) * (size_t)n_set);
+                HIP_CHECK(hipMemcpyAsync(d_set, set, sizeof(int32_t) * (size_t)n_set, hipMemcpyHostToDevice, st));
+                dsets.p = d_set;
+            }
+            push_blocks(s, d_in, nsamp, dp, dsets, d_out, st);
+            HIP_CHECK(hipMemcpyAsync(out, d_out, sizeof(double) * 2 * L * nsamp, hipMemcpyDeviceToHost, st));
+        });
     });
 }
 
@@ -721,13 +680,10 @@ int reset_object(const Kind& k, emagls_decode_stream* s, int64_t listener) {
     return guarded_call([&] {
         if (!s) throw Error(EMAGLS_ERR_ARG, k.null_handle);
         if (listener < -1 || listener >= s->d.L) throw Error(EMAGLS_ERR_ARG, "listener outside the group (-1: all of them)");
-        std::lock_guard<std::mutex> lk(s->mu);
-        DeviceGuard dg(s->device);
-        s->ensure_device();
-        HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
-        if (listener < 0) s->zero_state(nullptr, 0, s->d.L);
-        else s->zero_state(nullptr, listener, 1);
-        HIP_CHECK(hipStreamSynchronize(nullptr));
+        s->reset_frame([&](hipStream_t st) {
+            if (listener < 0) s->zero_state(st, 0, s->d.L);
+            else s->zero_state(st, listener, 1);
+        });
     });
 }
 
@@ -742,21 +698,6 @@ int info_object(const Kind& k, const emagls_decode_stream* s, int64_t* block, in
         if (filter_bytes) *filter_bytes = (int64_t)s->filter_bytes();
         // for all listeners: rotation (encoded: with the encoder, or the encoder alone), forward transform with the products, inverse transform
         if (launches_per_block) *launches_per_block = 3;
-    });
-}
-
-int destroy_object(emagls_decode_stream* s) {
-    return guarded_call([&] {
-        if (!s) return;
-        {
-            std::lock_guard<std::mutex> lk(s->mu);
-            if (s->ready) {
-                DeviceGuard dg(s->device);
-                (void)hipDeviceSynchronize();
-                s->release();
-            }
-        }
-        delete s;
     });
 }
 
@@ -812,13 +753,7 @@ int create_object(bool encoded, int64_t nmics, const void* enc, int64_t nch, int
                         if (wc && s->d.planes2) pl[(size_t)(nch + c) * len + t] = -w[2 * i + 1];
                     }
             }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
-            std::lock_guard<std::mutex> lk(s->mu);
-            s->ensure_device();
-        } else {
-            (void)hipGetLastError();
-        }
+        s->create_device_side();
         *out = s.release();
     });
 }
@@ -912,8 +847,8 @@ int emagls_decode_stream_sets(const emagls_decode_stream* s, int64_t* n_sets) {
     });
 }
 
-int emagls_decode_stream_destroy(emagls_decode_stream* s) { return destroy_object(s); }
+int emagls_decode_stream_destroy(emagls_decode_stream* s) { return emagls_decode_stream::destroy(s); }
 
-int emagls_decode_group_destroy(emagls_decode_group* g) { return destroy_object(object_of(g)); }
+int emagls_decode_group_destroy(emagls_decode_group* g) { return emagls_decode_stream::destroy(object_of(g)); }
 
 }  // extern "C"

@@ -9,7 +9,8 @@
 
 namespace emagls {
 
-using debug::Bufs;
+using debug::copy;
+using debug::filled;
 using debug::fill_sentinel;
 using debug::sentinel;
 
@@ -35,21 +36,21 @@ void factor_debug(const emagls_debug_factor_args& g) {
 
     fill_sentinel(g.Z, 2 * (size_t)nbins * csz);
     if (g.W) fill_sentinel(g.W, 2 * (size_t)2 * P * C);
-    Bufs b;
-    cplx* dZ = b.filled<cplx>(nz, sentinel());
-    cplx* dV = b.filled<cplx>((size_t)nbins * csz, 0.0);
-    double* dtau = b.filled<double>((size_t)nbins * C, 0.0);
-    cplx* dR2 = b.filled<cplx>((size_t)nbins * cc, 0.0);
-    cplx* dN = b.filled<cplx>((size_t)nbins * cc, 0.0);
-    double* dsv = b.filled<double>((size_t)P * C, sentinel());
-    int* dsw = b.get<int>((size_t)P);
+    Scratch b;
+    cplx* dZ = filled<cplx>(b, nz, sentinel());
+    cplx* dV = filled<cplx>(b, (size_t)nbins * csz, 0.0);
+    double* dtau = filled<double>(b, (size_t)nbins * C, 0.0);
+    cplx* dR2 = filled<cplx>(b, (size_t)nbins * cc, 0.0);
+    cplx* dN = filled<cplx>(b, (size_t)nbins * cc, 0.0);
+    double* dsv = filled<double>(b, (size_t)P * C, sentinel());
+    int* dsw = b.get<int>(sizeof(int) * (size_t)P);
     HIP_CHECK(hipMemset(dsw, 0xff, sizeof(int) * (size_t)P));   // -1: no sweep count written
     cplx* Zout = dZ;
     double* svout = dsv;
     int* swout = dsw;
     if (wide) {
         // (the wide forms factor in place: every bin gets a copy of its own)
-        cplx* dB = b.get<cplx>((size_t)nbins * csz);
+        cplx* dB = b.get<cplx>(sizeof(cplx) * (size_t)nbins * csz);
         for (int i = 0; i < nbins; ++i)
             HIP_CHECK(hipMemcpy(dB + (size_t)i * csz, static_cast<const cplx*>(g.Xd) + (size_t)i * g.xd_stride, csz * sizeof(cplx), hipMemcpyHostToDevice));
         launch_wa_factor(dB, dV, S, C, ldS, nbins, g.reg_c, dtau, dR2, dN, dsv, dsw, dZ, nullptr);
@@ -57,23 +58,23 @@ void factor_debug(const emagls_debug_factor_args& g) {
         FactorArgs a{};
         a.S = S; a.C = C; a.ldS = ldS; a.kb0 = kb0; a.P = P;
         if (dense) {
-            a.Xd = b.copy<cplx>(g.Xd, g.xd_stride == 0 ? csz : (size_t)nbins * csz);
+            a.Xd = copy<cplx>(b, g.Xd, g.xd_stride == 0 ? csz : (size_t)nbins * csz);
             a.xd_stride = g.xd_stride;
         } else {
-            a.Tn = g.tn_cplx ? (const void*)b.copy<cplx>(g.Tn, (size_t)g.nOrders * csz) : (const void*)b.copy<double>(g.Tn, (size_t)g.nOrders * csz);
-            a.bn = b.copy<cplx>(g.bn, (size_t)P * g.nOrders);
+            a.Tn = g.tn_cplx ? (const void*)copy<cplx>(b, g.Tn, (size_t)g.nOrders * csz) : (const void*)copy<double>(b, g.Tn, (size_t)g.nOrders * csz);
+            a.bn = copy<cplx>(b, g.bn, (size_t)P * g.nOrders);
             a.nOrders = g.nOrders;
         }
         a.reg_mode = g.reg_mode; a.reg_c = g.reg_c; a.tol_dim = g.tol_dim;
         a.Z = dZ; a.Vws = dV; a.sv = dsv; a.sweeps_out = dsw;
         a.tauw = dtau; a.R2w = dR2; a.Nw = dN;
         if (g.Hq) {
-            cplx* dH = b.filled<cplx>((size_t)2 * P * g.ldHq, 0.0);
+            cplx* dH = filled<cplx>(b, (size_t)2 * P * g.ldHq, 0.0);
             for (int e = 0; e < 2; ++e)
                 HIP_CHECK(hipMemcpy(dH + ((size_t)e * P + kb0) * g.ldHq, static_cast<const cplx*>(g.Hq) + (size_t)e * nbins * g.ldHq,
                                     (size_t)nbins * g.ldHq * sizeof(cplx), hipMemcpyHostToDevice));
             a.Hq = dH; a.ldHq = g.ldHq; a.hq_estride = (int64_t)P * g.ldHq; a.ls_end = g.ls_end; a.hq_conj = g.hq_conj;
-            a.W = b.filled<cplx>((size_t)2 * P * C, sentinel());
+            a.W = filled<cplx>(b, (size_t)2 * P * C, sentinel());
         }
         if (g.phases == 3) launch_factor(a, nbins, g.tn_cplx != 0, nullptr, 3);
         else { launch_factor(a, nbins, g.tn_cplx != 0, nullptr, 1); launch_factor(a, nbins, g.tn_cplx != 0, nullptr, 2); }
@@ -100,21 +101,21 @@ void factor_gram_debug(const void* A, int nbins, int C, const int* route, int jr
         if (route[i] != 1 && route[i] != 2) throw Error(1, "debug factor gram: route[bin] is 1 (Jacobi on A) or 2 (skipped)");
     const size_t cc = (size_t)C * C;
     fill_sentinel(M, 2 * (size_t)nbins * cc);
-    Bufs b;
+    Scratch b;
     FactorArgs fg{};
     fg.S = C; fg.C = C; fg.ldS = (int)(ceil_div(C, 64) * 64); fg.kb0 = 0; fg.P = nbins;
     fg.reg_mode = 0; fg.reg_c = reg_c;
-    fg.sv = b.filled<double>((size_t)nbins * C, sentinel());
-    fg.route = b.copy<int>(route, (size_t)nbins);
-    fg.status = b.get<int>(4);
+    fg.sv = filled<double>(b, (size_t)nbins * C, sentinel());
+    fg.route = copy<int>(b, route, (size_t)nbins);
+    fg.status = b.get<int>(sizeof(int) * 4);
     HIP_CHECK(hipMemset(fg.status, 0, 4 * sizeof(int)));
     fg.cond_limit = cond_limit;
-    fg.sweeps_out = b.get<int>((size_t)nbins);
+    fg.sweeps_out = b.get<int>(sizeof(int) * (size_t)nbins);
     HIP_CHECK(hipMemset(fg.sweeps_out, 0xff, sizeof(int) * (size_t)nbins));   // -1: skipped
-    fg.tauw = b.filled<double>((size_t)nbins * C, 0.0);
-    fg.R2w = b.copy<cplx>(A, (size_t)nbins * cc);
-    fg.Nw = b.filled<cplx>((size_t)nbins * cc, 0.0);
-    fg.Mw = b.filled<cplx>((size_t)nbins * cc, sentinel());
+    fg.tauw = filled<double>(b, (size_t)nbins * C, 0.0);
+    fg.R2w = copy<cplx>(b, A, (size_t)nbins * cc);
+    fg.Nw = filled<cplx>(b, (size_t)nbins * cc, 0.0);
+    fg.Mw = filled<cplx>(b, (size_t)nbins * cc, sentinel());
     fg.jrun = jrun;
     launch_factor_jacobi_gram(fg, nbins, nullptr);
     HIP_CHECK(hipDeviceSynchronize());

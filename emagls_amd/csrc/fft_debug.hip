@@ -11,7 +11,8 @@
 
 namespace emagls {
 
-using debug::Bufs;
+using debug::copy;
+using debug::filled;
 using debug::sentinel;
 
 namespace {
@@ -31,8 +32,8 @@ void check_indices(const int64_t* idx, int64_t n, int64_t bound, const char* wha
 void twiddles_debug(int nfft, void* tw) {
     if (!tw) throw Error(1, "null pointer");
     if (nfft < 2 || nfft > 8192) throw Error(1, "debug twiddles: 2 <= nfft <= 8192");
-    Bufs b;
-    cplx* d_tw = b.filled<cplx>((size_t)nfft, sentinel());
+    Scratch b;
+    cplx* d_tw = filled<cplx>(b, (size_t)nfft, sentinel());
     launch_twiddles(nfft, d_tw, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(tw, d_tw, (size_t)nfft * sizeof(cplx), hipMemcpyDeviceToHost));
@@ -54,12 +55,12 @@ void filter_epilogue_debug(const void* W, int C, int nfft, int len, const double
     if (grpd && (!std::isfinite(grpd[0]) || !std::isfinite(grpd[1]))) throw Error(1, "debug filter epilogue: grpd is finite");
     const int P = nfft / 2 + 1;
     const size_t nout = (size_t)C * len * (out_cplx ? 2 : 1);   // doubles per ear
-    Bufs b;
-    cplx* d_W = b.copy<cplx>(W, (size_t)n_ears * P * C);
-    cplx* d_tw = b.get<cplx>((size_t)nfft);
-    double* d_g = grpd ? b.copy<double>(grpd, 2) : nullptr;
-    double* d_L = b.filled<double>(nout, sentinel());
-    double* d_R = n_ears == 2 ? b.filled<double>(nout, sentinel()) : nullptr;
+    Scratch b;
+    cplx* d_W = copy<cplx>(b, W, (size_t)n_ears * P * C);
+    cplx* d_tw = b.get<cplx>(sizeof(cplx) * (size_t)nfft);
+    double* d_g = grpd ? copy<double>(b, grpd, 2) : nullptr;
+    double* d_L = filled<double>(b, nout, sentinel());
+    double* d_R = n_ears == 2 ? filled<double>(b, nout, sentinel()) : nullptr;
     launch_twiddles(nfft, d_tw, nullptr);
     launch_filter_epilogue(d_W, C, nfft, len, d_tw, d_g, conj_mode, dc_rule, shift_mode, out_cplx, d_L, d_R, nullptr, n_ears, fade_rel);
     HIP_CHECK(hipDeviceSynchronize());
@@ -97,25 +98,25 @@ void hrir_spectra_debug(const double* hL, const double* hR, int64_t L, int64_t D
     const size_t ng = 2 + 4 * (size_t)P;
     const size_t n_hc = spectra ? (size_t)2 * n_c * ldD : 0, n_ha = spectra ? (size_t)2 * (P - kabs0) * ldD : 0, n_t = HcT ? (size_t)D * ldT : 0;
     if (2 * (size_t)D_src * L * sizeof(double) + n_hc * sizeof(cplx) + (n_ha + n_t) * sizeof(double) > kMaxBytes) throw Error(1, "debug hrir spectra: more than 1 GiB of device memory");
-    Bufs b;
-    const double* d_hL = b.copy<double>(hL, (size_t)D_src * L);
-    const double* d_hR = b.copy<double>(hR, (size_t)D_src * L);
-    cplx* d_tw = b.get<cplx>((size_t)nfft);
-    double* d_g = b.filled<double>(ng, sentinel());
+    Scratch b;
+    const double* d_hL = copy<double>(b, hL, (size_t)D_src * L);
+    const double* d_hR = copy<double>(b, hR, (size_t)D_src * L);
+    cplx* d_tw = b.get<cplx>(sizeof(cplx) * (size_t)nfft);
+    double* d_g = filled<double>(b, ng, sentinel());
     launch_twiddles(nfft, d_tw, nullptr);
     if (grpd_in) {
         HIP_CHECK(hipMemcpy(d_g, grpd_in, 2 * sizeof(double), hipMemcpyHostToDevice));
     } else {
-        double* d_part = b.filled<double>((size_t)hrir_dirsum_chunks(D_src) * 2 * L, sentinel());
+        double* d_part = filled<double>(b, (size_t)hrir_dirsum_chunks(D_src) * 2 * L, sentinel());
         launch_hrir_grpdelay(d_hL, d_hR, L, D_src, nfft, d_tw, d_part, d_g, nullptr);
     }
     cplx* d_Hc = nullptr;
     double *d_Ha = nullptr, *d_T = nullptr;
     if (spectra) {
-        const int64_t* d_idx = didx ? b.copy<int64_t>(didx, (size_t)D) : nullptr;
-        d_Hc = b.filled<cplx>(n_hc, sentinel());
-        d_Ha = b.filled<double>(n_ha, sentinel());
-        if (HcT) d_T = b.filled<double>(n_t, sentinel());
+        const int64_t* d_idx = didx ? copy<int64_t>(b, didx, (size_t)D) : nullptr;
+        d_Hc = filled<cplx>(b, n_hc, sentinel());
+        d_Ha = filled<double>(b, n_ha, sentinel());
+        if (HcT) d_T = filled<double>(b, n_t, sentinel());
         launch_hrir_fft(d_hL, d_hR, L, D, d_idx, nfft, d_tw, d_g, mode, n_c, kabs0, d_Hc, d_Ha, ldD, nullptr, d_T, ldT);
     }
     HIP_CHECK(hipDeviceSynchronize());
@@ -140,11 +141,11 @@ void real_spectra_debug(const double* x, int64_t L, int64_t ncols_src, int64_t n
     if (colidx) check_indices(colidx, ncols, ncols_src, "debug real spectra: colidx holds columns of the input, 0 ... ncols_src-1");
     const int P = nfft / 2 + 1;
     if ((size_t)ncols_src * L * sizeof(double) + (size_t)P * ldo * sizeof(cplx) > kMaxBytes) throw Error(1, "debug real spectra: more than 1 GiB of device memory");
-    Bufs b;
-    const double* d_x = b.copy<double>(x, (size_t)ncols_src * L);
-    const int64_t* d_idx = colidx ? b.copy<int64_t>(colidx, (size_t)ncols) : nullptr;
-    cplx* d_tw = b.get<cplx>((size_t)nfft);
-    cplx* d_out = b.filled<cplx>((size_t)P * ldo, sentinel());
+    Scratch b;
+    const double* d_x = copy<double>(b, x, (size_t)ncols_src * L);
+    const int64_t* d_idx = colidx ? copy<int64_t>(b, colidx, (size_t)ncols) : nullptr;
+    cplx* d_tw = b.get<cplx>(sizeof(cplx) * (size_t)nfft);
+    cplx* d_out = filled<cplx>(b, (size_t)P * ldo, sentinel());
     launch_twiddles(nfft, d_tw, nullptr);
     launch_real_fft_gather(d_x, L, ncols, d_idx, nfft, d_tw, d_out, ldo, inner, ld_inner, nullptr);
     HIP_CHECK(hipDeviceSynchronize());

@@ -1,64 +1,45 @@
-// C ABI of the field stream (include/emagls.h: emagls_field_stream_*): the argument check, host staging and
-// the object's buffers, in the style of the decode stream's host side (decode_api.hip).  The kernels are field_stream.hip's and, for
-// the response spectra, decode_stream.hip's.  The object owns its device buffers: emagls_cache_clear() does not reach them.
+// C ABI of the field stream (include/emagls.h: emagls_field_stream_*): the argument check, the shapes, the
+// staging and the launches of the object; the lock, the lazily built device side, the stage buffers and the frames of create, push,
+// reset and destroy are the shared skeleton's (BlockStreamObject, block_stream.hpp).  The kernels are field_stream.hip's and, for the
+// response spectra, decode_stream.hip's.  The object owns its device buffers: emagls_cache_clear() does not reach them.
 // No CPU fallback.
 #include <memory>
-#include <mutex>
 #include <vector>
 
 #include "../../include/emagls.h"
-#include "kernels.hpp"
-#include "scratch.hpp"
+#include "block_stream.hpp"
 
 using namespace emagls;
 
-struct emagls_field_stream {
-    std::mutex mu;
+struct emagls_field_stream : BlockStreamObject<emagls_field_stream, 2> {   // stage: the push's input and output
     int64_t nch = 0, nr = 0;
-    int device = -1;              // bound at the first use of the device (creation, when there is one)
-    bool ready = false;
     std::vector<double> rpl;      // [nsrc][planes][nr] the real response planes, until the device has their spectra
-    FieldStreamState d;
-    void* stage[2] = {};          // host entry: the push's input and output on the device, grown on demand and kept
-    size_t stage_cap[2] = {};
+    FieldStreamState d;           // the launchers' view of mem
+    struct Mem { DevMem Rf, ring, hist, pos; } mem;
     size_t ring_bytes() const { return sizeof(cplx) * (size_t)d.nsrc * d.P * (d.B + 1); }
     size_t hist_bytes() const { return sizeof(double) * (size_t)d.nsrc * d.B; }
     size_t state_bytes() const { return ring_bytes() + hist_bytes() + sizeof(int); }
     size_t response_bytes() const { return sizeof(cplx) * (size_t)d.nsrc * d.P * d.planes * (d.B + 1); }
     size_t out_esz() const { return esz(d.out_c); }
-    void release() {
-        hipFree(d.Rf); hipFree(d.ring); hipFree(d.hist); hipFree(d.pos);
-        for (int i = 0; i < 2; ++i) { hipFree(stage[i]); stage[i] = nullptr; stage_cap[i] = 0; }
-        d.Rf = d.ring = nullptr; d.hist = nullptr; d.pos = nullptr;
-        ready = false;
-    }
+    void bind() { d.Rf = mem.Rf.get<cplx>(); d.ring = mem.ring.get<cplx>(); d.hist = mem.hist.get<double>(); d.pos = mem.pos.get<int>(); }
     void zero_state(hipStream_t st) {
         HIP_CHECK(hipMemsetAsync(d.ring, 0, ring_bytes(), st));
         HIP_CHECK(hipMemsetAsync(d.hist, 0, hist_bytes(), st));
         HIP_CHECK(hipMemsetAsync(d.pos, 0, sizeof(int), st));
     }
-    // the device side, once: buffers, the partition spectra, zero history (mu held)
-    void ensure_device() {
-        if (ready) return;
-        HIP_CHECK(hipGetDevice(&device));
-        try {
-            HIP_CHECK(hipMalloc(&d.Rf, response_bytes()));
-            HIP_CHECK(hipMalloc(&d.ring, ring_bytes()));
-            HIP_CHECK(hipMalloc(&d.hist, hist_bytes()));
-            HIP_CHECK(hipMalloc(&d.pos, sizeof(int)));
-            Scratch s;
-            launch_partition_spectra(s.put(rpl.data(), rpl.size()), d.planes, nr, d.B, d.P, d.nsrc, d.Rf, s.st);
-            zero_state(s.st);
-            s.sync();
-        } catch (...) { release(); device = -1; throw; }
+    void build_device() {
+        mem.Rf.alloc(response_bytes());
+        mem.ring.alloc(ring_bytes());
+        mem.hist.alloc(hist_bytes());
+        mem.pos.alloc(sizeof(int));
+        bind();
+        Scratch s;
+        launch_partition_spectra(s.put(rpl.data(), rpl.size()), d.planes, nr, d.B, d.P, d.nsrc, d.Rf, s.st);
+        zero_state(s.st);
+        s.sync();
         rpl = std::vector<double>();
-        ready = true;
     }
-    template <typename T> T* staged(int i, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        if (bytes > stage_cap[i]) { hipFree(stage[i]); stage[i] = nullptr; stage_cap[i] = 0; HIP_CHECK(hipMalloc(&stage[i], bytes)); stage_cap[i] = bytes; }
-        return reinterpret_cast<T*>(stage[i]);
-    }
+    void drop_device() { mem = Mem(); bind(); }
 };
 
 namespace {
@@ -115,13 +96,7 @@ int emagls_field_stream_create(int64_t nsrc, int64_t nch, const void* rir, int r
                     f->rpl[(2 * col + 1) * nr + t] = r[2 * (col * nr + t) + 1];
                 }
         }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
-            std::lock_guard<std::mutex> lk(f->mu);
-            f->ensure_device();
-        } else {
-            (void)hipGetLastError();
-        }
+        f->create_device_side();
         *out = f.release();
     });
 }
@@ -130,9 +105,7 @@ int emagls_field_stream_push_device(emagls_field_stream* f, const double* d_src,
     return guarded_call([&] {
         check_push(f, d_src, d_out, nsamp);
         if (nsamp == 0) return;
-        std::lock_guard<std::mutex> lk(f->mu);
-        DeviceGuard dg(f->device);
-        push_blocks(f, d_src, nsamp, d_out, (hipStream_t)stream);
+        f->device_frame([&] { push_blocks(f, d_src, nsamp, d_out, (hipStream_t)stream); });
     });
 }
 
@@ -140,30 +113,21 @@ int emagls_field_stream_push(emagls_field_stream* f, const double* src, int64_t 
     return guarded_call([&] {
         check_push(f, src, out, nsamp);
         if (nsamp == 0) return;
-        std::lock_guard<std::mutex> lk(f->mu);
-        DeviceGuard dg(f->device);
-        f->ensure_device();
-        hipStream_t st = pool_stream_take();
-        struct Give { hipStream_t st; ~Give() { pool_stream_give(st); } } give{st};
-        const size_t bin = sizeof(double) * (size_t)nsamp * f->d.nsrc, bout = f->out_esz() * (size_t)nsamp * f->nch;
-        double* d_src = f->staged<double>(0, bin);
-        char* d_out = f->staged<char>(1, bout);
-        HIP_CHECK(hipMemcpyAsync(d_src, src, bin, hipMemcpyHostToDevice, st));
-        push_blocks(f, d_src, nsamp, d_out, st);
-        HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
+        f->host_frame([&](hipStream_t st) {
+            const size_t bin = sizeof(double) * (size_t)nsamp * f->d.nsrc, bout = f->out_esz() * (size_t)nsamp * f->nch;
+            double* d_src = f->staged<double>(0, bin);
+            char* d_out = f->staged<char>(1, bout);
+            HIP_CHECK(hipMemcpyAsync(d_src, src, bin, hipMemcpyHostToDevice, st));
+            push_blocks(f, d_src, nsamp, d_out, st);
+            HIP_CHECK(hipMemcpyAsync(out, d_out, bout, hipMemcpyDeviceToHost, st));
+        });
     });
 }
 
 int emagls_field_stream_reset(emagls_field_stream* f) {
     return guarded_call([&] {
         if (!f) throw Error(EMAGLS_ERR_ARG, "null field stream");
-        std::lock_guard<std::mutex> lk(f->mu);
-        DeviceGuard dg(f->device);
-        f->ensure_device();
-        HIP_CHECK(hipDeviceSynchronize());   // the pushes in flight, on whatever stream
-        f->zero_state(nullptr);
-        HIP_CHECK(hipStreamSynchronize(nullptr));
+        f->reset_frame([&](hipStream_t st) { f->zero_state(st); });
     });
 }
 
@@ -180,18 +144,7 @@ int emagls_field_stream_info(const emagls_field_stream* f, int64_t* block, int64
 }
 
 int emagls_field_stream_destroy(emagls_field_stream* f) {
-    return guarded_call([&] {
-        if (!f) return;
-        {
-            std::lock_guard<std::mutex> lk(f->mu);
-            if (f->ready) {
-                DeviceGuard dg(f->device);
-                (void)hipDeviceSynchronize();
-                f->release();
-            }
-        }
-        delete f;
-    });
+    return emagls_field_stream::destroy(f);
 }
 
 }  // extern "C"

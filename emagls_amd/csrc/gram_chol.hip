@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "kernels.hpp"
+#include "device_mem.hpp"
 
 namespace emagls {
 
@@ -292,17 +292,14 @@ double gram_tile_selftest(bool four) {
             want[(size_t)i * S + j] = acc;
             gmax = std::max(gmax, std::fabs(acc));
         }
-    double *dY = nullptr, *dG = nullptr;
-    HIP_CHECK(hipMalloc(&dY, sizeof(double) * Y.size()));
-    HIP_CHECK(hipMalloc(&dG, sizeof(double) * G.size()));
+    DevMem mY(sizeof(double) * Y.size()), mG(sizeof(double) * G.size());
+    double *dY = mY.get<double>(), *dG = mG.get<double>();
     HIP_CHECK(hipMemcpy(dY, Y.data(), sizeof(double) * Y.size(), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemset(dG, 0, sizeof(double) * G.size()));
     if (four) gram_lds4_kernel<<<dim3(ntiles), 256>>>(dY, ld, S, rows, nbt, dG, nullptr, 0, 0);
     else gram_lds_kernel<<<dim3(ntiles), 256>>>(dY, ld, S, rows, nbt, dG, nullptr, 0, 0, 1);
     KERNEL_CHECK();
     HIP_CHECK(hipMemcpy(G.data(), dG, sizeof(double) * G.size(), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(dY));
-    HIP_CHECK(hipFree(dG));
     double err = 0.0;
     for (int i = 0; i < S; ++i)
         for (int j = 0; j < S; ++j) {

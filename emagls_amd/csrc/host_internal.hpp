@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/emagls.h"
+#include "device_mem.hpp"
 #include "kernels.hpp"
 
 using namespace emagls;
@@ -436,7 +437,7 @@ struct emagls_batch {
     CapturedGraph warm;                        // the warm form's stages before the sweep (the stages after it are the same in both forms)
     int last_form = 0;                         // the last execute: 0 independent designs (or another kind of batch), 1 cold, 2 warm
     long long geo_cold_runs = 0, geo_warm_runs = 0;
-    int* cmp_flag = nullptr;
+    emagls::DevMem cmp_flag;
     int nstreams = 1;                          // lane mode: streams the stages before the sweep fork onto (emagls_batch_set_streams)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     // the stages before the sweep, one graph per lane group (on `stream`, side[0], side[1], side[2]: batch_execute_lanes); [0] is also
@@ -454,7 +455,7 @@ struct emagls_batch {
     bool alone = true;                         // the batch has the device to itself: the default of emagls_batch_create; the job scheduler clears it for the chunks of a list that keeps several in flight
     int eager_runs = 0;
     bool use_graph = true;
-    void* sweep_args_dev = nullptr;            // argument blocks of the register-resident sweep, one per plan (sweep_reg.hip)
+    emagls::DevMem sweep_args_dev;             // argument blocks of the register-resident sweep, one per plan (sweep_reg.hip)
     std::vector<char> sweep_args_last;
     std::vector<hipEvent_t> events;
     size_t used = 0;
@@ -482,8 +483,6 @@ struct emagls_batch {
         for (auto e : sweep_ev) if (e) hipEventDestroy(e);
         if (stream && own_stream) emagls::pool_stream_give(stream);
         for (int i = 0; i < 3; ++i) if (side[i] && !(i == 0 && side0_external)) { hipStreamSynchronize(side[i]); emagls::pool_stream_give(side[i]); }
-        if (cmp_flag) hipFree(cmp_flag);
-        if (sweep_args_dev) hipFree(sweep_args_dev);
         for (auto* p : plans) if (p) { p->sync_stream = nullptr; p->owner = nullptr; }
     }
 };

@@ -1,7 +1,7 @@
 // Measured FP64 peaks of the device this library runs on: the denominators of the roofline figures that bench.py
 // reports (the MI355X FP64 peak is not in the local guides; measure it with a v_mfma_f64_16x16x4_f64
 // loop on every CU and use the measured figure).
-#include "kernels.hpp"
+#include "device_mem.hpp"
 
 namespace emagls {
 
@@ -82,8 +82,8 @@ double measure_fp64_peak(int which, int reps, bool burst, double* mhz) {
     int dev = 0, cus = 0;
     HIP_CHECK(hipGetDevice(&dev));
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    double* sink = nullptr;
-    HIP_CHECK(hipMalloc(&sink, 64));
+    DevMem sink_mem(64);
+    double* sink = sink_mem.get<double>();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_CHECK(hipEventCreate(&e0));
     HIP_CHECK(hipEventCreate(&e1));
@@ -112,7 +112,6 @@ double measure_fp64_peak(int which, int reps, bool burst, double* mhz) {
         }
         hipEventDestroy(e0);
         hipEventDestroy(e1);
-        hipFree(sink);
         return best4;
     }
     double best = 0.0;
@@ -148,7 +147,6 @@ double measure_fp64_peak(int which, int reps, bool burst, double* mhz) {
     }
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(sink);
     return best;
 }
 

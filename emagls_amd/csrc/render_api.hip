@@ -5,7 +5,7 @@
 
 #include "../../include/emagls.h"
 #include "kernels.hpp"
-#include "scratch.hpp"
+#include "device_mem.hpp"
 
 using namespace emagls;
 

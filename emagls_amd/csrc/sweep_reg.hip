@@ -26,7 +26,7 @@
 //
 // Everything around the chain is sweep_synth.hip's: synth_coeff_kernel (bsc), synth_mt_kernel (Mt = Pm^T M Pm, the chain's
 // start value), synth_rows_kernel (the filters' rows from the stored totals), the row order of the microphones (smap).
-#include "kernels.hpp"
+#include "device_mem.hpp"
 #include "persist_common.hpp"
 #include "synth_common.hpp"
 
@@ -650,20 +650,15 @@ double reg_contract_selftest() {
                     want[8 * u + 4 * eo + 2 * e] += tv.x * gv.x + tv.y * gv.y;       // t conj(g)
                     want[8 * u + 4 * eo + 2 * e + 1] += tv.y * gv.x - tv.x * gv.y;
                 }
-    cplx *d_t = nullptr, *d_g = nullptr;
-    double* d_out = nullptr;
-    HIP_CHECK(hipMalloc(&d_t, sizeof h_t));
-    HIP_CHECK(hipMalloc(&d_g, sizeof h_g));
-    HIP_CHECK(hipMalloc(&d_out, sizeof h_out));
+    DevMem m_t(sizeof h_t), m_g(sizeof h_g), m_out(sizeof h_out);
+    cplx *d_t = m_t.get<cplx>(), *d_g = m_g.get<cplx>();
+    double* d_out = m_out.get<double>();
     HIP_CHECK(hipMemcpy(d_t, h_t, sizeof h_t, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_g, h_g, sizeof h_g, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemset(d_out, 0, sizeof h_out));
     reg_contract_selftest_kernel<<<1, 64>>>(d_t, d_g, d_out);
     KERNEL_CHECK();
     HIP_CHECK(hipMemcpy(h_out, d_out, sizeof h_out, hipMemcpyDeviceToHost));
-    HIP_CHECK(hipFree(d_t));
-    HIP_CHECK(hipFree(d_g));
-    HIP_CHECK(hipFree(d_out));
     double err = 0.0;
     for (int i = 0; i < NO; ++i) err = std::max(err, std::fabs(h_out[i] - want[i]));
     return err;

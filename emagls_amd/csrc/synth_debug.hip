@@ -2,7 +2,7 @@
 // of synth_common.hpp, the function sweep_synth.hip, sweep_reg.hip and synth_ls_kernel call -- on coefficient rows and arguments
 // the caller supplies, so that a test can hold g(x) = E + O and g(-x) = E - O against a high-precision sum directly; and the argument
 // 2 cos(direction, microphone) the sweeps form from the angles (synth_x2).
-#include "kernels.hpp"
+#include "device_mem.hpp"
 #include "synth_common.hpp"
 
 namespace emagls {
@@ -56,25 +56,17 @@ __global__ void __launch_bounds__(SD_NT) synth_cosines_debug_kernel(const double
 void synth_cosines_debug(const double* dir_azi, const double* dir_zen, int64_t ndirs, const double* mic_azi, const double* mic_zen, int nmics, double* x2) {
     if (!dir_azi || !dir_zen || !mic_azi || !mic_zen || !x2) throw Error(1, "null pointer");
     if (ndirs < 1 || ndirs > ((int64_t)1 << 20) || nmics < 1 || nmics > 64) throw Error(1, "1 to 2^20 directions, 1 to 64 microphones");
-    double *d_da = nullptr, *d_dz = nullptr, *d_ma = nullptr, *d_mz = nullptr, *d_x = nullptr;
-    auto cleanup = [&] { hipFree(d_da); hipFree(d_dz); hipFree(d_ma); hipFree(d_mz); hipFree(d_x); };
     const size_t nb_d = sizeof(double) * (size_t)ndirs, nb_m = sizeof(double) * (size_t)nmics, nb_x = nb_d * (size_t)nmics;
-    try {
-        HIP_CHECK(hipMalloc(&d_da, nb_d));
-        HIP_CHECK(hipMalloc(&d_dz, nb_d));
-        HIP_CHECK(hipMalloc(&d_ma, nb_m));
-        HIP_CHECK(hipMalloc(&d_mz, nb_m));
-        HIP_CHECK(hipMalloc(&d_x, nb_x));
-        HIP_CHECK(hipMemcpy(d_da, dir_azi, nb_d, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_dz, dir_zen, nb_d, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_ma, mic_azi, nb_m, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_mz, mic_zen, nb_m, hipMemcpyHostToDevice));
-        synth_cosines_debug_kernel<<<(unsigned)ceil_div(ndirs * nmics, (int64_t)SD_NT), SD_NT>>>(d_da, d_dz, ndirs, d_ma, d_mz, nmics, d_x);
-        KERNEL_CHECK();
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(x2, d_x, nb_x, hipMemcpyDeviceToHost));
-    } catch (...) { cleanup(); throw; }
-    cleanup();
+    DevMem m_da(nb_d), m_dz(nb_d), m_ma(nb_m), m_mz(nb_m), m_x(nb_x);
+    double *d_da = m_da.get<double>(), *d_dz = m_dz.get<double>(), *d_ma = m_ma.get<double>(), *d_mz = m_mz.get<double>(), *d_x = m_x.get<double>();
+    HIP_CHECK(hipMemcpy(d_da, dir_azi, nb_d, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_dz, dir_zen, nb_d, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_ma, mic_azi, nb_m, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_mz, mic_zen, nb_m, hipMemcpyHostToDevice));
+    synth_cosines_debug_kernel<<<(unsigned)ceil_div(ndirs * nmics, (int64_t)SD_NT), SD_NT>>>(d_da, d_dz, ndirs, d_ma, d_mz, nmics, d_x);
+    KERNEL_CHECK();
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(x2, d_x, nb_x, hipMemcpyDeviceToHost));
 }
 
 void synth_operand_debug(const void* bsc, int nbins, int nord_pad, const double* x, int64_t nx, int gs, void* g_plus, void* g_minus) {
@@ -83,26 +75,19 @@ void synth_operand_debug(const void* bsc, int nbins, int nord_pad, const double*
     if (gs < 2 || gs > 4) throw Error(1, "the group size is 2, 3 or 4");
     if (nbins < 1 || nbins > 65535 || nx < 1 || nx > ((int64_t)1 << 24)) throw Error(1, "1 to 65535 bins, 1 to 2^24 arguments");
     const size_t nb_c = sizeof(cplx) * (size_t)nbins * nord_pad, nb_x = sizeof(double) * (size_t)nx, nb_g = sizeof(cplx) * (size_t)nbins * (size_t)nx;
-    cplx *d_c = nullptr, *d_p = nullptr, *d_m = nullptr;
-    double* d_x = nullptr;
-    auto cleanup = [&] { hipFree(d_c); hipFree(d_x); hipFree(d_p); hipFree(d_m); };
-    try {
-        HIP_CHECK(hipMalloc(&d_c, nb_c));
-        HIP_CHECK(hipMalloc(&d_x, nb_x));
-        HIP_CHECK(hipMalloc(&d_p, nb_g));
-        HIP_CHECK(hipMalloc(&d_m, nb_g));
-        HIP_CHECK(hipMemcpy(d_c, bsc, nb_c, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d_x, x, nb_x, hipMemcpyHostToDevice));
-        const dim3 grid((unsigned)ceil_div(ceil_div(nx, (int64_t)gs), (int64_t)SD_NT), (unsigned)nbins);
-        if (gs == 2) synth_operand_debug_kernel<2><<<grid, SD_NT>>>(d_c, nord_pad, d_x, nx, d_p, d_m);
-        else if (gs == 3) synth_operand_debug_kernel<3><<<grid, SD_NT>>>(d_c, nord_pad, d_x, nx, d_p, d_m);
-        else synth_operand_debug_kernel<4><<<grid, SD_NT>>>(d_c, nord_pad, d_x, nx, d_p, d_m);
-        KERNEL_CHECK();
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(g_plus, d_p, nb_g, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(g_minus, d_m, nb_g, hipMemcpyDeviceToHost));
-    } catch (...) { cleanup(); throw; }
-    cleanup();
+    DevMem m_c(nb_c), m_x(nb_x), m_p(nb_g), m_m(nb_g);
+    cplx *d_c = m_c.get<cplx>(), *d_p = m_p.get<cplx>(), *d_m = m_m.get<cplx>();
+    double* d_x = m_x.get<double>();
+    HIP_CHECK(hipMemcpy(d_c, bsc, nb_c, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_x, x, nb_x, hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)ceil_div(ceil_div(nx, (int64_t)gs), (int64_t)SD_NT), (unsigned)nbins);
+    if (gs == 2) synth_operand_debug_kernel<2><<<grid, SD_NT>>>(d_c, nord_pad, d_x, nx, d_p, d_m);
+    else if (gs == 3) synth_operand_debug_kernel<3><<<grid, SD_NT>>>(d_c, nord_pad, d_x, nx, d_p, d_m);
+    else synth_operand_debug_kernel<4><<<grid, SD_NT>>>(d_c, nord_pad, d_x, nx, d_p, d_m);
+    KERNEL_CHECK();
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(g_plus, d_p, nb_g, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(g_minus, d_m, nb_g, hipMemcpyDeviceToHost));
 }
 
 }  // namespace emagls

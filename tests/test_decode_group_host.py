@@ -187,3 +187,17 @@ def test_python_argument_errors(lib):
             g.push(x, setIndex=2)
         with pytest.raises(ValueError, match="multiple of blockSize"):
             g.push(np.zeros((100, 4)))
+
+
+def test_python_closed_and_host_tensor_texts(lib):
+    import torch
+    import emagls_amd as E
+    w = np.zeros((8, 4))
+    g = E.BinauralDecodeGroup(w, w, 64, 2)
+    with pytest.raises(ValueError, match=r"^a torch block must be on the GPU \(pass a NumPy array for the host entry\)$"):
+        g.push(torch.zeros(64, 4, dtype=torch.float64))
+    g.close()
+    g.close()
+    for call in (lambda: g.push(np.zeros((64, 4))), g.info, g.reset):
+        with pytest.raises(ValueError, match="^the decode group is closed$"):
+            call()

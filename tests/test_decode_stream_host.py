@@ -187,3 +187,19 @@ def test_python_argument_errors(lib):
     with E.BinauralDecodeStream(w15, w15, 64) as s:
         with pytest.raises(ValueError, match="SH channels"):
             s.push(np.zeros((64, 15)), 0.3, 0.0, 0.2)
+
+
+def test_python_closed_and_host_tensor_texts(lib):
+    import torch
+    import emagls_amd as E
+    w = np.zeros((8, 16))
+    s = E.BinauralDecodeStream(w, w, 64)
+    with pytest.raises(ValueError, match=r"^a torch block must be on the GPU \(pass a NumPy array for the host entry\)$"):
+        s.push(torch.zeros(64, 16, dtype=torch.float64))
+    with pytest.raises(ValueError, match="multiple of blockSize"):      # (the shape is looked at first)
+        s.push(torch.zeros(100, 16, dtype=torch.float64))
+    s.close()
+    s.close()
+    for call in (lambda: s.push(np.zeros((64, 16))), lambda: s.info, s.reset):
+        with pytest.raises(ValueError, match="^the decode stream is closed$"):
+            call()

@@ -228,3 +228,18 @@ def test_python_argument_errors(lib):
         f.push(np.zeros((64, 2)))
     with E.SourceFieldStream(r + 0j, 64) as f:
         assert f.complexOutput and f.info["response_bytes"] == 16 * 1 * 1 * 32 * 65
+
+
+def test_python_closed_and_host_tensor_texts(lib):
+    import torch
+    import emagls_amd as E
+    f = E.SourceFieldStream(np.zeros((8, 4)), 64)
+    with pytest.raises(ValueError, match=r"^a torch block must be on the GPU \(pass a NumPy array for the host entry\)$"):
+        f.push(torch.zeros(64, dtype=torch.float64))
+    with pytest.raises(ValueError, match="multiple of blockSize"):      # (the shape is looked at first)
+        f.push(torch.zeros(100, dtype=torch.float64))
+    f.close()
+    f.close()
+    for call in (lambda: f.push(np.zeros(64)), lambda: f.info, f.reset):
+        with pytest.raises(ValueError, match="^the field stream is closed$"):
+            call()
