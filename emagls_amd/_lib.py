@@ -176,6 +176,10 @@ SYMBOLS = {
     "emagls_field_stream_info": (C.c_int, [C.c_void_p, C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64),
                                            C.POINTER(C.c_int)]),
     "emagls_field_stream_destroy": (C.c_int, [C.c_void_p]),
+    "emagls_field_stream_create_bank": (C.c_int, [c_i64, c_i64, c_i64, C.c_void_p, C.c_int, c_i64, c_i64, C.POINTER(C.c_void_p)]),
+    "emagls_field_stream_push_sets": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p]),
+    "emagls_field_stream_push_sets_device": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p]),
+    "emagls_field_stream_sets": (C.c_int, [C.c_void_p, C.POINTER(c_i64)]),
     "emagls_get_magls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_double, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_get_emagls_filters_dc": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, C.c_void_p, C.c_double,

@@ -598,9 +598,10 @@ _ANGLE_NAMES = ("horRotAngleRad", "pitchRad", "rollRad")
 
 
 class _BlockStreamObject:
-    """What the block-stream objects share: the handle's life, the NumPy-or-torch dispatch of a push, the block-multiple check and
-    the frame of a torch push.  A subclass names itself (_kind) and its C destroy entry (_destroy), sets blockSize and has
-    _push_numpy(h, block, ...) and _push_torch(h, block, ...)."""
+    """What the block-stream objects share: the handle's life, the NumPy-or-torch dispatch of a push, the block-multiple check,
+    the set indices of a push into a bank and the frame of a torch push.  A subclass names itself (_kind) and its C destroy entry
+    (_destroy), sets blockSize and numSets and has _push_numpy(h, block, ...), _push_torch(h, block, ...) and
+    _shape_sets(a, nb, xp)."""
 
     _h = None
 
@@ -613,6 +614,27 @@ class _BlockStreamObject:
         if n % self.blockSize:
             raise ValueError("block must have a multiple of blockSize (%d) samples, not %d" % (self.blockSize, n))
         return n
+
+    def _set_index(self, setIndex, n, device=None):
+        """setIndex in the shape of the push, as int32 (None: None): a host array checked against the bank or, with `device`, a
+        tensor there.  A tensor that is given is not read on the host."""
+        if setIndex is None:
+            return None
+        nb = n // self.blockSize
+        if device is not None:
+            import torch
+            if torch.is_tensor(setIndex):
+                if setIndex.dtype != torch.int32:
+                    raise ValueError("a setIndex tensor must be int32")
+                return self._shape_sets(setIndex.to(device=device), nb, torch).contiguous()
+        a = np.asarray(setIndex)
+        if a.dtype.kind not in "iu":
+            raise ValueError("setIndex must be an integer or integers")
+        a = self._shape_sets(a, nb, np)
+        if a.size and (a.min() < 0 or a.max() >= self.numSets):
+            raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        return a if device is None else torch.as_tensor(a, device=device)
 
     def push(self, block, *args):
         h = self._handle()
@@ -719,27 +741,6 @@ class _DecodeObject(_BlockStreamObject):
             if self._layout != L.LAYOUT["sh"]:
                 raise ValueError("a CH signal can only be turned about z: pitchRad and rollRad must be 0")
             _sh_order(self.numChannels)
-
-    def _set_index(self, setIndex, n, device=None):
-        """setIndex in the shape of the push, as int32 (None: None): a host array checked against the bank or, with `device`, a
-        tensor there.  A tensor that is given is not read on the host."""
-        if setIndex is None:
-            return None
-        nb = n // self.blockSize
-        if device is not None:
-            import torch
-            if torch.is_tensor(setIndex):
-                if setIndex.dtype != torch.int32:
-                    raise ValueError("a setIndex tensor must be int32")
-                return self._shape_sets(setIndex.to(device=device), nb, torch).contiguous()
-        a = np.asarray(setIndex)
-        if a.dtype.kind not in "iu":
-            raise ValueError("setIndex must be an integer or integers")
-        a = self._shape_sets(a, nb, np)
-        if a.size and (a.min() < 0 or a.max() >= self.numSets):
-            raise ValueError("setIndex must lie in [0, numSets - 1] = [0, %d]" % (self.numSets - 1))
-        a = np.ascontiguousarray(a, dtype=np.int32)
-        return a if device is None else torch.as_tensor(a, device=device)
 
     def _push_numpy(self, h, block, horRotAngleRad, pitchRad, rollRad, setIndex):
         self._check_complex(np.iscomplexobj(block))
@@ -923,7 +924,13 @@ class SourceFieldStream(_BlockStreamObject):
     The output of a torch push lies as BinauralDecodeStream.push and BinauralDecodeGroup.push read their block: they take it
     without a copy, and the chain source -> room -> rotation -> filters runs on the device without a host synchronisation.
     numSources <= 16, numChannels <= 256, nr <= 1048576, response spectra <= 4 GiB; `info` gives block, partitions, state_bytes,
-    response_bytes and launches_per_block."""
+    response_bytes and launches_per_block.
+    A bank, for sources that move: rirs [numSets x numSources x nr x numChannels] make a stream of
+    `numSets` response sets, and `push` takes a set index per source and block.  A change of set is cross-faded over the block that
+    changes: its sample i goes to the new set with the gain (i + 1) / blockSize and to the old one with the rest; the first block
+    after creation or reset does not fade.  The outputs equal sum_q sum_s fftfilt(rirs[s][q][:, c], g_sq * s_q) with g_sq the gain
+    of set s per sample of source q; a constant index gives the bits of the plain stream on that set.  numSets <= 65536, and the
+    4 GiB hold for the whole bank."""
 
     _kind, _destroy = "field stream", "emagls_field_stream_destroy"
 
@@ -932,16 +939,20 @@ class SourceFieldStream(_BlockStreamObject):
         r = np.asarray(rirs, dtype=np.complex128 if r_c else np.float64)
         if r.ndim == 2:
             r = r[None]
-        if r.ndim != 3:
-            raise ValueError("rirs must be [nr x numChannels] or [numSources x nr x numChannels]")
+        if r.ndim == 3:
+            r = r[None]
+        if r.ndim != 4:
+            raise ValueError("rirs must be [nr x numChannels], [numSources x nr x numChannels] or [numSets x numSources x nr x numChannels]")
         if int(blockSize) != blockSize:
             raise ValueError("blockSize must be an integer")
-        self.numSources, nr, self.numChannels = r.shape
+        self.numSets, self.numSources, nr, self.numChannels = r.shape
+        if self.numSets < 1:
+            raise ValueError("a bank needs at least one response set")
         self.blockSize, self.complexOutput = int(blockSize), bool(r_c)
-        r = np.ascontiguousarray(r.transpose(0, 2, 1))   # the sources one after the other, each column-major [nr x numChannels]
+        r = np.ascontiguousarray(r.transpose(0, 1, 3, 2))   # set by set the sources one after the other, each column-major [nr x numChannels]
         h = C.c_void_p()
-        L.check(L.load().emagls_field_stream_create(self.numSources, self.numChannels, r.ctypes.data_as(C.c_void_p), 1 if r_c else 0, nr,
-                                                    self.blockSize, C.byref(h)))
+        L.check(L.load().emagls_field_stream_create_bank(self.numSources, self.numChannels, self.numSets, r.ctypes.data_as(C.c_void_p),
+                                                         1 if r_c else 0, nr, self.blockSize, C.byref(h)))
         self._h = h
 
     @property
@@ -957,36 +968,56 @@ class SourceFieldStream(_BlockStreamObject):
             raise ValueError("block must be [n] (one source) or [n x numSources] matching the responses' source count (%d)" % self.numSources)
         return self._check_multiple(shape[0])
 
-    def push(self, block):
+    def _shape_sets(self, a, nb, xp):
+        """setIndex as [numSources] or [numSources x nb]: a scalar is the same for every source."""
+        ns = self.numSources
+        shape = tuple(a.shape)
+        if len(shape) == 0 or (len(shape) == 1 and shape[0] == 1):
+            return xp.broadcast_to(a.reshape(1), (ns,))
+        if shape == (ns,) or shape == (ns, 1):
+            return a.reshape(ns)
+        if shape == (ns, nb):
+            return a
+        if ns == 1 and shape == (nb,):
+            return a.reshape(1, nb)
+        raise ValueError("setIndex must be a scalar, [numSources] or [numSources x n / blockSize] = [%d x %d], not %s" % (ns, nb, list(shape)))
+
+    def push(self, block, setIndex=None):
         """block [n] or [n x numSources], real, n a multiple of blockSize: a NumPy array (host entry; returns a NumPy array
         [n x numChannels]), or a torch tensor on the stream's device (device entry on torch's current stream, not synchronised;
-        returns a tensor [n x numChannels] that is the transposed view of the [numChannels][n] buffer the kernel wrote)."""
-        return super().push(block)
+        returns a tensor [n x numChannels] that is the transposed view of the [numChannels][n] buffer the kernel wrote).
+        setIndex: None (every source keeps its set; set 0 on a fresh object), an int (every source), [numSources] (constant over
+        this push) or [numSources x n / blockSize]; with torch blocks also a device int32 tensor, which is not read on the host:
+        the kernels then clamp its values into [0, numSets - 1]."""
+        return super().push(block, setIndex)
 
-    def _push_numpy(self, h, block):
+    def _push_numpy(self, h, block, setIndex):
         if np.iscomplexobj(block):
             raise ValueError("a field stream takes real source signals")
         x = np.asarray(block, dtype=np.float64)
         n = self._check_block(x.shape)
         x = np.asfortranarray(x.reshape(n, self.numSources))
+        sets = self._set_index(setIndex, n)
         out = np.zeros((self.numChannels, n), dtype=np.complex128 if self.complexOutput else np.float64)
-        L.check(L.load().emagls_field_stream_push(h, x.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p)))
+        L.check(L.load().emagls_field_stream_push_sets(h, x.ctypes.data_as(C.c_void_p), n, *_vp(sets), out.ctypes.data_as(C.c_void_p)))
         return out.T
 
-    def _push_torch(self, h, block):
+    def _push_torch(self, h, block, setIndex):
         import torch
         n = self._check_block(tuple(block.shape))
         self._need_gpu(block)
         if block.is_complex():
             raise ValueError("a field stream takes real source signals")
         xt = block.to(torch.float64).reshape(n, self.numSources).t().contiguous()   # [numSources][n]: column-major
+        ts = self._set_index(setIndex, n, block.device)
         out = torch.empty((self.numChannels, n), dtype=torch.complex128 if self.complexOutput else torch.float64, device=block.device)
-        self._on_current_stream(block, (xt,), lambda st: L.check(L.load().emagls_field_stream_push_device(
-            h, C.c_void_p(xt.data_ptr()), n, C.c_void_p(out.data_ptr()), st)))
+        self._on_current_stream(block, (xt, ts), lambda st: L.check(L.load().emagls_field_stream_push_sets_device(
+            h, C.c_void_p(xt.data_ptr()), n, C.c_void_p(ts.data_ptr()) if ts is not None else None, 0 if ts is None else ts.numel(),
+            C.c_void_p(out.data_ptr()), st)))
         return out.t()
 
     def reset(self):
-        """Zero history: what follows equals a fresh object bit for bit."""
+        """Zero history (and, for a bank, no selection): what follows equals a fresh object bit for bit."""
         L.check(L.load().emagls_field_stream_reset(self._handle()))
 
 

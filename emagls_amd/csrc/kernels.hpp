@@ -295,9 +295,17 @@ struct FieldStreamState {
     cplx* ring = nullptr;   // [nsrc][P][B + 1] the spectra of the last P windows [previous block, block] of every source
     double* hist = nullptr; // [nsrc][B] the previous block
     int* pos = nullptr;     // the ring slot of the block pushed last
+    // a bank of response sets; with S == 1 none of it exists and the layouts above hold
+    int S = 1;              // response sets: Rf [S][nsrc][P][planes][B + 1], ring [nsrc][P][3][B + 1]
+    int* tag = nullptr;     // [nsrc][P][3] the set of a ring entry, -1: empty
+    int* sel = nullptr;     // [nsrc][2] the set indices of the two previous blocks (-1: none yet)
 };
-// one block: src + q lds = source q's B samples; out + c ldo = channel c's B samples (doubles, or cplx when s.out_c).  Two launches
-void launch_field_stream_block(const FieldStreamState& s, const double* src, int64_t lds, void* out, int64_t ldo, hipStream_t st);
+constexpr int kFieldStreamEntries = 3;   // ring entries per slot of a bank: a window meets at most three sets
+constexpr int kFieldStreamMaxSources = 16;   // the limit of the C ABI; the bank's source kernel sizes its tables by it
+// one block: src + q lds = source q's B samples; out + c ldo = channel c's B samples (doubles, or cplx when s.out_c).  Two launches.
+// set (looked at only when s.S > 1): device, source q's set index of this block at set + q lset; null: every source keeps its set
+void launch_field_stream_block(const FieldStreamState& s, const double* src, int64_t lds, const int* set, int64_t lset, void* out, int64_t ldo,
+                               hipStream_t st);
 constexpr int kFieldStreamLaunches = 2;
 
 // ---- decode_api.hip: releases decode.hip's plans, rotate3.hip's tables, resample.hip's taps and the decode family's work buffers

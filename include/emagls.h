@@ -561,6 +561,41 @@ int emagls_field_stream_info(const emagls_field_stream* f, int64_t* block, int64
 
 int emagls_field_stream_destroy(emagls_field_stream* f);
 
+/* ---- a bank of room responses on a field stream, cross-faded per block ----
+ * A source that moves through measured or simulated positions: the bank holds n_sets >= 1 response sets of one shape, rir[s][q]
+ * [nr x nch] (s = 0 .. n_sets - 1, q = 0 .. nsrc - 1), and every source q has its OWN set index per block, s_(q,t).  With
+ * r[i] = (i + 1) / block, sample i of block t of source q goes to set s_(q,t) with the gain 1 when s_(q,t) == s_(q,t-1);
+ * otherwise to s_(q,t) with r[i] and to s_(q,t-1) with 1 - r[i]; s_(q,-1) := s_(q,0) (the first block after creation or reset
+ * does not fade).  DEFINING PROPERTY: with g_(s,q) the gain of set s per sample of source q and x_q everything pushed for it, the
+ * concatenated outputs equal, to rounding,
+ *     out(:, c) = sum_q sum_s fftfilt(rir[s][q](:, c), g_(s,q) .* x_q):
+ * the response a sample meets is that of the moment it was emitted, linearly interpolated across the block that changes.
+ * The ring of input spectra holds up to three tagged entries per slot (a window [previous block, block] meets at most the sets of
+ * the blocks t - 2, t - 1 and t), each multiplied with the partition spectra of its own set; empty entries are skipped.  Still two
+ * launches per block, no atomics, every order fixed.  With every index constant the bank returns the BITS of the plain field stream
+ * of that set's responses.  A bank of one set IS the plain field stream: same kernels, same state, same info.
+ * rir: n_sets consecutive groups of nsrc [nr x nch] arrays.  n_sets < 1: EMAGLS_ERR_ARG; above 65536: EMAGLS_ERR_UNSUPPORTED; the
+ * 4 GiB cap holds for the whole bank's response_bytes = n_sets nsrc P planes (block + 1) 16.  Everything else as
+ * emagls_field_stream_create, which is the bank of one set.  With n_sets > 1, state_bytes counts the ring as it is (three entries
+ * per slot), the entries' tags (nsrc P 3 int32) and the two previous indices per source; reset also forgets the selection. */
+int emagls_field_stream_create_bank(int64_t nsrc, int64_t nch, int64_t n_sets, const void* rir, int rir_is_complex, int64_t nr,
+                                    int64_t block, emagls_field_stream** f);
+
+/* emagls_field_stream_push with set indices: set [n_set], n_set = 0 (every source keeps its set; set 0 on a fresh object), nsrc
+ * (one index per source for every block of this push) or nsrc * nsamp / block ([nsrc][nsamp / block], source-major).  Any other
+ * count, a null array with a positive count, or an index outside [0, n_sets - 1] is EMAGLS_ERR_ARG, reported before the device is
+ * touched.  emagls_field_stream_push is this call with n_set = 0. */
+int emagls_field_stream_push_sets(emagls_field_stream* f, const double* src, int64_t nsamp, const int32_t* set, int64_t n_set, void* out);
+
+/* emagls_field_stream_push_device with set indices in device memory: d_set is not read by the host (the call still only
+ * enqueues), so the kernels clamp every index into [0, n_sets - 1] before they form an address from it.
+ * emagls_field_stream_push_device is this call with n_set = 0. */
+int emagls_field_stream_push_sets_device(emagls_field_stream* f, const double* d_src, int64_t nsamp, const int32_t* d_set, int64_t n_set,
+                                         void* d_out, void* stream);
+
+/* The number of response sets of the object's bank. */
+int emagls_field_stream_sets(const emagls_field_stream* f, int64_t* n_sets);
+
 /* The three designs with a covariance constraint in the place of the `applyDiffusenessConst` argument the reference's
  * functions used to take after `len` (verifyEMagLs.m:106-114 still shows the call form).  OWN SPECIFICATION, not the reference's
  * implementation: that code is not in the snapshot (CHANGELOG.md:10-12).  Per solved bin the two ears' filters are mixed by the

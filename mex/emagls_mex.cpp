@@ -187,8 +187,11 @@ void at_exit() {
 //                                     [], [1 x L] or [nBlocks x L]
 // emagls_mex('group_reset', h[, listener])   ONE-based; without it all listeners      emagls_mex('group_destroy', h)
 // h = emagls_mex('field_create', rirs, blockSize)   a field stream (mex/sourceFieldStream.m): rirs [nr x nch], or [nr x nch x numSources],
-//                                     real or complex: dry sources through room responses, a block at a time
-// out = emagls_mex('field_push', h, src)   src [k*blockSize x numSources] real; out [k*blockSize x nch], complex for a complex response
+//                                     real or complex: dry sources through room responses, a block at a time; rirs
+//                                     [nr x nch x numSources x numSets]: a bank of response sets, for sources that move
+// out = emagls_mex('field_push', h, src[, setIndex])   src [k*blockSize x numSources] real; out [k*blockSize x nch], complex for a complex
+//                                     response; setIndex ONE-based: [] (every source keeps its set), a scalar (every source),
+//                                     [numSources] or [numSources x k]
 // emagls_mex('field_reset', h)       emagls_mex('field_destroy', h)
 // emagls_mex('resample', x, p, q)   MATLAB's resample(x, p, q) (N = 10, bta = 5): a row vector along its length, else per column
 // emagls_mex('rotate',  in, yawRad[, shDefinition, domain])    yaw rotation of an SH ('sh', default) or CH ('ch') signal
@@ -293,26 +296,45 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "field_create needs (rirs, blockSize)");
         const mwSize nd = mxGetNumberOfDimensions(prhs[1]);
         const mwSize* dims = mxGetDimensions(prhs[1]);
-        if (!mxIsDouble(prhs[1]) || nd > 3)
-            mexErrMsgIdAndTxt("eMagLS:arg", "rirs must be a double [nr x numChannels] or [nr x numChannels x numSources] array");
-        const mwSize nr = dims[0], ch = nd >= 2 ? dims[1] : 1, nsrc = nd == 3 ? dims[2] : 1;
+        if (!mxIsDouble(prhs[1]) || nd > 4)
+            mexErrMsgIdAndTxt("eMagLS:arg",
+                              "rirs must be a double [nr x numChannels], [nr x numChannels x numSources] or [nr x numChannels x numSources x numSets] array");
+        // column-major, the sets of a bank lie one after the other, each the sources one after the other, as the library takes them
+        const mwSize nr = dims[0], ch = nd >= 2 ? dims[1] : 1, nsrc = nd >= 3 ? dims[2] : 1, nsets = nd == 4 ? dims[3] : 1;
         const double bs = mxGetScalar(prhs[2]);
         if (!(bs == std::floor(bs)) || std::fabs(bs) > 1e9) mexErrMsgIdAndTxt("eMagLS:arg", "blockSize must be an integer");
         const bool rc_ = mxIsComplex(prhs[1]);
         emagls_field_stream* f = nullptr;
-        const int rc = emagls_field_stream_create((int64_t)nsrc, (int64_t)ch, in_ptr(prhs[1]), rc_, (int64_t)nr, (int64_t)bs, &f);
+        const int rc = emagls_field_stream_create_bank((int64_t)nsrc, (int64_t)ch, (int64_t)nsets, in_ptr(prhs[1]), rc_, (int64_t)nr, (int64_t)bs, &f);
         if (rc) fail(rc);
         plhs[0] = g_fields.add({f, nsrc, rc_, ch});
         return;
     }
     if (c == "field_push") {
-        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "field_push needs (handle, src)");
+        if (nrhs < 3) mexErrMsgIdAndTxt("eMagLS:arg", "field_push needs (handle, src[, setIndex])");
         const auto& e = g_fields.of(prhs[1]);
         if (!mxIsDouble(prhs[2]) || mxIsComplex(prhs[2]) || mxGetNumberOfDimensions(prhs[2]) > 2 || mxGetN(prhs[2]) != e.cols)
             mexErrMsgIdAndTxt("eMagLS:arg", "src must be a real double array with the responses' source count (%d) of columns", (int)e.cols);
         const mwSize n = mxGetM(prhs[2]);
+        // setIndex: a scalar (every source), [numSources] or [numSources x k], which the library takes source-major: [numSources][k]
+        std::vector<int32_t> sets;
+        if (nrhs > 3 && !mxIsEmpty(prhs[3])) {
+            const std::vector<int32_t> given = zero_based(prhs[3]);
+            const mwSize rows = mxGetM(prhs[3]), cols = mxGetN(prhs[3]);
+            const bool as_it_lies = given.size() == e.cols || (e.cols == 1 && (rows == 1 || cols == 1));   // (one source: a vector over the blocks)
+            if (mxGetNumberOfDimensions(prhs[3]) > 2 || !(given.size() == 1 || as_it_lies || rows == e.cols))
+                mexErrMsgIdAndTxt("eMagLS:arg", "setIndex must be a scalar, [numSources] or [numSources x k] with %d sources", (int)e.cols);
+            if (given.size() == 1) sets.assign(e.cols, given[0]);
+            else if (as_it_lies) sets = given;
+            else {
+                sets.resize(given.size());
+                for (mwSize q = 0; q < rows; ++q)
+                    for (mwSize b = 0; b < cols; ++b) sets[q * cols + b] = given[b * rows + q];
+            }
+        }
         plhs[0] = mxCreateDoubleMatrix(n, e.listeners, e.in_complex ? mxCOMPLEX : mxREAL);
-        const int rc = emagls_field_stream_push(e.h, mxGetDoubles(prhs[2]), (int64_t)n, out_ptr(plhs[0]));
+        const int rc = emagls_field_stream_push_sets(e.h, mxGetDoubles(prhs[2]), (int64_t)n, sets.empty() ? nullptr : sets.data(),
+                                                     (int64_t)sets.size(), out_ptr(plhs[0]));
         if (rc) fail(rc);
         return;
     }

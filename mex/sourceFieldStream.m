@@ -9,19 +9,29 @@ classdef sourceFieldStream < handle
 % complex response; responses in the microphone domain go into one with an encoder) together with the head orientation of the
 % block: the chain is source -> room -> rotation -> filters.  blockSize: a power of two from 64 to 2048; numSources <= 16,
 % numChannels <= 256, nr <= 1048576.
+% A bank (DESIGN.md section 9.8), for sources that move: rirs [nr x numChannels x numSources x numSets], and
+%   x = f.push(src, setIndex)    setIndex ONE-based: [] (every source keeps its set; set 1 on a fresh object), a scalar (every
+%                                source), [numSources] or [numSources x k], one index per source and block
+% A change of set is cross-faded over the block that changes: its sample i goes to the new set with the gain i / blockSize
+% (i = 1 .. blockSize) and to the old one with the rest; the first block after creation or reset does not fade.  The outputs equal
+% sum_q sum_s fftfilt(rirs(:, c, q, s), g_sq .* s_q) with g_sq the gain of set s per sample of source q; a constant index gives
+% the bits of the plain stream on that set.  numSets <= 65536; the response spectra of the whole bank <= 4 GiB.
     properties (SetAccess = private)
         handle = 0
         blockSize
         numSources
+        numSets
     end
     methods
         function f = sourceFieldStream(rirs, blockSize)
             f.blockSize = blockSize;
             f.numSources = size(rirs, 3);
+            f.numSets = size(rirs, 4);
             f.handle = emagls_mex('field_create', double(rirs), double(blockSize));
         end
-        function out = push(f, src)
-            out = emagls_mex('field_push', f.handle, double(src));
+        function out = push(f, src, setIndex)
+            if nargin < 3, setIndex = []; end
+            out = emagls_mex('field_push', f.handle, double(src), double(setIndex));
         end
         function reset(f)
             emagls_mex('field_reset', f.handle);

@@ -13,6 +13,7 @@ Gates (exit status 1 when one fails): median (a) < median (b), and median (a) < 
                                          [--bank [--sets 3]] [--group [--listeners 1 8 64 256] [--sets 1]]
                                          [--encoded [--enc-shapes 32,25,512,64 ...] [--listeners 1 8 64]]
                                          [--field [--field-shapes 1,25,48000,64,1 ...]]
+                                         [--field-bank [--field-shapes 1,25,48000,64 ...] [--sets 3 64]]
 --dry-run prints the shapes and the bytes a push moves, computed from the shapes, without a device.
 
 --bank times the bank of filter sets (emagls_decode_stream_create_bank / _push_sets_device) instead, without
@@ -64,6 +65,22 @@ Median and spread = p90 - p10 of the run averages.  The one condition: median(ch
 shape that misses it is reported as such and the exit status is 1.  Also reported: the share of the block's duration the chain
 takes, and the bytes of the response spectra Rf the product kernel streams per block over the time of `field` (both launches: a
 lower bound of that kernel's own rate), as a share of the HBM peak.
+
+--field-bank times the bank of response sets on a field stream (emagls_field_stream_create_bank / _push_sets_device, DESIGN.md
+section 9.8) per shape (nsrc, nch, nr, B) (--field-shapes) and bank size (--sets), alternating in one process, every side on
+objects of its own:
+
+  plain    a plain field stream: the kernel instances without the bank
+  const    a bank stream with a constant index per source read from device memory
+  keep     a bank stream pushed without indices
+  switch   a bank stream with a new set for every source in EVERY block
+  streams  what a caller does without the bank for the output of `switch`: three plain field streams, the source blocks weighted
+           by r and by 1 - r on the device for the new and the old set, a zero block for the third (its tail still has to come
+           out), and the three outputs added on the device.  A lower bound: with P blocks of history more positions are audible
+
+Median and spread = p90 - p10 of the run averages, as --bank.  Reported and not gated: const / plain and keep / plain against the
+plain stream's spread, and whether switch is below streams.  A bank beyond the library's 4 GiB of response spectra is listed as
+refused.
 """
 import argparse
 import ctypes as C
@@ -447,6 +464,7 @@ def encoded_markdown(rows, device):
 
 
 FIELD_SHAPES = ["1,25,48000,64,1", "1,25,96000,256,1", "4,64,48000,128,1", "1,25,48000,64,8"]
+FIELD_BANK_SHAPES = ["1,25,48000,64", "1,25,96000,256", "4,64,48000,128"]
 FIELD_DECODE_TAPS = 512
 
 
@@ -559,6 +577,116 @@ def parse_field_shapes(items):
     return out
 
 
+def run_field_bank_shape(lib, L, torch, nsrc, nch, nr, B, S, blocks, warm, run):
+    """The sides of --field-bank for one shape."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(nsrc + nch + nr + B + S)
+    rnd = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)   # noqa: E731
+    rir = rnd(S, nsrc, nch, nr) / nr ** 0.5                 # [S][nsrc][nch][nr] row-major == S groups of nsrc column-major [nr x nch] arrays
+    d_src = rnd(nsrc, B).to(dev)
+    r = ((torch.arange(B, dtype=torch.float64) + 1) / B).to(dev)
+    omr = 1.0 - r
+    xa, xb, zero = torch.empty_like(d_src), torch.empty_like(d_src), torch.zeros_like(d_src)
+    outs = [torch.zeros((nch, B), dtype=torch.float64, device=dev) for _ in range(4)]
+    d_const = torch.ones(nsrc, dtype=torch.int32, device=dev)
+    # row c: the indices of block c, a new set for every source
+    d_idx = ((torch.arange(S).reshape(S, 1) + torch.arange(nsrc).reshape(1, nsrc)) % S).to(torch.int32).to(dev).contiguous()
+    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+    st = torch.cuda.Stream(device=dev)
+    sp = C.c_void_p(st.cuda_stream)
+
+    def plain_stream(s):
+        h = C.c_void_p()
+        L.check(lib.emagls_field_stream_create(nsrc, nch, p(rir[s]), 0, nr, B, C.byref(h)))
+        return h
+
+    def bank_stream():
+        h = C.c_void_p()
+        L.check(lib.emagls_field_stream_create_bank(nsrc, nch, S, p(rir), 0, nr, B, C.byref(h)))
+        return h
+
+    def push(h, x, out):
+        L.check(lib.emagls_field_stream_push_device(h, p(x), B, p(out), sp))
+
+    def push_sets(h, sets):
+        L.check(lib.emagls_field_stream_push_sets_device(h, p(d_src), B, sets, nsrc if sets else 0, p(outs[0]), sp))
+
+    h_plain = plain_stream(0)
+    h_three = [plain_stream(s) for s in range(3)]
+    h_const, h_keep, h_switch = bank_stream(), bank_stream(), bank_stream()   # (an object each: a side's index history is its own)
+    count = [0]
+
+    def side_switch():
+        count[0] += 1
+        push_sets(h_switch, C.c_void_p(d_idx.data_ptr() + 4 * nsrc * (count[0] % S)))
+
+    def side_streams():
+        count[0] += 1
+        new, prev, third = count[0] % 3, (count[0] - 1) % 3, (count[0] + 1) % 3
+        torch.mul(d_src, r, out=xa)
+        torch.mul(d_src, omr, out=xb)
+        push(h_three[new], xa, outs[1])
+        push(h_three[prev], xb, outs[2])
+        push(h_three[third], zero, outs[3])
+        torch.add(outs[1], outs[2], out=outs[0])
+        outs[0].add_(outs[3])
+
+    sides = [("plain", lambda: push(h_plain, d_src, outs[0])), ("const", lambda: push_sets(h_const, p(d_const))),
+             ("keep", lambda: push_sets(h_keep, None)), ("switch", side_switch), ("streams", side_streams)]
+    times = {k: [] for k, _ in sides}
+    with torch.cuda.stream(st):
+        for _, f in sides:
+            for _ in range(warm):
+                f()
+        st.synchronize()
+        for _ in range(max(1, blocks // run)):
+            for k, f in sides:                       # alternating
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                for _ in range(run):
+                    f()
+                e1.record(st)
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) * 1e3 / run)   # us per block
+    for h in [h_plain, h_const, h_keep, h_switch] + h_three:
+        lib.emagls_field_stream_destroy(h)
+    fb = field_bytes(nsrc, nch, nr, B)
+    res = {"shape": [nsrc, nch, nr, B], "sets": S, "partitions": -(-nr // B), "block_us": round(B / FS * 1e6, 1),
+           "response_mb_per_set": round(fb["response"] / 1e6, 1)}
+    for k, v in times.items():
+        res[k] = {"median_us": round(float(np.median(v)), 2), "min_us": round(float(np.min(v)), 2), "max_us": round(float(np.max(v)), 2),
+                  "spread_us": round(_spread(v), 2)}
+    base = res["plain"]
+    res["const_over_plain"] = round(res["const"]["median_us"] / base["median_us"], 3)
+    res["keep_over_plain"] = round(res["keep"]["median_us"] / base["median_us"], 3)
+    res["const_within_spread"] = res["const"]["median_us"] <= base["median_us"] + base["spread_us"]
+    res["keep_within_spread"] = res["keep"]["median_us"] <= base["median_us"] + base["spread_us"]
+    res["streams_over_switch"] = round(res["streams"]["median_us"] / res["switch"]["median_us"], 2)
+    res["switch_over_const"] = round(res["switch"]["median_us"] / res["const"]["median_us"], 2)
+    res["bank_wins"] = res["switch"]["median_us"] < res["streams"]["median_us"]
+    return res
+
+
+def field_bank_markdown(rows, device):
+    lines = ["`python tools/decode_stream_timing.py --field-bank` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
+             "plain: a plain field stream; const: a bank stream with a constant index from device memory; keep: a bank stream pushed",
+             "without indices; switch: a new set for every source in every block; streams: three plain field streams fed the",
+             "gain-weighted source blocks, outputs added on the device -- a lower bound of what a caller needs without the bank.", "",
+             "| (nsrc, nch, nr, B) | sets | P | Rf MB / set | plain | spread | const | spread | const / plain | within | keep | keep / plain | within | switch | spread | streams | spread | streams / switch | bank wins | switch / const |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        if "refused" in r:
+            lines.append("| %s | %d | %d | %.1f | %s |" % (tuple(r["shape"]), r["sets"], r["partitions"], r["response_mb_per_set"], r["refused"]))
+            continue
+        lines.append("| %s | %d | %d | %.1f | %.1f | %.2f | %.1f | %.2f | %.3f | %s | %.1f | %.3f | %s | %.1f | %.2f | %.1f | %.2f | %.2f | %s | %.2f |" % (
+            tuple(r["shape"]), r["sets"], r["partitions"], r["response_mb_per_set"], r["plain"]["median_us"], r["plain"]["spread_us"],
+            r["const"]["median_us"], r["const"]["spread_us"], r["const_over_plain"], "yes" if r["const_within_spread"] else "no",
+            r["keep"]["median_us"], r["keep_over_plain"], "yes" if r["keep_within_spread"] else "no", r["switch"]["median_us"],
+            r["switch"]["spread_us"], r["streams"]["median_us"], r["streams"]["spread_us"], r["streams_over_switch"],
+            "yes" if r["bank_wins"] else "NO", r["switch_over_const"]))
+    return "\n".join(lines) + "\n"
+
+
 def bank_markdown(rows, device):
     lines = ["`python tools/decode_stream_timing.py --bank` on %s: time per block in us, median of the run averages (spread = p90 - p10)." % device,
              "plain: the plain stream; const: a bank stream with a constant index from device memory; keep: a bank stream pushed without",
@@ -598,20 +726,58 @@ def main():
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--out", default=None, help="markdown table")
     ap.add_argument("--bank", action="store_true", help="time the bank of filter sets (see above)")
-    ap.add_argument("--sets", type=int, default=None, help="--bank: filter sets of the bank stream (at least 3; default 3); --group: default 1")
+    ap.add_argument("--sets", type=int, nargs="*", default=None,
+                    help="--bank: filter sets of the bank stream (at least 3; default 3); --group: default 1; --field-bank: one or more bank sizes, "
+                         "each at least 3 (default 3 64)")
     ap.add_argument("--group", action="store_true", help="time the listener group against a loop over streams (see above)")
     ap.add_argument("--listeners", type=int, nargs="*", default=None, help="--group: numbers of listeners (default 1 8 64 256); --encoded: default 1")
     ap.add_argument("--encoded", action="store_true", help="time the encoder inside the stream against matmul + plain stream (see above)")
     ap.add_argument("--enc-shapes", nargs="*", default=["32,25,512,64", "32,25,512,256", "64,64,2048,128"], help="--encoded: M,C,len,B ...")
     ap.add_argument("--field", action="store_true", help="time the field stream alone and its chain into a decode stream (see above)")
-    ap.add_argument("--field-shapes", nargs="*", default=FIELD_SHAPES, help="--field: nsrc,nch,nr,B,listeners ...")
+    ap.add_argument("--field-shapes", nargs="*", default=None, help="--field: nsrc,nch,nr,B,listeners ...; --field-bank: nsrc,nch,nr,B ...")
+    ap.add_argument("--field-bank", action="store_true", help="time the bank of response sets on a field stream (see above)")
     a = ap.parse_args()
-    if a.sets is None:
-        a.sets = 1 if a.group else 3
+    if a.field_bank:
+        a.sets = a.sets or [3, 64]
+    elif a.sets is not None and len(a.sets) != 1:
+        raise SystemExit("--sets takes one number here")
+    else:
+        a.sets = a.sets[0] if a.sets else (1 if a.group else 3)
+    if a.field_shapes is None:
+        a.field_shapes = FIELD_BANK_SHAPES if a.field_bank else FIELD_SHAPES
     if a.listeners is None:
         a.listeners = [1] if a.encoded else [1, 8, 64, 256]
     if a.blocks < a.run or a.run < 1 or a.warm < 0:
         raise SystemExit("--blocks must be at least --run, --run at least 1")
+    if a.field_bank:
+        fshapes = [fs_[:4] for fs_ in parse_field_shapes([it if it.count(",") == 4 else it + ",1" for it in a.field_shapes])]
+        if any(S < 3 or S > 65536 for S in a.sets):
+            raise SystemExit("--field-bank: --sets from 3 to 65536")
+        cases = [(fs_, S) for fs_ in fshapes for S in a.sets]
+        if a.dry_run:
+            for (nsrc, nch, nr, b), S in cases:
+                rf = field_bytes(nsrc, nch, nr, b)["response"]
+                print(json.dumps({"shape": [nsrc, nch, nr, b], "sets": S, "partitions": -(-nr // b), "response_bytes": S * rf,
+                                  "fits_4_gib": S * rf <= 4 << 30}))
+            return 0
+        import torch
+        from emagls_amd import _lib as L
+        lib = L.load()
+        rows = []
+        for (nsrc, nch, nr, b), S in cases:
+            rf = field_bytes(nsrc, nch, nr, b)["response"]
+            if S * rf > 4 << 30:    # the library refuses such a bank: the row says so
+                res = {"shape": [nsrc, nch, nr, b], "sets": S, "partitions": -(-nr // b), "response_mb_per_set": round(rf / 1e6, 1),
+                       "refused": "the bank's response spectra exceed 4 GiB (%.1f GB)" % (S * rf / 1e9)}
+            else:
+                res = run_field_bank_shape(lib, L, torch, nsrc, nch, nr, b, S, a.blocks, a.warm, a.run)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(field_bank_markdown(rows, torch.cuda.get_device_name(0)))
+        return 0
     if a.field:
         fshapes = parse_field_shapes(a.field_shapes)
         if a.dry_run:
