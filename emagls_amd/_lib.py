@@ -72,6 +72,12 @@ SYMBOLS = {
     "emagls_debug_factor": (C.c_int, [C.POINTER(DebugFactorArgs)]),
     "emagls_debug_factor_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
+    "emagls_debug_gram": (C.c_int, [C.c_void_p, c_i64, C.c_int, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "emagls_debug_gram_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "emagls_debug_gram_from_g": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "emagls_debug_gram_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "emagls_debug_twiddles": (C.c_int, [C.c_int, C.c_void_p]),
     "emagls_debug_filter_epilogue": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.c_double, C.c_void_p, C.c_void_p]),

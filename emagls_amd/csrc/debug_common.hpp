@@ -1,4 +1,4 @@
-// What the debug entries (factor_debug.hip, fft_debug.hip) share: the sentinel their outputs are filled with before a launch, and the
+// What the debug entries (factor_debug.hip, fft_debug.hip, gram_debug.hip) share: the sentinel their outputs are filled with before a launch, and the
 // filling of one call's device buffers (a Scratch of device_mem.hpp).
 #pragma once
 #include <algorithm>

@@ -137,6 +137,38 @@ int emagls_debug_factor(const emagls_debug_factor_args* args);
  * s_reg = 1 / max(s, reg_c s_max); sv [nbins][C], sweeps [nbins]; status [4]: [2] = 1 and [3] = the highest bin with s_max > cond_limit s_min. */
 int emagls_debug_factor_gram(const void* A, int nbins, int C, const int* route, int jrun, double reg_c, double cond_limit, void* M, double* sv, int* sweeps,
                              int* status);
+/* The Gram route of the array designs, step by step, on the caller's arrays: the launchers the designs use (launch_gram, launch_gram_kmat,
+ * launch_gram_gemm, launch_gram_from_g, launch_gram_solve) with their own dispatch.  Host arrays, row major, complex ones interleaved;
+ * synchronous; outputs are filled with the NaN of EMAGLS_DEBUG_SENTINEL_BITS (int outputs with -1) before the launch unless said otherwise;
+ * what a plan zero-fills once is zero-filled here, with the plan's padded leading dimensions.  No entry takes more than 1 GiB of device
+ * memory; arguments outside the ranges below: EMAGLS_ERR_ARG before the device is touched.  round_up(x, m): the next multiple of m.
+ *   emagls_debug_gram: Yc [D][ld], real (is_cplx 0) or complex -> G [S][S] = Yc^H Yc and R [Sh][Sh], its leading block.  The device copy of
+ *     Yc has gram_dpad rows, those from D on zero.  G and R hold the upper BLOCK triangle (64 x 64 tiles; inside a diagonal tile both
+ *     triangles), zeros below it.  1 <= Sh <= S <= ld <= 8192, 1 <= D <= 65536.
+ *   emagls_debug_gram_assemble: A_k = sum_{n,n'} conj(b_n(k)) b_n'(k) K_nn', K_nn' = conj(E_n) Gy[n,n'] E_n'^T, for the bins kb0 ... kb0+nbins-1,
+ *     as packed Hermitian rows.  Gy [S][S], S = nOrd^2, only its upper triangle is read; E [C][ldE], ldE >= S; bn [P][nOrd] complex; bin P-1
+ *     (Nyquist) takes real(b_n); real or complex arithmetic of Gy and E by is_cplx.  Outputs, with Kp = round_up(nOrd^2, 4),
+ *     ldK = round_up(C^2, 64), ldC = round_up(P, 64):
+ *       F (optional) [nOrd][C][ldE], F[n][c][s] = sum_{j in order n} Gy(s, j) E[c][j] for s < (n+1)^2, the rest keeps the sentinel;
+ *       Kmat [Kp][ldK], zero-filled first: row n = (K_nn + K_nn^H) / 2, rows nOrd + 2 q and nOrd + 2 q + 1 = K_nn' + K_nn'^H and
+ *         i (K_nn' - K_nn'^H) for the q-th pair n < n' in lexicographic order; a Hermitian X [C][C] is packed into C^2 reals as
+ *         P[c C + c'] = Re X[c][c'] for c <= c' and Im X[c'][c] for c > c';
+ *       Cf [Kp][ldC], zero-filled first: Cf[row][k - kb0] = the coefficient of that row, |b_n|^2, Re and Im of conj(b_n) b_n';
+ *       Apk [nbins][ldK] = Cf^T Kmat (FP64 MFMA over all Kp rows: the zero rows of Kmat and Cf are part of the product).
+ *     Kmat_in non-null (Gy and E null): the product alone, on the caller's Kmat_in [Kp][ldK] taken as it is, pad rows included.
+ *     1 <= C <= 32, 1 <= nOrd <= 96, 1 <= nbins, 0 <= kb0, kb0 + nbins <= P <= 8192.
+ *   emagls_debug_gram_from_g: G [nbins + kb0 - g0][C][ldD] complex, bin k at slot k - g0 -> Apk [nbins][round_up(C^2, 64)], row k - kb0 the
+ *     packed A_k = G_k^H G_k over the D directions.  1 <= C <= 32, 1 <= D <= ldD <= 65536, 0 <= g0 <= kb0, 1 <= nbins <= 8192.
+ *   emagls_debug_gram_solve: Apk [nbins][ldA] packed, ldA >= C^2 -> for every bin k = kb0 + i the direct inverse M_k = A_k^-1 (route 2) where
+ *     (||A||_F ||A^-1||_F)^2 <= 1 / reg_c^4 certifies cond_2(A_k) <= 1 / reg_c^2, else the unpacked A_k for the Jacobi kernel (route 1).  With
+ *     P = kb0 + nbins: Mw and R2w [P][C][C] complex, bin k at slot k - 1; sv [P][C] (route 2: sv[k][0] = ||A||_F^(1/2) >= s_max, the others
+ *     ||A^-1||_F^(-1/2) <= s_min); route [P]; sweeps [P] (route 2: 0).  1 <= C <= 32, 1 <= kb0, 1 <= nbins, P <= 8192, 0 < reg_c <= 1. */
+int emagls_debug_gram(const void* Yc, int64_t D, int S, int64_t ld, int is_cplx, int Sh, void* G, void* R);
+int emagls_debug_gram_assemble(const void* Gy, const void* E, int ldE, const void* bn, int C, int nOrd, int P, int kb0, int nbins, int is_cplx,
+                               const double* Kmat_in, void* F, double* Kmat, double* Cf, double* Apk);
+int emagls_debug_gram_from_g(const void* G, int D, int C, int64_t ldD, int kb0, int g0, int nbins, double* Apk);
+int emagls_debug_gram_solve(const double* Apk, int ldA, int C, int kb0, int nbins, double reg_c, void* Mw, void* R2w, double* sv, int* route,
+                            int* sweeps);
 /* The transforms at both ends of a design on the caller's arrays: the launchers the designs use, with their own choice of kernel for the
  * shape (radix-2 in LDS for a power of two, wave-private at nfft 1024, direct sums otherwise) and the table of launch_twiddles.  Host
  * arrays, complex ones interleaved; synchronous; every output is filled with the NaN of EMAGLS_DEBUG_SENTINEL_BITS before the launch.

@@ -198,3 +198,48 @@ def test_debug_fft_entries_reject_bad_arguments(lib):
     tw = np.zeros(16, dtype=np.complex128)
     for n, t in ((1, tw), (8193, tw), (16, None)):
         assert lib.emagls_debug_twiddles(n, p(t)) == L.ERR_ARG
+
+
+def test_debug_gram_entries_reject_bad_arguments(lib):
+    """emagls_debug_gram, emagls_debug_gram_assemble, emagls_debug_gram_from_g and emagls_debug_gram_solve validate before they touch the
+    device (no GPU is needed to be refused): the sizes within their ranges, one input form of the assembly, the 1 GiB cap, the pointers set."""
+    from emagls_amd import _lib as L
+    p = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+    S, D, ld = 5, 7, 8
+    Y, Gm, Rm = np.zeros((D, ld)), np.zeros((S, S)), np.zeros((S, S))
+
+    def gram(y=Y, D_=D, S_=S, ld_=ld, cplx=0, Sh=3, g=Gm, r=Rm):
+        return lib.emagls_debug_gram(p(y), D_, S_, ld_, cplx, Sh, p(g), p(r))
+    for kw in (dict(y=None), dict(g=None), dict(r=None), dict(cplx=2), dict(cplx=-1), dict(S_=0), dict(ld_=S - 1), dict(ld_=8193), dict(Sh=0), dict(Sh=S + 1),
+               dict(D_=0), dict(D_=65537), dict(S_=8192, ld_=8192, cplx=1)):
+        assert gram(**kw) == L.ERR_ARG, kw
+    assert gram(S_=8192, ld_=8192, cplx=1) == L.ERR_ARG and b"1 GiB" in lib.emagls_last_error()
+
+    C_, nO, P = 2, 3, 4
+    Gy, E, bn = np.zeros((9, 9)), np.zeros((C_, 16)), np.zeros((P, nO), dtype=np.complex128)
+    F, K, Cf, A = np.zeros((nO, C_, 16)), np.zeros((12, 64)), np.zeros((12, 64)), np.zeros((3, 64))
+
+    def asm(gy=Gy, e=E, ldE=16, b=bn, C=C_, nOrd=nO, P_=P, kb0=1, nbins=3, cplx=0, kin=None, f=F, k=K, cf=Cf, a=A):
+        return lib.emagls_debug_gram_assemble(p(gy), p(e), ldE, p(b), C, nOrd, P_, kb0, nbins, cplx, p(kin), p(f), p(k), p(cf), p(a))
+    for kw in (dict(b=None), dict(k=None), dict(cf=None), dict(a=None), dict(gy=None), dict(e=None), dict(kin=K), dict(kin=K, gy=None, e=None), dict(cplx=2),
+               dict(C=0), dict(C=33), dict(nOrd=0), dict(nOrd=97), dict(nbins=0), dict(kb0=-1), dict(kb0=2), dict(P_=8193), dict(ldE=8), dict(ldE=16385)):
+        assert asm(**kw) == L.ERR_ARG, kw
+    assert asm(kin=K) == L.ERR_ARG and b"Kmat_in" in lib.emagls_last_error()
+
+    Gk, Ak = np.zeros((4, C_, 8), dtype=np.complex128), np.zeros((3, 64))
+
+    def from_g(g=Gk, D_=5, C=C_, ldD=8, kb0=2, g0=1, nbins=3, a=Ak):
+        return lib.emagls_debug_gram_from_g(p(g), D_, C, ldD, kb0, g0, nbins, p(a))
+    for kw in (dict(g=None), dict(a=None), dict(C=0), dict(C=33), dict(D_=0), dict(ldD=4), dict(ldD=65537), dict(g0=-1), dict(g0=3), dict(nbins=0),
+               dict(nbins=8193), dict(kb0=8193, g0=8193), dict(C=32, D_=65536, ldD=65536, nbins=64)):
+        assert from_g(**kw) == L.ERR_ARG, kw
+
+    Ap, Mw, R2, sv = np.zeros((3, 64)), np.zeros((4, C_, C_), dtype=np.complex128), np.zeros((4, C_, C_), dtype=np.complex128), np.zeros((4, C_))
+    rt, sw = np.zeros(4, dtype=np.int32), np.zeros(4, dtype=np.int32)
+
+    def solve(a=Ap, ldA=64, C=C_, kb0=1, nbins=3, reg_c=0.01, m=Mw, r2=R2, s=sv, r=rt, w=sw):
+        return lib.emagls_debug_gram_solve(p(a), ldA, C, kb0, nbins, reg_c, p(m), p(r2), p(s), p(r), p(w))
+    for kw in (dict(a=None), dict(m=None), dict(r2=None), dict(s=None), dict(r=None), dict(w=None), dict(C=0), dict(C=33), dict(ldA=3), dict(ldA=4097),
+               dict(kb0=0), dict(nbins=0), dict(kb0=8000, nbins=193), dict(reg_c=0.0), dict(reg_c=-0.01), dict(reg_c=1.5), dict(reg_c=float("nan"))):
+        assert solve(**kw) == L.ERR_ARG, kw
+    assert solve(kb0=0) == L.ERR_ARG and b"kb0" in lib.emagls_last_error()
