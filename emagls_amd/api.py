@@ -19,6 +19,7 @@ hL/hR are [numSamples x numDirections]; filters come back [len x numChannels].
     getSH / sphModalCoeffs  the un-vendored third-party functions the above call
     getCH / getSMAIRMatrix  dependencies/getCH.m:1, dependencies/getSMAIRMatrix.m:1 (the array model materialised)
     getRenderedHrtfs        this project's: what a filter set renders per direction, and its error metrics
+    getArrayIrs             this project's: impulse responses of the simulated array to plane-wave components
 
 A custom `shFunction` (a callable with getSH's signature: shFunction(N, [azi zen], shDefinition) -> [dirs x (N+1)^2]) cannot
 cross the C ABI as a handle: it is evaluated here, at the simulation order the library reports, and its matrices go through the
@@ -1347,3 +1348,57 @@ def getRenderedHrtfs(wL, wR, model, dirsAziZenRad, fs, *, order=None, micRadius=
     if not many:
         res = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
     return RenderedHrtfs(**res)
+
+
+def _components(sources):
+    """The two forms of `sources` as CSR: ([Q+1] int64 offsets, azi, zen, delay or None, gain or None)."""
+    if not isinstance(sources, (list, tuple)) or (len(sources) and all(np.ndim(a) == 1 and np.size(a) == 2 for a in sources)):
+        sources = np.asarray(sources, dtype=np.float64)    # (an array, or rows of (azi, zen) written as a list)
+    if isinstance(sources, np.ndarray):
+        if sources.ndim != 2 or sources.shape[1] != 2 or sources.shape[0] < 1:
+            raise ValueError("sources must be a [Q x 2] array of directions, or a list of [J x 2|3|4] arrays (azi, zen, delay, gain)")
+        return np.arange(sources.shape[0] + 1, dtype=np.int64), _vec(sources[:, 0])[0], _vec(sources[:, 1])[0], None, None
+    arrs = [np.asarray(a, dtype=np.float64) for a in sources]
+    if not arrs:
+        raise ValueError("sources must hold at least one source")
+    arrs = [a.reshape(0, 2) if a.size == 0 else a for a in arrs]
+    if any(a.ndim != 2 or a.shape[1] not in (2, 3, 4) for a in arrs):
+        raise ValueError("every source must be a [J x 2|3|4] array with the columns azi, zen, delay, gain")
+    ptr = np.zeros(len(arrs) + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum([a.shape[0] for a in arrs])
+    col = lambda i, fill: np.ascontiguousarray(np.concatenate([a[:, i] if a.shape[1] > i else np.full(a.shape[0], fill) for a in arrs]))  # noqa: E731
+    delay = col(2, 0.0) if any(a.shape[1] > 2 for a in arrs) else None
+    gain = col(3, 1.0) if any(a.shape[1] > 3 for a in arrs) else None
+    return ptr, col(0, 0.0), col(1, 0.0), delay, gain
+
+
+def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4, encoder=None, nfft=None):
+    """Impulse responses of the simulated rigid-sphere array (the array of getSMAIRMatrix) to sources that are sums of plane-wave
+    components (include/emagls.h, emagls_array_irs).  `sources` is a [Q x 2] array of directions (azi, zen),
+    one unit plane wave each -- a direction bank for a moving virtual source -- or a list of Q arrays [J_q x 2|3|4] with the columns
+    azi, zen, delay in samples (default 0) and gain (default 1): an array room response from the image sources the caller lists (a
+    source may be empty).  preDelay (samples, required) makes the acausal part of the sphere's response causal.  micGridAziZenRad
+    [M x 2]; `order` only enters the simulation order max(order, ceil(fs pi r / 343)); `encoder` [C x M] is what arrayEncoder(...)
+    returns (absent: the raw microphones, C = M).  nfft: a power of two from 8 to 65536, default the smallest one >= 2 irLen.
+    Returns [Q x irLen x C], complex with a complex encoder: the `rirs` of SourceFieldStream for Q sources, or [:, None] for a bank
+    of Q sets of one source."""
+    ptr, azi, zen, delay, gain = _components(sources)
+    grid = np.asarray(micGridAziZenRad, dtype=np.float64)
+    if grid.ndim != 2 or grid.shape[1] != 2:
+        raise ValueError("micGridAziZenRad must be [numMics x 2]")
+    maz, _p = _vec(grid[:, 0])
+    mzn, _p = _vec(grid[:, 1])
+    M, Q, nr = maz.size, ptr.size - 1, int(irLen)
+    Cc, e_c, pe = M, False, None
+    if encoder is not None:
+        if np.ndim(encoder) != 2 or np.shape(encoder)[1] != M:
+            raise ValueError("encoder must be [numChannels x numMics] with one column per microphone (%d)" % M)
+        enc, pe, e_c, _m = _encoder(encoder, np.shape(encoder)[0])
+        Cc = enc.shape[0]
+    if nr < 1:
+        raise ValueError("irLen must be positive")
+    out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    L.check(L.load().emagls_array_irs(float(fs), float(micRadius), int(order), vp(maz), vp(mzn), M, pe, 1 if e_c else 0, Cc, Q, vp(ptr),
+                                      vp(azi), vp(zen), vp(delay), vp(gain), float(preDelay), int(nfft) if nfft else 0, nr, vp(out)))
+    return np.ascontiguousarray(out.transpose(0, 2, 1))

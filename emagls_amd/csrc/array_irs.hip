@@ -1,0 +1,312 @@
+// Array impulse responses: plane-wave components through the simulated rigid-sphere array (the host entry is
+// array_irs_api.hip).  Per source q, microphone m and bin k
+//
+//   H_q(k, m) = sum_j g_j exp(-2 pi i k d_j / nfft) sum_{n <= N} b'_n(k) P_n(u_j . v_m),    b'_n(k) = -b_n(k r) (2n+1) / (4 pi),
+//
+// the column pwGrid_k(:, dir_j) of the emagls2 operand by the addition theorem (dependencies/getSMAIRMatrix.m:102-121), delayed by
+// d_j = tau_j + tau_0 samples.  The work is ncomp * M * P * (N+1) complex-by-real multiply-adds in FP64, so the main kernel is a vector
+// kernel in the manner of sweep_reg.hip: a wave owns one microphone and AIR_R consecutive bins, the b' of those bins come through
+// wave-uniform loads (the four waves of a workgroup share the bins and take four microphones), and one three-term Legendre
+// recurrence per component feeds AIR_R complex accumulators.  Then the phases: one sincospi for the block's first bin, one for the
+// step, AIR_R - 1 complex products; the integer part of d_j is multiplied with k modulo nfft in integers, so the argument is exact
+// at nfft = 65536.
+//
+// TWO FORMS, chosen PER SOURCE by its own component count J_q (so that a source's bits do not depend on its neighbours):
+//   J_q >  AIR_LANE_SOURCE_MAX   lane = component: a lane sums the components j = lane, lane + 64, ... in that order, one wave
+//                                reduction (wave_sum: DPP inside the rows, then the four rows in a fixed order) per bin
+//   J_q <= AIR_LANE_SOURCE_MAX   lane = source: the short sources of a call are listed, a lane walks its own source's components in
+//                                order, no reduction (a direction bank is J = 1 for thousands of sources; an empty source gives zeros)
+// No atomics; every order is fixed.
+//
+// The rest of the chain: air_modes_kernel (the factor (2n+1) on launch_modal_bn's output, real part in the last bin, and the
+// recurrence's coefficients), air_prepare_kernel (unit vectors, delays split into integer and fraction), and the inverse real
+// transform per (source, channel) with the encoder in its load: on the LDS passes of lds_fft.hpp up to nfft = 4096
+// (air_irfft_kernel), through hipFFT's Z2D above (air_encode_kernel, air_pick_kernel around it).
+#include "kernels.hpp"
+#include "lds_fft.hpp"
+
+namespace emagls {
+
+constexpr int AIR_R = 8;   // bins per wave
+
+// rec[2 n] = (2n+1)/(n+1), rec[2 n + 1] = n/(n+1): P_(n+1) = rec[2n] x P_n - rec[2n+1] P_(n-1).  bn [N+1][Pld] comes as
+// -b_n / (4 pi) (launch_modal_bn's out_scale) with zeros beyond P.
+__global__ void __launch_bounds__(256) air_modes_kernel(int N, int P, int64_t Pld, cplx* __restrict__ bn, double* __restrict__ rec) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= N) {
+        rec[2 * i] = (double)(2 * i + 1) / (double)(i + 1);
+        rec[2 * i + 1] = (double)i / (double)(i + 1);
+    }
+    if (i >= (int64_t)(N + 1) * P) return;
+    const int n = (int)(i / P), k = (int)(i % P);
+    cplx v = bn[(int64_t)n * Pld + k];
+    const double s = (double)(2 * n + 1);
+    v.x *= s;
+    v.y = k == P - 1 ? 0.0 : v.y * s;   // getSMAIRMatrix.m:115-117
+    bn[(int64_t)n * Pld + k] = v;
+}
+
+// unit vectors [3][n] of directions (azimuth, zenith)
+__global__ void __launch_bounds__(256) air_units_kernel(int64_t n, const double* __restrict__ azi, const double* __restrict__ zen,
+                                                       double* __restrict__ u) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double sa, ca, sz, cz;
+    sincos(azi[i], &sa, &ca);
+    sincos(zen[i], &sz, &cz);
+    u[i] = sz * ca; u[n + i] = sz * sa; u[2 * n + i] = cz;
+}
+
+// d_j = tau_j + tau_0 as an integer below nfft and a fraction in [0, 1): the integer parts are added as integers, the fractions as
+// doubles (the host has checked 0 <= d_j <= nfft - 1)
+__global__ void __launch_bounds__(256) air_delays_kernel(int64_t n, const double* __restrict__ delay, double pre_delay, int nfft,
+                                                        int* __restrict__ dint, double* __restrict__ dfrac) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double t = delay ? delay[i] : 0.0;
+    const double ti = floor(t), pi = floor(pre_delay);
+    const double f = (t - ti) + (pre_delay - pi), fi = floor(f);
+    dint[i] = (int)(((int64_t)ti + (int64_t)pi + (int64_t)fi) & (nfft - 1));
+    dfrac[i] = f - fi;
+}
+
+struct AirArgs {
+    const cplx* bn;        // [N+1][Pld]
+    const double* rec;     // [2 (N+1)]
+    const double* u;       // [3][ncomp]
+    const double* v;       // [3][M]
+    const int* dint;       // [ncomp]
+    const double* dfrac;   // [ncomp]
+    const double* gain;    // [ncomp] or null
+    const int64_t* ptr;    // [Q+1]
+    const int* list;       // the sources of this launch
+    int nlist, N, M, P, nfft;
+    int64_t Pld, ncomp;
+    cplx* H;               // [Q][M][Pld]
+};
+
+// one component's terms of the AIR_R bins from k0: sum[r] += g w_r sum_n b'_n(k0 + r) P_n(x)
+__device__ __forceinline__ void air_component(const AirArgs& a, int k0, int64_t j, double vx, double vy, double vz, cplx (&sum)[AIR_R]) {
+    const double x = fma(a.u[2 * a.ncomp + j], vz, fma(a.u[a.ncomp + j], vy, a.u[j] * vx));
+    cplx acc[AIR_R];
+    const cplx* __restrict__ b = a.bn + k0;
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) acc[r] = b[r];   // n = 0: P_0 = 1
+    double p0 = 1.0, p1 = x;
+    for (int n = 1; n <= a.N; ++n) {
+        b += a.Pld;
+#pragma unroll
+        for (int r = 0; r < AIR_R; ++r) cfma(acc[r], b[r], p1);
+        const double p2 = fma(a.rec[2 * n] * x, p1, -(a.rec[2 * n + 1] * p0));
+        p0 = p1; p1 = p2;
+    }
+    // phases in half turns: -2 ((k dint mod nfft) + k dfrac) / nfft
+    const unsigned di = (unsigned)a.dint[j];
+    const double df = a.dfrac[j], inv = 1.0 / (double)a.nfft, g = a.gain ? a.gain[j] : 1.0;
+    const unsigned ki = ((unsigned)k0 * di) & (unsigned)(a.nfft - 1);
+    cplx w, s;
+    sincospi(-2.0 * (((double)ki + (double)k0 * df) * inv), &w.y, &w.x);
+    sincospi(-2.0 * (((double)di + df) * inv), &s.y, &s.x);
+    w = g * w;
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) {
+        cfma(sum[r], w, acc[r]);
+        w = w * s;
+    }
+}
+
+// grid (bin blocks, ceil(M / 4), sources of the list); 256 threads: wave w takes the microphone 4 blockIdx.y + w
+__global__ void __launch_bounds__(256) air_lane_component_kernel(AirArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int m = blockIdx.y * 4 + wave;
+    if (m >= a.M) return;
+    const int q = a.list[blockIdx.z], k0 = blockIdx.x * AIR_R;
+    const double vx = a.v[m], vy = a.v[a.M + m], vz = a.v[2 * a.M + m];
+    cplx sum[AIR_R];
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) sum[r] = mk(0.0, 0.0);
+    const int64_t j1 = a.ptr[q + 1];
+    for (int64_t j = a.ptr[q] + lane; j < j1; j += 64) air_component(a, k0, j, vx, vy, vz, sum);
+    cplx* out = a.H + ((int64_t)q * a.M + m) * a.Pld;
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) {
+        cplx t = wave_sum(sum[r]);
+        const int k = k0 + r;
+        if (k == a.P - 1) t.y = 0.0;   // the last bin's value is the real part of the sum
+        if (lane == 0 && k < a.P) out[k] = t;
+    }
+}
+
+// grid (bin blocks, ceil(M / 4), ceil(nlist / 64)): lane l takes the source list[64 blockIdx.z + l]
+__global__ void __launch_bounds__(256) air_lane_source_kernel(AirArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int m = blockIdx.y * 4 + wave;
+    if (m >= a.M) return;
+    const int i = blockIdx.z * 64 + lane, k0 = blockIdx.x * AIR_R;
+    if (i >= a.nlist) return;
+    const int q = a.list[i];
+    const double vx = a.v[m], vy = a.v[a.M + m], vz = a.v[2 * a.M + m];
+    cplx sum[AIR_R];
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) sum[r] = mk(0.0, 0.0);
+    const int64_t j1 = a.ptr[q + 1];
+    for (int64_t j = a.ptr[q]; j < j1; ++j) air_component(a, k0, j, vx, vy, vz, sum);
+    cplx* out = a.H + ((int64_t)q * a.M + m) * a.Pld;
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) {
+        const int k = k0 + r;
+        if (k == a.P - 1) sum[r].y = 0.0;
+        if (k < a.P) out[k] = sum[r];
+    }
+}
+
+// the encoder in a load: X(k) = sum_m enc(c, m) H(k, m), m ascending, accumulated from 0 with fma; the real and the imaginary part of
+// enc as separate chains.  enc_re null: X = H(:, c)
+struct AirEnc {
+    const double* re;   // [C][M] column-major: enc(c, m) at c + C m
+    const double* im;   // null: a real encoder
+    int C, M;
+};
+__device__ __forceinline__ void air_encoded(const AirEnc& e, const cplx* __restrict__ Hq, int64_t Pld, int c, int k, cplx& zr, cplx& zi) {
+    zi = mk(0.0, 0.0);
+    if (!e.re) { zr = Hq[(int64_t)c * Pld + k]; return; }
+    zr = mk(0.0, 0.0);
+    for (int m = 0; m < e.M; ++m) {
+        const cplx h = Hq[(int64_t)m * Pld + k];
+        cfma(zr, e.re[c + e.C * m], h);
+        if (e.im) cfma(zi, e.im[c + e.C * m], h);
+    }
+}
+
+// out [Q][C][nr] (real, or interleaved complex with a complex encoder) = irfft over k at length nfft, first nr samples: one complex
+// inverse transform of Z = X_re + i X_im, both Hermitian-extended (the imaginary parts of bin 0 and of the last bin do not enter, as
+// in every inverse real transform).  grid (C, Q); LDS: the padded buffer and nfft / 2 twiddles
+__global__ void __launch_bounds__(512) air_irfft_kernel(const cplx* __restrict__ H, int64_t Pld, AirEnc e, int nfft, int log2n,
+                                                       const cplx* __restrict__ tw, int nr, void* __restrict__ out) {
+    extern __shared__ __align__(16) unsigned char air_smem[];
+    cplx* buf = reinterpret_cast<cplx*>(air_smem);
+    cplx* tws = buf + lds_fft_ix<true>(nfft);
+    const int c = blockIdx.x, half = nfft >> 1;
+    const int64_t q = blockIdx.y;
+    const cplx* Hq = H + q * e.M * Pld;
+    for (int j = threadIdx.x; j < half; j += blockDim.x) tws[j] = tw[j];
+    for (int k = threadIdx.x; k <= half; k += blockDim.x) {
+        cplx zr, zi;
+        air_encoded(e, Hq, Pld, c, k, zr, zi);
+        if (k == 0 || k == half) { zr.y = 0.0; zi.y = 0.0; }
+        buf[lds_fft_ix<true>((int)bitrev((unsigned)k, log2n))] = mk(zr.x - zi.y, zr.y + zi.x);
+        if (k > 0 && k < half) buf[lds_fft_ix<true>((int)bitrev((unsigned)(nfft - k), log2n))] = mk(zr.x + zi.y, zi.x - zr.y);
+    }
+    __syncthreads();
+    lds_fft_stages<true, true>(buf, tws, nfft, log2n, 1);
+    const double inv = 1.0 / (double)nfft;
+    const int64_t o = (q * e.C + c) * nr;
+    for (int t = threadIdx.x; t < nr; t += blockDim.x) {
+        const cplx v = buf[lds_fft_ix<true>(t)];
+        if (e.im) reinterpret_cast<cplx*>(out)[o + t] = mk(v.x * inv, v.y * inv);
+        else reinterpret_cast<double*>(out)[o + t] = v.x * inv;
+    }
+}
+
+// the long transforms: X [Q][planes][P] for hipFFT (planes = C, or 2 C: every channel's real-encoder and imaginary-encoder spectrum)
+__global__ void __launch_bounds__(256) air_encode_kernel(const cplx* __restrict__ H, int64_t Pld, AirEnc e, int P, cplx* __restrict__ X) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y, np = e.im ? 2 : 1;
+    const int64_t q = blockIdx.z;
+    if (k >= P) return;
+    cplx zr, zi;
+    air_encoded(e, H + q * e.M * Pld, Pld, c, k, zr, zi);
+    if (k == 0 || k == P - 1) { zr.y = 0.0; zi.y = 0.0; }
+    X[((q * e.C + c) * np) * P + k] = zr;
+    if (e.im) X[((q * e.C + c) * np + 1) * P + k] = zi;
+}
+
+// y [Q C][np][nfft] (unscaled inverse transforms) -> out [Q C][nr], real (np = 1) or interleaved complex (np = 2)
+__global__ void __launch_bounds__(256) air_pick_kernel(const double* __restrict__ y, int64_t rows, int np, int nfft, int nr, void* __restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t row = blockIdx.y;
+    if (t >= nr || row >= rows) return;
+    const double inv = 1.0 / (double)nfft;
+    const double* yr = y + row * np * nfft;
+    if (np == 2) reinterpret_cast<cplx*>(out)[row * nr + t] = mk(yr[t] * inv, yr[nfft + t] * inv);
+    else reinterpret_cast<double*>(out)[row * nr + t] = yr[t] * inv;
+}
+
+// ---------------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------------
+int air_bins_padded(int P) { return (int)(ceil_div(P, AIR_R) * AIR_R); }
+
+void launch_air_modes(int N, int P, int64_t Pld, void* bn, double* rec, hipStream_t st) {
+    air_modes_kernel<<<(unsigned)ceil_div(std::max<int64_t>((int64_t)(N + 1) * P, N + 1), 256), 256, 0, st>>>(N, P, Pld, (cplx*)bn, rec);
+    KERNEL_CHECK();
+}
+
+void launch_air_units(int64_t n, const double* azi, const double* zen, double* u, hipStream_t st) {
+    if (n <= 0) return;
+    air_units_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(n, azi, zen, u);
+    KERNEL_CHECK();
+}
+
+void launch_air_delays(int64_t n, const double* delay, double pre_delay, int nfft, int* dint, double* dfrac, hipStream_t st) {
+    if (n <= 0) return;
+    air_delays_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(n, delay, pre_delay, nfft, dint, dfrac);
+    KERNEL_CHECK();
+}
+
+void launch_air_main(const AirMain& m, hipStream_t st) {
+    AirArgs a{};
+    a.bn = (const cplx*)m.bn; a.rec = m.rec; a.u = m.u; a.v = m.v; a.dint = m.dint; a.dfrac = m.dfrac; a.gain = m.gain; a.ptr = m.ptr;
+    a.N = m.N; a.M = m.M; a.P = m.P; a.nfft = m.nfft; a.Pld = m.Pld; a.ncomp = m.ncomp; a.H = (cplx*)m.H;
+    const unsigned gx = (unsigned)(m.Pld / AIR_R), gy = (unsigned)ceil_div(m.M, 4);
+    // (grid.z stops at 65535: the lists go in slices)
+    for (int i0 = 0; i0 < m.n_long; i0 += 65535) {
+        a.list = m.list_long + i0; a.nlist = std::min(65535, m.n_long - i0);
+        air_lane_component_kernel<<<dim3(gx, gy, (unsigned)a.nlist), 256, 0, st>>>(a);
+        KERNEL_CHECK();
+    }
+    for (int i0 = 0; i0 < m.n_short; i0 += 65535 * 64) {
+        a.list = m.list_short + i0; a.nlist = std::min(65535 * 64, m.n_short - i0);
+        air_lane_source_kernel<<<dim3(gx, gy, (unsigned)ceil_div(a.nlist, 64)), 256, 0, st>>>(a);
+        KERNEL_CHECK();
+    }
+}
+
+static int air_log2(int n) { int l = 0; while ((1 << l) < n) ++l; return l; }
+
+void launch_air_irfft(const void* H, int64_t Pld, const double* enc_re, const double* enc_im, int C, int M, int64_t Q, int nfft,
+                      const void* tw, int nr, void* out, hipStream_t st) {
+    const AirEnc e{enc_re, enc_im, C, M};
+    const size_t sm = sizeof(cplx) * ((size_t)nfft + (nfft >> 4) + (size_t)nfft / 2);   // (lds_fft_ix<true>(nfft) elements, and the twiddles)
+    static PerDeviceOnce attr_once;   // (function attributes are per device)
+    if (attr_once.first()) HIP_CHECK(hipFuncSetAttribute((const void*)air_irfft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const int threads = nfft >= 2048 ? 512 : nfft >= 512 ? 256 : 64;
+    for (int64_t q0 = 0; q0 < Q; q0 += 65535) {
+        const int64_t nq = std::min<int64_t>(65535, Q - q0);
+        air_irfft_kernel<<<dim3((unsigned)C, (unsigned)nq), threads, sm, st>>>((const cplx*)H + q0 * M * Pld, Pld, e, nfft, air_log2(nfft),
+                                                                             (const cplx*)tw, nr, (char*)out + (size_t)q0 * C * nr * esz(enc_im != nullptr));
+        KERNEL_CHECK();
+    }
+}
+
+void launch_air_encode(const void* H, int64_t Pld, const double* enc_re, const double* enc_im, int C, int M, int64_t Q, int P, void* X,
+                       hipStream_t st) {
+    const AirEnc e{enc_re, enc_im, C, M};
+    const int np = enc_im ? 2 : 1;
+    for (int64_t q0 = 0; q0 < Q; q0 += 65535) {
+        const int64_t nq = std::min<int64_t>(65535, Q - q0);
+        air_encode_kernel<<<dim3((unsigned)ceil_div(P, 256), (unsigned)C, (unsigned)nq), 256, 0, st>>>((const cplx*)H + q0 * M * Pld, Pld, e, P,
+                                                                                                     (cplx*)X + q0 * C * np * P);
+        KERNEL_CHECK();
+    }
+}
+
+void launch_air_pick(const double* y, int64_t rows, int np, int nfft, int nr, void* out, hipStream_t st) {
+    for (int64_t r0 = 0; r0 < rows; r0 += 65535) {
+        const int64_t n = std::min<int64_t>(65535, rows - r0);
+        air_pick_kernel<<<dim3((unsigned)ceil_div(nr, 256), (unsigned)n), 256, 0, st>>>(y + r0 * np * nfft, n, np, nfft, nr,
+                                                                                       (char*)out + (size_t)r0 * nr * esz(np == 2));
+        KERNEL_CHECK();
+    }
+}
+
+}  // namespace emagls

@@ -367,6 +367,33 @@ void launch_rh_gemm(const double* Tt, int64_t ldR, const double* Yk, int64_t ldY
 void launch_rh_atf(const void* W, const void* A, int M, int P, int64_t D, int nsets, const RhOut& o, hipStream_t st);
 void launch_rh_reduce(const double* partial, int64_t nrows, int ntile, double* out, hipStream_t st);
 
+// ---- array_irs.hip: plane-wave components through the simulated array, as impulse responses
+constexpr int AIR_LANE_SOURCE_MAX = 16;   // a source of at most this many components runs in the lane = source form
+int air_bins_padded(int P);               // leading dimension of the bins (whole bin blocks of a wave)
+// bn [N+1][Pld] from launch_modal_bn with out_scale = -1/(4 pi), zeros beyond P: times 2n+1, real in the last bin; rec [2 (N+1)]
+void launch_air_modes(int N, int P, int64_t Pld, void* bn, double* rec, hipStream_t st);
+void launch_air_units(int64_t n, const double* azi, const double* zen, double* u, hipStream_t st);   // u [3][n]
+void launch_air_delays(int64_t n, const double* delay, double pre_delay, int nfft, int* dint, double* dfrac, hipStream_t st);
+struct AirMain {
+    const void* bn; const double* rec;
+    const double *u, *v;                   // unit vectors [3][ncomp], [3][M]
+    const int* dint; const double* dfrac;  // [ncomp]
+    const double* gain;                    // [ncomp], null: ones
+    const int64_t* ptr;                    // [Q+1]
+    const int *list_long, *list_short;     // sources above / up to AIR_LANE_SOURCE_MAX components
+    int n_long, n_short, N, M, P, nfft;
+    int64_t Pld, ncomp;
+    void* H;                               // [Q][M][Pld] complex
+};
+void launch_air_main(const AirMain& m, hipStream_t st);
+// out [Q][C][nr], real or (enc_im given) interleaved complex; enc_re null: C = M raw microphones.  nfft <= 4096
+void launch_air_irfft(const void* H, int64_t Pld, const double* enc_re, const double* enc_im, int C, int M, int64_t Q, int nfft,
+                      const void* tw, int nr, void* out, hipStream_t st);
+// X [Q][C][np][P], np = 2 with enc_im; and the first nr samples of y [rows][np][nfft] over nfft
+void launch_air_encode(const void* H, int64_t Pld, const double* enc_re, const double* enc_im, int C, int M, int64_t Q, int P, void* X,
+                       hipStream_t st);
+void launch_air_pick(const double* y, int64_t rows, int np, int nfft, int nr, void* out, hipStream_t st);
+
 // ---- host_pools.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool in host_internal.hpp)
 hipStream_t pool_stream_take();
 void pool_stream_give(hipStream_t st);

@@ -747,6 +747,37 @@ int emagls_rendered_hrtfs(int model, const void* wL, const void* wR, int w_is_co
                           int64_t atf_taps, int64_t nfft, const double* hL, const double* hR, int64_t nsamp, int64_t nhrir_sets,
                           const double* weights, void* Hhat, double* mag_err_db, double* ild_err_db, double* cov_hat, double* cov_ref);
 
+/* ---- array impulse responses: plane-wave components through the simulated array (this project's) ----
+ * The content that goes INTO the field stream: time-domain responses of the rigid-sphere array of getSMAIRMatrix to nsrc sources,
+ * each a sum of plane-wave components with a direction, a delay in samples and a real gain.  One component per source: a
+ * direction bank for a moving virtual source; many: an array room response from image sources the caller lists.
+ * With N = max(order, ceil(fs pi r / 343)) (getSMAIRMatrix.m:95; N <= 85), f_k = k fs / nfft, k = 0 .. nfft/2,
+ * beta_n(k) = -b_n(2 pi f_k r / 343) (the rigid sphere, the sign of :107), u_j and v_m the unit vectors of component j and microphone m:
+ *   H_q(k, m) = sum_j g_j exp(-2 pi i k (tau_j + pre_delay) / nfft) sum_{n <= N} beta_n(k) (2n+1)/(4 pi) P_n(u_j . v_m)
+ * -- by the addition theorem Y_mic(m, :) diag(sh_repToOrder(beta(k))) conj(getSH(N, dir_j)).', the column pwGrid_k(:, dir_j) of the
+ * emagls2 operand, in either basis.  In the last bin real(beta_n) is used (:115-117) and the bin's value is the real part of the sum.
+ * With an encoder, X_q(k, c) = sum_m enc(c, m) H_q(k, m).  out = irfft over k at length nfft, first nr samples, no window; a complex
+ * encoder gives complex taps (the real and the imaginary part of enc transformed separately and joined).
+ * mic_azi, mic_zen [nmics], 1 <= nmics <= 64.  enc [nch x nmics] as emagls_decode_stream_create_encoded takes it (column-major,
+ * interleaved complex with enc_is_complex), 1 <= nch <= 64; NULL: raw microphones, nch must equal nmics.
+ * Sources in CSR form: comp_ptr [nsrc + 1], comp_ptr[0] = 0, non-decreasing; source q owns the components comp_ptr[q] ..
+ * comp_ptr[q+1] - 1 of comp_azi, comp_zen, comp_delay (>= 0, fractional allowed; NULL: zeros) and comp_gain (NULL: ones).  A source
+ * without components gives zeros.  pre_delay >= 0 samples (fractional allowed) makes the acausal part of the sphere's response
+ * causal; a component with tau_j + pre_delay > nfft - 1 would wrap: EMAGLS_ERR_ARG.
+ * nfft: a power of two from 8 to 65536; 0: the smallest one >= 2 nr.  nr <= nfft taps are returned.
+ * out: nsrc arrays [nr x nch] one after the other, column-major -- the rir of emagls_field_stream_create, or of
+ * emagls_field_stream_create_bank for nsrc sets of one source; interleaved complex when enc_is_complex.
+ * Sums run in a fixed order without atomics: equal calls give equal bits, and source q of a call gives the bits of the call with
+ * that source alone.  Every argument is checked before the device is touched; a call whose device memory estimate passes 24 GiB is
+ * EMAGLS_ERR_UNSUPPORTED (split the sources over several calls).  Transforms up to 4096 points run in LDS, longer ones in hipFFT. */
+int emagls_array_irs(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                     const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr, const double* comp_azi,
+                     const double* comp_zen, const double* comp_delay, const double* comp_gain, double pre_delay, int64_t nfft, int64_t nr,
+                     void* out);
+/* Device-event time in ms of the main kernel (both forms' launches) of the calling thread's last completed emagls_array_irs call
+ * (tools/array_irs_timing.py); EMAGLS_ERR_ARG before the first one. */
+int emagls_array_irs_kernel_time(double* ms);
+
 /* ---- plan API: inputs resident in HBM, repeated execution (benchmarks, batches) ------------- */
 
 typedef struct emagls_plan emagls_plan;

@@ -791,6 +791,41 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         metric(1, mag, 2); metric(2, ild, 1); metric(3, ch, 4); metric(4, cr, 4);
         return;
     }
+    if (c == "array_irs") {   // (compPtr, comps, fs, irLen, preDelay, micRadius, micGridAziZenRad, order, encoder, nfft)
+        // compPtr [numSources + 1]: zero-based offsets into the rows of comps [J x 4] = (azi, zen, delay, gain) (mex/getArrayIrs.m builds
+        // both); encoder [numChannels x numMics] or []; nfft or [].  irs = ...: [irLen x numChannels x numSources], as the library lays it
+        if (nrhs < 11) mexErrMsgIdAndTxt("eMagLS:arg", "array_irs needs 10 arguments ([] for no encoder and for the default nfft)");
+        auto given = [&](int i) { return prhs[i] && !mxIsEmpty(prhs[i]); };
+        const mwSize nptr = mxGetNumberOfElements(prhs[1]), J = mxGetM(prhs[2]);
+        if (nptr < 2) mexErrMsgIdAndTxt("eMagLS:arg", "compPtr must have numSources + 1 elements");
+        const double* pd = dbl(prhs[1], "compPtr");
+        std::vector<int64_t> ptr(nptr);
+        for (mwSize i = 0; i < nptr; ++i) {
+            if (pd[i] != std::floor(pd[i]) || std::fabs(pd[i]) > 9e15) mexErrMsgIdAndTxt("eMagLS:arg", "compPtr must hold integers");
+            ptr[i] = (int64_t)pd[i];
+        }
+        if (J && mxGetN(prhs[2]) != 4) mexErrMsgIdAndTxt("eMagLS:arg", "comps must be [J x 4] (azimuth, zenith, delay, gain)");
+        if (ptr[nptr - 1] != (int64_t)J) mexErrMsgIdAndTxt("eMagLS:arg", "compPtr must end at the number of rows of comps");
+        const double* comps = J ? dbl(prhs[2], "comps") : nullptr;
+        if (mxGetN(prhs[7]) != 2) mexErrMsgIdAndTxt("eMagLS:arg", "micGridAziZenRad must be [n x 2] (azimuth, zenith)");
+        const mwSize M = mxGetM(prhs[7]), nr = (mwSize)mxGetScalar(prhs[4]), Q = nptr - 1;
+        const double* mics = dbl(prhs[7], "micGridAziZenRad");
+        mwSize Cc = M;
+        bool ec = false;
+        if (given(9)) {
+            if (!mxIsDouble(prhs[9]) || mxGetN(prhs[9]) != M) mexErrMsgIdAndTxt("eMagLS:arg", "encoder must be [numChannels x numMics] with one column per microphone (%d)", (int)M);
+            Cc = mxGetM(prhs[9]);
+            ec = mxIsComplex(prhs[9]);
+        }
+        const mwSize od[3] = {nr, Cc, Q};
+        plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
+        const int rc = emagls_array_irs(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
+                                        given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
+                                        comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
+                                        mxGetScalar(prhs[5]), given(10) ? (int64_t)mxGetScalar(prhs[10]) : 0, (int64_t)nr, out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
     if (c == "encode") {
         if (nrhs < 5) mexErrMsgIdAndTxt("eMagLS:arg", "not enough input arguments");
         const mwSize n = mxGetM(prhs[1]), M = mxGetN(prhs[1]);

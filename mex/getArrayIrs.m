@@ -1,0 +1,39 @@
+function irs = getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, varargin)
+% Impulse responses of the simulated rigid-sphere array (the array of getSMAIRMatrix) to sources that are sums of plane-wave
+% components, on the MI355X library (DESIGN.md section 11; include/emagls.h, emagls_array_irs): per source, microphone and bin
+%   H(k, m) = sum_j g_j exp(-2 pi i k (tau_j + preDelay) / nfft) * pwGrid_k(m, dir_j),
+% pwGrid_k the operand of getEMagLs2Filters, then irfft at length nfft and the first irLen samples.
+%   irs = getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, 'name', value, ...)
+%   sources   [Q x 2] directions (azimuth, zenith), one unit plane wave each: a direction bank for a moving virtual source; or a
+%             cell of Q arrays [J_q x 2|3|4] with the columns azimuth, zenith, delay in samples (default 0), gain (default 1): an
+%             array room response from the image sources the caller lists (a source may be empty)
+%   preDelay  samples (fractional allowed): makes the acausal part of the sphere's response causal
+%   further names: order (4; only enters the simulation order max(order, ceil(fs*pi*micRadius/343))), encoder ([]: raw microphones;
+%             [numChannels x numMics], real or complex, e.g. pinv(getSH(order, micGridAziZenRad, shDefinition))), nfft ([]: the
+%             smallest power of two >= 2*irLen)
+%   irs       [irLen x numChannels x Q] (complex with a complex encoder): irs(:, :, q) is the rir of sourceFieldStream
+p = struct('order', 4, 'encoder', [], 'nfft', []);
+for i = 1:2:numel(varargin)
+    if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
+    p.(varargin{i}) = varargin{i + 1};
+end
+if ~iscell(sources)
+    if size(sources, 2) ~= 2; error('eMagLS:arg', 'sources must be [Q x 2] directions or a cell of [J x 2|3|4] arrays'); end
+    sources = num2cell(double(sources), 2);
+end
+Q = numel(sources);
+compPtr = zeros(Q + 1, 1);
+comps = zeros(0, 4);
+for q = 1:Q
+    s = double(sources{q});
+    if isempty(s); s = zeros(0, 2); end
+    if ~any(size(s, 2) == [2 3 4]); error('eMagLS:arg', 'every source must be [J x 2|3|4] (azimuth, zenith, delay, gain)'); end
+    J = size(s, 1);
+    if size(s, 2) < 3; s(:, 3) = zeros(J, 1); end
+    if size(s, 2) < 4; s(:, 4) = ones(J, 1); end
+    comps = [comps; s]; %#ok<AGROW>
+    compPtr(q + 1) = compPtr(q) + J;
+end
+irs = emagls_mex('array_irs', compPtr, comps, double(fs), double(irLen), double(preDelay), double(micRadius), double(micGridAziZenRad), ...
+    double(p.order), double(p.encoder), double(p.nfft));
+end

@@ -1,0 +1,114 @@
+"""Time of getArrayIrs (emagls_array_irs) on three shapes, em32 (32 microphones at 4.2 cm) at 48 kHz:
+  1. a bank of 2702 directions, one plane wave each, nfft = irLen = 512
+  2. the same behind the order-4 encoder (25 channels)
+  3. one room source of 20 000 components (delays up to 8000 samples, random gains) at nfft = 16384, irLen = 8192
+Seeded synthetic inputs; warm-up calls first; no profiler.  Per shape: the wall time of a call (host arrays in and out: a call
+includes its copies), the device-event time of the main kernel (emagls_array_irs_kernel_time), the real FMAs of the main kernel from
+the shapes -- 2 ncomp M (nfft/2 + 1) (N + 1) -- over that time as a share of the FP64 vector peak (README.md: 78.6 TFLOP/s, 39.3e12 FMA/s),
+and the time of the same spectra in NumPy (the Legendre sum of the definition; shape 3 on 64 of its bins, scaled).  Writes the table
+that profiles/r19_array_irs.md quotes, stamped with the kernel sources' hash.
+
+    python tools/array_irs_timing.py [reps] [out.md] [numpy: 0/1]
+"""
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FS, RADIUS, PEAK_FMA = 48000.0, 0.042, 39.3e12
+
+
+def unit(d):
+    return np.column_stack([np.sin(d[:, 1]) * np.cos(d[:, 0]), np.sin(d[:, 1]) * np.sin(d[:, 0]), np.cos(d[:, 1])])
+
+
+def random_dirs(rng, n):
+    return np.column_stack([rng.uniform(0, 2 * np.pi, n), np.arccos(rng.uniform(-1, 1, n))])
+
+
+def numpy_spectra(mics, comps, owner, nsrc, N, nfft, pre, bins):
+    """H [nsrc x len(bins) x M] of the definition for the components comps [J x 4] of the sources owner [J]; seconds."""
+    from oracle import emagls_oracle as O
+    t0 = time.perf_counter()
+    k = np.asarray(bins)
+    bn = -O.sphModalCoeffs(N, 2 * np.pi * (k * FS / nfft) / 343.0 * RADIUS).T * ((2 * np.arange(N + 1) + 1) / (4 * np.pi))[:, None]
+    last = k == nfft // 2
+    bn[:, last] = bn[:, last].real
+    x = unit(comps[:, :2]) @ unit(mics).T
+    p0, p1 = np.ones_like(x), x
+    A = bn[0][:, None, None] * p0
+    for n in range(1, N + 1):
+        A += bn[n][:, None, None] * p1
+        p0, p1 = p1, ((2 * n + 1) * x * p1 - n * p0) / (n + 1)
+    A *= (comps[:, 3][None, :] * np.exp(-2j * np.pi * k[:, None] * (comps[:, 2] + pre)[None, :] / nfft))[:, :, None]
+    H = np.zeros((nsrc, k.size, mics.shape[0]), dtype=complex)
+    np.add.at(H, owner, A.transpose(1, 0, 2))
+    H[:, last] = H[:, last].real
+    return H, time.perf_counter() - t0
+
+
+def main():
+    import emagls_amd as E
+    from emagls_amd import _lib as L
+    from oracle import emagls_oracle as O
+    from tools.csrc_hash import csrc_sha16
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    out = sys.argv[2] if len(sys.argv) > 2 else None
+    with_numpy = (sys.argv[3] != "0") if len(sys.argv) > 3 else True
+    rng = np.random.default_rng(19)
+    mics = random_dirs(rng, 32)
+    bank = random_dirs(rng, 2702)
+    room = [np.column_stack([random_dirs(rng, 20000), rng.uniform(0, 8000, 20000), rng.standard_normal(20000)])]
+    enc = E.arrayEncoder("sma", 4, mics[:, 0], mics[:, 1])
+    N = O.simulation_order(4, FS, RADIUS)
+    shapes = [("bank of 2702 directions, raw", bank, 512, 512, 64.0, None), ("bank of 2702 directions, order-4 encoder", bank, 512, 512, 64.0, enc),
+              ("room source of 20000 components", room, 8192, 16384, 64.0, None)]
+    lines = ["Kernel sources: csrc_sha16 %s.  Simulation order N = %d; %d calls per shape after 2 warm-up calls." % (csrc_sha16(), N, reps), "",
+             "| shape | nfft | ms per call (median) | min | main kernel ms | real FMAs | share of the FP64 vector peak | NumPy, same spectra |",
+             "|---|---|---|---|---|---|---|---|"]
+    ms = C.c_double(0.0)
+    for name, src, ir_len, nfft, pre, e in shapes:
+        call = lambda: E.getArrayIrs(src, FS, ir_len, pre, RADIUS, mics, encoder=e, nfft=nfft)   # noqa: E731  (returns host arrays: synchronised)
+        for _ in range(2):
+            call()
+        ts, ks = [], []
+        for _ in range(reps):
+            t = time.perf_counter()
+            call()
+            ts.append((time.perf_counter() - t) * 1e3)
+            L.check(L.load().emagls_array_irs_kernel_time(C.byref(ms)))
+            ks.append(ms.value)
+        if isinstance(src, np.ndarray):      # directions: one unit component per source
+            comps, nsrc = np.column_stack([src, np.zeros(len(src)), np.ones(len(src))]), len(src)
+            owner = np.arange(nsrc)
+        else:
+            comps, nsrc = np.vstack(src), len(src)
+            owner = np.repeat(np.arange(nsrc), [len(s) for s in src])
+        P = nfft // 2 + 1
+        fmas = 2.0 * comps.shape[0] * 32 * P * (N + 1)
+        k_ms = float(np.median(ks))
+        if not with_numpy:
+            np_text = "not measured"
+        elif comps.shape[0] * P > 5e6:
+            bins = np.arange(0, P, P // 64)[:64]
+            _, sec = numpy_spectra(mics, comps, owner, nsrc, N, nfft, pre, bins)
+            np_text = "%.0f s (from %.1f s on 64 of %d bins)" % (sec * P / 64, sec, P)
+        else:
+            _, sec = numpy_spectra(mics, comps, owner, nsrc, N, nfft, pre, np.arange(P))
+            np_text = "%.2f s" % sec
+        lines.append("| %s | %d | %.2f | %.2f | %.3f | %.3g | %.1f %% | %s |" % (name, nfft, np.median(ts), np.min(ts), k_ms, fmas,
+                                                                              100.0 * fmas / (k_ms * 1e-3) / PEAK_FMA, np_text))
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
