@@ -20,6 +20,7 @@ hL/hR are [numSamples x numDirections]; filters come back [len x numChannels].
     getCH / getSMAIRMatrix  dependencies/getCH.m:1, dependencies/getSMAIRMatrix.m:1 (the array model materialised)
     getRenderedHrtfs        this project's: what a filter set renders per direction, and its error metrics
     getArrayIrs             this project's: impulse responses of the simulated array to plane-wave components
+    getShoeboxComponents / getArrayRoomIrs   this project's: those components, and the responses, from a shoebox room (section 12)
 
 A custom `shFunction` (a callable with getSH's signature: shFunction(N, [azi zen], shDefinition) -> [dirs x (N+1)^2]) cannot
 cross the C ABI as a handle: it is evaluated here, at the simulation order the library reports, and its matrices go through the
@@ -1383,13 +1384,28 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
     Returns [Q x irLen x C], complex with a complex encoder: the `rirs` of SourceFieldStream for Q sources, or [:, None] for a bank
     of Q sets of one source."""
     ptr, azi, zen, delay, gain = _components(sources)
+    maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
+    Q = ptr.size - 1
+    out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
+    L.check(L.load().emagls_array_irs(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q, _addr(ptr),
+                                      _addr(azi), _addr(zen), _addr(delay), _addr(gain), float(preDelay), int(nfft) if nfft else 0, nr, _addr(out)))
+    return np.ascontiguousarray(out.transpose(0, 2, 1))
+
+
+def _addr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _array_side(micGridAziZenRad, encoder, irLen):
+    """The microphone grid, the encoder and the length of getArrayIrs / getArrayRoomIrs as the C ABI takes them (enc is returned to
+    keep the array behind its pointer pe alive)."""
     grid = np.asarray(micGridAziZenRad, dtype=np.float64)
     if grid.ndim != 2 or grid.shape[1] != 2:
         raise ValueError("micGridAziZenRad must be [numMics x 2]")
     maz, _p = _vec(grid[:, 0])
     mzn, _p = _vec(grid[:, 1])
-    M, Q, nr = maz.size, ptr.size - 1, int(irLen)
-    Cc, e_c, pe = M, False, None
+    M, nr = maz.size, int(irLen)
+    enc, Cc, e_c, pe = None, M, False, None
     if encoder is not None:
         if np.ndim(encoder) != 2 or np.shape(encoder)[1] != M:
             raise ValueError("encoder must be [numChannels x numMics] with one column per microphone (%d)" % M)
@@ -1397,8 +1413,57 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
         Cc = enc.shape[0]
     if nr < 1:
         raise ValueError("irLen must be positive")
+    return maz, mzn, M, enc, pe, e_c, Cc, nr
+
+
+def _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder):
+    """A shoebox room as the C ABI takes it: room_dim [3], wall_refl [6], array_pos [3], src_pos [Q x 3] (one position, or one per
+    row) and max_order (None: -1, no limit)."""
+    dim, _p = _vec(roomDim, 3, "roomDim")
+    refl, _p = _vec(wallReflection, 6, "wallReflection")
+    pos, _p = _vec(arrayPos, 3, "arrayPos")
+    src = np.ascontiguousarray(np.atleast_2d(np.asarray(sourcePos, dtype=np.float64)))
+    if src.ndim != 2 or src.shape[1] != 3 or src.shape[0] < 1:
+        raise ValueError("sourcePos must be [numSources x 3] (x, y, z per row)")
+    return dim, refl, pos, src, -1 if maxOrder is None else int(maxOrder)
+
+
+def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None):
+    """The image sources of a shoebox room as plane-wave components at the array's centre (include/emagls.h,
+    emagls_shoebox_components), enumerated on the device.  roomDim (Lx, Ly, Lz) in metres, one corner at the origin, axes as getSH's
+    (x front, y left, z up); wallReflection: six amplitude reflection coefficients in [-1, 1] for the walls x=0, x=Lx, y=0, y=Ly,
+    z=0, z=Lz; sourcePos [Q x 3] (or one position) and arrayPos inside the room; maxDelay in samples; maxOrder: the largest
+    reflection order kept (None: no limit).  Returns a list of Q arrays [J_q x 4] with the columns azi, zen, delay in samples and
+    gain (1 / distance times the walls' coefficients), in the definition's order: the `sources` of getArrayIrs."""
+    dim, refl, pos, src, mo = _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder)
+    Q = src.shape[0]
+    ptr = np.zeros(Q + 1, dtype=np.int64)
+    lib = L.load()
+    head = (_addr(dim), _addr(refl), _addr(pos), Q, _addr(src), float(fs), float(maxDelay), mo)
+    L.check(lib.emagls_shoebox_components(*head, 0, _addr(ptr), None, None, None, None))          # the counts
+    n = int(ptr[-1])
+    cols = np.zeros((4, max(n, 1)))
+    if n:
+        L.check(lib.emagls_shoebox_components(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3])))
+    return [np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)]
+
+
+def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4,
+                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False):
+    """Impulse responses of the simulated rigid-sphere array in a shoebox room (include/emagls.h,
+    emagls_array_room_irs): getArrayIrs(getShoeboxComponents(...), ...) bit for bit, with the components enumerated on the device
+    and fed to the responses' kernels there.  The room as in getShoeboxComponents (the array's whole sphere inside it), the array
+    as in getArrayIrs.  maxDelay (samples): default irLen - 1 - preDelay, the last component that lands inside the returned taps.
+    Returns [Q x irLen x C]; with returnCounts also the number of components of each source ([Q] int64)."""
+    dim, refl, pos, src, mo = _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder)
+    maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
+    Q = src.shape[0]
+    if maxDelay is None:
+        maxDelay = nr - 1 - float(preDelay)
     out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
-    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    L.check(L.load().emagls_array_irs(float(fs), float(micRadius), int(order), vp(maz), vp(mzn), M, pe, 1 if e_c else 0, Cc, Q, vp(ptr),
-                                      vp(azi), vp(zen), vp(delay), vp(gain), float(preDelay), int(nfft) if nfft else 0, nr, vp(out)))
-    return np.ascontiguousarray(out.transpose(0, 2, 1))
+    counts = np.zeros(Q, dtype=np.int64)
+    L.check(L.load().emagls_array_room_irs(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, _addr(dim),
+                                           _addr(refl), _addr(pos), Q, _addr(src), float(maxDelay), mo, float(preDelay), int(nfft) if nfft else 0,
+                                           nr, _addr(counts), _addr(out)))
+    out = np.ascontiguousarray(out.transpose(0, 2, 1))
+    return (out, counts) if returnCounts else out

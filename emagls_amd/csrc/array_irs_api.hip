@@ -1,6 +1,12 @@
-// C ABI of the array impulse responses (include/emagls.h, emagls_array_irs).  Host arrays in, host array out;
-// every argument is checked before the device is touched, and every array operation runs in the kernels of array_irs.hip, modal.hip
-// and fft.hip (the twiddles), with hipFFT's Z2D above 4096 points (the precedent of decode.hip above 2048 taps).  No CPU fallback.
+// C ABI of the array impulse responses (include/emagls.h; DESIGN.md sections 11 and 12): emagls_array_irs from listed components,
+// emagls_shoebox_components and emagls_array_room_irs from a shoebox room.  Host arrays in, host array out; every argument is
+// checked before the device is touched (a room call's scratch estimate, which needs the component count, after its count pass), and
+// every array operation runs in the kernels of array_irs.hip, shoebox.hip, modal.hip and fft.hip (the twiddles), with hipFFT's Z2D
+// above 4096 points (the precedent of decode.hip above 2048 taps).  No CPU fallback.
+//
+// Both response entries end in air_run: stages 1 to 4 on components that are already on the device.  emagls_array_irs uploads its
+// lists; emagls_array_room_irs enumerates them there and reads back only the nsrc + 1 offsets, for the two source lists of the main
+// kernel's forms.
 #include <hipfft/hipfft.h>
 
 #include <cmath>
@@ -19,20 +25,258 @@ constexpr int AIR_SIM_ORDER_MAX = 85;
 constexpr int64_t AIR_NFFT_MAX = 65536;
 constexpr int AIR_NFFT_LDS_MAX = 4096;     // the LDS transforms of lds_fft.hpp; hipFFT above
 constexpr size_t AIR_SCRATCH_MAX = (size_t)24 << 30;
+constexpr int64_t SBX_CAND_MAX = (int64_t)1 << 28;   // image-source candidates of one call, all sources together
 
 void fft_check(hipfftResult r, const char* what) {
     if (r != HIPFFT_SUCCESS) throw Error(EMAGLS_ERR_HIP, std::string("hipFFT error ") + std::to_string((int)r) + " in " + what);
 }
 
-// device events around the main kernel of a call, read after the call's synchronisation (emagls_array_irs_kernel_time)
+// device events around the kernels of a call, read after the call's synchronisation (emagls_array_irs_kernel_time,
+// emagls_shoebox_kernel_time)
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     EventPair() { HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b)); }
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
     EventPair(const EventPair&) = delete;
     EventPair& operator=(const EventPair&) = delete;
+    double ms() const {
+        float t = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&t, a, b));
+        return (double)t;
+    }
 };
-thread_local double g_main_ms = -1.0;
+thread_local double g_main_ms = -1.0, g_shoebox_ms = -1.0;
+
+// the checked arguments of a response call that do not concern its components, and the sizes that follow from them
+struct AirCall {
+    double fs, mic_radius, pre_delay;
+    const double *mic_azi, *mic_zen;
+    const void* enc;
+    bool ec, lds;                           // complex encoder; transforms in LDS
+    int N, nfft, P, M, C, np;
+    int64_t nsrc, nr, Pld, rows;
+    size_t out_bytes;
+    void* out;
+};
+
+AirCall air_check(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics, const void* enc,
+                  int enc_is_complex, int64_t nch, int64_t nsrc, double pre_delay, int64_t nfft_in, int64_t nr, void* out) {
+    if (!mic_azi || !mic_zen) throw Error(EMAGLS_ERR_ARG, "null pointer: microphone grid");
+    if (!out) throw Error(EMAGLS_ERR_ARG, "null pointer: out");
+    if (nsrc < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nsrc");
+    if (nmics < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nmics");
+    if (nmics > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 64 microphones are not supported");
+    if (nch < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nch");
+    if (nch > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 64 channels are not supported");
+    if (!enc && nch != nmics) throw Error(EMAGLS_ERR_ARG, "without an encoder nch must equal nmics (raw microphone responses)");
+    if (!(fs > 0) || !(mic_radius > 0) || !std::isfinite(fs) || !std::isfinite(mic_radius)) throw Error(EMAGLS_ERR_ARG, "fs and micRadius must be positive");
+    if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
+    if (nr < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nr");
+    if (nfft_in < 0) throw Error(EMAGLS_ERR_ARG, "nfft must be positive (0: the smallest power of two from 2*nr)");
+    int64_t nfft64 = nfft_in;
+    if (nfft64 == 0) {
+        nfft64 = 8;
+        while (nfft64 < 2 * nr && nfft64 <= AIR_NFFT_MAX) nfft64 *= 2;
+    }
+    if (nfft64 & (nfft64 - 1)) throw Error(EMAGLS_ERR_ARG, "nfft must be a power of two");
+    if (nfft64 < 8) throw Error(EMAGLS_ERR_UNSUPPORTED, "nfft below 8 is not supported");
+    if (nfft64 > AIR_NFFT_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "nfft above 65536 is not supported");
+    if (nr > nfft64) throw Error(EMAGLS_ERR_ARG, "nr exceeds nfft");
+    if (!(pre_delay >= 0.0) || !std::isfinite(pre_delay)) throw Error(EMAGLS_ERR_ARG, "pre_delay must be non-negative and finite");
+    AirCall c{};
+    c.fs = fs; c.mic_radius = mic_radius; c.pre_delay = pre_delay; c.mic_azi = mic_azi; c.mic_zen = mic_zen; c.enc = enc; c.out = out;
+    c.nfft = (int)nfft64; c.P = c.nfft / 2 + 1; c.M = (int)nmics; c.C = (int)nch; c.nsrc = nsrc; c.nr = nr;
+    if (pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "pre_delay beyond nfft - 1 would wrap");
+    c.N = std::max(order, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));     // getSMAIRMatrix.m:95
+    if (c.N > AIR_SIM_ORDER_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "simulation order above 85 is not supported");
+    c.ec = enc && enc_is_complex; c.lds = c.nfft <= AIR_NFFT_LDS_MAX;
+    c.np = c.ec ? 2 : 1;
+    c.Pld = air_bins_padded(c.P); c.rows = nsrc * c.C;
+    c.out_bytes = esz(c.ec) * (size_t)c.rows * nr;
+    return c;
+}
+
+// the device memory estimate of a call with ncomp components (in long double: the counts of a refused call may overflow 64 bits)
+void air_check_scratch(const AirCall& c, int64_t ncomp) {
+    const long double need = (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
+                             (long double)c.nsrc * 12 + (long double)c.out_bytes +
+                             (c.lds ? 0.0L : (c.enc ? (long double)c.rows * c.np * c.P * 16 : 0.0L) + (long double)c.rows * c.np * c.nfft * 8);
+    if (need > (long double)AIR_SCRATCH_MAX)
+        throw Error(EMAGLS_ERR_UNSUPPORTED, "the call needs more than 24 GiB of device memory; split the sources over several calls");
+}
+
+// stages 1 to 4 on components that are on the device: d_ptr [nsrc + 1] and its host copy h_ptr, d_azi, d_zen [ncomp], d_delay and
+// d_gain [ncomp] or null (zeros, ones).  The result is copied to c.out and the stream synchronised.
+void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* d_ptr, const double* d_azi, const double* d_zen,
+             const double* d_delay, const double* d_gain) {
+    const int N = c.N, nfft = c.nfft, P = c.P, M = c.M, C = c.C, np = c.np;
+    const int64_t nsrc = c.nsrc, nr = c.nr, Pld = c.Pld, rows = c.rows, ncomp = h_ptr[nsrc];
+    const double* enc = (const double*)c.enc;
+    // the two forms' source lists (array_irs.hip): by each source's own count
+    std::vector<int> list_long, list_short;
+    for (int64_t q = 0; q < nsrc; ++q) (h_ptr[q + 1] - h_ptr[q] > AIR_LANE_SOURCE_MAX ? list_long : list_short).push_back((int)q);
+    std::vector<double> e_re, e_im;
+    if (enc) {
+        e_re.resize((size_t)C * M);
+        if (c.ec) e_im.resize((size_t)C * M);
+        for (size_t i = 0; i < (size_t)C * M; ++i) {
+            e_re[i] = c.ec ? enc[2 * i] : enc[i];
+            if (c.ec) e_im[i] = enc[2 * i + 1];
+        }
+    }
+    // 1. mode coefficients b'_n(k) = -b_n (2n+1) / (4 pi) as rows [N+1][Pld]
+    cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)(N + 1) * Pld, true);
+    double* rec = s.get<double>(sizeof(double) * 2 * (N + 1));
+    const double kr_step = 2.0 * kPi * (c.fs / (double)nfft) / C_SOUND * c.mic_radius;
+    launch_modal_bn(N, P, nullptr, kr_step, -1.0 / (4.0 * kPi), bn, 1, Pld, s.st);     // bnAll = -sphModalCoeffs(...)  (:107)
+    launch_air_modes(N, P, Pld, bn, rec, s.st);
+    // 2. components and microphones
+    AirMain m{};
+    double* v = s.get<double>(sizeof(double) * 3 * M);
+    launch_air_units(M, s.put(c.mic_azi, (size_t)M), s.put(c.mic_zen, (size_t)M), v, s.st);
+    if (ncomp > 0) {
+        double* u = s.get<double>(sizeof(double) * 3 * (size_t)ncomp);
+        int* dint = s.get<int>(sizeof(int) * (size_t)ncomp);
+        double* dfrac = s.get<double>(sizeof(double) * (size_t)ncomp);
+        launch_air_units(ncomp, d_azi, d_zen, u, s.st);
+        launch_air_delays(ncomp, d_delay, c.pre_delay, nfft, dint, dfrac, s.st);
+        m.u = u; m.dint = dint; m.dfrac = dfrac;
+        m.gain = d_gain;
+    }
+    m.bn = bn; m.rec = rec; m.v = v;
+    m.ptr = d_ptr;
+    m.list_long = s.put_opt(list_long.data(), list_long.size());
+    m.list_short = s.put_opt(list_short.data(), list_short.size());
+    m.n_long = (int)list_long.size(); m.n_short = (int)list_short.size();
+    m.N = N; m.M = M; m.P = P; m.nfft = nfft; m.Pld = Pld; m.ncomp = ncomp;
+    cplx* H = s.get<cplx>(sizeof(cplx) * (size_t)nsrc * M * Pld);
+    m.H = H;
+    // 3. the main kernel
+    EventPair ev;
+    HIP_CHECK(hipEventRecord(ev.a, s.st));
+    launch_air_main(m, s.st);
+    HIP_CHECK(hipEventRecord(ev.b, s.st));
+    // 4. encoder and inverse real transform
+    const double* d_re = s.put_opt(e_re.data(), e_re.size());
+    const double* d_im = s.put_opt(e_im.data(), e_im.size());
+    void* d_out = s.get(c.out_bytes);
+    FftPlan plan;
+    if (c.lds) {
+        cplx* tw = s.get<cplx>(sizeof(cplx) * (size_t)nfft);
+        launch_twiddles(nfft, tw, s.st);
+        launch_air_irfft(H, Pld, d_re, d_im, C, M, nsrc, nfft, tw, (int)nr, d_out, s.st);
+    } else {
+        cplx* X = H;
+        int64_t ldx = Pld;
+        if (enc) {
+            X = s.get<cplx>(sizeof(cplx) * (size_t)rows * np * P);
+            ldx = P;
+            launch_air_encode(H, Pld, d_re, d_im, C, M, nsrc, P, X, s.st);
+        }
+        double* y = s.get<double>(sizeof(double) * (size_t)rows * np * nfft);
+        int nn[1] = {nfft}, inembed[1] = {P}, onembed[1] = {nfft};
+        fft_check(hipfftPlanMany(plan.fresh(), 1, nn, inembed, 1, (int)ldx, onembed, 1, nfft, HIPFFT_Z2D, (int)(rows * np)), "plan Z2D");
+        fft_check(hipfftSetStream(plan, s.st), "set stream");
+        fft_check(hipfftExecZ2D(plan, (hipfftDoubleComplex*)X, y), "exec Z2D");
+        launch_air_pick(y, rows, np, nfft, (int)nr, d_out, s.st);
+    }
+    HIP_CHECK(hipMemcpyAsync(c.out, d_out, c.out_bytes, hipMemcpyDeviceToHost, s.st));
+    s.sync();   // (the host vectors above live until their copies have run)
+    g_main_ms = ev.ms();
+}
+
+// ---- the shoebox room
+// The argument rules of a room; mic_radius 0 for the component lists alone.  Returns the search box and the tiling.
+ShoeboxArgs shoebox_check(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc, const double* src_pos,
+                          double fs, double mic_radius, double max_delay, int max_order) {
+    if (!room_dim || !wall_refl || !array_pos || !src_pos) throw Error(EMAGLS_ERR_ARG, "null pointer: room_dim, wall_refl, array_pos or src_pos");
+    if (nsrc < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nsrc");
+    if (!(fs > 0) || !std::isfinite(fs)) throw Error(EMAGLS_ERR_ARG, "fs must be positive");
+    if (!(max_delay > 0.0) || !std::isfinite(max_delay)) throw Error(EMAGLS_ERR_ARG, "max_delay must be positive and finite");
+    if (max_order < -1) throw Error(EMAGLS_ERR_ARG, "max_order must be -1 (no limit) or non-negative");
+    ShoeboxArgs a{};
+    for (int i = 0; i < 3; ++i) {
+        if (!(room_dim[i] > 0.0) || !std::isfinite(room_dim[i])) throw Error(EMAGLS_ERR_ARG, "room_dim must be positive and finite");
+        if (!(array_pos[i] >= mic_radius && array_pos[i] <= room_dim[i] - mic_radius))
+            throw Error(EMAGLS_ERR_ARG, "the array's sphere must lie inside the room (mic_radius <= array_pos <= room_dim - mic_radius)");
+        a.L[i] = room_dim[i]; a.pos[i] = array_pos[i];
+    }
+    for (int i = 0; i < 6; ++i) {
+        if (!(std::fabs(wall_refl[i]) <= 1.0)) throw Error(EMAGLS_ERR_ARG, "wall reflection coefficients must lie in [-1, 1]");
+        a.beta[i] = wall_refl[i];
+    }
+    for (int64_t q = 0; q < nsrc; ++q) {
+        const double* p = src_pos + 3 * q;
+        double d2 = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            if (!(p[i] > 0.0 && p[i] < room_dim[i]))
+                throw Error(EMAGLS_ERR_ARG, "source " + std::to_string(q) + " does not lie strictly inside the room");
+            d2 += (p[i] - array_pos[i]) * (p[i] - array_pos[i]);
+        }
+        if (!(std::sqrt(d2) > mic_radius))
+            throw Error(EMAGLS_ERR_ARG, "source " + std::to_string(q) + " lies inside the array's sphere (or on its centre)");
+    }
+    a.fs = fs; a.max_delay = max_delay; a.max_order = max_order;
+    // the box: an image with |n_i| beyond floor(reach / (2 L_i)) + 1 is farther than reach; one of reflection order <= max_order
+    // has |n_i| <= floor((max_order + 1) / 2)
+    const double reach = max_delay * C_SOUND / fs;
+    long double ncand = 8.0L * nsrc;
+    double B[3];
+    for (int i = 0; i < 3; ++i) {
+        B[i] = std::floor(reach / (2.0 * room_dim[i])) + 1.0;
+        if (max_order >= 0) B[i] = std::min(B[i], (double)(((int64_t)max_order + 1) / 2));
+        ncand *= 2.0L * B[i] + 1.0L;
+    }
+    if (!(ncand <= (long double)SBX_CAND_MAX))
+        throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 2^28 image-source candidates in one call: lower max_delay or max_order, or split the sources");
+    for (int i = 0; i < 3; ++i) { a.B[i] = (int)B[i]; a.W[i] = 2 * a.B[i] + 1; }
+    a.ncand = (int64_t)8 * a.W[0] * a.W[1] * a.W[2];
+    a.tiles = ceil_div(a.ncand, SBX_TILE);
+    return a;
+}
+
+// the enumeration in two steps around the host's look at the count: count() runs the count pass and the scan and returns with
+// comp_ptr on the host; fill() allocates the lists and runs the write pass (asynchronous on s.st)
+struct Shoebox {
+    Scratch& s;
+    ShoeboxArgs a;
+    int64_t nsrc;
+    const double* src = nullptr;
+    uint64_t* mask = nullptr;
+    int64_t *base = nullptr, *ptr = nullptr;
+    double *azi = nullptr, *zen = nullptr, *delay = nullptr, *gain = nullptr;
+    std::vector<int64_t> h_ptr;
+    EventPair ev_count, ev_write;
+    bool written = false;
+
+    Shoebox(Scratch& s_, const ShoeboxArgs& a_, int64_t nsrc_) : s(s_), a(a_), nsrc(nsrc_), h_ptr((size_t)nsrc_ + 1) {}
+    void count(const double* src_pos) {
+        const size_t ntiles = (size_t)(nsrc * a.tiles);
+        src = s.put(src_pos, (size_t)3 * nsrc);
+        mask = s.get<uint64_t>(sizeof(uint64_t) * ntiles * (SBX_TILE / 64));
+        int* cnt = s.get<int>(sizeof(int) * ntiles);
+        base = s.get<int64_t>(sizeof(int64_t) * (ntiles + 1));
+        ptr = s.get<int64_t>(sizeof(int64_t) * ((size_t)nsrc + 1));
+        HIP_CHECK(hipEventRecord(ev_count.a, s.st));
+        launch_shoebox_count(a, nsrc, src, mask, cnt, s.st);
+        launch_shoebox_scan(a, nsrc, cnt, base, ptr, s.st);
+        HIP_CHECK(hipEventRecord(ev_count.b, s.st));
+        HIP_CHECK(hipMemcpyAsync(h_ptr.data(), ptr, sizeof(int64_t) * h_ptr.size(), hipMemcpyDeviceToHost, s.st));
+        s.sync();
+    }
+    int64_t total() const { return h_ptr.back(); }
+    void fill() {
+        const size_t n = (size_t)total();
+        azi = s.get<double>(sizeof(double) * n); zen = s.get<double>(sizeof(double) * n);
+        delay = s.get<double>(sizeof(double) * n); gain = s.get<double>(sizeof(double) * n);
+        HIP_CHECK(hipEventRecord(ev_write.a, s.st));
+        if (n) launch_shoebox_write(a, nsrc, src, mask, base, azi, zen, delay, gain, s.st);
+        HIP_CHECK(hipEventRecord(ev_write.b, s.st));
+        written = true;
+    }
+    // after a synchronisation of s.st
+    void keep_time() const { g_shoebox_ms = ev_count.ms() + (written ? ev_write.ms() : 0.0); }
+};
 
 }  // namespace
 
@@ -42,134 +286,25 @@ extern "C" int emagls_array_irs(double fs, double mic_radius, int order, const d
                                 double pre_delay, int64_t nfft_in, int64_t nr, void* out) {
     return guarded_call([&] {
         // ---- arguments (nothing below this block fails on what the caller passed)
-        if (!mic_azi || !mic_zen) throw Error(EMAGLS_ERR_ARG, "null pointer: microphone grid");
         if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
-        if (!out) throw Error(EMAGLS_ERR_ARG, "null pointer: out");
-        if (nsrc < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nsrc");
-        if (nmics < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nmics");
-        if (nmics > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 64 microphones are not supported");
-        if (nch < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nch");
-        if (nch > 64) throw Error(EMAGLS_ERR_UNSUPPORTED, "more than 64 channels are not supported");
-        if (!enc && nch != nmics) throw Error(EMAGLS_ERR_ARG, "without an encoder nch must equal nmics (raw microphone responses)");
-        if (!(fs > 0) || !(mic_radius > 0) || !std::isfinite(fs) || !std::isfinite(mic_radius)) throw Error(EMAGLS_ERR_ARG, "fs and micRadius must be positive");
-        if (order < 0) throw Error(EMAGLS_ERR_ARG, "negative SH order");
-        if (nr < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nr");
-        if (nfft_in < 0) throw Error(EMAGLS_ERR_ARG, "nfft must be positive (0: the smallest power of two from 2*nr)");
-        int64_t nfft64 = nfft_in;
-        if (nfft64 == 0) {
-            nfft64 = 8;
-            while (nfft64 < 2 * nr && nfft64 <= AIR_NFFT_MAX) nfft64 *= 2;
-        }
-        if (nfft64 & (nfft64 - 1)) throw Error(EMAGLS_ERR_ARG, "nfft must be a power of two");
-        if (nfft64 < 8) throw Error(EMAGLS_ERR_UNSUPPORTED, "nfft below 8 is not supported");
-        if (nfft64 > AIR_NFFT_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "nfft above 65536 is not supported");
-        if (nr > nfft64) throw Error(EMAGLS_ERR_ARG, "nr exceeds nfft");
-        if (!(pre_delay >= 0.0) || !std::isfinite(pre_delay)) throw Error(EMAGLS_ERR_ARG, "pre_delay must be non-negative and finite");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
         if (comp_ptr[0] != 0) throw Error(EMAGLS_ERR_ARG, "comp_ptr must start at 0");
         for (int64_t q = 0; q < nsrc; ++q)
             if (comp_ptr[q + 1] < comp_ptr[q]) throw Error(EMAGLS_ERR_ARG, "comp_ptr must not decrease");
         const int64_t ncomp = comp_ptr[nsrc];
         if (ncomp > 0 && (!comp_azi || !comp_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: component directions");
-        const int nfft = (int)nfft64, P = nfft / 2 + 1, M = (int)nmics, C = (int)nch;
-        if (pre_delay > (double)(nfft - 1)) throw Error(EMAGLS_ERR_ARG, "pre_delay beyond nfft - 1 would wrap");
         for (int64_t j = 0; comp_delay && j < ncomp; ++j) {
             if (!(comp_delay[j] >= 0.0) || !std::isfinite(comp_delay[j])) throw Error(EMAGLS_ERR_ARG, "component delays must be non-negative and finite");
-            if (comp_delay[j] + pre_delay > (double)(nfft - 1)) throw Error(EMAGLS_ERR_ARG, "a component's delay plus pre_delay beyond nfft - 1 would wrap");
+            if (comp_delay[j] + pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "a component's delay plus pre_delay beyond nfft - 1 would wrap");
         }
         for (int64_t j = 0; comp_gain && j < ncomp; ++j)
             if (!std::isfinite(comp_gain[j])) throw Error(EMAGLS_ERR_ARG, "component gains must be finite");
-        const int N = std::max(order, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));     // getSMAIRMatrix.m:95
-        if (N > AIR_SIM_ORDER_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "simulation order above 85 is not supported");
-        // ---- sizes
-        const bool ec = enc && enc_is_complex, lds = nfft <= AIR_NFFT_LDS_MAX;
-        const int np = ec ? 2 : 1;
-        const int64_t Pld = air_bins_padded(P), rows = nsrc * C;
-        const size_t out_bytes = esz(ec) * (size_t)rows * nr;
-        {
-            // (in long double: the counts of a refused call may overflow 64 bits)
-            const long double need = (long double)nsrc * M * Pld * 16 + (long double)(N + 1) * Pld * 16 + (long double)ncomp * 52 +
-                                     (long double)nsrc * 12 + (long double)out_bytes +
-                                     (lds ? 0.0L : (enc ? (long double)rows * np * P * 16 : 0.0L) + (long double)rows * np * nfft * 8);
-            if (need > (long double)AIR_SCRATCH_MAX)
-                throw Error(EMAGLS_ERR_UNSUPPORTED, "the call needs more than 24 GiB of device memory; split the sources over several calls");
-        }
-        // the two forms' source lists (array_irs.hip): by each source's own count
-        std::vector<int> list_long, list_short;
-        for (int64_t q = 0; q < nsrc; ++q) (comp_ptr[q + 1] - comp_ptr[q] > AIR_LANE_SOURCE_MAX ? list_long : list_short).push_back((int)q);
-        std::vector<double> e_re, e_im;
-        if (enc) {
-            const double* e = (const double*)enc;
-            e_re.resize((size_t)C * M);
-            if (ec) e_im.resize((size_t)C * M);
-            for (size_t i = 0; i < (size_t)C * M; ++i) {
-                e_re[i] = ec ? e[2 * i] : e[i];
-                if (ec) e_im[i] = e[2 * i + 1];
-            }
-        }
-
+        air_check_scratch(c, ncomp);
         // ---- device
         Scratch s;
-        // 1. mode coefficients b'_n(k) = -b_n (2n+1) / (4 pi) as rows [N+1][Pld]
-        cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)(N + 1) * Pld, true);
-        double* rec = s.get<double>(sizeof(double) * 2 * (N + 1));
-        const double kr_step = 2.0 * kPi * (fs / (double)nfft) / C_SOUND * mic_radius;
-        launch_modal_bn(N, P, nullptr, kr_step, -1.0 / (4.0 * kPi), bn, 1, Pld, s.st);     // bnAll = -sphModalCoeffs(...)  (:107)
-        launch_air_modes(N, P, Pld, bn, rec, s.st);
-        // 2. components and microphones
-        AirMain m{};
-        double* v = s.get<double>(sizeof(double) * 3 * M);
-        launch_air_units(M, s.put(mic_azi, (size_t)M), s.put(mic_zen, (size_t)M), v, s.st);
-        if (ncomp > 0) {
-            double* u = s.get<double>(sizeof(double) * 3 * (size_t)ncomp);
-            int* dint = s.get<int>(sizeof(int) * (size_t)ncomp);
-            double* dfrac = s.get<double>(sizeof(double) * (size_t)ncomp);
-            launch_air_units(ncomp, s.put(comp_azi, (size_t)ncomp), s.put(comp_zen, (size_t)ncomp), u, s.st);
-            launch_air_delays(ncomp, s.put_opt(comp_delay, (size_t)ncomp), pre_delay, nfft, dint, dfrac, s.st);
-            m.u = u; m.dint = dint; m.dfrac = dfrac;
-            m.gain = s.put_opt(comp_gain, (size_t)ncomp);
-        }
-        m.bn = bn; m.rec = rec; m.v = v;
-        m.ptr = s.put(comp_ptr, (size_t)nsrc + 1);
-        m.list_long = s.put_opt(list_long.data(), list_long.size());
-        m.list_short = s.put_opt(list_short.data(), list_short.size());
-        m.n_long = (int)list_long.size(); m.n_short = (int)list_short.size();
-        m.N = N; m.M = M; m.P = P; m.nfft = nfft; m.Pld = Pld; m.ncomp = ncomp;
-        cplx* H = s.get<cplx>(sizeof(cplx) * (size_t)nsrc * M * Pld);
-        m.H = H;
-        // 3. the main kernel
-        EventPair ev;
-        HIP_CHECK(hipEventRecord(ev.a, s.st));
-        launch_air_main(m, s.st);
-        HIP_CHECK(hipEventRecord(ev.b, s.st));
-        // 4. encoder and inverse real transform
-        const double* d_re = s.put_opt(e_re.data(), e_re.size());
-        const double* d_im = s.put_opt(e_im.data(), e_im.size());
-        void* d_out = s.get(out_bytes);
-        FftPlan plan;
-        if (lds) {
-            cplx* tw = s.get<cplx>(sizeof(cplx) * (size_t)nfft);
-            launch_twiddles(nfft, tw, s.st);
-            launch_air_irfft(H, Pld, d_re, d_im, C, M, nsrc, nfft, tw, (int)nr, d_out, s.st);
-        } else {
-            cplx* X = H;
-            int64_t ldx = Pld;
-            if (enc) {
-                X = s.get<cplx>(sizeof(cplx) * (size_t)rows * np * P);
-                ldx = P;
-                launch_air_encode(H, Pld, d_re, d_im, C, M, nsrc, P, X, s.st);
-            }
-            double* y = s.get<double>(sizeof(double) * (size_t)rows * np * nfft);
-            int nn[1] = {nfft}, inembed[1] = {P}, onembed[1] = {nfft};
-            fft_check(hipfftPlanMany(plan.fresh(), 1, nn, inembed, 1, (int)ldx, onembed, 1, nfft, HIPFFT_Z2D, (int)(rows * np)), "plan Z2D");
-            fft_check(hipfftSetStream(plan, s.st), "set stream");
-            fft_check(hipfftExecZ2D(plan, (hipfftDoubleComplex*)X, y), "exec Z2D");
-            launch_air_pick(y, rows, np, nfft, (int)nr, d_out, s.st);
-        }
-        HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s.st));
-        s.sync();   // (the host vectors above live until their copies have run)
-        float ms = 0.0f;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
-        g_main_ms = (double)ms;
+        const size_t n = (size_t)ncomp;
+        const int64_t* d_ptr = s.put(comp_ptr, (size_t)nsrc + 1);
+        air_run(s, c, comp_ptr, d_ptr, s.put_opt(comp_azi, n), s.put_opt(comp_zen, n), s.put_opt(comp_delay, n), s.put_opt(comp_gain, n));
     });
 }
 
@@ -178,5 +313,59 @@ extern "C" int emagls_array_irs_kernel_time(double* ms) {
         if (!ms) throw Error(EMAGLS_ERR_ARG, "null pointer: ms");
         if (g_main_ms < 0.0) throw Error(EMAGLS_ERR_ARG, "no emagls_array_irs call has completed on this thread");
         *ms = g_main_ms;
+    });
+}
+
+extern "C" int emagls_shoebox_components(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc,
+                                         const double* src_pos, double fs, double max_delay, int max_order, int64_t capacity,
+                                         int64_t* comp_ptr, double* comp_azi, double* comp_zen, double* comp_delay, double* comp_gain) {
+    return guarded_call([&] {
+        if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
+        if (capacity < 0) throw Error(EMAGLS_ERR_ARG, "invalid shape: capacity");
+        if (capacity > 0 && (!comp_azi || !comp_zen || !comp_delay || !comp_gain))
+            throw Error(EMAGLS_ERR_ARG, "null pointer: component arrays (capacity 0 for a count-only call)");
+        const ShoeboxArgs a = shoebox_check(room_dim, wall_refl, array_pos, nsrc, src_pos, fs, 0.0, max_delay, max_order);
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        std::copy(box.h_ptr.begin(), box.h_ptr.end(), comp_ptr);
+        const size_t n = (size_t)box.total();
+        if (n > 0 && box.total() <= capacity) {
+            box.fill();
+            HIP_CHECK(hipMemcpyAsync(comp_azi, box.azi, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_zen, box.zen, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_delay, box.delay, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_gain, box.gain, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            s.sync();
+        }
+        box.keep_time();
+    });
+}
+
+extern "C" int emagls_array_room_irs(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                     const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
+                                     const double* array_pos, int64_t nsrc, const double* src_pos, double max_delay, int max_order,
+                                     double pre_delay, int64_t nfft_in, int64_t nr, int64_t* comp_count, void* out) {
+    return guarded_call([&] {
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        const ShoeboxArgs a = shoebox_check(room_dim, wall_refl, array_pos, nsrc, src_pos, fs, mic_radius, max_delay, max_order);
+        if (max_delay + pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "max_delay plus pre_delay beyond nfft - 1 would wrap");
+        air_check_scratch(c, 0);     // (what does not depend on the count; the whole estimate follows the count pass)
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        air_check_scratch(c, box.total());
+        box.fill();
+        air_run(s, c, box.h_ptr.data(), box.ptr, box.azi, box.zen, box.delay, box.gain);
+        box.keep_time();
+        for (int64_t q = 0; comp_count && q < nsrc; ++q) comp_count[q] = box.h_ptr[q + 1] - box.h_ptr[q];
+    });
+}
+
+extern "C" int emagls_shoebox_kernel_time(double* ms) {
+    return guarded_call([&] {
+        if (!ms) throw Error(EMAGLS_ERR_ARG, "null pointer: ms");
+        if (g_shoebox_ms < 0.0) throw Error(EMAGLS_ERR_ARG, "no emagls_shoebox_components or emagls_array_room_irs call has completed on this thread");
+        *ms = g_shoebox_ms;
     });
 }

@@ -394,6 +394,21 @@ void launch_air_encode(const void* H, int64_t Pld, const double* enc_re, const d
                        hipStream_t st);
 void launch_air_pick(const double* y, int64_t rows, int np, int nfft, int nr, void* out, hipStream_t st);
 
+// ---- shoebox.hip: image sources of a shoebox room as the component lists of array_irs.hip
+constexpr int SBX_TILE = 256;              // candidates per workgroup: four waves, one ballot word each
+struct ShoeboxArgs {
+    double L[3], beta[6], pos[3];          // room, walls (x=0, x=Lx, y=0, y=Ly, z=0, z=Lz), array centre
+    double fs, max_delay;
+    int max_order;                         // < 0: no limit
+    int B[3], W[3];                        // the search box |n_i| <= B_i, W_i = 2 B_i + 1
+    int64_t ncand, tiles;                  // candidates and tiles of ONE source: 8 Wx Wy Wz, ceil(ncand / SBX_TILE)
+};
+// mask [nsrc tiles][SBX_TILE / 64], cnt [nsrc tiles]; base [nsrc tiles + 1], comp_ptr [nsrc + 1]; src [nsrc][3]
+void launch_shoebox_count(const ShoeboxArgs& a, int64_t nsrc, const double* src, uint64_t* mask, int* cnt, hipStream_t st);
+void launch_shoebox_scan(const ShoeboxArgs& a, int64_t nsrc, const int* cnt, int64_t* base, int64_t* comp_ptr, hipStream_t st);
+void launch_shoebox_write(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                          double* zen, double* delay, double* gain, hipStream_t st);
+
 // ---- host_pools.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool in host_internal.hpp)
 hipStream_t pool_stream_take();
 void pool_stream_give(hipStream_t st);

@@ -778,6 +778,48 @@ int emagls_array_irs(double fs, double mic_radius, int order, const double* mic_
  * (tools/array_irs_timing.py); EMAGLS_ERR_ARG before the first one. */
 int emagls_array_irs_kernel_time(double* ms);
 
+/* ---- array room responses: shoebox image sources (this project's) ----
+ * The components of emagls_array_irs, enumerated on the device from a shoebox room: Allen & Berkley's image model with
+ * frequency-independent walls.  room_dim [3] = (Lx, Ly, Lz) in metres, all > 0; one corner at the origin, the axes those of getSH
+ * (x front, y left, z up) and parallel to the array's.  wall_refl [6]: real amplitude reflection coefficients in [-1, 1] of the walls
+ * x = 0, x = Lx, y = 0, y = Ly, z = 0, z = Lz.  array_pos [3]: the array's centre, the whole sphere inside the room
+ * (mic_radius <= array_pos[i] <= room_dim[i] - mic_radius; emagls_shoebox_components has no sphere: radius 0).  src_pos [3 x nsrc], xyz
+ * contiguous per source, nsrc >= 1, each strictly inside the room and farther than mic_radius from array_pos.  max_delay: samples,
+ * > 0 and finite.  max_order: >= 0, or -1 for no limit on the reflection order.  The speed of sound is 343 m/s.
+ * A candidate of a source s is n = (nx, ny, nz), integers, and p = (px, py, pz) in {0, 1}^3.  Per axis i: image_i = (1 - 2 p_i) s_i +
+ * 2 n_i L_i; exponents e0_i = |n_i - p_i| (the wall at 0), e1_i = |n_i| (the wall at L_i); reflection order = sum_i (e0_i + e1_i).
+ * With v = image - array_pos: d = sqrt((vx vx + vy vy) + vz vz), delay tau = d / 343 fs samples, gain g = prod_i b0_i^e0_i b1_i^e1_i / d
+ * (b^0 = 1 also for b = 0; the factors taken in the order x0, x1, y0, y1, z0, z1, then the division: a unit source at 1 m in the
+ * free field has gain 1), azi = atan2(vy, vx), zen = acos(vz / d).
+ * A candidate is a component iff (max_order < 0 or its reflection order <= max_order) and g != 0 and tau <= max_delay.  The
+ * components of a source lie in ascending lexicographic order of (nz, ny, nx, pz, py, px); this fixes the summation order of
+ * emagls_array_irs' main kernel, and so the bits of the responses.  No atomics: equal calls give equal lists, and the list of source
+ * q is the list of the call with that source alone.
+ * The search box is |n_i| <= floor(max_delay 343 / fs / (2 L_i)) + 1, and <= floor((max_order + 1) / 2) with an order limit; a call
+ * with more than 2^28 candidates (8 prod_i (2 B_i + 1) per source, times nsrc) is EMAGLS_ERR_UNSUPPORTED.
+ * Every argument is checked before the device is touched.  Plane-wave components are a far-field model: near-field (point-source)
+ * terms, frequency-dependent walls, air absorption and source directivity are not built.
+ *
+ * emagls_shoebox_components: comp_ptr [nsrc + 1] (host) is always written; comp_azi, comp_zen, comp_delay, comp_gain [capacity] are
+ * written only when comp_ptr[nsrc] <= capacity.  NULL arrays with capacity = 0: a count-only call. */
+int emagls_shoebox_components(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc, const double* src_pos,
+                              double fs, double max_delay, int max_order, int64_t capacity, int64_t* comp_ptr, double* comp_azi,
+                              double* comp_zen, double* comp_delay, double* comp_gain);
+/* emagls_array_irs of those components without their crossing the bus: the enumeration feeds the main kernel on the device, and only
+ * the nsrc + 1 offsets come back to the host (for the main kernel's two source lists).  out and every argument shared with
+ * emagls_array_irs as there.  max_delay + pre_delay > nfft - 1 would wrap: EMAGLS_ERR_ARG.  comp_count [nsrc] (optional, NULL for
+ * none): the number of components of each source.  The 24 GiB estimate of emagls_array_irs needs the component count: it is applied
+ * after the count pass (its part that does not depend on the count before the device is touched).  Source q of a call gives the bits
+ * of emagls_array_irs on the list emagls_shoebox_components returns for it. */
+int emagls_array_room_irs(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                          const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
+                          const double* array_pos, int64_t nsrc, const double* src_pos, double max_delay, int max_order, double pre_delay,
+                          int64_t nfft, int64_t nr, int64_t* comp_count, void* out);
+/* Device-event time in ms of the enumeration passes (count, scan, write) of the calling thread's last completed
+ * emagls_shoebox_components or emagls_array_room_irs call; EMAGLS_ERR_ARG before the first one.  A room call also sets the time of
+ * emagls_array_irs_kernel_time. */
+int emagls_shoebox_kernel_time(double* ms);
+
 /* ---- plan API: inputs resident in HBM, repeated execution (benchmarks, batches) ------------- */
 
 typedef struct emagls_plan emagls_plan;

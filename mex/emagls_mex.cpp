@@ -211,11 +211,12 @@ void at_exit() {
 // emagls_mex('ch', N, aziRad, basisType)        emagls_mex('smair', order, fs, irLen, oversamplingFactor, smaRadius, micAzi, micZen, ...)
 // emagls_mex('shf', micRadius, order, fs, len)                  [wShf, W_Shf] = ...
 // emagls_mex('adf', micRadius, micAzi, micZen, order, fs, len, shDefinition[, Yhi])
+// array responses: 'array_irs', 'shoebox_components', 'array_room_irs' (their argument lists stand at their branches)
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     static bool registered = false;
     if (!registered) { mexAtExit(at_exit); registered = true; }
     if (nrhs < 1 || !mxIsChar(prhs[0])) mexErrMsgIdAndTxt("eMagLS:arg", "first argument must be a command string");
-    char cmd[16] = {0};
+    char cmd[32] = {0};
     mxGetString(prhs[0], cmd, sizeof cmd);
     const std::string c(cmd);
     if (c == "decode" && nrhs > 5) {
@@ -824,6 +825,71 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                         comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
                                         mxGetScalar(prhs[5]), given(10) ? (int64_t)mxGetScalar(prhs[10]) : 0, (int64_t)nr, out_ptr(plhs[0]));
         if (rc) fail(rc);
+        return;
+    }
+    if (c == "shoebox_components" || c == "array_room_irs") {
+        // the room of both: (roomDim [3], wallReflection [6], sourcePos [numSources x 3], arrayPos [3], fs, ...
+        //   shoebox_components: ... maxDelay, maxOrder)                       [compPtr, comps] = ...: zero-based offsets [numSources + 1] and
+        //                                                                     comps [J x 4] = (azi, zen, delay, gain), the inputs of 'array_irs'
+        //   array_room_irs:     ... irLen, preDelay, micRadius, micGridAziZenRad, order, encoder, nfft, maxOrder, maxDelay)
+        //                                                                     [irs, counts] = ...: [irLen x numChannels x numSources], [numSources]
+        // maxOrder []: no limit; maxDelay [] (array_room_irs): irLen - 1 - preDelay
+        const bool irs = c == "array_room_irs";
+        if (nrhs < (irs ? 15 : 8))
+            mexErrMsgIdAndTxt("eMagLS:arg", irs ? "array_room_irs needs 14 arguments ([] for no encoder and for the defaults of nfft, maxOrder and maxDelay)"
+                                                : "shoebox_components needs 7 arguments ([] for no limit on the reflection order)");
+        auto given = [&](int i) { return prhs[i] && !mxIsEmpty(prhs[i]); };
+        if (mxGetNumberOfElements(prhs[1]) != 3 || mxGetNumberOfElements(prhs[4]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "roomDim and arrayPos must have 3 elements");
+        if (mxGetNumberOfElements(prhs[2]) != 6) mexErrMsgIdAndTxt("eMagLS:arg", "wallReflection must have 6 elements (x=0, x=Lx, y=0, y=Ly, z=0, z=Lz)");
+        const mwSize Q = mxGetM(prhs[3]);
+        if (Q < 1 || mxGetN(prhs[3]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "sourcePos must be [numSources x 3] (x, y, z per row)");
+        const double *dim = dbl(prhs[1], "roomDim"), *refl = dbl(prhs[2], "wallReflection"), *sp = dbl(prhs[3], "sourcePos"), *pos = dbl(prhs[4], "arrayPos");
+        std::vector<double> src(3 * Q);
+        for (mwSize q = 0; q < Q; ++q)
+            for (int i = 0; i < 3; ++i) src[3 * q + i] = sp[q + Q * i];
+        const double fs = mxGetScalar(prhs[5]);
+        const int mo = irs ? 13 : 7;
+        const int max_order = given(mo) ? (int)mxGetScalar(prhs[mo]) : -1;
+        if (!irs) {
+            std::vector<int64_t> ptr(Q + 1);
+            const double max_delay = mxGetScalar(prhs[6]);
+            int rc = emagls_shoebox_components(dim, refl, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, 0, ptr.data(), nullptr, nullptr,
+                                               nullptr, nullptr);
+            if (rc) fail(rc);
+            const mwSize J = (mwSize)ptr[Q];
+            plhs[0] = mxCreateDoubleMatrix(Q + 1, 1, mxREAL);
+            mxArray* comps = mxCreateDoubleMatrix(J, 4, mxREAL);
+            double* o = mxGetDoubles(comps);
+            if (J) rc = emagls_shoebox_components(dim, refl, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, (int64_t)J, ptr.data(), o, o + J,
+                                                  o + 2 * J, o + 3 * J);
+            for (mwSize q = 0; q <= Q; ++q) mxGetDoubles(plhs[0])[q] = (double)ptr[q];
+            if (nlhs > 1) plhs[1] = comps; else mxDestroyArray(comps);
+            if (rc) fail(rc);
+            return;
+        }
+        if (mxGetN(prhs[9]) != 2) mexErrMsgIdAndTxt("eMagLS:arg", "micGridAziZenRad must be [n x 2] (azimuth, zenith)");
+        const mwSize M = mxGetM(prhs[9]), nr = (mwSize)mxGetScalar(prhs[6]);
+        const double* mics = dbl(prhs[9], "micGridAziZenRad");
+        mwSize Cc = M;
+        bool ec = false;
+        if (given(11)) {
+            if (!mxIsDouble(prhs[11]) || mxGetN(prhs[11]) != M) mexErrMsgIdAndTxt("eMagLS:arg", "encoder must be [numChannels x numMics] with one column per microphone (%d)", (int)M);
+            Cc = mxGetM(prhs[11]);
+            ec = mxIsComplex(prhs[11]);
+        }
+        const double pre = mxGetScalar(prhs[7]), max_delay = given(14) ? mxGetScalar(prhs[14]) : (double)nr - 1.0 - pre;
+        const mwSize od[3] = {nr, Cc, Q};
+        plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
+        std::vector<int64_t> counts(Q);
+        const int rc = emagls_array_room_irs(fs, mxGetScalar(prhs[8]), (int)mxGetScalar(prhs[10]), mics, mics + M, (int64_t)M,
+                                             given(11) ? in_ptr(prhs[11]) : nullptr, ec ? 1 : 0, (int64_t)Cc, dim, refl, pos, (int64_t)Q, src.data(),
+                                             max_delay, max_order, pre, given(12) ? (int64_t)mxGetScalar(prhs[12]) : 0, (int64_t)nr, counts.data(),
+                                             out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        if (nlhs > 1) {
+            plhs[1] = mxCreateDoubleMatrix(Q, 1, mxREAL);
+            for (mwSize q = 0; q < Q; ++q) mxGetDoubles(plhs[1])[q] = (double)counts[q];
+        }
         return;
     }
     if (c == "encode") {

@@ -1,0 +1,21 @@
+function [irs, counts] = getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, preDelay, micRadius, micGridAziZenRad, varargin)
+% Impulse responses of the simulated rigid-sphere array in a shoebox room, on the MI355X library (DESIGN.md section 12;
+% include/emagls.h, emagls_array_room_irs): getArrayIrs(getShoeboxComponents(...), ...) bit for bit, with the image sources
+% enumerated on the device and fed to the responses' kernels there.
+%   [irs, counts] = getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, preDelay, micRadius, micGridAziZenRad, ...
+%                                   'name', value, ...)
+%   the room as in getShoeboxComponents (the array's whole sphere inside it, every source outside the sphere), the array as in
+%   getArrayIrs; further names: order (4), encoder ([]), nfft ([]) as there, maxOrder ([]: no limit on the reflection order),
+%   maxDelay ([]: irLen - 1 - preDelay samples; maxDelay + preDelay beyond nfft - 1 would wrap and is refused)
+%   irs       [irLen x numChannels x Q] (complex with a complex encoder): irs(:, :, q) is the rir of sourceFieldStream
+%   counts    [Q x 1] the number of image sources of each source position
+p = struct('order', 4, 'encoder', [], 'nfft', [], 'maxOrder', [], 'maxDelay', []);
+for i = 1:2:numel(varargin)
+    if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
+    p.(varargin{i}) = varargin{i + 1};
+end
+if size(sourcePos, 2) ~= 3; error('eMagLS:arg', 'sourcePos must be [Q x 3]'); end
+[irs, counts] = emagls_mex('array_room_irs', double(roomDim(:)), double(wallReflection(:)), double(sourcePos), double(arrayPos(:)), double(fs), ...
+    double(irLen), double(preDelay), double(micRadius), double(micGridAziZenRad), double(p.order), double(p.encoder), double(p.nfft), ...
+    double(p.maxOrder), double(p.maxDelay));
+end

@@ -9,6 +9,17 @@ and the time of the same spectra in NumPy (the Legendre sum of the definition; s
 that profiles/r19_array_irs.md quotes, stamped with the kernel sources' hash.
 
     python tools/array_irs_timing.py [reps] [out.md] [numpy: 0/1]
+
+With --room: getArrayRoomIrs (emagls_array_room_irs) on a shoebox room of 5.2 x 4.1 x 2.9 m, walls 0.9 .. 0.6, one
+source, the same array, raw microphones:
+  1. max_delay 6000 samples, nfft = irLen = 8192
+  2. max_delay 24000 samples, nfft = 65536, irLen = 32768
+Per shape: candidates and components, the wall time of the fused call, the device-event times of the enumeration passes
+(emagls_shoebox_kernel_time) and of the main kernel, the wall times of getShoeboxComponents and of getArrayIrs on its lists (the
+listed path, whose copies the fused call saves), and the time of the same enumeration in NumPy (vectorised).  The table of
+profiles/r20_array_room_irs.md.
+
+    python tools/array_irs_timing.py --room [reps] [out.md]
 """
 import ctypes as C
 import os
@@ -52,7 +63,81 @@ def numpy_spectra(mics, comps, owner, nsrc, N, nfft, pre, bins):
     return H, time.perf_counter() - t0
 
 
+def numpy_shoebox(room, beta, src, pos, max_delay):
+    """The definition of DESIGN.md section 12 for one source, vectorised: ([J x 4], candidates, seconds)."""
+    t0 = time.perf_counter()
+    L, beta, s, a = (np.asarray(v, dtype=np.float64) for v in (room, beta, src, pos))
+    box = [int(np.floor(max_delay * 343.0 / FS / (2 * L[i]))) + 1 for i in range(3)]
+    ax = [np.arange(-b, b + 1) for b in box]
+    nz, ny, nx, pz, py, px = (g.ravel() for g in np.meshgrid(ax[2], ax[1], ax[0], [0, 1], [0, 1], [0, 1], indexing="ij"))
+    g, v = np.ones(nx.size), []
+    for i, (n, p) in enumerate(((nx, px), (ny, py), (nz, pz))):
+        g = g * beta[2 * i] ** np.abs(n - p) * beta[2 * i + 1] ** np.abs(n)
+        v.append(((1 - 2 * p) * s[i] + 2 * n * L[i]) - a[i])
+    d = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    tau, g = d / 343.0 * FS, g / d
+    keep = (g != 0.0) & (tau <= max_delay)
+    comps = np.column_stack([np.arctan2(v[1], v[0]), np.arccos(v[2] / d), tau, g])[keep]
+    return comps, nx.size, time.perf_counter() - t0
+
+
+def main_room(argv):
+    import emagls_amd as E
+    from emagls_amd import _lib as L
+    from oracle import emagls_oracle as O
+    from tools.csrc_hash import csrc_sha16
+    reps = int(argv[0]) if argv else 5
+    out = argv[1] if len(argv) > 1 else None
+    mics = random_dirs(np.random.default_rng(19), 32)
+    room, beta, src, pos, pre = (5.2, 4.1, 2.9), (0.9, 0.85, 0.8, 0.75, 0.7, 0.6), (1.3, 2.2, 1.1), (3.4, 1.7, 1.6), 64.0
+    N = O.simulation_order(4, FS, RADIUS)
+    lines = ["Kernel sources: csrc_sha16 %s.  Simulation order N = %d, 32 microphones; %d calls per shape after 2 warm-up calls; medians." %
+             (csrc_sha16(), N, reps), "",
+             "| max_delay | nfft | candidates | components | fused call ms | enumeration passes ms | main kernel ms | getShoeboxComponents ms | "
+             "getArrayIrs on its lists ms | listed path ms | NumPy enumeration ms | lists equal NumPy's |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    ms = C.c_double(0.0)
+
+    def timed(f):
+        t = time.perf_counter()
+        r = f()
+        return r, (time.perf_counter() - t) * 1e3
+
+    for max_delay, nfft, ir_len in ((6000.0, 8192, 8192), (24000.0, 65536, 32768)):
+        fused = lambda: E.getArrayRoomIrs(room, beta, src, pos, FS, ir_len, pre, RADIUS, mics, nfft=nfft, maxDelay=max_delay)   # noqa: E731
+        lists = lambda: E.getShoeboxComponents(room, beta, src, pos, FS, max_delay)   # noqa: E731
+        for _ in range(2):
+            fused()
+            E.getArrayIrs(lists(), FS, ir_len, pre, RADIUS, mics, nfft=nfft)
+        t_f, t_e, t_m, t_c, t_l, t_n = [], [], [], [], [], []
+        for _ in range(reps):
+            a, t = timed(fused)
+            t_f.append(t)
+            L.check(L.load().emagls_shoebox_kernel_time(C.byref(ms)))
+            t_e.append(ms.value)
+            L.check(L.load().emagls_array_irs_kernel_time(C.byref(ms)))
+            t_m.append(ms.value)
+            comps, t = timed(lists)
+            t_c.append(t)
+            b, t = timed(lambda: E.getArrayIrs(comps, FS, ir_len, pre, RADIUS, mics, nfft=nfft))
+            t_l.append(t)
+            want, ncand, sec = numpy_shoebox(room, beta, src, pos, max_delay)
+            t_n.append(sec * 1e3)
+        same = comps[0].shape == want.shape and np.allclose(comps[0][:, 1:], want[:, 1:], rtol=1e-12, atol=1e-12) and np.array_equal(a, b)
+        med = lambda v: float(np.median(v))   # noqa: E731
+        lines.append("| %d | %d | %d | %d | %.2f | %.3f | %.3f | %.2f | %.2f | %.2f | %.1f | %s |" %
+                     (max_delay, nfft, ncand, comps[0].shape[0], med(t_f), med(t_e), med(t_m), med(t_c), med(t_l), med(t_c) + med(t_l), med(t_n),
+                      "yes, and fused = listed bit for bit" if same else "NO"))
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--room":
+        return main_room(sys.argv[2:])
     import emagls_amd as E
     from emagls_amd import _lib as L
     from oracle import emagls_oracle as O
