@@ -2,7 +2,8 @@
 // emagls_shoebox_components and emagls_array_room_irs from a shoebox room.  Host arrays in, host array out; every argument is
 // checked before the device is touched (a room call's scratch estimate, which needs the component count, after its count pass), and
 // every array operation runs in the kernels of array_irs.hip, shoebox.hip, modal.hip and fft.hip (the twiddles), with hipFFT's Z2D
-// above 4096 points (the precedent of decode.hip above 2048 taps).  No CPU fallback.
+// above 4096 points (the precedent of decode.hip above 2048 taps).  The speed of sound and the simulation order are
+// array_model.hpp's; the bin spacing fs / nfft of stage 1 stays its own expression.  No CPU fallback.
 //
 // Both response entries end in air_run: stages 1 to 4 on components that are already on the device.  emagls_array_irs uploads its
 // lists; emagls_array_room_irs enumerates them there and reads back only the nsrc + 1 offsets, for the two source lists of the main
@@ -13,14 +14,12 @@
 #include <vector>
 
 #include "../../include/emagls.h"
-#include "kernels.hpp"
-#include "device_mem.hpp"
+#include "array_model.hpp"
 
 using namespace emagls;
 
 namespace {
 
-constexpr double C_SOUND = 343.0;          // dependencies/getSMAIRMatrix.m:95
 constexpr int AIR_SIM_ORDER_MAX = 85;
 constexpr int64_t AIR_NFFT_MAX = 65536;
 constexpr int AIR_NFFT_LDS_MAX = 4096;     // the LDS transforms of lds_fft.hpp; hipFFT above
@@ -87,7 +86,7 @@ AirCall air_check(double fs, double mic_radius, int order, const double* mic_azi
     c.fs = fs; c.mic_radius = mic_radius; c.pre_delay = pre_delay; c.mic_azi = mic_azi; c.mic_zen = mic_zen; c.enc = enc; c.out = out;
     c.nfft = (int)nfft64; c.P = c.nfft / 2 + 1; c.M = (int)nmics; c.C = (int)nch; c.nsrc = nsrc; c.nr = nr;
     if (pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "pre_delay beyond nfft - 1 would wrap");
-    c.N = std::max(order, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));     // getSMAIRMatrix.m:95
+    c.N = smair_sim_order(order, fs, mic_radius);
     if (c.N > AIR_SIM_ORDER_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "simulation order above 85 is not supported");
     c.ec = enc && enc_is_complex; c.lds = c.nfft <= AIR_NFFT_LDS_MAX;
     c.np = c.ec ? 2 : 1;

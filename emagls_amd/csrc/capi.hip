@@ -850,9 +850,9 @@ int emagls_get_magls_filters_2d(const double* hL, const double* hR, int64_t nsam
 int emagls_simulation_order(int kind, int order, double fs, double mic_radius) {
     switch (kind) {
         case EMAGLS_KIND_EMAGLS: case EMAGLS_KIND_EMA_CH: case EMAGLS_KIND_EMA_SH:
-            return std::max(order, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));                   // getSMAIRMatrix.m:95
+            return smair_sim_order(order, fs, mic_radius);
         case EMAGLS_KIND_EMAGLS2:
-            return std::max(SMAIR_DEFAULT_ORDER, (int)std::ceil(fs * kPi * mic_radius / C_SOUND));     // params.order unset -> 4
+            return smair_sim_order(SMAIR_DEFAULT_ORDER, fs, mic_radius);     // params.order unset -> 4
         default: return order;
     }
 }

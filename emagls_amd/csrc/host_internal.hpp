@@ -1,5 +1,6 @@
 // Internal header of the host translation units (host_pools.hip, plan_setup.hip, plan_run.hip, batch_run.hip, capi.hip, jobs.hip): the
-// plan and batch structs, the pools they draw from, and the declarations of what one of these files calls in another.
+// plan and batch structs, the pools they draw from, and the declarations of what one of these files calls in another.  The array
+// model's scalars and shared host sequences come with array_model.hpp.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "../../include/emagls.h"
+#include "array_model.hpp"
 #include "device_mem.hpp"
 #include "kernels.hpp"
 
@@ -26,7 +28,6 @@ void emagls_batch_forget(emagls_batch* b, emagls_plan* p);
 
 namespace emagls {
 
-constexpr double C_SOUND = 343.0;       // dependencies/getSMAIRMatrix.m:86
 constexpr int NFFT_MAX_LEN = 2048;      // lib/getEMagLsFilters.m:35
 constexpr double F_CUT_MIN_FREQ = 1e3;  // :36
 constexpr double SVD_REGUL_CONST = 0.01;  // :39
@@ -174,13 +175,9 @@ struct Arena {
     ~Arena() { if (base) BlockPool::get().give(base, bytes); }
 };
 
-inline int round_up(int64_t v, int64_t m) { return (int)(ceil_div(v, m) * m); }
-
 // kinds that run the array-model pipeline (simulated array -> per-bin factor -> sweep)
 static inline bool magls_kind(int k) { return k == EMAGLS_KIND_MAGLS || k == EMAGLS_KIND_MAGLS_2D; }
 static inline bool array_kind(int k) { return k == EMAGLS_KIND_EMAGLS || k == EMAGLS_KIND_EMAGLS2 || k == EMAGLS_KIND_EMA_CH || k == EMAGLS_KIND_EMA_SH; }
-// evaluation points of the SH rotation fit (emash.hip): enough to resolve order N exactly
-static inline int ema_sh_npts(int C) { return 4 * C + 8; }
 
 // A captured graph and its executable instance, owned together (non-copyable).  The only place on the host side that begins a
 // capture, instantiates a graph or destroys one: a struct that holds such a member needs no line of its own for it.

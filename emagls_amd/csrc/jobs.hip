@@ -185,7 +185,7 @@ bool is_device_pointer(const void* p) {
 void job_shape(const emagls_design_desc& d, std::string& out) {
     emagls_design_desc k = d;
     if (array_kind(d.kind) && d.sim_order_pad > 0) {
-        const int own = std::max(d.kind == EMAGLS_KIND_EMAGLS2 ? SMAIR_DEFAULT_ORDER : d.order, (int)std::ceil(d.fs * kPi * d.mic_radius / C_SOUND));
+        const int own = smair_sim_order(d.kind == EMAGLS_KIND_EMAGLS2 ? SMAIR_DEFAULT_ORDER : d.order, d.fs, d.mic_radius);
         if (own <= d.sim_order_pad) k.mic_radius = 0.0;   // (laid out for sim_order_pad whatever the radius)
     }
     out.assign(reinterpret_cast<const char*>(&k), sizeof k);

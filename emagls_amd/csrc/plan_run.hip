@@ -1,5 +1,6 @@
 // Stage pipelines of every design kind, the resident sweep and its gate, and the execute of a plan on its own (eager, captured,
-// replayed), with the recovery from the device-side status words.
+// replayed), with the recovery from the device-side status words.  The array model's own sequences -- pinv of one matrix, the
+// encoder E, the EMAinSH operands -- are calls into array_model.hpp, on the buffers the plan names.
 #include "host_internal.hpp"
 
 namespace {
@@ -37,6 +38,12 @@ void record_sweep_event(emagls_plan& p, size_t i) {
     HIP_CHECK(hipEventRecord(p.sweep_events[i], p.stream));
 }
 
+// the workspace of array_model.hpp's pinv from a plan's buffers: the widened input, Z, Householder vectors, tau, R2, N
+PinvWs plan_pinv_ws(emagls_plan& p, const char* Xd, const char* Z, const char* Vws, const char* tauw, const char* R2w, const char* Nw) {
+    return PinvWs{p.get<cplx>(Xd), p.get<cplx>(Z), p.get<cplx>(Vws), p.get<double>(tauw), p.get<cplx>(R2w), p.get<cplx>(Nw)};
+}
+PinvWs plan_lo_ws(emagls_plan& p) { return plan_pinv_ws(p, "Ylo_c", "Zlo", "Vlo", "tau_lo", "R2_lo", "N_lo"); }   // pinv(Y_lo)
+
 void run_pinv_of_R(emagls_plan& p) {
     // pinv(Y_conj) = conj(Q) Z_B, Z_B from the SVD of B = R with MATLAB's pinv tolerance
     hipStream_t st = p.stream;
@@ -48,15 +55,7 @@ void run_pinv_of_R(emagls_plan& p) {
         return;
     }
     launch_widen(p.get("R"), p.S, cb, p.get("Rb"), p.ldS, p.C, p.S, /*transpose=*/true, /*upper_only=*/true, st);
-    FactorArgs a{};
-    a.S = p.S; a.C = p.C; a.ldS = p.ldS; a.kb0 = 0; a.P = 2;  // P=2: bin 0 is not a Nyquist bin
-    a.Tn = nullptr; a.bn = nullptr; a.nOrders = 0;
-    a.Xd = p.get<cplx>("Rb"); a.xd_stride = 0;
-    a.reg_mode = 1; a.reg_c = 0.0; a.tol_dim = (double)std::max<int64_t>(p.D, p.C);
-    a.Z = p.get<cplx>("Zb"); a.Vws = p.get<cplx>("Vws"); a.sv = p.get<double>("sv");
-    a.Hq = nullptr; a.W = nullptr; a.ls_end = 0; a.sweeps_out = nullptr;
-    a.tauw = p.get<double>("tauw"); a.R2w = p.get<cplx>("R2w"); a.Nw = p.get<cplx>("Nw");
-    launch_factor(a, 1, true, st);
+    pinv_matrix(plan_pinv_ws(p, "Rb", "Zb", "Vws", "tauw", "R2w", "Nw"), p.S, p.C, p.ldS, (double)std::max<int64_t>(p.D, p.C), p.get<double>("sv"), st);
     launch_ypinv(p.get("Q"), p.ldS, cb, p.get("Zb"), p.ldS, (int)p.D, p.S, p.C, p.get("Ypinv"), p.ldD, st);
     p.mark("pinv");
 }
@@ -154,10 +153,8 @@ void ema_sh_operands(emagls_plan& p) {
     const emagls_design_desc& d = p.d;
     const bool cb = p.cplx_basis;
     hipStream_t st = p.stream;
-    const int M = (int)d.nmics, ldM = round_up(M, 64), N = d.order, nCh = 2 * N + 1, nOrd = p.simOrder + 1;
+    const int M = (int)d.nmics, N = d.order, nOrd = p.simOrder + 1;
     const int ls_end = std::min(p.kcut0, p.P);
-    const int npts = ema_sh_npts(p.C), ldP = round_up(npts, 64);
-    const int64_t ldA = round_up((int64_t)(p.D + 1) * npts, 64);
     p.sync_used = 0;
     // ---- HRIR prologue
     launch_twiddles(p.nfft, p.get("tw"), st);
@@ -172,51 +169,21 @@ void ema_sh_operands(emagls_plan& p) {
     // ---- array model: E0 = J pinv(CH(micAzi)) Y_mic   (EMAinSH.m:66-82), b_n(kr)
     launch_sh_coeff(p.simOrder, p.get<double>("sh_tab"), st);
     launch_sh_basis(p.simOrder, M, p.get<double>("mic_azi"), p.get<double>("mic_zen"), p.get<double>("sh_tab"), cb, p.get("Ymic_cm"), M, st);
-    launch_transpose_conj(p.get("Ymic_cm"), M, p.S, M, p.get("Ymic_rm"), M, p.ldS, cb, false, st);
-    launch_ch_basis(N, M, p.get<double>("mic_azi"), cb, p.get("Ylo_c"), ldM, st);
-    {
-        FactorArgs a{};
-        a.S = M; a.C = nCh; a.ldS = ldM; a.kb0 = 0; a.P = 2;
-        a.Xd = p.get<cplx>("Ylo_c"); a.xd_stride = 0;
-        a.reg_mode = 1; a.tol_dim = (double)std::max(M, nCh);
-        a.Z = p.get<cplx>("Zlo"); a.Vws = p.get<cplx>("Vlo");
-        a.tauw = p.get<double>("tau_lo"); a.R2w = p.get<cplx>("R2_lo"); a.Nw = p.get<cplx>("N_lo");
-        launch_factor(a, 1, true, st);
-    }
-    launch_small_gemm(p.get("Zlo"), ldM, true, p.get("Ymic_rm"), p.ldS, cb, p.get("Ech"), p.ldS, cb, nCh, p.S, M, st);
-    launch_sh_coeff(N, p.get<double>("sh_tab_lo"), st);
-    launch_sh_basis(N, p.C, p.get<double>("nnm_azi"), p.get<double>("nnm_zen"), p.get<double>("sh_tab_lo"), cb, p.get("Ypts"), p.C, st);
-    launch_ema_sh_e0(p.get("Ech"), (int)p.ldS, p.get("Ypts"), p.C, p.S, cb, p.get("E"), st);
+    array_encoder(Encoder::CH_PINV, p.get("Ymic_cm"), M, p.S, p.ldS, cb, N, p.get<double>("mic_azi"), p.get("Ymic_rm"), plan_lo_ws(p), p.get("Ech"), st);
+    ema_sh_e0(N, p.C, p.S, p.ldS, cb, p.get<double>("nnm_azi"), p.get<double>("nnm_zen"), p.get<double>("sh_tab_lo"), p.get("Ypts"), p.get("Ech"),
+              p.get("E"), st);
     launch_modal_bn(p.simOrder, p.P, p.get<double>("kr"), 1.0, -1.0, p.get("bn"), nOrd, 1, st, p.get<int>("nvalid"));
     p.mark("array_model");
     // ---- per-direction SH rotations (EMAinSH.m:85-100)
-    launch_rot_points(p.get<double>("hrir_azi"), p.get<double>("hrir_zen"), (int)p.D, npts, p.get<double>("rot_azi"), p.get<double>("rot_zen"), st);
-    launch_sh_basis(N, (p.D + 1) * npts, p.get<double>("rot_azi"), p.get<double>("rot_zen"), p.get<double>("sh_tab_lo"), cb, p.get("Arot"), ldA, st);
     {
-        const char* B = (const char*)p.get("Arot") + esz(cb) * (size_t)p.D * npts;   // the unrotated point set: columns D*npts..
-        launch_widen(B, ldA, cb, p.get("Bc"), ldP, p.C, npts, false, false, st);
-        if (p.C > 32) {
-            // orders 5..7: pinv of the npts x C point matrix by wide_array.hip's QR + one-sided Jacobi (no clipping: the point set
-            // resolves the order, nothing is dropped) -- Z comes out as pinv(B) [C][ldP] like the narrow factorisation's
-            launch_wa_factor(p.get("Bc"), p.get("Vb"), npts, p.C, ldP, 1, 0.0, p.get<double>("tau_b"), p.get("R2_b"), p.get("N_b"), p.get<double>("sv"),
-                             p.get<int>("jsweeps"), p.get("Zb"), st);
-        } else {
-        FactorArgs a{};
-        a.S = npts; a.C = p.C; a.ldS = ldP; a.kb0 = 0; a.P = 2;
-        a.Xd = p.get<cplx>("Bc"); a.xd_stride = 0;
-        a.reg_mode = 1; a.tol_dim = (double)std::max(npts, p.C);
-        a.Z = p.get<cplx>("Zb"); a.Vws = p.get<cplx>("Vb");
-        a.tauw = p.get<double>("tau_b"); a.R2w = p.get<cplx>("R2_b"); a.Nw = p.get<cplx>("N_b");
-        launch_factor(a, 1, true, st);
-        }
+        EmaShRot r{p.get<double>("rot_azi"), p.get<double>("rot_zen"), p.get("Arot"), plan_pinv_ws(p, "Bc", "Zb", "Vb", "tau_b", "R2_b", "N_b"),
+                   p.get<double>("sv"), p.get<int>("jsweeps"), p.get("Rot")};
+        ema_sh_rotations(r, N, p.C, (int)p.D, cb, p.get<double>("hrir_azi"), p.get<double>("hrir_zen"), p.get<double>("sh_tab_lo"), st);
     }
-    launch_rot_from_points(p.get("Arot"), ldA, p.get("Zb"), ldP, p.C, npts, p.get<double>("hrir_zen"), (int)p.D, cb, p.get("Rot"), st);
     p.mark("sh_rotations");
     // ---- order terms of pwGrid.' on the horizontal projection of the grid, rotated per direction; G_k of every bin
-    launch_sh_basis(p.simOrder, p.D, p.get<double>("hrir_azi"), p.get<double>("hrir_zen_eq"), p.get<double>("sh_tab"), cb, p.get("Ycm"), p.ldD, st);
-    launch_transpose_conj(p.get("Ycm"), p.D, p.S, p.ldD, p.get("Yc"), p.Dpad, p.ldS, cb, true, st);
-    launch_qt(p.get("Yc"), p.ldS, p.get("E"), p.ldS, (int)p.D, p.S, p.C, nOrd, cb, p.get("QT"), p.ldD, st);
-    launch_qt_rotate(p.get("QT"), p.ldD, nOrd, p.C, N, (int)p.D, p.get("Rot"), cb, st);
+    ema_sh_order_terms(p.simOrder, N, (int)p.D, p.C, p.S, p.ldS, cb, p.get<double>("hrir_azi"), p.get<double>("hrir_zen_eq"), p.get<double>("sh_tab"),
+                       p.get("Ycm"), p.ldD, p.get("Yc"), p.Dpad, p.get("E"), p.get("Rot"), p.get("QT"), st);
     launch_dspace_g(p.get("QT"), p.ldD, cb, p.get("bn"), nOrd, (int)p.D, p.C, p.P, p.g0, p.get("G"), st, 0, -1);
     p.mark("order_terms+G");
 }
@@ -302,20 +269,9 @@ void execute_emagls_wide(emagls_plan& p) {
     launch_transpose_conj(p.get("Ycm"), p.D, p.S, p.ldD, p.get("Yc"), p.Dpad, p.ldS, false, true, st);
     launch_sh_basis(p.simOrder, M, p.get<double>("mic_azi"), p.get<double>("mic_zen"), p.get<double>("sh_tab"), false, p.get("Ymic_cm"), M, st);
     if (raw) {
-        launch_transpose_conj(p.get("Ymic_cm"), M, p.S, M, p.get("E"), M, p.ldS, false, false, st);   // E = Y_mic
-    } else if (p.nOut <= 32) {
-        const int ldM = round_up(M, 64);
-        launch_transpose_conj(p.get("Ymic_cm"), M, p.S, M, p.get("Ymic_rm"), M, p.ldS, false, false, st);
-        launch_widen(p.get("Ymic_cm"), M, false, p.get("Ylo_c"), ldM, p.nOut, M, false, false, st);
-        FactorArgs a{};
-        a.S = M; a.C = p.nOut; a.ldS = ldM; a.kb0 = 0; a.P = 2;
-        a.Xd = p.get<cplx>("Ylo_c"); a.xd_stride = 0;
-        a.reg_mode = 1; a.tol_dim = (double)std::max(M, p.nOut);
-        a.Z = p.get<cplx>("Zlo"); a.Vws = p.get<cplx>("Vlo");
-        a.tauw = p.get<double>("tau_lo"); a.R2w = p.get<cplx>("R2_lo"); a.Nw = p.get<cplx>("N_lo");
-        launch_factor(a, 1, true, st);
-        launch_small_gemm(p.get("Zlo"), ldM, true, p.get("Ymic_rm"), p.ldS, false, p.get("E"), p.ldS, false, p.nOut, p.S, M, st);
+        array_encoder(Encoder::RAW, p.get("Ymic_cm"), M, p.S, p.ldS, false, 0, nullptr, nullptr, PinvWs{}, p.get("E"), st);   // E = Y_mic
     } else {
+        // (eMagLS: nOut = C > 32 on this path, beyond the narrow pinv of array_model.hpp's encoder)
         // pinv(Y_lo) = (Y_lo^T Y_lo)^-1 Y_lo^T: the M x nOut SH matrix of the microphone grid has full column rank and is well
         // conditioned for any array that resolves the order (certified on the device like the SH Gram matrix of wide.hip)
         launch_wa_lo_gram(p.get("Ymic_cm"), M, p.nOut, p.get<double>("Ag"), st);
@@ -738,23 +694,9 @@ void emagls_pre_sweep(emagls_plan& p) {
     if (!p.custom_basis)
         launch_sh_basis(p.simOrder, M, p.get<double>("mic_azi"), p.get<double>("mic_zen"), p.get<double>("sh_tab"), cb,
                         p.get("Ymic_cm"), M, s1);
-    launch_transpose_conj(p.get("Ymic_cm"), M, p.S, M, p.get("Ymic_rm"), M, p.ldS, cb, false, s1);
-    if (raw) {
-        launch_transpose_conj(p.get("Ymic_cm"), M, p.S, M, p.get("E"), M, p.ldS, cb, false, s1);  // E = Y_mic
-    } else {
-        if (d.kind == EMAGLS_KIND_EMA_CH)   // pinv(chFunction(order, micGridAziRad))  (getEMagLsFiltersEMAinCH.m:70)
-            launch_ch_basis(d.order, M, p.get<double>("mic_azi"), cb, p.get("Ylo_c"), ldM, s1);
-        else
-            launch_widen(p.get("Ymic_cm"), M, cb, p.get("Ylo_c"), ldM, p.nOut, M, false, false, s1);
-        FactorArgs a{};
-        a.S = M; a.C = p.nOut; a.ldS = ldM; a.kb0 = 0; a.P = 2;
-        a.Xd = p.get<cplx>("Ylo_c"); a.xd_stride = 0;
-        a.reg_mode = 1; a.tol_dim = (double)std::max(M, p.nOut);
-        a.Z = p.get<cplx>("Zlo"); a.Vws = p.get<cplx>("Vlo");
-        a.tauw = p.get<double>("tau_lo"); a.R2w = p.get<cplx>("R2_lo"); a.Nw = p.get<cplx>("N_lo");
-        launch_factor(a, 1, true, s1);
-        launch_small_gemm(p.get("Zlo"), ldM, true, p.get("Ymic_rm"), p.ldS, cb, p.get("E"), p.ldS, cb, p.nOut, p.S, M, s1);
-    }
+    // (raw: both Ymic_rm and E are written; EMAinCH: pinv(chFunction(order, micGridAziRad)), getEMagLsFiltersEMAinCH.m:70)
+    array_encoder(raw ? Encoder::RAW : d.kind == EMAGLS_KIND_EMA_CH ? Encoder::CH_PINV : Encoder::SH_PINV, p.get("Ymic_cm"), M, p.S, p.ldS, cb, d.order,
+                  p.get<double>("mic_azi"), p.get("Ymic_rm"), raw ? PinvWs{} : plan_lo_ws(p), p.get("E"), s1);
     // bnAll = -sphModalCoeffs(simOrder, kr, 'rigid')   (getSMAIRMatrix.m:107)
     launch_modal_bn(p.simOrder, p.P, p.get<double>("kr"), 1.0, -1.0, p.get("bn"), nOrd, 1, s1, p.get<int>("nvalid"));
     if (p.synth)   // scaled modal terms of the Legendre series and pinv(Y_lo) as the real matrix Pm (identity: raw microphones)

@@ -264,7 +264,7 @@ void plan_setup(emagls_plan& p) {
         // getSMAIRMatrix.m:95: max(params.order, ceil(fs*pi*r/C)).  lib/getEMagLs2Filters.m:51-63 leaves params.order unset, so
         // getSMAIRMatrix.m:39-41 defaults it to 4 there: for eMagLS2 `order` only sets f_cut (:47), never the simulation order.
         const int smair_order = d.kind == EMAGLS_KIND_EMAGLS2 ? SMAIR_DEFAULT_ORDER : N;
-        p.simOrderOwn = std::max(smair_order, (int)std::ceil(d.fs * kPi * d.mic_radius / C_SOUND));
+        p.simOrderOwn = smair_sim_order(smair_order, d.fs, d.mic_radius);
         // sim_order_pad: simulate on more orders than the design's own, with b_n = 0 above its own order -- the same sum, so
         // the same filters; array radii of neighbouring simulation-order classes then have one shape and share a lane batch
         if (d.sim_order_pad < 0) throw Error(EMAGLS_ERR_ARG, "negative sim_order_pad");
@@ -387,13 +387,7 @@ void plan_setup(emagls_plan& p) {
             p.alloc("R2_b", sizeof(cplx) * (size_t)p.C * p.C);
             p.alloc("N_b", sizeof(cplx) * (size_t)p.C * p.C);
             p.alloc("Rot", esz(cb) * (size_t)p.D * p.C * p.C, false);
-            std::vector<double> eq((size_t)p.D, kPi / 2.0), na((size_t)p.C, 0.0), nz((size_t)p.C, kPi / 2.0);
-            for (int c = 0; c < p.C; ++c) {   // one azimuth per channel at which its circular harmonic is 1 (or sqrt 2)
-                int n = 0;
-                while ((n + 1) * (n + 1) <= c) ++n;
-                const int m = c - n * n - n;
-                na[c] = (!cb && m < 0) ? kPi / (2.0 * -m) : 0.0;
-            }
+            const std::vector<double> eq((size_t)p.D, kPi / 2.0), na = ema_sh_channel_azimuths(p.C, cb), nz((size_t)p.C, kPi / 2.0);
             p.upload("hrir_zen_eq", eq.data(), sizeof(double) * p.D);
             p.upload("nnm_azi", na.data(), sizeof(double) * p.C);
             p.upload("nnm_zen", nz.data(), sizeof(double) * p.C);

@@ -1,17 +1,16 @@
 // C ABI of the render-side neighbours (include/emagls.h, "render side"): radial filters, SH encoding and the two optional
 // equalisation filters.  Host arrays in, host arrays out; every array operation runs in the kernels of render.hip,
-// modal.hip, fft.hip (the IR epilogue), factor.hip (pinv) and decode.hip (overlap-save).  No CPU fallback.
+// modal.hip, fft.hip (the IR epilogue), factor.hip (pinv) and decode.hip (overlap-save); the array model's scalars, its pinv and its
+// encoder are array_model.hpp's.  No CPU fallback.
 #include <vector>
 
 #include "../../include/emagls.h"
-#include "kernels.hpp"
-#include "device_mem.hpp"
+#include "array_model.hpp"
 
 using namespace emagls;
 
 namespace {
 
-constexpr double C_SOUND = 343.0;     // dependencies/getRadialFilter.m:31, lib/getMagLsSphericalHeadFilter.m:26
 constexpr int NFFT_MAX_LEN = 2048;    // lib/getMagLsSphericalHeadFilter.m:23
 
 bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
@@ -19,8 +18,7 @@ bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 // b_n(kr) of a rigid sphere on the bin grid f = linspace(0, fs/2, P):  [P][nOrd]
 cplx* modal_on_bins(Scratch& s, int order, int P, double fs, double radius) {
     cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)P * (order + 1));
-    const double kr_step = 2.0 * kPi * ((fs / 2.0) / (double)(P - 1)) / C_SOUND * radius;
-    launch_modal_bn(order, P, nullptr, kr_step, 1.0, bn, order + 1, 1, s.st);
+    launch_modal_bn(order, P, nullptr, kr_bin_step(fs, P, radius), 1.0, bn, order + 1, 1, s.st);
     return bn;
 }
 
@@ -110,26 +108,16 @@ int emagls_sh_encode(const double* sig, int64_t nsamp, int64_t nmics, const doub
         const double* d_zen = s.put(mic_zen, (size_t)M);
         double* tab = s.get<double>(sizeof(double) * sh_coeff_count(order));
         void* Ycm = s.get(esz(cb) * (size_t)nOut * M);
-        cplx* Yc = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
-        cplx* Z = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
-        cplx* V = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
-        double* tau = s.get<double>(sizeof(double) * nOut);
-        cplx* R2 = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
-        cplx* Nw = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
+        const PinvWs ws = pinv_scratch(s, nOut, ldM);
         launch_sh_coeff(order, tab, s.st);
         launch_sh_basis(order, M, d_azi, d_zen, tab, cb, Ycm, M, s.st);
-        launch_widen(Ycm, M, cb, Yc, ldM, nOut, M, false, false, s.st);
+        launch_widen(Ycm, M, cb, ws.Xd, ldM, nOut, M, false, false, s.st);
         // pinv(Y_mic) with MATLAB's tolerance max(size) eps(norm)   (verifyEMagLs.m:235: pinv(E), E = Y_mic.')
-        FactorArgs a{};
-        a.S = M; a.C = nOut; a.ldS = ldM; a.kb0 = 0; a.P = 2;
-        a.Xd = Yc; a.xd_stride = 0;
-        a.reg_mode = 1; a.tol_dim = (double)std::max(M, nOut);
-        a.Z = Z; a.Vws = V; a.tauw = tau; a.R2w = R2; a.Nw = Nw;
-        launch_factor(a, 1, true, s.st);
+        pinv_matrix(ws, M, nOut, ldM, (double)std::max(M, nOut), nullptr, s.st);
         const double* d_sig = s.put(sig, (size_t)nsamp * M);
         const size_t out_bytes = esz(cb) * (size_t)nsamp * nOut;
         void* d_out = s.get(out_bytes);
-        launch_sh_encode(d_sig, nsamp, M, Z, ldM, nOut, cb, d_out, s.st);
+        launch_sh_encode(d_sig, nsamp, M, ws.Z, ldM, nOut, cb, d_out, s.st);
         HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s.st));
         s.sync();
     });
@@ -245,7 +233,7 @@ int emagls_get_smair_matrix(int order, double fs, int64_t ir_len, int oversampli
         if (nfft % 2) throw Error(EMAGLS_ERR_ARG, "nfft must be even");      // getSMAIRMatrix.m:88
         const bool cb = basis == EMAGLS_BASIS_COMPLEX, raw = return_raw_mic_sigs != 0;
         const int P = (int)(nfft / 2 + 1), M = (int)nmics;
-        const int simOrder = std::max(order, (int)std::ceil(fs * kPi * sma_radius / C_SOUND));     // :95
+        const int simOrder = smair_sim_order(order, fs, sma_radius);
         if (sim_order) *sim_order = simOrder;
         const int S = (simOrder + 1) * (simOrder + 1), nOut = (order + 1) * (order + 1), rows = raw ? M : nOut;
         if (!raw && nOut > 32) throw Error(EMAGLS_ERR_UNSUPPORTED, "SH order above 4 is not supported in this build");
@@ -260,29 +248,11 @@ int emagls_get_smair_matrix(int order, double fs, int64_t ir_len, int oversampli
         void* Yrm = s.get(esz(cb) * (size_t)ldM * ldS, true);             // [M][ldS]
         launch_sh_coeff(simOrder, tab, s.st);
         launch_sh_basis(simOrder, M, d_azi, d_zen, tab, cb, Ycm, M, s.st);
-        launch_transpose_conj(Ycm, M, S, M, Yrm, M, ldS, cb, false, s.st);
-        const void* E = Yrm;
-        if (!raw) {   // E = pinv(Y_Hi(:, 1:numShsOut)) Y_Hi   (:102, :119-121)
-            cplx* Yc = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
-            cplx* Z = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
-            cplx* V = s.get<cplx>(sizeof(cplx) * (size_t)nOut * ldM, true);
-            double* tau = s.get<double>(sizeof(double) * nOut);
-            cplx* R2 = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
-            cplx* Nw = s.get<cplx>(sizeof(cplx) * (size_t)nOut * nOut);
-            launch_widen(Ycm, M, cb, Yc, ldM, nOut, M, false, false, s.st);
-            FactorArgs a{};
-            a.S = M; a.C = nOut; a.ldS = ldM; a.kb0 = 0; a.P = 2;
-            a.Xd = Yc; a.xd_stride = 0;
-            a.reg_mode = 1; a.tol_dim = (double)std::max(M, nOut);
-            a.Z = Z; a.Vws = V; a.tauw = tau; a.R2w = R2; a.Nw = Nw;
-            launch_factor(a, 1, true, s.st);
-            void* Em = s.get(esz(cb) * (size_t)nOut * ldS, true);
-            launch_small_gemm(Z, ldM, true, Yrm, ldS, cb, Em, ldS, cb, nOut, S, M, s.st);
-            E = Em;
-        }
+        // E = Y_Hi, or pinv(Y_Hi(:, 1:numShsOut)) Y_Hi   (:102, :119-121)
+        void* E = raw ? Yrm : s.get(esz(cb) * (size_t)nOut * ldS, true);
+        array_encoder(raw ? Encoder::RAW : Encoder::SH_PINV, Ycm, M, S, ldS, cb, order, nullptr, Yrm, raw ? PinvWs{} : pinv_scratch(s, nOut, ldM), E, s.st);
         cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)P * (simOrder + 1));
-        const double kr_step = 2.0 * kPi * ((fs / 2.0) / (double)(P - 1)) / C_SOUND * sma_radius;
-        launch_modal_bn(simOrder, P, nullptr, kr_step, -1.0, bn, simOrder + 1, 1, s.st);            // bnAll = -sphModalCoeffs(...)  (:107)
+        launch_modal_bn(simOrder, P, nullptr, kr_bin_step(fs, P, sma_radius), -1.0, bn, simOrder + 1, 1, s.st);   // bnAll = -sphModalCoeffs(...)  (:107)
         cplx* rad = nullptr;
         if (!raw && radial_filter_type != EMAGLS_RADIAL_NONE) {
             if (radial_filter_type == EMAGLS_RADIAL_SOFTLIMIT && !std::isfinite(noise_gain_db)) throw Error(EMAGLS_ERR_ARG, "softlimit needs noiseGainDb");
