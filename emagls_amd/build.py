@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libemagls.so")
-SOURCES = ["sh_basis.hip", "modal.hip", "fft.hip", "gram_chol.hip", "factor.hip", "gramroute.hip", "sweep.hip", "sweep_persist.hip", "sweep_synth.hip", "sweep_reg.hip", "synth_debug.hip", "factor_debug.hip", "fft_debug.hip", "gram_debug.hip", "dspace.hip", "atf.hip", "decode.hip", "decode_stream.hip", "field_stream.hip", "rotate.hip", "rotate3.hip", "resample.hip", "render.hip", "render_api.hip", "response.hip", "response_api.hip", "array_irs.hip", "shoebox.hip", "array_irs_api.hip", "emash.hip", "wide.hip", "wide_array.hip", "microbench.hip",
+SOURCES = ["sh_basis.hip", "modal.hip", "fft.hip", "gram_chol.hip", "factor.hip", "gramroute.hip", "sweep.hip", "sweep_persist.hip", "sweep_synth.hip", "sweep_reg.hip", "ls_shared.hip", "synth_debug.hip", "factor_debug.hip", "fft_debug.hip", "gram_debug.hip", "dspace.hip", "atf.hip", "decode.hip", "decode_stream.hip", "field_stream.hip", "rotate.hip", "rotate3.hip", "resample.hip", "render.hip", "render_api.hip", "response.hip", "response_api.hip", "array_irs.hip", "shoebox.hip", "array_irs_api.hip", "emash.hip", "wide.hip", "wide_array.hip", "microbench.hip",
            "switches.hip", "decode_api.hip", "field_api.hip", "host_pools.hip", "plan_setup.hip", "plan_run.hip", "batch_run.hip", "capi.hip", "jobs.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",

@@ -173,7 +173,7 @@ void batch_set_sharing(emagls_batch& b, bool& field, bool share) {
     if (share == field) return;
     for (auto* p : b.plans) drop_plan_graphs(*p);
     drop_batch_graphs(b);
-    if (&field == &b.geo_share) batch_geo_forget(b);
+    if (&field == &b.geo_share || &field == &b.geo_ls_shared) batch_geo_forget(b);
     field = share;
 }
 // The whole batch as two single-stream graphs around the resident sweep: `stage(b, pre_part)` before it and `stage(b, 2)` after it on
@@ -283,6 +283,20 @@ uint64_t batch_geo_version(const emagls_batch& b) {
     for (const emagls_plan* p : b.plans) ver = (ver * 1000003ull + p->atf_side_version) * 1000003ull + p->solo_runs;
     return ver;
 }
+// The least-squares rows of a sharing batch come from ONE kept operand Yls = Y_reg_inv_k of the bins below k_cut (ls_shared.hip;
+// geo_yls_stage forms it in the cold run) when every such bin has a route to it: the Householder-route bins from plan 0's Z, the
+// Gram-route bins of a SYNTHESISING design from the angles.  A design whose Gram-route bins read the materialised G_k
+// (launch_ls_gram) keeps the stages that carry every HRIR set through the factors, and so does EMAGLS_GEO_LS_SHARED=0.  So do the
+// raw-microphone designs (eMagLS2): their explicit operand gives filters 2.5e-12 away from the single designs' (6 sets, em32, 901
+// directions; 3.6e-14 for eMagLS), and a sharing batch of them is held to 1e-12 of its single designs
+// (test_hrir_sets_on_one_geometry_share_it).  Decided here, once per batch and again whenever its plans' routes may have moved; a
+// change of the answer drops the graphs and the kept state.
+static bool batch_geo_ls_shared_wanted(const emagls_plan& p0) {
+    const int ls_end = std::min(p0.kcut0, p0.P);
+    const bool gram_ls = p0.gram_from > 0 && p0.gram_from < ls_end;
+    return sw_on<Sw::GEO_LS_SHARED>() && p0.d.kind != EMAGLS_KIND_EMAGLS2 && ls_end > 1 && p0.C <= 32 && (!gram_ls || p0.synth) &&
+           (p0.hh_end <= 1 || p0.has("Z"));
+}
 void batch_geo_decide_sharing(emagls_batch& b) {
     bool share = false;
     if (b.geo_want && b.plans.size() > 1) {
@@ -300,6 +314,7 @@ void batch_geo_decide_sharing(emagls_batch& b) {
         share = eligible && batch_inputs_same(b, {"hrir_azi", "hrir_zen", "mic_azi", "mic_zen"}, b.geo_checked_version, b.geo_inputs_same);
     }
     batch_set_sharing(b, b.geo_share, share);
+    batch_set_sharing(b, b.geo_ls_shared, share && batch_geo_ls_shared_wanted(*b.plans[0]));
 }
 // What the HRIR set of plan h enters, on plan 0's geometry (lib/getEMagLsFilters.m:72-81, :94): its spectra; behind plan 0's stages
 // the least-squares bins -- H conj(Q) R^-1 rows and the back-transform of the Householder-route bins (into h's own Z), G_k / M_k for the
@@ -317,6 +332,40 @@ void geo_hrir_side(emagls_plan& h, emagls_plan& g, emagls_plan& p0, hipStream_t 
     hrir_gram_ls_rows(h, g, p0, true, st);
     if (p0.synth) launch_synth_winit(h.get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, h.get("Winit"), st, true);
 }
+// The same with the kept operand (b.geo_ls_shared), in two steps.  The spectra of plan h -- without HcT: nothing reads HcT, Hyp, Hq,
+// Rinv or Z in this form --, then the least-squares rows W(k,:) = H(k,:) Yls_k of every lane of the launch context in one launch and the
+// start value of the chain from them.
+void geo_spectra_side(emagls_plan& h, emagls_plan& p0, hipStream_t st) {
+    subject_reset(h, st);
+    h.sync_used = 0;
+    hrir_spectra(h, p0, st, false);
+}
+void geo_ls_shared_rows(emagls_plan& h, emagls_plan& p0, const void* yls, hipStream_t st) {
+    launch_ls_shared_rows(h.get("Hc"), h.ldD, std::min(p0.kcut0, p0.P), yls, p0.ldD, (int)p0.D, p0.C, p0.P, h.get("W"), st);
+    if (p0.synth) launch_synth_winit(h.get("W"), p0.get("Pm"), p0.C, (int)p0.d.nmics, std::max(p0.kcut0, 1), p0.P, h.get("Winit"), st, true);
+}
+// Yls of plan 0's geometry, behind plan 0's whole pipeline (cold run; outside any lane scope: ONE design's operands).  Every bin from
+// the route it takes in hrir_hh_back / hrir_gram_ls_rows: [1, min(hh_end, ls_end)) Householder, [gram_from, ls_end) Gram.
+//   Householder route: Y_reg_inv_k = conj(Q) Z_k = conj(Yc) (Z_k R^-H), the form launch_yri_accurate gives the flagged swept bins, here
+//   for EVERY such bin (cond_ok null) and on a copy of Z: plan 0's own Z stays what its pipeline wrote.  R's diagonal-block inverses
+//   are plan 0's (hrir_hh_rows has just written them).
+//   Gram route: conj(g_k) Pm^T conj(M_k) from the angles (launch_yls_gram).
+void geo_yls_stage(emagls_batch& b, hipStream_t st) {
+    emagls_plan& g = *b.plans[0];
+    const bool cb = g.cplx_basis;
+    const int ls_end = std::min(g.kcut0, g.P), hh_ls = std::min(g.hh_end, ls_end), gf = g.gram_from;
+    cplx* yls = b.yls.get<cplx>();
+    if (hh_ls > 1) {
+        HIP_CHECK(hipMemcpyAsync(b.zls.get(), g.get("Z"), sizeof(cplx) * (size_t)hh_ls * g.C * g.ldS_h, hipMemcpyDeviceToDevice, st));
+        launch_zsolve_flagged(b.zls.get(), g.ldS_h, g.get(cb ? "R" : "Rc"), g.get(cb ? "Rinv" : "Rinvc"), nullptr, g.S_h, g.C, hh_ls, 1, st);
+        launch_yri_accurate(g.get("Yc"), g.ldS, cb, b.zls.get(), g.ldS_h, nullptr, (int)g.D, g.S_h, g.C, hh_ls, 1, yls, g.ldD, st,
+                            g.custom_basis ? nullptr : g.get("Ycm"), g.ldD);
+    }
+    if (gf > 0 && gf < ls_end)
+        launch_yls_gram(g.get("bsc"), synth_nord_pad(g.simOrder + 1), g.get<double>("hrir_azi"), g.get<double>("hrir_zen"), g.get<double>("mic_azi"),
+                        g.get<double>("mic_zen"), g.get<int>("smap"), g.get<double>("Pm"), g.get("Mw"), (int)g.D, g.C, gf, ls_end,
+                        yls, g.ldD, st);
+}
 // One stream for the whole batch (the subjects' stages are short and the sweep chain is what bounds a batch of HRIR sets), so
 // that the stages before and after the sweep are two single-stream graphs: issued eagerly, the ~250 launches of a 16-set batch
 // cost 11 ms of host time (measured: 1380 sets/s whatever the number of batches in flight).
@@ -329,6 +378,14 @@ void geo_hrir_side(emagls_plan& h, emagls_plan& g, emagls_plan& p0, hipStream_t 
 // Usw and Winit; the sweep writes ll, Wpart, W and Usw; the stages after it W, wL and wR.  Every plan buffer is a range of its own
 // in the arena (batch_try_lanes), so none of these aliases a kept one.  A warm run does NOT pass through plan_pre_stage, which would
 // zero plan 0's route.
+//
+// With the kept operand (b.geo_ls_shared, the default for synthesising designs) the warm run is shorter: it reads plan 0's Pm, bsc, Mt,
+// smap (the sweep and synth_winit) and the batch's Yls, written by the cold run's geo_yls_stage only; the HRIR-dependent stages write
+// flag, W, tw, dirsum, grpd, Hc, Habs and Winit.  Nothing reads or writes HcT, Hyp, Hq, Rinv, Z or the subjects' copies of Yc, R, Vws, Nw,
+// tauw, G, Mw.  In the cold run plan 0's own pipeline still writes its least-squares rows and Winit through the factors; the row
+// launch for all lanes, plan 0 included, overwrites them before the sweep is enqueued, so plan 0 returns the same bits cold and warm.
+// Plan 0's status words are those of its pipeline (it is not reset again); a subject's stages raise none in either form
+// (factor_back writes no status word), so batch_redo sees the geometry's flags through plan 0 as before.
 void batch_geo_stage(emagls_batch& b, int part) {
     emagls_plan& p0 = *b.plans[0];
     StreamLoan loan(b.plans, b.stream);
@@ -337,13 +394,22 @@ void batch_geo_stage(emagls_batch& b, int part) {
     // whole pipeline), every plan of a warm run.  Plan 0 CALLS the same functions here as inside its own pipeline (plan_run.hip:
     // hrir_spectra, hrir_hh_rows, hh_factor_args, hrir_hh_back, hrir_gram_ls_rows from emagls_pre_sweep's blk_prologue, blk_rows,
     // blk_back, blk_tail; synth_winit_kernel is block 0 of synth_mt_kernel), so its filters have the same bits in both forms.
-    auto hrir_side = [&](int first) {
+    // f(h, g) for the plans first .. n-1: one call with the lanes' launch context, or one call per plan (g: geo_hrir_side)
+    auto each = [&](int first, auto f) {
         if (first >= n) return;
         if (b.lanes) {
             BatchScope sc(n - first, b.stride);
-            geo_hrir_side(*b.plans[first], *b.plans[first], p0, b.stream);
+            f(*b.plans[first], *b.plans[first]);
         } else {
-            for (int j = first; j < n; ++j) geo_hrir_side(*b.plans[j], p0, p0, b.stream);
+            for (int j = first; j < n; ++j) f(*b.plans[j], p0);
+        }
+    };
+    auto hrir_side = [&](int first) {
+        if (b.geo_ls_shared) {   // spectra of the plans that have not run theirs; rows and start value of EVERY plan from the kept operand
+            each(first, [&](emagls_plan& h, emagls_plan&) { geo_spectra_side(h, p0, b.stream); });
+            each(0, [&](emagls_plan& h, emagls_plan&) { geo_ls_shared_rows(h, p0, b.yls.get(), b.stream); });
+        } else {
+            each(first, [&](emagls_plan& h, emagls_plan& g) { geo_hrir_side(h, g, p0, b.stream); });
         }
     };
     if (part == 1) {
@@ -355,7 +421,9 @@ void batch_geo_stage(emagls_batch& b, int part) {
             // few geometry operands those kernels read (conj(Y), R, the Householder-route factors, M_k and G_k of the
             // least-squares bins: ~40 MB) are copied into the subjects' own slots first, so that every pointer of a launch
             // moves by the same stride; the large ones (G_k, M_k of the swept bins) are only read by the sweep, through
-            // plan 0's pointers.  The copies stay: a warm run reads them again.
+            // plan 0's pointers.  The copies stay: a warm run reads them again.  (Only the stages that carry an HRIR set through the
+            // factors read them; with the kept operand Yls nobody does.  The broadcast stays in place as long as
+            // EMAGLS_GEO_LS_SHARED=0 can select those stages: it is cold-run work either way.)
             emagls_plan& g = p0;
             const bool cb = g.cplx_basis;
             const int gf = g.gram_from, hh_end = g.hh_end, ldSh = g.ldS_h;
@@ -379,6 +447,7 @@ void batch_geo_stage(emagls_batch& b, int part) {
                 bc("Mw", 0, sizeof(cplx) * (size_t)ls_end * g.C * g.C);
             }
         }
+        if (b.geo_ls_shared) geo_yls_stage(b, b.stream);
         hrir_side(1);
     } else if (b.lanes) {
         BatchScope sc(n, b.stride);
@@ -397,6 +466,14 @@ void batch_execute_geo(emagls_batch& b) {
         b.geo_kept_version = ~0ull;
         b.geo_ran_version = batch_geo_version(b);
         b.geo_cold_pending = true;
+        if (b.geo_ls_shared) {   // room for the kept operand (grown, never shrunk; graphs captured on an earlier block are dropped)
+            const emagls_plan& p0 = *b.plans[0];
+            const int ls_end = std::min(p0.kcut0, p0.P), hh_ls = std::min(p0.hh_end, ls_end);
+            const void *y0 = b.yls.get(), *z0 = b.zls.get();
+            b.yls.grow(sizeof(cplx) * (size_t)(ls_end - 1) * p0.C * p0.ldD);
+            b.zls.grow(sizeof(cplx) * (size_t)std::max(hh_ls, 1) * p0.C * p0.ldS_h);
+            if (b.yls.get() != y0 || b.zls.get() != z0) { b.group[0].reset(); b.warm.reset(); }
+        }
     }
     // the cold and the warm form each have a captured graph of their stages before the sweep, captured the first time the form runs
     // with replays on -- a batch's second execute is normally its first warm one, so the warm form needs no eager run of its own

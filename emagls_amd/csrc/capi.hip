@@ -484,6 +484,18 @@ int emagls_plan_debug_buffer(emagls_plan* p, const char* name, void* dst, size_t
     return guarded([&] {
         DeviceGuard dg(p ? p->device : -1);
         if (!p || !name || !nbytes) throw Error(EMAGLS_ERR_ARG, "null pointer");
+        if (std::string(name) == "Yls") {   // the kept operand of a sharing batch's least-squares rows: the batch owns it, its plans show it
+            emagls_batch* b = p->owner;
+            if (!b || !b->geo_share || !b->geo_ls_shared || !b->yls.get()) throw Error(EMAGLS_ERR_ARG, "Yls: the plan's batch keeps no such operand");
+            const emagls_plan& p0 = *b->plans[0];
+            const size_t bytes = sizeof(cplx) * (size_t)(std::min(p0.kcut0, p0.P) - 1) * p0.C * p0.ldD;
+            if (!dst) { *nbytes = bytes; return; }
+            HIP_CHECK(hipStreamSynchronize(b->stream));
+            const size_t n = std::min(*nbytes, bytes);
+            HIP_CHECK(hipMemcpy(dst, b->yls.get(), n, hipMemcpyDeviceToHost));
+            *nbytes = n;
+            return;
+        }
         auto it = p->bufs.find(name);
         if (it == p->bufs.end()) throw Error(EMAGLS_ERR_ARG, std::string("unknown buffer ") + name);
         if (!dst) { *nbytes = it->second.bytes; return; }

@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(256) yri_accurate_kernel(const T* __restrict__
                                                            cplx* __restrict__ Yri, int64_t ldD, size_t bstride) {
     Q = boff(Q, bstride); Z = boff(Z, bstride); cond_ok = boff(cond_ok, bstride); Yri = boff(Yri, bstride);
     const int kb = k0 + blockIdx.y;
-    if (cond_ok[kb] != 0.0) return;
+    if (cond_ok && cond_ok[kb] != 0.0) return;
     const int c = threadIdx.x >> 3, dl = threadIdx.x & 7;
     if (c >= C) return;
     for (int d = blockIdx.x * 8 + dl; d < D; d += gridDim.x * 8) {
@@ -259,7 +259,7 @@ __global__ void __launch_bounds__(256) yri_accurate_cm_kernel(const double* __re
                                                               cplx* __restrict__ Yri, int64_t ldD, size_t bstride) {
     Ycm = boff(Ycm, bstride); Z = boff(Z, bstride); cond_ok = boff(cond_ok, bstride); Yri = boff(Yri, bstride);
     const int kb = k0 + blockIdx.y;
-    if (cond_ok[kb] != 0.0) return;   // (uniform for the workgroup)
+    if (cond_ok && cond_ok[kb] != 0.0) return;   // (uniform for the workgroup)
     __shared__ __attribute__((aligned(16))) cplx zs[32][YA_SCH + 1];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int d = blockIdx.x * 128 + (wave & 1) * 64 + lane;     // two direction tiles x two channel halves per workgroup

@@ -709,7 +709,7 @@ __global__ void __launch_bounds__(256) zsolve_flagged_kernel(cplx* __restrict__ 
                                                              int S, int C, int k0, size_t bstride) {
     Z = boff(Z, bstride); R = boff(R, bstride); Rinv = boff(Rinv, bstride); cond_ok = boff(cond_ok, bstride);
     const int kb = k0 + blockIdx.x;
-    if (cond_ok[kb] != 0.0) return;
+    if (cond_ok && cond_ok[kb] != 0.0) return;
     __shared__ cplx as[32][33];
     __shared__ cplx ri[32][33];
     const int c = threadIdx.x >> 3, part = threadIdx.x & 7;

@@ -434,6 +434,11 @@ struct emagls_batch {
     CapturedGraph warm;                        // the warm form's stages before the sweep (the stages after it are the same in both forms)
     int last_form = 0;                         // the last execute: 0 independent designs (or another kind of batch), 1 cold, 2 warm
     long long geo_cold_runs = 0, geo_warm_runs = 0;
+    // the kept operand of the least-squares rows: Yls [bin 1 .. ls_end-1][C][ldD] = Y_reg_inv_k of plan 0's geometry, written by the
+    // cold run only (zls: its copy of plan 0's Z of those bins, solved against R^H in place); geo_ls_shared: this batch takes that form
+    // (batch_geo_decide_sharing)
+    bool geo_ls_shared = false;
+    emagls::DevMem yls, zls;
     emagls::DevMem cmp_flag;
     int nstreams = 1;                          // lane mode: streams the stages before the sweep fork onto (emagls_batch_set_streams)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
@@ -532,7 +537,8 @@ void magls_post_sweep(emagls_plan& p);
 bool plan_defers_hh_route(const emagls_plan& p);
 // the HRIR-side stages of an array design, for the plan h that owns the HRIR set on the geometry of plan g (h itself inside its own
 // pipeline): the ONE definition that emagls_pre_sweep and the geometry-sharing batch form (batch_geo_stage) both call
-void hrir_spectra(emagls_plan& h, const emagls_plan& g, hipStream_t st);
+// (transposed: also HcT, the direction-major copy of the least-squares bins' spectra that hrir_hh_rows reads)
+void hrir_spectra(emagls_plan& h, const emagls_plan& g, hipStream_t st, bool transposed = true);
 FactorArgs hh_factor_args(emagls_plan& h, emagls_plan& g, int* sweeps_out, double* cond_ok);
 void hrir_hh_rows(emagls_plan& h, emagls_plan& g, hipStream_t st);
 void hrir_hh_back(const FactorArgs& fa, const emagls_plan& g, hipStream_t st);

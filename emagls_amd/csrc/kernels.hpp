@@ -58,7 +58,7 @@ int64_t gram_dpad(int64_t D, int S);
 void launch_gram(const void* Yc, int64_t D, int S, int64_t ld, bool is_cplx, void* Gp, void* G, void* R, int Sh, hipStream_t st);
 void launch_cholesky(void* G, int S, bool is_cplx, int* flag, hipStream_t st);
 void launch_qform(const void* Yc, const void* R, void* Rinv, int S, int64_t D, int64_t ld, bool is_cplx, void* Q, hipStream_t st);
-// zs R^H = z for the rows Z[kb][c][:] of the flagged bins (cond_ok[kb] == 0), in place (complex basis)
+// zs R^H = z for the rows Z[kb][c][:] of the flagged bins (cond_ok[kb] == 0; cond_ok null: every bin of [k0, P)), in place (complex basis)
 void launch_zsolve_flagged(void* Z, int ldS, const void* R, const void* Rinv, const double* cond_ok, int S, int C, int P, int k0,
                            hipStream_t st);
 void launch_tn(const void* R, const void* E, int S, int C, int ldE, int nOrders, bool is_cplx, void* Tn, int64_t ldS,
@@ -128,6 +128,12 @@ int synth_ls_chunks(int D);
 void launch_synth_ls(const void* Hc, int64_t ldH, int n_c, const void* bsc, int nord_pad, const double* dir_azi, const double* dir_zen, const double* mic_azi,
                      const double* mic_zen, const int* smap, int D, int M, int P, int kb_lo, int kb_hi, void* Upart, hipStream_t st, bool shared_geometry = false);
 void launch_sweep_synth(const HalfSweepMulti& m, hipStream_t st);
+// ---- ls_shared.hip: least-squares rows of the HRIR sets of one geometry from the kept operand Yls [bin 1 .. ls_end-1][C][ldD] = Y_reg_inv_k
+// Gram-route bins [kb_lo, kb_hi) of a synthesising design: Yls[kb-1] = conj(g_kb) Pm^T conj(M_kb), g_kb from the angles (ONE design's operands)
+void launch_yls_gram(const void* bsc, int nord_pad, const double* dir_azi, const double* dir_zen, const double* mic_azi, const double* mic_zen,
+                     const int* smap, const double* Pm, const void* Mw, int D, int nOut, int kb_lo, int kb_hi, void* Yls, int64_t ldD, hipStream_t st);
+// W[e][kb][:] = Hc[e][kb][:] Yls[kb-1] for kb in [1, ls_end), for every lane of the launch context in ONE launch (Yls is the same for all)
+void launch_ls_shared_rows(const void* Hc, int64_t ldH, int ls_end, const void* Yls, int64_t ldD, int D, int C, int P, void* W, hipStream_t st);
 // ---- synth_debug.hip: synth_group<gs> on host arrays (bsc [nbins][nord_pad], x [nx]): g_plus / g_minus [nbins][nx] = E + O / E - O; synchronous
 // x2 [ndirs][nmics] = synth_x2 (twice the cosine between direction and microphone, as the sweeps form it) on host arrays; synchronous
 void synth_cosines_debug(const double* dir_azi, const double* dir_zen, int64_t ndirs, const double* mic_azi, const double* mic_zen, int nmics, double* x2);
@@ -193,6 +199,7 @@ void launch_dspace_g(const void* QT, int64_t ldD, bool is_cplx, const void* bn, 
                      hipStream_t st, int real_mode = 0, int sh_order = -1, int k_end = -1);
 void launch_cond_flags(const double* sv, int C, int P, int hh_end, double* cond_ok, hipStream_t st);
 // (Ycm: the column-major SH matrix [S][ldYcm] of a real basis -- the coalesced form; null: the row-major walk)
+// (cond_ok null: every bin of [k0, P), flagged or not -- the least-squares bins of the kept operand Yls, ls_shared.hip)
 void launch_yri_accurate(const void* Q, int64_t ldQ, bool is_cplx, const void* Z, int ldS, const double* cond_ok, int D, int S,
                          int C, int P, int k0, void* Yri, int64_t ldD, hipStream_t st, const void* Ycm = nullptr, int64_t ldYcm = 0);
 

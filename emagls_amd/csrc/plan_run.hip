@@ -591,14 +591,14 @@ bool plan_defers_hh_route(const emagls_plan& p) {
 // lane mode, with the lanes' own copies of plan 0's operands.  Both forms CALL these functions: that is what gives plan 0's filters
 // the same bits in a cold, a warm and a single-plan execute.
 // the spectra: H of the least-squares bins (and its transpose HcT for the rows below), |H| of the swept bins, the group delays
-void hrir_spectra(emagls_plan& h, const emagls_plan& g, hipStream_t st) {
+void hrir_spectra(emagls_plan& h, const emagls_plan& g, hipStream_t st, bool transposed) {
     const emagls_design_desc& d = h.d;
     const int ls_end = std::min(g.kcut0, g.P);
     launch_twiddles(h.nfft, h.get("tw"), st);
     launch_hrir_grpdelay(h.get<double>("hL"), h.get<double>("hR"), d.nsamp, d.ndirs, h.nfft, h.get("tw"), h.get<double>("dirsum"),
                          h.get<double>("grpd"), st);
     launch_hrir_fft(h.get<double>("hL"), h.get<double>("hR"), d.nsamp, h.D, nullptr, h.nfft, h.get("tw"), h.get<double>("grpd"), 0, ls_end,
-                    h.kcut0, h.get("Hc"), h.get<double>("Habs"), h.ldD, st, ls_end > 0 ? h.get<double>("HcT") : nullptr,
+                    h.kcut0, h.get("Hc"), h.get<double>("Habs"), h.ldD, st, (transposed && ls_end > 0) ? h.get<double>("HcT") : nullptr,
                     round_up(4 * std::max(ls_end, 1), 64));
 }
 // arguments of the Householder route's launches (factor.hip): Z, Hq, W and the status words are the HRIR set's, everything else the

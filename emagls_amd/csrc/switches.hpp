@@ -26,6 +26,7 @@ namespace emagls {
     X(STAGGER,           ON0,  1,     0, 1,         PROCESS, "=0: both lane groups of a batch issue the stages before the sweep in one order (default: complementary orders)") \
     X(DEFER_HH,          INT,  1,     0, 2,         PROCESS, "the orthonormal route of the low bins next to the sweep: 0 never, 1 batches and designs that have the device to themselves, 2 every lane batch") \
     X(GEO_KEEP,          ON0,  1,     0, 1,         PROCESS, "=0: sharing batches run their geometry stages on every execute") \
+    X(GEO_LS_SHARED,     ON0,  1,     0, 1,         CALL,    "=0: sharing batches carry every HRIR set's least-squares rows through the factors instead of one kept Y_reg_inv per bin") \
     X(GRAM_LDS,          ON0,  1,     0, 1,         PROCESS, "=0: lane batches take the K-split Gram kernel + reduce instead of the LDS-staged one") \
     X(GRAM_MFMA4,        ON1,  0,     0, 1,         CALL,    "=1: the Gram tile on the 4 x 4 x 4 MFMA shape (measured slower; the tests' second form)") \
     X(XCD_RUNS,          ON0,  1,     0, 1,         PROCESS, "=0: gram_lds, gemm_tn_f64, synth_ls take their tiles in dispatch order instead of XCD-aware runs") \

@@ -900,7 +900,9 @@ const char* emagls_plan_stage_name(emagls_plan* plan, int stage);
 int emagls_plan_stage_times(emagls_plan* plan, double* ms, int n);
 /* profiling level 2: sum and count of per-launch sweep kernel durations (ms) of the last execute */
 int emagls_plan_sweep_kernel_time(emagls_plan* plan, double* total_ms, int* launches);
-/* copy an internal device buffer to the host (tests): returns its size in *nbytes when dst == NULL */
+/* copy an internal device buffer to the host (tests): returns its size in *nbytes when dst == NULL.  "Yls": the kept operand of the
+   least-squares rows of the geometry-sharing batch the plan belongs to ([bin 1 .. k_cut-2][channel][padded directions], complex);
+   an error when the batch keeps none */
 int emagls_plan_debug_buffer(emagls_plan* plan, const char* name, void* dst, size_t* nbytes);
 /* the plan's hipStream_t, for callers that interleave their own work */
 void* emagls_plan_stream(emagls_plan* plan);
