@@ -21,6 +21,7 @@ hL/hR are [numSamples x numDirections]; filters come back [len x numChannels].
     getRenderedHrtfs        this project's: what a filter set renders per direction, and its error metrics
     getArrayIrs             this project's: impulse responses of the simulated array to plane-wave components
     getShoeboxComponents / getArrayRoomIrs   this project's: those components, and the responses, from a shoebox room (section 12)
+    getShoeboxImages / wallReflectionSpectra / airAttenuation   this project's: walls as reflection spectra and air absorption (section 13)
 
 A custom `shFunction` (a callable with getSH's signature: shFunction(N, [azi zen], shDefinition) -> [dirs x (N+1)^2]) cannot
 cross the C ABI as a handle: it is evaluated here, at the simulation order the library reports, and its matrices go through the
@@ -1373,7 +1374,45 @@ def _components(sources):
     return ptr, col(0, 0.0), col(1, 0.0), delay, gain
 
 
-def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4, encoder=None, nfft=None):
+def _nfft_for(irLen, nfft):
+    """The transform length of a spectral call, which must be given to the C ABI: nfft, or the smallest power of two >= 2 irLen."""
+    if nfft:
+        return int(nfft)
+    n = 8
+    while n < 2 * int(irLen) and n < 65536:
+        n *= 2
+    return n
+
+
+def _spectra(what, a, rows, P):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    want = (P,) if rows is None else (rows, P)
+    if a.shape != want:
+        raise ValueError("%s must have the shape %s (nfft / 2 + 1 = %d bins), got %s" % (what, want, P, a.shape))
+    return a
+
+
+def _per_component(what, arrs, ptr, width, dtype):
+    """A list shaped like `sources` ([J_q] or [J_q x width] per source) as one contiguous array over the components."""
+    if not isinstance(arrs, (list, tuple)) or len(arrs) != ptr.size - 1:
+        raise ValueError("%s must be a list with one array per source" % what)
+    out = []
+    for q, a in enumerate(arrs):
+        a = np.asarray(a)
+        J = int(ptr[q + 1] - ptr[q])
+        if a.size != J * width:
+            raise ValueError("%s[%d] must hold %d x %d values, got %d" % (what, q, J, width, a.size))
+        if dtype is np.int32 and a.size and not np.array_equal(a, np.round(a)):
+            raise ValueError("%s must be integers" % what)
+        out.append(a.reshape(J, width))
+    flat = np.concatenate(out) if out else np.zeros((0, width))
+    if dtype is np.int32 and flat.size and (np.abs(flat) >= 2 ** 31).any():
+        raise ValueError("%s must fit 32 bits" % what)
+    return np.ascontiguousarray(flat, dtype=dtype)
+
+
+def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4, encoder=None, nfft=None, surfaceReflection=None,
+                exponents=None, airAttenuation=None, pathLength=None):
     """Impulse responses of the simulated rigid-sphere array (the array of getSMAIRMatrix) to sources that are sums of plane-wave
     components (include/emagls.h, emagls_array_irs).  `sources` is a [Q x 2] array of directions (azi, zen),
     one unit plane wave each -- a direction bank for a moving virtual source -- or a list of Q arrays [J_q x 2|3|4] with the columns
@@ -1382,11 +1421,39 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
     [M x 2]; `order` only enters the simulation order max(order, ceil(fs pi r / 343)); `encoder` [C x M] is what arrayEncoder(...)
     returns (absent: the raw microphones, C = M).  nfft: a power of two from 8 to 65536, default the smallest one >= 2 irLen.
     Returns [Q x irLen x C], complex with a complex encoder: the `rirs` of SourceFieldStream for Q sources, or [:, None] for a bank
-    of Q sets of one source."""
+    of Q sets of one source.
+    The spectral gain (emagls_array_irs_spectral): surfaceReflection [W x P], W <= 8 real reflection spectra in
+    [-1, 1] over the P = nfft / 2 + 1 bins, with `exponents`, a list shaped like `sources` of integer arrays [J_q x W]; and
+    airAttenuation [P] in Np/m with pathLength, a list of [J_q] arrays in metres (both or neither).  A component's gain becomes
+    gain prod_w R_w(k)^e_w exp(-alpha(k) l) in bin k.  With none of the four given, this is the call without them."""
     ptr, azi, zen, delay, gain = _components(sources)
     maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
     Q = ptr.size - 1
     out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
+    if any(a is not None for a in (surfaceReflection, exponents, airAttenuation, pathLength)):
+        if (surfaceReflection is None) != (exponents is None):
+            raise ValueError("surfaceReflection and exponents must both be given or both be absent")
+        if (airAttenuation is None) != (pathLength is None):
+            raise ValueError("airAttenuation and pathLength must both be given or both be absent")
+        n_fft = _nfft_for(nr, nfft)
+        P = n_fft // 2 + 1
+        refl = ex = att = path = None
+        W = 0
+        if surfaceReflection is not None:
+            refl = np.ascontiguousarray(np.atleast_2d(np.asarray(surfaceReflection, dtype=np.float64)))
+            W = refl.shape[0]
+            refl = _spectra("surfaceReflection", refl, W, P)
+            ex = _per_component("exponents", exponents, ptr, W, np.int32)
+        if airAttenuation is not None:
+            att = _spectra("airAttenuation", airAttenuation, None, P)
+            path = _per_component("pathLength", pathLength, ptr, 1, np.float64)
+            if path.size == 0:
+                path = np.zeros((1, 1))        # (the pair rule is on the pointers)
+        L.check(L.load().emagls_array_irs_spectral(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q,
+                                                   _addr(ptr), _addr(azi), _addr(zen), _addr(delay), _addr(gain), W, _addr(refl),
+                                                   _addr(ex) if ex is not None and ex.size else None, _addr(att), _addr(path), float(preDelay),
+                                                   n_fft, nr, _addr(out)))
+        return np.ascontiguousarray(out.transpose(0, 2, 1))
     L.check(L.load().emagls_array_irs(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q, _addr(ptr),
                                       _addr(azi), _addr(zen), _addr(delay), _addr(gain), float(preDelay), int(nfft) if nfft else 0, nr, _addr(out)))
     return np.ascontiguousarray(out.transpose(0, 2, 1))
@@ -1448,20 +1515,94 @@ def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDe
     return [np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)]
 
 
+def getShoeboxImages(roomDim, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None):
+    """The image sources of a shoebox room without its walls (include/emagls.h, emagls_shoebox_images): every
+    candidate within maxOrder and maxDelay, for walls that are reflection spectra.  Returns (components, exponents, paths), one list
+    of Q arrays each: [J_q x 4] with the columns azi, zen, delay in samples and gain = 1 / distance -- the bits of
+    getShoeboxComponents with all six coefficients 1 --, [J_q x 6] int32 exponents of the walls x=0, x=Lx, y=0, y=Ly, z=0, z=Lz, and
+    [J_q] distances in metres: the `sources`, `exponents` and `pathLength` of getArrayIrs."""
+    dim, _refl, pos, src, mo = _room(roomDim, np.ones(6), sourcePos, arrayPos, maxOrder)
+    Q = src.shape[0]
+    ptr = np.zeros(Q + 1, dtype=np.int64)
+    lib = L.load()
+    head = (_addr(dim), _addr(pos), Q, _addr(src), float(fs), float(maxDelay), mo)
+    L.check(lib.emagls_shoebox_images(*head, 0, _addr(ptr), None, None, None, None, None, None))          # the counts
+    n = int(ptr[-1])
+    cols, ex, path = np.zeros((4, max(n, 1))), np.zeros((max(n, 1), 6), dtype=np.int32), np.zeros(max(n, 1))
+    if n:
+        L.check(lib.emagls_shoebox_images(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3]), _addr(ex),
+                                          _addr(path)))
+    cut = lambda a: [np.ascontiguousarray(a[ptr[q]:ptr[q + 1]]) for q in range(Q)]   # noqa: E731
+    return cut(cols.T), cut(ex), cut(path)
+
+
+def wallReflectionSpectra(absorption, bandCentresHz, fs, nfft):
+    """Reflection spectra [S x P] over the bins f_k = k fs / nfft, k = 0 .. nfft / 2, from absorption coefficients per band as data
+    sheets give them (host only): `absorption` [S x nb] (or [nb]) in [0, 1] at the ascending band centres bandCentresHz [nb], is
+    interpolated linearly in log2 f between the centres and held constant outside them (bin 0 takes the first band's value); then
+    R = sqrt(1 - a)."""
+    a = np.atleast_2d(np.asarray(absorption, dtype=np.float64))
+    fc = np.asarray(bandCentresHz, dtype=np.float64).ravel()
+    if a.shape[1] != fc.size or fc.size < 1:
+        raise ValueError("absorption must be [numSurfaces x numBands] with one column per band centre")
+    if not (np.all(fc > 0) and np.all(np.diff(fc) > 0)):
+        raise ValueError("bandCentresHz must be positive and ascending")
+    if not (np.all(a >= 0) and np.all(a <= 1)):
+        raise ValueError("absorption coefficients must lie in [0, 1]")
+    f = np.arange(int(nfft) // 2 + 1) * (float(fs) / int(nfft))
+    x = np.full(f.size, -np.inf)
+    x[1:] = np.log2(f[1:])
+    return np.sqrt(1.0 - np.stack([np.interp(x, np.log2(fc), row) for row in a]))
+
+
+def airAttenuation(fs, nfft, temperatureC=20.0, relHumidityPercent=50.0, pressureKPa=101.325):
+    """The attenuation of sound in air over the bins f_k = k fs / nfft, k = 0 .. nfft / 2, in nepers per metre (host only): the
+    pure-tone formula of ISO 9613-1, dB/m times ln(10) / 20."""
+    T0, T01, pr = 293.15, 273.16, 101.325
+    T, pa, hr = float(temperatureC) + 273.15, float(pressureKPa), float(relHumidityPercent)
+    f = np.arange(int(nfft) // 2 + 1) * (float(fs) / int(nfft))
+    psat = 10.0 ** (-6.8346 * (T01 / T) ** 1.261 + 4.6151)
+    h = hr * psat / (pa / pr)
+    frO = (pa / pr) * (24.0 + 4.04e4 * h * (0.02 + h) / (0.391 + h))
+    frN = (pa / pr) * (T / T0) ** -0.5 * (9.0 + 280.0 * h * np.exp(-4.170 * ((T / T0) ** (-1.0 / 3.0) - 1.0)))
+    db = 8.686 * f * f * (1.84e-11 * (pr / pa) * (T / T0) ** 0.5 +
+                          (T / T0) ** -2.5 * (0.01275 * np.exp(-2239.1 / T) / (frO + f * f / frO) +
+                                              0.1068 * np.exp(-3352.0 / T) / (frN + f * f / frN)))
+    return db * (np.log(10.0) / 20.0)
+
+
 def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4,
-                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False):
+                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False, airAttenuation=None):
     """Impulse responses of the simulated rigid-sphere array in a shoebox room (include/emagls.h,
     emagls_array_room_irs): getArrayIrs(getShoeboxComponents(...), ...) bit for bit, with the components enumerated on the device
     and fed to the responses' kernels there.  The room as in getShoeboxComponents (the array's whole sphere inside it), the array
     as in getArrayIrs.  maxDelay (samples): default irLen - 1 - preDelay, the last component that lands inside the returned taps.
-    Returns [Q x irLen x C]; with returnCounts also the number of components of each source ([Q] int64)."""
-    dim, refl, pos, src, mo = _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder)
+    Returns [Q x irLen x C]; with returnCounts also the number of components of each source ([Q] int64).
+    The spectral room (emagls_array_room_irs_spectral): wallReflection [6 x P], one reflection spectrum per wall
+    over the P = nfft / 2 + 1 bins (wallReflectionSpectra makes them from absorption coefficients), and / or airAttenuation [P] in
+    Np/m (the function airAttenuation of this module), each component's path its distance; six coefficients with an airAttenuation are
+    repeated over the bins.  Then every image within maxOrder and maxDelay is a component (getShoeboxImages), also behind a wall of 0."""
+    spectral = np.ndim(wallReflection) == 2 or airAttenuation is not None
+    dim, refl, pos, src, mo = _room(roomDim, np.ones(6) if spectral else wallReflection, sourcePos, arrayPos, maxOrder)
     maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
     Q = src.shape[0]
     if maxDelay is None:
         maxDelay = nr - 1 - float(preDelay)
     out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
     counts = np.zeros(Q, dtype=np.int64)
+    if spectral:
+        n_fft = _nfft_for(nr, nfft)
+        P = n_fft // 2 + 1
+        w = np.asarray(wallReflection, dtype=np.float64)
+        if w.ndim == 1:
+            w = np.repeat(_vec(w, 6, "wallReflection")[0][:, None], P, axis=1)
+        w = _spectra("wallReflection", w, 6, P)
+        att = None if airAttenuation is None else _spectra("airAttenuation", airAttenuation, None, P)
+        L.check(L.load().emagls_array_room_irs_spectral(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc,
+                                                        _addr(dim), _addr(w), _addr(att), _addr(pos), Q, _addr(src), float(maxDelay), mo,
+                                                        float(preDelay), n_fft, nr, _addr(counts), _addr(out)))
+        out = np.ascontiguousarray(out.transpose(0, 2, 1))
+        return (out, counts) if returnCounts else out
     L.check(L.load().emagls_array_room_irs(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, _addr(dim),
                                            _addr(refl), _addr(pos), Q, _addr(src), float(maxDelay), mo, float(preDelay), int(nfft) if nfft else 0,
                                            nr, _addr(counts), _addr(out)))

@@ -18,6 +18,17 @@
 //                                order, no reduction (a direction bank is J = 1 for thousands of sources; an empty source gives zeros)
 // No atomics; every order is fixed.
 //
+// THE SPECTRAL GAIN: with W <= 8 surfaces of real reflection spectra R_w(k), integer exponents e_jw >= 0 per
+// component, and optionally an attenuation alpha(k) in Np/m and a path length l_j, g_j becomes
+//   G_j(k) = g_j prod_w R_w(k)^e_jw exp(-alpha(k) l_j) = g_j (-1)^(number of w with R_w(k) < 0 and e_jw odd) exp(sum_w e_jw ln|R_w(k)| - alpha(k) l_j).
+// It depends on component and bin, so it is formed inside the main kernel, in a kernel of its own (air_two_mics_kernel, both forms;
+// the flat kernels are not touched): the per-bin tables ln|R_w|, the sign bits and alpha come wave-uniformly next to b'
+// (air_spectra_kernel writes them with the padding of Pld), the exponents and the path are per-lane loads, and one exp per
+// (component, bin) does the rest.  ln|0| is stored as AIR_LN_ZERO, large, finite and negative: e = 0 gives the factor exp(-0) = 1,
+// e > 0 gives exp(-huge) = 0 exactly.  A wave owns TWO microphones there, which share G, the phases and the loads of b': measured
+// against one microphone per wave and against binary powers per surface in profiles/r27_room_spectral.md.  Per microphone the
+// operations and their order are those of the flat kernel with G_r w_r in the place of (g w)_r.
+//
 // The rest of the chain: air_modes_kernel (the factor (2n+1) on launch_modal_bn's output, real part in the last bin, and the
 // recurrence's coefficients), air_prepare_kernel (unit vectors, delays split into integer and fraction), and the inverse real
 // transform per (source, channel) with the encoder in its load: on the LDS passes of lds_fft.hpp up to nfft = 4096
@@ -84,6 +95,123 @@ struct AirArgs {
     int64_t Pld, ncomp;
     cplx* H;               // [Q][M][Pld]
 };
+
+constexpr double AIR_LN_ZERO = -1.0e300;   // stands for ln|0|: 0 * AIR_LN_ZERO = -0, e * AIR_LN_ZERO <= -1e300 for e >= 1
+
+struct AirArgsSpectral : AirArgs {
+    const double* lnr;     // [W][Pld] ln|R_w(k)|, AIR_LN_ZERO where R_w(k) = 0, zeros beyond P
+    const unsigned* neg;   // [Pld] bit w: R_w(k) < 0
+    const double* att;     // [Pld] alpha(k), zeros beyond P; null (with path): no air term
+    const int* exp;        // [ncomp][W]
+    const double* path;    // [ncomp]
+    int W;
+};
+
+// the tables of the spectral gain from refl [W][P] and att [P] (or null); grid over Pld
+__global__ void __launch_bounds__(256) air_spectra_kernel(int W, int P, int64_t Pld, const double* __restrict__ refl, const double* __restrict__ att,
+                                                         double* __restrict__ lnr, unsigned* __restrict__ neg, double* __restrict__ attp) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= Pld) return;
+    unsigned bits = 0;
+    for (int w = 0; w < W; ++w) {
+        const double r = k < P ? refl[(int64_t)w * P + k] : 1.0;
+        if (r < 0.0) bits |= 1u << w;
+        lnr[(int64_t)w * Pld + k] = r == 0.0 ? AIR_LN_ZERO : log(fabs(r));
+    }
+    neg[k] = bits;
+    if (att) attp[k] = k < P ? att[k] : 0.0;
+}
+
+// the spectral gains of component j in the AIR_R bins from k0: G[r] = +-g exp(sum_w e_w ln|R_w(k0 + r)| - alpha(k0 + r) l), the
+// arguments summed first (the surfaces ascending on top of the air term), the sign from the bins' masks and the exponents' parities
+__device__ __forceinline__ void air_gains(const AirArgsSpectral& a, int k0, int64_t j, double g, double (&G)[AIR_R]) {
+    const double len = a.att ? a.path[j] : 0.0;
+    const int* __restrict__ e = a.exp + j * a.W;
+    const double* __restrict__ l = a.lnr + k0;
+    double arg[AIR_R];
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) arg[r] = a.att ? -(a.att[k0 + r] * len) : 0.0;
+    unsigned odd = 0;
+    for (int t = 0; t < a.W; ++t, l += a.Pld) {
+        const int et = e[t];
+        const double ed = (double)et;
+        odd |= (unsigned)(et & 1) << t;
+#pragma unroll
+        for (int r = 0; r < AIR_R; ++r) arg[r] = fma(ed, l[r], arg[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) G[r] = ((__popc(a.neg[k0 + r] & odd) & 1) ? -g : g) * exp(arg[r]);
+}
+
+// the same for the two microphones of a wave, which share G, the phases and the loads of b': sum[i][r] += G_r w_r sum_n b'_n P_n(x_i)
+__device__ __forceinline__ void air_component2(const AirArgsSpectral& a, int k0, int64_t j, const double (&vx)[2], const double (&vy)[2],
+                                               const double (&vz)[2], cplx (&sum)[2][AIR_R]) {
+    const double ux = a.u[j], uy = a.u[a.ncomp + j], uz = a.u[2 * a.ncomp + j];
+    const double x0 = fma(uz, vz[0], fma(uy, vy[0], ux * vx[0])), x1 = fma(uz, vz[1], fma(uy, vy[1], ux * vx[1]));
+    cplx acc0[AIR_R], acc1[AIR_R];
+    const cplx* __restrict__ b = a.bn + k0;
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) acc0[r] = acc1[r] = b[r];   // n = 0: P_0 = 1
+    double p0 = 1.0, p1 = x0, q0 = 1.0, q1 = x1;
+    for (int n = 1; n <= a.N; ++n) {
+        b += a.Pld;
+#pragma unroll
+        for (int r = 0; r < AIR_R; ++r) { cfma(acc0[r], b[r], p1); cfma(acc1[r], b[r], q1); }
+        const double p2 = fma(a.rec[2 * n] * x0, p1, -(a.rec[2 * n + 1] * p0)), q2 = fma(a.rec[2 * n] * x1, q1, -(a.rec[2 * n + 1] * q0));
+        p0 = p1; p1 = p2; q0 = q1; q1 = q2;
+    }
+    const unsigned di = (unsigned)a.dint[j];
+    const double df = a.dfrac[j], inv = 1.0 / (double)a.nfft, g = a.gain ? a.gain[j] : 1.0;
+    const unsigned ki = ((unsigned)k0 * di) & (unsigned)(a.nfft - 1);
+    cplx w, s;
+    sincospi(-2.0 * (((double)ki + (double)k0 * df) * inv), &w.y, &w.x);
+    sincospi(-2.0 * (((double)di + df) * inv), &s.y, &s.x);
+    double G[AIR_R];
+    air_gains(a, k0, j, g, G);
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) {
+        const cplx gw = G[r] * w;
+        cfma(sum[0][r], gw, acc0[r]);
+        cfma(sum[1][r], gw, acc1[r]);
+        w = w * s;
+    }
+}
+
+// the two forms with two microphones per wave: grid.y = ceil(M / 8), wave w takes the microphones 8 blockIdx.y + 2 w and the next
+// (an odd M's last wave computes its one microphone twice and stores it once)
+template <bool LANE_IS_SOURCE>
+__global__ void __launch_bounds__(256) air_two_mics_kernel(AirArgsSpectral a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int m0 = blockIdx.y * 8 + 2 * wave;
+    if (m0 >= a.M) return;
+    const int m1 = m0 + 1 < a.M ? m0 + 1 : m0, k0 = blockIdx.x * AIR_R;
+    int q;
+    if (LANE_IS_SOURCE) {
+        const int i = blockIdx.z * 64 + lane;
+        if (i >= a.nlist) return;
+        q = a.list[i];
+    } else {
+        q = a.list[blockIdx.z];
+    }
+    const double vx[2] = {a.v[m0], a.v[m1]}, vy[2] = {a.v[a.M + m0], a.v[a.M + m1]}, vz[2] = {a.v[2 * a.M + m0], a.v[2 * a.M + m1]};
+    cplx sum[2][AIR_R];
+#pragma unroll
+    for (int r = 0; r < AIR_R; ++r) sum[0][r] = sum[1][r] = mk(0.0, 0.0);
+    const int64_t j1 = a.ptr[q + 1];
+    for (int64_t j = a.ptr[q] + (LANE_IS_SOURCE ? 0 : lane); j < j1; j += LANE_IS_SOURCE ? 1 : 64) air_component2(a, k0, j, vx, vy, vz, sum);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if (i == 1 && m1 == m0) break;
+        cplx* out = a.H + ((int64_t)q * a.M + (i ? m1 : m0)) * a.Pld;
+#pragma unroll
+        for (int r = 0; r < AIR_R; ++r) {
+            cplx t = LANE_IS_SOURCE ? sum[i][r] : wave_sum(sum[i][r]);
+            const int k = k0 + r;
+            if (k == a.P - 1) t.y = 0.0;   // the last bin's value is the real part of the sum
+            if ((LANE_IS_SOURCE || lane == 0) && k < a.P) out[k] = t;
+        }
+    }
+}
 
 // one component's terms of the AIR_R bins from k0: sum[r] += g w_r sum_n b'_n(k0 + r) P_n(x)
 __device__ __forceinline__ void air_component(const AirArgs& a, int k0, int64_t j, double vx, double vy, double vz, cplx (&sum)[AIR_R]) {
@@ -253,21 +381,39 @@ void launch_air_delays(int64_t n, const double* delay, double pre_delay, int nff
     KERNEL_CHECK();
 }
 
-void launch_air_main(const AirMain& m, hipStream_t st) {
-    AirArgs a{};
+void launch_air_spectra(int W, int P, int64_t Pld, const double* refl, const double* att, double* lnr, unsigned* neg, double* attp,
+                        hipStream_t st) {
+    air_spectra_kernel<<<(unsigned)ceil_div(Pld, 256), 256, 0, st>>>(W, P, Pld, refl, att, lnr, neg, attp);
+    KERNEL_CHECK();
+}
+
+// the source lists of both forms in slices (grid.z stops at 65535): kernel_long on slices of the long sources, kernel_short on 64
+// short sources per grid.z
+template <class Args, class KL, class KS>
+static void air_main_launches(Args& a, const AirMain& m, unsigned gy, KL kernel_long, KS kernel_short, hipStream_t st) {
     a.bn = (const cplx*)m.bn; a.rec = m.rec; a.u = m.u; a.v = m.v; a.dint = m.dint; a.dfrac = m.dfrac; a.gain = m.gain; a.ptr = m.ptr;
     a.N = m.N; a.M = m.M; a.P = m.P; a.nfft = m.nfft; a.Pld = m.Pld; a.ncomp = m.ncomp; a.H = (cplx*)m.H;
-    const unsigned gx = (unsigned)(m.Pld / AIR_R), gy = (unsigned)ceil_div(m.M, 4);
-    // (grid.z stops at 65535: the lists go in slices)
+    const unsigned gx = (unsigned)(m.Pld / AIR_R);
     for (int i0 = 0; i0 < m.n_long; i0 += 65535) {
         a.list = m.list_long + i0; a.nlist = std::min(65535, m.n_long - i0);
-        air_lane_component_kernel<<<dim3(gx, gy, (unsigned)a.nlist), 256, 0, st>>>(a);
+        kernel_long<<<dim3(gx, gy, (unsigned)a.nlist), 256, 0, st>>>(a);
         KERNEL_CHECK();
     }
     for (int i0 = 0; i0 < m.n_short; i0 += 65535 * 64) {
         a.list = m.list_short + i0; a.nlist = std::min(65535 * 64, m.n_short - i0);
-        air_lane_source_kernel<<<dim3(gx, gy, (unsigned)ceil_div(a.nlist, 64)), 256, 0, st>>>(a);
+        kernel_short<<<dim3(gx, gy, (unsigned)ceil_div(a.nlist, 64)), 256, 0, st>>>(a);
         KERNEL_CHECK();
+    }
+}
+
+void launch_air_main(const AirMain& m, hipStream_t st) {
+    if (m.nsurf > 0 || m.att) {
+        AirArgsSpectral a{};
+        a.lnr = m.lnr; a.neg = m.neg; a.att = m.att; a.exp = m.exp; a.path = m.path; a.W = m.nsurf;
+        air_main_launches(a, m, (unsigned)ceil_div(m.M, 8), air_two_mics_kernel<false>, air_two_mics_kernel<true>, st);
+    } else {
+        AirArgs a{};
+        air_main_launches(a, m, (unsigned)ceil_div(m.M, 4), air_lane_component_kernel, air_lane_source_kernel, st);
     }
 }
 

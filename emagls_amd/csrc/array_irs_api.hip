@@ -1,5 +1,6 @@
-// C ABI of the array impulse responses (include/emagls.h; DESIGN.md sections 11 and 12): emagls_array_irs from listed components,
-// emagls_shoebox_components and emagls_array_room_irs from a shoebox room.  Host arrays in, host array out; every argument is
+// C ABI of the array impulse responses (include/emagls.h; DESIGN.md sections 11 to 13): emagls_array_irs from listed components,
+// emagls_shoebox_components and emagls_array_room_irs from a shoebox room, and their spectral forms (reflection spectra per surface
+// and air absorption: emagls_array_irs_spectral, emagls_shoebox_images, emagls_array_room_irs_spectral).  Host arrays in, host array out; every argument is
 // checked before the device is touched (a room call's scratch estimate, which needs the component count, after its count pass), and
 // every array operation runs in the kernels of array_irs.hip, shoebox.hip, modal.hip and fft.hip (the twiddles), with hipFFT's Z2D
 // above 4096 points (the precedent of decode.hip above 2048 taps).  The speed of sound and the simulation order are
@@ -24,6 +25,7 @@ constexpr int AIR_SIM_ORDER_MAX = 85;
 constexpr int64_t AIR_NFFT_MAX = 65536;
 constexpr int AIR_NFFT_LDS_MAX = 4096;     // the LDS transforms of lds_fft.hpp; hipFFT above
 constexpr size_t AIR_SCRATCH_MAX = (size_t)24 << 30;
+constexpr int AIR_SURFACES_MAX = 8;
 constexpr int64_t SBX_CAND_MAX = (int64_t)1 << 28;   // image-source candidates of one call, all sources together
 
 void fft_check(hipfftResult r, const char* what) {
@@ -95,9 +97,32 @@ AirCall air_check(double fs, double mic_radius, int order, const double* mic_azi
     return c;
 }
 
-// the device memory estimate of a call with ncomp components (in long double: the counts of a refused call may overflow 64 bits)
-void air_check_scratch(const AirCall& c, int64_t ncomp) {
-    const long double need = (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
+// the spectral gain of a call, checked: nsurf reflection spectra refl [nsurf][P] and the attenuation att [P] or
+// null on the host; the exponents exp [ncomp][nsurf] and the paths path [ncomp] (with att) on the device
+struct AirSpectral {
+    int nsurf = 0;
+    const double *refl = nullptr, *att = nullptr;
+    const int* d_exp = nullptr;
+    const double* d_path = nullptr;
+    bool any() const { return nsurf > 0 || att; }
+};
+
+// the rules of the spectra: finite, |R| <= 1, alpha >= 0
+void air_check_spectra(int64_t nsurf, const double* refl, const double* att, int P, const char* what) {
+    if (nsurf < 0 || nsurf > AIR_SURFACES_MAX) throw Error(EMAGLS_ERR_ARG, "nsurf must lie in 0 .. 8");
+    if (nsurf > 0 && !refl) throw Error(EMAGLS_ERR_ARG, std::string("null pointer: ") + what);
+    for (int64_t i = 0; i < nsurf * P; ++i)
+        if (!(std::fabs(refl[i]) <= 1.0)) throw Error(EMAGLS_ERR_ARG, "reflection spectra must be finite and lie in [-1, 1]");
+    for (int k = 0; att && k < P; ++k)
+        if (!(att[k] >= 0.0) || !std::isfinite(att[k])) throw Error(EMAGLS_ERR_ARG, "air attenuation must be non-negative and finite");
+}
+
+// the device memory estimate of a call with ncomp components, nsurf surfaces and (air) an air term (in long double: the counts of a
+// refused call may overflow 64 bits); room: the enumeration's lists are counted too
+void air_check_scratch(const AirCall& c, int64_t ncomp, int nsurf = 0, bool air = false) {
+    const long double spectral = nsurf > 0 || air ? (long double)(nsurf + 1) * (c.Pld + c.P) * 8 + (long double)c.Pld * 4 +
+                                                        (long double)ncomp * (4 * nsurf + (air ? 8 : 0)) : 0.0L;
+    const long double need = spectral + (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
                              (long double)c.nsrc * 12 + (long double)c.out_bytes +
                              (c.lds ? 0.0L : (c.enc ? (long double)c.rows * c.np * c.P * 16 : 0.0L) + (long double)c.rows * c.np * c.nfft * 8);
     if (need > (long double)AIR_SCRATCH_MAX)
@@ -105,9 +130,9 @@ void air_check_scratch(const AirCall& c, int64_t ncomp) {
 }
 
 // stages 1 to 4 on components that are on the device: d_ptr [nsrc + 1] and its host copy h_ptr, d_azi, d_zen [ncomp], d_delay and
-// d_gain [ncomp] or null (zeros, ones).  The result is copied to c.out and the stream synchronised.
+// d_gain [ncomp] or null (zeros, ones); sp: the spectral gain, or none.  The result is copied to c.out and the stream synchronised.
 void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* d_ptr, const double* d_azi, const double* d_zen,
-             const double* d_delay, const double* d_gain) {
+             const double* d_delay, const double* d_gain, const AirSpectral& sp = AirSpectral()) {
     const int N = c.N, nfft = c.nfft, P = c.P, M = c.M, C = c.C, np = c.np;
     const int64_t nsrc = c.nsrc, nr = c.nr, Pld = c.Pld, rows = c.rows, ncomp = h_ptr[nsrc];
     const double* enc = (const double*)c.enc;
@@ -148,6 +173,13 @@ void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* 
     m.list_short = s.put_opt(list_short.data(), list_short.size());
     m.n_long = (int)list_long.size(); m.n_short = (int)list_short.size();
     m.N = N; m.M = M; m.P = P; m.nfft = nfft; m.Pld = Pld; m.ncomp = ncomp;
+    if (sp.any()) {                                    // the per-bin tables of the spectral gain
+        double* lnr = s.get<double>(sizeof(double) * (size_t)std::max(sp.nsurf, 1) * Pld);
+        unsigned* neg = s.get<unsigned>(sizeof(unsigned) * (size_t)Pld);
+        double* att = sp.att ? s.get<double>(sizeof(double) * (size_t)Pld) : nullptr;
+        launch_air_spectra(sp.nsurf, P, Pld, s.put_opt(sp.refl, (size_t)sp.nsurf * P), s.put_opt(sp.att, sp.att ? (size_t)P : 0), lnr, neg, att, s.st);
+        m.nsurf = sp.nsurf; m.lnr = lnr; m.neg = neg; m.att = att; m.exp = sp.d_exp; m.path = sp.d_path;
+    }
     cplx* H = s.get<cplx>(sizeof(cplx) * (size_t)nsrc * M * Pld);
     m.H = H;
     // 3. the main kernel
@@ -189,6 +221,7 @@ void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* 
 ShoeboxArgs shoebox_check(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc, const double* src_pos,
                           double fs, double mic_radius, double max_delay, int max_order) {
     if (!room_dim || !wall_refl || !array_pos || !src_pos) throw Error(EMAGLS_ERR_ARG, "null pointer: room_dim, wall_refl, array_pos or src_pos");
+    // (the spectral entries pass SBX_ONES: the enumeration does not see their walls)
     if (nsrc < 1) throw Error(EMAGLS_ERR_ARG, "invalid shape: nsrc");
     if (!(fs > 0) || !std::isfinite(fs)) throw Error(EMAGLS_ERR_ARG, "fs must be positive");
     if (!(max_delay > 0.0) || !std::isfinite(max_delay)) throw Error(EMAGLS_ERR_ARG, "max_delay must be positive and finite");
@@ -243,7 +276,8 @@ struct Shoebox {
     const double* src = nullptr;
     uint64_t* mask = nullptr;
     int64_t *base = nullptr, *ptr = nullptr;
-    double *azi = nullptr, *zen = nullptr, *delay = nullptr, *gain = nullptr;
+    double *azi = nullptr, *zen = nullptr, *delay = nullptr, *gain = nullptr, *path = nullptr;
+    int* exp = nullptr;                      // [total][6], with path: fill(true)
     std::vector<int64_t> h_ptr;
     EventPair ev_count, ev_write;
     bool written = false;
@@ -264,18 +298,39 @@ struct Shoebox {
         s.sync();
     }
     int64_t total() const { return h_ptr.back(); }
-    void fill() {
+    void fill(bool images = false) {
         const size_t n = (size_t)total();
         azi = s.get<double>(sizeof(double) * n); zen = s.get<double>(sizeof(double) * n);
         delay = s.get<double>(sizeof(double) * n); gain = s.get<double>(sizeof(double) * n);
+        if (images) { exp = s.get<int>(sizeof(int) * 6 * n); path = s.get<double>(sizeof(double) * n); }
         HIP_CHECK(hipEventRecord(ev_write.a, s.st));
-        if (n) launch_shoebox_write(a, nsrc, src, mask, base, azi, zen, delay, gain, s.st);
+        if (n && images) launch_shoebox_write_images(a, nsrc, src, mask, base, azi, zen, delay, gain, exp, path, s.st);
+        else if (n) launch_shoebox_write(a, nsrc, src, mask, base, azi, zen, delay, gain, s.st);
         HIP_CHECK(hipEventRecord(ev_write.b, s.st));
         written = true;
     }
     // after a synchronisation of s.st
     void keep_time() const { g_shoebox_ms = ev_count.ms() + (written ? ev_write.ms() : 0.0); }
 };
+
+const double SBX_ONES[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};   // the walls of a spectral room's enumeration: gain = 1 / d, nothing dropped
+
+// the component lists of emagls_array_irs and emagls_array_irs_spectral, checked; returns ncomp
+int64_t air_check_lists(const AirCall& c, const int64_t* comp_ptr, const double* comp_azi, const double* comp_zen, const double* comp_delay,
+                        const double* comp_gain) {
+    if (comp_ptr[0] != 0) throw Error(EMAGLS_ERR_ARG, "comp_ptr must start at 0");
+    for (int64_t q = 0; q < c.nsrc; ++q)
+        if (comp_ptr[q + 1] < comp_ptr[q]) throw Error(EMAGLS_ERR_ARG, "comp_ptr must not decrease");
+    const int64_t ncomp = comp_ptr[c.nsrc];
+    if (ncomp > 0 && (!comp_azi || !comp_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: component directions");
+    for (int64_t j = 0; comp_delay && j < ncomp; ++j) {
+        if (!(comp_delay[j] >= 0.0) || !std::isfinite(comp_delay[j])) throw Error(EMAGLS_ERR_ARG, "component delays must be non-negative and finite");
+        if (comp_delay[j] + c.pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "a component's delay plus pre_delay beyond nfft - 1 would wrap");
+    }
+    for (int64_t j = 0; comp_gain && j < ncomp; ++j)
+        if (!std::isfinite(comp_gain[j])) throw Error(EMAGLS_ERR_ARG, "component gains must be finite");
+    return ncomp;
+}
 
 }  // namespace
 
@@ -287,23 +342,44 @@ extern "C" int emagls_array_irs(double fs, double mic_radius, int order, const d
         // ---- arguments (nothing below this block fails on what the caller passed)
         if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
         const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
-        if (comp_ptr[0] != 0) throw Error(EMAGLS_ERR_ARG, "comp_ptr must start at 0");
-        for (int64_t q = 0; q < nsrc; ++q)
-            if (comp_ptr[q + 1] < comp_ptr[q]) throw Error(EMAGLS_ERR_ARG, "comp_ptr must not decrease");
-        const int64_t ncomp = comp_ptr[nsrc];
-        if (ncomp > 0 && (!comp_azi || !comp_zen)) throw Error(EMAGLS_ERR_ARG, "null pointer: component directions");
-        for (int64_t j = 0; comp_delay && j < ncomp; ++j) {
-            if (!(comp_delay[j] >= 0.0) || !std::isfinite(comp_delay[j])) throw Error(EMAGLS_ERR_ARG, "component delays must be non-negative and finite");
-            if (comp_delay[j] + pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "a component's delay plus pre_delay beyond nfft - 1 would wrap");
-        }
-        for (int64_t j = 0; comp_gain && j < ncomp; ++j)
-            if (!std::isfinite(comp_gain[j])) throw Error(EMAGLS_ERR_ARG, "component gains must be finite");
+        const int64_t ncomp = air_check_lists(c, comp_ptr, comp_azi, comp_zen, comp_delay, comp_gain);
         air_check_scratch(c, ncomp);
         // ---- device
         Scratch s;
         const size_t n = (size_t)ncomp;
         const int64_t* d_ptr = s.put(comp_ptr, (size_t)nsrc + 1);
         air_run(s, c, comp_ptr, d_ptr, s.put_opt(comp_azi, n), s.put_opt(comp_zen, n), s.put_opt(comp_delay, n), s.put_opt(comp_gain, n));
+    });
+}
+
+extern "C" int emagls_array_irs_spectral(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                         const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr,
+                                         const double* comp_azi, const double* comp_zen, const double* comp_delay, const double* comp_gain,
+                                         int64_t nsurf, const double* surf_refl, const int32_t* comp_exp, const double* air_atten,
+                                         const double* comp_path, double pre_delay, int64_t nfft_in, int64_t nr, void* out) {
+    return guarded_call([&] {
+        // ---- arguments (nothing below this block fails on what the caller passed)
+        if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
+        if (nfft_in == 0) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the spectra have nfft / 2 + 1 bins");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        const int64_t ncomp = air_check_lists(c, comp_ptr, comp_azi, comp_zen, comp_delay, comp_gain);
+        if ((air_atten == nullptr) != (comp_path == nullptr)) throw Error(EMAGLS_ERR_ARG, "air_atten and comp_path must both be given or both be NULL");
+        air_check_spectra(nsurf, surf_refl, air_atten, c.P, "surf_refl");
+        if (nsurf > 0 && ncomp > 0 && !comp_exp) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_exp");
+        for (int64_t i = 0; i < ncomp * nsurf; ++i)
+            if (comp_exp[i] < 0) throw Error(EMAGLS_ERR_ARG, "component exponents must be non-negative");
+        for (int64_t j = 0; comp_path && j < ncomp; ++j)
+            if (!(comp_path[j] >= 0.0) || !std::isfinite(comp_path[j])) throw Error(EMAGLS_ERR_ARG, "component path lengths must be non-negative and finite");
+        air_check_scratch(c, ncomp, (int)nsurf, air_atten != nullptr);
+        // ---- device (nsurf = 0 and no air: the flat kernels, the bits of emagls_array_irs)
+        Scratch s;
+        const size_t n = (size_t)ncomp;
+        AirSpectral sp;
+        sp.nsurf = (int)nsurf; sp.refl = surf_refl; sp.att = air_atten;
+        sp.d_exp = nsurf > 0 ? s.put_opt(comp_exp, n * (size_t)nsurf) : nullptr;
+        sp.d_path = air_atten ? s.put_opt(comp_path, n) : nullptr;
+        const int64_t* d_ptr = s.put(comp_ptr, (size_t)nsrc + 1);
+        air_run(s, c, comp_ptr, d_ptr, s.put_opt(comp_azi, n), s.put_opt(comp_zen, n), s.put_opt(comp_delay, n), s.put_opt(comp_gain, n), sp);
     });
 }
 
@@ -341,6 +417,60 @@ extern "C" int emagls_shoebox_components(const double* room_dim, const double* w
     });
 }
 
+extern "C" int emagls_shoebox_images(const double* room_dim, const double* array_pos, int64_t nsrc, const double* src_pos, double fs,
+                                     double max_delay, int max_order, int64_t capacity, int64_t* comp_ptr, double* comp_azi, double* comp_zen,
+                                     double* comp_delay, double* comp_gain, int32_t* comp_exp, double* comp_path) {
+    return guarded_call([&] {
+        if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
+        if (capacity < 0) throw Error(EMAGLS_ERR_ARG, "invalid shape: capacity");
+        if (capacity > 0 && (!comp_azi || !comp_zen || !comp_delay || !comp_gain || !comp_exp || !comp_path))
+            throw Error(EMAGLS_ERR_ARG, "null pointer: component arrays (capacity 0 for a count-only call)");
+        const ShoeboxArgs a = shoebox_check(room_dim, SBX_ONES, array_pos, nsrc, src_pos, fs, 0.0, max_delay, max_order);
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        std::copy(box.h_ptr.begin(), box.h_ptr.end(), comp_ptr);
+        const size_t n = (size_t)box.total();
+        if (n > 0 && box.total() <= capacity) {
+            box.fill(true);
+            HIP_CHECK(hipMemcpyAsync(comp_azi, box.azi, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_zen, box.zen, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_delay, box.delay, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_gain, box.gain, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_exp, box.exp, sizeof(int) * 6 * n, hipMemcpyDeviceToHost, s.st));
+            HIP_CHECK(hipMemcpyAsync(comp_path, box.path, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            s.sync();
+        }
+        box.keep_time();
+    });
+}
+
+extern "C" int emagls_array_room_irs_spectral(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                              const void* enc, int enc_is_complex, int64_t nch, const double* room_dim,
+                                              const double* wall_refl_spec, const double* air_atten, const double* array_pos, int64_t nsrc,
+                                              const double* src_pos, double max_delay, int max_order, double pre_delay, int64_t nfft_in,
+                                              int64_t nr, int64_t* comp_count, void* out) {
+    return guarded_call([&] {
+        if (nfft_in == 0) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the spectra have nfft / 2 + 1 bins");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        if (!wall_refl_spec) throw Error(EMAGLS_ERR_ARG, "null pointer: wall_refl_spec");
+        const ShoeboxArgs a = shoebox_check(room_dim, SBX_ONES, array_pos, nsrc, src_pos, fs, mic_radius, max_delay, max_order);
+        air_check_spectra(6, wall_refl_spec, air_atten, c.P, "wall_refl_spec");
+        if (max_delay + pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "max_delay plus pre_delay beyond nfft - 1 would wrap");
+        air_check_scratch(c, 0, 6, air_atten != nullptr);
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        air_check_scratch(c, box.total(), 6, air_atten != nullptr);
+        box.fill(true);
+        AirSpectral sp;
+        sp.nsurf = 6; sp.refl = wall_refl_spec; sp.att = air_atten; sp.d_exp = box.exp; sp.d_path = air_atten ? box.path : nullptr;
+        air_run(s, c, box.h_ptr.data(), box.ptr, box.azi, box.zen, box.delay, box.gain, sp);
+        box.keep_time();
+        for (int64_t q = 0; comp_count && q < nsrc; ++q) comp_count[q] = box.h_ptr[q + 1] - box.h_ptr[q];
+    });
+}
+
 extern "C" int emagls_array_room_irs(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
                                      const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
                                      const double* array_pos, int64_t nsrc, const double* src_pos, double max_delay, int max_order,
@@ -364,7 +494,7 @@ extern "C" int emagls_array_room_irs(double fs, double mic_radius, int order, co
 extern "C" int emagls_shoebox_kernel_time(double* ms) {
     return guarded_call([&] {
         if (!ms) throw Error(EMAGLS_ERR_ARG, "null pointer: ms");
-        if (g_shoebox_ms < 0.0) throw Error(EMAGLS_ERR_ARG, "no emagls_shoebox_components or emagls_array_room_irs call has completed on this thread");
+        if (g_shoebox_ms < 0.0) throw Error(EMAGLS_ERR_ARG, "no emagls_shoebox_components, emagls_shoebox_images or emagls_array_room_irs call has completed on this thread");
         *ms = g_shoebox_ms;
     });
 }

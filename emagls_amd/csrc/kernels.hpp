@@ -391,8 +391,15 @@ struct AirMain {
     int n_long, n_short, N, M, P, nfft;
     int64_t Pld, ncomp;
     void* H;                               // [Q][M][Pld] complex
+    // the spectral gain: nsurf = 0 and att null is the flat kernel
+    int nsurf;                             // surfaces, <= 8
+    const double* lnr; const unsigned* neg; const double* att;   // launch_air_spectra's tables [nsurf][Pld], [Pld], [Pld] or null
+    const int* exp; const double* path;    // [ncomp][nsurf]; [ncomp] with att
 };
 void launch_air_main(const AirMain& m, hipStream_t st);
+// refl [W][P], att [P] or null (attp then unused) -> lnr [W][Pld], neg [Pld], attp [Pld]
+void launch_air_spectra(int W, int P, int64_t Pld, const double* refl, const double* att, double* lnr, unsigned* neg, double* attp,
+                        hipStream_t st);
 // out [Q][C][nr], real or (enc_im given) interleaved complex; enc_re null: C = M raw microphones.  nfft <= 4096
 void launch_air_irfft(const void* H, int64_t Pld, const double* enc_re, const double* enc_im, int C, int M, int64_t Q, int nfft,
                       const void* tw, int nr, void* out, hipStream_t st);
@@ -415,6 +422,9 @@ void launch_shoebox_count(const ShoeboxArgs& a, int64_t nsrc, const double* src,
 void launch_shoebox_scan(const ShoeboxArgs& a, int64_t nsrc, const int* cnt, int64_t* base, int64_t* comp_ptr, hipStream_t st);
 void launch_shoebox_write(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                           double* zen, double* delay, double* gain, hipStream_t st);
+// the same with the six exponents exp [n][6] (x0, x1, y0, y1, z0, z1) and the distance path [n] of every component (section 13)
+void launch_shoebox_write_images(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                                 double* zen, double* delay, double* gain, int* exp, double* path, hipStream_t st);
 
 // ---- host_pools.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool in host_internal.hpp)
 hipStream_t pool_stream_take();

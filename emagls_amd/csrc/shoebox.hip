@@ -1,5 +1,5 @@
-// Shoebox image sources (the host entries are in array_irs_api.hip): Allen & Berkley's image model with
-// frequency-independent walls, enumerated on the device into the component lists of section 11 (azi, zen, delay, gain per component,
+// Shoebox image sources (DESIGN.md sections 12 and 13; the host entries are in array_irs_api.hip): Allen & Berkley's image model,
+// with frequency-independent walls in the gain or -- the write pass's IMAGES form -- with the exponents and the path beside it, enumerated on the device into the component lists of section 11 (azi, zen, delay, gain per component,
 // CSR offsets per source), in an order that is part of the definition.
 //
 // A candidate of a source s is an integer triple n = (nx, ny, nz) and a parity triple p = (px, py, pz) in {0, 1}^3:
@@ -114,10 +114,13 @@ __global__ void __launch_bounds__(1024) shoebox_scan_kernel(int64_t ntiles, int6
     }
 }
 
-// grid nsrc * tiles; azi, zen, delay, gain [base[ntiles]]
+// grid nsrc * tiles; azi, zen, delay, gain [base[ntiles]]; IMAGES: also exp [base[ntiles]][6] and path [base[ntiles]] (the spectral
+// room of DESIGN.md section 13, whose a.beta are ones: the walls enter in the responses' main kernel)
+template <bool IMAGES>
 __global__ void __launch_bounds__(SBX_TILE) shoebox_write_kernel(ShoeboxArgs a, const double* __restrict__ src, const uint64_t* __restrict__ mask,
                                                                 const int64_t* __restrict__ base, double* __restrict__ azi,
-                                                                double* __restrict__ zen, double* __restrict__ delay, double* __restrict__ gain) {
+                                                                double* __restrict__ zen, double* __restrict__ delay, double* __restrict__ gain,
+                                                                int* __restrict__ exp, double* __restrict__ path) {
     const int64_t tile = blockIdx.x, q = tile / a.tiles, c = (tile % a.tiles) * SBX_TILE + threadIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t* __restrict__ mw = mask + tile * (SBX_TILE / 64);
@@ -131,6 +134,17 @@ __global__ void __launch_bounds__(SBX_TILE) shoebox_write_kernel(ShoeboxArgs a, 
     zen[r] = acos(o.vz / o.d);
     delay[r] = o.tau;
     gain[r] = o.gain;
+    if constexpr (IMAGES) {
+        int64_t t = c >> 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int n = (int)(i < 2 ? t % a.W[i] : t) - a.B[i], par = (int)(c >> i) & 1;
+            if (i < 2) t /= a.W[i];
+            exp[6 * r + 2 * i] = abs(n - par);
+            exp[6 * r + 2 * i + 1] = abs(n);
+        }
+        path[r] = o.d;
+    }
 }
 
 void launch_shoebox_count(const ShoeboxArgs& a, int64_t nsrc, const double* src, uint64_t* mask, int* cnt, hipStream_t st) {
@@ -145,7 +159,13 @@ void launch_shoebox_scan(const ShoeboxArgs& a, int64_t nsrc, const int* cnt, int
 
 void launch_shoebox_write(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                           double* zen, double* delay, double* gain, hipStream_t st) {
-    shoebox_write_kernel<<<(unsigned)(nsrc * a.tiles), SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain);
+    shoebox_write_kernel<false><<<(unsigned)(nsrc * a.tiles), SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, nullptr, nullptr);
+    KERNEL_CHECK();
+}
+
+void launch_shoebox_write_images(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                                 double* zen, double* delay, double* gain, int* exp, double* path, hipStream_t st) {
+    shoebox_write_kernel<true><<<(unsigned)(nsrc * a.tiles), SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, exp, path);
     KERNEL_CHECK();
 }
 

@@ -778,6 +778,27 @@ int emagls_array_irs(double fs, double mic_radius, int order, const double* mic_
  * (tools/array_irs_timing.py); EMAGLS_ERR_ARG before the first one. */
 int emagls_array_irs_kernel_time(double* ms);
 
+/* ---- array impulse responses with a spectral gain: surfaces and air (this project's) ----
+ * emagls_array_irs with a gain that depends on the bin.  With P = nfft / 2 + 1 and k = 0 .. P - 1 a call carries, next to the
+ * component lists, nsurf surfaces (0 <= nsurf <= 8) with real reflection spectra surf_refl [nsurf x P] (surface w at surf_refl + w P;
+ * every value finite, |R_w(k)| <= 1), per component nsurf integer exponents comp_exp [ncomp x nsurf] (those of component j contiguous
+ * at comp_exp + j nsurf; e_jw >= 0), and optionally an attenuation spectrum air_atten [P] (alpha(k) >= 0 in nepers per metre) with a
+ * path length per component comp_path [ncomp] (l_j >= 0 in metres): both given or both NULL.  The g_j of emagls_array_irs becomes
+ *   G_j(k) = g_j prod_{w < nsurf} R_w(k)^e_jw exp(-alpha(k) l_j).
+ * R^0 = 1, also for R = 0; G_j(k) is exactly 0 where some R_w(k) = 0 meets e_jw > 0, and exactly g_j where every e_jw = 0 and there is
+ * no air term.  G is real, so the rules for bin 0 and the last bin stand; R_w(0) and alpha(0) are used as given.  Everything else is
+ * emagls_array_irs: delays, pre_delay, encoder, transform, the fixed summation order, the per-source choice of the kernel's form, equal
+ * bits for equal calls and for source q alone.  nfft must be given (the length of the spectra depends on it): 0 is EMAGLS_ERR_ARG.
+ * With nsurf = 0 and no air term the call runs the kernels of emagls_array_irs and returns its bits.  The gain is formed inside the
+ * main kernel as one exponential of sum_w e_jw ln|R_w(k)| - alpha(k) l_j with the sign from the parities: it agrees with the direct
+ * powers to a few 1e-15 relative.  Every argument is checked before the device is touched; the 24 GiB estimate counts the tables and
+ * the per-component arrays.  emagls_array_irs_kernel_time covers the spectral launches. */
+int emagls_array_irs_spectral(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                              const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr, const double* comp_azi,
+                              const double* comp_zen, const double* comp_delay, const double* comp_gain, int64_t nsurf,
+                              const double* surf_refl, const int32_t* comp_exp, const double* air_atten, const double* comp_path,
+                              double pre_delay, int64_t nfft, int64_t nr, void* out);
+
 /* ---- array room responses: shoebox image sources (this project's) ----
  * The components of emagls_array_irs, enumerated on the device from a shoebox room: Allen & Berkley's image model with
  * frequency-independent walls.  room_dim [3] = (Lx, Ly, Lz) in metres, all > 0; one corner at the origin, the axes those of getSH
@@ -798,7 +819,7 @@ int emagls_array_irs_kernel_time(double* ms);
  * The search box is |n_i| <= floor(max_delay 343 / fs / (2 L_i)) + 1, and <= floor((max_order + 1) / 2) with an order limit; a call
  * with more than 2^28 candidates (8 prod_i (2 B_i + 1) per source, times nsrc) is EMAGLS_ERR_UNSUPPORTED.
  * Every argument is checked before the device is touched.  Plane-wave components are a far-field model: near-field (point-source)
- * terms, frequency-dependent walls, air absorption and source directivity are not built.
+ * terms and source directivity are not built.  Frequency-dependent walls and air absorption: the spectral entries below.
  *
  * emagls_shoebox_components: comp_ptr [nsrc + 1] (host) is always written; comp_azi, comp_zen, comp_delay, comp_gain [capacity] are
  * written only when comp_ptr[nsrc] <= capacity.  NULL arrays with capacity = 0: a count-only call. */
@@ -815,9 +836,27 @@ int emagls_array_room_irs(double fs, double mic_radius, int order, const double*
                           const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
                           const double* array_pos, int64_t nsrc, const double* src_pos, double max_delay, int max_order, double pre_delay,
                           int64_t nfft, int64_t nr, int64_t* comp_count, void* out);
+/* The spectral room: walls with reflection spectra, and air absorption.  The enumeration does not see the walls:
+ * a candidate is a component iff (max_order < 0 or its reflection order <= max_order) and tau <= max_delay -- there is no "gain != 0"
+ * rule.  emagls_shoebox_images returns per component azi, zen, delay as above, gain = 1 / d, the six exponents comp_exp [capacity x 6]
+ * (e0_x, e1_x, e0_y, e1_y, e0_z, e1_z contiguous per component: the walls x = 0, x = Lx, y = 0, y = Ly, z = 0, z = Lz) and comp_path = d
+ * in metres: the lists of emagls_array_irs_spectral with nsurf = 6.  Candidates, search box, cap, order of the list, the absence of
+ * atomics and the count-only convention are those of emagls_shoebox_components, and the first four columns are its bits with all six
+ * coefficients equal to 1. */
+int emagls_shoebox_images(const double* room_dim, const double* array_pos, int64_t nsrc, const double* src_pos, double fs, double max_delay,
+                          int max_order, int64_t capacity, int64_t* comp_ptr, double* comp_azi, double* comp_zen, double* comp_delay,
+                          double* comp_gain, int32_t* comp_exp, double* comp_path);
+/* emagls_array_irs_spectral of those images without their crossing the bus.  wall_refl_spec [6 x P]: the reflection spectra of the six
+ * walls in the order above (finite, in [-1, 1]), P = nfft / 2 + 1 with nfft given (0: EMAGLS_ERR_ARG).  air_atten [P] in Np/m, >= 0, or
+ * NULL for no air term; with it every component's path length is its d.  Everything else as emagls_array_room_irs.  Source q of a call
+ * gives the bits of emagls_array_irs_spectral on the lists emagls_shoebox_images returns for it. */
+int emagls_array_room_irs_spectral(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                   const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl_spec,
+                                   const double* air_atten, const double* array_pos, int64_t nsrc, const double* src_pos, double max_delay,
+                                   int max_order, double pre_delay, int64_t nfft, int64_t nr, int64_t* comp_count, void* out);
 /* Device-event time in ms of the enumeration passes (count, scan, write) of the calling thread's last completed
- * emagls_shoebox_components or emagls_array_room_irs call; EMAGLS_ERR_ARG before the first one.  A room call also sets the time of
- * emagls_array_irs_kernel_time. */
+ * emagls_shoebox_components, emagls_shoebox_images or emagls_array_room_irs(_spectral) call; EMAGLS_ERR_ARG before the first one.  A
+ * room call also sets the time of emagls_array_irs_kernel_time. */
 int emagls_shoebox_kernel_time(double* ms);
 
 /* ---- plan API: inputs resident in HBM, repeated execution (benchmarks, batches) ------------- */

@@ -42,6 +42,30 @@ mxArray* out_matrix(mwSize rows, mwSize cols, int basis) {
 }
 void* out_ptr(mxArray* a) { return mxIsComplex(a) ? (void*)mxGetComplexDoubles(a) : (void*)mxGetDoubles(a); }
 const void* in_ptr(const mxArray* a) { return mxIsComplex(a) ? (const void*)mxGetComplexDoubles(a) : (const void*)mxGetDoubles(a); }
+// the spectral array responses: nfft as given, or the smallest power of two >= 2 irLen (the library wants it
+// stated: the spectra's length follows from it); a MATLAB matrix [rows x cols] as rows one after the other; exponents as int32
+int64_t spectral_nfft(const mxArray* a, mwSize nr) {
+    if (a) return (int64_t)mxGetScalar(a);
+    int64_t n = 8;
+    while (n < 2 * (int64_t)nr && n < 65536) n *= 2;
+    return n;
+}
+std::vector<double> rows_of(const double* m, mwSize rows, mwSize cols) {
+    std::vector<double> v((size_t)rows * cols);
+    for (mwSize r = 0; r < rows; ++r)
+        for (mwSize k = 0; k < cols; ++k) v[(size_t)r * cols + k] = m[r + rows * k];
+    return v;
+}
+std::vector<int32_t> exponents_of(const double* m, mwSize J, mwSize W) {
+    std::vector<int32_t> v((size_t)J * W);
+    for (mwSize j = 0; j < J; ++j)
+        for (mwSize w = 0; w < W; ++w) {
+            const double e = m[j + J * w];
+            if (e != std::floor(e) || std::fabs(e) > 2147483647.0) mexErrMsgIdAndTxt("eMagLS:arg", "exponents must hold integers");
+            v[(size_t)j * W + w] = (int32_t)e;
+        }
+    return v;
+}
 // a caller-evaluated SH matrix must be real / complex like the basis asked for
 const void* basis_matrix(const mxArray* a, int basis, mwSize rows, mwSize cols, const char* what) {
     if (!mxIsDouble(a) || mxGetM(a) != rows || mxGetN(a) != cols) mexErrMsgIdAndTxt("eMagLS:arg", "%s must be a %d x %d double matrix", what, (int)rows, (int)cols);
@@ -211,7 +235,7 @@ void at_exit() {
 // emagls_mex('ch', N, aziRad, basisType)        emagls_mex('smair', order, fs, irLen, oversamplingFactor, smaRadius, micAzi, micZen, ...)
 // emagls_mex('shf', micRadius, order, fs, len)                  [wShf, W_Shf] = ...
 // emagls_mex('adf', micRadius, micAzi, micZen, order, fs, len, shDefinition[, Yhi])
-// array responses: 'array_irs', 'shoebox_components', 'array_room_irs' (their argument lists stand at their branches)
+// array responses: 'array_irs', 'shoebox_components', 'shoebox_images', 'array_room_irs' (their argument lists stand at their branches)
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     static bool registered = false;
     if (!registered) { mexAtExit(at_exit); registered = true; }
@@ -820,10 +844,70 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         }
         const mwSize od[3] = {nr, Cc, Q};
         plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
+        // the spectral gain, four further arguments, [] or absent for none: surfaceReflection [W x P], exponents
+        // [J x W], airAttenuation [P], pathLength [J]; P = nfft / 2 + 1
+        auto extra = [&](int i) { return nrhs > i && given(i); };
+        if (extra(11) || extra(12) || extra(13) || extra(14)) {
+            if (extra(11) != extra(12)) mexErrMsgIdAndTxt("eMagLS:arg", "surfaceReflection and exponents must both be given or both be []");
+            if (extra(13) != extra(14)) mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation and pathLength must both be given or both be []");
+            const int64_t nfft = spectral_nfft(given(10) ? prhs[10] : nullptr, nr);
+            const mwSize P = (mwSize)(nfft / 2 + 1), W = extra(11) ? mxGetM(prhs[11]) : 0;
+            std::vector<double> refl;
+            std::vector<int32_t> ex;
+            if (W) {
+                if (mxGetN(prhs[11]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "surfaceReflection must be [numSurfaces x %d] (nfft / 2 + 1 bins)", (int)P);
+                if (mxGetM(prhs[12]) != J || mxGetN(prhs[12]) != W) mexErrMsgIdAndTxt("eMagLS:arg", "exponents must be [J x numSurfaces]");
+                refl = rows_of(dbl(prhs[11], "surfaceReflection"), W, P);
+                ex = exponents_of(dbl(prhs[12], "exponents"), J, W);
+            }
+            if (extra(13) && (mxGetNumberOfElements(prhs[13]) != P || mxGetNumberOfElements(prhs[14]) != (J ? J : mxGetNumberOfElements(prhs[14]))))
+                mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation must have %d elements (nfft / 2 + 1 bins) and pathLength one per component", (int)P);
+            const int rc = emagls_array_irs_spectral(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
+                                                     given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
+                                                     comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
+                                                     (int64_t)W, W ? refl.data() : nullptr, ex.empty() ? nullptr : ex.data(),
+                                                     extra(13) ? dbl(prhs[13], "airAttenuation") : nullptr, extra(13) ? dbl(prhs[14], "pathLength") : nullptr,
+                                                     mxGetScalar(prhs[5]), nfft, (int64_t)nr, out_ptr(plhs[0]));
+            if (rc) fail(rc);
+            return;
+        }
         const int rc = emagls_array_irs(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
                                         given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
                                         comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
                                         mxGetScalar(prhs[5]), given(10) ? (int64_t)mxGetScalar(prhs[10]) : 0, (int64_t)nr, out_ptr(plhs[0]));
+        if (rc) fail(rc);
+        return;
+    }
+    if (c == "shoebox_images") {   // (roomDim [3], sourcePos [numSources x 3], arrayPos [3], fs, maxDelay, maxOrder)
+        // [compPtr, comps, exponents, paths] = ...: the lists of 'shoebox_components' without the walls: comps [J x 4]
+        // with gain = 1 / distance, exponents [J x 6] of the walls x=0, x=Lx, y=0, y=Ly, z=0, z=Lz, paths [J x 1] in metres
+        if (nrhs < 7) mexErrMsgIdAndTxt("eMagLS:arg", "shoebox_images needs 6 arguments ([] for no limit on the reflection order)");
+        if (mxGetNumberOfElements(prhs[1]) != 3 || mxGetNumberOfElements(prhs[3]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "roomDim and arrayPos must have 3 elements");
+        const mwSize Q = mxGetM(prhs[2]);
+        if (Q < 1 || mxGetN(prhs[2]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "sourcePos must be [numSources x 3] (x, y, z per row)");
+        const double *dim = dbl(prhs[1], "roomDim"), *sp = dbl(prhs[2], "sourcePos"), *pos = dbl(prhs[3], "arrayPos");
+        std::vector<double> src(3 * Q);
+        for (mwSize q = 0; q < Q; ++q)
+            for (int i = 0; i < 3; ++i) src[3 * q + i] = sp[q + Q * i];
+        const double fs = mxGetScalar(prhs[4]), max_delay = mxGetScalar(prhs[5]);
+        const int max_order = prhs[6] && !mxIsEmpty(prhs[6]) ? (int)mxGetScalar(prhs[6]) : -1;
+        std::vector<int64_t> ptr(Q + 1);
+        int rc = emagls_shoebox_images(dim, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, 0, ptr.data(), nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr);
+        if (rc) fail(rc);
+        const mwSize J = (mwSize)ptr[Q];
+        plhs[0] = mxCreateDoubleMatrix(Q + 1, 1, mxREAL);
+        mxArray *comps = mxCreateDoubleMatrix(J, 4, mxREAL), *exps = mxCreateDoubleMatrix(J, 6, mxREAL), *paths = mxCreateDoubleMatrix(J, 1, mxREAL);
+        double* o = mxGetDoubles(comps);
+        std::vector<int32_t> e(6 * (size_t)J);
+        if (J) rc = emagls_shoebox_images(dim, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, (int64_t)J, ptr.data(), o, o + J, o + 2 * J,
+                                          o + 3 * J, e.data(), mxGetDoubles(paths));
+        for (mwSize j = 0; j < J; ++j)
+            for (int w = 0; w < 6; ++w) mxGetDoubles(exps)[j + J * w] = (double)e[6 * j + w];
+        for (mwSize q = 0; q <= Q; ++q) mxGetDoubles(plhs[0])[q] = (double)ptr[q];
+        mxArray* outs[3] = {comps, exps, paths};
+        for (int i = 0; i < 3; ++i)
+            if (nlhs > i + 1) plhs[i + 1] = outs[i]; else mxDestroyArray(outs[i]);
         if (rc) fail(rc);
         return;
     }
@@ -834,13 +918,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         //   array_room_irs:     ... irLen, preDelay, micRadius, micGridAziZenRad, order, encoder, nfft, maxOrder, maxDelay)
         //                                                                     [irs, counts] = ...: [irLen x numChannels x numSources], [numSources]
         // maxOrder []: no limit; maxDelay [] (array_room_irs): irLen - 1 - preDelay
+        // array_room_irs, the spectral room: wallReflection [6 x P], P = nfft / 2 + 1, and / or a fifteenth argument
+        // airAttenuation [P] ([] or absent: none; six coefficients with it are repeated over the bins)
         const bool irs = c == "array_room_irs";
         if (nrhs < (irs ? 15 : 8))
             mexErrMsgIdAndTxt("eMagLS:arg", irs ? "array_room_irs needs 14 arguments ([] for no encoder and for the defaults of nfft, maxOrder and maxDelay)"
                                                 : "shoebox_components needs 7 arguments ([] for no limit on the reflection order)");
         auto given = [&](int i) { return prhs[i] && !mxIsEmpty(prhs[i]); };
         if (mxGetNumberOfElements(prhs[1]) != 3 || mxGetNumberOfElements(prhs[4]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "roomDim and arrayPos must have 3 elements");
-        if (mxGetNumberOfElements(prhs[2]) != 6) mexErrMsgIdAndTxt("eMagLS:arg", "wallReflection must have 6 elements (x=0, x=Lx, y=0, y=Ly, z=0, z=Lz)");
+        const bool air = irs && nrhs > 15 && given(15);
+        const bool spectral = irs && (air || (mxGetNumberOfElements(prhs[2]) > 6 && mxGetM(prhs[2]) == 6));
+        if (!spectral && mxGetNumberOfElements(prhs[2]) != 6)
+            mexErrMsgIdAndTxt("eMagLS:arg", "wallReflection must have 6 elements (x=0, x=Lx, y=0, y=Ly, z=0, z=Lz)");
         const mwSize Q = mxGetM(prhs[3]);
         if (Q < 1 || mxGetN(prhs[3]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "sourcePos must be [numSources x 3] (x, y, z per row)");
         const double *dim = dbl(prhs[1], "roomDim"), *refl = dbl(prhs[2], "wallReflection"), *sp = dbl(prhs[3], "sourcePos"), *pos = dbl(prhs[4], "arrayPos");
@@ -881,11 +970,29 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize od[3] = {nr, Cc, Q};
         plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
         std::vector<int64_t> counts(Q);
+        if (spectral) {
+            const int64_t nfft = spectral_nfft(given(12) ? prhs[12] : nullptr, nr);
+            const mwSize P = (mwSize)(nfft / 2 + 1);
+            std::vector<double> walls(6 * (size_t)P);
+            if (mxGetNumberOfElements(prhs[2]) == 6) {
+                for (size_t i = 0; i < walls.size(); ++i) walls[i] = refl[i / P];
+            } else {
+                if (mxGetM(prhs[2]) != 6 || mxGetN(prhs[2]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "wallReflection must be [6 x %d] (nfft / 2 + 1 bins)", (int)P);
+                walls = rows_of(refl, 6, P);
+            }
+            if (air && mxGetNumberOfElements(prhs[15]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation must have %d elements (nfft / 2 + 1 bins)", (int)P);
+            const int rc = emagls_array_room_irs_spectral(fs, mxGetScalar(prhs[8]), (int)mxGetScalar(prhs[10]), mics, mics + M, (int64_t)M,
+                                                          given(11) ? in_ptr(prhs[11]) : nullptr, ec ? 1 : 0, (int64_t)Cc, dim, walls.data(),
+                                                          air ? dbl(prhs[15], "airAttenuation") : nullptr, pos, (int64_t)Q, src.data(), max_delay,
+                                                          max_order, pre, nfft, (int64_t)nr, counts.data(), out_ptr(plhs[0]));
+            if (rc) fail(rc);
+        } else {
         const int rc = emagls_array_room_irs(fs, mxGetScalar(prhs[8]), (int)mxGetScalar(prhs[10]), mics, mics + M, (int64_t)M,
                                              given(11) ? in_ptr(prhs[11]) : nullptr, ec ? 1 : 0, (int64_t)Cc, dim, refl, pos, (int64_t)Q, src.data(),
                                              max_delay, max_order, pre, given(12) ? (int64_t)mxGetScalar(prhs[12]) : 0, (int64_t)nr, counts.data(),
                                              out_ptr(plhs[0]));
         if (rc) fail(rc);
+        }
         if (nlhs > 1) {
             plhs[1] = mxCreateDoubleMatrix(Q, 1, mxREAL);
             for (mwSize q = 0; q < Q; ++q) mxGetDoubles(plhs[1])[q] = (double)counts[q];

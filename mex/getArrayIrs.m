@@ -11,8 +11,12 @@ function irs = getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZe
 %   further names: order (4; only enters the simulation order max(order, ceil(fs*pi*micRadius/343))), encoder ([]: raw microphones;
 %             [numChannels x numMics], real or complex, e.g. pinv(getSH(order, micGridAziZenRad, shDefinition))), nfft ([]: the
 %             smallest power of two >= 2*irLen)
+%   the spectral gain (DESIGN.md section 13; emagls_array_irs_spectral), all [] by default: surfaceReflection [W x P], W <= 8 real
+%             reflection spectra in [-1, 1] over the P = nfft/2 + 1 bins, with exponents, a cell like sources of integer arrays
+%             [J_q x W]; airAttenuation [P] in Np/m with pathLength, a cell of [J_q x 1] arrays in metres (both or neither).  The gain
+%             of a component becomes gain * prod_w R_w(k)^e_w * exp(-alpha(k) * l) in bin k
 %   irs       [irLen x numChannels x Q] (complex with a complex encoder): irs(:, :, q) is the rir of sourceFieldStream
-p = struct('order', 4, 'encoder', [], 'nfft', []);
+p = struct('order', 4, 'encoder', [], 'nfft', [], 'surfaceReflection', [], 'exponents', [], 'airAttenuation', [], 'pathLength', []);
 for i = 1:2:numel(varargin)
     if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
     p.(varargin{i}) = varargin{i + 1};
@@ -34,6 +38,16 @@ for q = 1:Q
     comps = [comps; s]; %#ok<AGROW>
     compPtr(q + 1) = compPtr(q) + J;
 end
+exps = [];
+paths = [];
+if ~isempty(p.surfaceReflection) || ~isempty(p.airAttenuation)
+    if ~isempty(p.surfaceReflection); exps = zeros(0, size(p.surfaceReflection, 1)); end
+    for q = 1:Q
+        if ~isempty(p.surfaceReflection); exps = [exps; reshape(double(p.exponents{q}), [], size(exps, 2))]; end %#ok<AGROW>
+        if ~isempty(p.airAttenuation); paths = [paths; reshape(double(p.pathLength{q}), [], 1)]; end %#ok<AGROW>
+    end
+    if ~isempty(p.airAttenuation) && isempty(paths); paths = 0; end
+end
 irs = emagls_mex('array_irs', compPtr, comps, double(fs), double(irLen), double(preDelay), double(micRadius), double(micGridAziZenRad), ...
-    double(p.order), double(p.encoder), double(p.nfft));
+    double(p.order), double(p.encoder), double(p.nfft), double(p.surfaceReflection), exps, double(p.airAttenuation(:)), paths);
 end
