@@ -1412,7 +1412,7 @@ def _per_component(what, arrs, ptr, width, dtype):
 
 
 def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4, encoder=None, nfft=None, surfaceReflection=None,
-                exponents=None, airAttenuation=None, pathLength=None):
+                exponents=None, airAttenuation=None, pathLength=None, distance=None):
     """Impulse responses of the simulated rigid-sphere array (the array of getSMAIRMatrix) to sources that are sums of plane-wave
     components (include/emagls.h, emagls_array_irs).  `sources` is a [Q x 2] array of directions (azi, zen),
     one unit plane wave each -- a direction bank for a moving virtual source -- or a list of Q arrays [J_q x 2|3|4] with the columns
@@ -1425,12 +1425,29 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
     The spectral gain (emagls_array_irs_spectral): surfaceReflection [W x P], W <= 8 real reflection spectra in
     [-1, 1] over the P = nfft / 2 + 1 bins, with `exponents`, a list shaped like `sources` of integer arrays [J_q x W]; and
     airAttenuation [P] in Np/m with pathLength, a list of [J_q] arrays in metres (both or neither).  A component's gain becomes
-    gain prod_w R_w(k)^e_w exp(-alpha(k) l) in bin k.  With none of the four given, this is the call without them."""
+    gain prod_w R_w(k)^e_w exp(-alpha(k) l) in bin k.  With none of the four given, this is the call without them.
+    Point sources (emagls_array_irs_point): `distance`, a list shaped like `sources` of [J_q] arrays in metres
+    ([Q] for the [Q x 2] form), every value finite and greater than micRadius, for all components or (None) for none.  The order-n
+    term of a component then carries the near-field factor F_n(kappa rho); delay and gain stay the caller's (rho / 343 fs and
+    1 / rho make it the point source's spherical wave).  The simulation order is the plane-wave rule: raise `order` for a source
+    close to the sphere."""
     ptr, azi, zen, delay, gain = _components(sources)
     maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
     Q = ptr.size - 1
     out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
-    if any(a is not None for a in (surfaceReflection, exponents, airAttenuation, pathLength)):
+    dist = None
+    if distance is not None:
+        if isinstance(distance, (list, tuple)) and len(distance) == Q and all(a is None or np.ndim(a) >= 1 for a in distance):
+            if any(a is None or np.size(a) != ptr[q + 1] - ptr[q] for q, a in enumerate(distance)):
+                raise L.EmaglsError(L.ERR_ARG, "distances are given for all components of a call or for none")
+            dist = _per_component("distance", distance, ptr, 1, np.float64)
+        else:                                          # [Q]: one component per source
+            dist = np.ascontiguousarray(np.asarray(distance, dtype=np.float64)).reshape(-1, 1)
+            if dist.shape[0] != int(ptr[-1]) or not np.array_equal(np.diff(ptr), np.ones(Q, dtype=np.int64)):
+                raise ValueError("distance must be a list with one array [J_q] per source (or [Q] values for sources of one component)")
+        if dist.size == 0:
+            dist = np.full((1, 1), np.inf)             # (no component: the pointer alone says "point sources")
+    if any(a is not None for a in (surfaceReflection, exponents, airAttenuation, pathLength, distance)):
         if (surfaceReflection is None) != (exponents is None):
             raise ValueError("surfaceReflection and exponents must both be given or both be absent")
         if (airAttenuation is None) != (pathLength is None):
@@ -1449,10 +1466,12 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
             path = _per_component("pathLength", pathLength, ptr, 1, np.float64)
             if path.size == 0:
                 path = np.zeros((1, 1))        # (the pair rule is on the pointers)
-        L.check(L.load().emagls_array_irs_spectral(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q,
-                                                   _addr(ptr), _addr(azi), _addr(zen), _addr(delay), _addr(gain), W, _addr(refl),
-                                                   _addr(ex) if ex is not None and ex.size else None, _addr(att), _addr(path), float(preDelay),
-                                                   n_fft, nr, _addr(out)))
+        head = (float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q, _addr(ptr), _addr(azi),
+                _addr(zen), _addr(delay), _addr(gain), W, _addr(refl), _addr(ex) if ex is not None and ex.size else None, _addr(att), _addr(path))
+        if dist is not None:
+            L.check(L.load().emagls_array_irs_point(*head, _addr(dist), float(preDelay), n_fft, nr, _addr(out)))
+        else:
+            L.check(L.load().emagls_array_irs_spectral(*head, float(preDelay), n_fft, nr, _addr(out)))
         return np.ascontiguousarray(out.transpose(0, 2, 1))
     L.check(L.load().emagls_array_irs(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q, _addr(ptr),
                                       _addr(azi), _addr(zen), _addr(delay), _addr(gain), float(preDelay), int(nfft) if nfft else 0, nr, _addr(out)))
@@ -1495,13 +1514,14 @@ def _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder):
     return dim, refl, pos, src, -1 if maxOrder is None else int(maxOrder)
 
 
-def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None):
+def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None, returnDistance=False):
     """The image sources of a shoebox room as plane-wave components at the array's centre (include/emagls.h,
     emagls_shoebox_components), enumerated on the device.  roomDim (Lx, Ly, Lz) in metres, one corner at the origin, axes as getSH's
     (x front, y left, z up); wallReflection: six amplitude reflection coefficients in [-1, 1] for the walls x=0, x=Lx, y=0, y=Ly,
     z=0, z=Lz; sourcePos [Q x 3] (or one position) and arrayPos inside the room; maxDelay in samples; maxOrder: the largest
     reflection order kept (None: no limit).  Returns a list of Q arrays [J_q x 4] with the columns azi, zen, delay in samples and
-    gain (1 / distance times the walls' coefficients), in the definition's order: the `sources` of getArrayIrs."""
+    gain (1 / distance times the walls' coefficients), in the definition's order: the `sources` of getArrayIrs.  With returnDistance
+    also a list of Q arrays [J_q], the components' distances in metres: the `distance` of getArrayIrs."""
     dim, refl, pos, src, mo = _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder)
     Q = src.shape[0]
     ptr = np.zeros(Q + 1, dtype=np.int64)
@@ -1510,6 +1530,13 @@ def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDe
     L.check(lib.emagls_shoebox_components(*head, 0, _addr(ptr), None, None, None, None))          # the counts
     n = int(ptr[-1])
     cols = np.zeros((4, max(n, 1)))
+    if returnDistance:
+        dist = np.zeros(max(n, 1))
+        if n:
+            L.check(lib.emagls_shoebox_components_dist(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3]),
+                                                       _addr(dist)))
+        return ([np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)],
+                [np.ascontiguousarray(dist[ptr[q]:ptr[q + 1]]) for q in range(Q)])
     if n:
         L.check(lib.emagls_shoebox_components(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3])))
     return [np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)]
@@ -1572,7 +1599,7 @@ def airAttenuation(fs, nfft, temperatureC=20.0, relHumidityPercent=50.0, pressur
 
 
 def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4,
-                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False, airAttenuation=None):
+                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False, airAttenuation=None, waveModel="planeWave"):
     """Impulse responses of the simulated rigid-sphere array in a shoebox room (include/emagls.h,
     emagls_array_room_irs): getArrayIrs(getShoeboxComponents(...), ...) bit for bit, with the components enumerated on the device
     and fed to the responses' kernels there.  The room as in getShoeboxComponents (the array's whole sphere inside it), the array
@@ -1581,7 +1608,12 @@ def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, pre
     The spectral room (emagls_array_room_irs_spectral): wallReflection [6 x P], one reflection spectrum per wall
     over the P = nfft / 2 + 1 bins (wallReflectionSpectra makes them from absorption coefficients), and / or airAttenuation [P] in
     Np/m (the function airAttenuation of this module), each component's path its distance; six coefficients with an airAttenuation are
-    repeated over the bins.  Then every image within maxOrder and maxDelay is a component (getShoeboxImages), also behind a wall of 0."""
+    repeated over the bins.  Then every image within maxOrder and maxDelay is a component (getShoeboxImages), also behind a wall of 0.
+    waveModel (getSMAIRMatrix's parameter and default): 'planeWave', every image a plane wave at the array (a far-field model), or
+    'pointSource' (emagls_array_room_irs_point), every image a point source at its distance: getArrayIrs with
+    distance= on the lists of getShoeboxComponents(returnDistance=True) or getShoeboxImages (its paths), bit for bit."""
+    if waveModel not in ("planeWave", "pointSource"):
+        raise L.EmaglsError(L.ERR_ARG, "unknown waveModel %r: 'planeWave' or 'pointSource'" % (waveModel,))
     spectral = np.ndim(wallReflection) == 2 or airAttenuation is not None
     dim, refl, pos, src, mo = _room(roomDim, np.ones(6) if spectral else wallReflection, sourcePos, arrayPos, maxOrder)
     maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
@@ -1590,6 +1622,17 @@ def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, pre
         maxDelay = nr - 1 - float(preDelay)
     out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
     counts = np.zeros(Q, dtype=np.int64)
+    if waveModel == "pointSource":
+        n_fft = _nfft_for(nr, nfft)
+        P = n_fft // 2 + 1
+        w = np.asarray(wallReflection, dtype=np.float64)
+        w = _spectra("wallReflection", w, 6, P) if w.ndim == 2 else _vec(w, 6, "wallReflection")[0]     # (six coefficients: the C entry repeats them)
+        att = None if airAttenuation is None else _spectra("airAttenuation", airAttenuation, None, P)
+        L.check(L.load().emagls_array_room_irs_point(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc,
+                                                     _addr(dim), _addr(w), 1 if w.ndim == 2 else 0, _addr(att), _addr(pos), Q, _addr(src),
+                                                     float(maxDelay), mo, float(preDelay), n_fft, nr, _addr(counts), _addr(out)))
+        out = np.ascontiguousarray(out.transpose(0, 2, 1))
+        return (out, counts) if returnCounts else out
     if spectral:
         n_fft = _nfft_for(nr, nfft)
         P = n_fft // 2 + 1

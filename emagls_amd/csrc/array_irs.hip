@@ -288,6 +288,191 @@ __global__ void __launch_bounds__(256) air_lane_source_kernel(AirArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// POINT SOURCES: component j at the finite distance rho_j.  The order-n term gains the factor
+//   F_n(x) = (-i)^(n+1) x e^(ix) h_n^(2)(x),  x = kappa_k rho_j,
+// which turns "plane wave times e^(-i kappa rho) / rho" into the spherical wave about the array's centre.  F_n grows like
+// (2n-1)!! / x^n below x = n and b'_n shrinks like (kappa r)^n / (2n+1)!!, so the kernel multiplies three tame numbers instead:
+//   b'_n F_n P_n = bh_n(k) G_n(kappa_k rho_j) [(r / rho_j)^n P_n],    G_n(x) = F_n(x) (ix)^n / (2n-1)!!,  bh_n = b'_n (2n-1)!! / (i kappa r)^n,
+//   G_0 = 1, G_1 = 1 + ix, G_(n+1) = G_n - x^2 / (4n^2 - 1) G_(n-1)    (the forward Hankel recurrence, real coefficient, exact at x = 0),
+//   bh_0 = -e^(ix) / (1 + ix), bh_n = (2n+1) e^(ix) / (x^2 G_(n-1)(x) / (2n-1) - (n+1) G_n(x)),  x = kappa r    (no b_n, no y_n),
+// and (r / rho)^n rides on the Legendre recurrence.  Bin 0 is x = 0: G = 1, bh_n = -(2n+1)/(n+1), the limit of the definition.
+// A kernel of its own in both forms, the spectral gain a compile-time option; the plane-wave kernels above are not touched.
+// ---------------------------------------------------------------------------------------------
+#ifndef AIR_POINT_BINS
+#define AIR_POINT_BINS 4      // bins per wave (divides AIR_R, the padding of Pld)
+#endif
+#ifndef AIR_POINT_MICS
+#define AIR_POINT_MICS 4      // microphones per wave: they share G_n, bh_n G_n, the gain and the phases (measured against 1 and 2, and
+                              // 4 bins against 2 and 8, in profiles/r28_point_sources.md)
+#endif
+constexpr int APT_R = AIR_POINT_BINS, APT_M = AIR_POINT_MICS;
+static_assert(AIR_R % APT_R == 0, "the bins of a wave must divide the padding of Pld");
+
+// one thread per bin of Pld: bh [N+1][Pld], ginv [N+1]
+__global__ void __launch_bounds__(256) air_point_modes_kernel(int N, int P, int64_t Pld, double kr_step, cplx* __restrict__ bh,
+                                                             double* __restrict__ ginv) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k <= N) ginv[k] = 1.0 / (4.0 * (double)k * (double)k - 1.0);
+    if (k >= Pld) return;
+    if (k >= P) {
+        for (int n = 0; n <= N; ++n) bh[(int64_t)n * Pld + k] = mk(0.0, 0.0);
+        return;
+    }
+    const double x = (double)k * kr_step, x2 = x * x;
+    const bool last = k == P - 1;
+    cplx e;
+    sincos(x, &e.y, &e.x);
+    cplx g0 = mk(1.0, 0.0), g1 = mk(1.0, x);
+    cplx b = cdiv(-e, g1);
+    if (last) b.y = 0.0;
+    bh[k] = b;
+    for (int n = 1; n <= N; ++n) {
+        const double c = x2 / (double)(2 * n - 1), m = (double)(n + 1);
+        const cplx den = mk(fma(c, g0.x, -(m * g1.x)), fma(c, g0.y, -(m * g1.y)));
+        b = cdiv((double)(2 * n + 1) * e, den);
+        if (last) { if (n & 1) b.x = 0.0; else b.y = 0.0; }   // (-i)^n Re(i^n bh_n): Re b'_n in the scaled form
+        bh[(int64_t)n * Pld + k] = b;
+        const double s = x2 / (4.0 * (double)n * (double)n - 1.0);
+        const cplx g2 = mk(fma(-s, g0.x, g1.x), fma(-s, g0.y, g1.y));
+        g0 = g1; g1 = g2;
+    }
+}
+
+struct AirArgsPoint : AirArgsSpectral {
+    const cplx* bh;        // [N+1][Pld]
+    const double* ginv;    // [N+1]
+    const double* dist;    // [ncomp]
+    double r, kappa_step;
+};
+
+// air_gains for the APT_R bins of a point-source wave: the same operations in the same order per bin
+__device__ __forceinline__ void air_point_gains(const AirArgsPoint& a, int k0, int64_t j, double g, double (&G)[APT_R]) {
+    const double len = a.att ? a.path[j] : 0.0;
+    const int* __restrict__ e = a.exp + j * a.W;
+    const double* __restrict__ l = a.lnr + k0;
+    double arg[APT_R];
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) arg[r] = a.att ? -(a.att[k0 + r] * len) : 0.0;
+    unsigned odd = 0;
+    for (int t = 0; t < a.W; ++t, l += a.Pld) {
+        const int et = e[t];
+        const double ed = (double)et;
+        odd |= (unsigned)(et & 1) << t;
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) arg[r] = fma(ed, l[r], arg[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) G[r] = ((__popc(a.neg[k0 + r] & odd) & 1) ? -g : g) * exp(arg[r]);
+}
+
+// one component's terms of the APT_R bins from k0 at the APT_M microphones of the wave:
+// sum[i][r] += G_r w_r sum_n (bh_n(k0 + r) G_n(kappa_(k0 + r) rho)) (t^n P_n(x_i)),  t = r / rho
+template <bool SPECTRAL>
+__device__ __forceinline__ void air_point_component(const AirArgsPoint& a, int k0, int64_t j, const double (&vx)[APT_M], const double (&vy)[APT_M],
+                                                    const double (&vz)[APT_M], cplx (&sum)[APT_M][APT_R]) {
+    const double ux = a.u[j], uy = a.u[a.ncomp + j], uz = a.u[2 * a.ncomp + j];
+    const double rho = a.dist[j], t = a.r / rho, t2 = t * t;
+    double xm[APT_M], p0[APT_M], p1[APT_M];
+#pragma unroll
+    for (int i = 0; i < APT_M; ++i) {
+        xm[i] = t * fma(uz, vz[i], fma(uy, vy[i], ux * vx[i]));   // t x: t^(n+1) P_(n+1) = rec[2n] (t x) (t^n P_n) - rec[2n+1] t^2 (t^(n-1) P_(n-1))
+        p0[i] = 1.0; p1[i] = xm[i];
+    }
+    const cplx* __restrict__ b = a.bh + k0;
+    double x2[APT_R];
+    cplx g0[APT_R], g1[APT_R], acc[APT_M][APT_R];
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) {
+        const double x = ((double)(k0 + r) * a.kappa_step) * rho;
+        x2[r] = x * x;
+        g0[r] = mk(1.0, 0.0); g1[r] = mk(1.0, x);
+#pragma unroll
+        for (int i = 0; i < APT_M; ++i) acc[i][r] = b[r];   // n = 0: G_0 = 1, P_0 = 1
+    }
+    for (int n = 1; n <= a.N; ++n) {
+        b += a.Pld;
+        const double s = a.ginv[n];
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) {
+            const cplx c = b[r] * g1[r];
+#pragma unroll
+            for (int i = 0; i < APT_M; ++i) cfma(acc[i][r], c, p1[i]);
+            const double f = x2[r] * s;
+            const cplx g2 = mk(fma(-f, g0[r].x, g1[r].x), fma(-f, g0[r].y, g1[r].y));
+            g0[r] = g1[r]; g1[r] = g2;
+        }
+        const double ra = a.rec[2 * n], rb = a.rec[2 * n + 1] * t2;
+#pragma unroll
+        for (int i = 0; i < APT_M; ++i) {
+            const double p2 = fma(ra * xm[i], p1[i], -(rb * p0[i]));
+            p0[i] = p1[i]; p1[i] = p2;
+        }
+    }
+    const unsigned di = (unsigned)a.dint[j];
+    const double df = a.dfrac[j], inv = 1.0 / (double)a.nfft, g = a.gain ? a.gain[j] : 1.0;
+    const unsigned ki = ((unsigned)k0 * di) & (unsigned)(a.nfft - 1);
+    cplx w, s;
+    sincospi(-2.0 * (((double)ki + (double)k0 * df) * inv), &w.y, &w.x);
+    sincospi(-2.0 * (((double)di + df) * inv), &s.y, &s.x);
+    double G[APT_R];
+    if (SPECTRAL) {
+        air_point_gains(a, k0, j, g, G);
+    } else {
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) G[r] = g;
+    }
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) {
+        const cplx gw = G[r] * w;
+#pragma unroll
+        for (int i = 0; i < APT_M; ++i) cfma(sum[i][r], gw, acc[i][r]);
+        w = w * s;
+    }
+}
+
+// both forms: grid (Pld / APT_R, ceil(M / (4 APT_M)), sources of the list or ceil(nlist / 64)); wave w takes the microphones
+// (4 blockIdx.y + w) APT_M + i (beyond M: the last one again, computed and not stored)
+template <bool LANE_IS_SOURCE, bool SPECTRAL>
+__global__ void __launch_bounds__(256) air_point_kernel(AirArgsPoint a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int m0 = (blockIdx.y * 4 + wave) * APT_M;
+    if (m0 >= a.M) return;
+    const int k0 = blockIdx.x * APT_R;
+    int q;
+    if (LANE_IS_SOURCE) {
+        const int i = blockIdx.z * 64 + lane;
+        if (i >= a.nlist) return;
+        q = a.list[i];
+    } else {
+        q = a.list[blockIdx.z];
+    }
+    double vx[APT_M], vy[APT_M], vz[APT_M];
+    cplx sum[APT_M][APT_R];
+#pragma unroll
+    for (int i = 0; i < APT_M; ++i) {
+        const int m = m0 + i < a.M ? m0 + i : a.M - 1;
+        vx[i] = a.v[m]; vy[i] = a.v[a.M + m]; vz[i] = a.v[2 * a.M + m];
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) sum[i][r] = mk(0.0, 0.0);
+    }
+    const int64_t j1 = a.ptr[q + 1];
+    for (int64_t j = a.ptr[q] + (LANE_IS_SOURCE ? 0 : lane); j < j1; j += LANE_IS_SOURCE ? 1 : 64)
+        air_point_component<SPECTRAL>(a, k0, j, vx, vy, vz, sum);
+#pragma unroll
+    for (int i = 0; i < APT_M; ++i) {
+        if (m0 + i >= a.M) break;
+        cplx* out = a.H + ((int64_t)q * a.M + m0 + i) * a.Pld;
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) {
+            cplx t = LANE_IS_SOURCE ? sum[i][r] : wave_sum(sum[i][r]);
+            const int k = k0 + r;
+            if (k == a.P - 1) t.y = 0.0;   // the last bin's value is the real part of the sum
+            if ((LANE_IS_SOURCE || lane == 0) && k < a.P) out[k] = t;
+        }
+    }
+}
+
 // the encoder in a load: X(k) = sum_m enc(c, m) H(k, m), m ascending, accumulated from 0 with fma; the real and the imaginary part of
 // enc as separate chains.  enc_re null: X = H(:, c)
 struct AirEnc {
@@ -390,10 +575,10 @@ void launch_air_spectra(int W, int P, int64_t Pld, const double* refl, const dou
 // the source lists of both forms in slices (grid.z stops at 65535): kernel_long on slices of the long sources, kernel_short on 64
 // short sources per grid.z
 template <class Args, class KL, class KS>
-static void air_main_launches(Args& a, const AirMain& m, unsigned gy, KL kernel_long, KS kernel_short, hipStream_t st) {
+static void air_main_launches(Args& a, const AirMain& m, unsigned gy, KL kernel_long, KS kernel_short, hipStream_t st, int bins = AIR_R) {
     a.bn = (const cplx*)m.bn; a.rec = m.rec; a.u = m.u; a.v = m.v; a.dint = m.dint; a.dfrac = m.dfrac; a.gain = m.gain; a.ptr = m.ptr;
     a.N = m.N; a.M = m.M; a.P = m.P; a.nfft = m.nfft; a.Pld = m.Pld; a.ncomp = m.ncomp; a.H = (cplx*)m.H;
-    const unsigned gx = (unsigned)(m.Pld / AIR_R);
+    const unsigned gx = (unsigned)(m.Pld / bins);
     for (int i0 = 0; i0 < m.n_long; i0 += 65535) {
         a.list = m.list_long + i0; a.nlist = std::min(65535, m.n_long - i0);
         kernel_long<<<dim3(gx, gy, (unsigned)a.nlist), 256, 0, st>>>(a);
@@ -406,8 +591,20 @@ static void air_main_launches(Args& a, const AirMain& m, unsigned gy, KL kernel_
     }
 }
 
+void launch_air_point_modes(int N, int P, int64_t Pld, double kr_step, void* bh, double* ginv, hipStream_t st) {
+    air_point_modes_kernel<<<(unsigned)ceil_div(std::max<int64_t>(Pld, N + 1), 256), 256, 0, st>>>(N, P, Pld, kr_step, (cplx*)bh, ginv);
+    KERNEL_CHECK();
+}
+
 void launch_air_main(const AirMain& m, hipStream_t st) {
-    if (m.nsurf > 0 || m.att) {
+    if (m.dist) {                                      // point sources: one kernel, the spectral gain its option
+        AirArgsPoint a{};
+        a.lnr = m.lnr; a.neg = m.neg; a.att = m.att; a.exp = m.exp; a.path = m.path; a.W = m.nsurf;
+        a.bh = (const cplx*)m.bh; a.ginv = m.ginv; a.dist = m.dist; a.r = m.mic_radius; a.kappa_step = m.kappa_step;
+        const unsigned gy = (unsigned)ceil_div(m.M, 4 * APT_M);
+        if (m.nsurf > 0 || m.att) air_main_launches(a, m, gy, air_point_kernel<false, true>, air_point_kernel<true, true>, st, APT_R);
+        else air_main_launches(a, m, gy, air_point_kernel<false, false>, air_point_kernel<true, false>, st, APT_R);
+    } else if (m.nsurf > 0 || m.att) {
         AirArgsSpectral a{};
         a.lnr = m.lnr; a.neg = m.neg; a.att = m.att; a.exp = m.exp; a.path = m.path; a.W = m.nsurf;
         air_main_launches(a, m, (unsigned)ceil_div(m.M, 8), air_two_mics_kernel<false>, air_two_mics_kernel<true>, st);

@@ -1,6 +1,7 @@
-// C ABI of the array impulse responses (include/emagls.h; DESIGN.md sections 11 to 13): emagls_array_irs from listed components,
+// C ABI of the array impulse responses (include/emagls.h; DESIGN.md sections 11 to 14): emagls_array_irs from listed components,
 // emagls_shoebox_components and emagls_array_room_irs from a shoebox room, and their spectral forms (reflection spectra per surface
-// and air absorption: emagls_array_irs_spectral, emagls_shoebox_images, emagls_array_room_irs_spectral).  Host arrays in, host array out; every argument is
+// and air absorption: emagls_array_irs_spectral, emagls_shoebox_images, emagls_array_room_irs_spectral), and their point-source forms
+// (section 14: emagls_array_irs_point, emagls_shoebox_components_dist, emagls_array_room_irs_point).  Host arrays in, host array out; every argument is
 // checked before the device is touched (a room call's scratch estimate, which needs the component count, after its count pass), and
 // every array operation runs in the kernels of array_irs.hip, shoebox.hip, modal.hip and fft.hip (the twiddles), with hipFFT's Z2D
 // above 4096 points (the precedent of decode.hip above 2048 taps).  The speed of sound and the simulation order are
@@ -104,8 +105,31 @@ struct AirSpectral {
     const double *refl = nullptr, *att = nullptr;
     const int* d_exp = nullptr;
     const double* d_path = nullptr;
+    const double* d_dist = nullptr;       // [ncomp] on the device: point sources
     bool any() const { return nsurf > 0 || att; }
 };
+
+// the rules of a point-source call's distances: finite and beyond the sphere; returns the largest
+double air_check_dist(const AirCall& c, const double* comp_dist, int64_t ncomp) {
+    double far = 0.0;
+    for (int64_t j = 0; j < ncomp; ++j) {
+        if (!std::isfinite(comp_dist[j]) || !(comp_dist[j] > c.mic_radius))
+            throw Error(EMAGLS_ERR_ARG, "component distances must be finite and greater than mic_radius (component " + std::to_string(j) + ")");
+        far = std::max(far, comp_dist[j]);
+    }
+    return far;
+}
+
+// the scaled radial recurrence G_n(x) of array_irs.hip grows like x^n / (2n-1)!!: a call whose largest x = kappa_max rho_max brings it
+// within reach of FP64's range at n = N is refused
+void air_check_point_range(const AirCall& c, double rho_max) {
+    const double x = kPi * c.fs / C_SOUND * rho_max;
+    double lg = 0.0;                                   // log10 (2N-1)!!
+    for (int n = 1; n <= c.N; ++n) lg += std::log10((double)(2 * n - 1));
+    if (x > 0.0 && (double)c.N * std::log10(x) - lg >= 300.0)
+        throw Error(EMAGLS_ERR_UNSUPPORTED, "a point source this far away at this simulation order leaves the range of FP64 "
+                                            "(N log10(kappa_max rho_max) - log10((2N-1)!!) >= 300): treat it as a plane wave");
+}
 
 // the rules of the spectra: finite, |R| <= 1, alpha >= 0
 void air_check_spectra(int64_t nsurf, const double* refl, const double* att, int P, const char* what) {
@@ -119,10 +143,12 @@ void air_check_spectra(int64_t nsurf, const double* refl, const double* att, int
 
 // the device memory estimate of a call with ncomp components, nsurf surfaces and (air) an air term (in long double: the counts of a
 // refused call may overflow 64 bits); room: the enumeration's lists are counted too
-void air_check_scratch(const AirCall& c, int64_t ncomp, int nsurf = 0, bool air = false) {
+void air_check_scratch(const AirCall& c, int64_t ncomp, int nsurf = 0, bool air = false, bool point = false) {
     const long double spectral = nsurf > 0 || air ? (long double)(nsurf + 1) * (c.Pld + c.P) * 8 + (long double)c.Pld * 4 +
                                                         (long double)ncomp * (4 * nsurf + (air ? 8 : 0)) : 0.0L;
-    const long double need = spectral + (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
+    // (point sources: the scaled table in the place of b', the reciprocals and the distances)
+    const long double pt = point ? (long double)(c.N + 1) * 8 + (long double)ncomp * 8 : 0.0L;
+    const long double need = spectral + pt + (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
                              (long double)c.nsrc * 12 + (long double)c.out_bytes +
                              (c.lds ? 0.0L : (c.enc ? (long double)c.rows * c.np * c.P * 16 : 0.0L) + (long double)c.rows * c.np * c.nfft * 8);
     if (need > (long double)AIR_SCRATCH_MAX)
@@ -149,11 +175,19 @@ void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* 
         }
     }
     // 1. mode coefficients b'_n(k) = -b_n (2n+1) / (4 pi) as rows [N+1][Pld]
-    cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)(N + 1) * Pld, true);
+    // (point sources: the scaled table of section 14 in their place, from a kernel of its own that needs no b_n)
+    const bool point = sp.d_dist != nullptr;
+    cplx* bn = s.get<cplx>(sizeof(cplx) * (size_t)(N + 1) * Pld, !point);
     double* rec = s.get<double>(sizeof(double) * 2 * (N + 1));
-    const double kr_step = 2.0 * kPi * (c.fs / (double)nfft) / C_SOUND * c.mic_radius;
-    launch_modal_bn(N, P, nullptr, kr_step, -1.0 / (4.0 * kPi), bn, 1, Pld, s.st);     // bnAll = -sphModalCoeffs(...)  (:107)
-    launch_air_modes(N, P, Pld, bn, rec, s.st);
+    double* ginv = point ? s.get<double>(sizeof(double) * (N + 1)) : nullptr;
+    const double kappa_step = 2.0 * kPi * (c.fs / (double)nfft) / C_SOUND, kr_step = kappa_step * c.mic_radius;
+    if (point) {
+        launch_air_modes(N, 0, Pld, nullptr, rec, s.st);                                // (the Legendre coefficients alone)
+        launch_air_point_modes(N, P, Pld, kr_step, bn, ginv, s.st);
+    } else {
+        launch_modal_bn(N, P, nullptr, kr_step, -1.0 / (4.0 * kPi), bn, 1, Pld, s.st);     // bnAll = -sphModalCoeffs(...)  (:107)
+        launch_air_modes(N, P, Pld, bn, rec, s.st);
+    }
     // 2. components and microphones
     AirMain m{};
     double* v = s.get<double>(sizeof(double) * 3 * M);
@@ -168,6 +202,7 @@ void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* 
         m.gain = d_gain;
     }
     m.bn = bn; m.rec = rec; m.v = v;
+    if (point) { m.dist = sp.d_dist; m.bh = bn; m.ginv = ginv; m.mic_radius = c.mic_radius; m.kappa_step = kappa_step; }
     m.ptr = d_ptr;
     m.list_long = s.put_opt(list_long.data(), list_long.size());
     m.list_short = s.put_opt(list_short.data(), list_short.size());
@@ -298,13 +333,15 @@ struct Shoebox {
         s.sync();
     }
     int64_t total() const { return h_ptr.back(); }
-    void fill(bool images = false) {
+    void fill(bool images = false, bool dist = false) {    // dist: path beside the flat lists (images has it anyway)
         const size_t n = (size_t)total();
         azi = s.get<double>(sizeof(double) * n); zen = s.get<double>(sizeof(double) * n);
         delay = s.get<double>(sizeof(double) * n); gain = s.get<double>(sizeof(double) * n);
-        if (images) { exp = s.get<int>(sizeof(int) * 6 * n); path = s.get<double>(sizeof(double) * n); }
+        if (images) exp = s.get<int>(sizeof(int) * 6 * n);
+        if (images || dist) path = s.get<double>(sizeof(double) * n);
         HIP_CHECK(hipEventRecord(ev_write.a, s.st));
         if (n && images) launch_shoebox_write_images(a, nsrc, src, mask, base, azi, zen, delay, gain, exp, path, s.st);
+        else if (n && dist) launch_shoebox_write_dist(a, nsrc, src, mask, base, azi, zen, delay, gain, path, s.st);
         else if (n) launch_shoebox_write(a, nsrc, src, mask, base, azi, zen, delay, gain, s.st);
         HIP_CHECK(hipEventRecord(ev_write.b, s.st));
         written = true;
@@ -383,6 +420,40 @@ extern "C" int emagls_array_irs_spectral(double fs, double mic_radius, int order
     });
 }
 
+extern "C" int emagls_array_irs_point(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                      const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr,
+                                      const double* comp_azi, const double* comp_zen, const double* comp_delay, const double* comp_gain,
+                                      int64_t nsurf, const double* surf_refl, const int32_t* comp_exp, const double* air_atten,
+                                      const double* comp_path, const double* comp_dist, double pre_delay, int64_t nfft_in, int64_t nr, void* out) {
+    return guarded_call([&] {
+        // ---- arguments (nothing below this block fails on what the caller passed)
+        if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
+        if (nfft_in == 0 && (nsurf > 0 || air_atten)) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the spectra have nfft / 2 + 1 bins");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        const int64_t ncomp = air_check_lists(c, comp_ptr, comp_azi, comp_zen, comp_delay, comp_gain);
+        if (ncomp > 0 && !comp_dist) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_dist (distances are given for all components or, in emagls_array_irs, for none)");
+        air_check_point_range(c, air_check_dist(c, comp_dist, ncomp));
+        if ((air_atten == nullptr) != (comp_path == nullptr)) throw Error(EMAGLS_ERR_ARG, "air_atten and comp_path must both be given or both be NULL");
+        air_check_spectra(nsurf, surf_refl, air_atten, c.P, "surf_refl");
+        if (nsurf > 0 && ncomp > 0 && !comp_exp) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_exp");
+        for (int64_t i = 0; i < ncomp * nsurf; ++i)
+            if (comp_exp[i] < 0) throw Error(EMAGLS_ERR_ARG, "component exponents must be non-negative");
+        for (int64_t j = 0; comp_path && j < ncomp; ++j)
+            if (!(comp_path[j] >= 0.0) || !std::isfinite(comp_path[j])) throw Error(EMAGLS_ERR_ARG, "component path lengths must be non-negative and finite");
+        air_check_scratch(c, ncomp, (int)nsurf, air_atten != nullptr, true);
+        // ---- device
+        Scratch s;
+        const size_t n = (size_t)ncomp;
+        AirSpectral sp;
+        sp.nsurf = (int)nsurf; sp.refl = surf_refl; sp.att = air_atten;
+        sp.d_exp = nsurf > 0 ? s.put_opt(comp_exp, n * (size_t)nsurf) : nullptr;
+        sp.d_path = air_atten ? s.put_opt(comp_path, n) : nullptr;
+        sp.d_dist = s.put(comp_dist ? comp_dist : &c.mic_radius, std::max<size_t>(n, comp_dist ? 0 : 1));   // (never null: it selects the kernel)
+        const int64_t* d_ptr = s.put(comp_ptr, (size_t)nsrc + 1);
+        air_run(s, c, comp_ptr, d_ptr, s.put_opt(comp_azi, n), s.put_opt(comp_zen, n), s.put_opt(comp_delay, n), s.put_opt(comp_gain, n), sp);
+    });
+}
+
 extern "C" int emagls_array_irs_kernel_time(double* ms) {
     return guarded_call([&] {
         if (!ms) throw Error(EMAGLS_ERR_ARG, "null pointer: ms");
@@ -391,13 +462,14 @@ extern "C" int emagls_array_irs_kernel_time(double* ms) {
     });
 }
 
-extern "C" int emagls_shoebox_components(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc,
-                                         const double* src_pos, double fs, double max_delay, int max_order, int64_t capacity,
-                                         int64_t* comp_ptr, double* comp_azi, double* comp_zen, double* comp_delay, double* comp_gain) {
+// emagls_shoebox_components, and with want_dist its sibling with the distances beside the lists
+static int shoebox_components(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc, const double* src_pos,
+                              double fs, double max_delay, int max_order, int64_t capacity, int64_t* comp_ptr, double* comp_azi,
+                              double* comp_zen, double* comp_delay, double* comp_gain, bool want_dist, double* comp_dist) {
     return guarded_call([&] {
         if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
         if (capacity < 0) throw Error(EMAGLS_ERR_ARG, "invalid shape: capacity");
-        if (capacity > 0 && (!comp_azi || !comp_zen || !comp_delay || !comp_gain))
+        if (capacity > 0 && (!comp_azi || !comp_zen || !comp_delay || !comp_gain || (want_dist && !comp_dist)))
             throw Error(EMAGLS_ERR_ARG, "null pointer: component arrays (capacity 0 for a count-only call)");
         const ShoeboxArgs a = shoebox_check(room_dim, wall_refl, array_pos, nsrc, src_pos, fs, 0.0, max_delay, max_order);
         Scratch s;
@@ -406,15 +478,31 @@ extern "C" int emagls_shoebox_components(const double* room_dim, const double* w
         std::copy(box.h_ptr.begin(), box.h_ptr.end(), comp_ptr);
         const size_t n = (size_t)box.total();
         if (n > 0 && box.total() <= capacity) {
-            box.fill();
+            box.fill(false, want_dist);
             HIP_CHECK(hipMemcpyAsync(comp_azi, box.azi, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
             HIP_CHECK(hipMemcpyAsync(comp_zen, box.zen, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
             HIP_CHECK(hipMemcpyAsync(comp_delay, box.delay, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
             HIP_CHECK(hipMemcpyAsync(comp_gain, box.gain, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
+            if (want_dist) HIP_CHECK(hipMemcpyAsync(comp_dist, box.path, sizeof(double) * n, hipMemcpyDeviceToHost, s.st));
             s.sync();
         }
         box.keep_time();
     });
+}
+
+extern "C" int emagls_shoebox_components(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc,
+                                         const double* src_pos, double fs, double max_delay, int max_order, int64_t capacity,
+                                         int64_t* comp_ptr, double* comp_azi, double* comp_zen, double* comp_delay, double* comp_gain) {
+    return shoebox_components(room_dim, wall_refl, array_pos, nsrc, src_pos, fs, max_delay, max_order, capacity, comp_ptr, comp_azi, comp_zen,
+                              comp_delay, comp_gain, false, nullptr);
+}
+
+extern "C" int emagls_shoebox_components_dist(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc,
+                                              const double* src_pos, double fs, double max_delay, int max_order, int64_t capacity,
+                                              int64_t* comp_ptr, double* comp_azi, double* comp_zen, double* comp_delay, double* comp_gain,
+                                              double* comp_dist) {
+    return shoebox_components(room_dim, wall_refl, array_pos, nsrc, src_pos, fs, max_delay, max_order, capacity, comp_ptr, comp_azi, comp_zen,
+                              comp_delay, comp_gain, true, comp_dist);
 }
 
 extern "C" int emagls_shoebox_images(const double* room_dim, const double* array_pos, int64_t nsrc, const double* src_pos, double fs,
@@ -486,6 +574,43 @@ extern "C" int emagls_array_room_irs(double fs, double mic_radius, int order, co
         air_check_scratch(c, box.total());
         box.fill();
         air_run(s, c, box.h_ptr.data(), box.ptr, box.azi, box.zen, box.delay, box.gain);
+        box.keep_time();
+        for (int64_t q = 0; comp_count && q < nsrc; ++q) comp_count[q] = box.h_ptr[q + 1] - box.h_ptr[q];
+    });
+}
+
+extern "C" int emagls_array_room_irs_point(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                           const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
+                                           int wall_is_spectral, const double* air_atten, const double* array_pos, int64_t nsrc,
+                                           const double* src_pos, double max_delay, int max_order, double pre_delay, int64_t nfft_in,
+                                           int64_t nr, int64_t* comp_count, void* out) {
+    return guarded_call([&] {
+        const bool spectral = wall_is_spectral != 0 || air_atten != nullptr;
+        if (nfft_in == 0 && spectral) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the spectra have nfft / 2 + 1 bins");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        if (!wall_refl) throw Error(EMAGLS_ERR_ARG, "null pointer: wall_refl");
+        const ShoeboxArgs a = shoebox_check(room_dim, spectral ? SBX_ONES : wall_refl, array_pos, nsrc, src_pos, fs, mic_radius, max_delay, max_order);
+        std::vector<double> rep;                       // six coefficients with air: repeated over the bins
+        const double* walls = wall_refl;
+        if (spectral && !wall_is_spectral) {
+            rep.resize((size_t)6 * c.P);
+            for (int w = 0; w < 6; ++w) std::fill(rep.begin() + (size_t)w * c.P, rep.begin() + (size_t)(w + 1) * c.P, wall_refl[w]);
+            walls = rep.data();
+        }
+        if (spectral) air_check_spectra(6, walls, air_atten, c.P, "wall_refl");
+        if (max_delay + pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "max_delay plus pre_delay beyond nfft - 1 would wrap");
+        air_check_point_range(c, max_delay * C_SOUND / fs);      // (no kept image is farther than the reach of max_delay)
+        const int nsurf = spectral ? 6 : 0;
+        air_check_scratch(c, 0, nsurf, air_atten != nullptr, true);
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        air_check_scratch(c, box.total(), nsurf, air_atten != nullptr, true);
+        box.fill(spectral, true);
+        AirSpectral sp;
+        if (spectral) { sp.nsurf = 6; sp.refl = walls; sp.att = air_atten; sp.d_exp = box.exp; sp.d_path = air_atten ? box.path : nullptr; }
+        sp.d_dist = box.path;                          // (shoebox_check: every image lies beyond the sphere)
+        air_run(s, c, box.h_ptr.data(), box.ptr, box.azi, box.zen, box.delay, box.gain, sp);
         box.keep_time();
         for (int64_t q = 0; comp_count && q < nsrc; ++q) comp_count[q] = box.h_ptr[q + 1] - box.h_ptr[q];
     });

@@ -395,8 +395,15 @@ struct AirMain {
     int nsurf;                             // surfaces, <= 8
     const double* lnr; const unsigned* neg; const double* att;   // launch_air_spectra's tables [nsurf][Pld], [Pld], [Pld] or null
     const int* exp; const double* path;    // [ncomp][nsurf]; [ncomp] with att
+    // point sources: dist null is the plane-wave kernels above
+    const double* dist;                    // [ncomp] distances rho_j > mic_radius
+    const void* bh; const double* ginv;    // launch_air_point_modes' tables [N+1][Pld] complex, [N+1]
+    double mic_radius, kappa_step;         // r; kappa_k = k kappa_step
 };
 void launch_air_main(const AirMain& m, hipStream_t st);
+// the scaled mode table of the point-source kernels: bh [N+1][Pld] = b'_n(k) (2n-1)!! / (i kappa_k r)^n (zeros beyond P, the last bin
+// the scaled form of Re b'_n), ginv[n] = 1 / (4 n^2 - 1); kr_step = kappa_step r
+void launch_air_point_modes(int N, int P, int64_t Pld, double kr_step, void* bh, double* ginv, hipStream_t st);
 // refl [W][P], att [P] or null (attp then unused) -> lnr [W][Pld], neg [Pld], attp [Pld]
 void launch_air_spectra(int W, int P, int64_t Pld, const double* refl, const double* att, double* lnr, unsigned* neg, double* attp,
                         hipStream_t st);
@@ -422,6 +429,9 @@ void launch_shoebox_count(const ShoeboxArgs& a, int64_t nsrc, const double* src,
 void launch_shoebox_scan(const ShoeboxArgs& a, int64_t nsrc, const int* cnt, int64_t* base, int64_t* comp_ptr, hipStream_t st);
 void launch_shoebox_write(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                           double* zen, double* delay, double* gain, hipStream_t st);
+// the same lists, and the distance dist [n] of every component beside them (section 14)
+void launch_shoebox_write_dist(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                               double* zen, double* delay, double* gain, double* dist, hipStream_t st);
 // the same with the six exponents exp [n][6] (x0, x1, y0, y1, z0, z1) and the distance path [n] of every component (section 13)
 void launch_shoebox_write_images(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                                  double* zen, double* delay, double* gain, int* exp, double* path, hipStream_t st);

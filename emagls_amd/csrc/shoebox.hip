@@ -115,8 +115,9 @@ __global__ void __launch_bounds__(1024) shoebox_scan_kernel(int64_t ntiles, int6
 }
 
 // grid nsrc * tiles; azi, zen, delay, gain [base[ntiles]]; IMAGES: also exp [base[ntiles]][6] and path [base[ntiles]] (the spectral
-// room of DESIGN.md section 13, whose a.beta are ones: the walls enter in the responses' main kernel)
-template <bool IMAGES>
+// room of DESIGN.md section 13, whose a.beta are ones: the walls enter in the responses' main kernel); PATH without IMAGES: the
+// flat lists and path alone (the distances of the point-source responses, section 14)
+template <bool IMAGES, bool PATH = IMAGES>
 __global__ void __launch_bounds__(SBX_TILE) shoebox_write_kernel(ShoeboxArgs a, const double* __restrict__ src, const uint64_t* __restrict__ mask,
                                                                 const int64_t* __restrict__ base, double* __restrict__ azi,
                                                                 double* __restrict__ zen, double* __restrict__ delay, double* __restrict__ gain,
@@ -143,8 +144,8 @@ __global__ void __launch_bounds__(SBX_TILE) shoebox_write_kernel(ShoeboxArgs a, 
             exp[6 * r + 2 * i] = abs(n - par);
             exp[6 * r + 2 * i + 1] = abs(n);
         }
-        path[r] = o.d;
     }
+    if constexpr (PATH) path[r] = o.d;
 }
 
 void launch_shoebox_count(const ShoeboxArgs& a, int64_t nsrc, const double* src, uint64_t* mask, int* cnt, hipStream_t st) {
@@ -160,6 +161,12 @@ void launch_shoebox_scan(const ShoeboxArgs& a, int64_t nsrc, const int* cnt, int
 void launch_shoebox_write(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                           double* zen, double* delay, double* gain, hipStream_t st) {
     shoebox_write_kernel<false><<<(unsigned)(nsrc * a.tiles), SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, nullptr, nullptr);
+    KERNEL_CHECK();
+}
+
+void launch_shoebox_write_dist(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                               double* zen, double* delay, double* gain, double* dist, hipStream_t st) {
+    shoebox_write_kernel<false, true><<<(unsigned)(nsrc * a.tiles), SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, nullptr, dist);
     KERNEL_CHECK();
 }
 

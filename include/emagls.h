@@ -818,8 +818,9 @@ int emagls_array_irs_spectral(double fs, double mic_radius, int order, const dou
  * q is the list of the call with that source alone.
  * The search box is |n_i| <= floor(max_delay 343 / fs / (2 L_i)) + 1, and <= floor((max_order + 1) / 2) with an order limit; a call
  * with more than 2^28 candidates (8 prod_i (2 B_i + 1) per source, times nsrc) is EMAGLS_ERR_UNSUPPORTED.
- * Every argument is checked before the device is touched.  Plane-wave components are a far-field model: near-field (point-source)
- * terms and source directivity are not built.  Frequency-dependent walls and air absorption: the spectral entries below.
+ * Every argument is checked before the device is touched.  Plane-wave components are a far-field model: the images as point sources at
+ * their distances are emagls_array_room_irs_point below; source directivity is not built.  Frequency-dependent walls and air
+ * absorption: the spectral entries below.
  *
  * emagls_shoebox_components: comp_ptr [nsrc + 1] (host) is always written; comp_azi, comp_zen, comp_delay, comp_gain [capacity] are
  * written only when comp_ptr[nsrc] <= capacity.  NULL arrays with capacity = 0: a count-only call. */
@@ -858,6 +859,43 @@ int emagls_array_room_irs_spectral(double fs, double mic_radius, int order, cons
  * emagls_shoebox_components, emagls_shoebox_images or emagls_array_room_irs(_spectral) call; EMAGLS_ERR_ARG before the first one.  A
  * room call also sets the time of emagls_array_irs_kernel_time. */
 int emagls_shoebox_kernel_time(double* ms);
+
+/* ---- array impulse responses to point sources at a finite distance (this project's) ----
+ * emagls_array_irs_spectral with a distance rho_j in metres per component, comp_dist [ncomp]: every rho_j finite and > mic_radius
+ * (EMAGLS_ERR_ARG otherwise; distances are given for all components -- NULL with ncomp > 0 is EMAGLS_ERR_ARG -- and the entries
+ * without comp_dist are the calls with none).  With kappa_k = 2 pi f_k / 343 the order-n term of component j gains the factor
+ *   F_n(kappa_k rho_j),  F_n(x) = (-i)^(n+1) x e^(ix) h_n^(2)(x) = sum_{m <= n} (n+m)! / (m! (n-m)!) (1 / (2ix))^m,  F_0 = 1, F_n -> 1 as x -> inf:
+ *   H_q(k, m) = sum_j G_j(k) exp(-2 pi i k (tau_j + pre_delay) / nfft) sum_{n <= N} beta_n(k) (2n+1)/(4 pi) F_n(kappa_k rho_j) P_n(u_j . v_m).
+ * tau_j and g_j stay the caller's: with tau_j = rho_j / 343 fs and g_j = 1 / rho_j the component is the spherical wave
+ * e^(-i kappa R) / R of a point source, expanded about the array's centre (the e^(+i omega t), h^(2) convention of b_n).  Bin 0 is the
+ * limit kappa -> 0, beta_n (2n+1)/(4 pi) F_n -> -(2n+1)/(n+1) (r/rho_j)^n; in the last bin real(beta_n) is used and the real part of
+ * the sum is taken.  N is the plane-wave rule max(order, ceil(fs pi r / 343)): a source close to the sphere needs more orders, which
+ * `order` raises (N <= 85).  nsurf = 0 without an air term is allowed (then nfft = 0 also is).  The factors are formed inside the main
+ * kernel in a scaled form that stays inside FP64 at every order and bin; a call whose largest x = (pi fs / 343) max_j rho_j has
+ * N log10(x) - log10((2N-1)!!) >= 300 is EMAGLS_ERR_UNSUPPORTED (beyond a kilometre at N = 85, no room at N <= 60).  Encoder, transform,
+ * layout, the fixed summation order, the per-source form, equal bits for equal calls and for source q alone: emagls_array_irs.  Every
+ * argument is checked before the device is touched; the 24 GiB estimate counts the table and the distances;
+ * emagls_array_irs_kernel_time covers these launches.  Not built: +inf distances mixed into a call, source directivity, open or
+ * directional spheres, device-pointer outputs. */
+int emagls_array_irs_point(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                           const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr, const double* comp_azi,
+                           const double* comp_zen, const double* comp_delay, const double* comp_gain, int64_t nsurf,
+                           const double* surf_refl, const int32_t* comp_exp, const double* air_atten, const double* comp_path,
+                           const double* comp_dist, double pre_delay, int64_t nfft, int64_t nr, void* out);
+/* emagls_shoebox_components with the distance d of every component beside its columns, comp_dist [capacity] in metres: the comp_dist
+ * of emagls_array_irs_point, and the bits of emagls_shoebox_images' comp_path on walls of 1.  The four columns keep their bits. */
+int emagls_shoebox_components_dist(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc,
+                                   const double* src_pos, double fs, double max_delay, int max_order, int64_t capacity, int64_t* comp_ptr,
+                                   double* comp_azi, double* comp_zen, double* comp_delay, double* comp_gain, double* comp_dist);
+/* The room with its image sources as point sources: every component's rho is its d, handed to the main kernel on the device.
+ * wall_is_spectral = 0: wall_refl [6] coefficients (without air_atten the enumeration and the lists of emagls_array_room_irs, with it
+ * the coefficients are repeated over the bins); otherwise wall_refl [6 x P] spectra as in emagls_array_room_irs_spectral.  air_atten
+ * [P] or NULL.  The overflow rule above is applied to the reach of max_delay, before the device is touched.  Source q of a call gives
+ * the bits of emagls_array_irs_point on the lists emagls_shoebox_components_dist (emagls_shoebox_images, path = distance) returns. */
+int emagls_array_room_irs_point(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
+                                int wall_is_spectral, const double* air_atten, const double* array_pos, int64_t nsrc, const double* src_pos,
+                                double max_delay, int max_order, double pre_delay, int64_t nfft, int64_t nr, int64_t* comp_count, void* out);
 
 /* ---- plan API: inputs resident in HBM, repeated execution (benchmarks, batches) ------------- */
 

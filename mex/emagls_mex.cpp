@@ -846,8 +846,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
         // the spectral gain, four further arguments, [] or absent for none: surfaceReflection [W x P], exponents
         // [J x W], airAttenuation [P], pathLength [J]; P = nfft / 2 + 1
+        // point sources, a fifteenth argument, [] or absent for none: distance [J] in metres, one per component
         auto extra = [&](int i) { return nrhs > i && given(i); };
-        if (extra(11) || extra(12) || extra(13) || extra(14)) {
+        if (extra(15) && mxGetNumberOfElements(prhs[15]) != J) mexErrMsgIdAndTxt("eMagLS:arg", "distance must have one element per component (%d)", (int)J);
+        if (extra(11) || extra(12) || extra(13) || extra(14) || extra(15)) {
             if (extra(11) != extra(12)) mexErrMsgIdAndTxt("eMagLS:arg", "surfaceReflection and exponents must both be given or both be []");
             if (extra(13) != extra(14)) mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation and pathLength must both be given or both be []");
             const int64_t nfft = spectral_nfft(given(10) ? prhs[10] : nullptr, nr);
@@ -862,12 +864,18 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             }
             if (extra(13) && (mxGetNumberOfElements(prhs[13]) != P || mxGetNumberOfElements(prhs[14]) != (J ? J : mxGetNumberOfElements(prhs[14]))))
                 mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation must have %d elements (nfft / 2 + 1 bins) and pathLength one per component", (int)P);
-            const int rc = emagls_array_irs_spectral(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
-                                                     given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
-                                                     comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
-                                                     (int64_t)W, W ? refl.data() : nullptr, ex.empty() ? nullptr : ex.data(),
-                                                     extra(13) ? dbl(prhs[13], "airAttenuation") : nullptr, extra(13) ? dbl(prhs[14], "pathLength") : nullptr,
-                                                     mxGetScalar(prhs[5]), nfft, (int64_t)nr, out_ptr(plhs[0]));
+            const double *att = extra(13) ? dbl(prhs[13], "airAttenuation") : nullptr, *len = extra(13) ? dbl(prhs[14], "pathLength") : nullptr;
+            const int rc = extra(15)
+                ? emagls_array_irs_point(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
+                                         given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
+                                         comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
+                                         (int64_t)W, W ? refl.data() : nullptr, ex.empty() ? nullptr : ex.data(), att, len,
+                                         dbl(prhs[15], "distance"), mxGetScalar(prhs[5]), nfft, (int64_t)nr, out_ptr(plhs[0]))
+                : emagls_array_irs_spectral(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
+                                            given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
+                                            comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
+                                            (int64_t)W, W ? refl.data() : nullptr, ex.empty() ? nullptr : ex.data(), att, len,
+                                            mxGetScalar(prhs[5]), nfft, (int64_t)nr, out_ptr(plhs[0]));
             if (rc) fail(rc);
             return;
         }
@@ -926,6 +934,15 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
                                                 : "shoebox_components needs 7 arguments ([] for no limit on the reflection order)");
         auto given = [&](int i) { return prhs[i] && !mxIsEmpty(prhs[i]); };
         if (mxGetNumberOfElements(prhs[1]) != 3 || mxGetNumberOfElements(prhs[4]) != 3) mexErrMsgIdAndTxt("eMagLS:arg", "roomDim and arrayPos must have 3 elements");
+        // array_room_irs, a sixteenth argument waveModel ([] or absent: 'planeWave'): 'pointSource' makes every image a point source at its
+        // distance
+        bool point = false;
+        if (irs && nrhs > 16 && given(16)) {
+            char wm[32] = {0};
+            if (!mxIsChar(prhs[16]) || mxGetString(prhs[16], wm, sizeof wm)) wm[0] = '?';
+            point = std::string(wm) == "pointSource";
+            if (!point && std::string(wm) != "planeWave") mexErrMsgIdAndTxt("eMagLS:arg", "unknown waveModel: 'planeWave' or 'pointSource'");
+        }
         const bool air = irs && nrhs > 15 && given(15);
         const bool spectral = irs && (air || (mxGetNumberOfElements(prhs[2]) > 6 && mxGetM(prhs[2]) == 6));
         if (!spectral && mxGetNumberOfElements(prhs[2]) != 6)
@@ -949,8 +966,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             plhs[0] = mxCreateDoubleMatrix(Q + 1, 1, mxREAL);
             mxArray* comps = mxCreateDoubleMatrix(J, 4, mxREAL);
             double* o = mxGetDoubles(comps);
-            if (J) rc = emagls_shoebox_components(dim, refl, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, (int64_t)J, ptr.data(), o, o + J,
-                                                  o + 2 * J, o + 3 * J);
+            if (nlhs > 2) {                            // [compPtr, comps, dists] = ...: the distances [J x 1] in metres
+                plhs[2] = mxCreateDoubleMatrix(J, 1, mxREAL);
+                if (J) rc = emagls_shoebox_components_dist(dim, refl, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, (int64_t)J, ptr.data(), o,
+                                                           o + J, o + 2 * J, o + 3 * J, mxGetDoubles(plhs[2]));
+            } else if (J) {
+                rc = emagls_shoebox_components(dim, refl, pos, (int64_t)Q, src.data(), fs, max_delay, max_order, (int64_t)J, ptr.data(), o, o + J,
+                                               o + 2 * J, o + 3 * J);
+            }
             for (mwSize q = 0; q <= Q; ++q) mxGetDoubles(plhs[0])[q] = (double)ptr[q];
             if (nlhs > 1) plhs[1] = comps; else mxDestroyArray(comps);
             if (rc) fail(rc);
@@ -970,7 +993,22 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize od[3] = {nr, Cc, Q};
         plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
         std::vector<int64_t> counts(Q);
-        if (spectral) {
+        if (point) {
+            const int64_t nfft = spectral_nfft(given(12) ? prhs[12] : nullptr, nr);
+            const mwSize P = (mwSize)(nfft / 2 + 1);
+            const bool spectra = mxGetNumberOfElements(prhs[2]) != 6;
+            std::vector<double> walls;
+            if (spectra) {
+                if (mxGetM(prhs[2]) != 6 || mxGetN(prhs[2]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "wallReflection must be [6 x %d] (nfft / 2 + 1 bins)", (int)P);
+                walls = rows_of(refl, 6, P);
+            }
+            if (air && mxGetNumberOfElements(prhs[15]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation must have %d elements (nfft / 2 + 1 bins)", (int)P);
+            const int rc = emagls_array_room_irs_point(fs, mxGetScalar(prhs[8]), (int)mxGetScalar(prhs[10]), mics, mics + M, (int64_t)M,
+                                                       given(11) ? in_ptr(prhs[11]) : nullptr, ec ? 1 : 0, (int64_t)Cc, dim, spectra ? walls.data() : refl,
+                                                       spectra ? 1 : 0, air ? dbl(prhs[15], "airAttenuation") : nullptr, pos, (int64_t)Q, src.data(),
+                                                       max_delay, max_order, pre, nfft, (int64_t)nr, counts.data(), out_ptr(plhs[0]));
+            if (rc) fail(rc);
+        } else if (spectral) {
             const int64_t nfft = spectral_nfft(given(12) ? prhs[12] : nullptr, nr);
             const mwSize P = (mwSize)(nfft / 2 + 1);
             std::vector<double> walls(6 * (size_t)P);

@@ -15,8 +15,11 @@ function irs = getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZe
 %             reflection spectra in [-1, 1] over the P = nfft/2 + 1 bins, with exponents, a cell like sources of integer arrays
 %             [J_q x W]; airAttenuation [P] in Np/m with pathLength, a cell of [J_q x 1] arrays in metres (both or neither).  The gain
 %             of a component becomes gain * prod_w R_w(k)^e_w * exp(-alpha(k) * l) in bin k
+%   point sources (DESIGN.md section 14; emagls_array_irs_point): distance ([]), a cell like sources of [J_q x 1] arrays in metres (or
+%             [Q x 1] for the [Q x 2] form), every value finite and greater than micRadius, for all components or for none.  The
+%             order-n term of a component then carries the near-field factor F_n(kappa*rho); delay and gain stay the caller's
 %   irs       [irLen x numChannels x Q] (complex with a complex encoder): irs(:, :, q) is the rir of sourceFieldStream
-p = struct('order', 4, 'encoder', [], 'nfft', [], 'surfaceReflection', [], 'exponents', [], 'airAttenuation', [], 'pathLength', []);
+p = struct('order', 4, 'encoder', [], 'nfft', [], 'surfaceReflection', [], 'exponents', [], 'airAttenuation', [], 'pathLength', [], 'distance', []);
 for i = 1:2:numel(varargin)
     if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
     p.(varargin{i}) = varargin{i + 1};
@@ -48,6 +51,15 @@ if ~isempty(p.surfaceReflection) || ~isempty(p.airAttenuation)
     end
     if ~isempty(p.airAttenuation) && isempty(paths); paths = 0; end
 end
+dists = [];
+if ~isempty(p.distance)
+    if ~iscell(p.distance); p.distance = num2cell(double(p.distance(:))); end
+    if numel(p.distance) ~= Q; error('eMagLS:arg', 'distance must hold one array per source'); end
+    for q = 1:Q
+        dists = [dists; reshape(double(p.distance{q}), [], 1)]; %#ok<AGROW>
+    end
+    if numel(dists) ~= size(comps, 1); error('eMagLS:arg', 'distances are given for all components of a call or for none'); end
+end
 irs = emagls_mex('array_irs', compPtr, comps, double(fs), double(irLen), double(preDelay), double(micRadius), double(micGridAziZenRad), ...
-    double(p.order), double(p.encoder), double(p.nfft), double(p.surfaceReflection), exps, double(p.airAttenuation(:)), paths);
+    double(p.order), double(p.encoder), double(p.nfft), double(p.surfaceReflection), exps, double(p.airAttenuation(:)), paths, dists);
 end

@@ -10,9 +10,11 @@ function [irs, counts] = getArrayRoomIrs(roomDim, wallReflection, sourcePos, arr
 %   the spectral room (DESIGN.md section 13; emagls_array_room_irs_spectral): wallReflection [6 x P], one reflection spectrum per wall
 %   over the P = nfft/2 + 1 bins, and / or the name airAttenuation ([]), [P] in Np/m, each component's path its distance (six
 %   coefficients with it are repeated over the bins); then every image within maxOrder and maxDelay is a component
+%   waveModel ('planeWave', getSMAIRMatrix's parameter and default): 'pointSource' makes every image a point source at its distance
+%   (DESIGN.md section 14; emagls_array_room_irs_point): getArrayIrs with 'distance' on the lists of getShoeboxComponents, bit for bit
 %   irs       [irLen x numChannels x Q] (complex with a complex encoder): irs(:, :, q) is the rir of sourceFieldStream
 %   counts    [Q x 1] the number of image sources of each source position
-p = struct('order', 4, 'encoder', [], 'nfft', [], 'maxOrder', [], 'maxDelay', [], 'airAttenuation', []);
+p = struct('order', 4, 'encoder', [], 'nfft', [], 'maxOrder', [], 'maxDelay', [], 'airAttenuation', [], 'waveModel', 'planeWave');
 for i = 1:2:numel(varargin)
     if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
     p.(varargin{i}) = varargin{i + 1};
@@ -21,5 +23,5 @@ if size(sourcePos, 2) ~= 3; error('eMagLS:arg', 'sourcePos must be [Q x 3]'); en
 if numel(wallReflection) == 6; wallReflection = wallReflection(:); end
 [irs, counts] = emagls_mex('array_room_irs', double(roomDim(:)), double(wallReflection), double(sourcePos), double(arrayPos(:)), double(fs), ...
     double(irLen), double(preDelay), double(micRadius), double(micGridAziZenRad), double(p.order), double(p.encoder), double(p.nfft), ...
-    double(p.maxOrder), double(p.maxDelay), double(p.airAttenuation(:)));
+    double(p.maxOrder), double(p.maxDelay), double(p.airAttenuation(:)), char(p.waveModel));
 end

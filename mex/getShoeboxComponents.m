@@ -1,4 +1,4 @@
-function sources = getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, varargin)
+function [sources, distances] = getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, varargin)
 % The image sources of a shoebox room as plane-wave components at the array's centre, enumerated on the MI355X library (DESIGN.md
 % section 12; include/emagls.h, emagls_shoebox_components): Allen & Berkley's image model with frequency-independent walls.
 %   sources = getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, 'maxOrder', n)
@@ -10,17 +10,26 @@ function sources = getShoeboxComponents(roomDim, wallReflection, sourcePos, arra
 %   sources         cell of Q arrays [J_q x 4] with the columns azimuth, zenith, delay in samples and gain (1/distance times the
 %                   walls' coefficients; a unit source at 1 m in the free field has gain 1), in the definition's order: the
 %                   `sources` of getArrayIrs
+%   distances       (second output, on request) cell of Q arrays [J_q x 1], the components' distances in metres: the 'distance' of
+%                   getArrayIrs (DESIGN.md section 14)
 p = struct('maxOrder', []);
 for i = 1:2:numel(varargin)
     if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
     p.(varargin{i}) = varargin{i + 1};
 end
 if size(sourcePos, 2) ~= 3; error('eMagLS:arg', 'sourcePos must be [Q x 3]'); end
-[compPtr, comps] = emagls_mex('shoebox_components', double(roomDim(:)), double(wallReflection(:)), double(sourcePos), double(arrayPos(:)), ...
-    double(fs), double(maxDelay), double(p.maxOrder));
+args = {'shoebox_components', double(roomDim(:)), double(wallReflection(:)), double(sourcePos), double(arrayPos(:)), double(fs), ...
+    double(maxDelay), double(p.maxOrder)};
+if nargout > 1
+    [compPtr, comps, dists] = emagls_mex(args{:});
+else
+    [compPtr, comps] = emagls_mex(args{:});
+end
 Q = size(sourcePos, 1);
 sources = cell(Q, 1);
+distances = cell(Q, 1);
 for q = 1:Q
     sources{q} = comps(compPtr(q) + 1:compPtr(q + 1), :);
+    if nargout > 1; distances{q} = dists(compPtr(q) + 1:compPtr(q + 1)); end
 end
 end

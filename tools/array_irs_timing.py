@@ -27,6 +27,14 @@ alternating in one process after warm-up calls, at least five repetitions each: 
 The table of profiles/r27_room_spectral.md.
 
     python tools/array_irs_timing.py --spectral [reps] [out.md]
+
+With --point: the main kernel on the same two room shapes as plane waves (emagls_array_room_irs, the flat kernel) and as point sources
+(emagls_array_room_irs_point) -- flat walls, and the data-sheet form with flat spectra and air -- alternating in
+one process after warm-up calls, at least five repetitions each: medians, extremes, the ratio to the flat kernel, and how far the
+point-source response lies from the plane-wave one.  The table of profiles/r28_point_sources.md; a variant built with other
+AIR_POINT_BINS / AIR_POINT_MICS is run through EMAGLS_LIB_PATH.
+
+    python tools/array_irs_timing.py --point [reps] [out.md]
 """
 import ctypes as C
 import os
@@ -181,7 +189,50 @@ def main_spectral(argv):
             f.write(text + "\n")
 
 
+def main_point(argv):
+    import emagls_amd as E
+    from emagls_amd import _lib as L
+    from oracle import emagls_oracle as O
+    from tools.csrc_hash import csrc_sha16
+    reps = max(int(argv[0]) if argv else 5, 5)
+    out = argv[1] if len(argv) > 1 else None
+    mics = random_dirs(np.random.default_rng(19), 32)
+    room, beta, src, pos, pre = (5.2, 4.1, 2.9), (0.9, 0.85, 0.8, 0.75, 0.7, 0.6), (1.3, 2.2, 1.1), (3.4, 1.7, 1.6), 64.0
+    N = O.simulation_order(4, FS, RADIUS)
+    lines = ["Kernel sources: csrc_sha16 %s; library %s.  Simulation order N = %d, 32 microphones, one source; the forms alternate in one "
+             "process, %d calls each after 2 warm-up calls each; device-event time of the main kernel (emagls_array_irs_kernel_time)." %
+             (csrc_sha16(), os.path.basename(L.LIB_PATH), N, reps), "",
+             "| max_delay | nfft | components | form | main kernel ms: median | min | max | over flat (medians) | largest difference from the plane waves |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    ms = C.c_double(0.0)
+    for max_delay, nfft, ir_len in ((6000.0, 8192, 8192), (24000.0, 65536, 32768)):
+        walls, air = np.repeat(np.array(beta)[:, None], nfft // 2 + 1, axis=1), E.airAttenuation(FS, nfft)
+        forms = [("plane waves, flat", beta, None, "planeWave"), ("point sources, flat", beta, None, "pointSource"),
+                 ("point sources, flat spectra of the same coefficients and air", walls, air, "pointSource")]
+        call = lambda w, a, m: E.getArrayRoomIrs(room, w, src, pos, FS, ir_len, pre, RADIUS, mics, nfft=nfft, maxDelay=max_delay,   # noqa: E731
+                                                 airAttenuation=a, returnCounts=True, waveModel=m)
+        times, res = [[] for _ in forms], [None] * len(forms)
+        for i in range(2 + reps):
+            for f, (_name, w, a, m) in enumerate(forms):
+                res[f], counts = call(w, a, m)
+                L.check(L.load().emagls_array_irs_kernel_time(C.byref(ms)))
+                if i >= 2:
+                    times[f].append(ms.value)
+        flat = float(np.median(times[0]))
+        for f, (name, _w, _a, _m) in enumerate(forms):
+            diff = "" if f == 0 else "%.3g" % (np.abs(res[f] - res[0]).max() / np.abs(res[0]).max())
+            lines.append("| %d | %d | %d | %s | %.3f | %.3f | %.3f | %.3f | %s |" % (max_delay, nfft, counts[0], name, np.median(times[f]), np.min(times[f]),
+                                                                               np.max(times[f]), np.median(times[f]) / flat, diff))
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--point":
+        return main_point(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--room":
         return main_room(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--spectral":
