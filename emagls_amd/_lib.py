@@ -232,6 +232,15 @@ SYMBOLS = {
     "emagls_array_room_irs_point": (C.c_int, [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_int, c_i64,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_int,
                                               C.c_double, c_i64, c_i64, C.c_void_p, C.c_void_p]),
+    "emagls_array_irs_directive": (C.c_int, [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_int, c_i64, c_i64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, c_i64, c_i64,
+                                             C.c_void_p]),
+    "emagls_shoebox_emission": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_double, C.c_int, c_i64,
+                                          C.c_void_p, C.c_void_p]),
+    "emagls_array_room_irs_directive": (C.c_int, [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_int, c_i64,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_int,
+                                                  C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, c_i64, c_i64, C.c_void_p, C.c_void_p]),
     "emagls_eq_filter_nfft": (c_i64, [c_i64]),
     "emagls_get_magls_spherical_head_filter": (C.c_int, [C.c_double, C.c_int, C.c_double, c_i64, C.c_void_p, C.c_void_p]),
     "emagls_get_magls_array_diffuse_filter": (C.c_int, [C.c_double, C.c_void_p, C.c_void_p, c_i64, C.c_int, C.c_double, c_i64, C.c_int,

@@ -1411,8 +1411,44 @@ def _per_component(what, arrs, ptr, width, dtype):
     return np.ascontiguousarray(flat, dtype=dtype)
 
 
+def firstOrderDirectivity(a):
+    """The [4] real-SH coefficients of the first-order pattern a + (1 - a) cos(gamma) about the source's front axis (host only):
+    c_0 = a sqrt(4 pi), c_3 = (1 - a) sqrt(4 pi / 3) (the x term, n = 1, m = +1), the others 0.  a = 1 is omnidirectional, a = 0.5 a
+    cardioid, a = 0 a figure of eight: the `directivity` of getArrayIrs and getArrayRoomIrs."""
+    a = float(a)
+    return np.array([a * np.sqrt(4.0 * np.pi), 0.0, 0.0, (1.0 - a) * np.sqrt(4.0 * np.pi / 3.0)])
+
+
+def _directive(directivity, sourceOrientation, Q, P):
+    """directivity and sourceOrientation as the C ABI takes them: (Nd, coef [Q x Kd x P] complex128, rot [Q x 9] float64 or None)."""
+    c = np.asarray(directivity)
+    if c.ndim == 1:
+        c = c[None, :, None]
+    elif c.ndim == 2:
+        c = c[:, :, None]
+    if c.ndim != 3 or c.shape[0] not in (1, Q) or c.shape[2] not in (1, P):
+        raise ValueError("directivity must be [Q x Kd x P] (Q = %d sources, P = nfft / 2 + 1 = %d bins), [Q x Kd] or [Kd], got %s"
+                         % (Q, P, np.shape(directivity)))
+    Kd = c.shape[1]
+    Nd = int(round(np.sqrt(Kd))) - 1
+    if Kd < 1 or (Nd + 1) ** 2 != Kd:
+        raise ValueError("directivity holds %d coefficients per source and bin, which is not a square (Nd + 1)^2" % Kd)
+    coef = np.ascontiguousarray(np.broadcast_to(c, (Q, Kd, P)), dtype=np.complex128)
+    rot = None
+    if sourceOrientation is not None:
+        o = np.asarray(sourceOrientation, dtype=np.float64)
+        if o.shape == (Q, 2):                          # (azi, zen) of the front axis, zero roll: R = Rz(azi) Ry(zen - pi / 2)
+            ca, sa, cb, sb = np.cos(o[:, 0]), np.sin(o[:, 0]), np.cos(o[:, 1] - np.pi / 2), np.sin(o[:, 1] - np.pi / 2)
+            z = np.zeros(Q)
+            o = np.stack([np.stack([ca * cb, -sa, ca * sb], axis=1), np.stack([sa * cb, ca, sa * sb], axis=1), np.stack([-sb, z, cb], axis=1)], axis=1)
+        if o.shape != (Q, 3, 3):
+            raise ValueError("sourceOrientation must be [Q x 3 x 3] rotation matrices or [Q x 2] (azi, zen) of the front axis, got %s" % (o.shape,))
+        rot = np.ascontiguousarray(o.reshape(Q, 9))
+    return Nd, coef, rot
+
+
 def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4, encoder=None, nfft=None, surfaceReflection=None,
-                exponents=None, airAttenuation=None, pathLength=None, distance=None):
+                exponents=None, airAttenuation=None, pathLength=None, distance=None, emission=None, sourceOrientation=None, directivity=None):
     """Impulse responses of the simulated rigid-sphere array (the array of getSMAIRMatrix) to sources that are sums of plane-wave
     components (include/emagls.h, emagls_array_irs).  `sources` is a [Q x 2] array of directions (azi, zen),
     one unit plane wave each -- a direction bank for a moving virtual source -- or a list of Q arrays [J_q x 2|3|4] with the columns
@@ -1430,7 +1466,14 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
     ([Q] for the [Q x 2] form), every value finite and greater than micRadius, for all components or (None) for none.  The order-n
     term of a component then carries the near-field factor F_n(kappa rho); delay and gain stay the caller's (rho / 343 fs and
     1 / rho make it the point source's spherical wave).  The simulation order is the plane-wave rule: raise `order` for a source
-    close to the sphere."""
+    close to the sphere.
+    Directive sources (emagls_array_irs_directive): `directivity` [Q x Kd x P], real or complex, the
+    coefficients of each source's directivity per bin in the real basis of getSH(Nd, ., 'real'), Kd = (Nd + 1)^2 with Nd <= 8
+    ([Q x Kd] or [Kd] is repeated over bins and sources; firstOrderDirectivity makes first-order patterns); `emission`, a list shaped
+    like `sources` of [J_q x 3] unit vectors in room axes along which each component's ray left the real source ([Q x 3] for the
+    [Q x 2] form; getShoeboxComponents and getShoeboxImages return them with returnEmission); and sourceOrientation [Q x 3 x 3],
+    rotation matrices whose columns are each source's front, left and up axes in room axes, or [Q x 2] = (azi, zen) of the front axis
+    with zero roll (absent: the room's axes).  A component's gain is multiplied by sum_i c_i(k) Y_i(R^T e)."""
     ptr, azi, zen, delay, gain = _components(sources)
     maz, mzn, M, enc, pe, e_c, Cc, nr = _array_side(micGridAziZenRad, encoder, irLen)
     Q = ptr.size - 1
@@ -1447,7 +1490,9 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
                 raise ValueError("distance must be a list with one array [J_q] per source (or [Q] values for sources of one component)")
         if dist.size == 0:
             dist = np.full((1, 1), np.inf)             # (no component: the pointer alone says "point sources")
-    if any(a is not None for a in (surfaceReflection, exponents, airAttenuation, pathLength, distance)):
+    if directivity is None and (emission is not None or sourceOrientation is not None):
+        raise L.EmaglsError(L.ERR_ARG, "emission and sourceOrientation come with a directivity")
+    if any(a is not None for a in (surfaceReflection, exponents, airAttenuation, pathLength, distance, directivity)):
         if (surfaceReflection is None) != (exponents is None):
             raise ValueError("surfaceReflection and exponents must both be given or both be absent")
         if (airAttenuation is None) != (pathLength is None):
@@ -1468,7 +1513,16 @@ def getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, or
                 path = np.zeros((1, 1))        # (the pair rule is on the pointers)
         head = (float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc, Q, _addr(ptr), _addr(azi),
                 _addr(zen), _addr(delay), _addr(gain), W, _addr(refl), _addr(ex) if ex is not None and ex.size else None, _addr(att), _addr(path))
-        if dist is not None:
+        if directivity is not None:
+            if emission is None:
+                raise L.EmaglsError(L.ERR_ARG, "a directivity needs the emission vectors of the components (emission=)")
+            if isinstance(emission, np.ndarray) and emission.shape == (Q, 3):
+                emission = list(emission)              # (one component per source)
+            emit = _per_component("emission", emission, ptr, 3, np.float64)
+            Nd, coef, rot = _directive(directivity, sourceOrientation, Q, P)
+            L.check(L.load().emagls_array_irs_directive(*head, _addr(dist), _addr(emit) if emit.size else None, _addr(rot), Nd, _addr(coef),
+                                                        float(preDelay), n_fft, nr, _addr(out)))
+        elif dist is not None:
             L.check(L.load().emagls_array_irs_point(*head, _addr(dist), float(preDelay), n_fft, nr, _addr(out)))
         else:
             L.check(L.load().emagls_array_irs_spectral(*head, float(preDelay), n_fft, nr, _addr(out)))
@@ -1514,14 +1568,26 @@ def _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder):
     return dim, refl, pos, src, -1 if maxOrder is None else int(maxOrder)
 
 
-def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None, returnDistance=False):
+def _shoebox_emission(lib, dim, refl, pos, src, fs, maxDelay, mo, ptr):
+    """The emission vectors of the lists whose offsets are ptr (refl None: the images): a list of [J_q x 3] arrays."""
+    n, Q = int(ptr[-1]), src.shape[0]
+    emit, p2 = np.zeros((max(n, 1), 3)), np.zeros(Q + 1, dtype=np.int64)
+    if n:
+        L.check(lib.emagls_shoebox_emission(_addr(dim), _addr(refl), _addr(pos), Q, _addr(src), float(fs), float(maxDelay), mo, n, _addr(p2),
+                                            _addr(emit)))
+    return [np.ascontiguousarray(emit[ptr[q]:ptr[q + 1]]) for q in range(Q)]
+
+
+def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None, returnDistance=False, returnEmission=False):
     """The image sources of a shoebox room as plane-wave components at the array's centre (include/emagls.h,
     emagls_shoebox_components), enumerated on the device.  roomDim (Lx, Ly, Lz) in metres, one corner at the origin, axes as getSH's
     (x front, y left, z up); wallReflection: six amplitude reflection coefficients in [-1, 1] for the walls x=0, x=Lx, y=0, y=Ly,
     z=0, z=Lz; sourcePos [Q x 3] (or one position) and arrayPos inside the room; maxDelay in samples; maxOrder: the largest
     reflection order kept (None: no limit).  Returns a list of Q arrays [J_q x 4] with the columns azi, zen, delay in samples and
     gain (1 / distance times the walls' coefficients), in the definition's order: the `sources` of getArrayIrs.  With returnDistance
-    also a list of Q arrays [J_q], the components' distances in metres: the `distance` of getArrayIrs."""
+    also a list of Q arrays [J_q], the components' distances in metres: the `distance` of getArrayIrs.  With
+    returnEmission a further list of Q arrays [J_q x 3] comes last: the unit vectors in room axes along which the components' rays
+    left the real source, the `emission` of getArrayIrs (emagls_shoebox_emission)."""
     dim, refl, pos, src, mo = _room(roomDim, wallReflection, sourcePos, arrayPos, maxOrder)
     Q = src.shape[0]
     ptr = np.zeros(Q + 1, dtype=np.int64)
@@ -1535,19 +1601,22 @@ def getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDe
         if n:
             L.check(lib.emagls_shoebox_components_dist(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3]),
                                                        _addr(dist)))
-        return ([np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)],
-                [np.ascontiguousarray(dist[ptr[q]:ptr[q + 1]]) for q in range(Q)])
+        res = ([np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)],
+               [np.ascontiguousarray(dist[ptr[q]:ptr[q + 1]]) for q in range(Q)])
+        return res + (_shoebox_emission(lib, dim, refl, pos, src, fs, maxDelay, mo, ptr),) if returnEmission else res
     if n:
         L.check(lib.emagls_shoebox_components(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3])))
-    return [np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)]
+    res = [np.ascontiguousarray(cols[:, ptr[q]:ptr[q + 1]].T) for q in range(Q)]
+    return (res, _shoebox_emission(lib, dim, refl, pos, src, fs, maxDelay, mo, ptr)) if returnEmission else res
 
 
-def getShoeboxImages(roomDim, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None):
+def getShoeboxImages(roomDim, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=None, returnEmission=False):
     """The image sources of a shoebox room without its walls (include/emagls.h, emagls_shoebox_images): every
     candidate within maxOrder and maxDelay, for walls that are reflection spectra.  Returns (components, exponents, paths), one list
     of Q arrays each: [J_q x 4] with the columns azi, zen, delay in samples and gain = 1 / distance -- the bits of
     getShoeboxComponents with all six coefficients 1 --, [J_q x 6] int32 exponents of the walls x=0, x=Lx, y=0, y=Ly, z=0, z=Lz, and
-    [J_q] distances in metres: the `sources`, `exponents` and `pathLength` of getArrayIrs."""
+    [J_q] distances in metres: the `sources`, `exponents` and `pathLength` of getArrayIrs.  With returnEmission a fourth list of
+    [J_q x 3] emission vectors, as getShoeboxComponents returns them."""
     dim, _refl, pos, src, mo = _room(roomDim, np.ones(6), sourcePos, arrayPos, maxOrder)
     Q = src.shape[0]
     ptr = np.zeros(Q + 1, dtype=np.int64)
@@ -1560,7 +1629,8 @@ def getShoeboxImages(roomDim, sourcePos, arrayPos, fs, maxDelay, *, maxOrder=Non
         L.check(lib.emagls_shoebox_images(*head, n, _addr(ptr), _addr(cols[0]), _addr(cols[1]), _addr(cols[2]), _addr(cols[3]), _addr(ex),
                                           _addr(path)))
     cut = lambda a: [np.ascontiguousarray(a[ptr[q]:ptr[q + 1]]) for q in range(Q)]   # noqa: E731
-    return cut(cols.T), cut(ex), cut(path)
+    res = cut(cols.T), cut(ex), cut(path)
+    return res + (_shoebox_emission(lib, dim, None, pos, src, fs, maxDelay, mo, ptr),) if returnEmission else res
 
 
 def wallReflectionSpectra(absorption, bandCentresHz, fs, nfft):
@@ -1599,7 +1669,8 @@ def airAttenuation(fs, nfft, temperatureC=20.0, relHumidityPercent=50.0, pressur
 
 
 def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, preDelay, micRadius, micGridAziZenRad, *, order=4,
-                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False, airAttenuation=None, waveModel="planeWave"):
+                    encoder=None, nfft=None, maxOrder=None, maxDelay=None, returnCounts=False, airAttenuation=None, waveModel="planeWave",
+                    sourceOrientation=None, directivity=None):
     """Impulse responses of the simulated rigid-sphere array in a shoebox room (include/emagls.h,
     emagls_array_room_irs): getArrayIrs(getShoeboxComponents(...), ...) bit for bit, with the components enumerated on the device
     and fed to the responses' kernels there.  The room as in getShoeboxComponents (the array's whole sphere inside it), the array
@@ -1611,7 +1682,10 @@ def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, pre
     repeated over the bins.  Then every image within maxOrder and maxDelay is a component (getShoeboxImages), also behind a wall of 0.
     waveModel (getSMAIRMatrix's parameter and default): 'planeWave', every image a plane wave at the array (a far-field model), or
     'pointSource' (emagls_array_room_irs_point), every image a point source at its distance: getArrayIrs with
-    distance= on the lists of getShoeboxComponents(returnDistance=True) or getShoeboxImages (its paths), bit for bit."""
+    distance= on the lists of getShoeboxComponents(returnDistance=True) or getShoeboxImages (its paths), bit for bit.
+    Directive sources (emagls_array_room_irs_directive): `directivity` and sourceOrientation as in getArrayIrs,
+    with every wall and wave model above; the emission vectors are the enumeration's (returnEmission of the list functions), and the
+    result is getArrayIrs on those lists, bit for bit."""
     if waveModel not in ("planeWave", "pointSource"):
         raise L.EmaglsError(L.ERR_ARG, "unknown waveModel %r: 'planeWave' or 'pointSource'" % (waveModel,))
     spectral = np.ndim(wallReflection) == 2 or airAttenuation is not None
@@ -1622,6 +1696,21 @@ def getArrayRoomIrs(roomDim, wallReflection, sourcePos, arrayPos, fs, irLen, pre
         maxDelay = nr - 1 - float(preDelay)
     out = np.zeros((Q, Cc, nr), dtype=np.complex128 if e_c else np.float64)
     counts = np.zeros(Q, dtype=np.int64)
+    if directivity is None and sourceOrientation is not None:
+        raise L.EmaglsError(L.ERR_ARG, "sourceOrientation comes with a directivity")
+    if directivity is not None:
+        n_fft = _nfft_for(nr, nfft)
+        P = n_fft // 2 + 1
+        w = np.asarray(wallReflection, dtype=np.float64)
+        w = _spectra("wallReflection", w, 6, P) if w.ndim == 2 else _vec(w, 6, "wallReflection")[0]
+        att = None if airAttenuation is None else _spectra("airAttenuation", airAttenuation, None, P)
+        Nd, coef, rot = _directive(directivity, sourceOrientation, Q, P)
+        L.check(L.load().emagls_array_room_irs_directive(float(fs), float(micRadius), int(order), _addr(maz), _addr(mzn), M, pe, 1 if e_c else 0, Cc,
+                                                         _addr(dim), _addr(w), 1 if w.ndim == 2 else 0, _addr(att), _addr(pos), Q, _addr(src),
+                                                         float(maxDelay), mo, 1 if waveModel == "pointSource" else 0, _addr(rot), Nd, _addr(coef),
+                                                         float(preDelay), n_fft, nr, _addr(counts), _addr(out)))
+        out = np.ascontiguousarray(out.transpose(0, 2, 1))
+        return (out, counts) if returnCounts else out
     if waveModel == "pointSource":
         n_fft = _nfft_for(nr, nfft)
         P = n_fft // 2 + 1

@@ -29,6 +29,9 @@
 // against one microphone per wave and against binary powers per surface in profiles/r27_room_spectral.md.  Per microphone the
 // operations and their order are those of the flat kernel with G_r w_r in the place of (g w)_r.
 //
+// POINT SOURCES (section 14) and SOURCE DIRECTIVITY (section 15) have main kernels of their own further down, each with a heading
+// that says what it adds; the kernels above them are not touched by either.
+//
 // The rest of the chain: air_modes_kernel (the factor (2n+1) on launch_modal_bn's output, real part in the last bin, and the
 // recurrence's coefficients), air_prepare_kernel (unit vectors, delays split into integer and fraction), and the inverse real
 // transform per (source, channel) with the encoder in its load: on the LDS passes of lds_fft.hpp up to nfft = 4096
@@ -473,6 +476,186 @@ __global__ void __launch_bounds__(256) air_point_kernel(AirArgsPoint a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// SOURCE DIRECTIVITY: component j left its real source along the unit vector e_j (room axes); in the frame
+// of source q, w_j = R_q^T e_j, and the component's gain gains the factor
+//   D_j(k) = sum_{i < Kd} c_{q,i}(k) Y_i(w_j),    Y the real basis of sh_basis_kernel<false>, Kd = (Nd + 1)^2.
+// air_emission_angles_kernel turns e_j into the angles of w_j, launch_sh_basis writes Yd [Kd][ncomp] from them (no second SH
+// evaluator), and the main kernel forms D for the bins of its wave AFTER the order loop, when the accumulators' operands are dead:
+// Kd steps of one per-lane load of Yd and one complex-by-real multiply-add per bin, the coefficients [Q][Kd][Pld] wave-uniform in
+// the lane = component form and per lane in the lane = source form.  D depends on neither microphone nor order, so the APT_M
+// microphones of a wave share it.  A kernel of its own with the point kernel's shape (APT_R bins, APT_M microphones per wave), in
+// both forms, the spectral gain and the point-source factor compile-time options; the kernels above are not touched.
+// ---------------------------------------------------------------------------------------------
+struct AirArgsDir : AirArgsPoint {
+    const double* Yd;      // [Kd][ncomp]
+    const cplx* dc;        // [Q][Kd][Pld]
+    int Kd;
+};
+
+// one thread per component: the source by bisection in ptr (ptr[q] <= j < ptr[q + 1]), then the angles of R_q^T e_j
+__global__ void __launch_bounds__(256) air_emission_angles_kernel(int64_t n, int64_t nsrc, const int64_t* __restrict__ ptr,
+                                                                 const double* __restrict__ emit, const double* __restrict__ rot,
+                                                                 double* __restrict__ azi, double* __restrict__ zen) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    int64_t lo = 0, hi = nsrc;
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (ptr[mid] <= j) lo = mid; else hi = mid;
+    }
+    const double ex = emit[3 * j], ey = emit[3 * j + 1], ez = emit[3 * j + 2];
+    double wx = ex, wy = ey, wz = ez;
+    if (rot) {
+        const double* __restrict__ R = rot + 9 * lo;   // the columns of R are the source's axes
+        wx = fma(R[6], ez, fma(R[3], ey, R[0] * ex));
+        wy = fma(R[7], ez, fma(R[4], ey, R[1] * ex));
+        wz = fma(R[8], ez, fma(R[5], ey, R[2] * ex));
+    }
+    azi[j] = atan2(wy, wx);
+    zen[j] = acos(fmin(1.0, fmax(-1.0, wz)));
+}
+
+#ifndef AIR_DIR_UNROLL
+#define AIR_DIR_UNROLL 4       // steps of the D loop in flight together: left rolled (1) the loop waits for each step's two loads before its
+                               // eight FMAs and costs twice as much at Nd = 8 (measured against 1 and 8 in profiles/r29_source_directivity.md);
+                               // the order of the additions, and so the bits, do not depend on it
+#endif
+// D[r] = sum_i c_i(k0 + r) Y_i of component j: y walks Yd + j by ncomp, c walks the source's coefficients + k0 by Pld
+__device__ __forceinline__ void air_directivity(const double* __restrict__ y, int64_t ncomp, const cplx* __restrict__ c, int64_t Pld, int Kd,
+                                                cplx (&D)[APT_R]) {
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) D[r] = mk(0.0, 0.0);
+#pragma unroll AIR_DIR_UNROLL
+    for (int i = 0; i < Kd; ++i, y += ncomp, c += Pld) {
+        const double yi = *y;
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) cfma(D[r], c[r], yi);
+    }
+}
+
+// one component's terms of the APT_R bins from k0 at the APT_M microphones of the wave, plane wave or (POINT) point source:
+// sum[i][r] += (G_r w_r) D_r acc[i][r], acc the order sum of the flat kernel or of air_point_component; dc: the coefficients of
+// the component's source at bin k0
+template <bool SPECTRAL, bool POINT>
+__device__ __forceinline__ void air_directive_component(const AirArgsDir& a, int k0, int64_t j, const cplx* __restrict__ dc,
+                                                        const double (&vx)[APT_M], const double (&vy)[APT_M], const double (&vz)[APT_M],
+                                                        cplx (&sum)[APT_M][APT_R]) {
+    const double ux = a.u[j], uy = a.u[a.ncomp + j], uz = a.u[2 * a.ncomp + j];
+    const double rho = POINT ? a.dist[j] : 1.0, t = POINT ? a.r / rho : 1.0, t2 = t * t;
+    double xm[APT_M], p0[APT_M], p1[APT_M];
+#pragma unroll
+    for (int i = 0; i < APT_M; ++i) {
+        const double x = fma(uz, vz[i], fma(uy, vy[i], ux * vx[i]));
+        xm[i] = POINT ? t * x : x;
+        p0[i] = 1.0; p1[i] = xm[i];
+    }
+    const cplx* __restrict__ b = (POINT ? a.bh : a.bn) + k0;
+    double x2[APT_R];
+    cplx g0[APT_R], g1[APT_R], acc[APT_M][APT_R];
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) {
+        if constexpr (POINT) {
+            const double x = ((double)(k0 + r) * a.kappa_step) * rho;
+            x2[r] = x * x;
+            g0[r] = mk(1.0, 0.0); g1[r] = mk(1.0, x);
+        }
+#pragma unroll
+        for (int i = 0; i < APT_M; ++i) acc[i][r] = b[r];   // n = 0
+    }
+    for (int n = 1; n <= a.N; ++n) {
+        b += a.Pld;
+        if constexpr (POINT) {
+            const double s = a.ginv[n];
+#pragma unroll
+            for (int r = 0; r < APT_R; ++r) {
+                const cplx c = b[r] * g1[r];
+#pragma unroll
+                for (int i = 0; i < APT_M; ++i) cfma(acc[i][r], c, p1[i]);
+                const double f = x2[r] * s;
+                const cplx g2 = mk(fma(-f, g0[r].x, g1[r].x), fma(-f, g0[r].y, g1[r].y));
+                g0[r] = g1[r]; g1[r] = g2;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < APT_R; ++r) {
+#pragma unroll
+                for (int i = 0; i < APT_M; ++i) cfma(acc[i][r], b[r], p1[i]);
+            }
+        }
+        const double ra = a.rec[2 * n], rb = POINT ? a.rec[2 * n + 1] * t2 : a.rec[2 * n + 1];
+#pragma unroll
+        for (int i = 0; i < APT_M; ++i) {
+            const double p2 = fma(ra * xm[i], p1[i], -(rb * p0[i]));
+            p0[i] = p1[i]; p1[i] = p2;
+        }
+    }
+    const unsigned di = (unsigned)a.dint[j];
+    const double df = a.dfrac[j], inv = 1.0 / (double)a.nfft, g = a.gain ? a.gain[j] : 1.0;
+    const unsigned ki = ((unsigned)k0 * di) & (unsigned)(a.nfft - 1);
+    cplx w, s;
+    sincospi(-2.0 * (((double)ki + (double)k0 * df) * inv), &w.y, &w.x);
+    sincospi(-2.0 * (((double)di + df) * inv), &s.y, &s.x);
+    double G[APT_R];
+    if (SPECTRAL) {
+        air_point_gains(a, k0, j, g, G);
+    } else {
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) G[r] = g;
+    }
+    cplx D[APT_R];
+    air_directivity(a.Yd + j, a.ncomp, dc, a.Pld, a.Kd, D);
+#pragma unroll
+    for (int r = 0; r < APT_R; ++r) {
+        const cplx gw = (G[r] * w) * D[r];
+#pragma unroll
+        for (int i = 0; i < APT_M; ++i) cfma(sum[i][r], gw, acc[i][r]);
+        w = w * s;
+    }
+}
+
+// both forms, the grid and the microphones of a wave as in air_point_kernel
+template <bool LANE_IS_SOURCE, bool SPECTRAL, bool POINT>
+__global__ void __launch_bounds__(256) air_directive_kernel(AirArgsDir a) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int m0 = (blockIdx.y * 4 + wave) * APT_M;
+    if (m0 >= a.M) return;
+    const int k0 = blockIdx.x * APT_R;
+    int q;
+    if (LANE_IS_SOURCE) {
+        const int i = blockIdx.z * 64 + lane;
+        if (i >= a.nlist) return;
+        q = a.list[i];
+    } else {
+        q = a.list[blockIdx.z];
+    }
+    const cplx* __restrict__ dc = a.dc + (int64_t)q * a.Kd * a.Pld + k0;
+    double vx[APT_M], vy[APT_M], vz[APT_M];
+    cplx sum[APT_M][APT_R];
+#pragma unroll
+    for (int i = 0; i < APT_M; ++i) {
+        const int m = m0 + i < a.M ? m0 + i : a.M - 1;
+        vx[i] = a.v[m]; vy[i] = a.v[a.M + m]; vz[i] = a.v[2 * a.M + m];
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) sum[i][r] = mk(0.0, 0.0);
+    }
+    const int64_t j1 = a.ptr[q + 1];
+    for (int64_t j = a.ptr[q] + (LANE_IS_SOURCE ? 0 : lane); j < j1; j += LANE_IS_SOURCE ? 1 : 64)
+        air_directive_component<SPECTRAL, POINT>(a, k0, j, dc, vx, vy, vz, sum);
+#pragma unroll
+    for (int i = 0; i < APT_M; ++i) {
+        if (m0 + i >= a.M) break;
+        cplx* out = a.H + ((int64_t)q * a.M + m0 + i) * a.Pld;
+#pragma unroll
+        for (int r = 0; r < APT_R; ++r) {
+            cplx t = LANE_IS_SOURCE ? sum[i][r] : wave_sum(sum[i][r]);
+            const int k = k0 + r;
+            if (k == a.P - 1) t.y = 0.0;   // the last bin's value is the real part of the sum
+            if ((LANE_IS_SOURCE || lane == 0) && k < a.P) out[k] = t;
+        }
+    }
+}
+
 // the encoder in a load: X(k) = sum_m enc(c, m) H(k, m), m ascending, accumulated from 0 with fma; the real and the imaginary part of
 // enc as separate chains.  enc_re null: X = H(:, c)
 struct AirEnc {
@@ -596,8 +779,29 @@ void launch_air_point_modes(int N, int P, int64_t Pld, double kr_step, void* bh,
     KERNEL_CHECK();
 }
 
+void launch_air_emission_angles(int64_t n, int64_t nsrc, const int64_t* ptr, const double* emit, const double* rot, double* azi, double* zen,
+                                hipStream_t st) {
+    if (n <= 0) return;
+    air_emission_angles_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, st>>>(n, nsrc, ptr, emit, rot, azi, zen);
+    KERNEL_CHECK();
+}
+
+template <bool SPECTRAL, bool POINT>
+static void air_directive_launches(AirArgsDir& a, const AirMain& m, hipStream_t st) {
+    air_main_launches(a, m, (unsigned)ceil_div(m.M, 4 * APT_M), air_directive_kernel<false, SPECTRAL, POINT>, air_directive_kernel<true, SPECTRAL, POINT>,
+                      st, APT_R);
+}
+
 void launch_air_main(const AirMain& m, hipStream_t st) {
-    if (m.dist) {                                      // point sources: one kernel, the spectral gain its option
+    if (m.dc) {                                        // source directivity: one kernel, spectral gain and point sources its options
+        AirArgsDir a{};
+        a.lnr = m.lnr; a.neg = m.neg; a.att = m.att; a.exp = m.exp; a.path = m.path; a.W = m.nsurf;
+        a.bh = (const cplx*)m.bh; a.ginv = m.ginv; a.dist = m.dist; a.r = m.mic_radius; a.kappa_step = m.kappa_step;
+        a.Yd = m.Yd; a.dc = (const cplx*)m.dc; a.Kd = m.Kd;
+        const bool spectral = m.nsurf > 0 || m.att;
+        if (m.dist) spectral ? air_directive_launches<true, true>(a, m, st) : air_directive_launches<false, true>(a, m, st);
+        else spectral ? air_directive_launches<true, false>(a, m, st) : air_directive_launches<false, false>(a, m, st);
+    } else if (m.dist) {                                     // point sources: one kernel, the spectral gain its option
         AirArgsPoint a{};
         a.lnr = m.lnr; a.neg = m.neg; a.att = m.att; a.exp = m.exp; a.path = m.path; a.W = m.nsurf;
         a.bh = (const cplx*)m.bh; a.ginv = m.ginv; a.dist = m.dist; a.r = m.mic_radius; a.kappa_step = m.kappa_step;

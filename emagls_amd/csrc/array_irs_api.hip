@@ -1,7 +1,8 @@
 // C ABI of the array impulse responses (include/emagls.h; DESIGN.md sections 11 to 14): emagls_array_irs from listed components,
 // emagls_shoebox_components and emagls_array_room_irs from a shoebox room, and their spectral forms (reflection spectra per surface
 // and air absorption: emagls_array_irs_spectral, emagls_shoebox_images, emagls_array_room_irs_spectral), and their point-source forms
-// (section 14: emagls_array_irs_point, emagls_shoebox_components_dist, emagls_array_room_irs_point).  Host arrays in, host array out; every argument is
+// (section 14: emagls_array_irs_point, emagls_shoebox_components_dist, emagls_array_room_irs_point), and the directive, oriented sources
+// of section 15 (emagls_array_irs_directive, emagls_shoebox_emission, emagls_array_room_irs_directive).  Host arrays in, host array out; every argument is
 // checked before the device is touched (a room call's scratch estimate, which needs the component count, after its count pass), and
 // every array operation runs in the kernels of array_irs.hip, shoebox.hip, modal.hip and fft.hip (the twiddles), with hipFFT's Z2D
 // above 4096 points (the precedent of decode.hip above 2048 taps).  The speed of sound and the simulation order are
@@ -109,6 +110,41 @@ struct AirSpectral {
     bool any() const { return nsurf > 0 || att; }
 };
 
+// source directivity of a call, checked: the order, the coefficients coef [nsrc][Kd][P] (interleaved complex)
+// and the rotations rot [nsrc][9] or null on the host; the emission vectors emit [ncomp][3] on the device
+constexpr int AIR_DIR_ORDER_MAX = 8;
+struct AirDirective {
+    int order = 0;
+    const double *coef = nullptr, *rot = nullptr;
+    const double* d_emit = nullptr;
+    bool any() const { return coef != nullptr; }
+    int Kd() const { return (order + 1) * (order + 1); }
+};
+
+// the rules of dir_order, dir_coef and src_rot: finite coefficients; proper rotations, max|R^T R - I| <= 1e-12 and det > 0
+AirDirective air_check_directive(const AirCall& c, int dir_order, const double* dir_coef, const double* src_rot) {
+    if (dir_order < 0) throw Error(EMAGLS_ERR_ARG, "dir_order must be non-negative");
+    if (dir_order > AIR_DIR_ORDER_MAX) throw Error(EMAGLS_ERR_UNSUPPORTED, "directivity orders above 8 are not supported");
+    AirDirective dv;
+    dv.order = dir_order; dv.coef = dir_coef; dv.rot = src_rot;
+    const int64_t ncoef = c.nsrc * dv.Kd() * c.P * 2;
+    for (int64_t i = 0; i < ncoef; ++i)
+        if (!std::isfinite(dir_coef[i])) throw Error(EMAGLS_ERR_ARG, "directivity coefficients must be finite");
+    for (int64_t q = 0; src_rot && q < c.nsrc; ++q) {
+        const double* R = src_rot + 9 * q;
+        double dev = 0.0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                const double g = R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j];   // (R^T R)(i, j)
+                dev = std::max(dev, std::fabs(g - (i == j ? 1.0 : 0.0)));
+            }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(dev <= 1e-12) || !(det > 0.0))
+            throw Error(EMAGLS_ERR_ARG, "src_rot of source " + std::to_string(q) + " is not a proper rotation (max|R^T R - I| <= 1e-12, det > 0)");
+    }
+    return dv;
+}
+
 // the rules of a point-source call's distances: finite and beyond the sphere; returns the largest
 double air_check_dist(const AirCall& c, const double* comp_dist, int64_t ncomp) {
     double far = 0.0;
@@ -143,12 +179,14 @@ void air_check_spectra(int64_t nsurf, const double* refl, const double* att, int
 
 // the device memory estimate of a call with ncomp components, nsurf surfaces and (air) an air term (in long double: the counts of a
 // refused call may overflow 64 bits); room: the enumeration's lists are counted too
-void air_check_scratch(const AirCall& c, int64_t ncomp, int nsurf = 0, bool air = false, bool point = false) {
+void air_check_scratch(const AirCall& c, int64_t ncomp, int nsurf = 0, bool air = false, bool point = false, int dir_kd = 0) {
+    // (directivity: Yd, the two angles and the emission vectors per component, the padded coefficient table and the rotations per source)
+    const long double dir = dir_kd > 0 ? (long double)ncomp * (8 * dir_kd + 40) + (long double)c.nsrc * ((long double)dir_kd * c.Pld * 16 + 72) : 0.0L;
     const long double spectral = nsurf > 0 || air ? (long double)(nsurf + 1) * (c.Pld + c.P) * 8 + (long double)c.Pld * 4 +
                                                         (long double)ncomp * (4 * nsurf + (air ? 8 : 0)) : 0.0L;
     // (point sources: the scaled table in the place of b', the reciprocals and the distances)
     const long double pt = point ? (long double)(c.N + 1) * 8 + (long double)ncomp * 8 : 0.0L;
-    const long double need = spectral + pt + (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
+    const long double need = spectral + pt + dir + (long double)c.nsrc * c.M * c.Pld * 16 + (long double)(c.N + 1) * c.Pld * 16 + (long double)ncomp * 52 +
                              (long double)c.nsrc * 12 + (long double)c.out_bytes +
                              (c.lds ? 0.0L : (c.enc ? (long double)c.rows * c.np * c.P * 16 : 0.0L) + (long double)c.rows * c.np * c.nfft * 8);
     if (need > (long double)AIR_SCRATCH_MAX)
@@ -158,7 +196,7 @@ void air_check_scratch(const AirCall& c, int64_t ncomp, int nsurf = 0, bool air 
 // stages 1 to 4 on components that are on the device: d_ptr [nsrc + 1] and its host copy h_ptr, d_azi, d_zen [ncomp], d_delay and
 // d_gain [ncomp] or null (zeros, ones); sp: the spectral gain, or none.  The result is copied to c.out and the stream synchronised.
 void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* d_ptr, const double* d_azi, const double* d_zen,
-             const double* d_delay, const double* d_gain, const AirSpectral& sp = AirSpectral()) {
+             const double* d_delay, const double* d_gain, const AirSpectral& sp = AirSpectral(), const AirDirective& dv = AirDirective()) {
     const int N = c.N, nfft = c.nfft, P = c.P, M = c.M, C = c.C, np = c.np;
     const int64_t nsrc = c.nsrc, nr = c.nr, Pld = c.Pld, rows = c.rows, ncomp = h_ptr[nsrc];
     const double* enc = (const double*)c.enc;
@@ -215,11 +253,31 @@ void air_run(Scratch& s, const AirCall& c, const int64_t* h_ptr, const int64_t* 
         launch_air_spectra(sp.nsurf, P, Pld, s.put_opt(sp.refl, (size_t)sp.nsurf * P), s.put_opt(sp.att, sp.att ? (size_t)P : 0), lnr, neg, att, s.st);
         m.nsurf = sp.nsurf; m.lnr = lnr; m.neg = neg; m.att = att; m.exp = sp.d_exp; m.path = sp.d_path;
     }
+    double *dir_tab = nullptr, *dir_ang = nullptr, *dir_Y = nullptr;
+    const double* dir_rot = nullptr;
+    if (dv.any()) {                                    // source directivity: the padded coefficients, room for the basis at the emission directions
+        const int Kd = dv.Kd();
+        cplx* dc = s.get<cplx>(sizeof(cplx) * (size_t)nsrc * Kd * Pld, true);
+        HIP_CHECK(hipMemcpy2DAsync(dc, sizeof(cplx) * (size_t)Pld, dv.coef, sizeof(cplx) * (size_t)P, sizeof(cplx) * (size_t)P, (size_t)nsrc * Kd,
+                                   hipMemcpyHostToDevice, s.st));
+        if (ncomp > 0) {
+            dir_tab = s.get<double>(sizeof(double) * sh_coeff_count(dv.order));
+            dir_ang = s.get<double>(sizeof(double) * 2 * (size_t)ncomp);
+            dir_Y = s.get<double>(sizeof(double) * (size_t)Kd * ncomp);
+            dir_rot = s.put_opt(dv.rot, (size_t)9 * nsrc);
+        }
+        m.Yd = dir_Y; m.dc = dc; m.Kd = Kd;
+    }
     cplx* H = s.get<cplx>(sizeof(cplx) * (size_t)nsrc * M * Pld);
     m.H = H;
-    // 3. the main kernel
+    // 3. the main kernel (and, inside the timed span, the basis pass of a directive call)
     EventPair ev;
     HIP_CHECK(hipEventRecord(ev.a, s.st));
+    if (dir_Y) {
+        launch_sh_coeff(dv.order, dir_tab, s.st);
+        launch_air_emission_angles(ncomp, nsrc, d_ptr, dv.d_emit, dir_rot, dir_ang, dir_ang + ncomp, s.st);
+        launch_sh_basis(dv.order, ncomp, dir_ang, dir_ang + ncomp, dir_tab, false, dir_Y, ncomp, s.st);
+    }
     launch_air_main(m, s.st);
     HIP_CHECK(hipEventRecord(ev.b, s.st));
     // 4. encoder and inverse real transform
@@ -311,7 +369,7 @@ struct Shoebox {
     const double* src = nullptr;
     uint64_t* mask = nullptr;
     int64_t *base = nullptr, *ptr = nullptr;
-    double *azi = nullptr, *zen = nullptr, *delay = nullptr, *gain = nullptr, *path = nullptr;
+    double *azi = nullptr, *zen = nullptr, *delay = nullptr, *gain = nullptr, *path = nullptr, *emit = nullptr;   // emit [total][3]: fill(.., .., true)
     int* exp = nullptr;                      // [total][6], with path: fill(true)
     std::vector<int64_t> h_ptr;
     EventPair ev_count, ev_write;
@@ -333,14 +391,16 @@ struct Shoebox {
         s.sync();
     }
     int64_t total() const { return h_ptr.back(); }
-    void fill(bool images = false, bool dist = false) {    // dist: path beside the flat lists (images has it anyway)
+    void fill(bool images = false, bool dist = false, bool emission = false) {    // dist: path beside the flat lists (images has it anyway)
         const size_t n = (size_t)total();
+        if (emission) emit = s.get<double>(sizeof(double) * 3 * n);
         azi = s.get<double>(sizeof(double) * n); zen = s.get<double>(sizeof(double) * n);
         delay = s.get<double>(sizeof(double) * n); gain = s.get<double>(sizeof(double) * n);
         if (images) exp = s.get<int>(sizeof(int) * 6 * n);
         if (images || dist) path = s.get<double>(sizeof(double) * n);
         HIP_CHECK(hipEventRecord(ev_write.a, s.st));
-        if (n && images) launch_shoebox_write_images(a, nsrc, src, mask, base, azi, zen, delay, gain, exp, path, s.st);
+        if (n && emission) launch_shoebox_write_emit(a, nsrc, src, mask, base, azi, zen, delay, gain, exp, path, emit, s.st);
+        else if (n && images) launch_shoebox_write_images(a, nsrc, src, mask, base, azi, zen, delay, gain, exp, path, s.st);
         else if (n && dist) launch_shoebox_write_dist(a, nsrc, src, mask, base, azi, zen, delay, gain, path, s.st);
         else if (n) launch_shoebox_write(a, nsrc, src, mask, base, azi, zen, delay, gain, s.st);
         HIP_CHECK(hipEventRecord(ev_write.b, s.st));
@@ -367,6 +427,18 @@ int64_t air_check_lists(const AirCall& c, const int64_t* comp_ptr, const double*
     for (int64_t j = 0; comp_gain && j < ncomp; ++j)
         if (!std::isfinite(comp_gain[j])) throw Error(EMAGLS_ERR_ARG, "component gains must be finite");
     return ncomp;
+}
+
+// the spectral gain's arguments of a listed call, checked
+void air_check_gain_lists(const AirCall& c, int64_t ncomp, int64_t nsurf, const double* surf_refl, const int32_t* comp_exp, const double* air_atten,
+                          const double* comp_path) {
+    if ((air_atten == nullptr) != (comp_path == nullptr)) throw Error(EMAGLS_ERR_ARG, "air_atten and comp_path must both be given or both be NULL");
+    air_check_spectra(nsurf, surf_refl, air_atten, c.P, "surf_refl");
+    if (nsurf > 0 && ncomp > 0 && !comp_exp) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_exp");
+    for (int64_t i = 0; i < ncomp * nsurf; ++i)
+        if (comp_exp[i] < 0) throw Error(EMAGLS_ERR_ARG, "component exponents must be non-negative");
+    for (int64_t j = 0; comp_path && j < ncomp; ++j)
+        if (!(comp_path[j] >= 0.0) || !std::isfinite(comp_path[j])) throw Error(EMAGLS_ERR_ARG, "component path lengths must be non-negative and finite");
 }
 
 }  // namespace
@@ -400,13 +472,7 @@ extern "C" int emagls_array_irs_spectral(double fs, double mic_radius, int order
         if (nfft_in == 0) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the spectra have nfft / 2 + 1 bins");
         const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
         const int64_t ncomp = air_check_lists(c, comp_ptr, comp_azi, comp_zen, comp_delay, comp_gain);
-        if ((air_atten == nullptr) != (comp_path == nullptr)) throw Error(EMAGLS_ERR_ARG, "air_atten and comp_path must both be given or both be NULL");
-        air_check_spectra(nsurf, surf_refl, air_atten, c.P, "surf_refl");
-        if (nsurf > 0 && ncomp > 0 && !comp_exp) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_exp");
-        for (int64_t i = 0; i < ncomp * nsurf; ++i)
-            if (comp_exp[i] < 0) throw Error(EMAGLS_ERR_ARG, "component exponents must be non-negative");
-        for (int64_t j = 0; comp_path && j < ncomp; ++j)
-            if (!(comp_path[j] >= 0.0) || !std::isfinite(comp_path[j])) throw Error(EMAGLS_ERR_ARG, "component path lengths must be non-negative and finite");
+        air_check_gain_lists(c, ncomp, nsurf, surf_refl, comp_exp, air_atten, comp_path);
         air_check_scratch(c, ncomp, (int)nsurf, air_atten != nullptr);
         // ---- device (nsurf = 0 and no air: the flat kernels, the bits of emagls_array_irs)
         Scratch s;
@@ -433,13 +499,7 @@ extern "C" int emagls_array_irs_point(double fs, double mic_radius, int order, c
         const int64_t ncomp = air_check_lists(c, comp_ptr, comp_azi, comp_zen, comp_delay, comp_gain);
         if (ncomp > 0 && !comp_dist) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_dist (distances are given for all components or, in emagls_array_irs, for none)");
         air_check_point_range(c, air_check_dist(c, comp_dist, ncomp));
-        if ((air_atten == nullptr) != (comp_path == nullptr)) throw Error(EMAGLS_ERR_ARG, "air_atten and comp_path must both be given or both be NULL");
-        air_check_spectra(nsurf, surf_refl, air_atten, c.P, "surf_refl");
-        if (nsurf > 0 && ncomp > 0 && !comp_exp) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_exp");
-        for (int64_t i = 0; i < ncomp * nsurf; ++i)
-            if (comp_exp[i] < 0) throw Error(EMAGLS_ERR_ARG, "component exponents must be non-negative");
-        for (int64_t j = 0; comp_path && j < ncomp; ++j)
-            if (!(comp_path[j] >= 0.0) || !std::isfinite(comp_path[j])) throw Error(EMAGLS_ERR_ARG, "component path lengths must be non-negative and finite");
+        air_check_gain_lists(c, ncomp, nsurf, surf_refl, comp_exp, air_atten, comp_path);
         air_check_scratch(c, ncomp, (int)nsurf, air_atten != nullptr, true);
         // ---- device
         Scratch s;
@@ -611,6 +671,133 @@ extern "C" int emagls_array_room_irs_point(double fs, double mic_radius, int ord
         if (spectral) { sp.nsurf = 6; sp.refl = walls; sp.att = air_atten; sp.d_exp = box.exp; sp.d_path = air_atten ? box.path : nullptr; }
         sp.d_dist = box.path;                          // (shoebox_check: every image lies beyond the sphere)
         air_run(s, c, box.h_ptr.data(), box.ptr, box.azi, box.zen, box.delay, box.gain, sp);
+        box.keep_time();
+        for (int64_t q = 0; comp_count && q < nsrc; ++q) comp_count[q] = box.h_ptr[q + 1] - box.h_ptr[q];
+    });
+}
+
+// ---- source directivity
+extern "C" int emagls_array_irs_directive(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                          const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr,
+                                          const double* comp_azi, const double* comp_zen, const double* comp_delay, const double* comp_gain,
+                                          int64_t nsurf, const double* surf_refl, const int32_t* comp_exp, const double* air_atten,
+                                          const double* comp_path, const double* comp_dist, const double* comp_emit, const double* src_rot,
+                                          int dir_order, const double* dir_coef, double pre_delay, int64_t nfft_in, int64_t nr, void* out) {
+    if (!dir_coef) {                                   // no directivity: the existing entries and their bits
+        if (comp_emit || src_rot || dir_order != 0)
+            return guarded_call([] { throw Error(EMAGLS_ERR_ARG, "without dir_coef, comp_emit and src_rot must be NULL and dir_order 0"); });
+        if (comp_dist)
+            return emagls_array_irs_point(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, comp_ptr, comp_azi, comp_zen,
+                                          comp_delay, comp_gain, nsurf, surf_refl, comp_exp, air_atten, comp_path, comp_dist, pre_delay, nfft_in, nr, out);
+        if (nsurf != 0 || surf_refl || comp_exp || air_atten || comp_path)
+            return emagls_array_irs_spectral(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, comp_ptr, comp_azi,
+                                             comp_zen, comp_delay, comp_gain, nsurf, surf_refl, comp_exp, air_atten, comp_path, pre_delay, nfft_in, nr, out);
+        return emagls_array_irs(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, comp_ptr, comp_azi, comp_zen, comp_delay,
+                                comp_gain, pre_delay, nfft_in, nr, out);
+    }
+    return guarded_call([&] {
+        // ---- arguments (nothing below this block fails on what the caller passed)
+        if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
+        if (nfft_in == 0) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the directivity coefficients have nfft / 2 + 1 bins");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        const int64_t ncomp = air_check_lists(c, comp_ptr, comp_azi, comp_zen, comp_delay, comp_gain);
+        const AirDirective dv = air_check_directive(c, dir_order, dir_coef, src_rot);
+        if (ncomp > 0 && !comp_emit) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_emit (dir_coef needs the emission vector of every component)");
+        for (int64_t j = 0; j < ncomp; ++j) {
+            const double* e = comp_emit + 3 * j;
+            if (!(std::fabs((e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) - 1.0) <= 1e-12))
+                throw Error(EMAGLS_ERR_ARG, "emission vectors must have unit length (component " + std::to_string(j) + ")");
+        }
+        if (comp_dist) air_check_point_range(c, air_check_dist(c, comp_dist, ncomp));
+        air_check_gain_lists(c, ncomp, nsurf, surf_refl, comp_exp, air_atten, comp_path);
+        air_check_scratch(c, ncomp, (int)nsurf, air_atten != nullptr, comp_dist != nullptr, dv.Kd());
+        // ---- device
+        Scratch s;
+        const size_t n = (size_t)ncomp;
+        AirSpectral sp;
+        sp.nsurf = (int)nsurf; sp.refl = surf_refl; sp.att = air_atten;
+        sp.d_exp = nsurf > 0 ? s.put_opt(comp_exp, n * (size_t)nsurf) : nullptr;
+        sp.d_path = air_atten ? s.put_opt(comp_path, n) : nullptr;
+        if (comp_dist) sp.d_dist = s.put(n ? comp_dist : &c.mic_radius, std::max<size_t>(n, 1));   // (never null: it selects the kernel)
+        AirDirective d = dv;
+        d.d_emit = s.put_opt(comp_emit, 3 * n);
+        const int64_t* d_ptr = s.put(comp_ptr, (size_t)nsrc + 1);
+        air_run(s, c, comp_ptr, d_ptr, s.put_opt(comp_azi, n), s.put_opt(comp_zen, n), s.put_opt(comp_delay, n), s.put_opt(comp_gain, n), sp, d);
+    });
+}
+
+extern "C" int emagls_shoebox_emission(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc, const double* src_pos,
+                                       double fs, double max_delay, int max_order, int64_t capacity, int64_t* comp_ptr, double* comp_emit) {
+    return guarded_call([&] {
+        if (!comp_ptr) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_ptr");
+        if (capacity < 0) throw Error(EMAGLS_ERR_ARG, "invalid shape: capacity");
+        if (capacity > 0 && !comp_emit) throw Error(EMAGLS_ERR_ARG, "null pointer: comp_emit (capacity 0 for a count-only call)");
+        // (wall_refl null: the images of emagls_shoebox_images, nothing dropped; else the keep rule of emagls_shoebox_components)
+        const ShoeboxArgs a = shoebox_check(room_dim, wall_refl ? wall_refl : SBX_ONES, array_pos, nsrc, src_pos, fs, 0.0, max_delay, max_order);
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        std::copy(box.h_ptr.begin(), box.h_ptr.end(), comp_ptr);
+        const size_t n = (size_t)box.total();
+        if (n > 0 && box.total() <= capacity) {
+            box.fill(false, false, true);
+            HIP_CHECK(hipMemcpyAsync(comp_emit, box.emit, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s.st));
+            s.sync();
+        }
+        box.keep_time();
+    });
+}
+
+extern "C" int emagls_array_room_irs_directive(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                               const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
+                                               int wall_is_spectral, const double* air_atten, const double* array_pos, int64_t nsrc,
+                                               const double* src_pos, double max_delay, int max_order, int point_source, const double* src_rot,
+                                               int dir_order, const double* dir_coef, double pre_delay, int64_t nfft_in, int64_t nr,
+                                               int64_t* comp_count, void* out) {
+    if (point_source != 0 && point_source != 1) return guarded_call([] { throw Error(EMAGLS_ERR_ARG, "point_source must be 0 or 1"); });
+    if (!dir_coef) {                                   // no directivity: the existing entries and their bits
+        if (src_rot || dir_order != 0) return guarded_call([] { throw Error(EMAGLS_ERR_ARG, "without dir_coef, src_rot must be NULL and dir_order 0"); });
+        if (point_source)
+            return emagls_array_room_irs_point(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, room_dim, wall_refl,
+                                               wall_is_spectral, air_atten, array_pos, nsrc, src_pos, max_delay, max_order, pre_delay, nfft_in, nr,
+                                               comp_count, out);
+        if (wall_is_spectral)
+            return emagls_array_room_irs_spectral(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, room_dim, wall_refl, air_atten,
+                                                  array_pos, nsrc, src_pos, max_delay, max_order, pre_delay, nfft_in, nr, comp_count, out);
+        if (air_atten) return guarded_call([] { throw Error(EMAGLS_ERR_ARG, "air_atten without dir_coef needs wall spectra (wall_is_spectral) or point_source"); });
+        return emagls_array_room_irs(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, room_dim, wall_refl, array_pos, nsrc,
+                                     src_pos, max_delay, max_order, pre_delay, nfft_in, nr, comp_count, out);
+    }
+    return guarded_call([&] {
+        const bool spectral = wall_is_spectral != 0 || air_atten != nullptr, point = point_source != 0;
+        if (nfft_in == 0) throw Error(EMAGLS_ERR_ARG, "nfft must be given: the directivity coefficients have nfft / 2 + 1 bins");
+        const AirCall c = air_check(fs, mic_radius, order, mic_azi, mic_zen, nmics, enc, enc_is_complex, nch, nsrc, pre_delay, nfft_in, nr, out);
+        if (!wall_refl) throw Error(EMAGLS_ERR_ARG, "null pointer: wall_refl");
+        const ShoeboxArgs a = shoebox_check(room_dim, spectral ? SBX_ONES : wall_refl, array_pos, nsrc, src_pos, fs, mic_radius, max_delay, max_order);
+        const AirDirective dv = air_check_directive(c, dir_order, dir_coef, src_rot);
+        std::vector<double> rep;                       // six coefficients with air: repeated over the bins
+        const double* walls = wall_refl;
+        if (spectral && !wall_is_spectral) {
+            rep.resize((size_t)6 * c.P);
+            for (int w = 0; w < 6; ++w) std::fill(rep.begin() + (size_t)w * c.P, rep.begin() + (size_t)(w + 1) * c.P, wall_refl[w]);
+            walls = rep.data();
+        }
+        if (spectral) air_check_spectra(6, walls, air_atten, c.P, "wall_refl");
+        if (max_delay + pre_delay > (double)(c.nfft - 1)) throw Error(EMAGLS_ERR_ARG, "max_delay plus pre_delay beyond nfft - 1 would wrap");
+        if (point) air_check_point_range(c, max_delay * C_SOUND / fs);
+        const int nsurf = spectral ? 6 : 0;
+        air_check_scratch(c, 0, nsurf, air_atten != nullptr, point, dv.Kd());
+        Scratch s;
+        Shoebox box(s, a, nsrc);
+        box.count(src_pos);
+        air_check_scratch(c, box.total(), nsurf, air_atten != nullptr, point, dv.Kd());
+        box.fill(spectral, point, true);
+        AirSpectral sp;
+        if (spectral) { sp.nsurf = 6; sp.refl = walls; sp.att = air_atten; sp.d_exp = box.exp; sp.d_path = air_atten ? box.path : nullptr; }
+        if (point) sp.d_dist = box.path;
+        AirDirective d = dv;
+        d.d_emit = box.emit;
+        air_run(s, c, box.h_ptr.data(), box.ptr, box.azi, box.zen, box.delay, box.gain, sp, d);
         box.keep_time();
         for (int64_t q = 0; comp_count && q < nsrc; ++q) comp_count[q] = box.h_ptr[q + 1] - box.h_ptr[q];
     });

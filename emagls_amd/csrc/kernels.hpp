@@ -399,8 +399,16 @@ struct AirMain {
     const double* dist;                    // [ncomp] distances rho_j > mic_radius
     const void* bh; const double* ginv;    // launch_air_point_modes' tables [N+1][Pld] complex, [N+1]
     double mic_radius, kappa_step;         // r; kappa_k = k kappa_step
+    // source directivity: dc null is the kernels above
+    const double* Yd;                      // [Kd][ncomp] real SH of the emission directions in the sources' frames
+    const void* dc;                        // [Q][Kd][Pld] complex coefficients, zeros beyond P
+    int Kd;                                // (Nd + 1)^2 <= 81
 };
 void launch_air_main(const AirMain& m, hipStream_t st);
+// azimuth and zenith of w_j = R_q^T e_j: emit [n][3] unit vectors in room axes, rot [nsrc][9] row-major or null (identity), the
+// component's source from ptr [nsrc + 1]
+void launch_air_emission_angles(int64_t n, int64_t nsrc, const int64_t* ptr, const double* emit, const double* rot, double* azi, double* zen,
+                                hipStream_t st);
 // the scaled mode table of the point-source kernels: bh [N+1][Pld] = b'_n(k) (2n-1)!! / (i kappa_k r)^n (zeros beyond P, the last bin
 // the scaled form of Re b'_n), ginv[n] = 1 / (4 n^2 - 1); kr_step = kappa_step r
 void launch_air_point_modes(int N, int P, int64_t Pld, double kr_step, void* bh, double* ginv, hipStream_t st);
@@ -435,6 +443,9 @@ void launch_shoebox_write_dist(const ShoeboxArgs& a, int64_t nsrc, const double*
 // the same with the six exponents exp [n][6] (x0, x1, y0, y1, z0, z1) and the distance path [n] of every component (section 13)
 void launch_shoebox_write_images(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                                  double* zen, double* delay, double* gain, int* exp, double* path, hipStream_t st);
+// any of the three forms above (exp and path given, path alone, neither) with the emission vectors emit [n][3] beside them (section 15)
+void launch_shoebox_write_emit(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                               double* zen, double* delay, double* gain, int* exp, double* path, double* emit, hipStream_t st);
 
 // ---- host_pools.hip: process-wide stream pool (streams are recycled, never destroyed: see StreamPool in host_internal.hpp)
 hipStream_t pool_stream_take();

@@ -18,7 +18,7 @@
 //   scan    one workgroup: exclusive scan of the tile counts (64-bit) -> tile_base [ntiles + 1] and comp_ptr [nsrc + 1]
 //   write   reads the mask -- it does not decide again --: place = tile base + the population counts of the tile's lower waves'
 //           words + the population count of the lane's lower bits in its own word; evaluates the definition once more and writes
-//           azi, zen, delay, gain there
+//           azi, zen, delay, gain there (and, by its form, exponents, path, and the emission vectors of DESIGN.md section 15)
 // No atomics: the place of a component is a function of the masks alone, so equal calls give equal lists in equal order, and the
 // list of source q is the list of the call with that source alone.
 #include "kernels.hpp"
@@ -122,6 +122,7 @@ __global__ void __launch_bounds__(SBX_TILE) shoebox_write_kernel(ShoeboxArgs a, 
                                                                 const int64_t* __restrict__ base, double* __restrict__ azi,
                                                                 double* __restrict__ zen, double* __restrict__ delay, double* __restrict__ gain,
                                                                 int* __restrict__ exp, double* __restrict__ path) {
+    // (shoebox_write_emit_kernel below restates this body: a change here is a change there)
     const int64_t tile = blockIdx.x, q = tile / a.tiles, c = (tile % a.tiles) * SBX_TILE + threadIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t* __restrict__ mw = mask + tile * (SBX_TILE / 64);
@@ -146,6 +147,44 @@ __global__ void __launch_bounds__(SBX_TILE) shoebox_write_kernel(ShoeboxArgs a, 
         }
     }
     if constexpr (PATH) path[r] = o.d;
+}
+
+// The forms that also write emit [base[ntiles]][3]: the unit vector along which the component's ray left the
+// real source -- the image's ray to the array, -v / d, mirrored back through the walls it crossed, e_i = -(1 - 2 p_i) v_i / d.  A
+// kernel of its own with the body of shoebox_write_kernel restated: the forms above keep their text, so that their instruction
+// streams stay what they were (through a shared function the IMAGES form came out with other registers).
+template <bool IMAGES, bool PATH>
+__global__ void __launch_bounds__(SBX_TILE) shoebox_write_emit_kernel(ShoeboxArgs a, const double* __restrict__ src, const uint64_t* __restrict__ mask,
+                                                                     const int64_t* __restrict__ base, double* __restrict__ azi,
+                                                                     double* __restrict__ zen, double* __restrict__ delay, double* __restrict__ gain,
+                                                                     int* __restrict__ exp, double* __restrict__ path, double* __restrict__ emit) {
+    const int64_t tile = blockIdx.x, q = tile / a.tiles, c = (tile % a.tiles) * SBX_TILE + threadIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t* __restrict__ mw = mask + tile * (SBX_TILE / 64);
+    const uint64_t m = mw[wave];
+    if (!((m >> lane) & 1)) return;   // (a set bit implies c < ncand)
+    int64_t r = base[tile] + __popcll(m & (((uint64_t)1 << lane) - 1));
+    for (int w = 0; w < wave; ++w) r += __popcll(mw[w]);
+    SbxCand o;
+    (void)shoebox_eval(a, src + 3 * q, c, o);
+    azi[r] = atan2(o.vy, o.vx);
+    zen[r] = acos(o.vz / o.d);
+    delay[r] = o.tau;
+    gain[r] = o.gain;
+    if constexpr (IMAGES) {
+        int64_t t = c >> 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int n = (int)(i < 2 ? t % a.W[i] : t) - a.B[i], par = (int)(c >> i) & 1;
+            if (i < 2) t /= a.W[i];
+            exp[6 * r + 2 * i] = abs(n - par);
+            exp[6 * r + 2 * i + 1] = abs(n);
+        }
+    }
+    if constexpr (PATH) path[r] = o.d;
+    emit[3 * r] = ((c & 1) ? o.vx : -o.vx) / o.d;
+    emit[3 * r + 1] = ((c & 2) ? o.vy : -o.vy) / o.d;
+    emit[3 * r + 2] = ((c & 4) ? o.vz : -o.vz) / o.d;
 }
 
 void launch_shoebox_count(const ShoeboxArgs& a, int64_t nsrc, const double* src, uint64_t* mask, int* cnt, hipStream_t st) {
@@ -173,6 +212,15 @@ void launch_shoebox_write_dist(const ShoeboxArgs& a, int64_t nsrc, const double*
 void launch_shoebox_write_images(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
                                  double* zen, double* delay, double* gain, int* exp, double* path, hipStream_t st) {
     shoebox_write_kernel<true><<<(unsigned)(nsrc * a.tiles), SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, exp, path);
+    KERNEL_CHECK();
+}
+
+void launch_shoebox_write_emit(const ShoeboxArgs& a, int64_t nsrc, const double* src, const uint64_t* mask, const int64_t* base, double* azi,
+                               double* zen, double* delay, double* gain, int* exp, double* path, double* emit, hipStream_t st) {
+    const unsigned grid = (unsigned)(nsrc * a.tiles);
+    if (exp) shoebox_write_emit_kernel<true, true><<<grid, SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, exp, path, emit);
+    else if (path) shoebox_write_emit_kernel<false, true><<<grid, SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, nullptr, path, emit);
+    else shoebox_write_emit_kernel<false, false><<<grid, SBX_TILE, 0, st>>>(a, src, mask, base, azi, zen, delay, gain, nullptr, nullptr, emit);
     KERNEL_CHECK();
 }
 

@@ -819,7 +819,7 @@ int emagls_array_irs_spectral(double fs, double mic_radius, int order, const dou
  * The search box is |n_i| <= floor(max_delay 343 / fs / (2 L_i)) + 1, and <= floor((max_order + 1) / 2) with an order limit; a call
  * with more than 2^28 candidates (8 prod_i (2 B_i + 1) per source, times nsrc) is EMAGLS_ERR_UNSUPPORTED.
  * Every argument is checked before the device is touched.  Plane-wave components are a far-field model: the images as point sources at
- * their distances are emagls_array_room_irs_point below; source directivity is not built.  Frequency-dependent walls and air
+ * their distances are emagls_array_room_irs_point below; directive sources: emagls_array_room_irs_directive.  Frequency-dependent walls and air
  * absorption: the spectral entries below.
  *
  * emagls_shoebox_components: comp_ptr [nsrc + 1] (host) is always written; comp_azi, comp_zen, comp_delay, comp_gain [capacity] are
@@ -875,8 +875,8 @@ int emagls_shoebox_kernel_time(double* ms);
  * N log10(x) - log10((2N-1)!!) >= 300 is EMAGLS_ERR_UNSUPPORTED (beyond a kilometre at N = 85, no room at N <= 60).  Encoder, transform,
  * layout, the fixed summation order, the per-source form, equal bits for equal calls and for source q alone: emagls_array_irs.  Every
  * argument is checked before the device is touched; the 24 GiB estimate counts the table and the distances;
- * emagls_array_irs_kernel_time covers these launches.  Not built: +inf distances mixed into a call, source directivity, open or
- * directional spheres, device-pointer outputs. */
+ * emagls_array_irs_kernel_time covers these launches.  Not built: +inf distances mixed into a call, open or directional spheres,
+ * device-pointer outputs.  (Source directivity: emagls_array_irs_directive below.) */
 int emagls_array_irs_point(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
                            const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr, const double* comp_azi,
                            const double* comp_zen, const double* comp_delay, const double* comp_gain, int64_t nsurf,
@@ -896,6 +896,48 @@ int emagls_array_room_irs_point(double fs, double mic_radius, int order, const d
                                 const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
                                 int wall_is_spectral, const double* air_atten, const double* array_pos, int64_t nsrc, const double* src_pos,
                                 double max_delay, int max_order, double pre_delay, int64_t nfft, int64_t nr, int64_t* comp_count, void* out);
+
+/* ---- array impulse responses of directive, oriented sources (this project's) ----
+ * Next to the arguments of emagls_array_irs_point (comp_dist may be NULL: plane waves) a call may carry
+ *   dir_order = Nd, 0 <= Nd <= 8 (above: EMAGLS_ERR_UNSUPPORTED), Kd = (Nd + 1)^2, one order for all sources (pad with zeros);
+ *   dir_coef [nsrc][Kd][P], interleaved complex doubles, P = nfft / 2 + 1 with nfft given (0: EMAGLS_ERR_ARG): the coefficients
+ *     c_{q,i}(k) of source q's directivity in the REAL basis of emagls_get_sh (index n^2 + n + m, orthonormal, Y_0 = 1 / sqrt(4 pi),
+ *     m > 0 cosine, m < 0 sine); finite;
+ *   src_rot [nsrc][9], row-major R_q whose columns are the source's front (x), left (y) and up (z) axes in room axes; NULL: identity;
+ *     max|R^T R - I| > 1e-12 or det < 0 is EMAGLS_ERR_ARG;
+ *   comp_emit [ncomp][3], the unit vector e_j in room axes along which the ray of component j left the real source;
+ *     | |e|^2 - 1 | > 1e-12 is EMAGLS_ERR_ARG.
+ * With w_j = R_q^T e_j, azi = atan2(w_y, w_x), zen = acos(min(1, max(-1, w_z))):  D_j(k) = sum_{i < Kd} c_{q,i}(k) Y_i(azi_j, zen_j),
+ * and the gain G_j(k) of emagls_array_irs_spectral (g_j without surfaces and air) becomes G_j(k) D_j(k), inside the main kernel, for
+ * plane-wave components and point sources alike.  Delays, pre_delay, encoder, transform, layout, the last bin (Re beta_n and the real
+ * part of the sum), the fixed summation order without atomics, the per-source form, equal bits for equal calls and for source q alone:
+ * emagls_array_irs.  dir_coef = NULL requires comp_emit = NULL, src_rot = NULL and dir_order = 0 and is the call of
+ * emagls_array_irs_point (comp_dist given), emagls_array_irs_spectral (any of its five arguments given) or emagls_array_irs, with
+ * its bits.  Every argument is checked before the device is touched; the 24 GiB estimate counts the basis values, the angles and
+ * the padded coefficient table; emagls_array_irs_kernel_time covers the basis pass and the main kernel.  Not built: microphone
+ * directivity, open or directional spheres, an orientation per component or over time, Nd > 8, coefficients in the complex basis,
+ * device-pointer inputs or outputs. */
+int emagls_array_irs_directive(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                               const void* enc, int enc_is_complex, int64_t nch, int64_t nsrc, const int64_t* comp_ptr, const double* comp_azi,
+                               const double* comp_zen, const double* comp_delay, const double* comp_gain, int64_t nsurf,
+                               const double* surf_refl, const int32_t* comp_exp, const double* air_atten, const double* comp_path,
+                               const double* comp_dist, const double* comp_emit, const double* src_rot, int dir_order, const double* dir_coef,
+                               double pre_delay, int64_t nfft, int64_t nr, void* out);
+/* The emission vectors of a shoebox room's components, comp_emit [capacity x 3]: for candidate (n, p) with v and d as above, the
+ * image's ray to the array, -v / d, mirrored back through the walls it crossed: e_i = -(1 - 2 p_i) v_i / d (the direct sound: from the
+ * source to the array).  They do not depend on the source's orientation.  wall_refl NULL: the keep rule and rows of
+ * emagls_shoebox_images; otherwise those of emagls_shoebox_components.  comp_ptr and the count-only convention as there. */
+int emagls_shoebox_emission(const double* room_dim, const double* wall_refl, const double* array_pos, int64_t nsrc, const double* src_pos,
+                            double fs, double max_delay, int max_order, int64_t capacity, int64_t* comp_ptr, double* comp_emit);
+/* The room with directive sources, no component crossing the bus: the arguments of emagls_array_room_irs_point, point_source (0: plane
+ * waves, the lists of emagls_array_room_irs or, with spectra or air, emagls_array_room_irs_spectral; 1: point sources), and src_rot,
+ * dir_order, dir_coef as above.  Source q of a call gives the bits of emagls_array_irs_directive on the lists of the matching list
+ * entries and emagls_shoebox_emission.  dir_coef = NULL (src_rot NULL, dir_order 0): the matching entry without directivity. */
+int emagls_array_room_irs_directive(double fs, double mic_radius, int order, const double* mic_azi, const double* mic_zen, int64_t nmics,
+                                    const void* enc, int enc_is_complex, int64_t nch, const double* room_dim, const double* wall_refl,
+                                    int wall_is_spectral, const double* air_atten, const double* array_pos, int64_t nsrc, const double* src_pos,
+                                    double max_delay, int max_order, int point_source, const double* src_rot, int dir_order,
+                                    const double* dir_coef, double pre_delay, int64_t nfft, int64_t nr, int64_t* comp_count, void* out);
 
 /* ---- plan API: inputs resident in HBM, repeated execution (benchmarks, batches) ------------- */
 

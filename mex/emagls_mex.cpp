@@ -66,6 +66,44 @@ std::vector<int32_t> exponents_of(const double* m, mwSize J, mwSize W) {
         }
     return v;
 }
+// source directivity: a MATLAB matrix [numSources Kd x P], real or complex, whose row q Kd + i holds c_{q,i}(k)
+// (the .m wrappers build it), as [numSources][Kd][P] interleaved complex; returns Nd
+int directivity_of(const mxArray* a, mwSize Q, mwSize P, std::vector<double>& coef) {
+    const mwSize rows = mxGetM(a), Kd = rows / Q;
+    if (!mxIsDouble(a) || mxGetN(a) != P || rows != Kd * Q || Kd < 1)
+        mexErrMsgIdAndTxt("eMagLS:arg", "directivity must be [numSources*Kd x %d] (nfft / 2 + 1 bins) with Kd coefficients per source", (int)P);
+    const int Nd = (int)std::floor(std::sqrt((double)Kd) + 0.5) - 1;
+    if ((mwSize)((Nd + 1) * (Nd + 1)) != Kd) mexErrMsgIdAndTxt("eMagLS:arg", "directivity holds %d coefficients per source and bin, which is not a square (Nd + 1)^2", (int)Kd);
+    const bool cplx = mxIsComplex(a);
+    const double* d = (const double*)in_ptr(a);
+    coef.assign((size_t)2 * rows * P, 0.0);
+    for (mwSize r = 0; r < rows; ++r)
+        for (mwSize k = 0; k < P; ++k) {
+            const size_t src = r + (size_t)rows * k, dst = (size_t)r * P + k;
+            coef[2 * dst] = cplx ? d[2 * src] : d[src];
+            if (cplx) coef[2 * dst + 1] = d[2 * src + 1];
+        }
+    return Nd;
+}
+// sourceOrientation as the gateway takes it: [numSources x 9], row q = R_q row by row
+std::vector<double> rotations_of(const mxArray* a, mwSize Q) {
+    if (mxGetM(a) != Q || mxGetN(a) != 9) mexErrMsgIdAndTxt("eMagLS:arg", "sourceOrientation must be [numSources x 9] (each rotation matrix row by row)");
+    return rows_of(dbl(a, "sourceOrientation"), Q, 9);
+}
+// the emission vectors of a room's lists (emagls_shoebox_emission; refl null: the images) as a MATLAB matrix [J x 3]
+mxArray* shoebox_emission(const double* dim, const double* refl, const double* pos, mwSize Q, const double* src, double fs, double max_delay,
+                          int max_order, mwSize J) {
+    std::vector<int64_t> ptr(Q + 1);
+    std::vector<double> e(3 * (size_t)J);
+    if (J) {
+        const int rc = emagls_shoebox_emission(dim, refl, pos, (int64_t)Q, src, fs, max_delay, max_order, (int64_t)J, ptr.data(), e.data());
+        if (rc) fail(rc);
+    }
+    mxArray* out = mxCreateDoubleMatrix(J, 3, mxREAL);
+    for (mwSize j = 0; j < J; ++j)
+        for (int i = 0; i < 3; ++i) mxGetDoubles(out)[j + J * i] = e[3 * j + i];
+    return out;
+}
 // a caller-evaluated SH matrix must be real / complex like the basis asked for
 const void* basis_matrix(const mxArray* a, int basis, mwSize rows, mwSize cols, const char* what) {
     if (!mxIsDouble(a) || mxGetM(a) != rows || mxGetN(a) != cols) mexErrMsgIdAndTxt("eMagLS:arg", "%s must be a %d x %d double matrix", what, (int)rows, (int)cols);
@@ -235,7 +273,8 @@ void at_exit() {
 // emagls_mex('ch', N, aziRad, basisType)        emagls_mex('smair', order, fs, irLen, oversamplingFactor, smaRadius, micAzi, micZen, ...)
 // emagls_mex('shf', micRadius, order, fs, len)                  [wShf, W_Shf] = ...
 // emagls_mex('adf', micRadius, micAzi, micZen, order, fs, len, shDefinition[, Yhi])
-// array responses: 'array_irs', 'shoebox_components', 'shoebox_images', 'array_room_irs' (their argument lists stand at their branches)
+// array responses: 'array_irs', 'shoebox_components', 'shoebox_images', 'array_room_irs' (their argument lists stand at their branches;
+// directive sources, DESIGN.md section 15, are further arguments and outputs of the four)
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     static bool registered = false;
     if (!registered) { mexAtExit(at_exit); registered = true; }
@@ -849,7 +888,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         // point sources, a fifteenth argument, [] or absent for none: distance [J] in metres, one per component
         auto extra = [&](int i) { return nrhs > i && given(i); };
         if (extra(15) && mxGetNumberOfElements(prhs[15]) != J) mexErrMsgIdAndTxt("eMagLS:arg", "distance must have one element per component (%d)", (int)J);
-        if (extra(11) || extra(12) || extra(13) || extra(14) || extra(15)) {
+        // directive sources, three further arguments, [] or absent for none: emission [J x 3], sourceOrientation
+        // [numSources x 9] ([]: the room's axes), directivity [numSources Kd x P]
+        if ((extra(16) || extra(17)) && !extra(18)) mexErrMsgIdAndTxt("eMagLS:arg", "emission and sourceOrientation come with a directivity");
+        if (extra(18) && J && (!extra(16) || mxGetM(prhs[16]) != J || mxGetN(prhs[16]) != 3))
+            mexErrMsgIdAndTxt("eMagLS:arg", "a directivity needs emission [J x 3], one unit vector per component (%d)", (int)J);
+        if (extra(11) || extra(12) || extra(13) || extra(14) || extra(15) || extra(18)) {
             if (extra(11) != extra(12)) mexErrMsgIdAndTxt("eMagLS:arg", "surfaceReflection and exponents must both be given or both be []");
             if (extra(13) != extra(14)) mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation and pathLength must both be given or both be []");
             const int64_t nfft = spectral_nfft(given(10) ? prhs[10] : nullptr, nr);
@@ -865,6 +909,21 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             if (extra(13) && (mxGetNumberOfElements(prhs[13]) != P || mxGetNumberOfElements(prhs[14]) != (J ? J : mxGetNumberOfElements(prhs[14]))))
                 mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation must have %d elements (nfft / 2 + 1 bins) and pathLength one per component", (int)P);
             const double *att = extra(13) ? dbl(prhs[13], "airAttenuation") : nullptr, *len = extra(13) ? dbl(prhs[14], "pathLength") : nullptr;
+            if (extra(18)) {
+                std::vector<double> coef, rot, emit;
+                const int Nd = directivity_of(prhs[18], Q, P, coef);
+                if (extra(17)) rot = rotations_of(prhs[17], Q);
+                if (J) emit = rows_of(dbl(prhs[16], "emission"), J, 3);
+                const int rc = emagls_array_irs_directive(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
+                                                          given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
+                                                          comps ? comps + J : nullptr, comps ? comps + 2 * J : nullptr, comps ? comps + 3 * J : nullptr,
+                                                          (int64_t)W, W ? refl.data() : nullptr, ex.empty() ? nullptr : ex.data(), att, len,
+                                                          extra(15) ? dbl(prhs[15], "distance") : nullptr, J ? emit.data() : nullptr,
+                                                          extra(17) ? rot.data() : nullptr, Nd, coef.data(), mxGetScalar(prhs[5]), nfft, (int64_t)nr,
+                                                          out_ptr(plhs[0]));
+                if (rc) fail(rc);
+                return;
+            }
             const int rc = extra(15)
                 ? emagls_array_irs_point(mxGetScalar(prhs[3]), mxGetScalar(prhs[6]), (int)mxGetScalar(prhs[8]), mics, mics + M, (int64_t)M,
                                          given(9) ? in_ptr(prhs[9]) : nullptr, ec ? 1 : 0, (int64_t)Cc, (int64_t)Q, ptr.data(), comps,
@@ -917,6 +976,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         for (int i = 0; i < 3; ++i)
             if (nlhs > i + 1) plhs[i + 1] = outs[i]; else mxDestroyArray(outs[i]);
         if (rc) fail(rc);
+        if (nlhs > 4) plhs[4] = shoebox_emission(dim, nullptr, pos, Q, src.data(), fs, max_delay, max_order, J);   // emission [J x 3] (section 15)
         return;
     }
     if (c == "shoebox_components" || c == "array_room_irs") {
@@ -977,6 +1037,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
             for (mwSize q = 0; q <= Q; ++q) mxGetDoubles(plhs[0])[q] = (double)ptr[q];
             if (nlhs > 1) plhs[1] = comps; else mxDestroyArray(comps);
             if (rc) fail(rc);
+            if (nlhs > 3) plhs[3] = shoebox_emission(dim, refl, pos, Q, src.data(), fs, max_delay, max_order, J);   // emission [J x 3] (section 15)
             return;
         }
         if (mxGetN(prhs[9]) != 2) mexErrMsgIdAndTxt("eMagLS:arg", "micGridAziZenRad must be [n x 2] (azimuth, zenith)");
@@ -993,7 +1054,29 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         const mwSize od[3] = {nr, Cc, Q};
         plhs[0] = mxCreateNumericArray(3, od, mxDOUBLE_CLASS, ec ? mxCOMPLEX : mxREAL);
         std::vector<int64_t> counts(Q);
-        if (point) {
+        // directive sources, two further arguments: sourceOrientation [numSources x 9] ([]: the room's axes) and
+        // directivity [numSources Kd x P] ([] or absent: none); with every wall and wave model above
+        const bool rotated = nrhs > 17 && given(17), directive = nrhs > 18 && given(18);
+        if (rotated && !directive) mexErrMsgIdAndTxt("eMagLS:arg", "sourceOrientation comes with a directivity");
+        if (directive) {
+            const int64_t nfft = spectral_nfft(given(12) ? prhs[12] : nullptr, nr);
+            const mwSize P = (mwSize)(nfft / 2 + 1);
+            const bool spectra = mxGetNumberOfElements(prhs[2]) != 6;
+            std::vector<double> walls, coef, rot;
+            if (spectra) {
+                if (mxGetM(prhs[2]) != 6 || mxGetN(prhs[2]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "wallReflection must be [6 x %d] (nfft / 2 + 1 bins)", (int)P);
+                walls = rows_of(refl, 6, P);
+            }
+            if (air && mxGetNumberOfElements(prhs[15]) != P) mexErrMsgIdAndTxt("eMagLS:arg", "airAttenuation must have %d elements (nfft / 2 + 1 bins)", (int)P);
+            const int Nd = directivity_of(prhs[18], Q, P, coef);
+            if (rotated) rot = rotations_of(prhs[17], Q);
+            const int rc = emagls_array_room_irs_directive(fs, mxGetScalar(prhs[8]), (int)mxGetScalar(prhs[10]), mics, mics + M, (int64_t)M,
+                                                           given(11) ? in_ptr(prhs[11]) : nullptr, ec ? 1 : 0, (int64_t)Cc, dim, spectra ? walls.data() : refl,
+                                                           spectra ? 1 : 0, air ? dbl(prhs[15], "airAttenuation") : nullptr, pos, (int64_t)Q, src.data(),
+                                                           max_delay, max_order, point ? 1 : 0, rotated ? rot.data() : nullptr, Nd, coef.data(), pre, nfft,
+                                                           (int64_t)nr, counts.data(), out_ptr(plhs[0]));
+            if (rc) fail(rc);
+        } else if (point) {
             const int64_t nfft = spectral_nfft(given(12) ? prhs[12] : nullptr, nr);
             const mwSize P = (mwSize)(nfft / 2 + 1);
             const bool spectra = mxGetNumberOfElements(prhs[2]) != 6;

@@ -18,8 +18,15 @@ function irs = getArrayIrs(sources, fs, irLen, preDelay, micRadius, micGridAziZe
 %   point sources (DESIGN.md section 14; emagls_array_irs_point): distance ([]), a cell like sources of [J_q x 1] arrays in metres (or
 %             [Q x 1] for the [Q x 2] form), every value finite and greater than micRadius, for all components or for none.  The
 %             order-n term of a component then carries the near-field factor F_n(kappa*rho); delay and gain stay the caller's
+%   directive sources (DESIGN.md section 15; emagls_array_irs_directive): directivity ([]), [Q x Kd x P] real or complex coefficients of
+%             each source's directivity per bin in the real basis of getSH(Nd, ., 'real'), Kd = (Nd + 1)^2, Nd <= 8 ([Q x Kd] or a vector
+%             [Kd] is repeated over bins and sources; firstOrderDirectivity makes first-order patterns); emission, a cell like sources of
+%             [J_q x 3] unit vectors in room axes along which each component's ray left the real source ([Q x 3] for the [Q x 2] form;
+%             the further output of getShoeboxComponents / getShoeboxImages); sourceOrientation ([]: the room's axes), [3 x 3 x Q]
+%             rotation matrices whose columns are each source's front, left and up axes, or [Q x 2] = (azimuth, zenith) of the front axis
 %   irs       [irLen x numChannels x Q] (complex with a complex encoder): irs(:, :, q) is the rir of sourceFieldStream
-p = struct('order', 4, 'encoder', [], 'nfft', [], 'surfaceReflection', [], 'exponents', [], 'airAttenuation', [], 'pathLength', [], 'distance', []);
+p = struct('order', 4, 'encoder', [], 'nfft', [], 'surfaceReflection', [], 'exponents', [], 'airAttenuation', [], 'pathLength', [], 'distance', [], ...
+    'emission', [], 'sourceOrientation', [], 'directivity', []);
 for i = 1:2:numel(varargin)
     if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
     p.(varargin{i}) = varargin{i + 1};
@@ -60,6 +67,23 @@ if ~isempty(p.distance)
     end
     if numel(dists) ~= size(comps, 1); error('eMagLS:arg', 'distances are given for all components of a call or for none'); end
 end
+emit = [];
+rot = [];
+coef = [];
+if isempty(p.directivity) && (~isempty(p.emission) || ~isempty(p.sourceOrientation))
+    error('eMagLS:arg', 'emission and sourceOrientation come with a directivity');
+end
+if ~isempty(p.directivity)
+    if ~iscell(p.emission); p.emission = num2cell(double(p.emission), 2); end
+    if numel(p.emission) ~= Q; error('eMagLS:arg', 'emission must hold one array per source'); end
+    emit = zeros(0, 3);
+    for q = 1:Q
+        emit = [emit; reshape(double(p.emission{q}), [], 3)]; %#ok<AGROW>
+    end
+    nfft = double(p.nfft);
+    if isempty(nfft); nfft = min(65536, max(8, 2^nextpow2(2 * double(irLen)))); end
+    [rot, coef] = emaglsDirectiveArgs(p.sourceOrientation, p.directivity, Q, nfft / 2 + 1);
+end
 irs = emagls_mex('array_irs', compPtr, comps, double(fs), double(irLen), double(preDelay), double(micRadius), double(micGridAziZenRad), ...
-    double(p.order), double(p.encoder), double(p.nfft), double(p.surfaceReflection), exps, double(p.airAttenuation(:)), paths, dists);
+    double(p.order), double(p.encoder), double(p.nfft), double(p.surfaceReflection), exps, double(p.airAttenuation(:)), paths, dists, emit, rot, coef);
 end

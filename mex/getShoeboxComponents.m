@@ -1,4 +1,4 @@
-function [sources, distances] = getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, varargin)
+function [sources, distances, emission] = getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, varargin)
 % The image sources of a shoebox room as plane-wave components at the array's centre, enumerated on the MI355X library (DESIGN.md
 % section 12; include/emagls.h, emagls_shoebox_components): Allen & Berkley's image model with frequency-independent walls.
 %   sources = getShoeboxComponents(roomDim, wallReflection, sourcePos, arrayPos, fs, maxDelay, 'maxOrder', n)
@@ -12,6 +12,8 @@ function [sources, distances] = getShoeboxComponents(roomDim, wallReflection, so
 %                   `sources` of getArrayIrs
 %   distances       (second output, on request) cell of Q arrays [J_q x 1], the components' distances in metres: the 'distance' of
 %                   getArrayIrs (DESIGN.md section 14)
+%   emission        (third output, on request) cell of Q arrays [J_q x 3]: the unit vectors in room axes along which the components'
+%                   rays left the real source, the 'emission' of getArrayIrs (DESIGN.md section 15)
 p = struct('maxOrder', []);
 for i = 1:2:numel(varargin)
     if ~isfield(p, varargin{i}); error('eMagLS:arg', 'unknown option "%s"', varargin{i}); end
@@ -20,7 +22,9 @@ end
 if size(sourcePos, 2) ~= 3; error('eMagLS:arg', 'sourcePos must be [Q x 3]'); end
 args = {'shoebox_components', double(roomDim(:)), double(wallReflection(:)), double(sourcePos), double(arrayPos(:)), double(fs), ...
     double(maxDelay), double(p.maxOrder)};
-if nargout > 1
+if nargout > 2
+    [compPtr, comps, dists, emit] = emagls_mex(args{:});
+elseif nargout > 1
     [compPtr, comps, dists] = emagls_mex(args{:});
 else
     [compPtr, comps] = emagls_mex(args{:});
@@ -28,8 +32,10 @@ end
 Q = size(sourcePos, 1);
 sources = cell(Q, 1);
 distances = cell(Q, 1);
+emission = cell(Q, 1);
 for q = 1:Q
     sources{q} = comps(compPtr(q) + 1:compPtr(q + 1), :);
     if nargout > 1; distances{q} = dists(compPtr(q) + 1:compPtr(q + 1)); end
+    if nargout > 2; emission{q} = emit(compPtr(q) + 1:compPtr(q + 1), :); end
 end
 end

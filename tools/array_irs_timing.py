@@ -35,6 +35,14 @@ point-source response lies from the plane-wave one.  The table of profiles/r28_p
 AIR_POINT_BINS / AIR_POINT_MICS is run through EMAGLS_LIB_PATH.
 
     python tools/array_irs_timing.py --point [reps] [out.md]
+
+With --directive: the main kernel on the same two room shapes with directive sources (emagls_array_room_irs_directive, DESIGN.md section
+15) at Nd = 1, 4 and 8 -- plane waves with flat walls, with flat spectra and air, and point sources -- next to the three undirected
+kernels, alternating in one process after warm-up calls, at least five repetitions each: medians, extremes, the ratio to the undirected
+kernel of the same model and to the flat kernel, and the operation-count estimate.  The table of profiles/r29_source_directivity.md; a variant built with other
+AIR_POINT_BINS / AIR_POINT_MICS or with AIR_DIR_UNROLL is run through EMAGLS_LIB_PATH, on the first room alone with rooms = 1.
+
+    python tools/array_irs_timing.py --directive [reps] [out.md] [rooms: 1/2]
 """
 import ctypes as C
 import os
@@ -230,7 +238,64 @@ def main_point(argv):
             f.write(text + "\n")
 
 
+def main_directive(argv):
+    import emagls_amd as E
+    from emagls_amd import _lib as L
+    from oracle import emagls_oracle as O
+    from tools.csrc_hash import csrc_sha16
+    reps = max(int(argv[0]) if argv else 5, 5)
+    out = argv[1] if len(argv) > 1 else None
+    mics_per_wave = 4                              # (the estimate's; the kept AIR_POINT_MICS)
+    rng = np.random.default_rng(19)
+    mics = random_dirs(rng, 32)
+    room, beta, src, pos, pre = (5.2, 4.1, 2.9), (0.9, 0.85, 0.8, 0.75, 0.7, 0.6), (1.3, 2.2, 1.1), (3.4, 1.7, 1.6), 64.0
+    N = O.simulation_order(4, FS, RADIUS)
+    lines = ["Kernel sources: csrc_sha16 %s; library %s.  Simulation order N = %d, 32 microphones, one source turned by a random rotation, random "
+             "complex coefficients per bin; the forms alternate in one process, %d calls each after 2 warm-up calls each; device-event time of the "
+             "main kernel (emagls_array_irs_kernel_time; a directive call's span includes its basis pass).  Estimate: 1 + (2 Kd + 4) / (2 (N + 1) x %d "
+             "microphones per wave), over the flat kernel." % (csrc_sha16(), os.path.basename(L.LIB_PATH), N, reps, mics_per_wave), "",
+             "| max_delay | nfft | components | form | Nd | main kernel ms: median | min | max | over its undirected kernel | over flat | estimate |",
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    ms = C.c_double(0.0)
+    q, _ = np.linalg.qr(rng.standard_normal((3, 3)))
+    R = (q if np.linalg.det(q) > 0 else q * np.array([1.0, 1.0, -1.0]))[None]
+    shapes = ((6000.0, 8192, 8192), (24000.0, 65536, 32768))[:int(argv[2]) if len(argv) > 2 else 2]
+    for max_delay, nfft, ir_len in shapes:
+        P = nfft // 2 + 1
+        walls, air = np.repeat(np.array(beta)[:, None], P, axis=1), E.airAttenuation(FS, nfft)
+        base = [("plane waves, flat", beta, None, "planeWave"), ("plane waves, flat spectra and air", walls, air, "planeWave"),
+                ("point sources, flat", beta, None, "pointSource")]
+        forms = [(name, w, a, m, None) for name, w, a, m in base]
+        for Nd in (1, 4, 8):
+            coef = rng.standard_normal((1, (Nd + 1) ** 2, P)) + 1j * rng.standard_normal((1, (Nd + 1) ** 2, P))
+            forms += [(name, w, a, m, coef) for name, w, a, m in base]
+        call = lambda w, a, m, c: E.getArrayRoomIrs(room, w, src, pos, FS, ir_len, pre, RADIUS, mics, nfft=nfft, maxDelay=max_delay,   # noqa: E731
+                                                    airAttenuation=a, returnCounts=True, waveModel=m, directivity=c,
+                                                    sourceOrientation=None if c is None else R)
+        times = [[] for _ in forms]
+        for i in range(2 + reps):
+            for f, (_name, w, a, m, c) in enumerate(forms):
+                _res, counts = call(w, a, m, c)
+                L.check(L.load().emagls_array_irs_kernel_time(C.byref(ms)))
+                if i >= 2:
+                    times[f].append(ms.value)
+        med = [float(np.median(t)) for t in times]
+        for f, (name, _w, _a, _m, c) in enumerate(forms):
+            Kd = 0 if c is None else c.shape[1]
+            est = "" if c is None else "%.2f" % (1.0 + (2.0 * Kd + 4.0) / (2.0 * (N + 1) * mics_per_wave))
+            lines.append("| %d | %d | %d | %s | %s | %.3f | %.3f | %.3f | %.3f | %.3f | %s |" %
+                         (max_delay, nfft, counts[0], name, "" if c is None else str(int(round(np.sqrt(Kd))) - 1), med[f], np.min(times[f]), np.max(times[f]),
+                          med[f] / med[f % 3], med[f] / med[0], est))
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if out:
+        with open(out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--directive":
+        return main_directive(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--point":
         return main_point(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--room":
