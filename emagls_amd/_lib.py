@@ -48,7 +48,7 @@ class DebugFactorArgs(C.Structure):
                 ("Xd", C.c_void_p), ("xd_stride", c_i64), ("Tn", C.c_void_p), ("tn_cplx", C.c_int), ("bn", C.c_void_p), ("nOrders", C.c_int),
                 ("reg_mode", C.c_int), ("reg_c", C.c_double), ("tol_dim", C.c_double), ("Hq", C.c_void_p), ("ldHq", c_i64),
                 ("ls_end", C.c_int), ("hq_conj", C.c_int), ("phases", C.c_int), ("path", C.c_int), ("Z", C.c_void_p), ("sv", C.c_void_p),
-                ("sweeps", C.c_void_p), ("N", C.c_void_p), ("R2", C.c_void_p), ("tau", C.c_void_p), ("W", C.c_void_p)]
+                ("sweeps", C.c_void_p), ("N", C.c_void_p), ("R2", C.c_void_p), ("tau", C.c_void_p), ("W", C.c_void_p), ("leaf_rows", C.c_int)]
 
 
 DEBUG_SENTINEL_BITS = 0x7ff8dead0000beef
@@ -70,6 +70,7 @@ SYMBOLS = {
     "emagls_debug_synth_operand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, c_i64, C.c_int, C.c_void_p, C.c_void_p]),
     "emagls_debug_synth_cosines": (C.c_int, [C.c_void_p, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "emagls_debug_factor": (C.c_int, [C.POINTER(DebugFactorArgs)]),
+    "emagls_debug_wa_yri": (C.c_int, [C.c_void_p, c_i64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_i64, C.c_int, C.c_void_p]),
     "emagls_debug_factor_gram": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     "emagls_debug_gram": (C.c_int, [C.c_void_p, c_i64, C.c_int, c_i64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

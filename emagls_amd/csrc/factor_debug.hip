@@ -1,5 +1,6 @@
-// Debug entries of the per-bin factor chain (emagls_debug_factor, emagls_debug_factor_gram): the product's own launchers -- launch_factor,
-// launch_wa_factor and launch_factor_jacobi_gram, with their dispatch and their refusals -- on matrices the caller supplies, so that a test
+// Debug entries of the per-bin factor chain (emagls_debug_factor, emagls_debug_factor_gram, emagls_debug_wa_yri): the product's own
+// launchers -- launch_factor, launch_wa_factor, launch_wa_factor_tiled (with launch_wa_ls behind them), launch_factor_jacobi_gram and
+// launch_wa_yri, with their dispatch and their refusals -- on matrices the caller supplies, so that a test
 // can hold Z_k, the singular values and M_k against a factorisation of higher precision shape by shape.  No kernel is launched from here
 // and no dispatch is repeated here: an entry validates, allocates, copies, calls the launcher, synchronises, copies back and frees.
 #include "../../include/emagls.h"
@@ -16,23 +17,29 @@ using debug::sentinel;
 
 void factor_debug(const emagls_debug_factor_args& g) {
     const int S = g.S, C = g.C, ldS = g.ldS, nbins = g.nbins, kb0 = g.kb0, P = g.P;
-    const bool dense = g.Xd != nullptr, wide = g.path == 1;
+    const bool dense = g.Xd != nullptr, tiled = g.path == 2, wide = g.path == 1 || tiled;
     if (!g.Z) throw Error(1, "debug factor: Z is required");
     if (dense == (g.Tn != nullptr)) throw Error(1, "debug factor: exactly one of Xd (dense) and Tn (assembled) is given");
-    if (g.path != 0 && g.path != 1) throw Error(1, "debug factor: path is 0 (factor.hip) or 1 (wide_array.hip)");
+    if (g.path < 0 || g.path > 2) throw Error(1, "debug factor: path is 0 (factor.hip), 1 (wide_array.hip) or 2 (wide_array.hip, tiled)");
     if (g.phases != 3 && g.phases != 12) throw Error(1, "debug factor: phases is 3 (one call) or 12 (phase 1, then phase 2)");
-    if (S < 1 || C < 1 || C > 64 || ldS < S || ldS > 4096) throw Error(1, "debug factor: 1 <= S <= ldS <= 4096 and 1 <= C <= 64");
+    if (tiled) {
+        if (S < 1 || C < 1 || C > 32 || ldS < S || ldS > 16384 || nbins < 1 || nbins > 8)
+            throw Error(1, "debug factor: the tiled path takes 1 <= S <= ldS <= 16384, 1 <= C <= 32 and 1 <= nbins <= 8");
+    } else if (S < 1 || C < 1 || C > 64 || ldS < S || ldS > 4096) throw Error(1, "debug factor: 1 <= S <= ldS <= 4096 and 1 <= C <= 64");
     if (nbins < 1 || nbins > 4096 || kb0 < 0 || P < kb0 + nbins || P > 8192) throw Error(1, "debug factor: 1 <= nbins <= 4096 and kb0 + nbins <= P <= 8192");
     if (g.reg_mode != 0 && g.reg_mode != 1) throw Error(1, "debug factor: reg_mode is 0 (clip at reg_c s_max) or 1 (pinv tolerance)");
     if (!(g.reg_c >= 0.0) || !(g.reg_c <= 1.0) || !(g.tol_dim >= 0.0)) throw Error(1, "debug factor: 0 <= reg_c <= 1 and tol_dim >= 0");
     if (dense && (kb0 != 0 || (g.xd_stride != 0 && g.xd_stride != (int64_t)C * ldS))) throw Error(1, "debug factor: dense input has kb0 = 0 and xd_stride 0 or C ldS");
     if (!dense && (!g.bn || g.nOrders < 1 || g.nOrders > 1024)) throw Error(1, "debug factor: assembled input needs bn and 1 <= nOrders <= 1024");
-    if (g.Hq && (!g.W || g.ldHq < S || g.ldHq > 8192 || g.ls_end < 0 || g.ls_end > P)) throw Error(1, "debug factor: Hq needs W, S <= ldHq <= 8192 and 0 <= ls_end <= P");
-    if (wide && (!dense || g.Hq || g.reg_mode != 0 || g.phases != 3 || ldS % 64 != 0))
-        throw Error(1, "debug factor: the wide path takes dense input, reg_mode 0, phases 3, no Hq, and ldS a multiple of 64");
+    if (g.Hq && (!g.W || g.ldHq < S || g.ldHq > 16384 || g.ls_end < 0 || g.ls_end > P)) throw Error(1, "debug factor: Hq needs W, S <= ldHq <= 16384 and 0 <= ls_end <= P");
+    if (wide && (!dense || g.reg_mode != 0 || g.phases != 3 || ldS % 64 != 0 || (g.Hq && g.hq_conj)))
+        throw Error(1, "debug factor: the wide paths take dense input, reg_mode 0, phases 3, hq_conj 0, and ldS a multiple of 64");
+    if (g.leaf_rows != 0 && (!tiled || g.leaf_rows < 1024 || g.leaf_rows > 4096)) throw Error(1, "debug factor: leaf_rows is 0, or 1024 ... 4096 on the tiled path");
+    const WaTiling til = tiled ? wa_tiling(S, C, nbins, g.leaf_rows) : WaTiling{};   // (the cutting rule is the launcher's; it refuses a leaf shorter than C)
     const size_t csz = (size_t)C * ldS, cc = (size_t)C * C;
     const size_t nz = (wide ? (size_t)nbins : (size_t)P) * csz;
-    if ((nz + 2 * (size_t)nbins * csz + (dense ? 0 : (size_t)g.nOrders * csz)) * sizeof(cplx) > ((size_t)1 << 30)) throw Error(1, "debug factor: more than 1 GiB of device memory");
+    if ((nz + 2 * (size_t)nbins * csz + (dense ? 0 : (size_t)g.nOrders * csz) + (g.Hq ? (size_t)2 * P * g.ldHq : 0)) * sizeof(cplx) + til.bytes > ((size_t)1 << 30))
+        throw Error(1, "debug factor: more than 1 GiB of device memory");
 
     fill_sentinel(g.Z, 2 * (size_t)nbins * csz);
     if (g.W) fill_sentinel(g.W, 2 * (size_t)2 * P * C);
@@ -53,7 +60,20 @@ void factor_debug(const emagls_debug_factor_args& g) {
         cplx* dB = b.get<cplx>(sizeof(cplx) * (size_t)nbins * csz);
         for (int i = 0; i < nbins; ++i)
             HIP_CHECK(hipMemcpy(dB + (size_t)i * csz, static_cast<const cplx*>(g.Xd) + (size_t)i * g.xd_stride, csz * sizeof(cplx), hipMemcpyHostToDevice));
-        launch_wa_factor(dB, dV, S, C, ldS, nbins, g.reg_c, dtau, dR2, dN, dsv, dsw, dZ, nullptr);
+        if (tiled) {
+            void* ws = filled<double>(b, til.bytes / sizeof(double), sentinel());
+            launch_wa_factor_tiled(dB, dV, S, C, ldS, nbins, g.reg_c, dtau, dR2, dN, dsv, dsw, dZ, ws, nullptr, g.leaf_rows);
+        } else {
+            launch_wa_factor(dB, dV, S, C, ldS, nbins, g.reg_c, dtau, dR2, dN, dsv, dsw, dZ, nullptr);
+        }
+        if (g.Hq) {
+            // the least-squares rows as the designs form them behind these factors: Hc [2][nbins][ldHq], Z in the place of Y_reg_inv
+            cplx* dH = copy<cplx>(b, g.Hq, (size_t)2 * nbins * g.ldHq);
+            cplx* dW = filled<cplx>(b, (size_t)2 * P * C, sentinel());
+            launch_wa_ls(dH, g.ldHq, nbins, dZ, ldS, S, C, P, 0, std::min(g.ls_end, nbins), dW, nullptr);
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(g.W, dW, (size_t)2 * P * C * sizeof(cplx), hipMemcpyDeviceToHost));
+        }
     } else {
         FactorArgs a{};
         a.S = S; a.C = C; a.ldS = ldS; a.kb0 = kb0; a.P = P;
@@ -125,9 +145,29 @@ void factor_gram_debug(const void* A, int nbins, int C, const int* route, int jr
     HIP_CHECK(hipMemcpy(status, fg.status, 4 * sizeof(int), hipMemcpyDeviceToHost));
 }
 
+void wa_yri_debug(const double* Q, int64_t ldQ, const void* Z, int S, int C, int ldS, int D, int64_t ldD, int nbins, void* Yri) {
+    if (!Q || !Z || !Yri) throw Error(1, "null pointer");
+    if (C < 1 || C > 64 || S < 1 || ldS < S || ldS > 16384 || ldQ < S || ldQ > 16384) throw Error(1, "debug wa_yri: 1 <= C <= 64, 1 <= S <= ldS <= 16384 and S <= ldQ <= 16384");
+    if (D < 1 || ldD < D || ldD > 65536 || nbins < 1 || nbins > 4096) throw Error(1, "debug wa_yri: 1 <= D <= ldD <= 65536 and 1 <= nbins <= 4096");
+    const size_t nq = (size_t)D * ldQ, nz = (size_t)nbins * C * ldS, ny = (size_t)nbins * C * ldD;
+    if (nq * sizeof(double) + (nz + ny) * sizeof(cplx) > ((size_t)1 << 30)) throw Error(1, "debug wa_yri: more than 1 GiB of device memory");
+    fill_sentinel(Yri, 2 * ny);
+    Scratch b;
+    const double* dQ = copy<double>(b, Q, nq);
+    const cplx* dZ = copy<cplx>(b, Z, nz);
+    cplx* dY = filled<cplx>(b, ny, sentinel());
+    launch_wa_yri(dQ, ldQ, dZ, S, C, ldS, D, ldD, nbins, dY, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(Yri, dY, ny * sizeof(cplx), hipMemcpyDeviceToHost));
+}
+
 }  // namespace emagls
 
 extern "C" {
+
+int emagls_debug_wa_yri(const double* Q, int64_t ldQ, const void* Z, int S, int C, int ldS, int D, int64_t ldD, int nbins, void* Yri) {
+    return emagls::guarded_call([&] { emagls::wa_yri_debug(Q, ldQ, Z, S, C, ldS, D, ldD, nbins, Yri); });
+}
 
 int emagls_debug_factor(const emagls_debug_factor_args* args) {
     return emagls::guarded_call([&] {

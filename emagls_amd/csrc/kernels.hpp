@@ -180,9 +180,10 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
                       void* Z, hipStream_t st);
 // tiled form for S > 4096 rows and up to 32 columns (row blocks + a tree step over their triangles); ws: wa_tiling(...).bytes
 struct WaTiling { int leaves, leaf_h, ldT; size_t off_stack, off_vt, off_zt, off_tau, bytes; };
-WaTiling wa_tiling(int S, int C, int nbins);
+// leaf_bound: 0 = the library's bound of the leaf height (EMAGLS_WA_LEAF_ROWS or its default), else 1024 ... 4096 in its place
+WaTiling wa_tiling(int S, int C, int nbins, int leaf_bound = 0);
 void launch_wa_factor_tiled(void* B, void* Vw, int S, int C, int ldS, int nbins, double reg_c, double* tauw, void* R2w, void* Nw, double* sv,
-                            int* sweeps, void* Z, void* ws, hipStream_t st);
+                            int* sweeps, void* Z, void* ws, hipStream_t st, int leaf_bound = 0);
 void launch_wa_yri(const void* Q, int64_t ldQ, const void* Z, int S, int C, int ldS, int D, int64_t ldD, int nbins, void* Yri, hipStream_t st);
 void launch_wa_ls(const void* Hc, int64_t ldH, int n_c, const void* Yri, int64_t ldD, int D, int C, int P, int kb_first, int kb_end, void* W, hipStream_t st);
 void launch_wa_lo_gram(const void* Ycm, int M, int nOut, double* Ag, hipStream_t st);

@@ -1016,9 +1016,11 @@ void launch_wa_factor(void* B, void* Vw, int S, int C, int ldS, int nbins, doubl
 // less than 64 (leaves - 1) rows: at least 1085 rows for S > 4096 -- never fewer rows than columns, so every R_i is a full triangle.
 // No atomics, every sum in a fixed order: equal inputs give equal bits.
 // ---------------------------------------------------------------------------------------------
-WaTiling wa_tiling(int S, int C, int nbins) {
-    // EMAGLS_WA_LEAF_ROWS: another upper bound of the leaf height (1024 .. 4096; the measurements)
-    const int v = sw_int<Sw::WA_LEAF_ROWS>();
+WaTiling wa_tiling(int S, int C, int nbins, int leaf_bound) {
+    // EMAGLS_WA_LEAF_ROWS: another upper bound of the leaf height (1024 .. 4096; the measurements).  leaf_bound != 0 (the debug entry: the
+    // switch is read once per process) takes its place, within the same range.
+    if (leaf_bound != 0 && (leaf_bound < 1024 || leaf_bound > 128 * WA_PAIR)) throw Error(1, "tiled QR: the leaf bound is 0 (default) or 1024 ... 4096");
+    const int v = leaf_bound != 0 ? leaf_bound : sw_int<Sw::WA_LEAF_ROWS>();
     const int leaf_rows = v >= 1024 && v <= 128 * WA_PAIR ? v / 64 * 64 : WA_LEAF_ROWS;
     WaTiling t{};
     t.leaves = (int)ceil_div(S, leaf_rows);
@@ -1034,10 +1036,10 @@ WaTiling wa_tiling(int S, int C, int nbins) {
     return t;
 }
 void launch_wa_factor_tiled(void* B, void* Vw, int S, int C, int ldS, int nbins, double reg_c, double* tauw, void* R2w, void* Nw, double* sv,
-                            int* sweeps, void* Z, void* ws, hipStream_t st) {
+                            int* sweeps, void* Z, void* ws, hipStream_t st, int leaf_bound) {
     if (nbins <= 0) return;
     if (C > 32) throw Error(2, "tiled QR: at most 32 columns");
-    const WaTiling t = wa_tiling(S, C, nbins);
+    const WaTiling t = wa_tiling(S, C, nbins, leaf_bound);
     char* w = (char*)ws;
     cplx* Ri = (cplx*)w;
     cplx* St = (cplx*)(w + t.off_stack);

@@ -96,8 +96,12 @@ int emagls_debug_synth_cosines(const double* dir_azi, const double* dir_zen, int
 /* The per-bin factor chain on the caller's matrices: the launchers the designs use (assemble or load B_k, Householder QR, one-sided Jacobi,
  * back-transform to Z_k = conj(U) diag(s_reg) V^T with B_k = U S V^H), with their own choice of kernel for the shape and their own refusals
  * (EMAGLS_ERR_UNSUPPORTED).  All arrays are host arrays, complex ones interleaved; the call is synchronous.
- *   path 0: the forms for up to 32 columns and 4096 rows; path 1: the forms for up to 64 columns (dense input, reg_mode 0, phases 3, no
- *   Hq, ldS a multiple of 64; these write zeros into the rows S ... ldS-1 of Z).
+ *   path 0: the forms for up to 32 columns and 4096 rows; path 1: the forms for up to 64 columns; path 2: the tiled form of those (row
+ *   blocks and a tree step over their triangles) for up to 32 columns, ldS <= 16384 and nbins <= 8, its workspace filled with the sentinel
+ *   first.  Paths 1 and 2 take dense input, reg_mode 0, phases 3, hq_conj 0 and ldS a multiple of 64; they write zeros into the rows
+ *   S ... ldS-1 of Z, and form W by the least-squares kernel the designs run behind these factors (the bins below min(ls_end, nbins)).
+ *   leaf_rows (path 2 only; 0 elsewhere): 0 = the library's bound of a row block's height, 1024 ... 4096 = this bound in its place.
+ *   On path 2 the optional N, R2 and tau are those of the tree step (the factorisation of the stacked triangles).
  *   Input, dense: Xd [nbins][C][ldS], xd_stride = C ldS, or 0 for one matrix read by every bin; kb0 = 0.  Input, assembled (Xd null):
  *   B_k = sum_n bn[k][n] Tn[n], Tn [nOrders][C][ldS] real (tn_cplx = 0) or complex, bn [P][nOrders], for the bins k = kb0 ... kb0+nbins-1;
  *   row s takes the orders n with (n+1)^2 > s only, and bin P-1 (Nyquist) the real part of bn.
@@ -106,7 +110,8 @@ int emagls_debug_synth_cosines(const double* dir_azi, const double* dir_zen, int
  *   conjugate of those rows).  phases 3: one call of the launcher; 12: its phase 1 (QR, Jacobi) and phase 2 (back-transform) in two calls.
  *   Outputs: Z [nbins][C][ldS] (required) and W [2][P][C] are filled with the quiet NaN of bits EMAGLS_DEBUG_SENTINEL_BITS before the
  *   launch, so what the kernels leave alone shows; optional sv [nbins][C] (unsorted), sweeps [nbins], N and R2 [nbins][C][C], tau [nbins][C].
- * 1 <= S <= ldS <= 4096, 1 <= C <= 64, 1 <= nbins <= 4096, kb0 + nbins <= P <= 8192; otherwise EMAGLS_ERR_ARG before the device is touched. */
+ * 1 <= S <= ldS <= 4096, 1 <= C <= 64, 1 <= nbins <= 4096, kb0 + nbins <= P <= 8192 (path 2: ldS <= 16384, C <= 32, nbins <= 8), no more
+ * than 1 GiB of device memory, the workspace of path 2 included; otherwise EMAGLS_ERR_ARG before the device is touched. */
 #define EMAGLS_DEBUG_SENTINEL_BITS 0x7ff8dead0000beefULL
 typedef struct {
     int S, C, ldS, nbins, kb0, P;
@@ -129,8 +134,15 @@ typedef struct {
     void* R2;
     double* tau;
     void* W;
+    int leaf_rows;
 } emagls_debug_factor_args;
 int emagls_debug_factor(const emagls_debug_factor_args* args);
+/* Y_reg_inv of the designs with 33 ... 64 channels on the caller's arrays, by the launcher the designs use (launch_wa_yri; the scalar or the
+ * matrix-core form by EMAGLS_WA_YRI_MFMA, read per call): Yri[k][c][d] = sum_s Q[d][s] Z[k][c][s], Q [D][ldQ] real, Z [nbins][C][ldS] and
+ * Yri [nbins][C][ldD] complex.  Host arrays, synchronous; Yri is filled with the NaN of EMAGLS_DEBUG_SENTINEL_BITS before the launch (the
+ * columns D ... ldD-1 keep it).  1 <= C <= 64, 1 <= S <= ldS <= 16384, S <= ldQ <= 16384, 1 <= D <= ldD <= 65536, 1 <= nbins <= 4096, no more
+ * than 1 GiB of device memory; otherwise EMAGLS_ERR_ARG before the device is touched. */
+int emagls_debug_wa_yri(const double* Q, int64_t ldQ, const void* Z, int S, int C, int ldS, int D, int64_t ldD, int nbins, void* Yri);
 /* The Jacobi kernel of that chain in its Gram form, as the Gram route of the designs runs it: A [nbins][C][C] = B_k^H B_k, full Hermitian;
  * route [nbins] = 1 (factor this bin) or 2 (skip it: its M keeps the sentinel, sweeps = -1); a workgroup walks jrun (1 ... 16) neighbouring
  * bins and starts each from the rotations of the one before.  M [nbins][C][C] = V diag(s_reg / s) V^H with s = sqrt(eig(A)) and

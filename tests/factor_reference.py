@@ -1,4 +1,4 @@
-"""The per-bin factor chain (csrc/factor.hip, launch_wa_factor of csrc/wide_array.hip) against a multiprecision truth: the test matrices,
+"""The per-bin factor chain (csrc/factor.hip, launch_wa_factor and launch_wa_factor_tiled of csrc/wide_array.hip) against a multiprecision truth: the test matrices,
 the truth, the four measures and the stand-ins the host test runs through them.  CPU only.
 
 Inputs are not stored anywhere: they are rebuilt bit for bit from the integer generator below.  Every floating-point step of a
@@ -13,6 +13,10 @@ With X (S x C) the matrix of a bin, X = U S V^H:   A = X^H X = V S^2 V^H (mp.eig
 and for two rows Hq[e] of small integers  W[e] = sum_s Hq[e][s] Z[s][:]  -- a contraction over every row of Z.
 The fixture (tests/golden/factor_truth.npz, written by tests/golden/make_factor_truth.py) keeps per case s, s_reg, P, W and Z at no more
 than 16 listed rows as hi + lo doubles, and the errors FP64 LAPACK makes on the same case through the same formulas.
+
+Path 1 also has the shapes of 9 ... 32 columns at which FromAtf's dense route calls launch_wa_factor (NARROW1); path 2 is launch_wa_factor_tiled
+(TILED2: shape, classes, leaf bound), whose cutting rule tiling() restates and whose chain tiled_route() runs in NumPy, with the index errors
+a kernel could make as injectable faults.  Class K6 exists for it: a column exactly zero on the first leaf, another on the last.
 
 Measures of a result (sv, Z, W) -- the first three do not depend on the conditioning of X:
     A   max |sort(sv) - sort(s)| / s_max
@@ -30,7 +34,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIXTURE = os.path.join(HERE, "golden", "factor_truth.npz")   # path 0; the wide path and the Gram form have files of their own (size)
-FIXTURES = (FIXTURE, os.path.join(HERE, "golden", "factor_truth_wide.npz"), os.path.join(HERE, "golden", "factor_truth_gram.npz"))
+FIXTURES = (FIXTURE, os.path.join(HERE, "golden", "factor_truth_wide.npz"), os.path.join(HERE, "golden", "factor_truth_gram.npz"),
+            os.path.join(HERE, "golden", "factor_truth_tiled.npz"))
 EPS = 2.0 ** -52
 REG_C = 0.01
 MARGIN = 8.0          # a result passes within MARGIN x max(LAPACK's error on the case, C eps)
@@ -112,7 +117,7 @@ def spectrum(cls, C):
     raise ValueError(cls)
 
 
-def class_matrix(cls, S, C, seed):
+def class_matrix(cls, S, C, seed, leaf_rows=0):
     if cls in ("K1", "K2", "K4"):
         return spectrum_matrix(S, C, spectrum(cls, C), seed)
     if cls == "K3":     # rows n^2 ... (n+1)^2 - 1 scaled 10^(-2.6 n) (to the nearest power of two), the largest first: B_k at low k r
@@ -123,10 +128,32 @@ def class_matrix(cls, S, C, seed):
         x = integer_matrix(S, C, seed)
         x[:, C - 1] = x[:, 0]
         return x
+    if cls == "K6":     # block-deficient: a column exactly zero on the first leaf, another on the last; the whole matrix has full rank
+        leaves, leaf_h, _ = tiling(S, C, leaf_rows)
+        assert leaves >= 2
+        x = integer_matrix(S, C, seed)
+        x[:leaf_h, C // 2] = 0.0
+        if C > 1:
+            x[(leaves - 1) * leaf_h:, 0] = 0.0
+        return x
     raise ValueError(cls)
 
 
-MODE = {"K1": 0, "K2": 0, "K3": 0, "K4": 1, "K5": 1}
+# ------------------------------------------------------------------------------------------------ the tiled form (path 2)
+LEAF_ROWS = 3072       # the library's bound of a leaf's height
+
+
+def tiling(S, C, leaf_rows=0):
+    """(leaves, leaf_h, ldT) of launch_wa_factor_tiled, restated: leaves = ceil(S / bound), the bound rounded down to a multiple of 64;
+    leaf_h = ceil(S / leaves) rounded up to a multiple of 64, the last leaf takes the rest; ldT = leaves C rounded up to a multiple of 64"""
+    bound = (leaf_rows if leaf_rows else LEAF_ROWS) // 64 * 64
+    leaves = -(-S // bound)
+    leaf_h = 64 * -(-(-(-S // leaves)) // 64)
+    assert S - (leaves - 1) * leaf_h >= C, "a leaf with fewer rows than columns"
+    return leaves, leaf_h, 64 * -(-leaves * C // 64)
+
+
+MODE = {"K1": 0, "K2": 0, "K3": 0, "K4": 1, "K5": 1, "K6": 0}
 
 # path 0: the smallest and the largest shape of every instance dispatch() has; path 1: the forms of launch_wa_factor
 SHAPES0 = [(1, 1), (2, 2), (31, 25), (32, 32), (33, 32), (128, 31), (129, 8), (256, 25), (257, 2), (416, 32), (417, 25), (512, 7), (513, 32), (768, 25),
@@ -134,6 +161,13 @@ SHAPES0 = [(1, 1), (2, 2), (31, 25), (32, 32), (33, 32), (128, 31), (129, 8), (2
 EXTRA0 = [("K3", 33, 32), ("K3", 513, 32), ("K4", 31, 25), ("K4", 1537, 8), ("K5", 129, 8), ("K5", 4096, 8)]
 SHAPES1 = [(64, 64), (65, 33), (448, 64), (449, 40), (3072, 33), (3073, 34), (4096, 33)]
 EXTRA1 = [("K3", 449, 40)]
+# 9 ... 32 columns (FromAtf's dense route calls launch_wa_factor there): the ends of the reg-7, the tall and the pair form, partial grids
+NARROW1 = [(9, 9), (448, 32), (449, 9), (3072, 17), (3073, 9), (4096, 32)]
+# path 2 = launch_wa_factor_tiled: (S, C, classes, leaf bound; 0 = the library's)
+TILED2 = [(4097, 1, ("K1", "K2"), 0), (4097, 9, ("K1", "K2", "K6"), 0), (4097, 31, ("K1", "K2"), 0), (4160, 32, ("K1", "K2"), 0),
+          (6145, 8, ("K1", "K2", "K6"), 0), (16384, 32, ("K2",), 0),
+          (1025, 32, ("K1", "K2", "K6"), 1024), (2049, 5, ("K1", "K2"), 1024), (3073, 9, ("K1", "K2"), 1024), (16384, 32, ("K2",), 1024),
+          (6209, 9, ("K1", "K2"), 4096)]
 
 
 def instance(path, S, C):
@@ -150,22 +184,24 @@ def instance(path, S, C):
     raise ValueError((S, C))
 
 
-def _case(path, cls, S, C):
-    name = "p%d_%s_%dx%d" % (path, cls, S, C)
-    seed = 1000 * S + 10 * C + int(cls[1]) + 500000 * path
+def _case(path, cls, S, C, leaf_rows=0):
+    name = "p%d_%s_%dx%d" % (path, cls, S, C) + ("_h%d" % leaf_rows if leaf_rows else "")
+    seed = 1000 * S + 10 * C + int(cls[1]) + 500000 * path + 7 * leaf_rows
     return dict(name=name, path=path, cls=cls, S=S, C=C, mode=MODE[cls], reg_c=REG_C, tol_dim=float(max(S, C)), seed=seed,
-                ldS=64 * ((S + 63) // 64))
+                ldS=64 * ((S + 63) // 64), leaf_rows=leaf_rows)
 
 
 CASES = [_case(0, cls, S, C) for (S, C) in SHAPES0 for cls in ("K1", "K2")] + [_case(0, *e) for e in EXTRA0] + \
-        [_case(1, cls, S, C) for (S, C) in SHAPES1 for cls in ("K1", "K2")] + [_case(1, *e) for e in EXTRA1]
+        [_case(1, cls, S, C) for (S, C) in SHAPES1 for cls in ("K1", "K2")] + [_case(1, *e) for e in EXTRA1] + \
+        [_case(1, cls, S, C) for (S, C) in NARROW1 for cls in ("K1", "K2")] + \
+        [_case(2, cls, S, C, h) for (S, C, classes, h) in TILED2 for cls in classes]
 CASE = {c["name"]: c for c in CASES}
 
 
 def build_input(case):
     """X (S x C complex128) and Hq (2 x S, small complex integers)"""
     S, C = case["S"], case["C"]
-    X = class_matrix(case["cls"], S, C, case["seed"])
+    X = class_matrix(case["cls"], S, C, case["seed"], case.get("leaf_rows", 0))
     h = ints(case["seed"] + 77, 4 * S, -4, 4).astype(np.float64)
     Hq = (h[:2 * S] + 1j * h[2 * S:]).reshape(2, S)
     return np.ascontiguousarray(X), Hq
@@ -181,6 +217,8 @@ def checksum(*arrays):
 def listed_rows(case):
     """at most 16 rows: the first two, the last two, the rows on either side of the lane-group boundaries NCH i (evenly thinned to six)"""
     S = case["S"]
+    if case["path"] == 2:
+        return _listed_rows_tiled(case)
     nch, rpt = instance(case["path"], S, case["C"])
     bnd = [nch * i for i in range(1, rpt) if nch * i < S]
     if len(bnd) > 6:
@@ -189,6 +227,25 @@ def listed_rows(case):
     for b in bnd:
         rows |= {b - 1, b}
     return np.array(sorted(r for r in rows if 0 <= r < S), dtype=np.int64)
+
+
+def _listed_rows_tiled(case):
+    """path 2: the first two and the last two rows, the rows on either side of every leaf boundary (evenly thinned to four: 16 rows in all)
+    and of the 64-row group boundaries nearest the middle of the first and of the last leaf"""
+    S = case["S"]
+    leaves, leaf_h, _ = tiling(S, case["C"], case["leaf_rows"])
+    bnd = [leaf_h * i for i in range(1, leaves)]
+    if len(bnd) > 4:
+        bnd = [bnd[(len(bnd) - 1) * t // 3] for t in range(4)]
+    r0 = (leaves - 1) * leaf_h
+    bnd += [64 * ((leaf_h // 2 + 32) // 64), r0 + 64 * (((S - r0) // 2 + 32) // 64)]
+    rows = {0, 1, S - 2, S - 1}
+    for b in bnd:
+        if 0 < b < S:
+            rows |= {b - 1, b}
+    rows = np.array(sorted(r for r in rows if 0 <= r < S), dtype=np.int64)
+    assert len(rows) <= 16
+    return rows
 
 
 # ------------------------------------------------------------------------------------------------ regularisation rules (FP64 and mp share them)
@@ -364,7 +421,7 @@ def bound(lapack_err, C):
 
 
 ASSERTED = {"K1": ("A", "B", "C", "DW", "DZ"), "K2": ("A", "B", "C", "DW", "DZ"), "K3": ("A", "B", "C"), "K4": ("A", "B", "C", "DW", "DZ"),
-            "K5": ("A", "B", "C", "DW", "DZ")}   # (K3: LAPACK's own forward error is 1e-4 at cond 1e13 -- D is printed next to it, not asserted)
+            "K5": ("A", "B", "C", "DW", "DZ"), "K6": ("A", "B", "C", "DW", "DZ")}   # (K3: LAPACK's own forward error is 1e-4 at cond 1e13 -- D is printed next to it, not asserted)
 
 
 # ------------------------------------------------------------------------------------------------ stand-ins for the kernel (FP64)
@@ -383,8 +440,15 @@ def jacobi_route(X, Hq, mode, reg_c, tol_dim, order="cyclic", unrotate=None, **k
     """Householder QR, then one-sided (Hestenes) Jacobi on R^H -- the chain of factor.hip in plain NumPy.  order: 'cyclic' (row by row) or
     'reverse'.  unrotate = t (an injected error): the state one rotation before convergence -- the columns of the largest and the smallest
     singular value are turned back so that |gamma| / sqrt(alpha beta) = t between them, as if that last rotation had been left out."""
-    S, C = X.shape
     Q, R = np.linalg.qr(X)
+    J, s, Vn = _jacobi_of_r(R, mode, reg_c, order, unrotate)
+    # R^H = Xrot J^H  ->  R = J Xrot^H = J diag(s) (Xrot / s)^H:  X = (Q J) diag(s) (Xrot / s)^H
+    return from_svd(Q @ J, s, Vn.conj().T, X, Hq, mode, reg_c, tol_dim, **kw)
+
+
+def _jacobi_of_r(R, mode, reg_c, order="cyclic", unrotate=None):
+    """the Jacobi step of jacobi_route on a C x C triangle: J, s, Vn with R = J diag(s) Vn^H"""
+    C = R.shape[1]
     G = R.conj().T.copy()          # R^H = G: G J = Xrot with orthogonal columns; R = J Sigma (Xrot / Sigma)^H
     J = np.eye(C, dtype=np.complex128)
     pairs = [(p, q) for p in range(C - 1) for q in range(p + 1, C)]
@@ -421,9 +485,87 @@ def jacobi_route(X, Hq, mode, reg_c, tol_dim, order="cyclic", unrotate=None, **k
         th = unrotate * s[p] * s[q] / (s[p] ** 2 - s[q] ** 2)    # gamma = (beta - alpha) sin cos
         rotate(p, q, math.cos(th), math.sin(th), 1.0)
         s = np.sqrt(np.sum(np.abs(G) ** 2, axis=0))
-    # R^H = Xrot J^H  ->  R = J Xrot^H = J diag(s) (Xrot / s)^H:  X = (Q J) diag(s) (Xrot / s)^H
-    Vn = G / np.where(s > 0, s, 1.0)[None, :]
-    return from_svd(Q @ J, s, Vn.conj().T, X, Hq, mode, reg_c, tol_dim, **kw)
+    return J, s, G / np.where(s > 0, s, 1.0)[None, :]
+
+
+# ------------------------------------------------------------------------------------------------ the tiled chain (path 2) in NumPy
+def householder_qr(X):
+    """V (the reflectors, column j zero above row j), tau, R (C x C) with (I - tau_0 v_0 v_0^H) ... X = [R; 0], as the wide forms do it:
+    alpha = -x_0 / |x_0| |x|, v = x - alpha e_0, tau = 2 / |v|^2 -- and tau = 0, the step left out, on a column that is zero from j down"""
+    A = X.astype(np.complex128).copy()
+    S, C = A.shape
+    V = np.zeros_like(A)
+    tau = np.zeros(C)
+    for j in range(min(S, C)):
+        x = A[j:, j].copy()
+        nx, ax = math.sqrt(float(np.sum(x.real ** 2 + x.imag ** 2))), abs(x[0])
+        alpha = -x[0] / ax * nx if ax > 0 else -nx
+        nv2 = 2.0 * nx * (nx + ax)
+        tau[j] = 2.0 / nv2 if nv2 > 0 else 0.0
+        x[0] -= alpha
+        V[j:, j] = x
+        A[j:, j] = 0.0
+        A[j, j] = alpha
+        if j + 1 < C:
+            A[j:, j + 1:] -= tau[j] * np.outer(x, x.conj() @ A[j:, j + 1:])
+    R = np.zeros((C, C), dtype=np.complex128)
+    R[:min(S, C)] = np.triu(A[:C])[:min(S, C)]
+    return V, tau, R
+
+
+def apply_q(V, tau, T):
+    """Q [T; 0] for the reflectors of householder_qr (S x C) and a C x C block T: the back-transform"""
+    S, C = V.shape
+    Y = np.zeros((S, T.shape[1]), dtype=np.complex128)
+    Y[:min(S, C)] = T[:min(S, C)]
+    for j in range(C - 1, -1, -1):
+        Y -= tau[j] * np.outer(V[:, j], V[:, j].conj() @ Y)
+    return Y
+
+
+FAULTS = ("swap_T", "short_last", "stale_tau", "drop_row")
+
+
+def tiled_route(X, Hq, mode, reg_c, tol_dim, leaf_rows=0, fault=None, ldS=None):
+    """launch_wa_factor_tiled in plain NumPy: Householder QR of every leaf, the triangles one below the other, QR of that stack,
+    jacobi_route's Jacobi and clipping on the stack's R, and the two-level back-transform (the stack's, which leaves a C x C block T_i per
+    leaf, then every leaf's own with its T_i).  fault (an injected error, what a wrong index in the kernels would do):
+      'swap_T'      leaves 0 and 1 use each other's T_i
+      'short_last'  the last leaf is treated as leaf_h rows.  The rows beyond S are zeros -- up to ldS; the ones beyond ldS are, in the
+                    [C][ldS] storage of the kernels, the first rows of the NEXT column (zeros behind the last one), and they are what the
+                    error shows by: leaf_h rows of which all beyond S are zeros give the same R and the same rows of Z, bit for bit
+      'stale_tau'   the last leaf's back-transform reads leaf 0's tau
+      'drop_row'    the last row of the last leaf is left out of its QR (its row of Z stays zero)"""
+    assert fault is None or fault in FAULTS
+    S, C = X.shape
+    leaves, leaf_h, _ = tiling(S, C, leaf_rows)
+    ldS = 64 * ((S + 63) // 64) if ldS is None else ldS
+    blocks = []
+    for i in range(leaves):
+        r0 = i * leaf_h
+        Xi = X[r0:min(r0 + leaf_h, S)]
+        if i == leaves - 1 and fault == "drop_row":
+            Xi = Xi[:-1]
+        if i == leaves - 1 and fault == "short_last":
+            flat = np.zeros((C + 1) * ldS, dtype=np.complex128)       # the storage [C][ldS], one more column of zeros behind it
+            flat[:C * ldS].reshape(C, ldS)[:, :S] = X.T
+            Xi = np.stack([flat[c * ldS + r0:c * ldS + r0 + leaf_h] for c in range(C)], axis=1)
+        blocks.append((r0, Xi.shape[0]) + householder_qr(Xi))
+    Vs, taus, Rs = householder_qr(np.concatenate([b[4] for b in blocks], axis=0))
+    J, s, Vn = _jacobi_of_r(Rs, mode, reg_c)
+    sr = s_reg_fp64(s, mode, reg_c, tol_dim)
+    T = apply_q(Vs, taus, (J * sr[None, :]) @ Vn.conj().T)     # [T_0; T_1; ...] = Q_stack J diag(s_reg) Vn^H
+    Ti = [T[i * C:(i + 1) * C] for i in range(leaves)]
+    if fault == "swap_T":
+        Ti[0], Ti[1] = Ti[1], Ti[0]
+    Zc = np.zeros((S, C), dtype=np.complex128)
+    for i, (r0, h, V, tau, _) in enumerate(blocks):
+        if i == leaves - 1 and fault == "stale_tau":
+            tau = blocks[0][3]
+        n = min(h, S - r0)
+        Zc[r0:r0 + n] = apply_q(V, tau, Ti[i])[:n]
+    Z = np.conj(Zc)
+    return s, Z, Hq @ Z
 
 
 # ------------------------------------------------------------------------------------------------ the Gram form

@@ -3,8 +3,9 @@
     tests/golden/factor_truth.npz        the cases of csrc/factor.hip (path 0)
     tests/golden/factor_truth_wide.npz   the cases of launch_wa_factor (path 1)
     tests/golden/factor_truth_gram.npz   the Gram-form chains
+    tests/golden/factor_truth_tiled.npz  the cases of launch_wa_factor_tiled (path 2)
 
-(three files: with hi + lo doubles of P, Z and M one file would pass the size limit of a committed file).  Run from the repository root:
+(four files: with hi + lo doubles of P, Z and M one file would pass the size limit of a committed file).  Run from the repository root:
 
     python tests/golden/make_factor_truth.py [-j N] [case name ...]
 
@@ -12,6 +13,8 @@ Per case '<name>/<key>': s, s_reg [2][C], W [2][2][C], Z [2][rows][C] and rows, 
 row after row) -- each a hi + lo stack of float64 --, sum (checksum of the input the truth belongs to), zmax (the largest |Z|, a scale),
 lapack [5] = the errors A, B, C, DW, DZ of numpy.linalg.svd through the same formulas: the tests allow 8 x max(that, C eps).
 The generator asserts the stated condition of each matrix class.  Takes about a minute on eight cores (mpmath at 100 digits; the Gram matrices X^H X are formed in exact integer arithmetic first).
+The 36 cases of 9 ... 32 columns and of the tiled form (up to 16384 x 32: the exact Gram matrix is an object-array product) were written by a partial
+run, `-j 8` with their names: 17 s on eight cores (110 s of CPU time).
 For the Gram chains: s [2][11][C], Mu (upper triangle of M per bin), cond_limit (between the two largest conditionings of the chain),
 lapack [11][2] = the errors A, M of numpy.linalg.eigh per bin.
 """
@@ -47,6 +50,8 @@ def check_class(case, s):
         tol = R.pinv_tol(smax, case["tol_dim"])
         assert np.all((s > 100.0 * tol) | (s == 0.0)), case["name"]
         assert (cls == "K5") == bool(np.any(s == 0.0)), case["name"]
+    if cls == "K6":     # every leaf but the whole matrix is deficient: nothing is clipped
+        assert s.min() > R.REG_C * smax, case["name"]
     if cls == "K4":
         assert 4e3 < smax / s.min() < 2e4, case["name"]
 
@@ -93,7 +98,7 @@ def main():
     # the long ones first
     cost = lambda n: -(R.CASE[n]["S"] * R.CASE[n]["C"] ** 2 + 40 * R.CASE[n]["C"] ** 3) if n in R.CASE else -11 * 40 * R.GRAM_CASE[n]["C"] ** 3   # noqa: E731
     names = sorted(names, key=cost)
-    files = {"p0": {}, "p1": {}, "g": {}}
+    files = {"p0": {}, "p1": {}, "p2": {}, "g": {}}
     with ProcessPoolExecutor(a.j) as ex:
         futs = [ex.submit(one_case if n in R.CASE else one_gram, n) for n in names]
         for f in futs:
@@ -102,7 +107,7 @@ def main():
             for k, v in tr.items():
                 files[name.split("_")[0]]["%s/%s" % (name, k)] = v
     here = os.path.dirname(os.path.abspath(__file__))
-    for key, fn in (("p0", "factor_truth.npz"), ("p1", "factor_truth_wide.npz"), ("g", "factor_truth_gram.npz")):
+    for key, fn in (("p0", "factor_truth.npz"), ("p1", "factor_truth_wide.npz"), ("p2", "factor_truth_tiled.npz"), ("g", "factor_truth_gram.npz")):
         if not files[key]:
             continue
         path = os.path.join(here, fn)

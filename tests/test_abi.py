@@ -34,8 +34,11 @@ def test_struct_layouts_match_header(tmp_path):
     src = tmp_path / "layout.c"
     fields_d = [f[0] for f in _lib.DesignDesc._fields_]
     fields_i = [f[0] for f in _lib.PlanInfo._fields_]
+    fields_f = [f[0] for f in _lib.DebugFactorArgs._fields_]
     body = "".join('printf("%%zu\\n", offsetof(emagls_design_desc, %s));' % f for f in fields_d)
     body += "".join('printf("%%zu\\n", offsetof(emagls_plan_info, %s));' % f for f in fields_i)
+    body += "".join('printf("%%zu\\n", offsetof(emagls_debug_factor_args, %s));' % f for f in fields_f)
+    body += 'printf("%zu\\n", sizeof(emagls_debug_factor_args));'
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "emagls.h"\nint main(void){printf("%zu %zu\\n", '
                    'sizeof(emagls_design_desc), sizeof(emagls_plan_info));' + body + 'return 0;}\n')
     exe = tmp_path / "layout"
@@ -44,6 +47,8 @@ def test_struct_layouts_match_header(tmp_path):
     assert [int(out[0]), int(out[1])] == [C.sizeof(_lib.DesignDesc), C.sizeof(_lib.PlanInfo)]
     offs = [int(x) for x in out[2:]]
     want = [getattr(_lib.DesignDesc, f).offset for f in fields_d] + [getattr(_lib.PlanInfo, f).offset for f in fields_i]
+    want += [getattr(_lib.DebugFactorArgs, f).offset for f in fields_f] + [C.sizeof(_lib.DebugFactorArgs)]
+    assert "leaf_rows" in fields_f
     assert offs == want
 
 
@@ -132,9 +137,25 @@ def test_debug_factor_rejects_bad_arguments(lib):
                dict(P=8193), dict(reg_mode=2), dict(reg_c=-0.1), dict(reg_c=1.5), dict(reg_c=float("nan")), dict(tol_dim=-1.0), dict(xd_stride=5),
                dict(Xd=None, Tn=p(Tn), bn=None, nOrders=2), dict(Xd=None, Tn=p(Tn), bn=p(bn), nOrders=0), dict(Xd=None, Tn=p(Tn), bn=p(bn), nOrders=1025),
                dict(Hq=p(Hq), W=None, ldHq=ldS, ls_end=1), dict(Hq=p(Hq), W=p(W), ldHq=S - 1, ls_end=1), dict(Hq=p(Hq), W=p(W), ldHq=ldS, ls_end=2),
-               dict(path=1), dict(path=1, ldS=64, reg_mode=1), dict(path=1, ldS=64, phases=12), dict(path=1, ldS=64, Hq=p(Hq), W=p(W), ldHq=64, ls_end=1),
-               dict(path=1, ldS=64, Xd=None, Tn=p(Tn), bn=p(bn), nOrders=2)):
+               dict(path=1), dict(path=1, ldS=64, reg_mode=1), dict(path=1, ldS=64, phases=12),
+               dict(path=1, ldS=64, Hq=p(Hq), W=p(W), ldHq=64, ls_end=1, hq_conj=1), dict(path=1, ldS=64, Hq=p(Hq), W=None, ldHq=64, ls_end=1),
+               dict(path=1, ldS=64, Xd=None, Tn=p(Tn), bn=p(bn), nOrders=2),
+               dict(path=3)):
         assert call(**kw) == L.ERR_ARG, kw
+    # the tiled path (xd_stride = 0 is right for every ldS, so each case is refused for the reason it names): its own limits, the
+    # restrictions of the wide paths, the leaf bound, the memory cap with Hq counted
+    for frag, kw in ((b"tiled path", dict(path=2, ldS=64, C=33, S=40)), (b"tiled path", dict(path=2, ldS=16448)), (b"tiled path", dict(path=2, ldS=64, nbins=9, P=9)),
+                     (b"wide paths", dict(path=2, ldS=8)), (b"wide paths", dict(path=2, ldS=64, reg_mode=1)), (b"wide paths", dict(path=2, ldS=64, phases=12)),
+                     (b"wide paths", dict(path=2, ldS=64, Hq=p(Hq), W=p(W), ldHq=64, ls_end=1, hq_conj=1)),
+                     (b"wide paths", dict(path=1, ldS=64, Hq=p(Hq), W=p(W), ldHq=64, ls_end=1, hq_conj=1)),
+                     (b"wide paths", dict(path=2, ldS=64, Xd=None, Tn=p(Tn), bn=p(bn), nOrders=2)),
+                     (b"leaf_rows", dict(path=2, ldS=64, leaf_rows=1023)), (b"leaf_rows", dict(path=2, ldS=64, leaf_rows=4097)),
+                     (b"leaf_rows", dict(path=2, ldS=64, leaf_rows=-1)), (b"leaf_rows", dict(path=0, leaf_rows=1024)),
+                     (b"leaf_rows", dict(path=1, ldS=64, leaf_rows=1024)),
+                     (b"1 GiB", dict(path=2, ldS=16384, S=16384, C=32, nbins=8, P=8192, Hq=p(Hq), W=p(W), ldHq=16384, ls_end=1))):
+        assert call(xd_stride=0, **kw) == L.ERR_ARG and frag in lib.emagls_last_error(), (kw, lib.emagls_last_error())
+    # a leaf with fewer rows than columns is the launcher's refusal, made before the device is touched
+    assert call(xd_stride=0, path=2, ldS=15424, S=15361, C=3, leaf_rows=1024) == L.ERR_UNSUPPORTED and b"fewer rows than columns" in lib.emagls_last_error()
     assert call(phases=1) == L.ERR_ARG and b"phases" in lib.emagls_last_error()
     assert lib.emagls_debug_factor(None) == L.ERR_ARG
 
@@ -148,6 +169,22 @@ def test_debug_factor_rejects_bad_arguments(lib):
                dict(cond_limit=float("nan")), dict(r=bad_route), dict(a=None), dict(r=None), dict(m=None), dict(s=None), dict(w=None), dict(t=None)):
         assert gram(**kw) == L.ERR_ARG, kw
     assert gram(r=bad_route) == L.ERR_ARG and b"route" in lib.emagls_last_error()
+
+
+def test_debug_wa_yri_rejects_bad_arguments(lib):
+    """emagls_debug_wa_yri validates before it touches the device: 1 <= C <= 64, 1 <= S <= ldS, S <= ldQ, 1 <= D <= ldD, the bins, the memory
+    cap, the pointers set"""
+    from emagls_amd import _lib as L
+    p = lambda a: a.ctypes.data if a is not None else None   # noqa: E731
+    Q, Z, Y = np.zeros((3, 64)), np.zeros((1, 5, 64), dtype=np.complex128), np.zeros((1, 5, 64), dtype=np.complex128)
+
+    def call(q=Q, ldQ=64, z=Z, S=33, Cn=5, ldS=64, D=3, ldD=64, nbins=1, y=Y):
+        return lib.emagls_debug_wa_yri(p(q), ldQ, p(z), S, Cn, ldS, D, ldD, nbins, p(y))
+    for kw in (dict(q=None), dict(z=None), dict(y=None), dict(Cn=0), dict(Cn=65), dict(S=0), dict(S=65), dict(ldS=16448, S=16448, ldQ=16448), dict(ldQ=32),
+               dict(D=0), dict(D=65), dict(ldD=65537, D=65537), dict(nbins=0), dict(nbins=4097),
+               dict(Cn=64, S=16384, ldS=16384, ldQ=16384, D=65536, ldD=65536, nbins=1)):   # (8 GiB of Q)
+        assert call(**kw) == L.ERR_ARG, kw
+    assert call(Cn=65) == L.ERR_ARG and b"wa_yri" in lib.emagls_last_error()
 
 
 def test_debug_fft_entries_reject_bad_arguments(lib):

@@ -116,3 +116,78 @@ def test_injected_pinv_tolerance_fails(S, Cn):
     tr["lapack"] = np.array([m[key] for key in KEYS])
     assert max(m[key] for key in ("A", "B", "C")) < 100 * Cn * R.EPS     # the right rule: at rounding level
     assert misses(case, tr, X, *R.lapack_route(X, Hq, 1, R.REG_C, float(max(S, Cn)), tol_size=float(min(S, Cn)))) != []
+
+
+# ------------------------------------------------------------------------------------------------ the narrow and the tiled cases
+WIDE_BEFORE = [c["name"] for c in R.CASES if c["path"] == 1 and ((c["S"], c["C"]) in R.SHAPES1 or (c["cls"], c["S"], c["C"]) in R.EXTRA1)]
+WIDE_BEFORE_SHA256 = "eb347667a61bca7cffac2193e28d51b927e6f980a96cf767070845325cbb2951"
+
+
+def test_wide_fixture_kept_its_entries():
+    """factor_truth_wide.npz gained the cases of 9 ... 32 columns by a partial run of the generator: the entries of the fifteen cases it held
+    before are the bytes they were (key, dtype, shape and data of each, in the order of the keys, under one SHA-256 taken from the file as
+    it was)"""
+    import hashlib
+    z = np.load(R.FIXTURES[1])
+    assert len(WIDE_BEFORE) == 15
+    h = hashlib.sha256()
+    keys = sorted(k for k in z.files if k.split("/")[0] in WIDE_BEFORE)
+    assert len(keys) == 9 * 15
+    for k in keys:
+        h.update(k.encode()); h.update(str(z[k].dtype).encode()); h.update(str(z[k].shape).encode()); h.update(np.ascontiguousarray(z[k]).tobytes())
+    assert h.hexdigest() == WIDE_BEFORE_SHA256
+
+
+def test_tiling_rule():
+    """the cutting rule at the heights the issue of the tiled cases names"""
+    assert R.tiling(4097, 9) == (2, 2112, 64) and 4097 - 2112 == 1985
+    assert R.tiling(6145, 8) == (3, 2112, 64) and 6145 - 2 * 2112 == 1921
+    assert R.tiling(6144, 8)[0] == 2 and R.tiling(16384, 32) == (6, 2752, 192)
+    assert R.tiling(1025, 32, 1024) == (2, 576, 64) and 1025 - 576 == 449
+    assert R.tiling(2049, 5, 1024)[0] == 3 and R.tiling(3073, 9, 1024)[0] == 4 and R.tiling(16384, 32, 1024) == (16, 1024, 512)
+    assert R.tiling(6209, 9, 4096) == (2, 3136, 64)
+    for c in R.CASES:
+        if c["path"] == 2:
+            rows, (leaves, leaf_h, _) = R.listed_rows(c), R.tiling(c["S"], c["C"], c["leaf_rows"])
+            assert len(rows) <= 16 and {0, 1, c["S"] - 2, c["S"] - 1, leaf_h - 1, leaf_h, (leaves - 1) * leaf_h - 1, (leaves - 1) * leaf_h} <= set(rows.tolist())
+
+
+def test_block_deficient_class():
+    """K6: a leaf's own block has a zero column (a singular R_i, a tau = 0 step) while the matrix has full rank and nothing is clipped"""
+    for c in R.CASES:
+        if c["cls"] != "K6":
+            continue
+        X, _ = R.case_inputs(c)
+        leaves, leaf_h, _ = R.tiling(c["S"], c["C"], c["leaf_rows"])
+        first, last = X[:leaf_h], X[(leaves - 1) * leaf_h:]
+        assert np.all(first[:, c["C"] // 2] == 0) and np.all(last[:, 0] == 0)
+        _, tau, Ri = R.householder_qr(first)
+        assert tau[c["C"] // 2] == 0.0 and Ri[c["C"] // 2, c["C"] // 2] == 0.0
+        s = R.load_truth()[c["name"]]["s"][0]
+        assert s.min() > R.REG_C * s.max()
+
+
+TILED_HOST = ["p2_K1_1025x32_h1024", "p2_K2_1025x32_h1024", "p2_K6_1025x32_h1024", "p2_K1_2049x5_h1024", "p2_K2_3073x9_h1024", "p2_K1_4097x9",
+              "p2_K2_4097x9", "p2_K6_4097x9", "p2_K2_6145x8", "p2_K6_6145x8", "p2_K2_6209x9_h4096"]
+
+
+@pytest.mark.parametrize("name", TILED_HOST)
+def test_tiled_stand_in_and_its_faults(name):
+    """launch_wa_factor_tiled in plain NumPy (leaf QRs, stacked triangles, QR of the stack, Jacobi, two-level back-transform) meets all five
+    measures within the bound; with each of the four injected index errors at least one asserted measure is 100 x beyond its bound.
+    'short_last' is an error only where leaves x leaf_h passes ldS, so that the over-long last leaf reaches into the next column's storage
+    (2049 x 5 and 6209 x 9 end exactly at ldS: there the extra rows are zeros, the result is the right one, and the test says so)"""
+    case = R.CASE[name]
+    tr = R.load_truth()[name]
+    X, Hq = R.case_inputs(case)
+    args = (X, Hq, case["mode"], case["reg_c"], case["tol_dim"], case["leaf_rows"])
+    assert misses(case, tr, X, *R.tiled_route(*args)) == []
+    leaves, leaf_h, _ = R.tiling(case["S"], case["C"], case["leaf_rows"])
+    for fault in R.FAULTS:
+        sv, Z, W = R.tiled_route(*args, fault=fault)
+        if fault == "short_last" and leaves * leaf_h <= case["ldS"]:
+            assert misses(case, tr, X, sv, Z, W) == []
+            continue
+        m = R.measures(tr, X, sv, Z, W)
+        worst = max(m[k] / R.bound(float(tr["lapack"][i]), case["C"]) for i, k in enumerate(KEYS) if k in R.ASSERTED[case["cls"]])
+        assert worst >= 100.0, (fault, m)

@@ -1,5 +1,7 @@
 """The per-bin factor chain -- launch_factor (csrc/factor.hip: assemble or load, Householder QR, one-sided Jacobi in LDS, back-transform),
-launch_wa_factor (csrc/wide_array.hip, 33..64 columns) and launch_factor_jacobi_gram (the Jacobi kernel on A = B^H B with warm starts) --
+launch_wa_factor (csrc/wide_array.hip: 33..64 columns, and 9..32 as FromAtf's dense route calls it), launch_wa_factor_tiled (the same in
+row blocks with a tree step, path 2; the leaf bound as a parameter), launch_wa_ls behind both (the least-squares rows W) and
+launch_factor_jacobi_gram (the Jacobi kernel on A = B^H B with warm starts) --
 run by the debug entries emagls_debug_factor / emagls_debug_factor_gram on the matrices of tests/factor_reference.py and held against the
 multiprecision truth of tests/golden/factor_truth*.npz.
 
@@ -9,7 +11,8 @@ orthonormality of U), C (X^H conj(Z) against P) do not depend on the conditionin
 
 Tolerances are measured, not chosen: a kernel result passes within 8 x max(e, C eps), e the error FP64 LAPACK makes on the same case through
 the same formulas (stored next to the truth).  D is asserted on K1, K2, K4, K5 and printed for K3, where LAPACK's own forward error is 1e-4.
-With EMAGLS_FACTOR_CHAIN_REPORT=<file> the module writes every measured value there (profiles/r22_factor_chain.md is such a file).
+With EMAGLS_FACTOR_CHAIN_REPORT=<file> the module writes every measured value there (profiles/r22_factor_chain.md is such a file; profiles/r30_dense_route.md holds the rows of
+the narrow and the tiled cases).
 """
 import ctypes as C
 import os
@@ -64,7 +67,7 @@ def pack(Xs, ldS):
 
 
 def run_factor(S, Cn, ldS, nbins=1, Xd=None, xd_stride=None, Tn=None, bn=None, kb0=0, P=None, mode=0, reg_c=R.REG_C, tol_dim=0.0, Hq=None,
-               ls_end=None, hq_conj=0, phases=3, path=0, expect=0):
+               ls_end=None, hq_conj=0, phases=3, path=0, leaf_rows=0, expect=0):
     """one call of emagls_debug_factor; returns Z [bin][S][C], the padding [bin][C][ldS - S], sv, sweeps, N, R2, tau, W [2][P][C]"""
     from emagls_amd import _lib as L
     P = nbins if P is None else P
@@ -76,7 +79,7 @@ def run_factor(S, Cn, ldS, nbins=1, Xd=None, xd_stride=None, Tn=None, bn=None, k
     tau = np.zeros((nbins, Cn))
     W = np.zeros((2, P, Cn), dtype=np.complex128)
     a = L.DebugFactorArgs(S=S, C=Cn, ldS=ldS, nbins=nbins, kb0=kb0, P=P, reg_mode=mode, reg_c=reg_c, tol_dim=tol_dim, phases=phases, path=path,
-                          hq_conj=hq_conj, Z=ptr(Z), sv=ptr(sv), sweeps=ptr(sweeps), N=ptr(N), R2=ptr(R2), tau=ptr(tau), W=ptr(W))
+                          hq_conj=hq_conj, leaf_rows=leaf_rows, Z=ptr(Z), sv=ptr(sv), sweeps=ptr(sweeps), N=ptr(N), R2=ptr(R2), tau=ptr(tau), W=ptr(W))
     keep = []
     if Xd is not None:
         Xd = np.ascontiguousarray(Xd, dtype=np.complex128)
@@ -116,10 +119,12 @@ def run_case(case, variant="", **kw):
     tr = R.load_truth()[case["name"]]
     X, Hq = R.case_inputs(case)
     S, Cn, ldS = case["S"], case["C"], case["ldS"]
+    wide = case["path"] != 0
+    # (the wide paths: W by launch_wa_ls behind the factor, as the designs form it; one more row of W than bins, which nothing may write)
     out = run_factor(S, Cn, ldS, Xd=pack([X], ldS), mode=case["mode"], reg_c=case["reg_c"], tol_dim=case["tol_dim"], path=case["path"],
-                     Hq=None if case["path"] == 1 else Hq[:, None, :], **kw)
-    if case["path"] == 1:
-        out["W"] = (Hq @ out["Z"][0])[:, None, :]   # (the wide path forms its least-squares rows elsewhere: the contraction over all rows of Z, on the host)
+                     leaf_rows=case.get("leaf_rows", 0), Hq=Hq[:, None, :], P=2 if wide else None, ls_end=1 if wide else None, **kw)
+    if wide:
+        assert np.all(is_sentinel(out["W"][:, 1])) and not np.any(is_sentinel(out["W"][:, 0])), "W beyond the bins was written, or a row of a bin was not"
     failures = []
     judge(case, tr, X, out["sv"][0], out["Z"][0], out["W"][:, 0, :], variant or "single", failures)
     assert not failures, failures
@@ -140,6 +145,47 @@ def test_factor_case(name):
 @pytest.mark.parametrize("name", [c["name"] for c in R.CASES if c["path"] == 1])
 def test_wide_case(name):
     run_case(R.CASE[name])
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in R.CASES if c["path"] == 2])
+def test_tiled_case(name):
+    """launch_wa_factor_tiled: the leaves' QR (LEAF = true instances of the tall and, at a leaf bound of 4096, of the pair form), the stacked
+    triangles, the tree step through launch_wa_factor at 1 ... 32 columns, the leaves' back-transform with their T_i, launch_wa_ls"""
+    run_case(R.CASE[name])
+
+
+@pytest.mark.parametrize("name,switch", [("p1_K2_449x9", "EMAGLS_WA_TALL"), ("p1_K2_448x32", "EMAGLS_WA_REG")])
+def test_narrow_case_plain_forms(name, switch, monkeypatch):
+    """449 x 9 without the tall forms (the kernels that walk the columns through L2) and 448 x 32 without the register form (the tall one
+    in its place): the same truth, the same bound"""
+    monkeypatch.setenv(switch, "0")
+    run_case(R.CASE[name], variant=switch[7:].lower() + "=0")
+
+
+@pytest.mark.parametrize("shape,leaf_rows", [("4097x9", 0), ("1025x32_h1024", 1024)])
+def test_tiled_slots(shape, leaf_rows):
+    """the K1, K2 and K6 matrices of one shape as the three bins of one launch (tau, R_i and T_i at the slot bin x leaves + leaf): every
+    bin's Z, singular values and W are those of its single-bin launch, bit for bit"""
+    cases = [R.CASE["p2_%s_%s" % (k, shape)] for k in ("K1", "K2", "K6")]
+    Xs, Hs = zip(*[R.case_inputs(c) for c in cases])
+    S, Cn, ldS = cases[0]["S"], cases[0]["C"], cases[0]["ldS"]
+    out = run_factor(S, Cn, ldS, nbins=3, Xd=pack(Xs, ldS), Hq=np.stack(Hs, axis=1), path=2, leaf_rows=leaf_rows)
+    assert np.all(out["pad"] == 0) and np.all((out["sweeps"] >= 1) & (out["sweeps"] <= 20))
+    for i in range(3):
+        one = run_factor(S, Cn, ldS, Xd=pack(Xs[i:i + 1], ldS), Hq=Hs[i][:, None, :], path=2, leaf_rows=leaf_rows)
+        assert np.all(np.isfinite(one["Z"])) and np.all(np.isfinite(one["W"]))
+        assert np.array_equal(out["Z"][i], one["Z"][0]) and np.array_equal(out["sv"][i], one["sv"][0]), i
+        assert np.array_equal(out["W"][:, i], one["W"][:, 0]), i
+
+
+def test_tiled_equal_bits():
+    """no atomics, every sum in a fixed order: a second run gives the same bits"""
+    case = R.CASE["p2_K2_6145x8"]
+    X, Hq = R.case_inputs(case)
+    a, b = [run_factor(case["S"], case["C"], case["ldS"], Xd=pack([X], case["ldS"]), Hq=Hq[:, None, :], path=2) for _ in range(2)]
+    assert np.all(np.isfinite(a["Z"]))
+    for key in ("Z", "sv", "W", "N", "R2", "tau", "sweeps"):
+        assert np.array_equal(a[key], b[key]), key
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in R.CASES if c["path"] == 1 and (c["S"], c["C"]) in ((448, 64), (449, 40))])
@@ -254,6 +300,10 @@ def test_refusals():
     assert "more than 32 output channels" in msg
     msg = run_factor(30, 33, 64, Xd=one(30, 33), path=1, expect=L.ERR_UNSUPPORTED)
     assert "rank-deficient array model" in msg
+    msg = run_factor(40, 33, 64, Xd=one(40, 33), path=2, expect=L.ERR_ARG)
+    assert "the tiled path takes" in msg
+    msg = run_factor(64, 4, 16448, Xd=np.ones((1, 4, 64), dtype=np.complex128), path=2, expect=L.ERR_ARG)   # (refused before anything is read)
+    assert "the tiled path takes" in msg
     msg = run_factor(16, 4, 64, Tn=np.zeros((97, 4, 64)), bn=np.zeros((1, 97), dtype=np.complex128), expect=L.ERR_UNSUPPORTED)
     assert "simulation order above 95" in msg
 
